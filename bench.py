@@ -8,7 +8,11 @@ One "step" = one such pass over one synthetic batch (benchmark.py:52-64 input pr
     python bench.py --gpus 1 --steps 300 --warmup 50        (the defaults: the reference's benchmark.py protocol)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the steps and prints the line (`value`, `ms_per_step`, ...).
+--full adds the legs beyond the headline: the parity pass at the initial weights and the CPU baseline against the oracle (`parity`,
+`cpu_baseline`), the roofline leg with the batch scan (`roofline`), and the exposed all-reduce steps (`config.allreduce_exposed_ms`,
+`config.allreduce_update_ms_per_bucket`); --no-cpu-baseline / --no-roofline / --no-batch-scan drop single legs of a --full run.
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (see dump_outputs).
 """
 from __future__ import annotations
 
@@ -66,7 +70,8 @@ class Trainer:
     """bench harness around sast_amd.training.TrainStep (the reference's step is Lightning's, modules/detection.py:113-221)."""
 
     def __init__(self, dev, amp, world, use_graph, seq_len=1, fwd_only=False, infer=False, yolox_loss=False, segmented=None,
-                 label_every=0, sync_bn=False, event_dtype="int32", defer_dw=False, dw_rows=(0, 0), dw_discard=False, cuts=(3,)):
+                 label_every=0, sync_bn=False, event_dtype="int32", defer_dw=False, dw_rows=(0, 0), dw_discard=False, cuts=(3,),
+                 parity_pass=True):
         from sast_amd.detection import RNNDetector, YOLOPAFPN
         from sast_amd.training import TrainStep
         torch.manual_seed(0)  # random init on the host, identical on every rank (weights never depend on device RNG)
@@ -124,6 +129,24 @@ class Trainer:
         self.step0 = None
         self.graph = None
         self.use_graph = use_graph
+        self.parity_pass = parity_pass      # capture() records step0 (one extra fwd+bwd) for the --full parity leg
+        self.pred = None
+        self._state0 = None
+
+    def snapshot_state(self):
+        """device copies of what a training step reads and rewrites -- weights, AdamW moments and step count, BatchNorm statistics --
+        taken before the first step; restore_state() puts them back (in place: the captured graphs keep their pointers)"""
+        if self.fwd_only:
+            return          # the forward-only passes change no state
+        mods = [m for m in (self.net, self.fpn, self.head) if m is not None]
+        live = [self.flat.flat, self.opt.m, self.opt.v, self.opt.lr_step] + [b for m in mods for b in m.buffers()]
+        self._state0 = [(t, t.detach().clone()) for t in live]
+
+    def restore_state(self):
+        if self._state0 is not None:
+            with torch.no_grad():
+                for t, t0 in self._state0:
+                    t.copy_(t0)
 
     def fwd_only_pass(self):
         with torch.no_grad():
@@ -131,6 +154,7 @@ class Trainer:
             if self.infer:
                 pred = self.head.forward_nhwc(self.fpn.forward_nhwc(feats))
                 self.loss = pred[..., 4].sum()
+                self.pred = pred
             else:
                 self.loss = feats[4].sum()
         self.P, self.feats = P, feats
@@ -156,7 +180,7 @@ class Trainer:
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
             for it in range(2):
-                if it == 0 and not self.fwd_only:
+                if it == 0 and not self.fwd_only and self.parity_pass:
                     # loss, kept-token counts and every gradient AT THE INITIAL WEIGHTS: the cpu_baseline leg runs the oracle on
                     # the same weights and input and reports the disagreement in the JSON line (`parity`)
                     self.fwd_bwd()
@@ -348,6 +372,48 @@ def _fused_forward_in_use(amp):
     return bool(SF._FUSED_ENABLE and amp <= FUSED_FORWARD_MAX_AMP and rows >= SF._FUSED_MIN_ROWS and SL.lib().sast_mswsa_fused_ws_floats(64, 160, T, 32, 0) > 0)
 
 
+DUMP_SAMPLE = 1 << 20      # elements kept of a larger output: a fixed, seeded sample (4 MB per float32 file; the whole dump stays < 64 MB)
+
+
+def dump_outputs(tr, out_dir):
+    """what the timed path handed its caller in its LAST timed step, one DIR/<name>.npy each (float64 for the loss terms, the
+    kept-token counts and the gradient norms, float32 otherwise).  Training step (started from the initial weights and AdamW state,
+    see main): `loss` (+ `loss_<term>` of the YOLOX objective), `kept_tokens` per stage, the gradient as the flat fp32 buffer of
+    sast_amd.dist.FlatParams (`grad`) and the norm of every parameter tensor's gradient in FlatParams order (`grad_norm_per_tensor`).
+    The weights after the step's AdamW update are not written: a first AdamW step moves every weight by about lr * sign(gradient), so
+    where the gradient is rounding noise around zero the update differs from run to run by 2 * lr.  --fwd-only: the backbone
+    features `features_<stage>` (NHWC).  --infer: the decoded `predictions`.  Arrays of more than DUMP_SAMPLE elements are flattened
+    and sampled at numpy.random.default_rng(0).choice(n, DUMP_SAMPLE, replace=False) sorted: the same positions for the same shapes.
+    Inputs and initial weights are seeded, so runs with the same arguments -- of one build or of two -- compare file by file up to
+    the rounding of the device reductions."""
+    import numpy as np
+    torch.cuda.synchronize()
+    arrays = {"loss": tr.loss, "kept_tokens": torch.tensor([float(p) for p in tr.P], dtype=torch.float64)}
+    if tr.fwd_only:
+        if tr.infer:
+            arrays["predictions"] = tr.pred
+        else:
+            for k in sorted(tr.feats):
+                arrays[f"features_{k}"] = tr.feats[k]
+    else:
+        if tr.yolox_loss:
+            for k, v in tr.ts.losses.items():
+                if k != "loss":
+                    arrays[f"loss_{k}"] = torch.as_tensor(v)
+        arrays["grad"] = tr.flat.grad
+        g = tr.flat.grad.detach().double()
+        arrays["grad_norm_per_tensor"] = torch.stack([g[o:o + p.numel()].norm() for p, o in zip(tr.flat.params, tr.flat.offsets)])
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach()
+        scalar_like = name.startswith("loss") or name in ("kept_tokens", "grad_norm_per_tensor")
+        a = t.to("cpu", torch.float64 if scalar_like else torch.float32).numpy()
+        if a.size > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, DUMP_SAMPLE, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     global BATCH, HW, PART
     ap = argparse.ArgumentParser()
@@ -383,10 +449,15 @@ def main():
     ap.add_argument("--dw-max-rows", type=int, default=0, help="only weight-gradient jobs over at most this many rows are deferred (0 = all)")
     ap.add_argument("--dw-discard", action="store_true", help="TIMING PROBE: the parked jobs are dropped (the dX chain alone); gradients are wrong")
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also run the legs beyond the headline figure: parity pass + CPU baseline, roofline + "
+                    "batch scan, exposed all-reduce steps (each of them un-timed; off by default)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline / parity leg")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the roofline leg")
     ap.add_argument("--no-batch-scan", action="store_true", help="skip the un-timed B = 1, 2 legs behind roofline.whole_step.batch_independent_ms")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     BATCH = args.batch
     if args.precision == "bf16":       # before anything imports sast_amd._lib; opt-in build: `python -m sast_amd.build --bf16`
         os.environ["SAST_LIB_PATH"] = os.path.join(ROOT, "sast_amd", "libsast_hip_bf16.so")
@@ -440,31 +511,48 @@ def main():
     tr = Trainer(dev, args.amp, world, use_graph=not args.no_graph, seq_len=args.seq_len, fwd_only=args.fwd_only, infer=args.infer,
                  yolox_loss=args.loss == "yolox", segmented=args.segmented, label_every=args.label_every, sync_bn=args.sync_bn,
                  event_dtype=args.event_dtype, defer_dw=bool(args.defer_dw), dw_rows=(args.dw_min_rows, args.dw_max_rows), dw_discard=args.dw_discard,
-                 cuts=tuple(int(c) for c in args.cuts.split(",")))
+                 cuts=tuple(int(c) for c in args.cuts.split(",")), parity_pass=args.full)
+    # --dump-outputs: the last timed step starts from the state every run starts from (initial weights, fresh AdamW state), so that
+    # what it computes is the same from run to run up to rounding.  After many steps it is not: the device reductions round
+    # differently from run to run, and AdamW turns a gradient that is rounding noise around zero into a full-size update of either sign.
+    fixed_last = bool(args.dump_outputs) and not (args.fwd_only or args.infer)
+    if fixed_last:
+        tr.snapshot_state()
     graphed = tr.capture()
     loss_first = tr.loss_first
     for _ in range(args.warmup):
         tr.step()
-    torch.cuda.synchronize()
-    if world > 1:
-        dist.barrier()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        tr.step()
-    torch.cuda.synchronize()
-    if world > 1:
-        dist.barrier()
-    torch.cuda.synchronize()
-    el = time.perf_counter() - t0
+
+    def timed(n):
+        torch.cuda.synchronize()
+        if world > 1:
+            dist.barrier()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(n):
+            tr.step()
+        torch.cuda.synchronize()
+        if world > 1:
+            dist.barrier()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+
+    if fixed_last:
+        el = timed(args.steps - 1) if args.steps > 1 else 0.0
+        tr.restore_state()           # (outside the clock)
+        el += timed(1)
+    else:
+        el = timed(args.steps)
     if world > 1:
         t = torch.tensor([el], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(tr, args.dump_outputs)
     # N > 1: how much of the gradient exchange is NOT hidden behind the backward -- a few extra, un-timed steps on every rank with
-    # event pairs (main stream idle, side stream done); max over ranks
+    # event pairs (main stream idle, side stream done); max over ranks (--full)
     exposed_ms, bucket_ms = None, None
-    if (world > 1 or tr.segmented or args.defer_dw) and not tr.fwd_only:
+    if args.full and (world > 1 or tr.segmented or args.defer_dw) and not tr.fwd_only:
         tr.ts.measure_exposed = True
         for _ in range(20):
             tr.step()
@@ -491,7 +579,7 @@ def main():
         res = {
             "metric": metric, "baseline_metric": baseline_cfg,
             "value": BATCH * args.seq_len * world * args.steps / el, "unit": "frames/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": 1e3 * el / args.steps, "higher_is_better": True, "scaling": "weak",
+            "warmup": args.warmup, "ms_per_step": 1e3 * el / args.steps, "higher_is_better": True, "scaling": "weak", "full": bool(args.full),
             "vs_baseline": None, "dtype": "f32" if args.precision == "f32" else "bf16 operands / f32 accumulate", "data": "synthetic",
             "config": {"workload": ({"1mpx": "1Mpx 640x360 (padded 384x640)", "gen1": "Gen1 304x240 (padded 256x320)",
                                     "1mpx-split1": "1Mpx 640x360 (padded 384x640), partition_split_32 1 (12x20 = 240-token partitions)"}[args.res]) +
@@ -528,7 +616,7 @@ def main():
         }
         # (the roofline leg re-runs the step on rank 0 ALONE: with SyncBatchNorm over several ranks its statistics all-reduces would wait
         # for ranks that are not there -- skipped, `roofline` is then absent from the line)
-        if not args.no_roofline and not (tr.sync_bn and world > 1):
+        if args.full and not args.no_roofline and not (tr.sync_bn and world > 1):
             from sast_amd.profiling import dominant_kernel_roofline
             res["roofline"] = dominant_kernel_roofline(tr, ms_per_step=res["ms_per_step"], hw=HW, batch=BATCH, seq_len=max(args.seq_len, 1),
                                                        pmc_applies=baseline_cfg and args.event_dtype == "int32" and not tr.sync_bn)
@@ -537,7 +625,7 @@ def main():
                 ws["peak_memory_bytes"] = {"allocated": int(torch.cuda.max_memory_allocated()), "reserved": int(torch.cuda.max_memory_reserved())}
                 if world == 1 and not args.no_batch_scan and not (args.fwd_only or args.infer) and BATCH > 2:
                     ws.update(batch_scan(args, dev, world, res["ms_per_step"]))
-        if not args.no_cpu_baseline and world == 1 and args.seq_len == 1 and not args.infer and args.loss == "proxy" and args.precision == "f32":
+        if args.full and not args.no_cpu_baseline and world == 1 and args.seq_len == 1 and not args.infer and args.loss == "proxy" and args.precision == "f32":
             parity, res["cpu_baseline"] = cpu_baseline(args.amp, tr.init_state, fwd_only=args.fwd_only, tr=tr)
             if parity is not None:
                 res["parity"] = parity

@@ -5,7 +5,7 @@
 out=$1; shift
 set_=$1; shift
 mkdir -p $out
-B="python bench.py --steps 100 --warmup 20 --no-cpu-baseline --no-roofline $@"
+B="python bench.py --full --steps 100 --warmup 20 --no-cpu-baseline --no-roofline $@"
 run() { name=$1; shift; ( "$@" 2>$out/err_$name.log | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$name', round(d['ms_per_step'],4), round(d['value'],1), d['config'].get('allreduce_exposed_ms'))" || echo "$name FAILED" ) >> $out/defer_probe.txt; }
 if [ "$set_" = "first" ]; then
 for rep in 1 2; do

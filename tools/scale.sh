@@ -13,7 +13,7 @@ python bench.py --gpus 1 --steps $steps --warmup $warmup
 for n in 2 4 8; do
   for mode in "" "--sync-bn"; do
     python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port $((29500 + n)) \
-      bench.py --gpus $n --steps $steps --warmup $warmup $mode
+      bench.py --gpus $n --steps $steps --warmup $warmup --full $mode
   done
 done
 # every line carries config.sync_batchnorm (which semantics ran), config.collective_ranks_verified (an all-reduce of ones across the

@@ -15,7 +15,7 @@ def pmc_total_kb(amp, counter):
     subprocess.run(["rm", "-rf", d])
     env = dict(os.environ, TMPDIR="/tmp")
     r = subprocess.run(["timeout", "300", "rocprofv3", "--kernel-trace", "--pmc", counter, "-d", d, "-o", "p", "--", sys.executable, "bench.py",
-                        "--batch", "8", "--amp", str(amp), "--steps", str(PMC_STEPS), "--warmup", str(PMC_WARM), "--no-cpu-baseline",
+                        "--batch", "8", "--amp", str(amp), "--steps", str(PMC_STEPS), "--warmup", str(PMC_WARM), "--full", "--no-cpu-baseline",
                         "--no-roofline", "--no-graph"], capture_output=True, text=True, env=env)
     dbs = glob.glob(d + "/*.db")
     if not dbs:
@@ -29,7 +29,7 @@ def pmc_total_kb(amp, counter):
 
 out = []
 for amp in amps:
-    r = subprocess.run([sys.executable, "bench.py", "--batch", "8", "--amp", str(amp), "--steps", "30", "--warmup", "5", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--batch", "8", "--amp", str(amp), "--steps", "30", "--warmup", "5", "--no-cpu-baseline"],
                        capture_output=True, text=True)
     line = [l for l in r.stdout.splitlines() if l.startswith("{")]
     if not line:
