@@ -27,7 +27,7 @@ extern "C" {
 
 typedef void* sast_stream_t; /* hipStream_t */
 
-enum { SAST_DT_F32 = 0, SAST_DT_I32 = 1, SAST_DT_U8 = 2 };
+enum { SAST_DT_F32 = 0, SAST_DT_I32 = 1, SAST_DT_U8 = 2, SAST_DT_I64 = 3, SAST_DT_I16 = 4 };
 
 int sast_version(void);
 /* 1: the GEMM template evaluates fp32 products as six bf16 MFMAs on an exact three-way operand split (default build);
@@ -414,6 +414,48 @@ int sast_dw_defer_rows(long min_rows, long max_rows);
 int sast_dw_pending(void);
 int sast_dw_discard(void);
 int sast_dw_flush(sast_stream_t stream);
+
+/* ---- raw events -> stacked-histogram frames (csrc/k_events.hip).  The reference builds its input offline on the CPU:
+ * StackedHistogram.construct (data/utils/representations.py:37-121) once per window of scripts/genx/preprocess_dataset.py:476-530, on
+ * timestamps its reader made non-decreasing (:159-168) and polarities clipped at 0 (:177), downsampled by 2 with nearest-exact
+ * interpolation for Gen4 (:463-473).  Event arrays x, y, p are SAST_DT_I64 / I32 / I16, t is SAST_DT_I64 / I32.  Per-frame sizes (event
+ * count n, window ends, the time carry) live in device memory; grids are sized from capacities, so the calls replay inside a graph. */
+#define SAST_EVENT_SCAN_BLOCKS 512
+enum { SAST_EVENT_WINDOW_DURATION = 0, SAST_EVENT_WINDOW_COUNT = 1 };
+
+/* t_out[i] = max(t[i], t_last, t[0..i-1]) for i < min(*n, capacity), then *t_last = that running maximum (the carry into the next chunk;
+ * the reader starts it at 0).  t_out may alias t when t is int64.  ws: int64[SAST_EVENT_SCAN_BLOCKS + 1]. */
+int sast_event_correct_time(const void* t, int t_dtype, const int64_t* n, int64_t capacity, int64_t* t_out, int64_t* t_last, int64_t* ws,
+                            sast_stream_t stream);
+/* window b over the sorted t[0 .. min(*n, capacity)):  end = searchsorted(t, ends_us[b], 'right');  start = searchsorted(t, ends_us[b] -
+ * value, 'left') (SAST_EVENT_WINDOW_DURATION, value in microseconds) or max(end - value, 0) (SAST_EVENT_WINDOW_COUNT, value events).
+ * bounds: int64 [B, 2] = (start, end). */
+int sast_event_window_bounds(const int64_t* t, const int64_t* n, int64_t capacity, const int64_t* ends_us, int B, int mode, int64_t value,
+                             int64_t* bounds, sast_stream_t stream);
+
+typedef struct SastEventArgs {
+  const void* x;            /* event columns, `*_dtype` each; events [bounds[b][0], bounds[b][1]) form window b */
+  const void* y;
+  const void* p;            /* 0 / 1 (negative values are invalid, or 0 with clip_negative_polarity) */
+  const void* t;            /* non-decreasing within a window: the bin of an event is computed from the window's first / last t */
+  const int64_t* bounds;    /* int64 [B, 2], clipped to [0, capacity) */
+  uint8_t* out;             /* uint8 [B, 2*bins, H', W']: H' = height / 2, W' = width / 2 with downsample_by_2, else height, width */
+  int32_t* err;             /* int32 [2], ACCUMULATED: [0] invalid events (x, y outside the sensor, p outside 0..1) among those the
+                               windows hold, each counted once however many windows hold it (events in no window are not read);
+                               they are never written;
+                               [1] windows with more than window_capacity kept events (left all zero) */
+  void* ws;                 /* sast_event_frames_ws_bytes(); ZERO on first use, left zero for the next call */
+  int64_t capacity;         /* events the x / y / p / t buffers hold (<= 2^31 - 1) */
+  int64_t window_capacity;  /* kept events per window the workspace holds */
+  int32_t x_dtype, y_dtype, p_dtype, t_dtype;
+  int32_t B, bins, height, width;   /* height / width: the sensor, full resolution; 2*bins <= 640 */
+  int32_t count_cutoff;     /* 1 .. 255 (the reference's None is 255) */
+  int32_t fastmode;         /* 1: counts wrap modulo 256, then min(count, cutoff);  0: counts wrap as int16, then clamp(0, cutoff) */
+  int32_t downsample_by_2;  /* only events with odd x and odd y count, at (y / 2, x / 2) */
+  int32_t clip_negative_polarity;
+} SastEventArgs;
+size_t sast_event_frames_ws_bytes(int B, int bins, int height, int width, int downsample_by_2, int64_t window_capacity); /* 0: unsupported */
+int sast_event_frames(const SastEventArgs* a, sast_stream_t stream);
 
 /* ---- tuning knobs.  Every SAST_* environment variable the library reads (tile / split / launch-shape choices, all defaulting to the
  * measured-best setting: DESIGN.md section 7) goes through one registry: the value is read from the environment at first use and cached;

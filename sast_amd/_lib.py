@@ -18,7 +18,9 @@ P = C.c_void_p
 I32 = C.c_int32
 F32 = C.c_float
 
-DT_F32, DT_I32, DT_U8 = 0, 1, 2
+DT_F32, DT_I32, DT_U8, DT_I64, DT_I16 = 0, 1, 2, 3, 4
+EVENT_WINDOW_DURATION, EVENT_WINDOW_COUNT = 0, 1
+EVENT_SCAN_BLOCKS = 512   # SAST_EVENT_SCAN_BLOCKS
 
 
 def _struct(name, spec):
@@ -72,6 +74,10 @@ SastSampleGather = _struct("SastSampleGather", [
     (C.c_uint8 * 256, "t_of"), (C.c_uint8 * 256, "b_of"),
 ])
 SastSampleMask = _struct("SastSampleMask", [(C.c_uint8 * 256, "sel")])
+SastEventArgs = _struct("SastEventArgs", [
+    (P, "x y p t bounds out err ws"), (C.c_int64, "capacity window_capacity"),
+    (I32, "x_dtype y_dtype p_dtype t_dtype B bins height width count_cutoff fastmode downsample_by_2 clip_negative_polarity"),
+])
 
 _SIGNATURES = {
     "sast_version": (C.c_int, []),
@@ -138,6 +144,10 @@ _SIGNATURES = {
     "sast_prof_calibrate": (C.c_float, [P, C.c_int]),
     "sast_prof_report": (C.c_size_t, [C.c_char_p, C.c_size_t]),
     "sast_adamw": (C.c_int, [P, P, P, P, C.c_size_t, P, C.c_double, C.c_double, F32, F32, F32, F32, P]),
+    "sast_event_correct_time": (C.c_int, [P, C.c_int, P, C.c_int64, P, P, P, P]),
+    "sast_event_window_bounds": (C.c_int, [P, P, C.c_int64, P, C.c_int, C.c_int, C.c_int64, P, P]),
+    "sast_event_frames_ws_bytes": (C.c_size_t, [C.c_int] * 5 + [C.c_int64]),
+    "sast_event_frames": (C.c_int, [C.POINTER(SastEventArgs), P]),
 }
 
 _lib = None

@@ -1,0 +1,435 @@
+// Raw events (x, y, p, t) -> stacked-histogram frames on the device.
+//
+// Reference: StackedHistogram.construct (data/utils/representations.py:37-121) and the reader / windowing / downsampling of the offline
+// script around it (scripts/genx/preprocess_dataset.py:159-177 time correction and polarity clip, :463-473 nearest-exact downsampling
+// by 2, :507-530 window bounds).  Three entry points:
+//   sast_event_correct_time   running maximum of the timestamps with a carry in device memory (two passes over a fixed block count)
+//   sast_event_window_bounds  per window two binary searches (duration mode) or one (count mode) -> int64 [B, 2] event ranges
+//   sast_event_frames         the histogram: bucket each window's events by 32-column spatial tile (count -> scan -> scatter of packed
+//                             records), then one workgroup per (window, tile) counts its records in LDS and writes the finished uint8 tile
+// Integer counts do not depend on arrival order: the frames are bitwise reproducible.  Every per-frame size (event count, window
+// bounds, carry) is read on the device; the grids are sized from capacities, so a captured graph replays on new events.
+#include <climits>
+#include "common.cuh"
+#include "kernels.h"
+
+namespace sast {
+namespace {
+
+constexpr int EV_THREADS = 256;
+constexpr int EV_TILE_W = 32;          // tile columns; a record keeps the pixel in 10 bits (tile rows x 32 <= 1024)
+constexpr int EV_LDS_WORDS = 20480;    // u32 counters of one (window, tile) workgroup: 80 KiB (32 x 32 px x 20 channels)
+constexpr int EV_MAX_TILES = 8192;     // tiles per window: the LDS tile histogram of the bucketing kernels (32 KiB)
+constexpr int EV_MAX_CHANNELS = 640;   // 2 * bins: the channel of a record is 10 bits, and one tile row must fit EV_LDS_WORDS
+constexpr int EV_EVENTS_PER_BLOCK = 8192;
+constexpr int EV_MAX_BLOCKS = 1024;    // bucketing workgroups per window
+
+struct EvGeom {
+  int H, W;            // sensor size: events outside it are invalid
+  int Ho, Wo;          // frame size (H/2, W/2 with downsample_by_2)
+  int bins, C;         // C = 2 * bins channels
+  int th;              // tile rows
+  int tiles_x, tiles;  // tiles per frame row / per frame
+  int cutoff, fast, ds, clip_pol;
+};
+
+__device__ __forceinline__ long long ld_int(const void* p, int dt, long long i) {
+  if (dt == SAST_DT_I64) return static_cast<const long long*>(p)[i];
+  if (dt == SAST_DT_I32) return static_cast<const int*>(p)[i];
+  return static_cast<const short*>(p)[i];
+}
+
+struct EvWindow {
+  long long s, e;      // event range [s, e)
+  long long t0;
+  float span;          // max(t1 - t0, 1) as the reference's int64 / int division sees it: converted to fp32
+};
+
+__device__ __forceinline__ EvWindow ev_window(const SastEventArgs& a, int b) {
+  EvWindow w;
+  w.s = max(a.bounds[2 * b], 0LL);
+  w.e = min(a.bounds[2 * b + 1], (long long)a.capacity);
+  w.t0 = 0;
+  w.span = 1.0f;
+  if (w.e > w.s) {
+    w.t0 = ld_int(a.t, a.t_dtype, w.s);
+    const long long t1 = ld_int(a.t, a.t_dtype, w.e - 1);
+    w.span = (float)max(t1 - w.t0, 1LL);
+  }
+  return w;
+}
+
+// >0: a record (tile in *tile, packed pixel | channel << 10 in *rec);  0: dropped by the downsampling;  <0: an invalid event
+__device__ __forceinline__ int ev_record(const SastEventArgs& a, const EvGeom& g, const EvWindow& w, long long i, int* tile,
+                                         unsigned* rec) {
+  const long long x = ld_int(a.x, a.x_dtype, i), y = ld_int(a.y, a.y_dtype, i);
+  long long p = ld_int(a.p, a.p_dtype, i);
+  const long long dt = ld_int(a.t, a.t_dtype, i) - w.t0;
+  if (p < 0 && g.clip_pol) p = 0;                       // preprocess_dataset.py:177 np.clip(p, a_min=0)
+  if (x < 0 || x >= g.W || y < 0 || y >= g.H || p < 0 || p > 1 || dt < 0) return -1;
+  int ox = (int)x, oy = (int)y;
+  if (g.ds) {                                            // nearest-exact at scale 0.5: output (i, j) is input (2i+1, 2j+1)
+    if (!(ox & 1) || !(oy & 1)) return 0;
+    ox >>= 1;
+    oy >>= 1;
+    if (ox >= g.Wo || oy >= g.Ho) return 0;
+  }
+  // representations.py:98-104: (t - t0) / max(t1 - t0, 1) is int64 / int64 true division in fp32 (both operands rounded to fp32,
+  // one correctly rounded divide), then * bins, floor, clamp(max = bins - 1)
+  const float q = __fdiv_rn((float)dt, w.span) * (float)g.bins;
+  const int bin = min((int)floorf(q), g.bins - 1);
+  const int ty = oy / g.th, tx = ox / EV_TILE_W;
+  *tile = ty * g.tiles_x + tx;
+  *rec = (unsigned)((oy - ty * g.th) * EV_TILE_W + (ox - tx * EV_TILE_W)) | ((unsigned)(p * g.bins + bin) << 10);
+  return 1;
+}
+
+// the share of window b's events that bucketing workgroup blockIdx.x handles
+__device__ __forceinline__ bool ev_chunk(const EvWindow& w, long long* lo, long long* hi) {
+  const long long len = w.e - w.s;
+  const long long chunk = (len + gridDim.x - 1) / gridDim.x;
+  *lo = w.s + blockIdx.x * chunk;
+  *hi = min(*lo + chunk, w.e);
+  return *lo < *hi;
+}
+
+// windows may overlap (count mode, or ends closer than the duration): an invalid event is reported by the first window that holds it
+__device__ __forceinline__ bool ev_in_earlier_window(const SastEventArgs& a, int b, long long i) {
+  for (int k = 0; k < b; ++k)
+    if (i >= max(a.bounds[2 * k], 0LL) && i < min(a.bounds[2 * k + 1], (long long)a.capacity)) return true;
+  return false;
+}
+
+// pass 1: events per (window, tile) into tile_cnt (zero on entry; the scan clears it again); invalid events into err[0], each once
+__global__ __launch_bounds__(EV_THREADS) void ev_count_kernel(SastEventArgs a, EvGeom g, int* tile_cnt) {
+  extern __shared__ __attribute__((aligned(16))) int hist[];
+  __shared__ int s_bad;
+  const int b = blockIdx.y;
+  const EvWindow w = ev_window(a, b);
+  long long lo, hi;
+  if (!ev_chunk(w, &lo, &hi)) return;
+  for (int k = threadIdx.x; k < g.tiles; k += EV_THREADS) hist[k] = 0;
+  if (threadIdx.x == 0) s_bad = 0;
+  __syncthreads();
+  int bad = 0;
+  for (long long i = lo + threadIdx.x; i < hi; i += EV_THREADS) {
+    int tile;
+    unsigned rec;
+    const int r = ev_record(a, g, w, i, &tile, &rec);
+    if (r > 0) atomicAdd(&hist[tile], 1);
+    else if (r < 0 && !ev_in_earlier_window(a, b, i)) ++bad;
+  }
+  if (bad) atomicAdd(&s_bad, bad);
+  __syncthreads();
+  for (int k = threadIdx.x; k < g.tiles; k += EV_THREADS)
+    if (hist[k]) atomicAdd(&tile_cnt[(size_t)b * g.tiles + k], hist[k]);
+  if (threadIdx.x == 0 && s_bad) atomicAdd(&a.err[0], s_bad);
+}
+
+// pass 2, one workgroup per window: exclusive scan of the tile counts -> off[b][0..tiles] and the scatter cursors; clears tile_cnt.
+// A window with more events than window_capacity is left empty (all-zero frame) and counted in err[1].
+__global__ __launch_bounds__(EV_THREADS) void ev_scan_kernel(SastEventArgs a, EvGeom g, int* tile_cnt, int* off, int* cursor, int* ovf) {
+  __shared__ long long part[EV_THREADS];
+  const int b = blockIdx.x, T = g.tiles;
+  int* cnt = tile_cnt + (size_t)b * T;
+  int* o = off + (size_t)b * (T + 1);
+  int* cur = cursor + (size_t)b * T;
+  const int per = (T + EV_THREADS - 1) / EV_THREADS;
+  const int k0 = min(threadIdx.x * per, T), k1 = min(k0 + per, T);
+  long long sum = 0;
+  for (int k = k0; k < k1; ++k) sum += cnt[k];
+  part[threadIdx.x] = sum;
+  __syncthreads();
+  for (int d = 1; d < EV_THREADS; d <<= 1) {           // inclusive Hillis-Steele scan of the per-thread sums
+    const long long v = threadIdx.x >= d ? part[threadIdx.x - d] : 0;
+    __syncthreads();
+    part[threadIdx.x] += v;
+    __syncthreads();
+  }
+  const long long total = part[EV_THREADS - 1];
+  const bool over = total > a.window_capacity;
+  long long run = part[threadIdx.x] - sum;
+  for (int k = k0; k < k1; ++k) {
+    const int c = cnt[k];
+    o[k] = over ? 0 : (int)run;
+    cur[k] = over ? 0 : (int)run;
+    run += c;
+    cnt[k] = 0;
+  }
+  if (threadIdx.x == 0) {
+    o[T] = over ? 0 : (int)total;
+    ovf[b] = over ? 1 : 0;
+    if (over) atomicAdd(&a.err[1], 1);
+  }
+}
+
+// pass 3: the same events again; each workgroup reserves one range per tile (one global atomic per (workgroup, tile)), then places
+// its records there through LDS cursors
+__global__ __launch_bounds__(EV_THREADS) void ev_scatter_kernel(SastEventArgs a, EvGeom g, int* cursor, const int* ovf, unsigned* recs) {
+  extern __shared__ __attribute__((aligned(16))) int hist[];
+  const int b = blockIdx.y;
+  if (ovf[b]) return;
+  const EvWindow w = ev_window(a, b);
+  long long lo, hi;
+  if (!ev_chunk(w, &lo, &hi)) return;
+  for (int k = threadIdx.x; k < g.tiles; k += EV_THREADS) hist[k] = 0;
+  __syncthreads();
+  for (long long i = lo + threadIdx.x; i < hi; i += EV_THREADS) {
+    int tile;
+    unsigned rec;
+    if (ev_record(a, g, w, i, &tile, &rec) > 0) atomicAdd(&hist[tile], 1);
+  }
+  __syncthreads();
+  for (int k = threadIdx.x; k < g.tiles; k += EV_THREADS)
+    if (hist[k]) hist[k] = atomicAdd(&cursor[(size_t)b * g.tiles + k], hist[k]);
+  __syncthreads();
+  unsigned* wr = recs + (size_t)b * (size_t)a.window_capacity;
+  for (long long i = lo + threadIdx.x; i < hi; i += EV_THREADS) {
+    int tile;
+    unsigned rec;
+    if (ev_record(a, g, w, i, &tile, &rec) > 0) {
+      const int pos = atomicAdd(&hist[tile], 1);
+      if (pos < a.window_capacity) wr[pos] = rec;
+    }
+  }
+}
+
+// representations.py:115-118: fastmode accumulates in uint8 (wraps mod 256), otherwise in int16 (wraps to negative above 32767);
+// then clamp(0, count_cutoff)
+__device__ __forceinline__ unsigned char ev_finish(unsigned v, int cutoff, int fast) {
+  if (fast) return (unsigned char)min((int)(v & 255u), cutoff);
+  const int s = (short)(unsigned short)(v & 0xffffu);
+  return (unsigned char)min(max(s, 0), cutoff);
+}
+
+// pass 4, one workgroup per (tile, window): u32 counters of the tile's th x 32 pixels x C channels in LDS, then the finished uint8
+// tile, every pixel of it written once (no clear of the output, no finishing pass)
+__global__ __launch_bounds__(EV_THREADS) void ev_accum_kernel(SastEventArgs a, EvGeom g, const int* off, const unsigned* recs) {
+  extern __shared__ __attribute__((aligned(16))) unsigned cnt[];
+  const int t = blockIdx.x, b = blockIdx.y;
+  const int px = g.th * EV_TILE_W, n = px * g.C;
+  for (int k = threadIdx.x; k < n; k += EV_THREADS) cnt[k] = 0;
+  __syncthreads();
+  const int* o = off + (size_t)b * (g.tiles + 1);
+  const int beg = o[t], end = min(o[t + 1], (int)min(a.window_capacity, (long long)INT_MAX));
+  const unsigned* rd = recs + (size_t)b * (size_t)a.window_capacity;
+  for (int i = beg + threadIdx.x; i < end; i += EV_THREADS) {
+    const unsigned r = rd[i];
+    const unsigned k = (r >> 10) * px + (r & 1023u);
+    if (k < (unsigned)n) atomicAdd(&cnt[k], 1u);
+  }
+  __syncthreads();
+  const int oy0 = (t / g.tiles_x) * g.th, ox0 = (t % g.tiles_x) * EV_TILE_W;
+  for (int k = threadIdx.x; k < n; k += EV_THREADS) {
+    const int c = k / px, l = k - c * px;
+    const int oy = oy0 + l / EV_TILE_W, ox = ox0 + (l % EV_TILE_W);
+    if (oy < g.Ho && ox < g.Wo)
+      a.out[(((size_t)b * g.C + c) * g.Ho + oy) * g.Wo + ox] = ev_finish(cnt[k], g.cutoff, g.fast);
+  }
+}
+
+// ---- time correction (preprocess_dataset.py:159-168): t[i] = max(t[i], running max), the running max starting at the carry
+constexpr int EV_SCAN_BLOCKS = SAST_EVENT_SCAN_BLOCKS;
+
+__device__ __forceinline__ void ev_tchunk(long long n, long long* lo, long long* hi) {
+  const long long chunk = (n + gridDim.x - 1) / gridDim.x;
+  *lo = min((long long)blockIdx.x * chunk, n);
+  *hi = min(*lo + chunk, n);
+}
+
+__device__ __forceinline__ long long block_max(long long v, long long* red) {
+  for (int d = 32; d >= 1; d >>= 1) v = max(v, __shfl_xor(v, d));
+  const int wv = threadIdx.x >> 6;
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[wv] = v;
+  __syncthreads();
+  long long m = red[0];
+  for (int k = 1; k < EV_THREADS / 64; ++k) m = max(m, red[k]);
+  return m;
+}
+
+// ws[0] = the carry in, ws[1 + blk] = the maximum of block blk's chunk
+__global__ __launch_bounds__(EV_THREADS) void ev_tmax_partial_kernel(const void* t, int dt, const long long* n_dev, long long cap,
+                                                                     const long long* t_last, long long* ws) {
+  __shared__ long long red[EV_THREADS / 64];
+  const long long n = min(max(*n_dev, 0LL), cap);
+  long long lo, hi;
+  ev_tchunk(n, &lo, &hi);
+  long long m = LLONG_MIN;
+  for (long long i = lo + threadIdx.x; i < hi; i += EV_THREADS) m = max(m, ld_int(t, dt, i));
+  m = block_max(m, red);
+  if (threadIdx.x == 0) {
+    ws[1 + blockIdx.x] = m;
+    if (blockIdx.x == 0) ws[0] = *t_last;
+  }
+}
+
+__global__ __launch_bounds__(EV_THREADS) void ev_tmax_apply_kernel(const void* t, int dt, const long long* n_dev, long long cap,
+                                                                   const long long* ws, long long* t_out, long long* t_last) {
+  __shared__ long long red[EV_THREADS / 64];
+  __shared__ long long wtot[EV_THREADS / 64];
+  const long long n = min(max(*n_dev, 0LL), cap);
+  long long lo, hi;
+  ev_tchunk(n, &lo, &hi);
+  long long carry = LLONG_MIN;
+  for (int k = threadIdx.x; k < (int)blockIdx.x + 1; k += EV_THREADS) carry = max(carry, k == 0 ? ws[0] : ws[k]);
+  carry = block_max(carry, red);
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  for (long long base = lo; base < hi; base += EV_THREADS) {
+    const long long i = base + threadIdx.x;
+    long long v = i < hi ? ld_int(t, dt, i) : LLONG_MIN;
+    for (int d = 1; d < 64; d <<= 1) {                    // inclusive max-scan of the wave
+      const long long u = __shfl_up(v, d);
+      if (lane >= d) v = max(v, u);
+    }
+    __syncthreads();
+    if (lane == 63) wtot[wv] = v;
+    __syncthreads();
+    long long pre = carry;
+    for (int k = 0; k < wv; ++k) pre = max(pre, wtot[k]);
+    v = max(v, pre);
+    if (i < hi) t_out[i] = v;
+    for (int k = wv; k < EV_THREADS / 64; ++k) pre = max(pre, wtot[k]);
+    carry = pre;
+  }
+  if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) {
+    long long m = ws[0];
+    for (int k = 1; k <= (int)gridDim.x; ++k) m = max(m, ws[k]);
+    *t_last = m;
+  }
+}
+
+// ---- window bounds (preprocess_dataset.py:507-513): np.searchsorted over the corrected timestamps
+__device__ __forceinline__ long long search(const long long* t, long long n, long long v, bool right) {
+  long long lo = 0, hi = n;
+  while (lo < hi) {
+    const long long mid = (lo + hi) >> 1;
+    if (right ? t[mid] <= v : t[mid] < v) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
+}
+
+__global__ void ev_bounds_kernel(const long long* t, const long long* n_dev, long long cap, const long long* ends, int B, int mode,
+                                 long long value, long long* bounds) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const long long n = min(max(*n_dev, 0LL), cap);
+  const long long e = search(t, n, ends[b], true);
+  const long long s = mode == SAST_EVENT_WINDOW_COUNT ? max(e - value, 0LL) : search(t, n, ends[b] - value, false);
+  bounds[2 * b] = s;
+  bounds[2 * b + 1] = e;
+}
+
+bool int_dtype(int dt) { return dt == SAST_DT_I64 || dt == SAST_DT_I32 || dt == SAST_DT_I16; }
+
+// geometry of a call, or false for arguments the kernels do not take
+bool ev_geom(int B, int bins, int height, int width, int ds, long long wcap, EvGeom* g) {
+  if (B < 1 || B > 65535 || bins < 1 || 2 * bins > EV_MAX_CHANNELS || height < 1 || width < 1 || wcap < 0 || wcap > INT_MAX) return false;
+  g->H = height;
+  g->W = width;
+  g->Ho = ds ? height / 2 : height;
+  g->Wo = ds ? width / 2 : width;
+  if (g->Ho < 1 || g->Wo < 1) return false;
+  g->bins = bins;
+  g->C = 2 * bins;
+  g->th = min(32, EV_LDS_WORDS / (EV_TILE_W * g->C));
+  g->tiles_x = (g->Wo + EV_TILE_W - 1) / EV_TILE_W;
+  const long long tiles = (long long)g->tiles_x * ((g->Ho + g->th - 1) / g->th);
+  if (tiles > EV_MAX_TILES) return false;
+  g->tiles = (int)tiles;
+  g->ds = ds ? 1 : 0;
+  return true;
+}
+
+size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
+
+struct EvWs { int* tile_cnt; int* off; int* cursor; int* ovf; unsigned* recs; size_t bytes; };
+
+EvWs ev_ws(void* base, int B, const EvGeom& g, long long wcap) {
+  EvWs w;
+  char* p = static_cast<char*>(base);
+  size_t o = 0;
+  w.tile_cnt = reinterpret_cast<int*>(p + o); o += align16(sizeof(int) * (size_t)B * g.tiles);
+  w.off = reinterpret_cast<int*>(p + o);      o += align16(sizeof(int) * (size_t)B * (g.tiles + 1));
+  w.cursor = reinterpret_cast<int*>(p + o);   o += align16(sizeof(int) * (size_t)B * g.tiles);
+  w.ovf = reinterpret_cast<int*>(p + o);      o += align16(sizeof(int) * (size_t)B);
+  w.recs = reinterpret_cast<unsigned*>(p + o); o += align16(sizeof(unsigned) * (size_t)B * (size_t)wcap);
+  w.bytes = o;
+  return w;
+}
+
+}  // namespace
+}  // namespace sast
+
+extern "C" {
+
+int sast_event_correct_time(const void* t, int t_dtype, const int64_t* n, int64_t capacity, int64_t* t_out, int64_t* t_last, int64_t* ws,
+                            sast_stream_t stream) {
+  SAST_ENTRY();
+  using namespace sast;
+  if (!t || !n || !t_out || !t_last || !ws || capacity < 0 || (t_dtype != SAST_DT_I64 && t_dtype != SAST_DT_I32)) return SAST_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  const long long* nd = reinterpret_cast<const long long*>(n);
+  long long* w = reinterpret_cast<long long*>(ws);
+  SAST_LAUNCH(ev_tmax_partial_kernel, dim3(EV_SCAN_BLOCKS), dim3(EV_THREADS), 0, st, t, t_dtype, nd, (long long)capacity,
+              reinterpret_cast<const long long*>(t_last), w);
+  SAST_LAUNCH(ev_tmax_apply_kernel, dim3(EV_SCAN_BLOCKS), dim3(EV_THREADS), 0, st, t, t_dtype, nd, (long long)capacity,
+              reinterpret_cast<const long long*>(w), reinterpret_cast<long long*>(t_out), reinterpret_cast<long long*>(t_last));
+  SAST_CHECK_LAUNCH();
+  return SAST_OK;
+}
+
+int sast_event_window_bounds(const int64_t* t, const int64_t* n, int64_t capacity, const int64_t* ends_us, int B, int mode, int64_t value,
+                             int64_t* bounds, sast_stream_t stream) {
+  SAST_ENTRY();
+  using namespace sast;
+  if (!t || !n || !ends_us || !bounds || B < 1 || capacity < 0 || value < 0 ||
+      (mode != SAST_EVENT_WINDOW_DURATION && mode != SAST_EVENT_WINDOW_COUNT))
+    return SAST_EINVAL;
+  SAST_LAUNCH(ev_bounds_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, reinterpret_cast<const long long*>(t),
+              reinterpret_cast<const long long*>(n), (long long)capacity, reinterpret_cast<const long long*>(ends_us), B, mode,
+              (long long)value, reinterpret_cast<long long*>(bounds));
+  SAST_CHECK_LAUNCH();
+  return SAST_OK;
+}
+
+size_t sast_event_frames_ws_bytes(int B, int bins, int height, int width, int downsample_by_2, int64_t window_capacity) {
+  sast::EvGeom g;
+  if (!sast::ev_geom(B, bins, height, width, downsample_by_2, window_capacity, &g)) return 0;
+  return sast::ev_ws(nullptr, B, g, window_capacity).bytes;
+}
+
+int sast_event_frames(const SastEventArgs* a, sast_stream_t stream) {
+  SAST_ENTRY();
+  using namespace sast;
+  if (!a) return SAST_EINVAL;
+  EvGeom g;
+  if (!ev_geom(a->B, a->bins, a->height, a->width, a->downsample_by_2, a->window_capacity, &g)) return SAST_EINVAL;
+  if (!a->x || !a->y || !a->p || !a->t || !a->bounds || !a->out || !a->err || !a->ws || a->capacity < 0 || a->capacity > INT_MAX)
+    return SAST_EINVAL;
+  if (!int_dtype(a->x_dtype) || !int_dtype(a->y_dtype) || !int_dtype(a->p_dtype) || (a->t_dtype != SAST_DT_I64 && a->t_dtype != SAST_DT_I32))
+    return SAST_EINVAL;
+  if (a->count_cutoff < 1 || a->count_cutoff > 255) return SAST_EINVAL;
+  g.cutoff = a->count_cutoff;
+  g.fast = a->fastmode ? 1 : 0;
+  g.clip_pol = a->clip_negative_polarity ? 1 : 0;
+  const EvWs w = ev_ws(a->ws, a->B, g, a->window_capacity);
+  const int lds_acc = (int)(sizeof(unsigned) * g.th * EV_TILE_W * g.C);
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&ev_accum_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                          (int)(sizeof(unsigned) * EV_LDS_WORDS)) != hipSuccess)
+    return SAST_ELAUNCH;
+  hipStream_t st = (hipStream_t)stream;
+  const long long per = (a->capacity + EV_EVENTS_PER_BLOCK - 1) / EV_EVENTS_PER_BLOCK;
+  const dim3 gb((unsigned)std::min<long long>(std::max<long long>(per, 1), EV_MAX_BLOCKS), (unsigned)a->B);
+  const size_t lds_hist = sizeof(int) * (size_t)g.tiles;
+  SAST_LAUNCH(ev_count_kernel, gb, dim3(EV_THREADS), lds_hist, st, *a, g, w.tile_cnt);
+  SAST_LAUNCH(ev_scan_kernel, dim3((unsigned)a->B), dim3(EV_THREADS), 0, st, *a, g, w.tile_cnt, w.off, w.cursor, w.ovf);
+  SAST_LAUNCH(ev_scatter_kernel, gb, dim3(EV_THREADS), lds_hist, st, *a, g, w.cursor, (const int*)w.ovf, w.recs);
+  SAST_LAUNCH(ev_accum_kernel, dim3((unsigned)g.tiles, (unsigned)a->B), dim3(EV_THREADS), (size_t)lds_acc, st, *a, g, (const int*)w.off,
+              (const unsigned*)w.recs);
+  SAST_CHECK_LAUNCH();
+  return SAST_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,245 @@
+"""Raw events (x, y, p, t) -> stacked-histogram frames on the GPU (csrc/k_events.hip).
+
+The reference builds the detector's input offline on the CPU: StackedHistogram.construct (data/utils/representations.py:37-121) once per
+window of scripts/genx/preprocess_dataset.py:476-530, on timestamps its reader forced non-decreasing (:159-168) with negative polarities
+clipped to 0 (:177), downsampled by 2 with nearest-exact interpolation for Gen4 (:463-473).  Both classes here give the same uint8 frames,
+bit for bit, from device tensors:
+
+- `StackedHistogram`: the reference's class and `construct(x, y, pol, time)` signature (one window: the whole arrays, time assumed sorted).
+- `EventFrames`: the streaming front end.  One event buffer, a tensor of window ends, duration or count windows, the reader's time
+  correction with its carry kept on the device, optional downsampling by 2 -> uint8 [B, 2*bins, H', W'], the input of `RNNDetector` /
+  `YoloXDetector`.  Every per-frame value stays on the device, so a call can be captured in a graph and replayed on new events written
+  into the same buffers.
+
+There is no CPU path: CPU tensors raise the library's "no CPU fallback" error.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional, Tuple
+
+import torch
+
+from . import _lib as L
+from .functional import _need_gpu, _stream
+
+_EV_DT = {torch.int64: L.DT_I64, torch.int32: L.DT_I32, torch.int16: L.DT_I16}
+
+
+def _dtype_code(t: torch.Tensor, name: str, allowed=(torch.int64, torch.int32, torch.int16)) -> int:
+    if t.dtype not in allowed:
+        raise TypeError(f"sast_amd.events: {name} must be one of {[str(d) for d in allowed]}, got {t.dtype}")
+    return _EV_DT[t.dtype]
+
+
+def _columns(x, y, pol, time):
+    _need_gpu(x, y, pol, time)
+    cols = []
+    for t, name in ((x, "x"), (y, "y"), (pol, "pol"), (time, "time")):
+        if t.dim() != 1:
+            raise ValueError(f"sast_amd.events: {name} must be 1-D, got shape {tuple(t.shape)}")
+        cols.append(t.contiguous())
+    if not x.numel() == y.numel() == pol.numel() == time.numel():
+        raise ValueError("sast_amd.events: x, y, pol and time must hold the same number of events")
+    if len({t.device for t in cols}) != 1:
+        raise ValueError("sast_amd.events: x, y, pol and time must be on the same device")
+    codes = [_dtype_code(cols[0], "x"), _dtype_code(cols[1], "y"), _dtype_code(cols[2], "pol"),
+             _dtype_code(cols[3], "time", (torch.int64, torch.int32))]
+    return cols, codes
+
+
+def _cutoff(count_cutoff: Optional[int]) -> int:
+    # representations.py:51-56: None means 255, larger values are capped at 255
+    if count_cutoff is None:
+        return 255
+    if int(count_cutoff) < 1:
+        raise ValueError("sast_amd.events: count_cutoff must be >= 1 (or None)")
+    return min(int(count_cutoff), 255)
+
+
+class _Frames:
+    """geometry + the device workspace of sast_event_frames (zero when created, left zero by every call)"""
+
+    def __init__(self, bins: int, height: int, width: int, count_cutoff: Optional[int], fastmode: bool, downsample_by_2: bool):
+        if int(bins) < 1 or int(height) < 1 or int(width) < 1:
+            raise ValueError("sast_amd.events: bins, height and width must be >= 1")
+        self.bins, self.height, self.width = int(bins), int(height), int(width)
+        self.count_cutoff = _cutoff(count_cutoff)
+        self.fastmode = bool(fastmode)
+        self.downsample_by_2 = bool(downsample_by_2)
+        self.out_hw = (self.height // 2, self.width // 2) if self.downsample_by_2 else (self.height, self.width)
+        self._ws = {}
+
+    def get_shape(self) -> Tuple[int, int, int]:
+        return 2 * self.bins, self.out_hw[0], self.out_hw[1]
+
+    def ws_bytes(self, B: int, window_capacity: int) -> int:
+        n = int(L.lib().sast_event_frames_ws_bytes(B, self.bins, self.height, self.width, int(self.downsample_by_2), int(window_capacity)))
+        if n == 0:
+            raise ValueError(f"sast_amd.events: unsupported frame geometry (B={B}, bins={self.bins}, {self.height}x{self.width}, "
+                             f"window capacity {window_capacity}); 2*bins <= 640")
+        return n
+
+    def workspace(self, device, B: int, window_capacity: int) -> torch.Tensor:
+        # the record area comes last in the layout: a workspace made for more events per window serves fewer as well
+        need = self.ws_bytes(B, window_capacity)
+        key = (device, B)
+        ws = self._ws.get(key)
+        if ws is None or ws.numel() < need:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("sast_amd.events: one un-captured warm-up call is needed before graph capture")
+            self._ws.clear()
+            ws = self._ws[key] = torch.zeros(need, dtype=torch.uint8, device=device)
+        return ws
+
+    def launch(self, cols, codes, capacity: int, bounds: torch.Tensor, out: torch.Tensor, err: torch.Tensor, window_capacity: int,
+               clip_negative_polarity: bool):
+        B = bounds.shape[0]
+        ws = self.workspace(out.device, B, window_capacity)
+        a = L.SastEventArgs()
+        x, y, p, t = cols
+        # an empty column has no storage: any valid device pointer will do, the kernels read no event
+        a.x, a.y, a.p, a.t = (c.data_ptr() or out.data_ptr() for c in (x, y, p, t))
+        a.bounds, a.out, a.err, a.ws = bounds.data_ptr(), out.data_ptr(), err.data_ptr(), ws.data_ptr()
+        a.capacity, a.window_capacity = int(capacity), int(window_capacity)
+        a.x_dtype, a.y_dtype, a.p_dtype, a.t_dtype = codes
+        a.B, a.bins, a.height, a.width = B, self.bins, self.height, self.width
+        a.count_cutoff, a.fastmode, a.downsample_by_2 = self.count_cutoff, int(self.fastmode), int(self.downsample_by_2)
+        a.clip_negative_polarity = int(clip_negative_polarity)
+        L.check(L.lib().sast_event_frames(C.byref(a), _stream()), "event_frames")
+
+
+def _raise_on_errors(err: torch.Tensor):
+    bad, over = (int(v) for v in err.tolist())
+    if bad:
+        raise ValueError(f"sast_amd.events: {bad} invalid events (x or y outside the sensor, or a polarity outside 0..1); they were skipped")
+    if over:
+        raise ValueError(f"sast_amd.events: {over} windows hold more events than window_capacity; they were left empty")
+
+
+class StackedHistogram(_Frames):
+    """representations.py:37-121 on device tensors: `construct(x, y, pol, time)` -> uint8 [2*bins, height, width].
+
+    x, y, pol: int64 / int32 / int16; time: int64 / int32, sorted (the reference's assumption: the first and last timestamps set the
+    time bins).  Invalid events (x or y outside the sensor, pol outside 0..1, a time before time[0]), which the reference rejects with an
+    assertion or an index error, are skipped and counted; with check=True (the default) construct synchronises and raises ValueError."""
+
+    def __init__(self, bins: int, height: int, width: int, count_cutoff: Optional[int] = None, fastmode: bool = True):
+        super().__init__(bins, height, width, count_cutoff, fastmode, downsample_by_2=False)
+        self.channels = 2
+
+    @staticmethod
+    def get_torch_dtype() -> torch.dtype:
+        return torch.uint8
+
+    @property
+    def dtype(self) -> torch.dtype:
+        return torch.uint8
+
+    def construct(self, x: torch.Tensor, y: torch.Tensor, pol: torch.Tensor, time: torch.Tensor, check: bool = True) -> torch.Tensor:
+        cols, codes = _columns(x, y, pol, time)
+        dev = cols[0].device
+        n = cols[0].numel()
+        bounds = torch.tensor([[0, n]], dtype=torch.int64, device=dev)
+        err = torch.zeros(2, dtype=torch.int32, device=dev)
+        out = torch.empty((1,) + self.get_shape(), dtype=torch.uint8, device=dev)
+        self.launch(cols, codes, n, bounds, out, err, max(n, 1), clip_negative_polarity=False)
+        if check:
+            _raise_on_errors(err)
+        return out[0]
+
+
+class EventFrames(_Frames):
+    """Batched stacked-histogram frames from one event buffer (the windowing of preprocess_dataset.py:507-530).
+
+    frames = ef(x, y, p, t, ends_us, n=None) -> uint8 [B, 2*bins, H', W'] (H' = height // 2, W' = width // 2 with downsample_by_2).
+      x, y, p: int64 / int32 / int16;  t: int64 / int32;  ends_us: int64 [B] window end times (microseconds);
+      n: the number of valid events at the head of the buffers, a device int64 tensor of one element (default: the buffers' length).
+    Windows: duration_us=D -> events with ends_us[b] - D <= t <= ends_us[b];  num_events=N -> the last N events with t <= ends_us[b].
+    correct_time (default True): the reader's correction first -- t[i] = max(t[i], running max) -- with the
+      running maximum carried across calls in `t_last` (a device tensor; `reset()` sets it back to 0 for a new recording).  The buffer
+      passed in is not modified: the corrected timestamps go to an internal int64 buffer.  correct_time=False takes t as it is (int64,
+      sorted) and leaves the carry alone.  Negative polarities are clipped to 0, as the reader does.  Each call continues the
+      recording: feeding the same events again without reset() raises every timestamp to the carry (the last call's maximum).
+    window_capacity: kept events one window may hold (default: the buffers' length); a window over it is left zero and reported.
+    check=False (the default) never synchronises, so a call can be captured in a graph; errors accumulate in `err` (int32 [2]:
+      invalid events -- each counted once, among the events the windows hold --, windows over capacity) until `reset()`.  check=True clears them, synchronises after the call and raises
+      ValueError if the call met any."""
+
+    def __init__(self, height: int, width: int, bins: int = 10, count_cutoff: Optional[int] = 10, fastmode: bool = True,
+                 duration_us: Optional[int] = None, num_events: Optional[int] = None, downsample_by_2: bool = False,
+                 correct_time: bool = True, window_capacity: Optional[int] = None):
+        super().__init__(bins, height, width, count_cutoff, fastmode, downsample_by_2)
+        if (duration_us is None) == (num_events is None):
+            raise ValueError("sast_amd.events: give exactly one of duration_us and num_events")
+        if (duration_us if duration_us is not None else num_events) < (0 if duration_us is not None else 1):
+            raise ValueError("sast_amd.events: duration_us must be >= 0, num_events >= 1")
+        self.mode = L.EVENT_WINDOW_DURATION if duration_us is not None else L.EVENT_WINDOW_COUNT
+        self.value = int(duration_us if duration_us is not None else num_events)
+        self.correct_time = bool(correct_time)
+        self.window_capacity = None if window_capacity is None else int(window_capacity)
+        self.t_last: Optional[torch.Tensor] = None
+        self.err: Optional[torch.Tensor] = None
+        self._state = {}
+
+    def _buffers(self, dev, capacity: int):
+        st = self._state.get("cap")
+        if st is None or st[0] != dev or st[1] < capacity:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("sast_amd.events: one un-captured warm-up call is needed before graph capture")
+            self._state = {"cap": (dev, capacity), "t": torch.empty(max(capacity, 1), dtype=torch.int64, device=dev),
+                           "scan": torch.empty(L.EVENT_SCAN_BLOCKS + 1, dtype=torch.int64, device=dev)}
+        if self.t_last is None or self.t_last.device != dev:
+            self.t_last = torch.zeros((), dtype=torch.int64, device=dev)
+            self.err = torch.zeros(2, dtype=torch.int32, device=dev)
+        return self._state
+
+    def reset(self):
+        """a new recording: the time-correction carry back to 0, the error counters cleared"""
+        if self.t_last is not None:
+            self.t_last.zero_()
+            self.err.zero_()
+
+    def errors(self) -> Tuple[int, int]:
+        """(invalid events, windows over capacity) since the last reset() (synchronises)"""
+        return (0, 0) if self.err is None else tuple(int(v) for v in self.err.tolist())
+
+    def __call__(self, x: torch.Tensor, y: torch.Tensor, p: torch.Tensor, t: torch.Tensor, ends_us: torch.Tensor,
+                 n: Optional[torch.Tensor] = None, check: bool = False) -> torch.Tensor:
+        cols, codes = _columns(x, y, p, t)
+        _need_gpu(ends_us, n)
+        if ends_us.dim() != 1 or ends_us.dtype != torch.int64 or ends_us.numel() < 1:
+            raise ValueError("sast_amd.events: ends_us must be a 1-D int64 tensor of at least one window end")
+        dev = cols[0].device
+        cap = cols[0].numel()
+        st = self._buffers(dev, cap)
+        if n is None:
+            n = st.get("n")
+            if n is None or int(st["n_val"]) != cap:
+                if torch.cuda.is_current_stream_capturing():
+                    raise RuntimeError("sast_amd.events: pass n (a device tensor) when capturing, or warm up with the same buffer length")
+                n = st["n"] = torch.full((1,), cap, dtype=torch.int64, device=dev)
+                st["n_val"] = cap
+        elif n.dtype != torch.int64 or n.numel() != 1:
+            raise ValueError("sast_amd.events: n must be a one-element int64 device tensor")
+        if check:
+            self.err.zero_()
+        B = ends_us.numel()
+        wcap = self.window_capacity if self.window_capacity is not None else max(cap, 1)
+        if self.correct_time:
+            tc = st["t"]
+            L.check(L.lib().sast_event_correct_time(cols[3].data_ptr() or tc.data_ptr(), codes[3], n.data_ptr(), cap, tc.data_ptr(),
+                                                    self.t_last.data_ptr(), st["scan"].data_ptr(), _stream()), "event_correct_time")
+            cols = cols[:3] + [tc[:max(cap, 1)]]
+            codes = codes[:3] + [L.DT_I64]
+        elif cols[3].dtype != torch.int64:
+            raise TypeError("sast_amd.events: correct_time=False needs int64 timestamps")
+        bounds = torch.empty(B, 2, dtype=torch.int64, device=dev)
+        L.check(L.lib().sast_event_window_bounds(cols[3].data_ptr() or st["t"].data_ptr(), n.data_ptr(), cap, ends_us.contiguous().data_ptr(),
+                                                 B, self.mode, self.value, bounds.data_ptr(), _stream()), "event_window_bounds")
+        out = torch.empty((B,) + self.get_shape(), dtype=torch.uint8, device=dev)
+        self.launch(cols, codes, cap, bounds, out, self.err, wcap, clip_negative_polarity=True)
+        self.last_bounds = bounds
+        if check:
+            _raise_on_errors(self.err)
+        return out
