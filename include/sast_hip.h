@@ -457,6 +457,33 @@ typedef struct SastEventArgs {
 size_t sast_event_frames_ws_bytes(int B, int bins, int height, int width, int downsample_by_2, int64_t window_capacity); /* 0: unsupported */
 int sast_event_frames(const SastEventArgs* a, sast_stream_t stream);
 
+/* ---- spatial augmentation of event frames and box labels (csrc/k_augment.hip).  The reference augments on the CPU in its data-loader
+ * workers: RandomSpatialAugmentorGenX.__call__ (data/utils/augmentor.py:347-364) -- horizontal flip, then zoom-in (:203-222) or zoom-out
+ * (:134-153) -- with the label transforms of ObjectLabels (data/genx_utils/labels.py:255-339).  Both calls read the per-sample
+ * parameters from DEVICE memory: int32 [B][SAST_AUGMENT_PARAM_WORDS], frame n uses sample n % B (frames are [T, B, ...]), so a captured
+ * graph is replayed with new parameters by rewriting that tensor.  Words of one sample:
+ *   0 flip (0 / 1)   1 mode (SAST_AUGMENT_NONE / ZOOM_IN / ZOOM_OUT)   2 x0   3 y0   4 window height   5 window width   6, 7 reserved
+ *   8..11  fp32 bits: zoom-in clamp bounds of the labels  x lo, x hi, y lo, y hi  (z_x0, z_x1 - 1, z_y0, z_y1 - 1 of labels.py:272-281)
+ *   12..14 fp32 bits: the multiplier of scale_ and its clamps  s, s * width' - 1, s * height' - 1  (labels.py:323-327)   15 reserved
+ * The host computes 8..14 in double as the reference's Python does and rounds each to fp32 once; the kernels repeat the reference's
+ * single fp32 operations in its order, so frames are equal byte for byte and box coordinates bit for bit.  The caller validates the
+ * parameters (zoom-in: 0 <= x0 < W, 0 <= y0 < H;  zoom-out: x0 + window width <= W, y0 + window height <= H;  windows >= 1); the
+ * kernels clamp every index they form all the same. */
+#define SAST_AUGMENT_PARAM_WORDS 16
+enum { SAST_AUGMENT_NONE = 0, SAST_AUGMENT_ZOOM_IN = 1, SAST_AUGMENT_ZOOM_OUT = 2 };
+
+/* in, out: uint8 [N, C, H, W], distinct buffers;  H, W <= 4096, N, C <= 65535.  One launch, one pass: out[n, c, y, x] =
+ * in[n, c, sy(y), W - 1 - sx(x)] (sx(x) without flip), zero outside the zoom-out window (written by the same kernel).  The source index
+ * is ATen's nearest-exact one in fp32: min(int(floorf((d + 0.5f) * (float(in) / float(out)))), in - 1).  W a multiple of 16 with both
+ * bases 16-byte aligned takes the 16-byte load / store path, anything else a byte path with the same result. */
+int sast_augment_frames(const uint8_t* in, uint8_t* out, const int32_t* params, int N, int B, int C, int H, int W, sast_stream_t stream);
+/* labels: fp32 [N, M, 7] rows (t, x, y, w, h, class_id, class_confidence) (labels.py:13-21), counts: int32 [N] valid rows at the head of
+ * each frame (0: the reference's None).  out / counts_out: the same layout, the rows that survive remove_flat_labels_ compacted to the
+ * front in their order, the rest zero.  yolox (may be NULL): fp32 [N, M, 5] = (class_id, x + 0.5 w, y + 0.5 h, w, h) of the same rows
+ * (labels.py:341-355), zero after the count.  W: the frame width (flip_lr_).  out and counts_out must not alias the inputs. */
+int sast_augment_labels(const float* labels, const int32_t* counts, const int32_t* params, int N, int B, int M, int W, float* out,
+                        int32_t* counts_out, float* yolox, sast_stream_t stream);
+
 /* ---- tuning knobs.  Every SAST_* environment variable the library reads (tile / split / launch-shape choices, all defaulting to the
  * measured-best setting: DESIGN.md section 7) goes through one registry: the value is read from the environment at first use and cached;
  * sast_config_reload() makes every call site re-read its knob at its next use (a host that sets os.environ inside the process calls

@@ -21,6 +21,8 @@ F32 = C.c_float
 DT_F32, DT_I32, DT_U8, DT_I64, DT_I16 = 0, 1, 2, 3, 4
 EVENT_WINDOW_DURATION, EVENT_WINDOW_COUNT = 0, 1
 EVENT_SCAN_BLOCKS = 512   # SAST_EVENT_SCAN_BLOCKS
+AUGMENT_PARAM_WORDS = 16  # SAST_AUGMENT_PARAM_WORDS
+AUGMENT_NONE, AUGMENT_ZOOM_IN, AUGMENT_ZOOM_OUT = 0, 1, 2
 
 
 def _struct(name, spec):
@@ -148,6 +150,8 @@ _SIGNATURES = {
     "sast_event_window_bounds": (C.c_int, [P, P, C.c_int64, P, C.c_int, C.c_int, C.c_int64, P, P]),
     "sast_event_frames_ws_bytes": (C.c_size_t, [C.c_int] * 5 + [C.c_int64]),
     "sast_event_frames": (C.c_int, [C.POINTER(SastEventArgs), P]),
+    "sast_augment_frames": (C.c_int, [P, P, P] + [C.c_int] * 5 + [P]),
+    "sast_augment_labels": (C.c_int, [P, P, P] + [C.c_int] * 4 + [P, P, P, P]),
 }
 
 _lib = None
