@@ -97,6 +97,8 @@ typedef struct SastDownArgs {
   int32_t no_overlap;    /* 0: downsample_cfg.overlap True (every shipped config): k = 2*factor-1, replicate padding factor-1.
                             1: overlap False (ops.py:74-76): k = factor, no padding; w is [Cout][factor][factor][Cin] */
 } SastDownArgs;
+/* Ho = H / factor, Wo = W / factor.  The overlapping form takes H, W that are multiples of the factor only (SAST_EINVAL otherwise: the
+ * conv would have ceil(H / factor) rows and a replicate clamp at the bottom / right edge); no_overlap floors, as nn.Conv2d does. */
 int sast_downsample_ln_fwd(const SastDownArgs* a, sast_stream_t stream);
 int sast_downsample_ln_bwd(const SastDownArgs* a, sast_stream_t stream);
 

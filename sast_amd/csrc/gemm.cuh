@@ -1340,7 +1340,7 @@ struct ConvGeom {
   int B, H, W, Cin, Ho, Wo, KH, KW, stride, pad, replicate, ldx;  // ldx: channel stride of the input rows
   int stride_shift, kw_mul;                                        // stride == 1 << stride_shift; kw_mul = small_div_mul(KW)
   unsigned wo_mul, ho_mul;   // n / Wo == umulhi(n, wo_mul) for every row index n of the problem (0: use the division); same for Ho
-  unsigned cin_mul;          // r / Cin == umulhi(r, cin_mul) for reduce indices r < KH*KW*Cin (never 0: geom_of checks)
+  unsigned cin_mul;          // r / Cin == umulhi(r, cin_mul) for reduce indices r < KH*KW*Cin (never 0 in a launch: conv_gemm, the stem's uint8 entry and conv_bwd_pair refuse it)
   unsigned w_mul, h_mul;     // the same for INPUT pixel indices n < B*H*W: n / W, (n / W) / H  (0: plain division)
 };
 // (fast_div / div_mul_of: common.cuh)

@@ -425,6 +425,7 @@ inline ConvGeom geom_of(int B, int H, int W, int Cin, int k, int stride, int pad
 // forward implicit GEMM of a k x k convolution: the uniform-tap loader whenever a 16-wide k-tile lies inside one tap (gemm.cuh: LdIm2colU)
 template <class LB, class EP>
 int conv_gemm(const float* x, const ConvGeom& g, const LB& lb, const EP& ep, int M, int NJ, int K, hipStream_t st) {
+  if (!g.cin_mul) return SAST_EINVAL;     // the loaders decode (tap, channel) with this multiplier only (gemm.cuh: split_tap)
   if (g.Cin % 16 == 0) return gemm_auto(LdIm2colU{{x, g}}, lb, ep, M, NJ, K, st);
   return gemm_auto(LdIm2col{x, g}, lb, ep, M, NJ, K, st);
 }
@@ -488,6 +489,14 @@ int conv_bwd_pair(const float* dconv, const float* x, const ConvGeom& g, int Cou
                    nullptr, st, pair_tn_blocks_conv());
 }
 
+// sizes the downsample conv accepts.  The overlapping form (k = 2f-1, replicate padding f-1) has ceil(H / f) output rows: at an H or W
+// that is not a multiple of the factor that is more rows than the H / f the callers size their buffers for, and the replicate clamp
+// would also act at the bottom / right edge, which LdConvDx / LdConvDxP do not fold.  The reference only uses multiples: refused.
+bool down_size_ok(const SastDownArgs* a) {
+  if (a->factor < 1 || a->B < 1 || a->H < a->factor || a->W < a->factor) return false;
+  return a->no_overlap || (a->H % a->factor == 0 && a->W % a->factor == 0);
+}
+
 }  // namespace
 
 extern "C" {
@@ -496,14 +505,14 @@ extern "C" {
 int sast_downsample_ln_fwd(const SastDownArgs* a, sast_stream_t stream) { SAST_ENTRY();
   hipStream_t st = (hipStream_t)stream;
   ProfScope ps_("down_fwd", a ? a->Cout : 0, a ? a->B * a->H * a->W : 0, st);
-  if (!a || a->Cin % 4 || a->Cout % 4) return SAST_EINVAL;
+  if (!a || a->Cin % 4 || a->Cout % 4 || !down_size_ok(a)) return SAST_EINVAL;
   // ops.py:70-76: overlap (default) k = 2f-1 with replicate padding f-1; no_overlap: k = f, no padding (non-overlapping patches)
   const int k = a->no_overlap ? a->factor : 2 * a->factor - 1;
   const ConvGeom g = geom_of(a->B, a->H, a->W, a->Cin, k, a->factor, a->no_overlap ? 0 : a->factor - 1, 1, a->Cin);
   const int M = a->B * g.Ho * g.Wo, K = k * k * a->Cin;
   int rc;
   if (a->x_dtype == SAST_DT_U8)       // the stem on the stored uint8 event tensor (NHWC bytes, written by sast_input_prep_u8)
-    rc = gemm_auto(LdIm2colQ8{(const unsigned char*)a->x, g}, LdWeightNT{a->w, K, 0}, EpStore{a->conv_out, a->Cout, nullptr}, M, a->Cout, K, st);
+    rc = !g.cin_mul ? SAST_EINVAL : gemm_auto(LdIm2colQ8{(const unsigned char*)a->x, g}, LdWeightNT{a->w, K, 0}, EpStore{a->conv_out, a->Cout, nullptr}, M, a->Cout, K, st);
   else if (a->x_dtype != SAST_DT_F32) return SAST_EINVAL;
   else rc = conv_gemm(a->x, g, LdWeightNT{a->w, K, 0}, EpStore{a->conv_out, a->Cout, nullptr}, M, a->Cout, K, st);
   if (rc) return rc;
@@ -513,6 +522,7 @@ int sast_downsample_ln_fwd(const SastDownArgs* a, sast_stream_t stream) { SAST_E
 int sast_downsample_ln_bwd(const SastDownArgs* a, sast_stream_t stream) { SAST_ENTRY();
   hipStream_t st = (hipStream_t)stream;
   ProfScope ps_("down_bwd", a->Cout, a->B * a->H * a->W, st);
+  if (a->Cin % 4 || a->Cout % 4 || !down_size_ok(a) || (a->x_dtype == SAST_DT_U8 && a->dx)) return SAST_EINVAL;   // (an integer input has no gradient)
   const int k = a->no_overlap ? a->factor : 2 * a->factor - 1;
   const ConvGeom g = geom_of(a->B, a->H, a->W, a->Cin, k, a->factor, a->no_overlap ? 0 : a->factor - 1, 1, a->Cin);
   const int M = a->B * g.Ho * g.Wo, K = k * k * a->Cin;
@@ -520,7 +530,7 @@ int sast_downsample_ln_bwd(const SastDownArgs* a, sast_stream_t stream) { SAST_E
   int rc = ln_bwd_launch(a->conv_out, a->dy, a->ln_w, a->mean, a->rstd, dconv, a->d_ln_w, a->d_ln_b, M, a->Cout, st);
   if (rc) return rc;
   if (a->x_dtype == SAST_DT_U8) {     // an integer input has no gradient: the weight gradient only
-    if (a->dx) return SAST_EINVAL;
+    if (a->dx || !g.cin_mul) return SAST_EINVAL;
     return gemm_tn(LdRowsT{dconv, a->Cout}, LdIm2colTQ8{(const unsigned char*)a->x, g}, a->dw, K, a->Cout, K, M, st);
   }
   if (a->x_dtype != SAST_DT_F32) return SAST_EINVAL;

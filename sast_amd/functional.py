@@ -378,6 +378,27 @@ def add_pos_embedding(x: torch.Tensor, table: torch.Tensor) -> torch.Tensor:
 
 
 # ---------------------------------------------------------------------------------------------- a2
+def downsample_out_hw(H: int, W: int, factor: int, k: int) -> Tuple[int, int]:
+    """(Ho, Wo) of the factor-`factor` downsampling conv with a k x k kernel (ops.py:70-76), the one place this size is computed.
+    No overlap (k = f, no padding): floor(H / f), what `nn.Conv2d` gives; the rows / columns of a last partial patch are never read.
+    Overlap (k = 2f-1, replicate padding f-1): H / f -- for H, W that are multiples of the factor only.  The conv would give
+    ceil(H / f) at other sizes, where the clamp of the replicate padding also acts at the bottom / right edge; the backward-data loaders
+    fold it at row / column 0 only, and the reference model never gets there (its partition reshape needs multiples), so such a size is
+    refused (RuntimeError) here and by the library (SAST_EINVAL)."""
+    H, W, factor, k = int(H), int(W), int(factor), int(k)
+    if factor < 1 or k not in (factor, 2 * factor - 1):
+        raise RuntimeError(f"sast_amd: a factor-{factor} downsampling conv has a {2 * factor - 1}x{2 * factor - 1} (overlap) or "
+                           f"{factor}x{factor} (no overlap) kernel, not {k}x{k}")
+    if k == factor:
+        if H < factor or W < factor:
+            raise RuntimeError(f"sast_amd: downsample_ln: the map H = {H}, W = {W} is smaller than the factor-{factor} patch")
+        return H // factor, W // factor
+    if H % factor or W % factor or H < factor or W < factor:
+        raise RuntimeError(f"sast_amd: downsample_ln: the overlapping factor-{factor} conv needs H and W that are multiples of {factor}, "
+                           f"got H = {H}, W = {W} (factor {factor})")
+    return H // factor, W // factor
+
+
 class _DownsampleLN(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, ln_w, ln_b, pe, factor):
@@ -392,7 +413,7 @@ class _DownsampleLN(torch.autograd.Function):
             raise RuntimeError(f"sast_amd: a factor-{factor} downsampling conv has a {2 * factor - 1}x{2 * factor - 1} (overlap) or "
                                f"{factor}x{factor} (no overlap) kernel, not {tuple(w.shape[-2:])}")
         no_overlap = int(k == factor)
-        Ho, Wo = H // factor, W // factor
+        Ho, Wo = downsample_out_hw(H, W, factor, k)
         M = B * Ho * Wo
         dev = x.device
         conv_out = torch.empty(M, Cout, device=dev)
@@ -427,6 +448,7 @@ class _DownsampleLN(torch.autograd.Function):
 
 
 def downsample_ln(x_nhwc, w, ln_w, ln_b, pe, factor):
+    downsample_out_hw(x_nhwc.shape[1], x_nhwc.shape[2], factor, w.shape[-1])     # refuses a bad size before anything touches the library
     return _DownsampleLN.apply(x_nhwc, w, ln_w, ln_b, pe, factor)
 
 
