@@ -50,6 +50,16 @@ int sast_nzratio_padded(const void* x, int dtype, int B, int Cin, int H, int W, 
  * workgroup finishes the ratios and clears it), so a caller allocates and clears it once. */
 int sast_input_prep(const void* x, int dtype, int B, int C, int H, int W, int Hp, int Wp, int32_t* ws, float* r, float* y,
                     sast_stream_t stream);
+/* the same, and additionally *nonexact (one word that belongs to THIS call's y, allocated with it by the caller) = 0 iff every value
+ * of y is exactly one bf16 (low 16 bits of the fp32 pattern zero: stacked-histogram counts, every integer of magnitude <= 256), else
+ * non-zero.  Handed to the stem conv (SastDownArgs.x_nonexact) it lets the stem GEMMs skip the three product terms of the operand's
+ * zero bf16 planes; evaluated on the device at every call, also on every replay of a captured graph.  y must not be written after the call while
+ * the word is in use (a stale 0 drops the lower planes: ~2^-8 relative error).  +-Inf and the default quiet NaN also have zero low
+ * bits: such an input counts as exact, and an Inf then gives Inf * w where the six-term split gives NaN (Inf - Inf) -- not
+ * reachable from event counts.  ws: int32[B*4*C + 2] here (one
+ * more scratch word than sast_input_prep, which keeps its size), zero on entry and left zero on exit. */
+int sast_input_prep_flag(const void* x, int dtype, int B, int C, int H, int W, int Hp, int Wp, int32_t* ws, float* r, float* y,
+                         uint32_t* nonexact, sast_stream_t stream);
 /* the same for the event tensor as the dataset stores it (uint8 counts, data/genx_utils/sequence_base.py:88-98): y keeps the BYTES,
  * (B,Hp,Wp,C) uint8 NHWC, zero padded -- a quarter of the traffic of the fp32 copy.  The stem conv reads it directly
  * (SastDownArgs.x_dtype = SAST_DT_U8); the `.float()` of modules/detection.py:143-144 / sast_rnn.py:153 happens in its loaders. */
@@ -96,6 +106,10 @@ typedef struct SastDownArgs {
                             copy of the input never exists (modules/detection.py:143-144 does `.float()` first) */
   int32_t no_overlap;    /* 0: downsample_cfg.overlap True (every shipped config): k = 2*factor-1, replicate padding factor-1.
                             1: overlap False (ops.py:74-76): k = factor, no padding; w is [Cout][factor][factor][Cin] */
+  const uint32_t* x_nonexact; /* fwd + bwd, optional (stem, x_dtype SAST_DT_F32, dx == NULL in the backward): the word sast_input_prep_flag
+                            wrote for x.  While it reads 0 the conv and its weight gradient issue only the three bf16 product terms of
+                            x's top plane (the other three multiply zeros: same results).  NULL = nothing known about x: all six terms.
+                            A SAST_DT_U8 input is exact by type and needs no word.  SAST_STEM_EXACT_BF16=0 turns both off. */
 } SastDownArgs;
 /* Ho = H / factor, Wo = W / factor.  The overlapping form takes H, W that are multiples of the factor only (SAST_EINVAL otherwise: the
  * conv would have ceil(H / factor) rows and a replicate clamp at the bottom / right edge); no_overlap floors, as nn.Conv2d does. */
@@ -207,7 +221,15 @@ typedef struct SastLstmArgs {
   const float* x; const float* h0; const float* c0;   /* h0/c0 NULL = zero state */
   const float* w; const float* b;                      /* conv1x1 [4C,2C], [4C] */
   float* h1; float* c1;
-  float* gates;          /* [B*L,4C] saved: sigmoid(f,i,o), tanh(g) */
+  float* gates;          /* [B*L,4C] saved: sigmoid(f,i,o), tanh(g).  c0 == NULL (and SAST_LSTM_SKIP_DEAD_GATE, default 1): the forget gate
+                            multiplies a zero cell state, so the forward runs the GEMM over the three live gates (weight rows [C, 4C))
+                            and gates[:, 0:C] is UNDEFINED afterwards; a NaN / Inf that would enter c1 only through the forget gate's
+                            pre-activation no longer does.  The backward then works on the gate rows [C, 4C) alone: dw[0:C, :] and
+                            db[0:C] are left as they are (the four-gate form adds exact zeros), and a non-NULL dc0 is refused
+                            (SAST_EINVAL: dc0 = dc * f needs the f that was not saved).  With c0 != NULL nothing changes.  dx / dh0
+                            equal the four-gate form's bit for bit when C is a multiple of 64 (128 for the 8-k-group tile), else
+                            up to summation order.  The knob
+                            must not change between a forward and its backward. */
   /* backward */
   const float* dh1; const float* dc1;                  /* dc1 may be NULL */
   float* dx; float* dh0; float* dc0;                   /* dh0/dc0 may be NULL */

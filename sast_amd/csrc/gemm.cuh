@@ -142,10 +142,29 @@ __device__ __forceinline__ void store_split3_probe(float* dst, int plane_floats,
   *reinterpret_cast<u32x2*>(dst + 2 * plane_floats) = z;
 }
 
+// an operand whose values are EXACTLY one bf16 each (loader trait EXACT_BF16: the stem's event tensor, small integers): its middle and
+// bottom planes are zero, so only the top plane is staged -- the packed high halves, no subtract / mask rounds
+__device__ __forceinline__ void store_hi(float* dst, float4 v) {
+  const u32x2 h = {__builtin_amdgcn_perm(__float_as_uint(v.y), __float_as_uint(v.x), 0x07060302u),
+                   __builtin_amdgcn_perm(__float_as_uint(v.w), __float_as_uint(v.z), 0x07060302u)};
+  *reinterpret_cast<u32x2*>(dst) = h;
+}
+__device__ __forceinline__ bf16x8 split_hi(const float (&x)[8]) {
+  u32x4 ph;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) ph[i] = __builtin_amdgcn_perm(__float_as_uint(x[2 * i + 1]), __float_as_uint(x[2 * i]), 0x07060302u);
+  return __builtin_bit_cast(bf16x8, ph);
+}
+// which of the six product terms (l.h, h.l, m.m, m.h, h.m, h.h, in issue order) survive when the A / B operand has a top plane only
+__device__ __forceinline__ constexpr bool term_live(int term, bool exact_a, bool exact_b) {
+  return !(exact_a && (term == 0 || term == 2 || term == 3)) && !(exact_b && (term == 1 || term == 2 || term == 4));
+}
+
 // a lane's MFMA operand (8 consecutive k of index c0 + lane % 32, k = 8 * (lane / 32) + j) from the three [k][W] bf16 planes of an
 // index-contiguous presplit operand (OperandPresplitIC): per plane two transposing reads of a 4(k) x 16(index) block each
 using bf16x4 = __attribute__((ext_vector_type(4))) __bf16;
-template <int W>
+// (NP = 1: the top plane only, for an exact-bf16 operand; the other two members repeat it and are never used)
+template <int W, int NP = 3>
 __device__ __forceinline__ Split3 psi_read(const float* planes, int c0, int lane) {
   using lds_bf16x4 = __attribute__((address_space(3))) bf16x4;
   const int i = lane & 15;
@@ -154,13 +173,14 @@ __device__ __forceinline__ Split3 psi_read(const float* planes, int c0, int lane
   const char* base = reinterpret_cast<const char*>(planes) + k * (2 * W) + gran * 8;
   bf16x8 r[3];
 #pragma unroll
-  for (int p = 0; p < 3; ++p) {
+  for (int p = 0; p < NP; ++p) {
     const char* q = base + p * (32 * W);                                   // plane = 16 rows x 2W bytes
     const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(q));
     const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(q + 4 * (2 * W)));
     r[p] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
   }
-  return Split3{r[0], r[1], r[2]};
+  if constexpr (NP == 1) return Split3{r[0], r[0], r[0]};
+  else return Split3{r[0], r[1], r[2]};
 }
 
 // PF: k-tiles kept in flight in registers per k-group (global-load latency under load is ~2-3 us on MI355X, one k-tile of
@@ -249,6 +269,13 @@ template <class EP> inline int ep_side_blocks(const EP& ep) {
 }
 template <class L, class = void> struct LoaderUniformTile : std::false_type {};
 template <class L> struct LoaderUniformTile<L, std::void_t<decltype(L::UNIFORM_TILE)>> : std::bool_constant<L::UNIFORM_TILE> {};
+// a loader may declare its operand exact in bf16 (EXACT_BF16 = true, `bool exact() const` evaluated once per workgroup, block-uniform):
+// the kernel then carries a second k-loop that stages one plane of that operand and issues the three MFMAs that involve its top plane
+template <class L, class = void> struct LoaderExactBf16 : std::false_type {};
+template <class L> struct LoaderExactBf16<L, std::void_t<decltype(L::EXACT_BF16)>> : std::bool_constant<L::EXACT_BF16> {};
+// EXACT_BF16_ALWAYS = true: exact by type (uint8 counts): the kernel carries the three-term loop ONLY, no word is read
+template <class L, class = void> struct LoaderExactAlways : std::false_type {};
+template <class L> struct LoaderExactAlways<L, std::void_t<decltype(L::EXACT_BF16_ALWAYS)>> : std::bool_constant<L::EXACT_BF16_ALWAYS> {};
 template <class EP, class = void> struct EpHasStats : std::false_type {};
 template <class EP> struct EpHasStats<EP, std::void_t<decltype(EP::COLSTATS)>> : std::bool_constant<EP::COLSTATS> {};
 
@@ -258,10 +285,10 @@ template <class EP> struct EpHasStats<EP, std::void_t<decltype(EP::COLSTATS)>> :
 // operand halves; measured, the split is 0.7 ms of the 5.3 ms step).  Plane layout [row][BK] bf16 (32-byte rows with a chunk swizzle, ps_chunk_swizzle: ds_write_b64 of a
 // thread's 4 k-values, one conflict-free ds_read_b128 per plane = a lane's 8 k-values as one MFMA operand).  Index-contiguous (IC)
 // operands keep the fp32 [k][row] layout and are split after the read.  Not for 8-way k-split tiles, nor where the planes (24 instead of
-// 20 floats per row) would push a workgroup beyond 80 KB of LDS, nor for the 4-gate LSTM tiles (one wave reads all 128 B rows there: nothing
-// is shared, and the larger planes made the stage-1/2 LSTM GEMMs 25 % slower).
+// 20 floats per row) would push a workgroup beyond 80 KB of LDS, nor for the LSTM tiles (G = 4, and G = 3 of the zero-cell-state form: one wave reads all
+// 128 / 96 B rows there: nothing is shared, and the larger planes made the stage-1/2 LSTM GEMMs 25 % slower).
 template <class T, class L>
-struct OperandPresplitWanted { static constexpr bool value = SAST_MFMA_SPLIT3 && !SAST_MFMA_BF16 && SAST_PRESPLIT_RC && L::RC && (T::BK == 16 || T::BK == 32) && T::KS <= 4 && T::G < 4; };
+struct OperandPresplitWanted { static constexpr bool value = SAST_MFMA_SPLIT3 && !SAST_MFMA_BF16 && SAST_PRESPLIT_RC && L::RC && (T::BK == 16 || T::BK == 32) && T::KS <= 4 && T::G < 3; };
 constexpr int PS_ROW_FLOATS = 3 * 16 / 2;         // 3 planes x 16 bf16 per row, in floats (24)
 // unpadded 32-byte plane rows: the 16-byte chunk (k 0-7 | k 8-15) of a row is XOR-ed with bit 3 of the row index.  ds_read_b128 serves
 // the lane groups {0-3,12-15,20-27} / {4-11,16-19,28-31}: with the swizzle their 16 chunks are 16 different 16-byte bank groups
@@ -276,7 +303,7 @@ constexpr int PS_MAX_FLOATS = 20480;              // a workgroup's LDS with pres
 // banks, so the granule index is XOR-ed with a function of k that moves the 4 rows of a block to 4 different 64-byte bank groups.
 template <class T, class L, int W>
 struct OperandPresplitIC {
-  static constexpr bool value = SAST_MFMA_SPLIT3 && !SAST_MFMA_BF16 && SAST_PRESPLIT_IC && !L::RC && (T::BK == 16 || T::BK == 32) && T::KS <= 4 && T::G < 4 &&
+  static constexpr bool value = SAST_MFMA_SPLIT3 && !SAST_MFMA_BF16 && SAST_PRESPLIT_IC && !L::RC && (T::BK == 16 || T::BK == 32) && T::KS <= 4 && T::G < 3 &&
                                 (W == 32 || W == 64 || W == 128);
 };
 // granule (8 bytes = 4 index values) XOR of row k for a plane row of W values
@@ -446,7 +473,15 @@ __device__ __forceinline__ void gemm_body(const LA& la, const LB& lb, const EP& 
 #pragma unroll
   for (int it = 0; it < A_PER; ++it) csacc[it] = zero4();
 
-  auto lstore = [&](int buf, int set) {
+  // XA / XB: the operand may be exact in bf16 (at most one of the two); `ex` (std::bool_constant) selects the k-loop body
+  constexpr bool XA = SAST_MFMA_SPLIT3 && !SAST_MFMA_BF16 && LoaderExactBf16<LA>::value;
+  constexpr bool XB = SAST_MFMA_SPLIT3 && !SAST_MFMA_BF16 && LoaderExactBf16<LB>::value;
+  static_assert(!(XA && XB), "one exact-bf16 operand per GEMM");
+  // the three-term body accumulates into accs[0] alone: with two accumulator chains the six-term body would round differently
+  static_assert(!(XA || XB) || SAST_SINGLE_TILE_ACCS == 1, "exact-bf16 loaders: three-term == six-term bit for bit needs SAST_SINGLE_TILE_ACCS == 1");
+  constexpr bool XALWAYS = (XA && LoaderExactAlways<LA>::value) || (XB && LoaderExactAlways<LB>::value);
+  auto lstore = [&](int buf, int set, auto ex) {
+    constexpr bool EA = decltype(ex)::value && XA, EB = decltype(ex)::value && XB;
     float* as = As + buf * A_STAGE;
     float* bs = Bs + buf * B_STAGE;
 #pragma unroll
@@ -456,13 +491,15 @@ __device__ __forceinline__ void gemm_body(const LA& la, const LB& lb, const EP& 
         if constexpr (SPLIT && !LA::RC) {
           if (do_colsum) { csacc[it].x += v.x; csacc[it].y += v.y; csacc[it].z += v.z; csacc[it].w += v.w; }
         }
-        if constexpr (PSA) store_split3(as + la_off[it], BM * 8, v);
+        if constexpr (PSA && EA) store_hi(as + la_off[it], v);
+        else if constexpr (PSA) store_split3(as + la_off[it], BM * 8, v);
         else st4(as + la_off[it], v);
       }
 #pragma unroll
     for (int it = 0; it < B_PER; ++it)
       if (B_SLOTS % NT == 0 || tid + it * NT < B_SLOTS) {
-        if constexpr (PSB && SAST_PROBE_B_SPLIT_FREE && !SPLIT) store_split3_probe(bs + lb_off[it], BN * 8, lb.finish(rb[set][it], ab[set][it], ob[set][it]));
+        if constexpr (PSB && EB) store_hi(bs + lb_off[it], lb.finish(rb[set][it], ab[set][it], ob[set][it]));
+        else if constexpr (PSB && SAST_PROBE_B_SPLIT_FREE && !SPLIT) store_split3_probe(bs + lb_off[it], BN * 8, lb.finish(rb[set][it], ab[set][it], ob[set][it]));
         else if constexpr (PSB) store_split3(bs + lb_off[it], BN * 8, lb.finish(rb[set][it], ab[set][it], ob[set][it]));
         else st4(bs + lb_off[it], lb.finish(rb[set][it], ab[set][it], ob[set][it]));
       }
@@ -497,7 +534,8 @@ __device__ __forceinline__ void gemm_body(const LA& la, const LB& lb, const EP& 
 #pragma unroll
   for (int a = 0; a < T::TM; ++a) csum[a] = 0.f;
 
-  auto compute = [&](int buf) {
+  auto compute = [&](int buf, auto ex) {
+    constexpr bool EA = decltype(ex)::value && XA, EB = decltype(ex)::value && XB;
     const float* as = As + buf * A_STAGE;
     const float* bs = Bs + buf * B_STAGE;
     const int l31 = lane & 31, hf = lane >> 5;
@@ -507,18 +545,22 @@ __device__ __forceinline__ void gemm_body(const LA& la, const LB& lb, const EP& 
         Split3 sa[T::TM], sb[T::TN];
 #pragma unroll
         for (int t = 0; t < T::TM; ++t) {
-          if constexpr (!LA::RC) sa[t] = psi_read<BM>(as + u * SUB_A, wm * T::WTM + t * 32, lane);
+          if constexpr (!LA::RC) sa[t] = psi_read<BM, EA ? 1 : 3>(as + u * SUB_A, wm * T::WTM + t * 32, lane);
           else {
             const float* p = as + u * SUB_A + (wm * T::WTM + t * 32 + l31) * 8 + (hf ^ ps_chunk_swizzle(l31)) * 4;
-            sa[t] = Split3{__builtin_bit_cast(bf16x8, ld4(p)), __builtin_bit_cast(bf16x8, ld4(p + BM * 8)), __builtin_bit_cast(bf16x8, ld4(p + 2 * BM * 8))};
+            const bf16x8 h = __builtin_bit_cast(bf16x8, ld4(p));
+            if constexpr (EA) sa[t] = Split3{h, h, h};
+            else sa[t] = Split3{h, __builtin_bit_cast(bf16x8, ld4(p + BM * 8)), __builtin_bit_cast(bf16x8, ld4(p + 2 * BM * 8))};
           }
         }
 #pragma unroll
         for (int t = 0; t < T::TN; ++t) {
-          if constexpr (!LB::RC) sb[t] = psi_read<BN>(bs + u * SUB_B, wn * T::WTN + t * 32, lane);
+          if constexpr (!LB::RC) sb[t] = psi_read<BN, EB ? 1 : 3>(bs + u * SUB_B, wn * T::WTN + t * 32, lane);
           else {
             const float* p = bs + u * SUB_B + (wn * T::WTN + t * 32 + l31) * 8 + (hf ^ ps_chunk_swizzle(l31)) * 4;
-            sb[t] = Split3{__builtin_bit_cast(bf16x8, ld4(p)), __builtin_bit_cast(bf16x8, ld4(p + BN * 8)), __builtin_bit_cast(bf16x8, ld4(p + 2 * BN * 8))};
+            const bf16x8 h = __builtin_bit_cast(bf16x8, ld4(p));
+            if constexpr (EB) sb[t] = Split3{h, h, h};
+            else sb[t] = Split3{h, __builtin_bit_cast(bf16x8, ld4(p + BN * 8)), __builtin_bit_cast(bf16x8, ld4(p + 2 * BN * 8))};
           }
         }
 #pragma unroll
@@ -527,6 +569,7 @@ __device__ __forceinline__ void gemm_body(const LA& la, const LB& lb, const EP& 
           for (int ta = 0; ta < T::TM; ++ta)
 #pragma unroll
             for (int tb = 0; tb < T::TN; ++tb) {
+              if (!term_live(term, EA, EB)) continue;     // (an exact-bf16 operand: the terms of its zero planes are not issued; same order)
               const bf16x8 x = term == 0 ? sa[ta].l : (term == 2 || term == 3) ? sa[ta].m : sa[ta].h;      // l.h, h.l, m.m, m.h, h.m, h.h: smallest terms first
               const bf16x8 y = term == 1 ? sb[tb].l : (term == 2 || term == 4) ? sb[tb].m : sb[tb].h;
               accs[0][ta][tb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x, y, accs[0][ta][tb], 0, 0, 0);
@@ -539,10 +582,12 @@ __device__ __forceinline__ void gemm_body(const LA& la, const LB& lb, const EP& 
 #pragma unroll
     for (int t = 0; t < T::TM; ++t) {
       if constexpr (PSA && !LA::RC) {
-        sa[t] = psi_read<BM>(as, wm * T::WTM + t * 32, lane);
+        sa[t] = psi_read<BM, EA ? 1 : 3>(as, wm * T::WTM + t * 32, lane);
       } else if constexpr (PSA) {
         const float* p = as + (wm * T::WTM + t * 32 + l31) * 8 + (hf ^ ps_chunk_swizzle(l31)) * 4;       // 16 bytes = this lane's 8 k-values of one plane
-        sa[t] = Split3{__builtin_bit_cast(bf16x8, ld4(p)), __builtin_bit_cast(bf16x8, ld4(p + BM * 8)), __builtin_bit_cast(bf16x8, ld4(p + 2 * BM * 8))};
+        const bf16x8 h = __builtin_bit_cast(bf16x8, ld4(p));
+        if constexpr (EA) sa[t] = Split3{h, h, h};
+        else sa[t] = Split3{h, __builtin_bit_cast(bf16x8, ld4(p + BM * 8)), __builtin_bit_cast(bf16x8, ld4(p + 2 * BM * 8))};
       } else if constexpr (LA::RC) {
         const float* p = as + (wm * T::WTM + t * 32 + l31) * LDK + hf * HK;
 #pragma unroll
@@ -555,10 +600,12 @@ __device__ __forceinline__ void gemm_body(const LA& la, const LB& lb, const EP& 
 #pragma unroll
     for (int t = 0; t < T::TN; ++t) {
       if constexpr (PSB && !LB::RC) {
-        sb[t] = psi_read<BN>(bs, wn * T::WTN + t * 32, lane);
+        sb[t] = psi_read<BN, EB ? 1 : 3>(bs, wn * T::WTN + t * 32, lane);
       } else if constexpr (PSB) {
         const float* p = bs + (wn * T::WTN + t * 32 + l31) * 8 + (hf ^ ps_chunk_swizzle(l31)) * 4;
-        sb[t] = Split3{__builtin_bit_cast(bf16x8, ld4(p)), __builtin_bit_cast(bf16x8, ld4(p + BN * 8)), __builtin_bit_cast(bf16x8, ld4(p + 2 * BN * 8))};
+        const bf16x8 h = __builtin_bit_cast(bf16x8, ld4(p));
+        if constexpr (EB) sb[t] = Split3{h, h, h};
+        else sb[t] = Split3{h, __builtin_bit_cast(bf16x8, ld4(p + BN * 8)), __builtin_bit_cast(bf16x8, ld4(p + 2 * BN * 8))};
       } else if constexpr (LB::RC) {
         const float* p = bs + (wn * T::WTN + t * 32 + l31) * LDK + hf * HK;
 #pragma unroll
@@ -601,16 +648,22 @@ __device__ __forceinline__ void gemm_body(const LA& la, const LB& lb, const EP& 
       // replace 8 of 64 per 32 x 32 x 16 tile step, at the price of ~90 VALU operations per lane for the split.
       if constexpr (!PSA) {
 #pragma unroll
-        for (int t = 0; t < T::TM; ++t) sa[t] = split3(a[t]);
+        for (int t = 0; t < T::TM; ++t) {
+          if constexpr (EA) { const bf16x8 h = split_hi(a[t]); sa[t] = Split3{h, h, h}; }
+          else sa[t] = split3(a[t]);
+        }
       }
       if constexpr (!PSB) {
 #pragma unroll
-        for (int t = 0; t < T::TN; ++t) sb[t] = split3(b[t]);
+        for (int t = 0; t < T::TN; ++t) {
+          if constexpr (EB) { const bf16x8 h = split_hi(b[t]); sb[t] = Split3{h, h, h}; }
+          else sb[t] = split3(b[t]);
+        }
       }
       // MFMA order: a wave with several output tiles issues term by term ACROSS its tiles, so that consecutive MFMAs do not share an
       // accumulator.  For a wave with ONE tile two chains (even / odd terms, -DSAST_SINGLE_TILE_ACCS=2) were measured again under the bf16
       // split: +-0 in the micro-benchmarks, +0.5 % on the step (16 more VGPRs) -- the chain is not what the k-loop waits for
-      if constexpr (NACC > 1) {
+      if constexpr (NACC > 1 && !(EA || EB)) {
         f32x16 c0 = accs[0][0][0], c1 = accs[1][0][0];
         c0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sa[0].l, sb[0].h, c0, 0, 0, 0);     // smallest terms first
         c1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sa[0].h, sb[0].l, c1, 0, 0, 0);
@@ -626,6 +679,7 @@ __device__ __forceinline__ void gemm_body(const LA& la, const LB& lb, const EP& 
           for (int ta = 0; ta < T::TM; ++ta)
 #pragma unroll
             for (int tb = 0; tb < T::TN; ++tb) {
+              if (!term_live(term, EA, EB)) continue;
               const bf16x8 x = term == 0 ? sa[ta].l : (term == 2 || term == 3) ? sa[ta].m : sa[ta].h;      // l.h, h.l, m.m, m.h, h.m, h.h
               const bf16x8 y = term == 1 ? sb[tb].l : (term == 2 || term == 4) ? sb[tb].m : sb[tb].h;
               accs[0][ta][tb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x, y, accs[0][ta][tb], 0, 0, 0);
@@ -657,45 +711,25 @@ __device__ __forceinline__ void gemm_body(const LA& la, const LB& lb, const EP& 
     if constexpr (NT > 64 || !SAST_WAVE_GROUPS_FREE) __syncthreads();
     else { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); }
   };
-#pragma unroll
-  for (int u = 0; u < PF; ++u) gload(tile_of(u), u);
-  lstore(0, 0);
-  group_sync();
-  SAST_TL(1);
-  int i = 0;
-  SAST_TLF_DECL
-  for (; i + PF <= n_it; i += PF) {   // no exits inside the unrolled body: one straight-line block per PF phases
-#pragma unroll
-    for (int u = 0; u < PF; ++u) {
-      gload(tile_of(i + u + PF), u);
-      SAST_PHASE_FENCE();
-      SAST_TLF(0);
-      compute(u & 1);
-      SAST_TLF(1);
-      SAST_TLF_WAIT_OLDER(A_PER + B_PER);      // (instrumented builds: the wait for the tile loaded a phase ago, apart from its split + store)
-      lstore((u + 1) & 1, (u + 1) % PF);
-      SAST_TLF(2);
-      group_sync();
-      SAST_TLF(3);
-      SAST_TLF_COUNT();
+  // the reduction loop (gemm_kloop.inc).  An instantiation with an exact-bf16 operand carries it twice -- ex = true: one plane of that
+  // operand, three product terms; ex = false: the general six-term loop -- under ONE block-uniform branch, straight-line code inside each
+  // body; every other instantiation has the one loop it always had, in the function's own scope
+  if constexpr (XALWAYS) {
+    constexpr std::true_type ex{};
+#include "gemm_kloop.inc"
+  } else if constexpr (XA || XB) {
+    bool exact;
+    if constexpr (XA) exact = la.exact(); else exact = lb.exact();
+    if (exact) {
+      constexpr std::true_type ex{};
+#include "gemm_kloop.inc"
+    } else {
+      constexpr std::false_type ex{};
+#include "gemm_kloop.inc"
     }
-  }
-  SAST_TLF_FLUSH();
-  if constexpr (EARLY_AUX) {
-    const int jc = min(j0 + wn * 32 + (lane & 31), NJ - 1), mb = m0 + wm * T::WTM + 4 * (lane >> 5);
-#pragma unroll
-    for (int reg = 0; reg < 16; ++reg) eaux[reg] = ep.pre(min(mb + (reg & 3) + 8 * (reg >> 2), Meff - 1), jc);
-  }
-  {   // remainder (< PF phases): everything it needs is already in registers
-    const int rem = n_it - i;
-#pragma unroll
-    for (int u = 0; u < PF - 1; ++u) {
-      if (u < rem) {
-        compute(u & 1);
-        lstore((u + 1) & 1, (u + 1) % PF);
-        group_sync();
-      }
-    }
+  } else {
+    constexpr std::false_type ex{};
+#include "gemm_kloop.inc"
   }
 
   if constexpr (NACC > 1) {
@@ -964,6 +998,7 @@ template <class L> struct LoaderSrcBytes<L, std::void_t<decltype(std::declval<co
 void prof_kernel_events_ex(const char* tag, double flops, double bytes, hipStream_t st, hipEvent_t* e0, hipEvent_t* e1);
 void prof_sum_k(const int* Kw, int W, hipStream_t st, double* sum_k, double* sum_k2);
 bool prof_enabled();
+void prof_flops_credit(double flops);   // FLOPs of skipped dead work, added to the next profiled GEMM launch (k_prof.hip)
 bool xcd_remap_enabled();   // SAST_XCD_REMAP (default on)
 void prof_scope(const char* name, int c, int m, hipStream_t st, bool begin);
 struct ProfScope {
@@ -1123,6 +1158,11 @@ using TileG4K4  = Tile<32, 128, 1, 1, 4, 16, 4>;  // LSTM, 4 single-wave k-group
 using TileG4    = Tile<64, 128, 2, 1, 4>;   // LSTM: 64 rows x (32 ch x 4 gates); 2 waves
 using TileG4Big = Tile<128, 128, 4, 1, 4>;  // 128 rows x (32 ch x 4 gates)
 using TileG4Tiny = Tile<32, 128, 1, 1, 4>;  // one wave: 32 rows x (32 ch x 4 gates)
+// the ConvLSTM from a zero cell state: the forget gate multiplies zero, three live gates (i|o|g) per output channel.  BN = 96: nothing in
+// gemm_body needs a power of two for a reduce-contiguous, not presplit B operand (slots 96 * BK / 4 divide by the thread count, nnmap and the
+// stage sizes are linear in BN); psi_swizzle<BN> / psi_read<BN> belong to the index-contiguous presplit path these tiles stay off
+using TileG3    = Tile<64, 96, 2, 1, 3>;    // 64 rows x (32 ch x 3 gates); 2 waves
+using TileG3K4  = Tile<32, 96, 1, 1, 3, 16, 4>;   // 4 single-wave k-groups: 32 rows x (32 ch x 3 gates)
 
 // fast exact division by a small runtime constant d (d <= 64, n < 4096): n / d == (n * mul) >> 16
 __host__ __device__ inline int small_div_mul(int d) { return 65536 / d + 1; }
@@ -1465,6 +1505,24 @@ struct LdIm2colT {
   }
   SAST_DEFAULT_FINISH
 };
+// the stem's loaders on an event tensor that may be exact in bf16 (stacked-histogram counts: small non-negative integers).  uint8 is
+// exact by type (LdExactBf16Always); otherwise `nonexact` points at the word sast_input_prep_flag published for THIS tensor (0 = every value is
+// one bf16) -- read once per workgroup; NULL = not known, the six-term loop
+template <class Base>
+struct LdExactBf16 : Base {
+  static constexpr bool EXACT_BF16 = true;
+  const unsigned* nonexact;
+  __device__ __forceinline__ bool exact() const { return nonexact != nullptr && *nonexact == 0u; }
+};
+template <class Base>
+struct LdExactBf16Always : Base {      // exact by type: the three-term loop is the only one compiled in
+  static constexpr bool EXACT_BF16 = true, EXACT_BF16_ALWAYS = true;
+  __device__ __forceinline__ bool exact() const { return true; }
+};
+using LdIm2colX = LdExactBf16<LdIm2col>;
+using LdIm2colTX = LdExactBf16<LdIm2colT>;
+using LdIm2colQ8X = LdExactBf16Always<LdIm2colQ8>;
+using LdIm2colTQ8X = LdExactBf16Always<LdIm2colTQ8>;
 // RC: backward-data gather  A[m = (b,iy,ix)][r = (kh,kw,co)] = dY[b,(iy+p-kh)/s,(ix+p-kw)/s,co]
 // replicate padding: the clamped taps (kh < pad at iy == 0, same for x) fold onto output row/col 0.
 struct LdConvDx {

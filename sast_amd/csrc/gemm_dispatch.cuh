@@ -45,12 +45,16 @@ inline int tiny_nb() { return SAST_KNOB("SAST_TINY_NB", 128); }
 // (stand-alone launches only: as the dX job of a paired launch it measured slower, +0.02 ms/step)
 inline bool use_tiny(int M, int NJ, int R) { return (long)((M + 31) / 32) * ((NJ + 63) / 64) <= tiny_nb() && R >= 512; }
 
+// R_tile (optional): the reduction length the TILE is chosen for when the caller has cut a prefix of exact zeros off a longer reduction
+// (ConvLSTM backward from a zero cell state): the same tile as the full-length call, and -- when the cut is a multiple of BK * KS, so
+// that every k-group keeps its tiles -- the same summation order
 template <class LA, class LB, class EP>
-int gemm_auto(const LA& la, const LB& lb, const EP& ep, int M, int NJ, int R, const int* dM, hipStream_t st) {
+int gemm_auto(const LA& la, const LB& lb, const EP& ep, int M, int NJ, int R, const int* dM, hipStream_t st, int R_tile = 0) {
   const long nb = (long)((M + 63) / 64) * ((NJ + 63) / 64);
-  if (!dM && use_tiny(M, NJ, R)) return launch_gemm<TileTinyK8>(la, lb, ep, M, NJ, R, dM, nullptr, st);
-  if (nb <= pair_thin_nb() && R >= pair_ks_min_r()) return launch_gemm<TileAutoThin>(la, lb, ep, M, NJ, R, dM, nullptr, st);
-  if (nb <= pair_ks_nb() && R >= pair_ks_min_r()) return launch_gemm<TileAutoK2>(la, lb, ep, M, NJ, R, dM, nullptr, st);
+  const int Rt = R_tile > 0 ? R_tile : R;
+  if (!dM && use_tiny(M, NJ, Rt)) return launch_gemm<TileTinyK8>(la, lb, ep, M, NJ, R, dM, nullptr, st);
+  if (nb <= pair_thin_nb() && Rt >= pair_ks_min_r()) return launch_gemm<TileAutoThin>(la, lb, ep, M, NJ, R, dM, nullptr, st);
+  if (nb <= pair_ks_nb() && Rt >= pair_ks_min_r()) return launch_gemm<TileAutoK2>(la, lb, ep, M, NJ, R, dM, nullptr, st);
   return launch_gemm<TileAutoK1>(la, lb, ep, M, NJ, R, dM, nullptr, st);
 }
 template <class LA, class LB, class EP>
@@ -150,23 +154,27 @@ int gemm_tn(const LA& la, const LB& lb, float* out, int ldc, int Mo, int NJ, int
 // job 2: plain GEMM (M2 rows, device-side count dM2) with epilogue ep2
 template <class LA1, class LB1, class EP1, class LA2, class LB2, class EP2>
 int gemm_pair_ep(const LA1& la1, const LB1& lb1, const EP1& ep1, int Mo, int NJ1, int R1, const int* dR1, float* colsum,
-                 const LA2& la2, const LB2& lb2, const EP2& ep2, int M2, int NJ2, int R2, const int* dM2, hipStream_t st, int tn_target = 0);
+                 const LA2& la2, const LB2& lb2, const EP2& ep2, int M2, int NJ2, int R2, const int* dM2, hipStream_t st, int tn_target = 0,
+                 int R2_tile = 0);
 template <class LA1, class LB1, class LA2, class LB2, class EP2>
 int gemm_pair(const LA1& la1, const LB1& lb1, float* out, int ldc, int Mo, int NJ1, int R1, const int* dR1, float* colsum,
-              const LA2& la2, const LB2& lb2, const EP2& ep2, int M2, int NJ2, int R2, const int* dM2, hipStream_t st, int tn_target = 0) {
-  return gemm_pair_ep(la1, lb1, EpAtomic{out, ldc}, Mo, NJ1, R1, dR1, colsum, la2, lb2, ep2, M2, NJ2, R2, dM2, st, tn_target);
+              const LA2& la2, const LB2& lb2, const EP2& ep2, int M2, int NJ2, int R2, const int* dM2, hipStream_t st, int tn_target = 0,
+              int R2_tile = 0) {
+  return gemm_pair_ep(la1, lb1, EpAtomic{out, ldc}, Mo, NJ1, R1, dR1, colsum, la2, lb2, ep2, M2, NJ2, R2, dM2, st, tn_target, R2_tile);
 }
 // the same with any accumulating epilogue for job 1
 template <class LA1, class LB1, class EP1, class LA2, class LB2, class EP2>
 int gemm_pair_ep(const LA1& la1, const LB1& lb1, const EP1& ep1, int Mo, int NJ1, int R1, const int* dR1, float* colsum,
-                 const LA2& la2, const LB2& lb2, const EP2& ep2, int M2, int NJ2, int R2, const int* dM2, hipStream_t st, int tn_target) {
+                 const LA2& la2, const LB2& lb2, const EP2& ep2, int M2, int NJ2, int R2, const int* dM2, hipStream_t st, int tn_target,
+                 int R2_tile) {     // R2_tile: see gemm_auto
   if (dw_defer_rows_ok(R1) && Mo > 0 && NJ1 > 0 && R1 > 0) {      // job 1 parked, job 2 alone with the stand-alone tile choice
     const int rc = dw_park(la1, lb1, ep1, Mo, NJ1, R1, dR1, colsum);
     if (rc) return rc;
-    return gemm_auto(la2, lb2, ep2, M2, NJ2, R2, dM2, st);
+    return gemm_auto(la2, lb2, ep2, M2, NJ2, R2, dM2, st, R2_tile);
   }
   const long nb2 = (long)((M2 + 63) / 64) * ((NJ2 + 63) / 64);
-  const bool thin = nb2 <= pair_thin_nb() && R2 >= pair_ks_min_r(), k2 = nb2 <= pair_ks_nb() && R2 >= pair_ks_min_r();
+  const int R2t = R2_tile > 0 ? R2_tile : R2;
+  const bool thin = nb2 <= pair_thin_nb() && R2t >= pair_ks_min_r(), k2 = nb2 <= pair_ks_nb() && R2t >= pair_ks_min_r();
   const int nb1 = ((Mo + 63) / 64) * ((NJ1 + 63) / 64);
   if (gemm_pair_enabled() && pair_tn_blocks_small() > 0 && nb1 <= pair_tn_small_tiles()) tn_target = pair_tn_blocks_small();
   const int splits = tn_splits(Mo, NJ1, R1, gemm_pair_enabled() ? (tn_target > 0 ? tn_target : pair_tn_blocks_paired()) : 0);

@@ -140,7 +140,31 @@ struct EpLstm {  // rnn.py:57-67
     st_saved(gp, f); st_saved(gp + C, i); st_saved(gp + 2 * C, o); st_saved(gp + 3 * C, g);     // the gates: read by the backward only
   }
 };
+// the same from a ZERO cell state (c0 == NULL): c = f * 0 + i * (g * d) does not depend on the forget gate, so the GEMM runs over the three
+// live gates (weight rows [C, 4C): i | o | g) and f is neither evaluated nor saved (gates[:, 0:C] stays unwritten).  The cell value keeps
+// the bits of the four-gate form: (+0) + i * (g * d), i.e. a product of -0 still becomes +0.
+struct EpLstm3 {
+  const float* bias; float* h1; float* c1; float* gates; int C; const float* drop;
+  struct Col { float bi, bo, bg; };
+  struct Aux { float d; };
+  __device__ __forceinline__ Col col(int j) const { return Col{bias[C + j], bias[2 * C + j], bias[3 * C + j]}; }
+  __device__ __forceinline__ Aux pre(int m, int j) const { return Aux{drop ? drop[(size_t)m * C + j] : 1.f}; }
+  __device__ __forceinline__ void post(int m, int j, const float (&v)[3], const Col& k, const Aux& x) const {
+    const float i = sigmoid_hw(v[0] + k.bi), o = sigmoid_hw(v[1] + k.bo), g = tanh_hw(v[2] + k.bg);
+    const float c = 0.f + i * (g * x.d);
+    c1[(size_t)m * C + j] = c;
+    h1[(size_t)m * C + j] = o * tanh_hw(c);
+    float* gp = gates + (size_t)m * 4 * C + j;
+    st_saved(gp + C, i); st_saved(gp + 2 * C, o); st_saved(gp + 3 * C, g);
+  }
+};
+// zero cell state + SAST_LSTM_SKIP_DEAD_GATE (default 1): forward and backward run on the three live gates.  The knob must not change
+// between a forward and its backward: the four-gate backward reads the f the three-gate forward did not save.
+inline bool lstm_skip_f(const SastLstmArgs* a) { return !a->c0 && SAST_KNOB("SAST_LSTM_SKIP_DEAD_GATE", 1) != 0; }
 
+// SKIPF: zero cell state, three live gates -- f is not read (the forward did not save it) and dmix[:, 0:C] (= dc * 0 * f * (1 - f)) is
+// not written: the GEMMs behind read the columns [C, 4C) only
+template <bool SKIPF>
 __global__ __launch_bounds__(256) void lstm_bwd_pointwise_kernel(const float* __restrict__ gates, const float* __restrict__ c0,
                                                                  const float* __restrict__ c1, const float* __restrict__ dh1,
                                                                  const float* __restrict__ dh1b, const float* __restrict__ dc1,
@@ -151,18 +175,18 @@ __global__ __launch_bounds__(256) void lstm_bwd_pointwise_kernel(const float* __
   if (e >= n) return;
   const size_t m = fast_div((int)e, C, c_mul); const int j = (int)(e - m * C);   // n < 2^31 (launcher)
   const float* gp = gates + m * 4 * C + j;
-  const float f = gp[0], i = gp[C], o = gp[2 * C], g = gp[3 * C];
+  const float f = SKIPF ? 0.f : gp[0], i = gp[C], o = gp[2 * C], g = gp[3 * C];
   const float tc = tanh_hw(c1[e]);
   const float dh = dh1[e] + (dh1b ? dh1b[e] : 0.f);   // h1 may have been handed out twice (next stage and FPN): the gradients are summed here
   const float dc = (dc1 ? dc1[e] : 0.f) + dh * o * (1.f - tc * tc);
-  const float cp = c0 ? c0[e] : 0.f;
+  const float cp = (!SKIPF && c0) ? c0[e] : 0.f;
   float* dp = dmix + m * 4 * C + j;
-  dp[0] = dc * cp * f * (1.f - f);
+  if constexpr (!SKIPF) dp[0] = dc * cp * f * (1.f - f);
   const float d = drop ? drop[e] : 1.f;           // cell input = dropout(tanh(.)) = g * d (the saved g is the tanh itself)
   dp[C] = dc * (g * d) * i * (1.f - i);
   dp[2 * C] = dh * tc * o * (1.f - o);
   dp[3 * C] = dc * i * d * (1.f - g * g);
-  if (dc0) dc0[e] = dc * f;
+  if constexpr (!SKIPF) { if (dc0) dc0[e] = dc * f; }
 }
 
 }  // namespace
@@ -191,6 +215,11 @@ int sast_nchw_to_nhwc_padded(const void* x, int dtype, int B, int C, int H, int 
 int sast_input_prep(const void* x, int dtype, int B, int C, int H, int W, int Hp, int Wp, int32_t* ws, float* r, float* y, sast_stream_t stream) { SAST_ENTRY();
   if (!x || !ws || !r || !y || H > Hp || W > Wp || H % 4 || W % 4 || Hp % 32 || Wp % 32 || C != 20 || ((Hp / 32) * (Wp / 32)) % 2) return SAST_EINVAL;
   return input_prep_dispatch(x, dtype, y, ws, r, B, C, H, W, Hp, Wp, (hipStream_t)stream);
+}
+int sast_input_prep_flag(const void* x, int dtype, int B, int C, int H, int W, int Hp, int Wp, int32_t* ws, float* r, float* y, uint32_t* nonexact,
+                         sast_stream_t stream) { SAST_ENTRY();
+  if (!x || !ws || !r || !y || !nonexact || H > Hp || W > Wp || H % 4 || W % 4 || Hp % 32 || Wp % 32 || C != 20 || ((Hp / 32) * (Wp / 32)) % 2) return SAST_EINVAL;
+  return input_prep_dispatch(x, dtype, y, ws, r, B, C, H, W, Hp, Wp, (hipStream_t)stream, nonexact);
 }
 int sast_input_prep_u8(const uint8_t* x, int B, int C, int H, int W, int Hp, int Wp, int32_t* ws, float* r, uint8_t* y, sast_stream_t stream) { SAST_ENTRY();
   if (!x || !ws || !r || !y || H > Hp || W > Wp || H % 4 || W % 4 || Hp % 32 || Wp % 32 || C != 20 || ((Hp / 32) * (Wp / 32)) % 2) return SAST_EINVAL;
@@ -501,7 +530,15 @@ int sast_lstm_fwd(const SastLstmArgs* a, sast_stream_t stream) { SAST_ENTRY();
   const LdWeightNT lb{a->w, 2 * C, C};
   const EpLstm ep{a->b, a->c0, a->h1, a->c1, a->gates, C, a->drop};
   const int mode = SAST_KNOB("SAST_LSTM_TILE", 0);
-  if (mode && Kred >= 256 && (long)((M + 63) / 64) * ((C + 31) / 32) <= 2 * pair_thin_nb())
+  const bool k4 = mode && Kred >= 256 && (long)((M + 63) / 64) * ((C + 31) / 32) <= 2 * pair_thin_nb();
+  if (lstm_skip_f(a)) {     // the three live gates: weight / bias rows [C, 4C)
+    const LdWeightNT lb3{a->w + (size_t)C * 2 * C, 2 * C, C};
+    const EpLstm3 ep3{a->b, a->h1, a->c1, a->gates, C, a->drop};
+    prof_flops_credit(2.0 * M * C * Kred);      // the roofline leg counts the full operator
+    if (k4) return launch_gemm<TileG3K4>(la, lb3, ep3, M, C, Kred, nullptr, nullptr, st);
+    return launch_gemm<TileG3>(la, lb3, ep3, M, C, Kred, nullptr, nullptr, st);
+  }
+  if (k4)
     return launch_gemm<TileG4K4>(la, lb, ep, M, C, Kred, nullptr, nullptr, st);
   return launch_gemm<TileG4>(la, lb, ep, M, C, Kred, nullptr, nullptr, st);
 }
@@ -513,9 +550,22 @@ int sast_lstm_bwd(const SastLstmArgs* a, sast_stream_t stream) { SAST_ENTRY();
   float* dmix = a->ws;
   const size_t n = (size_t)M * C;
   if (n >= (1ull << 31)) return SAST_EINVAL;
-  SAST_LAUNCH(lstm_bwd_pointwise_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a->gates, a->c0, a->c1, a->dh1,
-                     a->dh1b, a->dc1, dmix, a->dc0, n, C, div_mul_of((unsigned)C, n), a->drop);
   const int NJ = (a->h0 && a->dh0) ? 2 * C : C;
+  if (lstm_skip_f(a)) {
+    if (a->dc0) return SAST_EINVAL;     // dc0 = dc * f, and f was not saved (a zero state has no gradient to ask for: functional.py never does)
+    SAST_LAUNCH(lstm_bwd_pointwise_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a->gates, a->c0, a->c1, a->dh1,
+                       a->dh1b, a->dc1, dmix, a->dc0, n, C, div_mul_of((unsigned)C, n), a->drop);
+    // both jobs on the gate rows [C, 4C): dW / db leave their rows [0, C) alone (today's call adds exact zeros there), dX drops the
+    // reduction's first C terms (exact zeros); its tile is the one of the 4C-long reduction.  The surviving terms are summed in the
+    // four-gate call's order -- bit-identical dx / dh0 -- when the cut is whole k-tiles per k-group: C % (16 * KS) == 0 (every C of the
+    // model: 64 .. 512 with the KS <= 4 tiles, >= 128 where the 8-group tile is chosen); other C: same value up to summation order
+    const size_t wo = (size_t)C * 2 * C;
+    prof_flops_credit(2.0 * M * C * (a->h0 ? 2 * C : C) + 2.0 * M * NJ * C);
+    return gemm_pair(LdRowsT{dmix + C, 4 * C}, LdRowsT2{a->x, C, C, a->h0, C}, a->dw + wo, 2 * C, 3 * C, a->h0 ? 2 * C : C, M, nullptr, a->db ? a->db + C : nullptr,
+                     LdRows{dmix + C, 4 * C, nullptr}, LdWeightNN{a->w + wo, 2 * C}, EpSplit2{a->dx, a->dh0, C, C}, M, NJ, 3 * C, nullptr, st, 0, 4 * C);
+  }
+  SAST_LAUNCH(lstm_bwd_pointwise_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a->gates, a->c0, a->c1, a->dh1,
+                     a->dh1b, a->dc1, dmix, a->dc0, n, C, div_mul_of((unsigned)C, n), a->drop);
   return gemm_pair(LdRowsT{dmix, 4 * C}, LdRowsT2{a->x, C, C, a->h0, C}, a->dw, 2 * C, 4 * C, a->h0 ? 2 * C : C, M, nullptr, a->db,
                    LdRows{dmix, 4 * C, nullptr}, LdWeightNN{a->w, 2 * C}, EpSplit2{a->dx, a->dh0, C, C}, M, NJ, 4 * C, nullptr, st);
 }

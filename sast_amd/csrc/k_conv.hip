@@ -492,6 +492,7 @@ int conv_bwd_pair(const float* dconv, const float* x, const ConvGeom& g, int Cou
 // sizes the downsample conv accepts.  The overlapping form (k = 2f-1, replicate padding f-1) has ceil(H / f) output rows: at an H or W
 // that is not a multiple of the factor that is more rows than the H / f the callers size their buffers for, and the replicate clamp
 // would also act at the bottom / right edge, which LdConvDx / LdConvDxP do not fold.  The reference only uses multiples: refused.
+inline bool stem_exact_bf16() { return SAST_KNOB("SAST_STEM_EXACT_BF16", 1) != 0; }
 bool down_size_ok(const SastDownArgs* a) {
   if (a->factor < 1 || a->B < 1 || a->H < a->factor || a->W < a->factor) return false;
   return a->no_overlap || (a->H % a->factor == 0 && a->W % a->factor == 0);
@@ -511,9 +512,16 @@ int sast_downsample_ln_fwd(const SastDownArgs* a, sast_stream_t stream) { SAST_E
   const ConvGeom g = geom_of(a->B, a->H, a->W, a->Cin, k, a->factor, a->no_overlap ? 0 : a->factor - 1, 1, a->Cin);
   const int M = a->B * g.Ho * g.Wo, K = k * k * a->Cin;
   int rc;
-  if (a->x_dtype == SAST_DT_U8)       // the stem on the stored uint8 event tensor (NHWC bytes, written by sast_input_prep_u8)
+  // an event tensor that is exact in bf16 (uint8: by type; fp32: the word of sast_input_prep_flag, read by the kernel): the loaders with
+  // the EXACT_BF16 trait (gemm.cuh), whose kernels carry the three-term k-loop beside the six-term one
+  const bool exact_ok = stem_exact_bf16();
+  if (a->x_dtype == SAST_DT_U8 && exact_ok)
+    rc = !g.cin_mul ? SAST_EINVAL : gemm_auto(LdIm2colQ8X{{(const unsigned char*)a->x, g}}, LdWeightNT{a->w, K, 0}, EpStore{a->conv_out, a->Cout, nullptr}, M, a->Cout, K, st);
+  else if (a->x_dtype == SAST_DT_U8)       // the stem on the stored uint8 event tensor (NHWC bytes, written by sast_input_prep_u8)
     rc = !g.cin_mul ? SAST_EINVAL : gemm_auto(LdIm2colQ8{(const unsigned char*)a->x, g}, LdWeightNT{a->w, K, 0}, EpStore{a->conv_out, a->Cout, nullptr}, M, a->Cout, K, st);
   else if (a->x_dtype != SAST_DT_F32) return SAST_EINVAL;
+  else if (a->x_nonexact && exact_ok && g.Cin % 16)
+    rc = !g.cin_mul ? SAST_EINVAL : gemm_auto(LdIm2colX{{a->x, g}, a->x_nonexact}, LdWeightNT{a->w, K, 0}, EpStore{a->conv_out, a->Cout, nullptr}, M, a->Cout, K, st);
   else rc = conv_gemm(a->x, g, LdWeightNT{a->w, K, 0}, EpStore{a->conv_out, a->Cout, nullptr}, M, a->Cout, K, st);
   if (rc) return rc;
   return ln_fwd_launch(a->conv_out, a->y, a->ln_w, a->ln_b, a->pe, g.Ho * g.Wo, a->mean, a->rstd, M, a->Cout, 1e-5f, st);
@@ -531,9 +539,14 @@ int sast_downsample_ln_bwd(const SastDownArgs* a, sast_stream_t stream) { SAST_E
   if (rc) return rc;
   if (a->x_dtype == SAST_DT_U8) {     // an integer input has no gradient: the weight gradient only
     if (a->dx || !g.cin_mul) return SAST_EINVAL;
+    if (stem_exact_bf16()) return gemm_tn(LdRowsT{dconv, a->Cout}, LdIm2colTQ8X{{(const unsigned char*)a->x, g}}, a->dw, K, a->Cout, K, M, st);
     return gemm_tn(LdRowsT{dconv, a->Cout}, LdIm2colTQ8{(const unsigned char*)a->x, g}, a->dw, K, a->Cout, K, M, st);
   }
   if (a->x_dtype != SAST_DT_F32) return SAST_EINVAL;
+  if (a->x_nonexact && !a->dx && stem_exact_bf16() && g.Cin % 16) {     // the stem's weight gradient on the flagged fp32 copy of the event tensor
+    if (!g.cin_mul) return SAST_EINVAL;
+    return gemm_tn(LdRowsT{dconv, a->Cout}, LdIm2colTX{{a->x, g}, a->x_nonexact}, a->dw, K, a->Cout, K, M, st);
+  }
   return conv_bwd_pair(dconv, a->x, g, a->Cout, a->w, a->dw, a->dx, a->Cin, st);
 }
 

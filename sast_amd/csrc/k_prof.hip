@@ -18,6 +18,11 @@ static std::vector<ProfLaunch> g_launches;
 static std::vector<hipEvent_t> g_pending;
 
 bool prof_enabled() { return g_on; }
+// algorithmic FLOPs of work a caller skipped because its result is known (the dead forget gate of a ConvLSTM from a zero cell state):
+// credited to the next profiled GEMM launch, so that the roofline leg keeps counting the FLOPs of the full operator
+static double g_flops_credit = 0.0;
+void prof_flops_credit(double flops) { if (g_on) g_flops_credit += flops; }
+static double take_credit() { const double c = g_flops_credit; g_flops_credit = 0.0; return c; }
 
 bool xcd_remap_enabled() {
   return SAST_KNOB("SAST_XCD_REMAP", 1) != 0;
@@ -54,7 +59,7 @@ void prof_kernel_events(const char* tag, int G, int M, int NJ, int R, const int*
   int m = M, r = R;
   if (dM) { int v; hipMemcpyAsync(&v, dM, sizeof(int), hipMemcpyDeviceToHost, st); hipStreamSynchronize(st); if (v < m) m = v; }
   if (dR) { int v; hipMemcpyAsync(&v, dR, sizeof(int), hipMemcpyDeviceToHost, st); hipStreamSynchronize(st); if (v < r) r = v; }
-  l.flops = 2.0 * (double)m * (double)NJ * (double)G * (double)r;
+  l.flops = 2.0 * (double)m * (double)NJ * (double)G * (double)r + take_credit();
   // A + B + C once each (operands read / written once); a gathered operand (implicit-GEMM conv) at the size of its source tensor
   l.bytes = capped(4.0 * (double)m * r, a_cap) + capped(4.0 * (double)NJ * G * r, b_cap) + 4.0 * (double)m * NJ * G;
   l.tag = tag;
@@ -79,7 +84,7 @@ void prof_kernel_events2(const char* tag, double flops_static, int G1, int M1, i
   hipEventCreate(&l.e0);
   hipEventCreate(&l.e1);
   const double m1 = dev_min(M1, dM1, st), r1 = dev_min(R1, dR1, st), m2 = dev_min(M2, dM2, st), r2 = dev_min(R2, dR2, st);
-  l.flops = flops_static + 2.0 * m1 * NJ1 * G1 * r1 + 2.0 * m2 * NJ2 * G2 * r2;
+  l.flops = flops_static + 2.0 * m1 * NJ1 * G1 * r1 + 2.0 * m2 * NJ2 * G2 * r2 + take_credit();
   l.bytes = capped(4.0 * m1 * r1, a1_cap) + capped(4.0 * NJ1 * G1 * r1, b1_cap) + 4.0 * m1 * NJ1 * G1 +
             capped(4.0 * m2 * r2, a2_cap) + capped(4.0 * NJ2 * G2 * r2, b2_cap) + 4.0 * m2 * NJ2 * G2;
   l.tag = tag;

@@ -150,8 +150,13 @@ constexpr int PREP_WAVES = 2;
 template <typename T, int C, typename TY = float>
 __global__ __launch_bounds__(64 * PREP_WAVES) void input_prep_kernel(const T* __restrict__ x, TY* __restrict__ y, int* __restrict__ ws,
                                                                      float* __restrict__ r, int B, int H, int W, int Hp, int Wp,
-                                                                     float s0, float s1, float s2, float s3) {
+                                                                     float s0, float s1, float s2, float s3,
+                                                                     unsigned* __restrict__ nonexact) {
+  // nonexact (optional, an OUTPUT of the call): 0 iff every value of y is exactly one bf16 (the low 16 bits of its fp32 pattern are
+  // zero: every integer of magnitude <= 256, among others) -- the stem GEMMs then run their three-term k-loop (gemm.cuh: EXACT_BF16).
+  // The workgroups OR into the scratch word ws[B*4*C + 1]; the last one (the ticket below) publishes it and clears it again.
   __shared__ __attribute__((aligned(16))) TY tile_s[PREP_WAVES][8 * 32 * C];
+  unsigned low = 0u;
   constexpr bool BYTES = sizeof(TY) == 1;
   __shared__ int cnt_s[4 * C];
   __shared__ int last;
@@ -189,6 +194,7 @@ __global__ __launch_bounds__(64 * PREP_WAVES) void input_prep_kernel(const T* __
 #pragma unroll
         for (int px = 0; px < 4; ++px) {
           v[ch][px] = inside ? (float)q[c0 + ch].v[px] : 0.f;
+          if constexpr (!BYTES) low |= __float_as_uint(v[ch][px]);
           m[c0 + ch] = fmaxf(m[c0 + ch], v[ch][px]);
         }
 #pragma unroll
@@ -238,6 +244,12 @@ __global__ __launch_bounds__(64 * PREP_WAVES) void input_prep_kernel(const T* __
   int* cnt = ws;                                                      // [B][4][C]
   if (b_blk < B)
     for (int i = threadIdx.x; i < 4 * C; i += 64 * PREP_WAVES) if (cnt_s[i]) atomicAdd(cnt + (size_t)b_blk * 4 * C + i, cnt_s[i]);
+  if constexpr (!BYTES) {
+    if (nonexact) {     // uniform
+      const unsigned long long any = __ballot((low & 0xffffu) != 0u);
+      if (lane == 0 && any) atomicOr(reinterpret_cast<unsigned*>(ws) + B * 4 * C + 1, 1u);
+    }
+  }
   __threadfence();
   __syncthreads();
   if (threadIdx.x == 0) last = atomicAdd(ws + B * 4 * C, 1) == (int)gridDim.x - 1;
@@ -251,11 +263,18 @@ __global__ __launch_bounds__(64 * PREP_WAVES) void input_prep_kernel(const T* __
       cnt[i] = 0;
     }
     if (threadIdx.x == 0) ws[B * 4 * C] = 0;
+    if constexpr (!BYTES) {
+      if (nonexact && threadIdx.x == 0) {
+        unsigned* word = reinterpret_cast<unsigned*>(ws) + B * 4 * C + 1;
+        *nonexact = __hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        *word = 0u;
+      }
+    }
   }
 }
 
 template <typename T, typename TY = float>
-int input_prep_launch(const void* x, TY* y, int* ws, float* r, int B, int C, int H, int W, int Hp, int Wp, hipStream_t st) {
+int input_prep_launch(const void* x, TY* y, int* ws, float* r, int B, int C, int H, int W, int Hp, int Wp, hipStream_t st, unsigned* nonexact = nullptr) {
   if (C != 20) return SAST_EINVAL;               // the stacked-histogram representation of the path: 2 polarities x 10 bins
   const int tiles = B * (Hp / 32) * (Wp / 32);
   float s[4];
@@ -266,18 +285,19 @@ int input_prep_launch(const void* x, TY* y, int* ws, float* r, int B, int C, int
     f *= 2;
   }
   SAST_LAUNCH((input_prep_kernel<T, 20, TY>), dim3((tiles + PREP_WAVES - 1) / PREP_WAVES), dim3(64 * PREP_WAVES), 0, st, (const T*)x, y, ws, r,
-                     B, H, W, Hp, Wp, s[0], s[1], s[2], s[3]);
+                     B, H, W, Hp, Wp, s[0], s[1], s[2], s[3], nonexact);
   SAST_CHECK_LAUNCH();
   return SAST_OK;
 }
 int input_prep_u8(const unsigned char* x, unsigned char* y, int* ws, float* r, int B, int C, int H, int W, int Hp, int Wp, hipStream_t st) {
   return input_prep_launch<unsigned char, unsigned char>(x, y, ws, r, B, C, H, W, Hp, Wp, st);
 }
-int input_prep_dispatch(const void* x, int dtype, float* y, int* ws, float* r, int B, int C, int H, int W, int Hp, int Wp, hipStream_t st) {
+int input_prep_dispatch(const void* x, int dtype, float* y, int* ws, float* r, int B, int C, int H, int W, int Hp, int Wp, hipStream_t st,
+                        unsigned* nonexact) {
   switch (dtype) {
-    case SAST_DT_F32: return input_prep_launch<float>(x, y, ws, r, B, C, H, W, Hp, Wp, st);
-    case SAST_DT_I32: return input_prep_launch<int>(x, y, ws, r, B, C, H, W, Hp, Wp, st);
-    case SAST_DT_U8:  return input_prep_launch<unsigned char>(x, y, ws, r, B, C, H, W, Hp, Wp, st);
+    case SAST_DT_F32: return input_prep_launch<float>(x, y, ws, r, B, C, H, W, Hp, Wp, st, nonexact);
+    case SAST_DT_I32: return input_prep_launch<int>(x, y, ws, r, B, C, H, W, Hp, Wp, st, nonexact);
+    case SAST_DT_U8:  return input_prep_launch<unsigned char>(x, y, ws, r, B, C, H, W, Hp, Wp, st, nonexact);
     default: return SAST_EINVAL;
   }
 }

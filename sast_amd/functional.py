@@ -269,7 +269,11 @@ def input_prep(x: torch.Tensor, pad_hw=None, ws_cache: Optional[dict] = None, ke
     in ONE launch that reads the event tensor once -> (r (B,4,C) fp32, x_nhwc (B,Hp,Wp,C) fp32).  Falls back to the two separate
     launches for shapes the fused kernel does not cover (padded sizes that are not multiples of 32, channel counts other than 20).
     keep_bytes (uint8 input, the dataset's storage type): x_nhwc stays uint8 -- only `downsample_ln` (the stem) may consume it; its
-    loaders do the `.float()`.  Ignored (fp32 result) for other dtypes and for the fallback shapes."""
+    loaders do the `.float()`.  Ignored (fp32 result) for other dtypes and for the fallback shapes.
+    The fp32 copy of the fused path carries `x_nhwc.sast_nonexact`: one int32 word allocated behind it, written by the same launch (0 =
+    every value is exactly one bf16, as stacked-histogram counts are); `downsample_ln` hands it to the stem's GEMMs.  The attribute
+    does not follow views / clones (those get the general six-term GEMMs), and x_nhwc must NOT be written in place after this call: the
+    word would keep describing the old values and a stale 0 makes the stem drop the operand's lower bf16 planes (~2^-8 relative error)."""
     _need_gpu(x)
     if x.dtype not in _DT:
         x = x.float()
@@ -290,15 +294,22 @@ def input_prep(x: torch.Tensor, pad_hw=None, ws_cache: Optional[dict] = None, ke
     if ws is None:
         if torch.cuda.is_current_stream_capturing():
             raise RuntimeError("sast_amd: input_prep needs one un-captured warm-up call (per model and batch size) before graph capture")
-        ws = cache[key] = torch.zeros(B * 4 * Cc + 1, device=x.device, dtype=torch.int32)
+        ws = cache[key] = torch.zeros(B * 4 * Cc + 2, device=x.device, dtype=torch.int32)     # counters, ticket, exactness scratch word
     r = torch.empty(B, 4, Cc, device=x.device, dtype=torch.float32)
     u8 = keep_bytes and x.dtype == torch.uint8
-    y = torch.empty(B, Hp, Wp, Cc, device=x.device, dtype=torch.uint8 if u8 else torch.float32)
+    if u8:
+        y = torch.empty(B, Hp, Wp, Cc, device=x.device, dtype=torch.uint8)
+    else:       # the fp32 copy and, behind it, this call's exactness word (one per y: the stem's weight gradient reads it at the far end of the step)
+        n = B * Hp * Wp * Cc
+        buf = torch.empty(n + 4, device=x.device, dtype=torch.float32)
+        y = buf[:n].view(B, Hp, Wp, Cc)
+        y.sast_nonexact = buf[n:n + 1].view(torch.int32)
     try:
         if u8:
             L.check(L.lib().sast_input_prep_u8(x.data_ptr(), B, Cc, H, W, Hp, Wp, ws.data_ptr(), r.data_ptr(), y.data_ptr(), _stream()), "input_prep_u8")
         else:
-            L.check(L.lib().sast_input_prep(x.data_ptr(), _DT[x.dtype], B, Cc, H, W, Hp, Wp, ws.data_ptr(), r.data_ptr(), y.data_ptr(), _stream()), "input_prep")
+            L.check(L.lib().sast_input_prep_flag(x.data_ptr(), _DT[x.dtype], B, Cc, H, W, Hp, Wp, ws.data_ptr(), r.data_ptr(), y.data_ptr(),
+                                                 y.sast_nonexact.data_ptr(), _stream()), "input_prep")
     except Exception:
         cache.pop(key, None)         # a failed launch may leave counters / the ticket non-zero: never reuse this buffer
         raise
@@ -401,7 +412,7 @@ def downsample_out_hw(H: int, W: int, factor: int, k: int) -> Tuple[int, int]:
 
 class _DownsampleLN(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, w, ln_w, ln_b, pe, factor):
+    def forward(ctx, x, w, ln_w, ln_b, pe, factor, nonexact=None):
         _need_gpu(x, w)
         x = x.contiguous()
         if not is_channels_last_weight(w):
@@ -423,9 +434,10 @@ class _DownsampleLN(torch.autograd.Function):
             raise RuntimeError("sast_amd: downsample_ln reads fp32 rows, or (the stem) the uint8 event tensor from input_prep(keep_bytes=True)")
         xdt = _DT[x.dtype]
         a = _fill(L.SastDownArgs(), B=B, H=H, W=W, Cin=Cin, Cout=Cout, factor=factor, x=x, w=w, ln_w=ln_w, ln_b=ln_b,
-                  pe=_ptr(pe), conv_out=conv_out, mean=stats[0], rstd=stats[1], y=y, x_dtype=xdt, no_overlap=no_overlap)
+                  pe=_ptr(pe), conv_out=conv_out, mean=stats[0], rstd=stats[1], y=y, x_dtype=xdt, no_overlap=no_overlap, x_nonexact=_ptr(nonexact))
         L.check(L.lib().sast_downsample_ln_fwd(C.byref(a), _stream()), "downsample_ln_fwd")
         ctx.save_for_backward(x, conv_out, stats)
+        ctx.nonexact = nonexact
         ctx.params = (w, ln_w, ln_b)
         ctx.meta = (B, H, W, Cin, Cout, factor, xdt, no_overlap)
         return y
@@ -441,15 +453,17 @@ class _DownsampleLN(torch.autograd.Function):
         pg = _ParamGrads(w, ln_w, ln_b)
         a = _fill(L.SastDownArgs(), B=B, H=H, W=W, Cin=Cin, Cout=Cout, factor=factor, x=x, w=w, ln_w=ln_w, ln_b=ln_b,
                   conv_out=conv_out, mean=stats[0], rstd=stats[1], dy=dy, dx=_ptr(dx), dw=pg[0], d_ln_w=pg[1], d_ln_b=pg[2], ws=ws,
-                  x_dtype=xdt, no_overlap=no_overlap)
+                  x_dtype=xdt, no_overlap=no_overlap, x_nonexact=_ptr(ctx.nonexact))
         L.check(L.lib().sast_downsample_ln_bwd(C.byref(a), _stream()), "downsample_ln_bwd")
-        _dw_hold((x, conv_out, stats, dy, ws, pg))
-        return (dx,) + pg.out() + (None, None)
+        _dw_hold((x, conv_out, stats, dy, ws, pg, ctx.nonexact))
+        return (dx,) + pg.out() + (None, None, None)
 
 
 def downsample_ln(x_nhwc, w, ln_w, ln_b, pe, factor):
     downsample_out_hw(x_nhwc.shape[1], x_nhwc.shape[2], factor, w.shape[-1])     # refuses a bad size before anything touches the library
-    return _DownsampleLN.apply(x_nhwc, w, ln_w, ln_b, pe, factor)
+    # the exactness word input_prep wrote for the event tensor (stem only; any other input: None = nothing known, the six-term GEMMs)
+    nonexact = getattr(x_nhwc, "sast_nonexact", None) if x_nhwc.dtype == torch.float32 and x_nhwc.is_contiguous() else None
+    return _DownsampleLN.apply(x_nhwc, w, ln_w, ln_b, pe, factor, nonexact)
 
 
 class _MaskToken(torch.autograd.Function):
