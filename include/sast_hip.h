@@ -508,6 +508,52 @@ int sast_augment_frames(const uint8_t* in, uint8_t* out, const int32_t* params, 
 int sast_augment_labels(const float* labels, const int32_t* counts, const int32_t* params, int N, int B, int M, int W, float* out,
                         int32_t* counts_out, float* yolox, sast_stream_t stream);
 
+/* ---- Prophesee mAP evaluation of detections (csrc/k_eval.hip).  The reference converts every validation step's labels and detections
+ * to numpy (to_prophesee, utils/evaluation/prophesee/io/box_loading.py:58-99), buffers them in PropheseeEvaluator and at epoch end runs
+ * filter_boxes (io/box_filtering.py), _match_times / _to_coco_format (metrics/coco_eval.py) and pycocotools' COCOeval (bbox, useCats,
+ * maxDets 100).  Here the buffer lives on the device: sast_eval_add filters, flattens and MATCHES the frames it is given (COCOeval.evaluate
+ * is per image) and appends one record per kept detection; sast_eval_accumulate sorts the records and computes COCOeval.accumulate /
+ * summarize.  Nothing synchronises with the host; what does not fit a capacity is counted in the state words, never dropped silently.
+ *   state  int32 [SAST_EVAL_STATE_WORDS]: 0 images, 1 ground-truth rows, 2 detection rows, 3 records, 4..7 records per category,
+ *          8 frames refused for max_images, 9 for max_detections, 10 for max_labels_per_frame, 11 sast_eval_add calls since the reset,
+ *          12.. non-ignored ground truths [K][4]
+ *   tables gt_box fp32 [max_images * max_labels_per_frame][4] (x, y, w, h), gt_cls / gt_img int32; det_box fp32 [max_detections][5]
+ *          (x, y, w, h, score), det_cls / det_img int32; img_t int64 [max_images]: image i is the i-th frame that kept a label
+ *   records rec_key / rec_match / rec_ign uint64 [max_detections]: bit (area * 10 + threshold) of match / ignore; key = category << 62 |
+ *          ~(order-preserving bits of the score) << 30 | record index
+ *   precision fp64 [10][101][K][4] (COCOeval.eval['precision'] at maxDets 100), result fp64 [8 + SAST_EVAL_STATE_WORDS]: AP, AP_50, AP_75,
+ *          AP_S, AP_M, AP_L, 2 unused, then the state words
+ * iou_thr: the 10 doubles of np.linspace(.5, .95, 10); rec_thr: the 101 of np.linspace(0, 1, 101).  A <= 8192, max_labels_per_frame <= 128,
+ * K <= 4, max_detections < 2^30. */
+#define SAST_EVAL_STATE_WORDS 32
+#define SAST_EVAL_MAX_CLASSES 4
+#define SAST_EVAL_IOU_THRS 10
+#define SAST_EVAL_REC_THRS 101
+#define SAST_EVAL_AREAS 4
+typedef struct {
+  const float* labels;    /* [N, M, 7] (t, x, y, w, h, class_id, class_confidence) */
+  const int32_t* counts;  /* [N] valid rows; 0: not a frame */
+  const float* det;       /* [N, A, 7] (x1, y1, x2, y2, obj_conf, class_conf, class_pred): sast_postprocess's out */
+  const int32_t* n_det;   /* [N] */
+  int32_t N, M, A, K;
+  float min_diag2, min_side; /* filter_boxes: w*w + h*h >= min_diag2, w >= min_side, h >= min_side */
+  int32_t max_images, max_labels_per_frame;
+  int64_t max_detections;
+  int32_t* state;
+  int32_t* info;          /* scratch of one add: int32 [N][16] */
+  float* gt_box; int32_t* gt_cls; int32_t* gt_img; int64_t* img_t;
+  float* det_box; int32_t* det_cls; int32_t* det_img;
+  uint64_t* rec_key; uint64_t* rec_match; uint64_t* rec_ign;
+  const double* iou_thr; const double* rec_thr;
+  uint64_t* sorted;       /* [max_detections] */
+  void* sort_ws; size_t sort_ws_bytes; /* sast_eval_sort_ws_bytes(max_detections) */
+  double* precision; double* result;
+} SastEvalArgs;
+int sast_eval_reset(const SastEvalArgs* a, sast_stream_t stream);
+int sast_eval_add(const SastEvalArgs* a, sast_stream_t stream);
+size_t sast_eval_sort_ws_bytes(int64_t max_detections);
+int sast_eval_accumulate(const SastEvalArgs* a, sast_stream_t stream);
+
 /* ---- tuning knobs.  Every SAST_* environment variable the library reads (tile / split / launch-shape choices, all defaulting to the
  * measured-best setting: DESIGN.md section 7) goes through one registry: the value is read from the environment at first use and cached;
  * sast_config_reload() makes every call site re-read its knob at its next use (a host that sets os.environ inside the process calls

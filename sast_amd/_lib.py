@@ -23,6 +23,8 @@ EVENT_WINDOW_DURATION, EVENT_WINDOW_COUNT = 0, 1
 EVENT_SCAN_BLOCKS = 512   # SAST_EVENT_SCAN_BLOCKS
 AUGMENT_PARAM_WORDS = 16  # SAST_AUGMENT_PARAM_WORDS
 AUGMENT_NONE, AUGMENT_ZOOM_IN, AUGMENT_ZOOM_OUT = 0, 1, 2
+EVAL_STATE_WORDS, EVAL_MAX_CLASSES = 32, 4   # SAST_EVAL_STATE_WORDS, SAST_EVAL_MAX_CLASSES
+EVAL_IOU_THRS, EVAL_REC_THRS, EVAL_AREAS = 10, 101, 4
 
 
 def _struct(name, spec):
@@ -80,6 +82,12 @@ SastSampleMask = _struct("SastSampleMask", [(C.c_uint8 * 256, "sel")])
 SastEventArgs = _struct("SastEventArgs", [
     (P, "x y p t bounds out err ws"), (C.c_int64, "capacity window_capacity"),
     (I32, "x_dtype y_dtype p_dtype t_dtype B bins height width count_cutoff fastmode downsample_by_2 clip_negative_polarity"),
+])
+SastEvalArgs = _struct("SastEvalArgs", [
+    (P, "labels counts det n_det"), (I32, "N M A K"), (F32, "min_diag2 min_side"), (I32, "max_images max_labels_per_frame"),
+    (C.c_int64, "max_detections"),
+    (P, "state info gt_box gt_cls gt_img img_t det_box det_cls det_img rec_key rec_match rec_ign iou_thr rec_thr sorted sort_ws"),
+    (C.c_size_t, "sort_ws_bytes"), (P, "precision result"),
 ])
 
 _SIGNATURES = {
@@ -154,6 +162,10 @@ _SIGNATURES = {
     "sast_event_frames": (C.c_int, [C.POINTER(SastEventArgs), P]),
     "sast_augment_frames": (C.c_int, [P, P, P] + [C.c_int] * 5 + [P]),
     "sast_augment_labels": (C.c_int, [P, P, P] + [C.c_int] * 4 + [P, P, P, P]),
+    "sast_eval_reset": (C.c_int, [C.POINTER(SastEvalArgs), P]),
+    "sast_eval_add": (C.c_int, [C.POINTER(SastEvalArgs), P]),
+    "sast_eval_sort_ws_bytes": (C.c_size_t, [C.c_int64]),
+    "sast_eval_accumulate": (C.c_int, [C.POINTER(SastEvalArgs), P]),
 }
 
 _lib = None

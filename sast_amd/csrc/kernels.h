@@ -85,4 +85,6 @@ size_t mswsa_fused_plane_floats(int C, int inner);
 int mswsa_fused_planes_launch(const SastMswsaArgs* a, float* planes, hipStream_t st);
 int mswsa_fused_fwd_launch(const SastMswsaArgs* a, const float* planes, hipStream_t st);
 
+// k_eval.hip: the Prophesee mAP evaluator has no internal launchers, only the sast_eval_* entry points of include/sast_hip.h
+
 }  // namespace sast

@@ -1,0 +1,203 @@
+"""Prophesee mAP evaluation of detections on the GPU (csrc/k_eval.hip).
+
+The reference copies every validation step's labels and detections to the host (to_prophesee, utils/evaluation/prophesee/io/
+box_loading.py:58-99), buffers them in PropheseeEvaluator (evaluator.py) and at epoch end runs filter_boxes, _match_times,
+_to_coco_format and pycocotools' COCOeval in Python (evaluation.py, metrics/coco_eval.py).  `PropheseeEvaluator` here keeps the buffer
+on the device: `add` takes the label tensors `SpatialAugmentor` returns and the padded detections of
+`sast_amd.functional.postprocess_padded`, filters, flattens and matches them (COCOeval.evaluate is per image), and
+`evaluate_buffer` sorts the per-detection records and computes COCOeval's precision table and the six numbers of coco_eval.py:109.
+
+- `add` enqueues three launches and synchronises nothing: cursors, counts and overflow counters live in device memory, so after one
+  eager call it can be captured in a graph together with the detector.
+- Each added frame is its own "file" of the reference's _match_times: a frame none of whose labels passes the filter is no image and
+  its detections vanish with it; image ids follow the order of `add` calls and of the rows within a call.
+- What does not fit `max_images`, `max_detections` (filtered detections over the whole buffer) or `max_labels_per_frame` (filtered
+  labels of one frame) is counted on the device and raised by `evaluate_buffer`, never dropped silently.
+- Not implemented: the multi-timestamp form of _match_times (to_prophesee asserts one timestamp per entry), AR and maxDets 1 / 10
+  (the reference discards them), merging across ranks, visualisation.
+
+There is no CPU path: CPU tensors raise the library's "no CPU fallback" error.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Dict, Optional
+from warnings import warn
+
+import numpy as np
+import torch
+
+from . import _lib as L
+from .functional import _need_gpu, _stream
+
+OUT_KEYS = ('AP', 'AP_50', 'AP_75', 'AP_S', 'AP_M', 'AP_L')   # coco_eval.py:109
+CLASSES = {'gen1': ("car", "pedestrian"), 'gen4': ("pedestrian", "two-wheeler", "car")}   # evaluation.py:15-18
+IOU_THRS = np.linspace(.5, 0.95, int(np.round((0.95 - .5) / .05)) + 1, endpoint=True)      # pycocotools Params.setDetParams
+REC_THRS = np.linspace(.0, 1.00, int(np.round((1.00 - .0) / .01)) + 1, endpoint=True)
+MAX_ANCHORS, MAX_LABELS_PER_FRAME = 8192, 128
+
+
+class PropheseeEvaluator:
+    """ev = PropheseeEvaluator(dataset, downsample_by_2, max_images, max_detections, max_labels_per_frame)
+      dataset: 'gen1' (car, pedestrian) or 'gen4' (pedestrian, two-wheeler, car); the box filter is diag 30 / side 10 for gen1 and
+      60 / 20 for gen4, halved with downsample_by_2.
+    ev.add(labels, counts, det, n_det)
+      labels fp32 [N, M, 7] rows (t, x, y, w, h, class_id, class_confidence), counts int32 [N] (0: not a frame), det fp32 [N, A, 7] and
+      n_det int32 [N] as `postprocess_padded` returns them for the same N frames.
+    ev.evaluate_buffer(img_height, img_width) -> {'AP', 'AP_50', 'AP_75', 'AP_S', 'AP_M', 'AP_L'} as Python floats (one sync, at the end)
+    ev.precision() -> fp64 [10, 101, K, 4] of the last evaluate_buffer; ev.tables() -> the flattened image / annotation / result records
+    ev.reset_buffer(), ev.has_data() as in the reference."""
+
+    def __init__(self, dataset: str, downsample_by_2: bool, max_images: int = 65536, max_detections: int = 1 << 22,
+                 max_labels_per_frame: int = 64):
+        assert dataset in {'gen1', 'gen4'}
+        self.dataset = dataset
+        self.downsample_by_2 = bool(downsample_by_2)
+        self.classes = CLASSES[dataset]
+        self.max_images, self.max_detections, self.max_labels_per_frame = int(max_images), int(max_detections), int(max_labels_per_frame)
+        if self.max_images < 1 or not 1 <= self.max_detections < (1 << 30) or not 1 <= self.max_labels_per_frame <= MAX_LABELS_PER_FRAME:
+            raise ValueError(f"sast_amd.evaluation: capacities must be max_images >= 1, 1 <= max_detections < 2^30, "
+                             f"1 <= max_labels_per_frame <= {MAX_LABELS_PER_FRAME}")
+        if self.max_images * self.max_labels_per_frame >= (1 << 31):
+            raise ValueError("sast_amd.evaluation: max_images * max_labels_per_frame must stay below 2^31")
+        min_box_diag = 60 if dataset == 'gen4' else 30          # evaluation.py:24-31
+        min_box_side = 20 if dataset == 'gen4' else 10
+        if self.downsample_by_2:
+            min_box_diag //= 2
+            min_box_side //= 2
+        self.min_box_diag, self.min_box_side = min_box_diag, min_box_side
+        self._buffer_empty = True
+        self._dev: Optional[torch.device] = None
+        self._t: Dict[str, torch.Tensor] = {}
+        self._args = L.SastEvalArgs()
+        self._evaluated = False
+
+    # ------------------------------------------------------------------------------------------------------------------ buffers
+    def _allocate(self, dev: torch.device):
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("sast_amd.evaluation: one un-captured call is needed before graph capture (it allocates the buffers)")
+        K, D, G = len(self.classes), self.max_detections, self.max_images * self.max_labels_per_frame
+        ws_bytes = int(L.lib().sast_eval_sort_ws_bytes(D))
+        if ws_bytes == 0:
+            raise RuntimeError("sast_amd.evaluation: the library refused the sort workspace size")
+
+        def e(shape, dt):
+            return torch.empty(shape, dtype=dt, device=dev)
+
+        t = self._t = {
+            "state": e(L.EVAL_STATE_WORDS, torch.int32),
+            "gt_box": e((G, 4), torch.float32), "gt_cls": e(G, torch.int32), "gt_img": e(G, torch.int32),
+            "img_t": e(self.max_images, torch.int64),
+            "det_box": e((D, 5), torch.float32), "det_cls": e(D, torch.int32), "det_img": e(D, torch.int32),
+            "rec_key": e(D, torch.int64), "rec_match": e(D, torch.int64), "rec_ign": e(D, torch.int64), "sorted": e(D, torch.int64),
+            "sort_ws": e(ws_bytes, torch.uint8),
+            "iou_thr": torch.from_numpy(IOU_THRS).to(dev), "rec_thr": torch.from_numpy(REC_THRS).to(dev),
+            "precision": e((L.EVAL_IOU_THRS, L.EVAL_REC_THRS, K, L.EVAL_AREAS), torch.float64),
+            "result": e(8 + L.EVAL_STATE_WORDS, torch.float64),
+        }
+        a = self._args
+        for name in ("state", "gt_box", "gt_cls", "gt_img", "img_t", "det_box", "det_cls", "det_img", "rec_key", "rec_match", "rec_ign",
+                     "sorted", "sort_ws", "iou_thr", "rec_thr", "precision", "result"):
+            setattr(a, name, t[name].data_ptr())
+        a.sort_ws_bytes = ws_bytes
+        a.K = K
+        a.min_diag2, a.min_side = float(self.min_box_diag ** 2), float(self.min_box_side)
+        a.max_images, a.max_labels_per_frame, a.max_detections = self.max_images, self.max_labels_per_frame, self.max_detections
+        self._dev = dev
+        L.check(L.lib().sast_eval_reset(C.byref(a), _stream()), "eval_reset")
+
+    def reset_buffer(self) -> None:
+        """empties the buffer (e.g. in on_validation_epoch_start): one launch, no sync"""
+        self._buffer_empty = True
+        self._evaluated = False
+        if self._dev is not None:
+            L.check(L.lib().sast_eval_reset(C.byref(self._args), _stream()), "eval_reset")
+
+    def has_data(self) -> bool:
+        """True after an `add` since the last reset.  Adds of a replayed graph are not seen by the host: when it knows of none, the
+        device's count of adds is read (a synchronisation, on that path only)."""
+        if not self._buffer_empty:
+            return True
+        return self._dev is not None and int(self._t["state"][11]) > 0
+
+    # ---------------------------------------------------------------------------------------------------------------------- add
+    def add(self, labels: torch.Tensor, counts: torch.Tensor, det: torch.Tensor, n_det: torch.Tensor) -> None:
+        _need_gpu(labels, counts, det, n_det)
+        if labels.dtype != torch.float32 or labels.dim() != 3 or labels.shape[-1] != 7:
+            raise TypeError("sast_amd.evaluation: labels must be fp32 [N, M, 7]")
+        N, M = int(labels.shape[0]), int(labels.shape[1])
+        if counts.dtype != torch.int32 or tuple(counts.shape) != (N,):
+            raise TypeError("sast_amd.evaluation: counts must be int32 [N]")
+        if det.dtype != torch.float32 or det.dim() != 3 or det.shape[0] != N or det.shape[-1] != 7:
+            raise TypeError("sast_amd.evaluation: det must be fp32 [N, A, 7] for the same N frames")
+        A = int(det.shape[1])
+        if n_det.dtype != torch.int32 or tuple(n_det.shape) != (N,):
+            raise TypeError("sast_amd.evaluation: n_det must be int32 [N]")
+        if not 1 <= N <= 65535 or M < 1 or not 1 <= A <= MAX_ANCHORS:
+            raise ValueError(f"sast_amd.evaluation: need 1 <= N <= 65535 frames, M >= 1 label rows and 1 <= A <= {MAX_ANCHORS} detection rows")
+        if len({labels.device, counts.device, det.device, n_det.device}) != 1:
+            raise ValueError("sast_amd.evaluation: labels, counts, det and n_det must be on the same device")
+        if self._dev is None:
+            self._allocate(labels.device)
+        elif labels.device != self._dev:
+            raise ValueError("sast_amd.evaluation: the buffer lives on another device")
+        labels, counts, det, n_det = labels.contiguous(), counts.contiguous(), det.contiguous(), n_det.contiguous()
+        info = torch.empty(N * 16, dtype=torch.int32, device=self._dev)
+        a = self._args
+        a.labels, a.counts, a.det, a.n_det, a.info = labels.data_ptr(), counts.data_ptr(), det.data_ptr(), n_det.data_ptr(), info.data_ptr()
+        a.N, a.M, a.A = N, M, A
+        L.check(L.lib().sast_eval_add(C.byref(a), _stream()), "eval_add")
+        self._buffer_empty = False
+        self._evaluated = False
+
+    # ----------------------------------------------------------------------------------------------------------------- evaluate
+    def evaluate_buffer(self, img_height: int, img_width: int) -> Optional[Dict[str, float]]:
+        """the six COCO numbers of everything added since the last reset (e.g. in on_validation_epoch_end).  img_height / img_width
+        are the reference's arguments: they only fill the image records of its COCO dataset and enter no number."""
+        if self._dev is None:
+            warn("Attempt to use prophesee evaluation buffer, but it is empty", UserWarning, stacklevel=2)
+            return None
+        L.check(L.lib().sast_eval_accumulate(C.byref(self._args), _stream()), "eval_accumulate")
+        res = self._t["result"].cpu().numpy()        # the one synchronisation
+        state = res[8:].astype(np.int64)
+        self._state = state
+        if self._buffer_empty and state[11] == 0:    # no add by the host and none by a replayed graph (the device counts them)
+            warn("Attempt to use prophesee evaluation buffer, but it is empty", UserWarning, stacklevel=2)
+            return None
+        refused = {"max_images": int(state[8]), "max_detections": int(state[9]), "max_labels_per_frame": int(state[10])}
+        if any(refused.values()):
+            raise OverflowError("sast_amd.evaluation: frames did not fit the buffer and were not evaluated -- "
+                                + ", ".join(f"{v} frame(s) refused for {k}={getattr(self, k)}" for k, v in refused.items() if v))
+        self._evaluated = True
+        if state[2] == 0:                            # coco_eval.py:112-115: no detection in any image
+            return {k: 0.0 for k in OUT_KEYS}
+        return {k: float(res[i]) for i, k in enumerate(OUT_KEYS)}
+
+    def precision(self) -> torch.Tensor:
+        """COCOeval.eval['precision'][:, :, :, :, 2] (maxDets 100) of the last evaluate_buffer: fp64 [T=10, R=101, K, A=4] on the device"""
+        if not self._evaluated:
+            raise RuntimeError("sast_amd.evaluation: precision() follows a successful evaluate_buffer()")
+        return self._t["precision"].clone()
+
+    def tables(self) -> Dict[str, np.ndarray]:
+        """the flattened records of _to_coco_format (coco_eval.py:143-194) as numpy arrays (synchronises):
+        image_t int64 [I] (image id i + 1 is row i); gt_image_id, gt_category_id int64 [G], gt_bbox fp32 [G, 4] (x, y, w, h), gt_area fp64;
+        dt_image_id, dt_category_id int64 [D], dt_score fp32, dt_bbox fp32 [D, 4], dt_area fp64 (what COCO.loadRes adds)"""
+        if self._dev is None:
+            raise RuntimeError("sast_amd.evaluation: nothing was added")
+        t = self._t
+        st = t["state"].cpu().numpy()
+        ni, ng, nd = int(st[0]), int(st[1]), int(st[2])
+        gb, db = t["gt_box"][:ng].cpu().numpy(), t["det_box"][:nd].cpu().numpy()
+        return {
+            "image_t": t["img_t"][:ni].cpu().numpy(),
+            "gt_image_id": t["gt_img"][:ng].cpu().numpy().astype(np.int64) + 1,
+            "gt_category_id": t["gt_cls"][:ng].cpu().numpy().astype(np.int64) + 1,
+            "gt_bbox": gb,
+            "gt_area": (gb[:, 2] * gb[:, 3]).astype(np.float64),          # the fp32 product, widened (coco_eval.py:167, :172)
+            "dt_image_id": t["det_img"][:nd].cpu().numpy().astype(np.int64) + 1,
+            "dt_category_id": t["det_cls"][:nd].cpu().numpy().astype(np.int64) + 1,
+            "dt_score": db[:, 4].copy(),
+            "dt_bbox": db[:, :4].copy(),
+            "dt_area": (db[:, 2] * db[:, 3]).astype(np.float64),
+        }

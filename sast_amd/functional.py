@@ -1837,3 +1837,20 @@ def postprocess(prediction: torch.Tensor, num_classes: int, conf_thre: float = 0
                                      n_out.data_ptr(), ws.data_ptr(), _stream()), "postprocess")
     counts = n_out.tolist()
     return [out[b, :n].clone() if n else None for b, n in enumerate(counts)]
+
+
+@torch.no_grad()
+def postprocess_padded(prediction: torch.Tensor, num_classes: int, conf_thre: float = 0.7, nms_thre: float = 0.45, class_agnostic: bool = False):
+    """`postprocess` without its host sync: the same launch, returned as it is on the device -> (out [B, A, 7] fp32, n_out [B] int32);
+    the first n_out[b] rows of out[b] are image b's detections by decreasing score (the rows `postprocess` clones), the rest is
+    uninitialised.  What `sast_amd.evaluation.PropheseeEvaluator.add` takes; can be captured in a graph."""
+    _need_gpu(prediction)
+    prediction = prediction.float().contiguous()
+    B, A, no = prediction.shape
+    assert no == 5 + num_classes
+    out = torch.empty(B, A, 7, device=prediction.device)
+    n_out = torch.empty(B, device=prediction.device, dtype=torch.int32)
+    ws = torch.empty(L.lib().sast_postprocess_ws_bytes(B, A), device=prediction.device, dtype=torch.uint8)
+    L.check(L.lib().sast_postprocess(prediction.data_ptr(), B, A, num_classes, float(conf_thre), float(nms_thre), int(bool(class_agnostic)), out.data_ptr(),
+                                     n_out.data_ptr(), ws.data_ptr(), _stream()), "postprocess")
+    return out, n_out
