@@ -481,6 +481,27 @@ typedef struct SastEventArgs {
 size_t sast_event_frames_ws_bytes(int B, int bins, int height, int width, int downsample_by_2, int64_t window_capacity); /* 0: unsupported */
 int sast_event_frames(const SastEventArgs* a, sast_stream_t stream);
 
+/* ---- S recordings side by side: event buffers [S, stream_capacity], row s one recording with counts[s] valid events at its head
+ * (int64 [S] in device memory), its own time-correction carry t_last[s] and its own windows.  The two calls below are the per-row
+ * forms of sast_event_correct_time / sast_event_window_bounds; sast_event_frames is then called unchanged with B = T * S windows,
+ * capacity = S * stream_capacity and these bounds.  A window never spans two rows: both of its bounds lie in
+ * [s * stream_capacity, s * stream_capacity + n_s], n_s = min(max(counts[s], 0), stream_capacity), so events past a row's count are
+ * never read.  Each call is a fixed number of launches (2 and 1) whatever S is; the grids are sized from S and stream_capacity. */
+
+/* int64 elements of the `ws` of sast_evstreams_correct_time (0: S < 1 or S > 65535) */
+size_t sast_evstreams_ws_count(int S);
+/* per row s: t_out[s][i] = max(t[s][i], carry_s, t[s][0..i-1]) for i < n_s, then t_last[s] = that running maximum;  carry_s =
+ * t_last[s], or 0 when reset != NULL and reset[s] != 0 (uint8 [S] in device memory: a new recording starts in row s with this call).
+ * A row with n_s == 0 leaves t_last[s] = carry_s.  t: SAST_DT_I64 / I32 [S, stream_capacity]; t_out int64 [S, stream_capacity], may
+ * alias t when t is int64.  The running maximum never crosses from one row into the next. */
+int sast_evstreams_correct_time(const void* t, int t_dtype, const int64_t* counts, int S, int64_t stream_capacity, int64_t* t_out,
+                                int64_t* t_last, const uint8_t* reset, int64_t* ws, sast_stream_t stream);
+/* window w = k * S + s (ends_us int64 [T, S]) over the sorted t[s][0 .. n_s): the search of sast_event_window_bounds inside row s, as
+ * absolute indices into the flattened buffer (s * stream_capacity + local).  SAST_EVENT_WINDOW_COUNT clips at the start of the row:
+ * start = max(end - value, s * stream_capacity).  bounds: int64 [T * S, 2]. */
+int sast_evstreams_window_bounds(const int64_t* t, const int64_t* counts, int S, int64_t stream_capacity, const int64_t* ends_us, int T,
+                                 int mode, int64_t value, int64_t* bounds, sast_stream_t stream);
+
 /* ---- spatial augmentation of event frames and box labels (csrc/k_augment.hip).  The reference augments on the CPU in its data-loader
  * workers: RandomSpatialAugmentorGenX.__call__ (data/utils/augmentor.py:347-364) -- horizontal flip, then zoom-in (:203-222) or zoom-out
  * (:134-153) -- with the label transforms of ObjectLabels (data/genx_utils/labels.py:255-339).  Both calls read the per-sample

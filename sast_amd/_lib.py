@@ -160,6 +160,9 @@ _SIGNATURES = {
     "sast_event_window_bounds": (C.c_int, [P, P, C.c_int64, P, C.c_int, C.c_int, C.c_int64, P, P]),
     "sast_event_frames_ws_bytes": (C.c_size_t, [C.c_int] * 5 + [C.c_int64]),
     "sast_event_frames": (C.c_int, [C.POINTER(SastEventArgs), P]),
+    "sast_evstreams_ws_count": (C.c_size_t, [C.c_int]),
+    "sast_evstreams_correct_time": (C.c_int, [P, C.c_int, P, C.c_int, C.c_int64, P, P, P, P, P]),
+    "sast_evstreams_window_bounds": (C.c_int, [P, P, C.c_int, C.c_int64, P, C.c_int, C.c_int, C.c_int64, P, P]),
     "sast_augment_frames": (C.c_int, [P, P, P] + [C.c_int] * 5 + [P]),
     "sast_augment_labels": (C.c_int, [P, P, P] + [C.c_int] * 4 + [P, P, P, P]),
     "sast_eval_reset": (C.c_int, [C.POINTER(SastEvalArgs), P]),

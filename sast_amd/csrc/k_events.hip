@@ -7,6 +7,8 @@
 //   sast_event_window_bounds  per window two binary searches (duration mode) or one (count mode) -> int64 [B, 2] event ranges
 //   sast_event_frames         the histogram: bucket each window's events by 32-column spatial tile (count -> scan -> scatter of packed
 //                             records), then one workgroup per (window, tile) counts its records in LDS and writes the finished uint8 tile
+//   sast_evstreams_*          the first two for S recordings side by side ([S, capacity] buffers, one count / carry per row), in the
+//                             same number of launches; their bounds index the flattened buffer, so sast_event_frames serves unchanged
 // Integer counts do not depend on arrival order: the frames are bitwise reproducible.  Every per-frame size (event count, window
 // bounds, carry) is read on the device; the grids are sized from capacities, so a captured graph replays on new events.
 #include <climits>
@@ -321,6 +323,80 @@ __global__ void ev_bounds_kernel(const long long* t, const long long* n_dev, lon
   bounds[2 * b + 1] = e;
 }
 
+// ---- S recordings side by side: [S, cap] buffers, row blockIdx.y one recording with its own count, carry and windows.  The same two
+// passes as above with gridDim.x blocks per row: a row's partial maxima and its carry live in its own ws row
+// (ws[s][0] = carry in, ws[s][1 + blk] = the maximum of block blk's chunk of row s), so no maximum is ever taken across rows.
+constexpr int EV_ROW_WS = EV_SCAN_BLOCKS + 1;
+constexpr int EV_ROW_EVENTS_PER_BLOCK = 4096;
+
+__global__ __launch_bounds__(EV_THREADS) void ev_rows_tmax_partial_kernel(const void* t, int dt, const long long* counts, long long cap,
+                                                                          const long long* t_last, const unsigned char* reset,
+                                                                          long long* ws) {
+  __shared__ long long red[EV_THREADS / 64];
+  const int s = blockIdx.y;
+  const long long n = min(max(counts[s], 0LL), cap), row = (long long)s * cap;
+  long long lo, hi;
+  ev_tchunk(n, &lo, &hi);
+  long long m = LLONG_MIN;
+  for (long long i = lo + threadIdx.x; i < hi; i += EV_THREADS) m = max(m, ld_int(t, dt, row + i));
+  m = block_max(m, red);
+  if (threadIdx.x == 0) {
+    long long* w = ws + (size_t)s * EV_ROW_WS;
+    w[1 + blockIdx.x] = m;
+    if (blockIdx.x == 0) w[0] = (reset && reset[s]) ? 0LL : t_last[s];
+  }
+}
+
+__global__ __launch_bounds__(EV_THREADS) void ev_rows_tmax_apply_kernel(const void* t, int dt, const long long* counts, long long cap,
+                                                                        const long long* ws_all, long long* t_out, long long* t_last) {
+  __shared__ long long red[EV_THREADS / 64];
+  __shared__ long long wtot[EV_THREADS / 64];
+  const int s = blockIdx.y;
+  const long long n = min(max(counts[s], 0LL), cap), row = (long long)s * cap;
+  const long long* ws = ws_all + (size_t)s * EV_ROW_WS;
+  long long lo, hi;
+  ev_tchunk(n, &lo, &hi);
+  long long carry = LLONG_MIN;
+  for (int k = threadIdx.x; k < (int)blockIdx.x + 1; k += EV_THREADS) carry = max(carry, ws[k]);
+  carry = block_max(carry, red);
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  for (long long base = lo; base < hi; base += EV_THREADS) {
+    const long long i = base + threadIdx.x;
+    long long v = i < hi ? ld_int(t, dt, row + i) : LLONG_MIN;
+    for (int d = 1; d < 64; d <<= 1) {                    // inclusive max-scan of the wave
+      const long long u = __shfl_up(v, d);
+      if (lane >= d) v = max(v, u);
+    }
+    __syncthreads();
+    if (lane == 63) wtot[wv] = v;
+    __syncthreads();
+    long long pre = carry;
+    for (int k = 0; k < wv; ++k) pre = max(pre, wtot[k]);
+    v = max(v, pre);
+    if (i < hi) t_out[row + i] = v;
+    for (int k = wv; k < EV_THREADS / 64; ++k) pre = max(pre, wtot[k]);
+    carry = pre;
+  }
+  // an empty row has only LLONG_MIN partials: t_last[s] = the carry in (0 after a reset)
+  if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) {
+    long long m = ws[0];
+    for (int k = 1; k <= (int)gridDim.x; ++k) m = max(m, ws[k]);
+    t_last[s] = m;
+  }
+}
+
+__global__ void ev_rows_bounds_kernel(const long long* t, const long long* counts, int S, long long cap, const long long* ends, int B,
+                                      int mode, long long value, long long* bounds) {
+  const int w = blockIdx.x * blockDim.x + threadIdx.x;     // window k * S + s
+  if (w >= B) return;
+  const int s = w % S;
+  const long long n = min(max(counts[s], 0LL), cap), row = (long long)s * cap;
+  const long long e = search(t + row, n, ends[w], true);
+  const long long b = mode == SAST_EVENT_WINDOW_COUNT ? max(e - value, 0LL) : search(t + row, n, ends[w] - value, false);
+  bounds[2 * w] = row + b;
+  bounds[2 * w + 1] = row + e;
+}
+
 bool int_dtype(int dt) { return dt == SAST_DT_I64 || dt == SAST_DT_I32 || dt == SAST_DT_I16; }
 
 // geometry of a call, or false for arguments the kernels do not take
@@ -390,6 +466,43 @@ int sast_event_window_bounds(const int64_t* t, const int64_t* n, int64_t capacit
   SAST_LAUNCH(ev_bounds_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, reinterpret_cast<const long long*>(t),
               reinterpret_cast<const long long*>(n), (long long)capacity, reinterpret_cast<const long long*>(ends_us), B, mode,
               (long long)value, reinterpret_cast<long long*>(bounds));
+  SAST_CHECK_LAUNCH();
+  return SAST_OK;
+}
+
+size_t sast_evstreams_ws_count(int S) { return S < 1 || S > 65535 ? 0 : (size_t)S * sast::EV_ROW_WS; }
+
+int sast_evstreams_correct_time(const void* t, int t_dtype, const int64_t* counts, int S, int64_t stream_capacity, int64_t* t_out,
+                                int64_t* t_last, const uint8_t* reset, int64_t* ws, sast_stream_t stream) {
+  SAST_ENTRY();
+  using namespace sast;
+  if (!t || !counts || !t_out || !t_last || !ws || S < 1 || S > 65535 || stream_capacity < 0 ||
+      (t_dtype != SAST_DT_I64 && t_dtype != SAST_DT_I32))
+    return SAST_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  const long long per = (stream_capacity + EV_ROW_EVENTS_PER_BLOCK - 1) / EV_ROW_EVENTS_PER_BLOCK;
+  const dim3 grid((unsigned)std::min<long long>(std::max<long long>(per, 1), EV_SCAN_BLOCKS), (unsigned)S);
+  const long long* cd = reinterpret_cast<const long long*>(counts);
+  long long* w = reinterpret_cast<long long*>(ws);
+  SAST_LAUNCH(ev_rows_tmax_partial_kernel, grid, dim3(EV_THREADS), 0, st, t, t_dtype, cd, (long long)stream_capacity,
+              reinterpret_cast<const long long*>(t_last), reinterpret_cast<const unsigned char*>(reset), w);
+  SAST_LAUNCH(ev_rows_tmax_apply_kernel, grid, dim3(EV_THREADS), 0, st, t, t_dtype, cd, (long long)stream_capacity,
+              reinterpret_cast<const long long*>(w), reinterpret_cast<long long*>(t_out), reinterpret_cast<long long*>(t_last));
+  SAST_CHECK_LAUNCH();
+  return SAST_OK;
+}
+
+int sast_evstreams_window_bounds(const int64_t* t, const int64_t* counts, int S, int64_t stream_capacity, const int64_t* ends_us, int T,
+                                 int mode, int64_t value, int64_t* bounds, sast_stream_t stream) {
+  SAST_ENTRY();
+  using namespace sast;
+  if (!t || !counts || !ends_us || !bounds || S < 1 || T < 1 || (long long)S * T > INT_MAX || stream_capacity < 0 || value < 0 ||
+      (mode != SAST_EVENT_WINDOW_DURATION && mode != SAST_EVENT_WINDOW_COUNT))
+    return SAST_EINVAL;
+  const int B = S * T;
+  SAST_LAUNCH(ev_rows_bounds_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, reinterpret_cast<const long long*>(t),
+              reinterpret_cast<const long long*>(counts), S, (long long)stream_capacity, reinterpret_cast<const long long*>(ends_us), B,
+              mode, (long long)value, reinterpret_cast<long long*>(bounds));
   SAST_CHECK_LAUNCH();
   return SAST_OK;
 }

@@ -243,3 +243,138 @@ class EventFrames(_Frames):
         if check:
             _raise_on_errors(self.err)
         return out
+
+
+class EventStreams(_Frames):
+    """`EventFrames` for S recordings side by side: frames for every recording, and for T steps of each, in one call.
+
+    frames = es(x, y, p, t, counts, ends_us, reset=None, check=False, out=None)
+      x, y, p, t: contiguous [S, cap] device tensors (dtypes as in `EventFrames`), row s one recording with its events at the head of the row;
+      counts: int64 [S], the valid events of each row (what lies past them is never read);
+      ends_us: int64 [S] -> uint8 [S, 2*bins, H', W'], or int64 [T, S] -> uint8 [T, S, 2*bins, H', W'] (the layout `SpatialAugmentor` and
+        `TrainStep` take); ends_us[k, s] is a window end on recording s's own clock;
+      reset: uint8 / bool [S] device tensor, non-zero for the rows that start a new recording with this call: their time-correction carry
+        starts at 0 (the device-side counterpart of `reset(streams=...)`, for a captured call);
+      out: the uint8 tensor to write (default: a new one from the caching allocator, as `EventFrames` returns).
+    Every row has its own carry (`t_last`, int64 [S]) and its own windows: the running maximum of the time correction never crosses
+    from one row into the next, a count window stops at the start of its row.  One call is 7 library launches whatever S and T are
+    (2 time correction, 1 window search, 4 histogram; 5 with correct_time=False).  After one un-captured warm-up call with the same
+    shapes nothing is allocated but `out`, and nothing synchronises: the `bounds` tensor (`last_bounds`, int64 [T*S, 2], indices into
+    the flattened [S*cap] buffer) is kept in the object, so a call can be captured in a graph and replayed on new events, counts, ends and reset
+    flags written into the same tensors.
+    window_capacity: kept events one window may hold (default: cap, one row); the workspace holds T*S*window_capacity records.
+    `err`, `errors()`, check=True: as in `EventFrames`; the counters are global to the call, not per row."""
+
+    def __init__(self, num_streams: int, height: int, width: int, bins: int = 10, count_cutoff: Optional[int] = 10, fastmode: bool = True,
+                 duration_us: Optional[int] = None, num_events: Optional[int] = None, downsample_by_2: bool = False,
+                 correct_time: bool = True, window_capacity: Optional[int] = None):
+        super().__init__(bins, height, width, count_cutoff, fastmode, downsample_by_2)
+        if int(num_streams) < 1 or int(num_streams) > 65535:
+            raise ValueError("sast_amd.events: num_streams must be in 1 .. 65535")
+        if (duration_us is None) == (num_events is None):
+            raise ValueError("sast_amd.events: give exactly one of duration_us and num_events")
+        if (duration_us if duration_us is not None else num_events) < (0 if duration_us is not None else 1):
+            raise ValueError("sast_amd.events: duration_us must be >= 0, num_events >= 1")
+        self.num_streams = int(num_streams)
+        self.mode = L.EVENT_WINDOW_DURATION if duration_us is not None else L.EVENT_WINDOW_COUNT
+        self.value = int(duration_us if duration_us is not None else num_events)
+        self.correct_time = bool(correct_time)
+        self.window_capacity = None if window_capacity is None else int(window_capacity)
+        self.t_last: Optional[torch.Tensor] = None
+        self.err: Optional[torch.Tensor] = None
+        self.last_bounds: Optional[torch.Tensor] = None
+        self._state = {}
+
+    def _buffers(self, dev, cap: int, windows: int):
+        S = self.num_streams
+        st = self._state
+        if st.get("cap") is None or st["cap"][0] != dev or st["cap"][1] < cap:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("sast_amd.events: one un-captured warm-up call is needed before graph capture")
+            st = self._state = {"cap": (dev, cap), "t": torch.empty(max(S * cap, 1), dtype=torch.int64, device=dev),
+                                "scan": torch.empty(int(L.lib().sast_evstreams_ws_count(S)), dtype=torch.int64, device=dev), "bounds": {}}
+        if windows not in st["bounds"]:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("sast_amd.events: one un-captured warm-up call with the same number of windows is needed before graph capture")
+            st["bounds"][windows] = torch.empty(windows, 2, dtype=torch.int64, device=dev)
+        if self.t_last is None or self.t_last.device != dev:
+            self.t_last = torch.zeros(S, dtype=torch.int64, device=dev)
+            self.err = torch.zeros(2, dtype=torch.int32, device=dev)
+        return st
+
+    def reset(self, streams=None):
+        """new recordings, from the host: the time-correction carry of `streams` (default: all of them) back to 0; with streams=None the
+        error counters are cleared as well"""
+        if self.t_last is None:
+            return
+        if streams is None:
+            self.t_last.zero_()
+            self.err.zero_()
+            return
+        idx = [int(s) for s in streams]
+        if any(s < 0 or s >= self.num_streams for s in idx):
+            raise ValueError(f"sast_amd.events: streams must be in 0 .. {self.num_streams - 1}")
+        if idx:
+            self.t_last[torch.tensor(idx, dtype=torch.int64, device=self.t_last.device)] = 0
+
+    def errors(self) -> Tuple[int, int]:
+        """(invalid events, windows over capacity) since the last reset() (synchronises)"""
+        return (0, 0) if self.err is None else tuple(int(v) for v in self.err.tolist())
+
+    def __call__(self, x: torch.Tensor, y: torch.Tensor, p: torch.Tensor, t: torch.Tensor, counts: torch.Tensor, ends_us: torch.Tensor,
+                 reset: Optional[torch.Tensor] = None, check: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        S = self.num_streams
+        cols = [x, y, p, t]
+        for c, name in zip(cols, ("x", "y", "p", "t")):
+            if c.dim() != 2 or c.shape[0] != S:
+                raise ValueError(f"sast_amd.events: {name} must be [num_streams={S}, capacity], got shape {tuple(c.shape)}")
+            if not c.is_contiguous():
+                raise ValueError(f"sast_amd.events: {name} must be contiguous")
+        if not x.shape == y.shape == p.shape == t.shape:
+            raise ValueError("sast_amd.events: x, y, p and t must have the same shape")
+        codes = [_dtype_code(x, "x"), _dtype_code(y, "y"), _dtype_code(p, "p"), _dtype_code(t, "t", (torch.int64, torch.int32))]
+        if not self.correct_time and t.dtype != torch.int64:
+            raise TypeError("sast_amd.events: correct_time=False needs int64 timestamps")
+        if counts.dtype != torch.int64 or tuple(counts.shape) != (S,) or not counts.is_contiguous():
+            raise ValueError(f"sast_amd.events: counts must be a contiguous int64 tensor of shape [{S}]")
+        if ends_us.dtype != torch.int64 or ends_us.dim() not in (1, 2) or ends_us.shape[-1] != S or ends_us.numel() < 1 \
+                or not ends_us.is_contiguous():
+            raise ValueError(f"sast_amd.events: ends_us must be a contiguous int64 tensor of shape [{S}] or [T, {S}], T >= 1")
+        if reset is not None and (reset.dtype not in (torch.uint8, torch.bool) or tuple(reset.shape) != (S,) or not reset.is_contiguous()):
+            raise ValueError(f"sast_amd.events: reset must be a contiguous uint8 or bool tensor of shape [{S}]")
+        dev = x.device
+        cap = x.shape[1]
+        if S * cap > 2 ** 31 - 1:
+            raise ValueError("sast_amd.events: num_streams * capacity must be below 2^31")
+        T = ends_us.shape[0] if ends_us.dim() == 2 else 1
+        B = T * S
+        wcap = self.window_capacity if self.window_capacity is not None else max(cap, 1)
+        self.ws_bytes(B, wcap)                  # ValueError for more windows than the histogram kernels take
+        _need_gpu(x, y, p, t, counts, ends_us, reset, out)
+        if len({c.device for c in cols + [counts, ends_us] + ([reset] if reset is not None else [])}) != 1:
+            raise ValueError("sast_amd.events: x, y, p, t, counts, ends_us and reset must be on the same device")
+        shape = tuple(ends_us.shape) + self.get_shape()
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=dev)
+        elif out.dtype != torch.uint8 or tuple(out.shape) != tuple(shape) or not out.is_contiguous() or out.device != dev:
+            raise ValueError(f"sast_amd.events: out must be a contiguous uint8 tensor of shape {tuple(shape)} on the events' device")
+        st = self._buffers(dev, cap, B)
+        if check:
+            self.err.zero_()
+        lib = L.lib()
+        tc = st["t"]
+        if self.correct_time:
+            L.check(lib.sast_evstreams_correct_time(t.data_ptr() or tc.data_ptr(), codes[3], counts.data_ptr(), S, cap, tc.data_ptr(),
+                                                    self.t_last.data_ptr(), None if reset is None else reset.data_ptr(),
+                                                    st["scan"].data_ptr(), _stream()), "evstreams_correct_time")
+            tcol, codes = tc, codes[:3] + [L.DT_I64]
+        else:
+            tcol = t
+        bounds = st["bounds"][B]
+        L.check(lib.sast_evstreams_window_bounds(tcol.data_ptr() or tc.data_ptr(), counts.data_ptr(), S, cap, ends_us.data_ptr(), T,
+                                                 self.mode, self.value, bounds.data_ptr(), _stream()), "evstreams_window_bounds")
+        self.launch([x, y, p, tcol], codes, S * cap, bounds, out, self.err, wcap, clip_negative_polarity=True)
+        self.last_bounds = bounds
+        if check:
+            _raise_on_errors(self.err)
+        return out
