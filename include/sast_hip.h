@@ -27,7 +27,10 @@ extern "C" {
 
 typedef void* sast_stream_t; /* hipStream_t */
 
-enum { SAST_DT_F32 = 0, SAST_DT_I32 = 1, SAST_DT_U8 = 2, SAST_DT_I64 = 3, SAST_DT_I16 = 4 };
+/* SAST_DT_I8: the int8 frames of the mixed-density event stack.  sast_nzratio*, sast_input_prep / sast_input_prep_flag and
+ * sast_nchw_to_nhwc* take F32 / I32 / U8 / I8; a pooled cell of non_zero_ratio counts when its MAXIMUM is non-zero (max_pool2d), so for
+ * signed data a cell of only {-1, 0} is empty and a cell of only negative values is occupied. */
+enum { SAST_DT_F32 = 0, SAST_DT_I32 = 1, SAST_DT_U8 = 2, SAST_DT_I64 = 3, SAST_DT_I16 = 4, SAST_DT_I8 = 5 };
 
 int sast_version(void);
 /* 1: the GEMM template evaluates fp32 products as six bf16 MFMAs on an exact three-way operand split (default build);
@@ -480,6 +483,35 @@ typedef struct SastEventArgs {
 } SastEventArgs;
 size_t sast_event_frames_ws_bytes(int B, int bins, int height, int width, int downsample_by_2, int64_t window_capacity); /* 0: unsupported */
 int sast_event_frames(const SastEventArgs* a, sast_stream_t stream);
+
+/* ---- raw events -> mixed-density event stack (csrc/k_events.hip): MixedDensityEventStack.construct (data/utils/representations.py:
+ * 130-218), the second representation of the reference's preprocessing (scripts/genx/preprocess_dataset.py:631-676), on the windows,
+ * bounds, event columns, error counters and workspace rules of sast_event_frames.  Per window [s, e): t0 = t[s], t1 = t[e-1];
+ * t_norm = fp32(t - t0) / fp32(max(t1 - t0, 1)) (one correctly rounded fp32 division) clamped to [fp32(1e-6), fp32(1 - 1e-6)];
+ * bin = max(bins + floor(log2(t_norm)), 0), read from the fp32 exponent (what the reference's floor(bins - log(t_norm) / log(1/2)) gives
+ * while neighbouring integer times stay distinguishable in fp32 near a bin boundary: window spans up to about 2 s); each event adds
+ * 2p - 1 at (bin, y, x); channel i becomes the sum of channels 0..i; the sums wrap to int8 and are clamped to +-count_cutoff.
+ * downsample_by_2: output (i, j) is input (2i+1, 2j+1) (downsample_ev_repr, preprocess_dataset.py:463-473, int8 branch).  Integer
+ * sums: bitwise reproducible.  4 launches, grids sized from capacities: replays inside a graph. */
+typedef struct SastMdStackArgs {
+  const void* x;            /* event columns, `*_dtype` each; events [bounds[b][0], bounds[b][1]) form window b */
+  const void* y;
+  const void* p;            /* 0 / 1 (negative values are invalid, or 0 with clip_negative_polarity) */
+  const void* t;            /* non-decreasing within a window */
+  const int64_t* bounds;    /* int64 [B, 2], clipped to [0, capacity) */
+  int8_t* out;              /* int8 [B, bins, H', W']: H' = height / 2, W' = width / 2 with downsample_by_2, else height, width */
+  int32_t* err;             /* int32 [2], ACCUMULATED, as SastEventArgs.err: [0] invalid events, [1] windows over window_capacity */
+  void* ws;                 /* sast_mdstack_frames_ws_bytes(); ZERO on first use, left zero for the next call */
+  int64_t capacity;         /* events the x / y / p / t buffers hold (<= 2^31 - 1) */
+  int64_t window_capacity;  /* kept events per window the workspace holds */
+  int32_t x_dtype, y_dtype, p_dtype, t_dtype;
+  int32_t B, bins, height, width;   /* height / width: the sensor, full resolution; bins <= 512 */
+  int32_t count_cutoff;     /* 0 .. 127: clamp to [-cutoff, cutoff] (0: an all-zero frame);  -1: the reference's None, no clamp */
+  int32_t downsample_by_2;  /* only events with odd x and odd y count, at (y / 2, x / 2) */
+  int32_t clip_negative_polarity;
+} SastMdStackArgs;
+size_t sast_mdstack_frames_ws_bytes(int B, int bins, int height, int width, int downsample_by_2, int64_t window_capacity); /* 0: unsupported */
+int sast_mdstack_frames(const SastMdStackArgs* a, sast_stream_t stream);
 
 /* ---- S recordings side by side: event buffers [S, stream_capacity], row s one recording with counts[s] valid events at its head
  * (int64 [S] in device memory), its own time-correction carry t_last[s] and its own windows.  The two calls below are the per-row

@@ -18,7 +18,7 @@ P = C.c_void_p
 I32 = C.c_int32
 F32 = C.c_float
 
-DT_F32, DT_I32, DT_U8, DT_I64, DT_I16 = 0, 1, 2, 3, 4
+DT_F32, DT_I32, DT_U8, DT_I64, DT_I16, DT_I8 = 0, 1, 2, 3, 4, 5
 EVENT_WINDOW_DURATION, EVENT_WINDOW_COUNT = 0, 1
 EVENT_SCAN_BLOCKS = 512   # SAST_EVENT_SCAN_BLOCKS
 AUGMENT_PARAM_WORDS = 16  # SAST_AUGMENT_PARAM_WORDS
@@ -82,6 +82,10 @@ SastSampleMask = _struct("SastSampleMask", [(C.c_uint8 * 256, "sel")])
 SastEventArgs = _struct("SastEventArgs", [
     (P, "x y p t bounds out err ws"), (C.c_int64, "capacity window_capacity"),
     (I32, "x_dtype y_dtype p_dtype t_dtype B bins height width count_cutoff fastmode downsample_by_2 clip_negative_polarity"),
+])
+SastMdStackArgs = _struct("SastMdStackArgs", [
+    (P, "x y p t bounds out err ws"), (C.c_int64, "capacity window_capacity"),
+    (I32, "x_dtype y_dtype p_dtype t_dtype B bins height width count_cutoff downsample_by_2 clip_negative_polarity"),
 ])
 SastEvalArgs = _struct("SastEvalArgs", [
     (P, "labels counts det n_det"), (I32, "N M A K"), (F32, "min_diag2 min_side"), (I32, "max_images max_labels_per_frame"),
@@ -160,6 +164,8 @@ _SIGNATURES = {
     "sast_event_window_bounds": (C.c_int, [P, P, C.c_int64, P, C.c_int, C.c_int, C.c_int64, P, P]),
     "sast_event_frames_ws_bytes": (C.c_size_t, [C.c_int] * 5 + [C.c_int64]),
     "sast_event_frames": (C.c_int, [C.POINTER(SastEventArgs), P]),
+    "sast_mdstack_frames_ws_bytes": (C.c_size_t, [C.c_int] * 5 + [C.c_int64]),
+    "sast_mdstack_frames": (C.c_int, [C.POINTER(SastMdStackArgs), P]),
     "sast_evstreams_ws_count": (C.c_size_t, [C.c_int]),
     "sast_evstreams_correct_time": (C.c_int, [P, C.c_int, P, C.c_int, C.c_int64, P, P, P, P, P]),
     "sast_evstreams_window_bounds": (C.c_int, [P, P, C.c_int, C.c_int64, P, C.c_int, C.c_int, C.c_int64, P, P]),

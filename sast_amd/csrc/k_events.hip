@@ -9,6 +9,10 @@
 //                             records), then one workgroup per (window, tile) counts its records in LDS and writes the finished uint8 tile
 //   sast_evstreams_*          the first two for S recordings side by side ([S, capacity] buffers, one count / carry per row), in the
 //                             same number of launches; their bounds index the flattened buffer, so sast_event_frames serves unchanged
+//   sast_mdstack_frames       the mixed-density event stack (MixedDensityEventStack, representations.py:130-218) on the same windows:
+//                             the same three bucketing passes with the bin taken from the logarithm of the event's age, then one
+//                             workgroup per (window, tile) sums the signed polarities per (pixel, bin) in LDS, takes the prefix sum
+//                             over the bins and writes the finished int8 tile
 // Integer counts do not depend on arrival order: the frames are bitwise reproducible.  Every per-frame size (event count, window
 // bounds, carry) is read on the device; the grids are sized from capacities, so a captured graph replays on new events.
 #include <climits>
@@ -23,13 +27,14 @@ constexpr int EV_TILE_W = 32;          // tile columns; a record keeps the pixel
 constexpr int EV_LDS_WORDS = 20480;    // u32 counters of one (window, tile) workgroup: 80 KiB (32 x 32 px x 20 channels)
 constexpr int EV_MAX_TILES = 8192;     // tiles per window: the LDS tile histogram of the bucketing kernels (32 KiB)
 constexpr int EV_MAX_CHANNELS = 640;   // 2 * bins: the channel of a record is 10 bits, and one tile row must fit EV_LDS_WORDS
+constexpr int EV_MD_MAX_BINS = 512;    // mixed density: the record's channel field holds 2 * bin + polarity
 constexpr int EV_EVENTS_PER_BLOCK = 8192;
 constexpr int EV_MAX_BLOCKS = 1024;    // bucketing workgroups per window
 
 struct EvGeom {
   int H, W;            // sensor size: events outside it are invalid
   int Ho, Wo;          // frame size (H/2, W/2 with downsample_by_2)
-  int bins, C;         // C = 2 * bins channels
+  int bins, C;         // C = 2 * bins channels (mixed density: C = bins)
   int th;              // tile rows
   int tiles_x, tiles;  // tiles per frame row / per frame
   int cutoff, fast, ds, clip_pol;
@@ -61,7 +66,18 @@ __device__ __forceinline__ EvWindow ev_window(const SastEventArgs& a, int b) {
   return w;
 }
 
-// >0: a record (tile in *tile, packed pixel | channel << 10 in *rec);  0: dropped by the downsampling;  <0: an invalid event
+// MixedDensityEventStack.construct (representations.py:193-208): t_norm = (t - t0) / max(t1 - t0, 1) in fp32 as above, clamped to
+// [1e-6, 1 - 1e-6] (the scalars rounded to fp32), bin = floor(max(bins - log(t_norm) / log(1/2), 0)) = max(bins + floor(log2(t_norm)), 0).
+// floor(log2) of a normal fp32 is its exponent field: no logarithm, and no libm whose last bit could decide a bin boundary.
+__device__ __forceinline__ int md_bin(long long dt, float span, int bins) {
+  float q = __fdiv_rn((float)dt, span);
+  q = fminf(fmaxf(q, 1e-6f), (float)(1.0 - 1e-6));
+  return max(bins + (int)((__float_as_uint(q) >> 23) & 255u) - 127, 0);     // q < 1: the bin is at most bins - 1
+}
+
+// >0: a record (tile in *tile, packed pixel | channel << 10 in *rec);  0: dropped by the downsampling;  <0: an invalid event.
+// MD: the mixed-density record, channel field = 2 * bin + polarity
+template <bool MD>
 __device__ __forceinline__ int ev_record(const SastEventArgs& a, const EvGeom& g, const EvWindow& w, long long i, int* tile,
                                          unsigned* rec) {
   const long long x = ld_int(a.x, a.x_dtype, i), y = ld_int(a.y, a.y_dtype, i);
@@ -76,13 +92,18 @@ __device__ __forceinline__ int ev_record(const SastEventArgs& a, const EvGeom& g
     oy >>= 1;
     if (ox >= g.Wo || oy >= g.Ho) return 0;
   }
-  // representations.py:98-104: (t - t0) / max(t1 - t0, 1) is int64 / int64 true division in fp32 (both operands rounded to fp32,
-  // one correctly rounded divide), then * bins, floor, clamp(max = bins - 1)
-  const float q = __fdiv_rn((float)dt, w.span) * (float)g.bins;
-  const int bin = min((int)floorf(q), g.bins - 1);
+  int ch;
+  if constexpr (MD) {
+    ch = 2 * md_bin(dt, w.span, g.bins) + (int)p;
+  } else {
+    // representations.py:98-104: (t - t0) / max(t1 - t0, 1) is int64 / int64 true division in fp32 (both operands rounded to fp32,
+    // one correctly rounded divide), then * bins, floor, clamp(max = bins - 1)
+    const float q = __fdiv_rn((float)dt, w.span) * (float)g.bins;
+    ch = (int)p * g.bins + min((int)floorf(q), g.bins - 1);
+  }
   const int ty = oy / g.th, tx = ox / EV_TILE_W;
   *tile = ty * g.tiles_x + tx;
-  *rec = (unsigned)((oy - ty * g.th) * EV_TILE_W + (ox - tx * EV_TILE_W)) | ((unsigned)(p * g.bins + bin) << 10);
+  *rec = (unsigned)((oy - ty * g.th) * EV_TILE_W + (ox - tx * EV_TILE_W)) | ((unsigned)ch << 10);
   return 1;
 }
 
@@ -103,6 +124,7 @@ __device__ __forceinline__ bool ev_in_earlier_window(const SastEventArgs& a, int
 }
 
 // pass 1: events per (window, tile) into tile_cnt (zero on entry; the scan clears it again); invalid events into err[0], each once
+template <bool MD>
 __global__ __launch_bounds__(EV_THREADS) void ev_count_kernel(SastEventArgs a, EvGeom g, int* tile_cnt) {
   extern __shared__ __attribute__((aligned(16))) int hist[];
   __shared__ int s_bad;
@@ -117,7 +139,7 @@ __global__ __launch_bounds__(EV_THREADS) void ev_count_kernel(SastEventArgs a, E
   for (long long i = lo + threadIdx.x; i < hi; i += EV_THREADS) {
     int tile;
     unsigned rec;
-    const int r = ev_record(a, g, w, i, &tile, &rec);
+    const int r = ev_record<MD>(a, g, w, i, &tile, &rec);
     if (r > 0) atomicAdd(&hist[tile], 1);
     else if (r < 0 && !ev_in_earlier_window(a, b, i)) ++bad;
   }
@@ -167,6 +189,7 @@ __global__ __launch_bounds__(EV_THREADS) void ev_scan_kernel(SastEventArgs a, Ev
 
 // pass 3: the same events again; each workgroup reserves one range per tile (one global atomic per (workgroup, tile)), then places
 // its records there through LDS cursors
+template <bool MD>
 __global__ __launch_bounds__(EV_THREADS) void ev_scatter_kernel(SastEventArgs a, EvGeom g, int* cursor, const int* ovf, unsigned* recs) {
   extern __shared__ __attribute__((aligned(16))) int hist[];
   const int b = blockIdx.y;
@@ -179,7 +202,7 @@ __global__ __launch_bounds__(EV_THREADS) void ev_scatter_kernel(SastEventArgs a,
   for (long long i = lo + threadIdx.x; i < hi; i += EV_THREADS) {
     int tile;
     unsigned rec;
-    if (ev_record(a, g, w, i, &tile, &rec) > 0) atomicAdd(&hist[tile], 1);
+    if (ev_record<MD>(a, g, w, i, &tile, &rec) > 0) atomicAdd(&hist[tile], 1);
   }
   __syncthreads();
   for (int k = threadIdx.x; k < g.tiles; k += EV_THREADS)
@@ -189,7 +212,7 @@ __global__ __launch_bounds__(EV_THREADS) void ev_scatter_kernel(SastEventArgs a,
   for (long long i = lo + threadIdx.x; i < hi; i += EV_THREADS) {
     int tile;
     unsigned rec;
-    if (ev_record(a, g, w, i, &tile, &rec) > 0) {
+    if (ev_record<MD>(a, g, w, i, &tile, &rec) > 0) {
       const int pos = atomicAdd(&hist[tile], 1);
       if (pos < a.window_capacity) wr[pos] = rec;
     }
@@ -227,6 +250,46 @@ __global__ __launch_bounds__(EV_THREADS) void ev_accum_kernel(SastEventArgs a, E
     const int oy = oy0 + l / EV_TILE_W, ox = ox0 + (l % EV_TILE_W);
     if (oy < g.Ho && ox < g.Wo)
       a.out[(((size_t)b * g.C + c) * g.Ho + oy) * g.Wo + ox] = ev_finish(cnt[k], g.cutoff, g.fast);
+  }
+}
+
+// representations.py:210-217: the sums wrap as int8 (put_ accumulates in int8, the channel sums are stored back to int8), then
+// clamp(-count_cutoff, count_cutoff) unless the cutoff is None (< 0 here)
+__device__ __forceinline__ signed char md_finish(int v, int cutoff) {
+  int s = (signed char)(unsigned char)(v & 255);
+  if (cutoff >= 0) s = min(max(s, -cutoff), cutoff);
+  return (signed char)s;
+}
+
+// pass 4 of the mixed-density stack, one workgroup per (tile, window): signed counters of the tile's th x 32 pixels x bins in LDS
+// (+1 / -1 per record), then per pixel the inclusive prefix sum over the bins (representations.py:124-127), every int8 of the tile
+// written once (no clear of the output, no finishing pass)
+__global__ __launch_bounds__(EV_THREADS) void md_accum_kernel(SastEventArgs a, EvGeom g, const int* off, const unsigned* recs) {
+  extern __shared__ __attribute__((aligned(16))) int scnt[];
+  const int t = blockIdx.x, b = blockIdx.y;
+  const int px = g.th * EV_TILE_W, n = px * g.C;
+  for (int k = threadIdx.x; k < n; k += EV_THREADS) scnt[k] = 0;
+  __syncthreads();
+  const int* o = off + (size_t)b * (g.tiles + 1);
+  const int beg = o[t], end = min(o[t + 1], (int)min(a.window_capacity, (long long)INT_MAX));
+  const unsigned* rd = recs + (size_t)b * (size_t)a.window_capacity;
+  for (int i = beg + threadIdx.x; i < end; i += EV_THREADS) {
+    const unsigned r = rd[i];
+    const unsigned ch = r >> 10;
+    const unsigned k = (ch >> 1) * px + (r & 1023u);
+    if (k < (unsigned)n) atomicAdd(&scnt[k], (ch & 1u) ? 1 : -1);
+  }
+  __syncthreads();
+  const int oy0 = (t / g.tiles_x) * g.th, ox0 = (t % g.tiles_x) * EV_TILE_W;
+  signed char* out = reinterpret_cast<signed char*>(a.out);
+  for (int l = threadIdx.x; l < px; l += EV_THREADS) {
+    const int oy = oy0 + l / EV_TILE_W, ox = ox0 + (l % EV_TILE_W);
+    if (oy >= g.Ho || ox >= g.Wo) continue;
+    int run = 0;
+    for (int c = 0; c < g.C; ++c) {
+      run += scnt[c * px + l];
+      out[(((size_t)b * g.C + c) * g.Ho + oy) * g.Wo + ox] = md_finish(run, g.cutoff);
+    }
   }
 }
 
@@ -400,15 +463,16 @@ __global__ void ev_rows_bounds_kernel(const long long* t, const long long* count
 bool int_dtype(int dt) { return dt == SAST_DT_I64 || dt == SAST_DT_I32 || dt == SAST_DT_I16; }
 
 // geometry of a call, or false for arguments the kernels do not take
-bool ev_geom(int B, int bins, int height, int width, int ds, long long wcap, EvGeom* g) {
-  if (B < 1 || B > 65535 || bins < 1 || 2 * bins > EV_MAX_CHANNELS || height < 1 || width < 1 || wcap < 0 || wcap > INT_MAX) return false;
+bool ev_geom(int B, int bins, int height, int width, int ds, long long wcap, EvGeom* g, bool md = false) {
+  if (B < 1 || B > 65535 || bins < 1 || height < 1 || width < 1 || wcap < 0 || wcap > INT_MAX) return false;
+  if (md ? bins > EV_MD_MAX_BINS : 2 * bins > EV_MAX_CHANNELS) return false;
   g->H = height;
   g->W = width;
   g->Ho = ds ? height / 2 : height;
   g->Wo = ds ? width / 2 : width;
   if (g->Ho < 1 || g->Wo < 1) return false;
   g->bins = bins;
-  g->C = 2 * bins;
+  g->C = md ? bins : 2 * bins;
   g->th = min(32, EV_LDS_WORDS / (EV_TILE_W * g->C));
   g->tiles_x = (g->Wo + EV_TILE_W - 1) / EV_TILE_W;
   const long long tiles = (long long)g->tiles_x * ((g->Ho + g->th - 1) / g->th);
@@ -536,10 +600,61 @@ int sast_event_frames(const SastEventArgs* a, sast_stream_t stream) {
   const long long per = (a->capacity + EV_EVENTS_PER_BLOCK - 1) / EV_EVENTS_PER_BLOCK;
   const dim3 gb((unsigned)std::min<long long>(std::max<long long>(per, 1), EV_MAX_BLOCKS), (unsigned)a->B);
   const size_t lds_hist = sizeof(int) * (size_t)g.tiles;
-  SAST_LAUNCH(ev_count_kernel, gb, dim3(EV_THREADS), lds_hist, st, *a, g, w.tile_cnt);
+  SAST_LAUNCH(ev_count_kernel<false>, gb, dim3(EV_THREADS), lds_hist, st, *a, g, w.tile_cnt);
   SAST_LAUNCH(ev_scan_kernel, dim3((unsigned)a->B), dim3(EV_THREADS), 0, st, *a, g, w.tile_cnt, w.off, w.cursor, w.ovf);
-  SAST_LAUNCH(ev_scatter_kernel, gb, dim3(EV_THREADS), lds_hist, st, *a, g, w.cursor, (const int*)w.ovf, w.recs);
+  SAST_LAUNCH(ev_scatter_kernel<false>, gb, dim3(EV_THREADS), lds_hist, st, *a, g, w.cursor, (const int*)w.ovf, w.recs);
   SAST_LAUNCH(ev_accum_kernel, dim3((unsigned)g.tiles, (unsigned)a->B), dim3(EV_THREADS), (size_t)lds_acc, st, *a, g, (const int*)w.off,
+              (const unsigned*)w.recs);
+  SAST_CHECK_LAUNCH();
+  return SAST_OK;
+}
+
+size_t sast_mdstack_frames_ws_bytes(int B, int bins, int height, int width, int downsample_by_2, int64_t window_capacity) {
+  sast::EvGeom g;
+  if (!sast::ev_geom(B, bins, height, width, downsample_by_2, window_capacity, &g, true)) return 0;
+  return sast::ev_ws(nullptr, B, g, window_capacity).bytes;
+}
+
+int sast_mdstack_frames(const SastMdStackArgs* m, sast_stream_t stream) {
+  SAST_ENTRY();
+  using namespace sast;
+  if (!m) return SAST_EINVAL;
+  EvGeom g;
+  if (!ev_geom(m->B, m->bins, m->height, m->width, m->downsample_by_2, m->window_capacity, &g, true)) return SAST_EINVAL;
+  if (!m->x || !m->y || !m->p || !m->t || !m->bounds || !m->out || !m->err || !m->ws || m->capacity < 0 || m->capacity > INT_MAX)
+    return SAST_EINVAL;
+  if (!int_dtype(m->x_dtype) || !int_dtype(m->y_dtype) || !int_dtype(m->p_dtype) || (m->t_dtype != SAST_DT_I64 && m->t_dtype != SAST_DT_I32))
+    return SAST_EINVAL;
+  if (m->count_cutoff < -1 || m->count_cutoff > 127) return SAST_EINVAL;
+  g.cutoff = m->count_cutoff;
+  g.fast = 0;
+  g.clip_pol = m->clip_negative_polarity ? 1 : 0;
+  SastEventArgs ea = {};                    // the bucketing passes are the histogram's: the same fields under the same names
+  ea.x = m->x; ea.y = m->y; ea.p = m->p; ea.t = m->t;
+  ea.bounds = m->bounds;
+  ea.out = reinterpret_cast<uint8_t*>(m->out);
+  ea.err = m->err;
+  ea.ws = m->ws;
+  ea.capacity = m->capacity;
+  ea.window_capacity = m->window_capacity;
+  ea.x_dtype = m->x_dtype; ea.y_dtype = m->y_dtype; ea.p_dtype = m->p_dtype; ea.t_dtype = m->t_dtype;
+  ea.B = m->B; ea.bins = m->bins; ea.height = m->height; ea.width = m->width;
+  ea.downsample_by_2 = m->downsample_by_2;
+  ea.clip_negative_polarity = m->clip_negative_polarity;
+  const SastEventArgs* a = &ea;
+  const EvWs w = ev_ws(a->ws, a->B, g, a->window_capacity);
+  const int lds_acc = (int)(sizeof(int) * g.th * EV_TILE_W * g.C);
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&md_accum_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                          (int)(sizeof(int) * EV_LDS_WORDS)) != hipSuccess)
+    return SAST_ELAUNCH;
+  hipStream_t st = (hipStream_t)stream;
+  const long long per = (a->capacity + EV_EVENTS_PER_BLOCK - 1) / EV_EVENTS_PER_BLOCK;
+  const dim3 gb((unsigned)std::min<long long>(std::max<long long>(per, 1), EV_MAX_BLOCKS), (unsigned)a->B);
+  const size_t lds_hist = sizeof(int) * (size_t)g.tiles;
+  SAST_LAUNCH(ev_count_kernel<true>, gb, dim3(EV_THREADS), lds_hist, st, *a, g, w.tile_cnt);
+  SAST_LAUNCH(ev_scan_kernel, dim3((unsigned)a->B), dim3(EV_THREADS), 0, st, *a, g, w.tile_cnt, w.off, w.cursor, w.ovf);
+  SAST_LAUNCH(ev_scatter_kernel<true>, gb, dim3(EV_THREADS), lds_hist, st, *a, g, w.cursor, (const int*)w.ovf, w.recs);
+  SAST_LAUNCH(md_accum_kernel, dim3((unsigned)g.tiles, (unsigned)a->B), dim3(EV_THREADS), (size_t)lds_acc, st, *a, g, (const int*)w.off,
               (const unsigned*)w.recs);
   SAST_CHECK_LAUNCH();
   return SAST_OK;

@@ -130,6 +130,7 @@ int nzr_dispatch(const void* x, int dtype, int* cnt, float* r, int B, int C, int
     case SAST_DT_F32: return nzr_launch<float>(x, cnt, r, B, C, H, W, Hp, Wp, st);
     case SAST_DT_I32: return nzr_launch<int>(x, cnt, r, B, C, H, W, Hp, Wp, st);
     case SAST_DT_U8:  return nzr_launch<unsigned char>(x, cnt, r, B, C, H, W, Hp, Wp, st);
+    case SAST_DT_I8:  return nzr_launch<signed char>(x, cnt, r, B, C, H, W, Hp, Wp, st);   // (signed: the cell MAXIMUM != 0, as max_pool2d)
     default: return SAST_EINVAL;
   }
 }
@@ -298,6 +299,7 @@ int input_prep_dispatch(const void* x, int dtype, float* y, int* ws, float* r, i
     case SAST_DT_F32: return input_prep_launch<float>(x, y, ws, r, B, C, H, W, Hp, Wp, st, nonexact);
     case SAST_DT_I32: return input_prep_launch<int>(x, y, ws, r, B, C, H, W, Hp, Wp, st, nonexact);
     case SAST_DT_U8:  return input_prep_launch<unsigned char>(x, y, ws, r, B, C, H, W, Hp, Wp, st, nonexact);
+    case SAST_DT_I8:  return input_prep_launch<signed char>(x, y, ws, r, B, C, H, W, Hp, Wp, st, nonexact);   // int8 mixed-density frames
     default: return SAST_EINVAL;
   }
 }
@@ -335,6 +337,7 @@ int nchw_to_nhwc_dispatch(const void* x, int dtype, float* y, int B, int C, int 
     case SAST_DT_F32: SAST_LAUNCH((nchw_to_nhwc_kernel<float>), grid, dim3(256), sh, st, (const float*)x, y, C, H, W, Hp, Wp, div_mul_of((unsigned)C, 64ull * C)); break;
     case SAST_DT_I32: SAST_LAUNCH((nchw_to_nhwc_kernel<int>), grid, dim3(256), sh, st, (const int*)x, y, C, H, W, Hp, Wp, div_mul_of((unsigned)C, 64ull * C)); break;
     case SAST_DT_U8:  SAST_LAUNCH((nchw_to_nhwc_kernel<unsigned char>), grid, dim3(256), sh, st, (const unsigned char*)x, y, C, H, W, Hp, Wp, div_mul_of((unsigned)C, 64ull * C)); break;
+    case SAST_DT_I8:  SAST_LAUNCH((nchw_to_nhwc_kernel<signed char>), grid, dim3(256), sh, st, (const signed char*)x, y, C, H, W, Hp, Wp, div_mul_of((unsigned)C, 64ull * C)); break;
     default: return SAST_EINVAL;
   }
   SAST_CHECK_LAUNCH();

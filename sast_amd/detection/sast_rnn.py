@@ -218,7 +218,7 @@ class RNNDetector(nn.Module):
         return output, states, P
 
     def forward(self, x: torch.Tensor, prev_states=None, token_mask: Optional[torch.Tensor] = None):
-        """x (B,20,H,W) NCHW any of {uint8,int32,float32}; -> ({1..4: h NCHW}, [(h,c)], P)  (sast_rnn.py:144-162)"""
+        """x (B,20,H,W) NCHW any of {uint8,int8,int32,float32}; -> ({1..4: h NCHW}, [(h,c)], P)  (sast_rnn.py:144-162)"""
         ps = None
         if prev_states is not None:
             ps = [None if s is None else (SF.as_nhwc(s[0]), SF.as_nhwc(s[1])) for s in prev_states]

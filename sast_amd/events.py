@@ -1,4 +1,4 @@
-"""Raw events (x, y, p, t) -> stacked-histogram frames on the GPU (csrc/k_events.hip).
+"""Raw events (x, y, p, t) -> stacked-histogram or mixed-density frames on the GPU (csrc/k_events.hip).
 
 The reference builds the detector's input offline on the CPU: StackedHistogram.construct (data/utils/representations.py:37-121) once per
 window of scripts/genx/preprocess_dataset.py:476-530, on timestamps its reader forced non-decreasing (:159-168) with negative polarities
@@ -10,6 +10,10 @@ bit for bit, from device tensors:
   correction with its carry kept on the device, optional downsampling by 2 -> uint8 [B, 2*bins, H', W'], the input of `RNNDetector` /
   `YoloXDetector`.  Every per-frame value stays on the device, so a call can be captured in a graph and replayed on new events written
   into the same buffers.
+
+The reference's second representation, MixedDensityEventStack (representations.py:130-218: signed int8 frames of `bins` channels, events
+binned by the logarithm of their age and accumulated over the bins), is `MixedDensityEventStack` here, and
+`representation="mixed_density"` of `EventFrames` / `EventStreams`: the same windows, carries and error counters, int8 frames.
 
 There is no CPU path: CPU tensors raise the library's "no CPU fallback" error.
 """
@@ -57,27 +61,51 @@ def _cutoff(count_cutoff: Optional[int]) -> int:
     return min(int(count_cutoff), 255)
 
 
-class _Frames:
-    """geometry + the device workspace of sast_event_frames (zero when created, left zero by every call)"""
+def _md_cutoff(count_cutoff: Optional[int]) -> Optional[int]:
+    # representations.py:139-142: None, or an int in 0 .. 127
+    if count_cutoff is None:
+        return None
+    if isinstance(count_cutoff, bool) or not isinstance(count_cutoff, int) or not 0 <= count_cutoff <= 127:
+        raise ValueError("sast_amd.events: the mixed-density count_cutoff must be an int in 0 .. 127 (or None)")
+    return count_cutoff
 
-    def __init__(self, bins: int, height: int, width: int, count_cutoff: Optional[int], fastmode: bool, downsample_by_2: bool):
+
+REPRESENTATIONS = ("stacked_histogram", "mixed_density")
+
+
+class _Frames:
+    """geometry + the device workspace of sast_event_frames / sast_mdstack_frames (zero when created, left zero by every call)"""
+
+    def __init__(self, bins: int, height: int, width: int, count_cutoff: Optional[int], fastmode: bool, downsample_by_2: bool,
+                 representation: str = "stacked_histogram"):
         if int(bins) < 1 or int(height) < 1 or int(width) < 1:
             raise ValueError("sast_amd.events: bins, height and width must be >= 1")
+        if representation not in REPRESENTATIONS:
+            raise ValueError(f"sast_amd.events: representation must be one of {REPRESENTATIONS}, got {representation!r}")
+        self.representation = representation
+        self.mixed_density = representation == "mixed_density"
         self.bins, self.height, self.width = int(bins), int(height), int(width)
-        self.count_cutoff = _cutoff(count_cutoff)
+        if self.mixed_density:
+            if fastmode is not True:
+                raise ValueError("sast_amd.events: fastmode does not apply to the mixed-density representation")
+            self.count_cutoff = _md_cutoff(count_cutoff)
+        else:
+            self.count_cutoff = _cutoff(count_cutoff)
+        self.frame_dtype = torch.int8 if self.mixed_density else torch.uint8
         self.fastmode = bool(fastmode)
         self.downsample_by_2 = bool(downsample_by_2)
         self.out_hw = (self.height // 2, self.width // 2) if self.downsample_by_2 else (self.height, self.width)
         self._ws = {}
 
     def get_shape(self) -> Tuple[int, int, int]:
-        return 2 * self.bins, self.out_hw[0], self.out_hw[1]
+        return (self.bins if self.mixed_density else 2 * self.bins), self.out_hw[0], self.out_hw[1]
 
     def ws_bytes(self, B: int, window_capacity: int) -> int:
-        n = int(L.lib().sast_event_frames_ws_bytes(B, self.bins, self.height, self.width, int(self.downsample_by_2), int(window_capacity)))
+        query = L.lib().sast_mdstack_frames_ws_bytes if self.mixed_density else L.lib().sast_event_frames_ws_bytes
+        n = int(query(B, self.bins, self.height, self.width, int(self.downsample_by_2), int(window_capacity)))
         if n == 0:
             raise ValueError(f"sast_amd.events: unsupported frame geometry (B={B}, bins={self.bins}, {self.height}x{self.width}, "
-                             f"window capacity {window_capacity}); 2*bins <= 640")
+                             f"window capacity {window_capacity}); " + ("bins <= 512" if self.mixed_density else "2*bins <= 640"))
         return n
 
     def workspace(self, device, B: int, window_capacity: int) -> torch.Tensor:
@@ -96,7 +124,7 @@ class _Frames:
                clip_negative_polarity: bool):
         B = bounds.shape[0]
         ws = self.workspace(out.device, B, window_capacity)
-        a = L.SastEventArgs()
+        a = L.SastMdStackArgs() if self.mixed_density else L.SastEventArgs()
         x, y, p, t = cols
         # an empty column has no storage: any valid device pointer will do, the kernels read no event
         a.x, a.y, a.p, a.t = (c.data_ptr() or out.data_ptr() for c in (x, y, p, t))
@@ -104,8 +132,12 @@ class _Frames:
         a.capacity, a.window_capacity = int(capacity), int(window_capacity)
         a.x_dtype, a.y_dtype, a.p_dtype, a.t_dtype = codes
         a.B, a.bins, a.height, a.width = B, self.bins, self.height, self.width
-        a.count_cutoff, a.fastmode, a.downsample_by_2 = self.count_cutoff, int(self.fastmode), int(self.downsample_by_2)
-        a.clip_negative_polarity = int(clip_negative_polarity)
+        a.downsample_by_2, a.clip_negative_polarity = int(self.downsample_by_2), int(clip_negative_polarity)
+        if self.mixed_density:
+            a.count_cutoff = -1 if self.count_cutoff is None else self.count_cutoff
+            L.check(L.lib().sast_mdstack_frames(C.byref(a), _stream()), "mdstack_frames")
+            return
+        a.count_cutoff, a.fastmode = self.count_cutoff, int(self.fastmode)
         L.check(L.lib().sast_event_frames(C.byref(a), _stream()), "event_frames")
 
 
@@ -149,6 +181,40 @@ class StackedHistogram(_Frames):
         return out[0]
 
 
+class MixedDensityEventStack(_Frames):
+    """representations.py:130-218 on device tensors: `construct(x, y, pol, time)` -> int8 [bins, height, width].
+
+    Events are binned by the logarithm of their age: with t_norm = (t - time[0]) / max(time[-1] - time[0], 1) in fp32, clamped to
+    [1e-6, 1 - 1e-6], bin = max(bins + floor(log2(t_norm)), 0) (the last bin holds the older half of the window, the one before it the
+    quarter before that, ...); each event adds 2*pol - 1, channel i is the sum of channels 0..i, wrapped to int8, then clamped to
+    [-count_cutoff, count_cutoff] (count_cutoff: an int in 0 .. 127, or None for no clamp).  The bin is read from the fp32 exponent, which
+    equals the reference's floor(bins - log(t_norm) / log(1/2)) as long as neighbouring integer times stay distinguishable in fp32 near a
+    bin boundary: window spans up to about 2 s.  Column dtypes, invalid events and `check` as in `StackedHistogram`."""
+
+    def __init__(self, bins: int, height: int, width: int, count_cutoff: Optional[int] = None):
+        super().__init__(bins, height, width, count_cutoff, True, downsample_by_2=False, representation="mixed_density")
+
+    @staticmethod
+    def get_torch_dtype() -> torch.dtype:
+        return torch.int8
+
+    @property
+    def dtype(self) -> torch.dtype:
+        return torch.int8
+
+    def construct(self, x: torch.Tensor, y: torch.Tensor, pol: torch.Tensor, time: torch.Tensor, check: bool = True) -> torch.Tensor:
+        cols, codes = _columns(x, y, pol, time)
+        dev = cols[0].device
+        n = cols[0].numel()
+        bounds = torch.tensor([[0, n]], dtype=torch.int64, device=dev)
+        err = torch.zeros(2, dtype=torch.int32, device=dev)
+        out = torch.empty((1,) + self.get_shape(), dtype=torch.int8, device=dev)
+        self.launch(cols, codes, n, bounds, out, err, max(n, 1), clip_negative_polarity=False)
+        if check:
+            _raise_on_errors(err)
+        return out[0]
+
+
 class EventFrames(_Frames):
     """Batched stacked-histogram frames from one event buffer (the windowing of preprocess_dataset.py:507-530).
 
@@ -164,12 +230,14 @@ class EventFrames(_Frames):
     window_capacity: kept events one window may hold (default: the buffers' length); a window over it is left zero and reported.
     check=False (the default) never synchronises, so a call can be captured in a graph; errors accumulate in `err` (int32 [2]:
       invalid events -- each counted once, among the events the windows hold --, windows over capacity) until `reset()`.  check=True clears them, synchronises after the call and raises
-      ValueError if the call met any."""
+      ValueError if the call met any.
+    representation="mixed_density": the frames are the mixed-density event stack (`MixedDensityEventStack`) of every window instead,
+      int8 [B, bins, H', W']; count_cutoff is then an int in 0 .. 127 or None, and fastmode does not apply.  Everything else is unchanged."""
 
     def __init__(self, height: int, width: int, bins: int = 10, count_cutoff: Optional[int] = 10, fastmode: bool = True,
                  duration_us: Optional[int] = None, num_events: Optional[int] = None, downsample_by_2: bool = False,
-                 correct_time: bool = True, window_capacity: Optional[int] = None):
-        super().__init__(bins, height, width, count_cutoff, fastmode, downsample_by_2)
+                 correct_time: bool = True, window_capacity: Optional[int] = None, representation: str = "stacked_histogram"):
+        super().__init__(bins, height, width, count_cutoff, fastmode, downsample_by_2, representation)
         if (duration_us is None) == (num_events is None):
             raise ValueError("sast_amd.events: give exactly one of duration_us and num_events")
         if (duration_us if duration_us is not None else num_events) < (0 if duration_us is not None else 1):
@@ -237,7 +305,7 @@ class EventFrames(_Frames):
         bounds = torch.empty(B, 2, dtype=torch.int64, device=dev)
         L.check(L.lib().sast_event_window_bounds(cols[3].data_ptr() or st["t"].data_ptr(), n.data_ptr(), cap, ends_us.contiguous().data_ptr(),
                                                  B, self.mode, self.value, bounds.data_ptr(), _stream()), "event_window_bounds")
-        out = torch.empty((B,) + self.get_shape(), dtype=torch.uint8, device=dev)
+        out = torch.empty((B,) + self.get_shape(), dtype=self.frame_dtype, device=dev)
         self.launch(cols, codes, cap, bounds, out, self.err, wcap, clip_negative_polarity=True)
         self.last_bounds = bounds
         if check:
@@ -263,12 +331,14 @@ class EventStreams(_Frames):
     the flattened [S*cap] buffer) is kept in the object, so a call can be captured in a graph and replayed on new events, counts, ends and reset
     flags written into the same tensors.
     window_capacity: kept events one window may hold (default: cap, one row); the workspace holds T*S*window_capacity records.
-    `err`, `errors()`, check=True: as in `EventFrames`; the counters are global to the call, not per row."""
+    `err`, `errors()`, check=True: as in `EventFrames`; the counters are global to the call, not per row.
+    representation="mixed_density": as in `EventFrames`, int8 [S, bins, H', W'] / [T, S, bins, H', W'] frames (and an int8 `out`), in the
+      same 7 launches."""
 
     def __init__(self, num_streams: int, height: int, width: int, bins: int = 10, count_cutoff: Optional[int] = 10, fastmode: bool = True,
                  duration_us: Optional[int] = None, num_events: Optional[int] = None, downsample_by_2: bool = False,
-                 correct_time: bool = True, window_capacity: Optional[int] = None):
-        super().__init__(bins, height, width, count_cutoff, fastmode, downsample_by_2)
+                 correct_time: bool = True, window_capacity: Optional[int] = None, representation: str = "stacked_histogram"):
+        super().__init__(bins, height, width, count_cutoff, fastmode, downsample_by_2, representation)
         if int(num_streams) < 1 or int(num_streams) > 65535:
             raise ValueError("sast_amd.events: num_streams must be in 1 .. 65535")
         if (duration_us is None) == (num_events is None):
@@ -355,9 +425,10 @@ class EventStreams(_Frames):
             raise ValueError("sast_amd.events: x, y, p, t, counts, ends_us and reset must be on the same device")
         shape = tuple(ends_us.shape) + self.get_shape()
         if out is None:
-            out = torch.empty(shape, dtype=torch.uint8, device=dev)
-        elif out.dtype != torch.uint8 or tuple(out.shape) != tuple(shape) or not out.is_contiguous() or out.device != dev:
-            raise ValueError(f"sast_amd.events: out must be a contiguous uint8 tensor of shape {tuple(shape)} on the events' device")
+            out = torch.empty(shape, dtype=self.frame_dtype, device=dev)
+        elif out.dtype != self.frame_dtype or tuple(out.shape) != tuple(shape) or not out.is_contiguous() or out.device != dev:
+            raise ValueError(f"sast_amd.events: out must be a contiguous {str(self.frame_dtype).replace('torch.', '')} tensor of shape "
+                             f"{tuple(shape)} on the events' device")
         st = self._buffers(dev, cap, B)
         if check:
             self.err.zero_()

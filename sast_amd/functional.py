@@ -26,7 +26,7 @@ import torch
 
 from . import _lib as L
 
-_DT = {torch.float32: L.DT_F32, torch.int32: L.DT_I32, torch.uint8: L.DT_U8}
+_DT = {torch.float32: L.DT_F32, torch.int32: L.DT_I32, torch.uint8: L.DT_U8, torch.int8: L.DT_I8}
 
 
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)     # the handle without building a torch.cuda.Stream object per launch
@@ -221,7 +221,8 @@ def is_channels_last_weight(w: torch.Tensor) -> bool:
 # ---------------------------------------------------------------------------------------------- a1
 @torch.no_grad()
 def non_zero_ratio(x: torch.Tensor, pad_hw=None) -> torch.Tensor:
-    """sast_rnn.py:45-60.  x (B,Cin,H,W) NCHW {uint8,int32,float32} -> (B,4,Cin) fp32.
+    """sast_rnn.py:45-60.  x (B,Cin,H,W) NCHW {uint8,int8,int32,float32} -> (B,4,Cin) fp32.  A cell counts when its MAXIMUM is non-zero
+    (max_pool2d, then != 0): for signed data a cell of only {-1, 0} is empty and a cell of only negatives is occupied.
     pad_hw: x stands for its zero padding (bottom / right) to this size (InputPadderFromShape, utils/padding.py:29-53)."""
     _need_gpu(x)
     if x.dtype not in _DT:
@@ -268,6 +269,7 @@ def input_prep(x: torch.Tensor, pad_hw=None, ws_cache: Optional[dict] = None, ke
     """non_zero_ratio (sast_rnn.py:45-60) + x.float() + zero padding to pad_hw (utils/padding.py:29-53) + NCHW->NHWC (ops.py:19-24)
     in ONE launch that reads the event tensor once -> (r (B,4,C) fp32, x_nhwc (B,Hp,Wp,C) fp32).  Falls back to the two separate
     launches for shapes the fused kernel does not cover (padded sizes that are not multiples of 32, channel counts other than 20).
+    int8 input (mixed-density frames, sast_amd.events) is read directly like uint8 / int32 and always gives the fp32 copy.
     keep_bytes (uint8 input, the dataset's storage type): x_nhwc stays uint8 -- only `downsample_ln` (the stem) may consume it; its
     loaders do the `.float()`.  Ignored (fp32 result) for other dtypes and for the fallback shapes.
     The fp32 copy of the fused path carries `x_nhwc.sast_nonexact`: one int32 word allocated behind it, written by the same launch (0 =
