@@ -514,8 +514,9 @@ size_t sast_mdstack_frames_ws_bytes(int B, int bins, int height, int width, int 
 int sast_mdstack_frames(const SastMdStackArgs* a, sast_stream_t stream);
 
 /* ---- S recordings side by side: event buffers [S, stream_capacity], row s one recording with counts[s] valid events at its head
- * (int64 [S] in device memory), its own time-correction carry t_last[s] and its own windows.  The two calls below are the per-row
- * forms of sast_event_correct_time / sast_event_window_bounds; sast_event_frames is then called unchanged with B = T * S windows,
+ * (int64 [S] in device memory), its own time-correction carry t_last[s] and its own windows.  sast_event_correct_time /
+ * sast_event_window_bounds are the S = 1 form of the two calls below (the same kernels: counts = n, t_last a one-element row, reset =
+ * NULL, T = B); sast_event_frames is then called unchanged with B = T * S windows,
  * capacity = S * stream_capacity and these bounds.  A window never spans two rows: both of its bounds lie in
  * [s * stream_capacity, s * stream_capacity + n_s], n_s = min(max(counts[s], 0), stream_capacity), so events past a row's count are
  * never read.  Each call is a fixed number of launches (2 and 1) whatever S is; the grids are sized from S and stream_capacity. */

@@ -2,15 +2,16 @@
 //
 // Reference: StackedHistogram.construct (data/utils/representations.py:37-121) and the reader / windowing / downsampling of the offline
 // script around it (scripts/genx/preprocess_dataset.py:159-177 time correction and polarity clip, :463-473 nearest-exact downsampling
-// by 2, :507-530 window bounds).  Three entry points:
-//   sast_event_correct_time   running maximum of the timestamps with a carry in device memory (two passes over a fixed block count)
-//   sast_event_window_bounds  per window two binary searches (duration mode) or one (count mode) -> int64 [B, 2] event ranges
+// by 2, :507-530 window bounds).  Entry points:
+//   sast_evstreams_correct_time   S recordings side by side ([S, capacity] buffers, one count / carry per row): per row the running
+//                                 maximum of the timestamps with a carry in device memory (two passes over a fixed block count)
+//   sast_evstreams_window_bounds  per window two binary searches (duration mode) or one (count mode) inside its row -> int64 [T * S, 2]
+//                                 event ranges that index the flattened buffer
+//   sast_event_correct_time / sast_event_window_bounds   one recording: the same kernels with S = 1
 //   sast_event_frames         the histogram: bucket each window's events by 32-column spatial tile (count -> scan -> scatter of packed
 //                             records), then one workgroup per (window, tile) counts its records in LDS and writes the finished uint8 tile
-//   sast_evstreams_*          the first two for S recordings side by side ([S, capacity] buffers, one count / carry per row), in the
-//                             same number of launches; their bounds index the flattened buffer, so sast_event_frames serves unchanged
 //   sast_mdstack_frames       the mixed-density event stack (MixedDensityEventStack, representations.py:130-218) on the same windows:
-//                             the same three bucketing passes with the bin taken from the logarithm of the event's age, then one
+//                             the same driver and bucketing passes with the bin taken from the logarithm of the event's age, then one
 //                             workgroup per (window, tile) sums the signed polarities per (pixel, bin) in LDS, takes the prefix sum
 //                             over the bins and writes the finished int8 tile
 // Integer counts do not depend on arrival order: the frames are bitwise reproducible.  Every per-frame size (event count, window
@@ -40,6 +41,17 @@ struct EvGeom {
   int cutoff, fast, ds, clip_pol;
 };
 
+// what the frame kernels read of SastEventArgs / SastMdStackArgs: the fields the two public structs share under the same names
+struct EvIn {
+  const void *x, *y, *p, *t;
+  const int64_t* bounds;
+  void* out;           // uint8 (histogram) or int8 (mixed density) frames
+  int32_t* err;
+  int64_t capacity, window_capacity;
+  int32_t x_dtype, y_dtype, p_dtype, t_dtype;
+  int32_t B;
+};
+
 __device__ __forceinline__ long long ld_int(const void* p, int dt, long long i) {
   if (dt == SAST_DT_I64) return static_cast<const long long*>(p)[i];
   if (dt == SAST_DT_I32) return static_cast<const int*>(p)[i];
@@ -52,7 +64,7 @@ struct EvWindow {
   float span;          // max(t1 - t0, 1) as the reference's int64 / int division sees it: converted to fp32
 };
 
-__device__ __forceinline__ EvWindow ev_window(const SastEventArgs& a, int b) {
+__device__ __forceinline__ EvWindow ev_window(const EvIn& a, int b) {
   EvWindow w;
   w.s = max(a.bounds[2 * b], 0LL);
   w.e = min(a.bounds[2 * b + 1], (long long)a.capacity);
@@ -78,7 +90,7 @@ __device__ __forceinline__ int md_bin(long long dt, float span, int bins) {
 // >0: a record (tile in *tile, packed pixel | channel << 10 in *rec);  0: dropped by the downsampling;  <0: an invalid event.
 // MD: the mixed-density record, channel field = 2 * bin + polarity
 template <bool MD>
-__device__ __forceinline__ int ev_record(const SastEventArgs& a, const EvGeom& g, const EvWindow& w, long long i, int* tile,
+__device__ __forceinline__ int ev_record(const EvIn& a, const EvGeom& g, const EvWindow& w, long long i, int* tile,
                                          unsigned* rec) {
   const long long x = ld_int(a.x, a.x_dtype, i), y = ld_int(a.y, a.y_dtype, i);
   long long p = ld_int(a.p, a.p_dtype, i);
@@ -117,7 +129,7 @@ __device__ __forceinline__ bool ev_chunk(const EvWindow& w, long long* lo, long 
 }
 
 // windows may overlap (count mode, or ends closer than the duration): an invalid event is reported by the first window that holds it
-__device__ __forceinline__ bool ev_in_earlier_window(const SastEventArgs& a, int b, long long i) {
+__device__ __forceinline__ bool ev_in_earlier_window(const EvIn& a, int b, long long i) {
   for (int k = 0; k < b; ++k)
     if (i >= max(a.bounds[2 * k], 0LL) && i < min(a.bounds[2 * k + 1], (long long)a.capacity)) return true;
   return false;
@@ -125,7 +137,7 @@ __device__ __forceinline__ bool ev_in_earlier_window(const SastEventArgs& a, int
 
 // pass 1: events per (window, tile) into tile_cnt (zero on entry; the scan clears it again); invalid events into err[0], each once
 template <bool MD>
-__global__ __launch_bounds__(EV_THREADS) void ev_count_kernel(SastEventArgs a, EvGeom g, int* tile_cnt) {
+__global__ __launch_bounds__(EV_THREADS) void ev_count_kernel(EvIn a, EvGeom g, int* tile_cnt) {
   extern __shared__ __attribute__((aligned(16))) int hist[];
   __shared__ int s_bad;
   const int b = blockIdx.y;
@@ -152,7 +164,7 @@ __global__ __launch_bounds__(EV_THREADS) void ev_count_kernel(SastEventArgs a, E
 
 // pass 2, one workgroup per window: exclusive scan of the tile counts -> off[b][0..tiles] and the scatter cursors; clears tile_cnt.
 // A window with more events than window_capacity is left empty (all-zero frame) and counted in err[1].
-__global__ __launch_bounds__(EV_THREADS) void ev_scan_kernel(SastEventArgs a, EvGeom g, int* tile_cnt, int* off, int* cursor, int* ovf) {
+__global__ __launch_bounds__(EV_THREADS) void ev_scan_kernel(EvIn a, EvGeom g, int* tile_cnt, int* off, int* cursor, int* ovf) {
   __shared__ long long part[EV_THREADS];
   const int b = blockIdx.x, T = g.tiles;
   int* cnt = tile_cnt + (size_t)b * T;
@@ -190,7 +202,7 @@ __global__ __launch_bounds__(EV_THREADS) void ev_scan_kernel(SastEventArgs a, Ev
 // pass 3: the same events again; each workgroup reserves one range per tile (one global atomic per (workgroup, tile)), then places
 // its records there through LDS cursors
 template <bool MD>
-__global__ __launch_bounds__(EV_THREADS) void ev_scatter_kernel(SastEventArgs a, EvGeom g, int* cursor, const int* ovf, unsigned* recs) {
+__global__ __launch_bounds__(EV_THREADS) void ev_scatter_kernel(EvIn a, EvGeom g, int* cursor, const int* ovf, unsigned* recs) {
   extern __shared__ __attribute__((aligned(16))) int hist[];
   const int b = blockIdx.y;
   if (ovf[b]) return;
@@ -229,7 +241,7 @@ __device__ __forceinline__ unsigned char ev_finish(unsigned v, int cutoff, int f
 
 // pass 4, one workgroup per (tile, window): u32 counters of the tile's th x 32 pixels x C channels in LDS, then the finished uint8
 // tile, every pixel of it written once (no clear of the output, no finishing pass)
-__global__ __launch_bounds__(EV_THREADS) void ev_accum_kernel(SastEventArgs a, EvGeom g, const int* off, const unsigned* recs) {
+__global__ __launch_bounds__(EV_THREADS) void ev_accum_kernel(EvIn a, EvGeom g, const int* off, const unsigned* recs) {
   extern __shared__ __attribute__((aligned(16))) unsigned cnt[];
   const int t = blockIdx.x, b = blockIdx.y;
   const int px = g.th * EV_TILE_W, n = px * g.C;
@@ -245,11 +257,12 @@ __global__ __launch_bounds__(EV_THREADS) void ev_accum_kernel(SastEventArgs a, E
   }
   __syncthreads();
   const int oy0 = (t / g.tiles_x) * g.th, ox0 = (t % g.tiles_x) * EV_TILE_W;
+  unsigned char* out = static_cast<unsigned char*>(a.out);
   for (int k = threadIdx.x; k < n; k += EV_THREADS) {
     const int c = k / px, l = k - c * px;
     const int oy = oy0 + l / EV_TILE_W, ox = ox0 + (l % EV_TILE_W);
     if (oy < g.Ho && ox < g.Wo)
-      a.out[(((size_t)b * g.C + c) * g.Ho + oy) * g.Wo + ox] = ev_finish(cnt[k], g.cutoff, g.fast);
+      out[(((size_t)b * g.C + c) * g.Ho + oy) * g.Wo + ox] = ev_finish(cnt[k], g.cutoff, g.fast);
   }
 }
 
@@ -264,7 +277,7 @@ __device__ __forceinline__ signed char md_finish(int v, int cutoff) {
 // pass 4 of the mixed-density stack, one workgroup per (tile, window): signed counters of the tile's th x 32 pixels x bins in LDS
 // (+1 / -1 per record), then per pixel the inclusive prefix sum over the bins (representations.py:124-127), every int8 of the tile
 // written once (no clear of the output, no finishing pass)
-__global__ __launch_bounds__(EV_THREADS) void md_accum_kernel(SastEventArgs a, EvGeom g, const int* off, const unsigned* recs) {
+__global__ __launch_bounds__(EV_THREADS) void md_accum_kernel(EvIn a, EvGeom g, const int* off, const unsigned* recs) {
   extern __shared__ __attribute__((aligned(16))) int scnt[];
   const int t = blockIdx.x, b = blockIdx.y;
   const int px = g.th * EV_TILE_W, n = px * g.C;
@@ -281,7 +294,7 @@ __global__ __launch_bounds__(EV_THREADS) void md_accum_kernel(SastEventArgs a, E
   }
   __syncthreads();
   const int oy0 = (t / g.tiles_x) * g.th, ox0 = (t % g.tiles_x) * EV_TILE_W;
-  signed char* out = reinterpret_cast<signed char*>(a.out);
+  signed char* out = static_cast<signed char*>(a.out);
   for (int l = threadIdx.x; l < px; l += EV_THREADS) {
     const int oy = oy0 + l / EV_TILE_W, ox = ox0 + (l % EV_TILE_W);
     if (oy >= g.Ho || ox >= g.Wo) continue;
@@ -313,88 +326,16 @@ __device__ __forceinline__ long long block_max(long long v, long long* red) {
   return m;
 }
 
-// ws[0] = the carry in, ws[1 + blk] = the maximum of block blk's chunk
-__global__ __launch_bounds__(EV_THREADS) void ev_tmax_partial_kernel(const void* t, int dt, const long long* n_dev, long long cap,
-                                                                     const long long* t_last, long long* ws) {
-  __shared__ long long red[EV_THREADS / 64];
-  const long long n = min(max(*n_dev, 0LL), cap);
-  long long lo, hi;
-  ev_tchunk(n, &lo, &hi);
-  long long m = LLONG_MIN;
-  for (long long i = lo + threadIdx.x; i < hi; i += EV_THREADS) m = max(m, ld_int(t, dt, i));
-  m = block_max(m, red);
-  if (threadIdx.x == 0) {
-    ws[1 + blockIdx.x] = m;
-    if (blockIdx.x == 0) ws[0] = *t_last;
-  }
-}
-
-__global__ __launch_bounds__(EV_THREADS) void ev_tmax_apply_kernel(const void* t, int dt, const long long* n_dev, long long cap,
-                                                                   const long long* ws, long long* t_out, long long* t_last) {
-  __shared__ long long red[EV_THREADS / 64];
-  __shared__ long long wtot[EV_THREADS / 64];
-  const long long n = min(max(*n_dev, 0LL), cap);
-  long long lo, hi;
-  ev_tchunk(n, &lo, &hi);
-  long long carry = LLONG_MIN;
-  for (int k = threadIdx.x; k < (int)blockIdx.x + 1; k += EV_THREADS) carry = max(carry, k == 0 ? ws[0] : ws[k]);
-  carry = block_max(carry, red);
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  for (long long base = lo; base < hi; base += EV_THREADS) {
-    const long long i = base + threadIdx.x;
-    long long v = i < hi ? ld_int(t, dt, i) : LLONG_MIN;
-    for (int d = 1; d < 64; d <<= 1) {                    // inclusive max-scan of the wave
-      const long long u = __shfl_up(v, d);
-      if (lane >= d) v = max(v, u);
-    }
-    __syncthreads();
-    if (lane == 63) wtot[wv] = v;
-    __syncthreads();
-    long long pre = carry;
-    for (int k = 0; k < wv; ++k) pre = max(pre, wtot[k]);
-    v = max(v, pre);
-    if (i < hi) t_out[i] = v;
-    for (int k = wv; k < EV_THREADS / 64; ++k) pre = max(pre, wtot[k]);
-    carry = pre;
-  }
-  if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) {
-    long long m = ws[0];
-    for (int k = 1; k <= (int)gridDim.x; ++k) m = max(m, ws[k]);
-    *t_last = m;
-  }
-}
-
-// ---- window bounds (preprocess_dataset.py:507-513): np.searchsorted over the corrected timestamps
-__device__ __forceinline__ long long search(const long long* t, long long n, long long v, bool right) {
-  long long lo = 0, hi = n;
-  while (lo < hi) {
-    const long long mid = (lo + hi) >> 1;
-    if (right ? t[mid] <= v : t[mid] < v) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
-
-__global__ void ev_bounds_kernel(const long long* t, const long long* n_dev, long long cap, const long long* ends, int B, int mode,
-                                 long long value, long long* bounds) {
-  const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= B) return;
-  const long long n = min(max(*n_dev, 0LL), cap);
-  const long long e = search(t, n, ends[b], true);
-  const long long s = mode == SAST_EVENT_WINDOW_COUNT ? max(e - value, 0LL) : search(t, n, ends[b] - value, false);
-  bounds[2 * b] = s;
-  bounds[2 * b + 1] = e;
-}
-
-// ---- S recordings side by side: [S, cap] buffers, row blockIdx.y one recording with its own count, carry and windows.  The same two
-// passes as above with gridDim.x blocks per row: a row's partial maxima and its carry live in its own ws row
-// (ws[s][0] = carry in, ws[s][1 + blk] = the maximum of block blk's chunk of row s), so no maximum is ever taken across rows.
+// Row blockIdx.y of the [S, cap] buffers is one recording with its own count, carry and windows; a single recording is S = 1.  Two
+// passes with gridDim.x blocks per row: a row's partial maxima and its carry live in its own ws row (ws[s][0] = carry in,
+// ws[s][1 + blk] = the maximum of block blk's chunk of row s), so no maximum is ever taken across rows.  The results are integer
+// maxima: they do not depend on gridDim.x.
 constexpr int EV_ROW_WS = EV_SCAN_BLOCKS + 1;
 constexpr int EV_ROW_EVENTS_PER_BLOCK = 4096;
 
-__global__ __launch_bounds__(EV_THREADS) void ev_rows_tmax_partial_kernel(const void* t, int dt, const long long* counts, long long cap,
-                                                                          const long long* t_last, const unsigned char* reset,
-                                                                          long long* ws) {
+__global__ __launch_bounds__(EV_THREADS) void ev_tmax_partial_kernel(const void* t, int dt, const long long* counts, long long cap,
+                                                                     const long long* t_last, const unsigned char* reset,
+                                                                     long long* ws) {
   __shared__ long long red[EV_THREADS / 64];
   const int s = blockIdx.y;
   const long long n = min(max(counts[s], 0LL), cap), row = (long long)s * cap;
@@ -410,8 +351,8 @@ __global__ __launch_bounds__(EV_THREADS) void ev_rows_tmax_partial_kernel(const 
   }
 }
 
-__global__ __launch_bounds__(EV_THREADS) void ev_rows_tmax_apply_kernel(const void* t, int dt, const long long* counts, long long cap,
-                                                                        const long long* ws_all, long long* t_out, long long* t_last) {
+__global__ __launch_bounds__(EV_THREADS) void ev_tmax_apply_kernel(const void* t, int dt, const long long* counts, long long cap,
+                                                                   const long long* ws_all, long long* t_out, long long* t_last) {
   __shared__ long long red[EV_THREADS / 64];
   __shared__ long long wtot[EV_THREADS / 64];
   const int s = blockIdx.y;
@@ -448,8 +389,19 @@ __global__ __launch_bounds__(EV_THREADS) void ev_rows_tmax_apply_kernel(const vo
   }
 }
 
-__global__ void ev_rows_bounds_kernel(const long long* t, const long long* counts, int S, long long cap, const long long* ends, int B,
-                                      int mode, long long value, long long* bounds) {
+// ---- window bounds (preprocess_dataset.py:507-513): np.searchsorted over the corrected timestamps
+__device__ __forceinline__ long long search(const long long* t, long long n, long long v, bool right) {
+  long long lo = 0, hi = n;
+  while (lo < hi) {
+    const long long mid = (lo + hi) >> 1;
+    if (right ? t[mid] <= v : t[mid] < v) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
+}
+
+__global__ void ev_bounds_kernel(const long long* t, const long long* counts, int S, long long cap, const long long* ends, int B,
+                                 int mode, long long value, long long* bounds) {
   const int w = blockIdx.x * blockDim.x + threadIdx.x;     // window k * S + s
   if (w >= B) return;
   const int s = w % S;
@@ -499,39 +451,91 @@ EvWs ev_ws(void* base, int B, const EvGeom& g, long long wcap) {
   return w;
 }
 
+// the checked fields that SastEventArgs and SastMdStackArgs share, or false for arguments the kernels do not take
+template <class Args>
+bool ev_in(const Args* a, EvIn* in) {
+  if (!a->x || !a->y || !a->p || !a->t || !a->bounds || !a->out || !a->err || !a->ws || a->capacity < 0 || a->capacity > INT_MAX)
+    return false;
+  if (!int_dtype(a->x_dtype) || !int_dtype(a->y_dtype) || !int_dtype(a->p_dtype) || (a->t_dtype != SAST_DT_I64 && a->t_dtype != SAST_DT_I32))
+    return false;
+  *in = EvIn{a->x, a->y, a->p, a->t, a->bounds, a->out, a->err, a->capacity, a->window_capacity,
+             a->x_dtype, a->y_dtype, a->p_dtype, a->t_dtype, a->B};
+  return true;
+}
+
+// sast_event_frames (MD = false) / sast_mdstack_frames: count -> scan -> scatter -> accumulate.  g arrives with cutoff, fast and
+// clip_pol set by the entry point, which has checked its own cutoff range
+template <bool MD, class Args>
+int ev_frames(const Args* a, EvGeom g, sast_stream_t stream) {
+  EvIn in;
+  if (!ev_geom(a->B, a->bins, a->height, a->width, a->downsample_by_2, a->window_capacity, &g, MD) || !ev_in(a, &in)) return SAST_EINVAL;
+  const EvWs w = ev_ws(a->ws, in.B, g, in.window_capacity);
+  const void* accum = MD ? reinterpret_cast<const void*>(&md_accum_kernel) : reinterpret_cast<const void*>(&ev_accum_kernel);
+  if (hipFuncSetAttribute(accum, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(int) * EV_LDS_WORDS)) != hipSuccess)
+    return SAST_ELAUNCH;
+  hipStream_t st = (hipStream_t)stream;
+  const long long per = (in.capacity + EV_EVENTS_PER_BLOCK - 1) / EV_EVENTS_PER_BLOCK;
+  const dim3 gb((unsigned)std::min<long long>(std::max<long long>(per, 1), EV_MAX_BLOCKS), (unsigned)in.B);
+  const dim3 gt((unsigned)g.tiles, (unsigned)in.B);
+  const size_t lds_hist = sizeof(int) * (size_t)g.tiles;
+  const size_t lds_acc = sizeof(int) * (size_t)(g.th * EV_TILE_W * g.C);     // both accumulate kernels keep 4-byte counters
+  SAST_LAUNCH(ev_count_kernel<MD>, gb, dim3(EV_THREADS), lds_hist, st, in, g, w.tile_cnt);
+  SAST_LAUNCH(ev_scan_kernel, dim3((unsigned)in.B), dim3(EV_THREADS), 0, st, in, g, w.tile_cnt, w.off, w.cursor, w.ovf);
+  SAST_LAUNCH(ev_scatter_kernel<MD>, gb, dim3(EV_THREADS), lds_hist, st, in, g, w.cursor, (const int*)w.ovf, w.recs);
+  if constexpr (MD) SAST_LAUNCH(md_accum_kernel, gt, dim3(EV_THREADS), lds_acc, st, in, g, (const int*)w.off, (const unsigned*)w.recs);
+  else SAST_LAUNCH(ev_accum_kernel, gt, dim3(EV_THREADS), lds_acc, st, in, g, (const int*)w.off, (const unsigned*)w.recs);
+  SAST_CHECK_LAUNCH();
+  return SAST_OK;
+}
+
+// the time correction of S rows with `blocks` workgroups per row
+int ev_correct_time(const void* t, int t_dtype, const int64_t* counts, int S, int64_t cap, int64_t* t_out, int64_t* t_last,
+                    const uint8_t* reset, int64_t* ws, long long blocks, sast_stream_t stream) {
+  if (!t || !counts || !t_out || !t_last || !ws || S < 1 || S > 65535 || cap < 0 || (t_dtype != SAST_DT_I64 && t_dtype != SAST_DT_I32))
+    return SAST_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid((unsigned)blocks, (unsigned)S);
+  const long long* cd = reinterpret_cast<const long long*>(counts);
+  long long* w = reinterpret_cast<long long*>(ws);
+  SAST_LAUNCH(ev_tmax_partial_kernel, grid, dim3(EV_THREADS), 0, st, t, t_dtype, cd, (long long)cap,
+              reinterpret_cast<const long long*>(t_last), reinterpret_cast<const unsigned char*>(reset), w);
+  SAST_LAUNCH(ev_tmax_apply_kernel, grid, dim3(EV_THREADS), 0, st, t, t_dtype, cd, (long long)cap, reinterpret_cast<const long long*>(w),
+              reinterpret_cast<long long*>(t_out), reinterpret_cast<long long*>(t_last));
+  SAST_CHECK_LAUNCH();
+  return SAST_OK;
+}
+
+// the window search of T windows in each of S rows
+int ev_window_bounds(const int64_t* t, const int64_t* counts, int S, int64_t cap, const int64_t* ends_us, int T, int mode, int64_t value,
+                     int64_t* bounds, sast_stream_t stream) {
+  if (!t || !counts || !ends_us || !bounds || S < 1 || T < 1 || (long long)S * T > INT_MAX || cap < 0 || value < 0 ||
+      (mode != SAST_EVENT_WINDOW_DURATION && mode != SAST_EVENT_WINDOW_COUNT))
+    return SAST_EINVAL;
+  const int B = S * T;
+  SAST_LAUNCH(ev_bounds_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, reinterpret_cast<const long long*>(t),
+              reinterpret_cast<const long long*>(counts), S, (long long)cap, reinterpret_cast<const long long*>(ends_us), B, mode,
+              (long long)value, reinterpret_cast<long long*>(bounds));
+  SAST_CHECK_LAUNCH();
+  return SAST_OK;
+}
+
 }  // namespace
 }  // namespace sast
 
 extern "C" {
 
+// one recording is the S = 1 form of the per-row calls: n is its one-element counts, t_last its one-element carry row, no reset flags.
+// Each entry point keeps its own grid (here every scan block, per row as many as the capacity needs).
 int sast_event_correct_time(const void* t, int t_dtype, const int64_t* n, int64_t capacity, int64_t* t_out, int64_t* t_last, int64_t* ws,
                             sast_stream_t stream) {
   SAST_ENTRY();
-  using namespace sast;
-  if (!t || !n || !t_out || !t_last || !ws || capacity < 0 || (t_dtype != SAST_DT_I64 && t_dtype != SAST_DT_I32)) return SAST_EINVAL;
-  hipStream_t st = (hipStream_t)stream;
-  const long long* nd = reinterpret_cast<const long long*>(n);
-  long long* w = reinterpret_cast<long long*>(ws);
-  SAST_LAUNCH(ev_tmax_partial_kernel, dim3(EV_SCAN_BLOCKS), dim3(EV_THREADS), 0, st, t, t_dtype, nd, (long long)capacity,
-              reinterpret_cast<const long long*>(t_last), w);
-  SAST_LAUNCH(ev_tmax_apply_kernel, dim3(EV_SCAN_BLOCKS), dim3(EV_THREADS), 0, st, t, t_dtype, nd, (long long)capacity,
-              reinterpret_cast<const long long*>(w), reinterpret_cast<long long*>(t_out), reinterpret_cast<long long*>(t_last));
-  SAST_CHECK_LAUNCH();
-  return SAST_OK;
+  return sast::ev_correct_time(t, t_dtype, n, 1, capacity, t_out, t_last, nullptr, ws, sast::EV_SCAN_BLOCKS, stream);
 }
 
 int sast_event_window_bounds(const int64_t* t, const int64_t* n, int64_t capacity, const int64_t* ends_us, int B, int mode, int64_t value,
                              int64_t* bounds, sast_stream_t stream) {
   SAST_ENTRY();
-  using namespace sast;
-  if (!t || !n || !ends_us || !bounds || B < 1 || capacity < 0 || value < 0 ||
-      (mode != SAST_EVENT_WINDOW_DURATION && mode != SAST_EVENT_WINDOW_COUNT))
-    return SAST_EINVAL;
-  SAST_LAUNCH(ev_bounds_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, reinterpret_cast<const long long*>(t),
-              reinterpret_cast<const long long*>(n), (long long)capacity, reinterpret_cast<const long long*>(ends_us), B, mode,
-              (long long)value, reinterpret_cast<long long*>(bounds));
-  SAST_CHECK_LAUNCH();
-  return SAST_OK;
+  return sast::ev_window_bounds(t, n, 1, capacity, ends_us, B, mode, value, bounds, stream);
 }
 
 size_t sast_evstreams_ws_count(int S) { return S < 1 || S > 65535 ? 0 : (size_t)S * sast::EV_ROW_WS; }
@@ -539,36 +543,15 @@ size_t sast_evstreams_ws_count(int S) { return S < 1 || S > 65535 ? 0 : (size_t)
 int sast_evstreams_correct_time(const void* t, int t_dtype, const int64_t* counts, int S, int64_t stream_capacity, int64_t* t_out,
                                 int64_t* t_last, const uint8_t* reset, int64_t* ws, sast_stream_t stream) {
   SAST_ENTRY();
-  using namespace sast;
-  if (!t || !counts || !t_out || !t_last || !ws || S < 1 || S > 65535 || stream_capacity < 0 ||
-      (t_dtype != SAST_DT_I64 && t_dtype != SAST_DT_I32))
-    return SAST_EINVAL;
-  hipStream_t st = (hipStream_t)stream;
-  const long long per = (stream_capacity + EV_ROW_EVENTS_PER_BLOCK - 1) / EV_ROW_EVENTS_PER_BLOCK;
-  const dim3 grid((unsigned)std::min<long long>(std::max<long long>(per, 1), EV_SCAN_BLOCKS), (unsigned)S);
-  const long long* cd = reinterpret_cast<const long long*>(counts);
-  long long* w = reinterpret_cast<long long*>(ws);
-  SAST_LAUNCH(ev_rows_tmax_partial_kernel, grid, dim3(EV_THREADS), 0, st, t, t_dtype, cd, (long long)stream_capacity,
-              reinterpret_cast<const long long*>(t_last), reinterpret_cast<const unsigned char*>(reset), w);
-  SAST_LAUNCH(ev_rows_tmax_apply_kernel, grid, dim3(EV_THREADS), 0, st, t, t_dtype, cd, (long long)stream_capacity,
-              reinterpret_cast<const long long*>(w), reinterpret_cast<long long*>(t_out), reinterpret_cast<long long*>(t_last));
-  SAST_CHECK_LAUNCH();
-  return SAST_OK;
+  const long long per = (stream_capacity + sast::EV_ROW_EVENTS_PER_BLOCK - 1) / sast::EV_ROW_EVENTS_PER_BLOCK;
+  const long long blocks = std::min<long long>(std::max<long long>(per, 1), sast::EV_SCAN_BLOCKS);
+  return sast::ev_correct_time(t, t_dtype, counts, S, stream_capacity, t_out, t_last, reset, ws, blocks, stream);
 }
 
 int sast_evstreams_window_bounds(const int64_t* t, const int64_t* counts, int S, int64_t stream_capacity, const int64_t* ends_us, int T,
                                  int mode, int64_t value, int64_t* bounds, sast_stream_t stream) {
   SAST_ENTRY();
-  using namespace sast;
-  if (!t || !counts || !ends_us || !bounds || S < 1 || T < 1 || (long long)S * T > INT_MAX || stream_capacity < 0 || value < 0 ||
-      (mode != SAST_EVENT_WINDOW_DURATION && mode != SAST_EVENT_WINDOW_COUNT))
-    return SAST_EINVAL;
-  const int B = S * T;
-  SAST_LAUNCH(ev_rows_bounds_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, reinterpret_cast<const long long*>(t),
-              reinterpret_cast<const long long*>(counts), S, (long long)stream_capacity, reinterpret_cast<const long long*>(ends_us), B,
-              mode, (long long)value, reinterpret_cast<long long*>(bounds));
-  SAST_CHECK_LAUNCH();
-  return SAST_OK;
+  return sast::ev_window_bounds(t, counts, S, stream_capacity, ends_us, T, mode, value, bounds, stream);
 }
 
 size_t sast_event_frames_ws_bytes(int B, int bins, int height, int width, int downsample_by_2, int64_t window_capacity) {
@@ -579,34 +562,12 @@ size_t sast_event_frames_ws_bytes(int B, int bins, int height, int width, int do
 
 int sast_event_frames(const SastEventArgs* a, sast_stream_t stream) {
   SAST_ENTRY();
-  using namespace sast;
-  if (!a) return SAST_EINVAL;
-  EvGeom g;
-  if (!ev_geom(a->B, a->bins, a->height, a->width, a->downsample_by_2, a->window_capacity, &g)) return SAST_EINVAL;
-  if (!a->x || !a->y || !a->p || !a->t || !a->bounds || !a->out || !a->err || !a->ws || a->capacity < 0 || a->capacity > INT_MAX)
-    return SAST_EINVAL;
-  if (!int_dtype(a->x_dtype) || !int_dtype(a->y_dtype) || !int_dtype(a->p_dtype) || (a->t_dtype != SAST_DT_I64 && a->t_dtype != SAST_DT_I32))
-    return SAST_EINVAL;
-  if (a->count_cutoff < 1 || a->count_cutoff > 255) return SAST_EINVAL;
+  if (!a || a->count_cutoff < 1 || a->count_cutoff > 255) return SAST_EINVAL;
+  sast::EvGeom g = {};
   g.cutoff = a->count_cutoff;
   g.fast = a->fastmode ? 1 : 0;
   g.clip_pol = a->clip_negative_polarity ? 1 : 0;
-  const EvWs w = ev_ws(a->ws, a->B, g, a->window_capacity);
-  const int lds_acc = (int)(sizeof(unsigned) * g.th * EV_TILE_W * g.C);
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&ev_accum_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          (int)(sizeof(unsigned) * EV_LDS_WORDS)) != hipSuccess)
-    return SAST_ELAUNCH;
-  hipStream_t st = (hipStream_t)stream;
-  const long long per = (a->capacity + EV_EVENTS_PER_BLOCK - 1) / EV_EVENTS_PER_BLOCK;
-  const dim3 gb((unsigned)std::min<long long>(std::max<long long>(per, 1), EV_MAX_BLOCKS), (unsigned)a->B);
-  const size_t lds_hist = sizeof(int) * (size_t)g.tiles;
-  SAST_LAUNCH(ev_count_kernel<false>, gb, dim3(EV_THREADS), lds_hist, st, *a, g, w.tile_cnt);
-  SAST_LAUNCH(ev_scan_kernel, dim3((unsigned)a->B), dim3(EV_THREADS), 0, st, *a, g, w.tile_cnt, w.off, w.cursor, w.ovf);
-  SAST_LAUNCH(ev_scatter_kernel<false>, gb, dim3(EV_THREADS), lds_hist, st, *a, g, w.cursor, (const int*)w.ovf, w.recs);
-  SAST_LAUNCH(ev_accum_kernel, dim3((unsigned)g.tiles, (unsigned)a->B), dim3(EV_THREADS), (size_t)lds_acc, st, *a, g, (const int*)w.off,
-              (const unsigned*)w.recs);
-  SAST_CHECK_LAUNCH();
-  return SAST_OK;
+  return sast::ev_frames<false>(a, g, stream);
 }
 
 size_t sast_mdstack_frames_ws_bytes(int B, int bins, int height, int width, int downsample_by_2, int64_t window_capacity) {
@@ -617,47 +578,12 @@ size_t sast_mdstack_frames_ws_bytes(int B, int bins, int height, int width, int 
 
 int sast_mdstack_frames(const SastMdStackArgs* m, sast_stream_t stream) {
   SAST_ENTRY();
-  using namespace sast;
-  if (!m) return SAST_EINVAL;
-  EvGeom g;
-  if (!ev_geom(m->B, m->bins, m->height, m->width, m->downsample_by_2, m->window_capacity, &g, true)) return SAST_EINVAL;
-  if (!m->x || !m->y || !m->p || !m->t || !m->bounds || !m->out || !m->err || !m->ws || m->capacity < 0 || m->capacity > INT_MAX)
-    return SAST_EINVAL;
-  if (!int_dtype(m->x_dtype) || !int_dtype(m->y_dtype) || !int_dtype(m->p_dtype) || (m->t_dtype != SAST_DT_I64 && m->t_dtype != SAST_DT_I32))
-    return SAST_EINVAL;
-  if (m->count_cutoff < -1 || m->count_cutoff > 127) return SAST_EINVAL;
+  if (!m || m->count_cutoff < -1 || m->count_cutoff > 127) return SAST_EINVAL;
+  sast::EvGeom g = {};
   g.cutoff = m->count_cutoff;
   g.fast = 0;
   g.clip_pol = m->clip_negative_polarity ? 1 : 0;
-  SastEventArgs ea = {};                    // the bucketing passes are the histogram's: the same fields under the same names
-  ea.x = m->x; ea.y = m->y; ea.p = m->p; ea.t = m->t;
-  ea.bounds = m->bounds;
-  ea.out = reinterpret_cast<uint8_t*>(m->out);
-  ea.err = m->err;
-  ea.ws = m->ws;
-  ea.capacity = m->capacity;
-  ea.window_capacity = m->window_capacity;
-  ea.x_dtype = m->x_dtype; ea.y_dtype = m->y_dtype; ea.p_dtype = m->p_dtype; ea.t_dtype = m->t_dtype;
-  ea.B = m->B; ea.bins = m->bins; ea.height = m->height; ea.width = m->width;
-  ea.downsample_by_2 = m->downsample_by_2;
-  ea.clip_negative_polarity = m->clip_negative_polarity;
-  const SastEventArgs* a = &ea;
-  const EvWs w = ev_ws(a->ws, a->B, g, a->window_capacity);
-  const int lds_acc = (int)(sizeof(int) * g.th * EV_TILE_W * g.C);
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&md_accum_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          (int)(sizeof(int) * EV_LDS_WORDS)) != hipSuccess)
-    return SAST_ELAUNCH;
-  hipStream_t st = (hipStream_t)stream;
-  const long long per = (a->capacity + EV_EVENTS_PER_BLOCK - 1) / EV_EVENTS_PER_BLOCK;
-  const dim3 gb((unsigned)std::min<long long>(std::max<long long>(per, 1), EV_MAX_BLOCKS), (unsigned)a->B);
-  const size_t lds_hist = sizeof(int) * (size_t)g.tiles;
-  SAST_LAUNCH(ev_count_kernel<true>, gb, dim3(EV_THREADS), lds_hist, st, *a, g, w.tile_cnt);
-  SAST_LAUNCH(ev_scan_kernel, dim3((unsigned)a->B), dim3(EV_THREADS), 0, st, *a, g, w.tile_cnt, w.off, w.cursor, w.ovf);
-  SAST_LAUNCH(ev_scatter_kernel<true>, gb, dim3(EV_THREADS), lds_hist, st, *a, g, w.cursor, (const int*)w.ovf, w.recs);
-  SAST_LAUNCH(md_accum_kernel, dim3((unsigned)g.tiles, (unsigned)a->B), dim3(EV_THREADS), (size_t)lds_acc, st, *a, g, (const int*)w.off,
-              (const unsigned*)w.recs);
-  SAST_CHECK_LAUNCH();
-  return SAST_OK;
+  return sast::ev_frames<true>(m, g, stream);
 }
 
 }  // extern "C"

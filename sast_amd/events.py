@@ -73,6 +73,12 @@ def _md_cutoff(count_cutoff: Optional[int]) -> Optional[int]:
 REPRESENTATIONS = ("stacked_histogram", "mixed_density")
 
 
+def _not_capturing(what: str = "one un-captured warm-up call is needed before graph capture"):
+    """buffers are allocated outside graph capture only: the first call with new sizes must be an ordinary one"""
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("sast_amd.events: " + what)
+
+
 class _Frames:
     """geometry + the device workspace of sast_event_frames / sast_mdstack_frames (zero when created, left zero by every call)"""
 
@@ -114,8 +120,7 @@ class _Frames:
         key = (device, B)
         ws = self._ws.get(key)
         if ws is None or ws.numel() < need:
-            if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("sast_amd.events: one un-captured warm-up call is needed before graph capture")
+            _not_capturing()
             self._ws.clear()
             ws = self._ws[key] = torch.zeros(need, dtype=torch.uint8, device=device)
         return ws
@@ -139,6 +144,19 @@ class _Frames:
             return
         a.count_cutoff, a.fastmode = self.count_cutoff, int(self.fastmode)
         L.check(L.lib().sast_event_frames(C.byref(a), _stream()), "event_frames")
+
+    def construct(self, x: torch.Tensor, y: torch.Tensor, pol: torch.Tensor, time: torch.Tensor, check: bool = True) -> torch.Tensor:
+        """one window, the whole arrays (time sorted) -> frame_dtype [C, height, width]: the reference classes' `construct`"""
+        cols, codes = _columns(x, y, pol, time)
+        dev = cols[0].device
+        n = cols[0].numel()
+        bounds = torch.tensor([[0, n]], dtype=torch.int64, device=dev)
+        err = torch.zeros(2, dtype=torch.int32, device=dev)
+        out = torch.empty((1,) + self.get_shape(), dtype=self.frame_dtype, device=dev)
+        self.launch(cols, codes, n, bounds, out, err, max(n, 1), clip_negative_polarity=False)
+        if check:
+            _raise_on_errors(err)
+        return out[0]
 
 
 def _raise_on_errors(err: torch.Tensor):
@@ -168,18 +186,6 @@ class StackedHistogram(_Frames):
     def dtype(self) -> torch.dtype:
         return torch.uint8
 
-    def construct(self, x: torch.Tensor, y: torch.Tensor, pol: torch.Tensor, time: torch.Tensor, check: bool = True) -> torch.Tensor:
-        cols, codes = _columns(x, y, pol, time)
-        dev = cols[0].device
-        n = cols[0].numel()
-        bounds = torch.tensor([[0, n]], dtype=torch.int64, device=dev)
-        err = torch.zeros(2, dtype=torch.int32, device=dev)
-        out = torch.empty((1,) + self.get_shape(), dtype=torch.uint8, device=dev)
-        self.launch(cols, codes, n, bounds, out, err, max(n, 1), clip_negative_polarity=False)
-        if check:
-            _raise_on_errors(err)
-        return out[0]
-
 
 class MixedDensityEventStack(_Frames):
     """representations.py:130-218 on device tensors: `construct(x, y, pol, time)` -> int8 [bins, height, width].
@@ -202,20 +208,40 @@ class MixedDensityEventStack(_Frames):
     def dtype(self) -> torch.dtype:
         return torch.int8
 
-    def construct(self, x: torch.Tensor, y: torch.Tensor, pol: torch.Tensor, time: torch.Tensor, check: bool = True) -> torch.Tensor:
-        cols, codes = _columns(x, y, pol, time)
-        dev = cols[0].device
-        n = cols[0].numel()
-        bounds = torch.tensor([[0, n]], dtype=torch.int64, device=dev)
-        err = torch.zeros(2, dtype=torch.int32, device=dev)
-        out = torch.empty((1,) + self.get_shape(), dtype=torch.int8, device=dev)
-        self.launch(cols, codes, n, bounds, out, err, max(n, 1), clip_negative_polarity=False)
-        if check:
-            _raise_on_errors(err)
-        return out[0]
+
+class _Windowed(_Frames):
+    """what `EventFrames` and `EventStreams` share: the window rule (duration or count), the time-correction carry `t_last`, the error
+    counters `err`, and the buffers kept between calls.  Those are allocated by ordinary calls only: one un-captured warm-up call with
+    the same sizes is needed before a call can be captured in a graph."""
+
+    def __init__(self, bins: int, height: int, width: int, count_cutoff: Optional[int], fastmode: bool, downsample_by_2: bool,
+                 representation: str, duration_us: Optional[int], num_events: Optional[int], correct_time: bool,
+                 window_capacity: Optional[int]):
+        super().__init__(bins, height, width, count_cutoff, fastmode, downsample_by_2, representation)
+        if (duration_us is None) == (num_events is None):
+            raise ValueError("sast_amd.events: give exactly one of duration_us and num_events")
+        if (duration_us if duration_us is not None else num_events) < (0 if duration_us is not None else 1):
+            raise ValueError("sast_amd.events: duration_us must be >= 0, num_events >= 1")
+        self.mode = L.EVENT_WINDOW_DURATION if duration_us is not None else L.EVENT_WINDOW_COUNT
+        self.value = int(duration_us if duration_us is not None else num_events)
+        self.correct_time = bool(correct_time)
+        self.window_capacity = None if window_capacity is None else int(window_capacity)
+        self.t_last: Optional[torch.Tensor] = None
+        self.err: Optional[torch.Tensor] = None
+        self.last_bounds: Optional[torch.Tensor] = None
+        self._state = {}
+
+    def _carry(self, dev, shape):
+        if self.t_last is None or self.t_last.device != dev:
+            self.t_last = torch.zeros(shape, dtype=torch.int64, device=dev)
+            self.err = torch.zeros(2, dtype=torch.int32, device=dev)
+
+    def errors(self) -> Tuple[int, int]:
+        """(invalid events, windows over capacity) since the last reset() (synchronises)"""
+        return (0, 0) if self.err is None else tuple(int(v) for v in self.err.tolist())
 
 
-class EventFrames(_Frames):
+class EventFrames(_Windowed):
     """Batched stacked-histogram frames from one event buffer (the windowing of preprocess_dataset.py:507-530).
 
     frames = ef(x, y, p, t, ends_us, n=None) -> uint8 [B, 2*bins, H', W'] (H' = height // 2, W' = width // 2 with downsample_by_2).
@@ -237,29 +263,16 @@ class EventFrames(_Frames):
     def __init__(self, height: int, width: int, bins: int = 10, count_cutoff: Optional[int] = 10, fastmode: bool = True,
                  duration_us: Optional[int] = None, num_events: Optional[int] = None, downsample_by_2: bool = False,
                  correct_time: bool = True, window_capacity: Optional[int] = None, representation: str = "stacked_histogram"):
-        super().__init__(bins, height, width, count_cutoff, fastmode, downsample_by_2, representation)
-        if (duration_us is None) == (num_events is None):
-            raise ValueError("sast_amd.events: give exactly one of duration_us and num_events")
-        if (duration_us if duration_us is not None else num_events) < (0 if duration_us is not None else 1):
-            raise ValueError("sast_amd.events: duration_us must be >= 0, num_events >= 1")
-        self.mode = L.EVENT_WINDOW_DURATION if duration_us is not None else L.EVENT_WINDOW_COUNT
-        self.value = int(duration_us if duration_us is not None else num_events)
-        self.correct_time = bool(correct_time)
-        self.window_capacity = None if window_capacity is None else int(window_capacity)
-        self.t_last: Optional[torch.Tensor] = None
-        self.err: Optional[torch.Tensor] = None
-        self._state = {}
+        super().__init__(bins, height, width, count_cutoff, fastmode, downsample_by_2, representation, duration_us, num_events,
+                         correct_time, window_capacity)
 
     def _buffers(self, dev, capacity: int):
         st = self._state.get("cap")
         if st is None or st[0] != dev or st[1] < capacity:
-            if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("sast_amd.events: one un-captured warm-up call is needed before graph capture")
+            _not_capturing()
             self._state = {"cap": (dev, capacity), "t": torch.empty(max(capacity, 1), dtype=torch.int64, device=dev),
                            "scan": torch.empty(L.EVENT_SCAN_BLOCKS + 1, dtype=torch.int64, device=dev)}
-        if self.t_last is None or self.t_last.device != dev:
-            self.t_last = torch.zeros((), dtype=torch.int64, device=dev)
-            self.err = torch.zeros(2, dtype=torch.int32, device=dev)
+        self._carry(dev, ())
         return self._state
 
     def reset(self):
@@ -267,10 +280,6 @@ class EventFrames(_Frames):
         if self.t_last is not None:
             self.t_last.zero_()
             self.err.zero_()
-
-    def errors(self) -> Tuple[int, int]:
-        """(invalid events, windows over capacity) since the last reset() (synchronises)"""
-        return (0, 0) if self.err is None else tuple(int(v) for v in self.err.tolist())
 
     def __call__(self, x: torch.Tensor, y: torch.Tensor, p: torch.Tensor, t: torch.Tensor, ends_us: torch.Tensor,
                  n: Optional[torch.Tensor] = None, check: bool = False) -> torch.Tensor:
@@ -284,8 +293,7 @@ class EventFrames(_Frames):
         if n is None:
             n = st.get("n")
             if n is None or int(st["n_val"]) != cap:
-                if torch.cuda.is_current_stream_capturing():
-                    raise RuntimeError("sast_amd.events: pass n (a device tensor) when capturing, or warm up with the same buffer length")
+                _not_capturing("pass n (a device tensor) when capturing, or warm up with the same buffer length")
                 n = st["n"] = torch.full((1,), cap, dtype=torch.int64, device=dev)
                 st["n_val"] = cap
         elif n.dtype != torch.int64 or n.numel() != 1:
@@ -313,7 +321,7 @@ class EventFrames(_Frames):
         return out
 
 
-class EventStreams(_Frames):
+class EventStreams(_Windowed):
     """`EventFrames` for S recordings side by side: frames for every recording, and for T steps of each, in one call.
 
     frames = es(x, y, p, t, counts, ends_us, reset=None, check=False, out=None)
@@ -338,38 +346,23 @@ class EventStreams(_Frames):
     def __init__(self, num_streams: int, height: int, width: int, bins: int = 10, count_cutoff: Optional[int] = 10, fastmode: bool = True,
                  duration_us: Optional[int] = None, num_events: Optional[int] = None, downsample_by_2: bool = False,
                  correct_time: bool = True, window_capacity: Optional[int] = None, representation: str = "stacked_histogram"):
-        super().__init__(bins, height, width, count_cutoff, fastmode, downsample_by_2, representation)
+        super().__init__(bins, height, width, count_cutoff, fastmode, downsample_by_2, representation, duration_us, num_events,
+                         correct_time, window_capacity)
         if int(num_streams) < 1 or int(num_streams) > 65535:
             raise ValueError("sast_amd.events: num_streams must be in 1 .. 65535")
-        if (duration_us is None) == (num_events is None):
-            raise ValueError("sast_amd.events: give exactly one of duration_us and num_events")
-        if (duration_us if duration_us is not None else num_events) < (0 if duration_us is not None else 1):
-            raise ValueError("sast_amd.events: duration_us must be >= 0, num_events >= 1")
         self.num_streams = int(num_streams)
-        self.mode = L.EVENT_WINDOW_DURATION if duration_us is not None else L.EVENT_WINDOW_COUNT
-        self.value = int(duration_us if duration_us is not None else num_events)
-        self.correct_time = bool(correct_time)
-        self.window_capacity = None if window_capacity is None else int(window_capacity)
-        self.t_last: Optional[torch.Tensor] = None
-        self.err: Optional[torch.Tensor] = None
-        self.last_bounds: Optional[torch.Tensor] = None
-        self._state = {}
 
     def _buffers(self, dev, cap: int, windows: int):
         S = self.num_streams
         st = self._state
         if st.get("cap") is None or st["cap"][0] != dev or st["cap"][1] < cap:
-            if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("sast_amd.events: one un-captured warm-up call is needed before graph capture")
+            _not_capturing()
             st = self._state = {"cap": (dev, cap), "t": torch.empty(max(S * cap, 1), dtype=torch.int64, device=dev),
                                 "scan": torch.empty(int(L.lib().sast_evstreams_ws_count(S)), dtype=torch.int64, device=dev), "bounds": {}}
         if windows not in st["bounds"]:
-            if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("sast_amd.events: one un-captured warm-up call with the same number of windows is needed before graph capture")
+            _not_capturing("one un-captured warm-up call with the same number of windows is needed before graph capture")
             st["bounds"][windows] = torch.empty(windows, 2, dtype=torch.int64, device=dev)
-        if self.t_last is None or self.t_last.device != dev:
-            self.t_last = torch.zeros(S, dtype=torch.int64, device=dev)
-            self.err = torch.zeros(2, dtype=torch.int32, device=dev)
+        self._carry(dev, (S,))
         return st
 
     def reset(self, streams=None):
@@ -386,10 +379,6 @@ class EventStreams(_Frames):
             raise ValueError(f"sast_amd.events: streams must be in 0 .. {self.num_streams - 1}")
         if idx:
             self.t_last[torch.tensor(idx, dtype=torch.int64, device=self.t_last.device)] = 0
-
-    def errors(self) -> Tuple[int, int]:
-        """(invalid events, windows over capacity) since the last reset() (synchronises)"""
-        return (0, 0) if self.err is None else tuple(int(v) for v in self.err.tolist())
 
     def __call__(self, x: torch.Tensor, y: torch.Tensor, p: torch.Tensor, t: torch.Tensor, counts: torch.Tensor, ends_us: torch.Tensor,
                  reset: Optional[torch.Tensor] = None, check: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -339,3 +339,54 @@ def test_event_front_end_and_backbone_in_one_graph():
         assert torch.equal(g_fr, fr)
         for u, v in zip(flat(g_out), outs):
             assert torch.equal(u, v)
+
+
+@gpu
+def test_time_correction_and_window_search_do_not_depend_on_the_entry_point():
+    """one recording through the single-recording calls (512 scan blocks of 5 events, the last 12 with an empty chunk, and a carry loop
+    that strides over more partial maxima than a block has threads from block 256 on) and through the per-row calls with S = 1 (one
+    block): the same kernels on two grids give what numpy gives, and neither reads or writes past the count"""
+    from sast_amd import _lib as L
+    from sast_amd.functional import _stream
+    lib = L.lib()
+    cap, n, sentinel = 3000, 2500, -7
+    t = np.full(cap, 2 ** 31 - 1, dtype=np.int64)
+    t[:n] = G.stream(seed=77, n=n, height=24, width=40, t_step=4, jitter=30)[3]
+    carry = int(np.sort(t[:n])[25]) + 1
+    assert (t[:5] < carry).all() and (np.diff(t[:n]) < 0).any()
+    want = np.maximum.accumulate(np.maximum(t[:n], carry))
+    t_dev, n_dev = _dev(t, torch.int32), _dev([n])
+    scan = torch.empty(int(lib.sast_evstreams_ws_count(1)), dtype=torch.int64, device="cuda")
+    assert scan.numel() == L.EVENT_SCAN_BLOCKS + 1
+    corrected = []
+    for rows in (False, True):
+        t_out = torch.full((cap,), sentinel, dtype=torch.int64, device="cuda")
+        t_last = _dev([carry])
+        if rows:
+            L.check(lib.sast_evstreams_correct_time(t_dev.data_ptr(), L.DT_I32, n_dev.data_ptr(), 1, cap, t_out.data_ptr(),
+                                                    t_last.data_ptr(), None, scan.data_ptr(), _stream()), "evstreams_correct_time")
+        else:
+            L.check(lib.sast_event_correct_time(t_dev.data_ptr(), L.DT_I32, n_dev.data_ptr(), cap, t_out.data_ptr(), t_last.data_ptr(),
+                                                scan.data_ptr(), _stream()), "event_correct_time")
+        got = t_out.cpu().numpy()
+        assert np.array_equal(got[:n], want), rows
+        assert int(t_last) == int(want[-1]), rows
+        assert (got[n:] == sentinel).all(), rows
+        corrected.append(t_out)
+    repeated = int(want[np.flatnonzero(np.diff(want) == 0)[600]])
+    ends = np.array([want[0] - 1, want[-1] + 5, repeated, want[300], want[1700]], dtype=np.int64)
+    end = np.searchsorted(want, ends, "right")
+    assert end[0] == 0 and end[1] == n and end[2] - np.searchsorted(want, repeated, "left") >= 2
+    ends_dev = _dev(ends)
+    for mode, value in ((L.EVENT_WINDOW_DURATION, 500), (L.EVENT_WINDOW_COUNT, 700)):
+        start = np.maximum(end - value, 0) if mode == L.EVENT_WINDOW_COUNT else np.searchsorted(want, ends - value, "left")
+        assert mode != L.EVENT_WINDOW_COUNT or 0 < end[3] < value                  # a count window clipped at the first event
+        for rows, tc in zip((False, True), corrected):
+            bounds = torch.full((5, 2), sentinel, dtype=torch.int64, device="cuda")
+            if rows:
+                L.check(lib.sast_evstreams_window_bounds(tc.data_ptr(), n_dev.data_ptr(), 1, cap, ends_dev.data_ptr(), 5, mode, value,
+                                                         bounds.data_ptr(), _stream()), "evstreams_window_bounds")
+            else:
+                L.check(lib.sast_event_window_bounds(tc.data_ptr(), n_dev.data_ptr(), cap, ends_dev.data_ptr(), 5, mode, value,
+                                                     bounds.data_ptr(), _stream()), "event_window_bounds")
+            assert np.array_equal(bounds.cpu().numpy(), np.stack([start, end], 1)), (mode, rows)
