@@ -535,6 +535,62 @@ int sast_evstreams_correct_time(const void* t, int t_dtype, const int64_t* count
 int sast_evstreams_window_bounds(const int64_t* t, const int64_t* counts, int S, int64_t stream_capacity, const int64_t* ends_us, int T,
                                  int mode, int64_t value, int64_t* bounds, sast_stream_t stream);
 
+/* ---- event retention across chunks (csrc/k_events.hip): S rows of [S, capacity] storage keep exactly the events that later windows can
+ * still need, so a host pushes chunks cut at arbitrary points (a camera's transfer size) and asks for windows as their ends pass.  The
+ * reference has no such stage: it reads a whole recording and windows it offline (scripts/genx/preprocess_dataset.py:476-530); the
+ * frames here equal what sast_evstreams_* + sast_event_frames give for the whole recording in one buffer.  Row s's live events are
+ * storage indices [head[s], count[s]); timestamps are stored corrected (the reader's running maximum, :159-168, carried in t_last[s]).
+ * All state is device memory owned by the caller; every per-row size is read on the device and clamped to capacity there; grids are
+ * sized from capacities, so the calls replay inside a graph.  Rows never see each other's carry, head or events. */
+typedef struct SastEvQueueArgs {
+  int16_t* x;               /* retained columns, int16 [S, capacity] (narrowed with saturation: a value outside int16 stays invalid) */
+  int16_t* y;
+  int16_t* p;
+  int64_t* t;               /* corrected timestamps, int64 [S, capacity] */
+  int64_t* head;            /* int64 [S] */
+  int64_t* count;           /* int64 [S] */
+  int64_t* t_last;          /* int64 [S]: the time-correction carry */
+  int64_t* retired;         /* int64 [S]: events retired from the row since its last reset */
+  int64_t* retired_t;       /* int64 [S]: the corrected time of the last retired event */
+  int32_t* err;             /* int32 [4], ACCUMULATED: [0] invalid events, [1] windows over window_capacity (both written by
+                               sast_event_frames / sast_mdstack_frames, which take this pointer as their err), [2] events dropped for
+                               lack of room, [3] late windows */
+  int64_t* ws;              /* int64 [sast_evqueue_ws_count(S)]; no initial contents needed */
+  int64_t capacity;         /* events one row holds; S * capacity <= 2^31 - 1 */
+  int32_t S;                /* 1 .. 65535 */
+  int32_t reserved;
+} SastEvQueueArgs;
+/* the dtype code of packed records (sast_evqueue_push only): Prophesee's Event2D as the reference reads it, EV_TYPE of
+ * utils/evaluation/prophesee/io/dat_events_tools.py:18-50 -- 8 bytes, little-endian: u4 t, then i4 x | y << 14 | p << 28 */
+enum { SAST_EVQUEUE_DT_DAT = 6 };
+
+/* int64 elements of SastEvQueueArgs.ws: S * (SAST_EVENT_SCAN_BLOCKS + 6) -- per row the time scan's carry and partial maxima
+ * (SAST_EVENT_SCAN_BLOCKS + 1), the append plan (3) and the move plan (2).  0: S < 1 or S > 65535.  Host only. */
+size_t sast_evqueue_ws_count(int S);
+/* per row s: with reset != NULL and reset[s] != 0 the row is emptied first (head, count, t_last, retired, retired_t = 0).  Then the
+ * first n_s = min(max(counts[s], 0), chunk_capacity) events of chunk row s are appended behind count[s], as many as fit
+ * (capacity - count[s]; the chunk's first ones); the rest are added to err[2].  The stored timestamps are max(t, carry, the stored
+ * timestamps before it in the chunk) with carry = t_last[s] (preprocess_dataset.py:159-168); t_last[s] advances over the stored events.
+ * x, y, p: SAST_DT_I64 / I32 / I16 [S, chunk_capacity], t: SAST_DT_I64 / I32.  t_dtype == SAST_EVQUEUE_DT_DAT: t holds int32
+ * [S, chunk_capacity, 2] packed records, decoded as load_td_data does (dat_events_tools.py:39-50): t the unsigned word 0 (the 32-bit
+ * clock is not unwrapped), x = w & 16383, y = (w >> 14) & 16383, p = (w >> 28) & 1 of word 1, bits 29-31 ignored; x, y, p and their
+ * dtypes are then not read.  2 launches (partial maxima; scan + decode + append). */
+int sast_evqueue_push(const SastEvQueueArgs* q, const void* x, const void* y, const void* p, const void* t, int x_dtype, int y_dtype,
+                      int p_dtype, int t_dtype, const int64_t* counts, int64_t chunk_capacity, const uint8_t* reset, sast_stream_t stream);
+/* sast_evstreams_window_bounds (preprocess_dataset.py:507-513) over each row's live events: window w = k * S + s (ends_us int64 [T, S])
+ * -> bounds int64 [T * S, 2], indices into the flattened [S * capacity] storage; a count window stops at the row's first live event.
+ * A window that needs retired events is added to err[3]: duration -- retired[s] > 0 and retired_t[s] >= end - value; count -- fewer
+ * than `value` live events up to the end and retired[s] > 0.  1 launch. */
+int sast_evqueue_window_bounds(const SastEvQueueArgs* q, const int64_t* ends_us, int T, int mode, int64_t value, int64_t* bounds,
+                               sast_stream_t stream);
+/* after the frames of `bounds` (as written by sast_evqueue_window_bounds with the same T): row s keeps its events from the start of
+ * its last window, step T - 1; those before it are retired (retired[s], retired_t[s]).  A row whose live events number no more than
+ * the slots in front of them is moved to the front of its storage (source and destination disjoint); any other row keeps its place,
+ * so capacity >= 2 x (the most live events of a row right after this call) + (the most events pushed to it between two such calls)
+ * never drops an event.
+ * 2 launches (one thread per row decides and writes the plan; the copy reads only the plan). */
+int sast_evqueue_retire(const SastEvQueueArgs* q, const int64_t* bounds, int T, sast_stream_t stream);
+
 /* ---- spatial augmentation of event frames and box labels (csrc/k_augment.hip).  The reference augments on the CPU in its data-loader
  * workers: RandomSpatialAugmentorGenX.__call__ (data/utils/augmentor.py:347-364) -- horizontal flip, then zoom-in (:203-222) or zoom-out
  * (:134-153) -- with the label transforms of ObjectLabels (data/genx_utils/labels.py:255-339).  Both calls read the per-sample

@@ -21,6 +21,7 @@ F32 = C.c_float
 DT_F32, DT_I32, DT_U8, DT_I64, DT_I16, DT_I8 = 0, 1, 2, 3, 4, 5
 EVENT_WINDOW_DURATION, EVENT_WINDOW_COUNT = 0, 1
 EVENT_SCAN_BLOCKS = 512   # SAST_EVENT_SCAN_BLOCKS
+EVQUEUE_DT_DAT = 6        # SAST_EVQUEUE_DT_DAT
 AUGMENT_PARAM_WORDS = 16  # SAST_AUGMENT_PARAM_WORDS
 AUGMENT_NONE, AUGMENT_ZOOM_IN, AUGMENT_ZOOM_OUT = 0, 1, 2
 EVAL_STATE_WORDS, EVAL_MAX_CLASSES = 32, 4   # SAST_EVAL_STATE_WORDS, SAST_EVAL_MAX_CLASSES
@@ -86,6 +87,9 @@ SastEventArgs = _struct("SastEventArgs", [
 SastMdStackArgs = _struct("SastMdStackArgs", [
     (P, "x y p t bounds out err ws"), (C.c_int64, "capacity window_capacity"),
     (I32, "x_dtype y_dtype p_dtype t_dtype B bins height width count_cutoff downsample_by_2 clip_negative_polarity"),
+])
+SastEvQueueArgs = _struct("SastEvQueueArgs", [
+    (P, "x y p t head count t_last retired retired_t err ws"), (C.c_int64, "capacity"), (I32, "S reserved"),
 ])
 SastEvalArgs = _struct("SastEvalArgs", [
     (P, "labels counts det n_det"), (I32, "N M A K"), (F32, "min_diag2 min_side"), (I32, "max_images max_labels_per_frame"),
@@ -169,6 +173,10 @@ _SIGNATURES = {
     "sast_evstreams_ws_count": (C.c_size_t, [C.c_int]),
     "sast_evstreams_correct_time": (C.c_int, [P, C.c_int, P, C.c_int, C.c_int64, P, P, P, P, P]),
     "sast_evstreams_window_bounds": (C.c_int, [P, P, C.c_int, C.c_int64, P, C.c_int, C.c_int, C.c_int64, P, P]),
+    "sast_evqueue_ws_count": (C.c_size_t, [C.c_int]),
+    "sast_evqueue_push": (C.c_int, [C.POINTER(SastEvQueueArgs), P, P, P, P, C.c_int, C.c_int, C.c_int, C.c_int, P, C.c_int64, P, P]),
+    "sast_evqueue_window_bounds": (C.c_int, [C.POINTER(SastEvQueueArgs), P, C.c_int, C.c_int, C.c_int64, P, P]),
+    "sast_evqueue_retire": (C.c_int, [C.POINTER(SastEvQueueArgs), P, C.c_int, P]),
     "sast_augment_frames": (C.c_int, [P, P, P] + [C.c_int] * 5 + [P]),
     "sast_augment_labels": (C.c_int, [P, P, P] + [C.c_int] * 4 + [P, P, P, P]),
     "sast_eval_reset": (C.c_int, [C.POINTER(SastEvalArgs), P]),

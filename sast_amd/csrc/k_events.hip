@@ -326,6 +326,25 @@ __device__ __forceinline__ long long block_max(long long v, long long* red) {
   return m;
 }
 
+// one EV_THREADS-wide step of a running maximum: *v becomes max(*v, the values of the threads before it, carry); returns the carry out
+// (the maximum of the whole step and the carry in).  Every thread of the workgroup calls it.
+__device__ __forceinline__ long long block_max_scan(long long* v, long long carry, long long* wtot) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  long long m = *v;
+  for (int d = 1; d < 64; d <<= 1) {                      // inclusive max-scan of the wave
+    const long long u = __shfl_up(m, d);
+    if (lane >= d) m = max(m, u);
+  }
+  __syncthreads();
+  if (lane == 63) wtot[wv] = m;
+  __syncthreads();
+  long long pre = carry;
+  for (int k = 0; k < wv; ++k) pre = max(pre, wtot[k]);
+  *v = max(m, pre);
+  for (int k = wv; k < EV_THREADS / 64; ++k) pre = max(pre, wtot[k]);
+  return pre;
+}
+
 // Row blockIdx.y of the [S, cap] buffers is one recording with its own count, carry and windows; a single recording is S = 1.  Two
 // passes with gridDim.x blocks per row: a row's partial maxima and its carry live in its own ws row (ws[s][0] = carry in,
 // ws[s][1 + blk] = the maximum of block blk's chunk of row s), so no maximum is ever taken across rows.  The results are integer
@@ -363,23 +382,11 @@ __global__ __launch_bounds__(EV_THREADS) void ev_tmax_apply_kernel(const void* t
   long long carry = LLONG_MIN;
   for (int k = threadIdx.x; k < (int)blockIdx.x + 1; k += EV_THREADS) carry = max(carry, ws[k]);
   carry = block_max(carry, red);
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   for (long long base = lo; base < hi; base += EV_THREADS) {
     const long long i = base + threadIdx.x;
     long long v = i < hi ? ld_int(t, dt, row + i) : LLONG_MIN;
-    for (int d = 1; d < 64; d <<= 1) {                    // inclusive max-scan of the wave
-      const long long u = __shfl_up(v, d);
-      if (lane >= d) v = max(v, u);
-    }
-    __syncthreads();
-    if (lane == 63) wtot[wv] = v;
-    __syncthreads();
-    long long pre = carry;
-    for (int k = 0; k < wv; ++k) pre = max(pre, wtot[k]);
-    v = max(v, pre);
+    carry = block_max_scan(&v, carry, wtot);
     if (i < hi) t_out[row + i] = v;
-    for (int k = wv; k < EV_THREADS / 64; ++k) pre = max(pre, wtot[k]);
-    carry = pre;
   }
   // an empty row has only LLONG_MIN partials: t_last[s] = the carry in (0 after a reset)
   if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) {
@@ -519,6 +526,190 @@ int ev_window_bounds(const int64_t* t, const int64_t* counts, int S, int64_t cap
   return SAST_OK;
 }
 
+
+// ---- the event queue (sast_evqueue_*): S rows of retained events [head, count) in [S, capacity] storage, fed by chunks of any size.
+// Every index into a row is formed from device-read sizes and clamped to capacity / chunk_capacity before it is used.
+constexpr int EVQ_ROW_WS = EV_ROW_WS + 5;     // a row's ws: the scan's carry + partial maxima, then the append plan and the move plan
+constexpr int EVQ_APPEND_BASE = EV_ROW_WS, EVQ_APPEND_N = EV_ROW_WS + 1, EVQ_DROPPED = EV_ROW_WS + 2, EVQ_MOVE_SRC = EV_ROW_WS + 3,
+              EVQ_MOVE_N = EV_ROW_WS + 4;
+
+struct EvqChunk {
+  const void *x, *y, *p, *t;     // columns [S, chunk_cap]; packed records: t holds them, x / y / p are not read
+  int xd, yd, pd, td;
+  const long long* counts;
+  long long chunk_cap;
+  const unsigned char* reset;
+};
+
+// Event2D of the reference's reader (dat_events_tools.py:18-50): word 0 the unsigned 32-bit time, word 1 x | y << 14 | p << 28
+__device__ __forceinline__ long long evq_time(const EvqChunk& c, long long i) {
+  if (c.td == SAST_EVQUEUE_DT_DAT) return (long long)static_cast<const unsigned*>(c.t)[2 * i];
+  return ld_int(c.t, c.td, i);
+}
+
+__device__ __forceinline__ short sat16(long long v) { return (short)min(max(v, -32768LL), 32767LL); }
+
+// push, pass 1: the partial maxima of the timestamps that will be stored, and (block 0 of a row) the append plan: where the chunk
+// goes and how much of it fits.  Reads the queue's state, writes only ws.
+__global__ __launch_bounds__(EV_THREADS) void evq_partial_kernel(SastEvQueueArgs q, EvqChunk c, long long* ws_all) {
+  __shared__ long long red[EV_THREADS / 64];
+  const int s = blockIdx.y;
+  const bool rst = c.reset && c.reset[s];
+  const long long cap = q.capacity;
+  const long long base = rst ? 0LL : min(max((long long)q.count[s], 0LL), cap);
+  const long long want = min(max(c.counts[s], 0LL), c.chunk_cap);
+  const long long n = min(want, cap - base), row = (long long)s * c.chunk_cap;
+  long long lo, hi;
+  ev_tchunk(n, &lo, &hi);
+  long long m = LLONG_MIN;
+  for (long long i = lo + threadIdx.x; i < hi; i += EV_THREADS) m = max(m, evq_time(c, row + i));
+  m = block_max(m, red);
+  if (threadIdx.x == 0) {
+    long long* w = ws_all + (size_t)s * EVQ_ROW_WS;
+    w[1 + blockIdx.x] = m;
+    if (blockIdx.x == 0) {
+      w[0] = rst ? 0LL : (long long)q.t_last[s];
+      w[EVQ_APPEND_BASE] = base;
+      w[EVQ_APPEND_N] = n;
+      w[EVQ_DROPPED] = want - n;
+    }
+  }
+}
+
+// push, pass 2: the running maximum from the row's carry, the decode / saturating narrowing, the append behind the plan's base; the
+// row's last workgroup then writes the new state.  No workgroup reads state that another one writes: sizes come from the plan.
+__global__ __launch_bounds__(EV_THREADS) void evq_append_kernel(SastEvQueueArgs q, EvqChunk c, const long long* ws_all) {
+  __shared__ long long red[EV_THREADS / 64];
+  __shared__ long long wtot[EV_THREADS / 64];
+  const int s = blockIdx.y;
+  const long long* ws = ws_all + (size_t)s * EVQ_ROW_WS;
+  const long long cap = q.capacity;
+  const long long base = min(max(ws[EVQ_APPEND_BASE], 0LL), cap);
+  const long long n = min(min(max(ws[EVQ_APPEND_N], 0LL), cap - base), c.chunk_cap);
+  const long long row = (long long)s * c.chunk_cap, qrow = (long long)s * cap + base;
+  long long lo, hi;
+  ev_tchunk(n, &lo, &hi);
+  long long carry = LLONG_MIN;
+  for (int k = threadIdx.x; k < (int)blockIdx.x + 1; k += EV_THREADS) carry = max(carry, ws[k]);
+  carry = block_max(carry, red);
+  for (long long b0 = lo; b0 < hi; b0 += EV_THREADS) {
+    const long long i = b0 + threadIdx.x;
+    long long v = LLONG_MIN;
+    short x = 0, y = 0, p = 0;
+    if (i < hi) {
+      if (c.td == SAST_EVQUEUE_DT_DAT) {
+        const uint2 r = static_cast<const uint2*>(c.t)[row + i];       // one coalesced 8-byte load per record
+        v = (long long)r.x;
+        x = (short)(r.y & 16383u);
+        y = (short)((r.y >> 14) & 16383u);
+        p = (short)((r.y >> 28) & 1u);
+      } else {
+        v = ld_int(c.t, c.td, row + i);
+        x = sat16(ld_int(c.x, c.xd, row + i));
+        y = sat16(ld_int(c.y, c.yd, row + i));
+        p = sat16(ld_int(c.p, c.pd, row + i));
+      }
+    }
+    carry = block_max_scan(&v, carry, wtot);
+    if (i < hi) {
+      q.t[qrow + i] = v;
+      q.x[qrow + i] = x;
+      q.y[qrow + i] = y;
+      q.p[qrow + i] = p;
+    }
+  }
+  if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) {
+    long long m = ws[0];
+    for (int k = 1; k <= (int)gridDim.x; ++k) m = max(m, ws[k]);
+    q.t_last[s] = m;
+    q.count[s] = base + n;
+    if (c.reset && c.reset[s]) {
+      q.head[s] = 0;
+      q.retired[s] = 0;
+      q.retired_t[s] = 0;
+    }
+    if (ws[EVQ_DROPPED] > 0) atomicAdd(&q.err[2], (int)min(ws[EVQ_DROPPED], (long long)INT_MAX));
+  }
+}
+
+// a row's live range [h, c) inside its storage
+__device__ __forceinline__ void evq_live(const SastEvQueueArgs& q, int s, long long* h, long long* c) {
+  *h = min(max((long long)q.head[s], 0LL), (long long)q.capacity);
+  *c = min(max((long long)q.count[s], *h), (long long)q.capacity);
+}
+
+// the search of ev_bounds_kernel over a row's live events; a window that needs retired events is counted in err[3]
+__global__ void evq_bounds_kernel(SastEvQueueArgs q, const long long* ends, int B, int mode, long long value, long long* bounds) {
+  const int w = blockIdx.x * blockDim.x + threadIdx.x;     // window k * S + s
+  if (w >= B) return;
+  const int s = w % q.S;
+  long long h, c;
+  evq_live(q, s, &h, &c);
+  const long long row = (long long)s * q.capacity;
+  const long long* t = reinterpret_cast<const long long*>(q.t) + row + h;
+  const long long e = h + search(t, c - h, ends[w], true);
+  long long b;
+  bool late;
+  if (mode == SAST_EVENT_WINDOW_COUNT) {
+    b = max(e - value, h);
+    late = e - h < value && q.retired[s] > 0;
+  } else {
+    b = h + search(t, c - h, ends[w] - value, false);
+    late = q.retired[s] > 0 && (long long)q.retired_t[s] >= ends[w] - value;
+  }
+  bounds[2 * w] = row + b;
+  bounds[2 * w + 1] = row + e;
+  if (late) atomicAdd(&q.err[3], 1);
+}
+
+// retire, pass 1, one thread per row: everything before the start of the row's last window leaves; the row moves to the front of its
+// storage only when the live part fits into the freed part (source and destination disjoint).  Writes the new head / count and the
+// move plan.
+__global__ void evq_plan_kernel(SastEvQueueArgs q, const long long* bounds, int T, long long* ws_all) {
+  const int s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= q.S) return;
+  long long h, c;
+  evq_live(q, s, &h, &c);
+  const long long row = (long long)s * q.capacity;
+  const long long start = min(max(bounds[2 * ((long long)(T - 1) * q.S + s)] - row, h), c);
+  if (start > h) {
+    q.retired[s] += start - h;
+    q.retired_t[s] = reinterpret_cast<const long long*>(q.t)[row + start - 1];
+  }
+  const long long live = c - start;
+  const bool move = start > 0 && live <= start;
+  long long* w = ws_all + (size_t)s * EVQ_ROW_WS;
+  w[EVQ_MOVE_SRC] = start;
+  w[EVQ_MOVE_N] = move ? live : 0;
+  q.head[s] = move ? 0 : start;
+  q.count[s] = move ? live : c;
+}
+
+// retire, pass 2: the moves of the plan.  Reads the plan only; n <= src, so no element is read after it was overwritten.
+__global__ __launch_bounds__(EV_THREADS) void evq_move_kernel(SastEvQueueArgs q, const long long* ws_all) {
+  const int s = blockIdx.y;
+  const long long* w = ws_all + (size_t)s * EVQ_ROW_WS;
+  const long long cap = q.capacity;
+  const long long src = min(max(w[EVQ_MOVE_SRC], 0LL), cap);
+  const long long n = min(min(max(w[EVQ_MOVE_N], 0LL), src), cap - src);
+  const long long row = (long long)s * cap;
+  for (long long i = (long long)blockIdx.x * EV_THREADS + threadIdx.x; i < n; i += (long long)gridDim.x * EV_THREADS) {
+    q.t[row + i] = q.t[row + src + i];
+    q.x[row + i] = q.x[row + src + i];
+    q.y[row + i] = q.y[row + src + i];
+    q.p[row + i] = q.p[row + src + i];
+  }
+}
+
+bool evq_args(const SastEvQueueArgs* q) {
+  return q && q->x && q->y && q->p && q->t && q->head && q->count && q->t_last && q->retired && q->retired_t && q->err && q->ws &&
+         q->S >= 1 && q->S <= 65535 && q->capacity >= 1 && (long long)q->S * q->capacity <= INT_MAX;
+}
+
+long long evq_blocks(long long events) {
+  const long long per = (events + EV_ROW_EVENTS_PER_BLOCK - 1) / EV_ROW_EVENTS_PER_BLOCK;
+  return std::min<long long>(std::max<long long>(per, 1), EV_SCAN_BLOCKS);
+}
 }  // namespace
 }  // namespace sast
 
@@ -584,6 +775,54 @@ int sast_mdstack_frames(const SastMdStackArgs* m, sast_stream_t stream) {
   g.fast = 0;
   g.clip_pol = m->clip_negative_polarity ? 1 : 0;
   return sast::ev_frames<true>(m, g, stream);
+}
+
+size_t sast_evqueue_ws_count(int S) { return S < 1 || S > 65535 ? 0 : (size_t)S * sast::EVQ_ROW_WS; }
+
+int sast_evqueue_push(const SastEvQueueArgs* q, const void* x, const void* y, const void* p, const void* t, int x_dtype, int y_dtype,
+                      int p_dtype, int t_dtype, const int64_t* counts, int64_t chunk_capacity, const uint8_t* reset, sast_stream_t stream) {
+  SAST_ENTRY();
+  if (!sast::evq_args(q) || !t || !counts || chunk_capacity < 0 || chunk_capacity > INT_MAX / q->S) return SAST_EINVAL;
+  if (t_dtype != SAST_EVQUEUE_DT_DAT) {
+    if (!x || !y || !p || !sast::int_dtype(x_dtype) || !sast::int_dtype(y_dtype) || !sast::int_dtype(p_dtype) ||
+        (t_dtype != SAST_DT_I64 && t_dtype != SAST_DT_I32))
+      return SAST_EINVAL;
+  }
+  const sast::EvqChunk c{x, y, p, t, x_dtype, y_dtype, p_dtype, t_dtype, reinterpret_cast<const long long*>(counts),
+                         (long long)chunk_capacity, reinterpret_cast<const unsigned char*>(reset)};
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid((unsigned)sast::evq_blocks(chunk_capacity), (unsigned)q->S);
+  long long* ws = reinterpret_cast<long long*>(q->ws);
+  SAST_LAUNCH(sast::evq_partial_kernel, grid, dim3(sast::EV_THREADS), 0, st, *q, c, ws);
+  SAST_LAUNCH(sast::evq_append_kernel, grid, dim3(sast::EV_THREADS), 0, st, *q, c, (const long long*)ws);
+  SAST_CHECK_LAUNCH();
+  return SAST_OK;
+}
+
+int sast_evqueue_window_bounds(const SastEvQueueArgs* q, const int64_t* ends_us, int T, int mode, int64_t value, int64_t* bounds,
+                               sast_stream_t stream) {
+  SAST_ENTRY();
+  if (!sast::evq_args(q) || !ends_us || !bounds || T < 1 || (long long)q->S * T > INT_MAX || value < 0 ||
+      (mode != SAST_EVENT_WINDOW_DURATION && mode != SAST_EVENT_WINDOW_COUNT))
+    return SAST_EINVAL;
+  const int B = q->S * T;
+  SAST_LAUNCH(sast::evq_bounds_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, *q, reinterpret_cast<const long long*>(ends_us),
+              B, mode, (long long)value, reinterpret_cast<long long*>(bounds));
+  SAST_CHECK_LAUNCH();
+  return SAST_OK;
+}
+
+int sast_evqueue_retire(const SastEvQueueArgs* q, const int64_t* bounds, int T, sast_stream_t stream) {
+  SAST_ENTRY();
+  if (!sast::evq_args(q) || !bounds || T < 1 || (long long)q->S * T > INT_MAX) return SAST_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  long long* ws = reinterpret_cast<long long*>(q->ws);
+  SAST_LAUNCH(sast::evq_plan_kernel, dim3((q->S + 63) / 64), dim3(64), 0, st, *q, reinterpret_cast<const long long*>(bounds), T, ws);
+  // at most half a row moves (live <= head)
+  SAST_LAUNCH(sast::evq_move_kernel, dim3((unsigned)sast::evq_blocks(q->capacity / 2), (unsigned)q->S), dim3(sast::EV_THREADS), 0, st, *q,
+              (const long long*)ws);
+  SAST_CHECK_LAUNCH();
+  return SAST_OK;
 }
 
 }  // extern "C"

@@ -15,6 +15,9 @@ The reference's second representation, MixedDensityEventStack (representations.p
 binned by the logarithm of their age and accumulated over the bins), is `MixedDensityEventStack` here, and
 `representation="mixed_density"` of `EventFrames` / `EventStreams`: the same windows, carries and error counters, int8 frames.
 
+`EventQueue` keeps the events that later windows still need on the device, so a host pushes chunks cut at arbitrary points (columns, or
+Prophesee's packed Event2D records) and gets the frames `EventStreams` gives for the whole recording.
+
 There is no CPU path: CPU tensors raise the library's "no CPU fallback" error.
 """
 from __future__ import annotations
@@ -437,4 +440,207 @@ class EventStreams(_Windowed):
         self.last_bounds = bounds
         if check:
             _raise_on_errors(self.err)
+        return out
+
+
+_QUEUE_ERRORS = ("{} invalid events (x or y outside the sensor, or a polarity outside 0..1); they were skipped",
+                 "{} windows hold more events than window_capacity; they were left empty",
+                 "{} events were dropped: their row of the queue was full (capacity >= 2 x the row's live events right after a `frames` call + all events pushed between two `frames` calls never drops)",
+                 "{} late windows: they end before one the row already gave, and events they need were retired")
+
+
+class EventQueue(_Windowed):
+    """Device-resident event retention across chunks: push chunks of any size as they arrive, ask for windows as their ends pass.
+
+    q = EventQueue(num_streams, capacity, height, width, ..., duration_us=D | num_events=N)
+    q.push(x, y, p, t, counts, reset=None)      chunk columns [S, chunk_cap] (x, y, p: int64 / int32 / int16; t: int64 / int32),
+                                                counts int64 [S]: row s appends the first counts[s] events of chunk row s
+    q.push_dat(records, counts, reset=None)     int32 [S, chunk_cap, 2]: Prophesee's packed Event2D records as the reference's reader
+                                                takes them (EV_TYPE, utils/evaluation/prophesee/io/dat_events_tools.py:18-50):
+                                                word 0 is t, an UNSIGNED 32-bit count of microseconds; word 1 gives x = w & 16383,
+                                                y = (w >> 14) & 16383, p = (w >> 28) & 1, bits 29-31 ignored.  Decoded in the append
+                                                kernel: no unpacked copy exists.  The 32-bit clock wraps after ~71.6 minutes; it is
+                                                NOT unwrapped (the reference does not either): after a wrap the time correction holds
+                                                every timestamp at the maximum before it.
+    frames = q.frames(ends_us, out=None, check=False)    ends_us int64 [S] or [T, S] -> frames as `EventStreams` returns them
+    q.reset(streams=None); q.errors(); q.get_shape()
+
+    The frames equal, byte for byte, what `EventStreams` gives for the whole recording in one buffer.  Geometry, representations, `out`,
+    `window_capacity` (default: capacity), frame dtype and shape are `EventStreams`'.
+
+    State, all device tensors, allocated by the first ordinary call and never during capture: x, y, p int16 [S, capacity] (narrowed
+    with saturation: x = 65541 stays outside the sensor and is counted invalid, it is not drawn in column 5), t int64 [S, capacity]
+    (corrected: the running maximum from `t_last[s]`, carried on), head, count int64 [S] (row s's live events are [head[s], count[s])),
+    t_last int64 [S], retired / retired_t int64 [S] (how many events the row retired, the corrected time of the last one), err int32 [4]
+    (invalid events, windows over window_capacity, events dropped for lack of room, late windows).
+
+    push: `reset[s] != 0` (uint8 / bool [S], device) first empties row s and zeroes its carry and retirement record (`reset(streams=...)`
+    is the host-side form).  Of a chunk that does not fit, the first events that do are stored, the rest are counted in err[2]; the carry
+    advances over the stored ones only.
+    frames: windows are searched in each row's live events by `EventStreams`' rules (duration: end - D <= t <= end; count: the last N
+    events with t <= end, stopping at the row's first live event); `last_bounds` (int64 [T*S, 2]) holds flat indices into the
+    [S * capacity] storage as it was during the call, so num_streams * capacity < 2^31.  Then the row retires: it keeps its events from
+    the start of its LAST window (step T-1), everything before is gone.  A row is moved to the front of its storage only when its live
+    events fit into the freed slots in front of them (live <= head: source and destination are disjoint, the copy needs no scratch);
+    otherwise it keeps filling.  Sizing rule: capacity >= 2 x R + P never drops an event, with R the most live events a row has right
+    after a `frames` call (its last window plus whatever was already pushed beyond that window's end) and P the most events the row is
+    pushed between two `frames` calls (one chunk only if `frames` follows every push): a row that just missed the move has head = R - 1
+    slots unused in front of R live events, and fills up to 2 R - 1 + P before the next retirement.
+
+    Contract: (1) ends_us[., s] is non-decreasing over steps and over calls; (2) a window is asked for once every event with t <= end
+    has been pushed -- an event later than `end` has arrived, or the recording is over.  A window that breaks (1) after events were
+    retired is counted in err[3] (duration: the row's last retired time is >= end - D; count: the window reaches the row's first live
+    event with fewer than N events, and the row has retired events); its frame is whatever the live events give.
+
+    check=True: after the call the counters are read (this synchronises) and cleared, and ValueError names the first non-zero one.
+    Unlike `EventFrames` / `EventStreams`, which clear the counters BEFORE a checked call and so report that call alone, this reports
+    everything since the counters were last cleared: drops happen in `push`, which has no check of its own, and must not be lost.
+    After one un-captured warm-up call of each method with the same shapes nothing synchronises and nothing but `out` is allocated, so
+    push + frames (+ augmentor + backbone) can be captured in one graph and replayed on new chunks, counts, ends and reset flags written
+    into the same tensors.  Launches, whatever S, T and the chunk size are: 2 per push (partial maxima; scan + decode + append), 7 per
+    frames (1 window search, 4 frame launches, 2 retire: plan, compaction)."""
+
+    PUSH_LAUNCHES = 2
+    FRAMES_LAUNCHES = 7
+
+    def __init__(self, num_streams: int, capacity: int, height: int, width: int, bins: int = 10, count_cutoff: Optional[int] = 10,
+                 fastmode: bool = True, duration_us: Optional[int] = None, num_events: Optional[int] = None, downsample_by_2: bool = False,
+                 window_capacity: Optional[int] = None, representation: str = "stacked_histogram"):
+        super().__init__(bins, height, width, count_cutoff, fastmode, downsample_by_2, representation, duration_us, num_events, True,
+                         window_capacity)
+        if int(height) > 32767 or int(width) > 32767:
+            raise ValueError("sast_amd.events: EventQueue keeps x and y as int16: height and width must be <= 32767")
+        if int(num_streams) < 1 or int(num_streams) > 65535:
+            raise ValueError("sast_amd.events: num_streams must be in 1 .. 65535")
+        if int(capacity) < 1:
+            raise ValueError("sast_amd.events: capacity must be >= 1")
+        if int(num_streams) * int(capacity) > 2 ** 31 - 1:
+            raise ValueError("sast_amd.events: num_streams * capacity must be below 2^31")
+        self.num_streams, self.capacity = int(num_streams), int(capacity)
+        self.x = self.y = self.p = self.t = self.head = self.count = self.retired = self.retired_t = None
+        self._args = None
+
+    def _storage(self, dev):
+        """the queue's state on `dev` (allocated by the first ordinary call)"""
+        if self._args is not None and self.t.device != dev:
+            raise ValueError(f"sast_amd.events: the queue's state lives on {self.t.device}, the call's tensors on {dev}")
+        if self._args is None:
+            _not_capturing()
+            S, cap = self.num_streams, self.capacity
+            self.x, self.y, self.p = (torch.zeros(S, cap, dtype=torch.int16, device=dev) for _ in range(3))
+            self.t = torch.zeros(S, cap, dtype=torch.int64, device=dev)
+            self.head, self.count, self.t_last, self.retired, self.retired_t = (torch.zeros(S, dtype=torch.int64, device=dev) for _ in range(5))
+            self.err = torch.zeros(4, dtype=torch.int32, device=dev)
+            self._state = {"ws": torch.zeros(int(L.lib().sast_evqueue_ws_count(S)), dtype=torch.int64, device=dev), "bounds": {}}
+            a = self._args = L.SastEvQueueArgs()
+            a.x, a.y, a.p, a.t = self.x.data_ptr(), self.y.data_ptr(), self.p.data_ptr(), self.t.data_ptr()
+            a.head, a.count, a.t_last = self.head.data_ptr(), self.count.data_ptr(), self.t_last.data_ptr()
+            a.retired, a.retired_t, a.err, a.ws = self.retired.data_ptr(), self.retired_t.data_ptr(), self.err.data_ptr(), self._state["ws"].data_ptr()
+            a.capacity, a.S = cap, S
+        return self._args
+
+    def errors(self) -> Tuple[int, int, int, int]:
+        """(invalid events, windows over capacity, dropped events, late windows) since they were last cleared (synchronises)"""
+        return (0, 0, 0, 0) if self.err is None else tuple(int(v) for v in self.err.tolist())
+
+    def reset(self, streams=None):
+        """new recordings, from the host: rows `streams` (default: all of them) are emptied, their carry and retirement record zeroed;
+        with streams=None the error counters are cleared as well"""
+        if self._args is None:
+            return
+        state = (self.head, self.count, self.t_last, self.retired, self.retired_t)
+        if streams is None:
+            for v in state:
+                v.zero_()
+            self.err.zero_()
+            return
+        idx = [int(s) for s in streams]
+        if any(s < 0 or s >= self.num_streams for s in idx):
+            raise ValueError(f"sast_amd.events: streams must be in 0 .. {self.num_streams - 1}")
+        if idx:
+            sel = torch.tensor(idx, dtype=torch.int64, device=self.head.device)
+            for v in state:
+                v[sel] = 0
+
+    def _counts_reset(self, counts, reset):
+        S = self.num_streams
+        if counts.dtype != torch.int64 or tuple(counts.shape) != (S,) or not counts.is_contiguous():
+            raise ValueError(f"sast_amd.events: counts must be a contiguous int64 tensor of shape [{S}]")
+        if reset is not None and (reset.dtype not in (torch.uint8, torch.bool) or tuple(reset.shape) != (S,) or not reset.is_contiguous()):
+            raise ValueError(f"sast_amd.events: reset must be a contiguous uint8 or bool tensor of shape [{S}]")
+
+    def _push(self, ptrs, codes, chunk_cap, counts, reset, tensors):
+        _need_gpu(*tensors, counts, reset)
+        if len({c.device for c in tensors + [counts] + ([reset] if reset is not None else [])}) != 1:
+            raise ValueError("sast_amd.events: the chunk, counts and reset must be on the same device")
+        if self.num_streams * chunk_cap > 2 ** 31 - 1:
+            raise ValueError("sast_amd.events: num_streams * chunk capacity must be below 2^31")
+        a = self._storage(counts.device)
+        # an empty chunk has no storage: any valid device pointer will do, the kernels read no event
+        ptrs = [v or self.t.data_ptr() for v in ptrs]
+        L.check(L.lib().sast_evqueue_push(C.byref(a), *ptrs, *codes, counts.data_ptr(), chunk_cap, None if reset is None else reset.data_ptr(),
+                                          _stream()), "evqueue_push")
+
+    def push(self, x: torch.Tensor, y: torch.Tensor, p: torch.Tensor, t: torch.Tensor, counts: torch.Tensor,
+             reset: Optional[torch.Tensor] = None) -> None:
+        S = self.num_streams
+        cols = [x, y, p, t]
+        for c, name in zip(cols, ("x", "y", "p", "t")):
+            if c.dim() != 2 or c.shape[0] != S:
+                raise ValueError(f"sast_amd.events: {name} must be [num_streams={S}, chunk capacity], got shape {tuple(c.shape)}")
+            if not c.is_contiguous():
+                raise ValueError(f"sast_amd.events: {name} must be contiguous")
+        if not x.shape == y.shape == p.shape == t.shape:
+            raise ValueError("sast_amd.events: x, y, p and t must have the same shape")
+        codes = [_dtype_code(x, "x"), _dtype_code(y, "y"), _dtype_code(p, "p"), _dtype_code(t, "t", (torch.int64, torch.int32))]
+        self._counts_reset(counts, reset)
+        self._push([c.data_ptr() for c in cols], codes, x.shape[1], counts, reset, cols)
+
+    def push_dat(self, records: torch.Tensor, counts: torch.Tensor, reset: Optional[torch.Tensor] = None) -> None:
+        S = self.num_streams
+        if records.dim() != 3 or records.shape[0] != S or records.shape[2] != 2:
+            raise ValueError(f"sast_amd.events: records must be [num_streams={S}, chunk capacity, 2], got shape {tuple(records.shape)}")
+        if records.dtype != torch.int32:
+            raise TypeError(f"sast_amd.events: records must be torch.int32 (two words per Event2D record), got {records.dtype}")
+        if not records.is_contiguous():
+            raise ValueError("sast_amd.events: records must be contiguous")
+        self._counts_reset(counts, reset)
+        self._push([records.data_ptr()] * 4, [L.EVQUEUE_DT_DAT] * 4, records.shape[1], counts, reset, [records])
+
+    def frames(self, ends_us: torch.Tensor, out: Optional[torch.Tensor] = None, check: bool = False) -> torch.Tensor:
+        S, cap = self.num_streams, self.capacity
+        if ends_us.dtype != torch.int64 or ends_us.dim() not in (1, 2) or ends_us.shape[-1] != S or ends_us.numel() < 1 \
+                or not ends_us.is_contiguous():
+            raise ValueError(f"sast_amd.events: ends_us must be a contiguous int64 tensor of shape [{S}] or [T, {S}], T >= 1")
+        T = ends_us.shape[0] if ends_us.dim() == 2 else 1
+        B = T * S
+        wcap = self.window_capacity if self.window_capacity is not None else cap
+        self.ws_bytes(B, wcap)                  # ValueError for more windows than the frame kernels take
+        _need_gpu(ends_us, out)
+        dev = ends_us.device
+        shape = tuple(ends_us.shape) + self.get_shape()
+        if out is None:
+            out = torch.empty(shape, dtype=self.frame_dtype, device=dev)
+        elif out.dtype != self.frame_dtype or tuple(out.shape) != tuple(shape) or not out.is_contiguous() or out.device != dev:
+            raise ValueError(f"sast_amd.events: out must be a contiguous {str(self.frame_dtype).replace('torch.', '')} tensor of shape "
+                             f"{tuple(shape)} on the queue's device")
+        a = self._storage(dev)
+        st = self._state
+        if B not in st["bounds"]:
+            _not_capturing("one un-captured warm-up call with the same number of windows is needed before graph capture")
+            st["bounds"][B] = torch.empty(B, 2, dtype=torch.int64, device=dev)
+        bounds = st["bounds"][B]
+        lib = L.lib()
+        L.check(lib.sast_evqueue_window_bounds(C.byref(a), ends_us.data_ptr(), T, self.mode, self.value, bounds.data_ptr(), _stream()),
+                "evqueue_window_bounds")
+        self.launch([self.x, self.y, self.p, self.t], [L.DT_I16, L.DT_I16, L.DT_I16, L.DT_I64], S * cap, bounds, out, self.err, wcap,
+                    clip_negative_polarity=True)
+        L.check(lib.sast_evqueue_retire(C.byref(a), bounds.data_ptr(), T, _stream()), "evqueue_retire")
+        self.last_bounds = bounds
+        if check:
+            err = self.errors()
+            self.err.zero_()
+            for n, msg in zip(err, _QUEUE_ERRORS):
+                if n:
+                    raise ValueError("sast_amd.events: " + msg.format(n))
         return out
