@@ -591,6 +591,72 @@ int sast_evqueue_window_bounds(const SastEvQueueArgs* q, const int64_t* ends_us,
  * 2 launches (one thread per row decides and writes the plan; the copy reads only the plan). */
 int sast_evqueue_retire(const SastEvQueueArgs* q, const int64_t* bounds, int T, sast_stream_t stream);
 
+/* ---- label front end (csrc/k_labels.hip): the raw Prophesee box records of S recordings side by side -> the filtered labels, the
+ * label-frame timestamps, the window-end schedule, the frame -> window map and per-step label tensors, all on the device.  The reference
+ * does this offline, per recording: apply_filters, get_base_delta_ts_for_labels_us and labels_and_ev_repr_timestamps of
+ * scripts/genx/preprocess_dataset.py:191-428, then ObjectLabelFactory (data/genx_utils/labels.py:149-198).  Every integer equals the
+ * reference's, every fp32 value bit for bit.
+ * records: int32 [S, capacity, 10], the 40-byte BBOX_DTYPE record of utils/evaluation/prophesee/io/box_loading.py:19-21 as ten
+ * little-endian words: 0-1 t (int64, us), 2-5 the bits of fp32 x, y, w, h, 6 class_id (u32), 7 track_id (ignored), 8 class_confidence
+ * (fp32), 9 padding.  counts: int64 [S], the records at the head of each row, sorted by t; clamped to [0, capacity] on the device.
+ * status bits of a row (SastLabelArgs.status, set by sast_labels_load; a row with any bit but FRAME_OVERFULL / WINDOW_INDEX has
+ * n_frames = n_windows = 0): */
+enum {
+  SAST_LABELS_UNSORTED = 1,            /* a record's t is smaller than its predecessor's */
+  SAST_LABELS_NEGATIVE_SIZE = 2,       /* a record with w < 0 or h < 0 (the reference asserts) */
+  SAST_LABELS_NO_LABELS = 4,           /* no record survives the filters (NoLabelsException), or the row is empty */
+  SAST_LABELS_BAD_RATE = 8,            /* base_delta_us == 0: fewer than two unique timestamps, or a label rate that is not 30 / 60 Hz */
+  SAST_LABELS_NO_ALIGNED_LABEL = 16,   /* no label at or after align_t_us */
+  SAST_LABELS_ZERO_COUNT = 32,         /* a timestamp within 2 ms of the last label frame (the reference asserts) */
+  SAST_LABELS_TOO_MANY_FRAMES = 64,    /* more than max_frames label frames */
+  SAST_LABELS_TOO_MANY_WINDOWS = 128,  /* more than max_windows window ends */
+  SAST_LABELS_FRAME_OVERFULL = 256,    /* a label frame with more than max_labels_per_frame boxes: cut to its first ones */
+  SAST_LABELS_FRAMES_TOO_CLOSE = 512,  /* two label frames <= 98 000 us apart (the reference asserts) */
+  SAST_LABELS_WINDOW_INDEX = 1024      /* sast_labels_gather was given a window index outside [0, n_windows) */
+};
+typedef struct SastLabelArgs {
+  void* ws;                  /* sast_labels_ws_bytes(S, capacity, max_frames) bytes, 8-byte aligned; no initial contents needed */
+  int64_t* ends_us;          /* [S, max_windows] window ends */
+  int32_t* n_windows;        /* [S] */
+  int64_t* frame_ts_us;      /* [S, max_frames] label-frame timestamps */
+  int32_t* n_frames;         /* [S] */
+  int64_t* frame_2_window;   /* [S, max_frames] searchsorted(ends_us, frame_ts_us, 'left') */
+  int32_t* window_2_frame;   /* [S, max_windows] its inverse; -1: not a label frame */
+  float* labels;             /* [S, capacity, 7] (t, x, y, w, h, class_id, class_confidence) of the label frames' boxes, in frame order */
+  int32_t* frame_start;      /* [S, max_frames] first row of a frame in `labels` */
+  int32_t* frame_count;      /* [S, max_frames] its rows (<= max_labels_per_frame) */
+  int32_t* status;           /* [S] */
+  int64_t capacity;          /* records one row holds; S * capacity <= (2^31 - 1) / 16 */
+  int64_t base_delta_us;     /* the label period: 250 000 (gen1), or 0 for gen4's rule -- np.median of the differences of the unique
+                                timestamps in fp64, hz = rint(1e6 / median) in {30, 60}, int(6 * median) or int(3 * median) */
+  int64_t align_t_us;        /* the first label frame is the first unique timestamp >= this */
+  int64_t delta_t_us;        /* ts_step_ev_repr_ms * 1000: the step of the windows before the first label frame */
+  int32_t S;                 /* 1 .. 65535 */
+  int32_t width, height;     /* the sensor: 304 x 240 (gen1), 1280 x 720 (gen4) */
+  int32_t class_max;         /* keep class_id <= class_max (gen4: 2); < 0: no class filter */
+  float min_diag2;           /* > 0: keep w * w + h * h >= min_diag2 (prophesee_bbox_filter); 0: no diagonal rule */
+  float min_side;            /* keep w >= min_side and h >= min_side (10 / 20, or conservative_bbox_filter's 5) */
+  float max_width;           /* >= 0: keep w <= max_width (remove_faulty_huge_bbox_filter, train split); < 0: off */
+  int32_t reprs_per_frame;   /* 100 / ts_step_ev_repr_ms: windows per 100 ms */
+  int32_t downsample_by_2;   /* ObjectLabels.scale_(0.5) and its removal of flat boxes */
+  int32_t max_frames, max_windows, max_labels_per_frame;
+  int32_t reserved;
+} SastLabelArgs;
+/* bytes of SastLabelArgs.ws; 0: an argument out of range.  Host only. */
+size_t sast_labels_ws_bytes(int S, int64_t capacity, int max_frames);
+/* once per recording and row: row s with reset == NULL or reset[s] != 0 is rebuilt from records row s, any other row is left as it
+ * is.  Filters (stable), unique timestamps, base delta, the sequential acceptance of label frames (count = rint(diff / base) in fp64,
+ * |diff - count * base| <= 2000), window ends (the lead-in f0 - k * delta_t_us, then numpy's linspace per pair of label frames in fp64
+ * truncated to int64), frame_2_window and its inverse, and the labels of the accepted frames through clamp_to_frame_ (and scale_).
+ * 1 launch, one 1024-thread workgroup per row; the grid depends on S alone, every count is read on the device. */
+int sast_labels_load(const SastLabelArgs* a, const int32_t* records, const int64_t* counts, const uint8_t* reset, sast_stream_t stream);
+/* window_idx int64 [T, S] -> labels fp32 [T, S, max_labels_per_frame, 7] (a frame's rows at the front, zeros behind), counts int32
+ * [T, S], ends_us int64 [T, S], labelled uint8 [T, S] (1: the window is a label frame, even when all its boxes vanished in the
+ * downscale).  An index outside [0, n_windows[s]): counts 0, ends_us -1, labelled 0, and SAST_LABELS_WINDOW_INDEX in status[s].
+ * 1 launch. */
+int sast_labels_gather(const SastLabelArgs* a, const int64_t* window_idx, int T, float* labels, int32_t* counts, int64_t* ends_us,
+                       uint8_t* labelled, sast_stream_t stream);
+
 /* ---- spatial augmentation of event frames and box labels (csrc/k_augment.hip).  The reference augments on the CPU in its data-loader
  * workers: RandomSpatialAugmentorGenX.__call__ (data/utils/augmentor.py:347-364) -- horizontal flip, then zoom-in (:203-222) or zoom-out
  * (:134-153) -- with the label transforms of ObjectLabels (data/genx_utils/labels.py:255-339).  Both calls read the per-sample

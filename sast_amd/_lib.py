@@ -26,6 +26,9 @@ AUGMENT_PARAM_WORDS = 16  # SAST_AUGMENT_PARAM_WORDS
 AUGMENT_NONE, AUGMENT_ZOOM_IN, AUGMENT_ZOOM_OUT = 0, 1, 2
 EVAL_STATE_WORDS, EVAL_MAX_CLASSES = 32, 4   # SAST_EVAL_STATE_WORDS, SAST_EVAL_MAX_CLASSES
 EVAL_IOU_THRS, EVAL_REC_THRS, EVAL_AREAS = 10, 101, 4
+# SAST_LABELS_*: the status bits of a LabelStreams row
+(LABELS_UNSORTED, LABELS_NEGATIVE_SIZE, LABELS_NO_LABELS, LABELS_BAD_RATE, LABELS_NO_ALIGNED_LABEL, LABELS_ZERO_COUNT, LABELS_TOO_MANY_FRAMES,
+ LABELS_TOO_MANY_WINDOWS, LABELS_FRAME_OVERFULL, LABELS_FRAMES_TOO_CLOSE, LABELS_WINDOW_INDEX) = (1 << k for k in range(11))
 
 
 def _struct(name, spec):
@@ -90,6 +93,11 @@ SastMdStackArgs = _struct("SastMdStackArgs", [
 ])
 SastEvQueueArgs = _struct("SastEvQueueArgs", [
     (P, "x y p t head count t_last retired retired_t err ws"), (C.c_int64, "capacity"), (I32, "S reserved"),
+])
+SastLabelArgs = _struct("SastLabelArgs", [
+    (P, "ws ends_us n_windows frame_ts_us n_frames frame_2_window window_2_frame labels frame_start frame_count status"),
+    (C.c_int64, "capacity base_delta_us align_t_us delta_t_us"), (I32, "S width height class_max"), (F32, "min_diag2 min_side max_width"),
+    (I32, "reprs_per_frame downsample_by_2 max_frames max_windows max_labels_per_frame reserved"),
 ])
 SastEvalArgs = _struct("SastEvalArgs", [
     (P, "labels counts det n_det"), (I32, "N M A K"), (F32, "min_diag2 min_side"), (I32, "max_images max_labels_per_frame"),
@@ -177,6 +185,9 @@ _SIGNATURES = {
     "sast_evqueue_push": (C.c_int, [C.POINTER(SastEvQueueArgs), P, P, P, P, C.c_int, C.c_int, C.c_int, C.c_int, P, C.c_int64, P, P]),
     "sast_evqueue_window_bounds": (C.c_int, [C.POINTER(SastEvQueueArgs), P, C.c_int, C.c_int, C.c_int64, P, P]),
     "sast_evqueue_retire": (C.c_int, [C.POINTER(SastEvQueueArgs), P, C.c_int, P]),
+    "sast_labels_ws_bytes": (C.c_size_t, [C.c_int, C.c_int64, C.c_int]),
+    "sast_labels_load": (C.c_int, [C.POINTER(SastLabelArgs), P, P, P, P]),
+    "sast_labels_gather": (C.c_int, [C.POINTER(SastLabelArgs), P, C.c_int, P, P, P, P, P]),
     "sast_augment_frames": (C.c_int, [P, P, P] + [C.c_int] * 5 + [P]),
     "sast_augment_labels": (C.c_int, [P, P, P] + [C.c_int] * 4 + [P, P, P, P]),
     "sast_eval_reset": (C.c_int, [C.POINTER(SastEvalArgs), P]),

@@ -87,4 +87,6 @@ int mswsa_fused_fwd_launch(const SastMswsaArgs* a, const float* planes, hipStrea
 
 // k_eval.hip: the Prophesee mAP evaluator has no internal launchers, only the sast_eval_* entry points of include/sast_hip.h
 
+// k_labels.hip: the label front end has no internal launchers either, only the sast_labels_* entry points
+
 }  // namespace sast
