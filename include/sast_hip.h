@@ -407,6 +407,49 @@ int sast_gather_samples_bwd(const SastSampleGather* a, sast_stream_t stream);
 typedef struct { uint8_t sel[256]; } SastSampleMask;
 int sast_zero_samples(float* x, int B, size_t sample_floats, const SastSampleMask* sel, sast_stream_t stream);
 
+/* (f)2 on the device: the same selection with the table and the reset flags in DEVICE memory, so that a captured training step is
+ * replayed on a new label pattern and new sequence starts (the host-table structs above travel by value: one pattern per graph).
+ * sast_select_table turns labelled [T, B] (uint8, != 0: the pair carries a label frame, modules/detection.py:161-171) into the list of
+ * selected pairs in the reference's order (timestep-major, batch index ascending), one workgroup, nothing read from the host:
+ *   table[j] = (t, b) for j < min(n_sel, n_out), (-1, -1) behind that;  slot_of[t * B + b] = j, or -1 (not selected, or j >= n_out)
+ *   *n_sel = the number of flagged pairs;  err[0] += 1 when n_sel > n_out (pattern truncated), err[1] += 1 when n_sel < n_out (under-full)
+ * T <= 32, B <= 256, n_out <= 256 (n_out = K, the batch of the PAFPN / head pass, is the host's: BatchNorm statistics over exactly K rows). */
+int sast_select_table(const uint8_t* labelled, int T, int B, int n_out, int32_t* table, int32_t* slot_of, int32_t* n_sel, int32_t* err,
+                      sast_stream_t stream);
+typedef struct {
+  int32_t n_src, n_out, B, _pad;
+  size_t sample_floats;                  /* any count >= 1: 16-byte accesses where both rows are 16-byte aligned, a scalar tail */
+  const float* src[SAST_GATHER_MAX_SRC]; /* forward: the timestep tensors */
+  float* dsrc[SAST_GATHER_MAX_SRC];      /* backward: their gradients (all written) */
+  float* out;                            /* forward: [n_out, sample_floats]; backward: the gradient of it (read) */
+  const int32_t* table;                  /* device, [n_out][2] = (t, b) or (-1, -1): forward */
+  const int32_t* slot_of;                /* device, [n_src * B]: backward */
+} SastSampleGatherDev;
+/* forward: out row j = src[table[j].t] sample table[j].b; a row whose entry is negative (or names no sample of the call) is written as zeros.
+ * backward: EVERY sample of every dsrc[t] is written -- row slot_of[t * B + b] of `out`, or zeros (slot < 0 or >= n_out).  The words are
+ * moved as bit patterns: the same entry points carry feature maps, label rows and int32 counts. */
+int sast_gather_samples_dev(const SastSampleGatherDev* a, sast_stream_t stream);
+int sast_gather_samples_dev_bwd(const SastSampleGatherDev* a, sast_stream_t stream);
+/* RNNStates.reset with the flags on the device: sample b of each of the n tensors (x[i]: [B, sample_floats[i]]) is zeroed where
+ * flags[b] != 0, in ONE launch (the eight ConvLSTM state tensors of a four-stage backbone go in one call) */
+#define SAST_ZERO_MAX_TENSORS 16
+typedef struct {
+  int32_t n, B;
+  float* x[SAST_ZERO_MAX_TENSORS];
+  size_t sample_floats[SAST_ZERO_MAX_TENSORS];
+  const uint8_t* flags;                  /* device, [B] */
+} SastSampleZeroDev;
+int sast_zero_samples_dev(const SastSampleZeroDev* a, sast_stream_t stream);
+/* dst[i][0 .. floats[i]) = src[i][...] for n <= 16 tensors in ONE launch, a kernel (no memcpy node when captured): the training step
+ * hands the final recurrent states back into its input state tensors with it (RNNStates.save_states_and_detach for a replayed step) */
+typedef struct {
+  int32_t n, _pad;
+  float* dst[SAST_ZERO_MAX_TENSORS];
+  const float* src[SAST_ZERO_MAX_TENSORS];
+  size_t floats[SAST_ZERO_MAX_TENSORS];
+} SastTensorCopy;
+int sast_copy_tensors(const SastTensorCopy* a, sast_stream_t stream);
+
 /* fused AdamW over a flat parameter buffer (torch.optim.AdamW semantics, modules/detection.py:409-441).  The betas are doubles and
  * the bias corrections 1 - beta^step are evaluated in double, as torch does with its python scalars.  Every element is updated:
  * a parameter that received no gradient counts as gradient 0 (torch skips grad=None parameters; identical when every parameter is

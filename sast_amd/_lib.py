@@ -83,6 +83,12 @@ SastSampleGather = _struct("SastSampleGather", [
     (C.c_uint8 * 256, "t_of"), (C.c_uint8 * 256, "b_of"),
 ])
 SastSampleMask = _struct("SastSampleMask", [(C.c_uint8 * 256, "sel")])
+SastSampleGatherDev = _struct("SastSampleGatherDev", [
+    (I32, "n_src n_out B _pad"), (C.c_size_t, "sample_floats"), (P * 32, "src"), (P * 32, "dsrc"), (P, "out table slot_of"),
+])
+ZERO_MAX_TENSORS = 16     # SAST_ZERO_MAX_TENSORS
+SastSampleZeroDev = _struct("SastSampleZeroDev", [(I32, "n B"), (P * 16, "x"), (C.c_size_t * 16, "sample_floats"), (P, "flags")])
+SastTensorCopy = _struct("SastTensorCopy", [(I32, "n _pad"), (P * 16, "dst"), (P * 16, "src"), (C.c_size_t * 16, "floats")])
 SastEventArgs = _struct("SastEventArgs", [
     (P, "x y p t bounds out err ws"), (C.c_int64, "capacity window_capacity"),
     (I32, "x_dtype y_dtype p_dtype t_dtype B bins height width count_cutoff fastmode downsample_by_2 clip_negative_polarity"),
@@ -157,6 +163,11 @@ _SIGNATURES = {
     "sast_gather_samples": (C.c_int, [C.POINTER(SastSampleGather), P]),
     "sast_gather_samples_bwd": (C.c_int, [C.POINTER(SastSampleGather), P]),
     "sast_zero_samples": (C.c_int, [P, C.c_int, C.c_size_t, C.POINTER(SastSampleMask), P]),
+    "sast_select_table": (C.c_int, [P, C.c_int, C.c_int, C.c_int, P, P, P, P, P]),
+    "sast_gather_samples_dev": (C.c_int, [C.POINTER(SastSampleGatherDev), P]),
+    "sast_gather_samples_dev_bwd": (C.c_int, [C.POINTER(SastSampleGatherDev), P]),
+    "sast_zero_samples_dev": (C.c_int, [C.POINTER(SastSampleZeroDev), P]),
+    "sast_copy_tensors": (C.c_int, [C.POINTER(SastTensorCopy), P]),
     "sast_adamw_onecycle": (C.c_int, [P, P, P, P, C.c_size_t, P, C.c_double, C.c_double, F32, F32, F32, F32, C.c_double, C.c_double, C.c_double,
                                       C.c_double, C.c_double, P]),
     "sast_dw_defer": (C.c_int, [C.c_int]),

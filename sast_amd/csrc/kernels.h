@@ -54,6 +54,11 @@ int cb_apply_bwd_launch(const float* dout, const float* gsum, const int* row_tok
 
 int sample_gather_launch(const SastSampleGather& a, bool backward, hipStream_t st);
 int zero_samples_launch(float* x, int B, size_t sample_floats, const SastSampleMask& m, hipStream_t st);
+int select_table_launch(const uint8_t* labelled, int T, int B, int n_out, int32_t* table, int32_t* slot_of, int32_t* n_sel, int32_t* err,
+                        hipStream_t st);
+int sample_gather_dev_launch(const SastSampleGatherDev& a, bool backward, hipStream_t st);
+int zero_samples_dev_launch(const SastSampleZeroDev& a, hipStream_t st);
+int copy_tensors_launch(const SastTensorCopy& a, hipStream_t st);
 
 // k_select.hip
 int select_launch(const float* tok, int B, int H, int W, int ph, int pw, int mode, float thr_win, float thr_tok, const SastSel* s,

@@ -4,7 +4,7 @@ from .network_blocks import BaseConv, Bottleneck, CSPLayer, DWConv, convert_sync
 from .yolo_head import YOLOXHead  # noqa: F401
 from .detector import YoloXDetector  # noqa: F401
 from ..functional import postprocess  # noqa: F401  (models/detection/yolox/utils/boxes.py:32-76)
-from .sequence import BackboneFeatureSelector, RNNStates  # noqa: F401
+from .sequence import BackboneFeatureSelector, DeviceFeatureSelector, RNNStates  # noqa: F401
 
 
 def build_recurrent_backbone(backbone_cfg):

@@ -6,6 +6,10 @@ Same class and method names as the reference.  The data movement runs in libsast
 of all timesteps is ONE launch per feature map (`sast_gather_samples`, backward `sast_gather_samples_bwd`), the per-sample
 state reset is `sast_zero_samples`.  Feature maps may be logical NCHW tensors in channels-last memory (what the modules of
 this package return) or NHWC buffers; a sample is a contiguous chunk either way.
+
+`DeviceFeatureSelector` and `RNNStates.reset_on_device` are the same two operations with the selection in DEVICE memory
+(`functional.SelectionTable`, a flags tensor): nothing of the label pattern or of the sequence starts is a kernel argument, so a
+captured training step follows them from replay to replay (`sast_gather_samples_dev`, `sast_zero_samples_dev`).
 """
 from __future__ import annotations
 
@@ -45,6 +49,32 @@ class BackboneFeatureSelector:
             else:
                 out[k] = SF.gather_samples(xs, idx)
         return out
+
+
+class DeviceFeatureSelector:
+    """BackboneFeatureSelector with the selection in device memory (`SF.SelectionTable`): the feature maps of EVERY timestep are added,
+    in order, and the labelled (timestep, sample) pairs are read from the table when the gather kernel runs -- one launch per feature
+    map, and a captured step follows the label pattern of each replay.  The batch of the result is the table's n_out."""
+
+    def __init__(self, sel: "SF.SelectionTable"):
+        self.sel = sel
+        self.features = None
+        self.reset()
+
+    def reset(self):
+        self.features: Dict[int, List[torch.Tensor]] = dict()
+
+    def add_backbone_features(self, backbone_features: Dict[int, torch.Tensor]) -> None:
+        for k, v in backbone_features.items():
+            self.features.setdefault(k, []).append(v)
+
+    def get_batched_backbone_features(self) -> Optional[Dict[int, torch.Tensor]]:
+        if len(self.features) == 0:
+            return None
+        for k, xs in self.features.items():
+            if len(xs) != self.sel.T:
+                raise RuntimeError(f"sast_amd: DeviceFeatureSelector holds {len(xs)} timesteps of feature map {k}, the selection table is for {self.sel.T}")
+        return {k: SF.gather_samples_dev(xs, self.sel) for k, xs in self.features.items()}
 
 
 def _map_leaves(tree, fn):
@@ -95,3 +125,19 @@ class RNNStates:
         held = self.states.get(worker_id)
         if held is not None:
             self.states[worker_id] = self.recursive_reset(held, indices_or_bool_tensor)
+
+    def reset_on_device(self, worker_id: int, flags: torch.Tensor) -> None:
+        """`reset` with the selection as a device tensor (uint8 / bool [B], != 0: the sample starts a new sequence): every held state
+        tensor in ONE launch (`sast_zero_samples_dev`), no copy of the flags to the host -- capturable, and a replay follows its flags"""
+        held = self.states.get(worker_id)
+        if held is None:
+            return
+        leaves = []
+
+        def collect(t: torch.Tensor) -> torch.Tensor:
+            if t.requires_grad:
+                raise AssertionError("RNNStates.reset_on_device: saved states are detached; got a tensor that requires grad")
+            leaves.append(t)
+            return t
+        _map_leaves(held, collect)
+        SF.zero_samples_dev(leaves, flags)

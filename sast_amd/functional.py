@@ -20,7 +20,7 @@ from __future__ import annotations
 import collections
 import ctypes as C
 import os
-from typing import Optional, Tuple
+from typing import Dict, Optional, Tuple
 
 import torch
 
@@ -1726,6 +1726,197 @@ def zero_samples(x: torch.Tensor, indices_or_bool=None) -> torch.Tensor:
         m.sel[b] = 1
     L.check(L.lib().sast_zero_samples(x.data_ptr(), B, x[0].numel(), C.byref(m), _stream()), "zero_samples")
     return x
+
+
+# ---------------------------------------------------------------------------------------------- (f)2 with the selection on the device
+class SelectionTable:
+    """sel = SelectionTable(T, B, n_out, device);  sel.update(labelled)
+
+    The label-sparse selection of a sequence step (modules/detection.py:161-177) as DEVICE data: `update` turns labelled [T, B] (uint8 /
+    bool, what `LabelStreams.labels` returns) into
+      table   int32 [n_out, 2]  the selected (timestep, sample) pairs, timestep-major then batch index ascending (the order of
+                                BackboneFeatureSelector / get_valid_labels_and_batch_indices), (-1, -1) behind the first n_sel
+      slot_of int32 [T, B]      the row of the pair in `table`, -1 for a pair that is not selected or does not fit
+      n_sel   int32 [1]         the number of flagged pairs
+      err     int32 [2]         counters: [0] updates whose pattern had more than n_out pairs (truncated), [1] fewer (under-full)
+    in ONE launch (`sast_select_table`) that reads nothing from the host.  Everything is allocated here, so `update` can be captured in a
+    graph; `gather_samples_dev`, `select_labels` and `DeviceFeatureSelector` read the tables when they RUN, so a replay follows the
+    pattern of the replay.  n_out = K stays the host's: it is the batch of the PAFPN / head pass (their BatchNorm statistics are taken
+    over exactly the selected samples).  T <= 32, B <= 256, n_out <= 256, as on the host-table path."""
+
+    LAUNCHES = 1
+
+    def __init__(self, T: int, B: int, n_out: int, device):
+        T, B, n_out = int(T), int(B), int(n_out)
+        if not (1 <= T <= 32 and 1 <= B <= 256 and 0 <= n_out <= 256):
+            raise ValueError("sast_amd: SelectionTable supports 1 <= T <= 32 timesteps, 1 <= B <= 256 samples and 0 <= n_out <= 256 selected pairs")
+        device = torch.device(device)
+        self.T, self.B, self.n_out, self.device = T, B, n_out, device
+        i32 = dict(dtype=torch.int32, device=device)
+        self.table, self.slot_of = torch.full((n_out, 2), -1, **i32), torch.full((T, B), -1, **i32)
+        self.n_sel, self.err = torch.zeros(1, **i32), torch.zeros(2, **i32)
+
+    def update(self, labelled: torch.Tensor, check: bool = False) -> "SelectionTable":
+        """check=True synchronises and raises ValueError when the pattern has more (truncated) or fewer (under-full) pairs than n_out"""
+        if not torch.is_tensor(labelled) or labelled.dtype not in (torch.uint8, torch.bool):
+            raise TypeError(f"sast_amd: SelectionTable.update needs a uint8 or bool tensor, got {getattr(labelled, 'dtype', type(labelled).__name__)}")
+        if tuple(labelled.shape) != (self.T, self.B) or not labelled.is_contiguous():
+            raise ValueError(f"sast_amd: SelectionTable.update needs a contiguous tensor of shape [{self.T}, {self.B}], got {tuple(labelled.shape)}")
+        _need_gpu(labelled)
+        if labelled.device != self.device:
+            raise ValueError(f"sast_amd: the selection table lives on {self.device}, labelled on {labelled.device}")
+        L.check(L.lib().sast_select_table(labelled.data_ptr(), self.T, self.B, self.n_out, _ptr(self.table) if self.n_out else None, self.slot_of.data_ptr(),
+                                          self.n_sel.data_ptr(), self.err.data_ptr(), _stream()), "select_table")
+        if check:
+            n = int(self.n_sel)
+            if n > self.n_out:
+                raise ValueError(f"sast_amd: selection truncated: the pattern has {n} labelled (timestep, sample) pairs, the table holds n_out = {self.n_out}")
+            if n < self.n_out:
+                raise ValueError(f"sast_amd: selection under-full: the pattern has {n} labelled (timestep, sample) pairs, the table expects n_out = {self.n_out}")
+        return self
+
+    def errors(self) -> Dict[str, int]:
+        """{'truncated': updates with n_sel > n_out, 'under_full': updates with n_sel < n_out} since construction (synchronises)"""
+        t, u = self.err.tolist()
+        return {"truncated": int(t), "under_full": int(u)}
+
+
+def _gather_dev_args(sel: SelectionTable, n_src: int, B: int, sample: int):
+    if n_src != sel.T or B != sel.B:
+        raise RuntimeError(f"sast_amd: the selection table is for {sel.T} timesteps of {sel.B} samples, got {n_src} timesteps of {B}")
+    a = L.SastSampleGatherDev()
+    a.n_src, a.n_out, a.B, a.sample_floats = n_src, sel.n_out, B, sample
+    a.table, a.slot_of = _ptr(sel.table) if sel.n_out else None, sel.slot_of.data_ptr()
+    return a
+
+
+class _GatherSamplesDev(torch.autograd.Function):
+    """_GatherSamples with the (timestep, sample) table read from device memory when the kernels run"""
+
+    @staticmethod
+    def forward(ctx, sel, *xs):
+        _need_gpu(*xs)
+        xs = tuple(x.contiguous() for x in xs)
+        if any(x.shape != xs[0].shape or x.dtype != torch.float32 for x in xs) or xs[0].dim() < 2:
+            raise RuntimeError("sast_amd: gather_samples_dev needs fp32 tensors of one shape (one feature map over the timesteps)")
+        if len(xs) > 32 or xs[0].shape[0] > 256 or xs[0][0].numel() < 1:
+            raise RuntimeError("sast_amd: gather_samples_dev supports <= 32 timesteps, <= 256 selected samples, batch <= 256")
+        if any(x.device != sel.device for x in xs):
+            raise RuntimeError(f"sast_amd: the selection table lives on {sel.device}, the feature maps on {xs[0].device}")
+        B, sample = xs[0].shape[0], xs[0][0].numel()
+        a = _gather_dev_args(sel, len(xs), B, sample)
+        out = torch.empty((sel.n_out,) + tuple(xs[0].shape[1:]), device=xs[0].device)
+        a.out = _ptr(out) if sel.n_out else None
+        for t, x in enumerate(xs):
+            a.src[t] = x.data_ptr()
+        L.check(L.lib().sast_gather_samples_dev(C.byref(a), _stream()), "gather_samples_dev")
+        ctx.sel, ctx.meta = sel, (len(xs), B, sample, tuple(xs[0].shape))
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        n_src, B, sample, shape = ctx.meta
+        dout = dout.contiguous()
+        dxs = tuple(torch.empty(shape, device=dout.device) for _ in range(n_src))
+        a = _gather_dev_args(ctx.sel, n_src, B, sample)
+        a.out = _ptr(dout) if ctx.sel.n_out else None
+        for t, d in enumerate(dxs):
+            a.dsrc[t] = d.data_ptr()
+        L.check(L.lib().sast_gather_samples_dev_bwd(C.byref(a), _stream()), "gather_samples_dev_bwd")
+        return (None,) + dxs
+
+
+def gather_samples_dev(xs, sel: SelectionTable) -> torch.Tensor:
+    """gather_samples with the pairs of `sel` (a SelectionTable updated for these T = len(xs) timesteps): (sel.n_out, ...), row j =
+    xs[table[j].t][table[j].b], rows behind n_sel zero; the backward writes the gradient of every sample of every timestep (unselected:
+    zeros).  One launch each way.  Logical NCHW tensors over channels-last storage come back as the same kind of view."""
+    if not isinstance(sel, SelectionTable):
+        raise TypeError(f"sast_amd: gather_samples_dev needs a SelectionTable, got {type(sel).__name__}")
+    xs = list(xs)
+    x0 = xs[0]
+    if x0.dim() == 4 and not x0.is_contiguous() and x0.permute(0, 2, 3, 1).is_contiguous():
+        return as_nchw_view(_GatherSamplesDev.apply(sel, *[as_nhwc(x) for x in xs]))
+    return _GatherSamplesDev.apply(sel, *xs)
+
+
+@torch.no_grad()
+def select_labels(labels: torch.Tensor, counts: Optional[torch.Tensor], sel: SelectionTable):
+    """the label tensors of the selected pairs, through the gather kernel (no gradient): labels fp32 [T, B, M, C] -> [K, M, C] and
+    counts int32 [T, B] -> [K] (None stays None), K = sel.n_out, in the table's order.  One launch per tensor."""
+    todo = [(labels, torch.float32, 4, "labels")] + ([(counts, torch.int32, 2, "counts")] if counts is not None else [])
+    for x, dt, nd, name in todo:
+        if not torch.is_tensor(x) or x.dtype != dt or x.dim() != nd or tuple(x.shape[:2]) != (sel.T, sel.B) or not x.is_contiguous() or x[0, 0].numel() < 1:
+            raise ValueError(f"sast_amd: select_labels needs {name} as a contiguous {str(dt).replace('torch.', '')} tensor of shape "
+                             f"[{sel.T}, {sel.B}{', M, C' if nd == 4 else ''}], got {tuple(getattr(x, 'shape', ()))} {getattr(x, 'dtype', type(x).__name__)}")
+    _need_gpu(*[x for x, *_ in todo])
+    outs = []
+    for x, dt, _nd, name in todo:
+        if x.device != sel.device:
+            raise ValueError(f"sast_amd: the selection table lives on {sel.device}, {name} on {x.device}")
+        sample = x[0, 0].numel()
+        a = _gather_dev_args(sel, sel.T, sel.B, sample)
+        out = torch.empty((sel.n_out,) + tuple(x.shape[2:]), dtype=dt, device=x.device)
+        a.out = _ptr(out) if sel.n_out else None
+        for t in range(sel.T):
+            a.src[t] = x.data_ptr() + t * sel.B * sample * 4
+        L.check(L.lib().sast_gather_samples_dev(C.byref(a), _stream()), "select_labels")
+        outs.append(out)
+    outs.append(None)
+    return outs[0], outs[1]
+
+
+def _check_flags(flags: torch.Tensor, B: int, what: str):
+    if not torch.is_tensor(flags) or flags.dtype not in (torch.uint8, torch.bool):
+        raise TypeError(f"sast_amd: {what} needs the flags as a uint8 or bool tensor, got {getattr(flags, 'dtype', type(flags).__name__)}")
+    if tuple(flags.shape) != (B,) or not flags.is_contiguous():
+        raise ValueError(f"sast_amd: {what} needs contiguous flags of shape [{B}], got {tuple(flags.shape)}")
+
+
+@torch.no_grad()
+def zero_samples_dev(tensors, flags: torch.Tensor):
+    """zero_samples with the selection on the device: sample b of every tensor is zeroed in place where flags[b] != 0 (uint8 / bool [B]);
+    one launch for up to 16 tensors, the flags are read when the kernel runs (a replayed graph follows the flags of the replay)."""
+    tensors = list(tensors)
+    if not tensors:
+        return tensors
+    B = tensors[0].shape[0]
+    for x in tensors:
+        if x.dtype != torch.float32 or x.dim() < 2 or x.shape[0] != B or x[0].numel() < 1 or \
+                not (x.is_contiguous() or (x.dim() == 4 and x.permute(0, 2, 3, 1).is_contiguous())):
+            raise RuntimeError("sast_amd: zero_samples_dev needs dense fp32 tensors with the same batch as their outermost dimension")
+    if B > 256:
+        raise RuntimeError("sast_amd: zero_samples_dev supports batch <= 256")
+    _check_flags(flags, B, "zero_samples_dev")
+    _need_gpu(flags, *tensors)
+    if any(x.device != flags.device for x in tensors):
+        raise ValueError("sast_amd: zero_samples_dev needs the tensors and the flags on one device")
+    for i0 in range(0, len(tensors), L.ZERO_MAX_TENSORS):
+        a = L.SastSampleZeroDev()
+        chunk = tensors[i0:i0 + L.ZERO_MAX_TENSORS]
+        a.n, a.B, a.flags = len(chunk), B, flags.data_ptr()
+        for i, x in enumerate(chunk):
+            a.x[i], a.sample_floats[i] = x.data_ptr(), x[0].numel()
+        L.check(L.lib().sast_zero_samples_dev(C.byref(a), _stream()), "zero_samples_dev")
+    return tensors
+
+
+@torch.no_grad()
+def copy_tensors(dsts, srcs) -> None:
+    """dsts[i] <- srcs[i] (dense fp32 tensors of equal shapes and memory layouts), one kernel launch for up to 16 pairs"""
+    dsts, srcs = list(dsts), list(srcs)
+    _need_gpu(*dsts, *srcs)
+    if len(dsts) != len(srcs):
+        raise RuntimeError("sast_amd: copy_tensors needs as many destinations as sources")
+    for d, s in zip(dsts, srcs):
+        if d.dtype != torch.float32 or s.dtype != torch.float32 or d.shape != s.shape or d.stride() != s.stride() or d.device != s.device or \
+                d.numel() < 1 or not (d.is_contiguous() or (d.dim() == 4 and d.permute(0, 2, 3, 1).is_contiguous())):
+            raise RuntimeError("sast_amd: copy_tensors needs pairs of dense fp32 tensors with one shape and memory layout on one device")
+    for i0 in range(0, len(dsts), L.ZERO_MAX_TENSORS):
+        a = L.SastTensorCopy()
+        a.n = len(dsts[i0:i0 + L.ZERO_MAX_TENSORS])
+        for i, (d, s) in enumerate(zip(dsts[i0:i0 + L.ZERO_MAX_TENSORS], srcs[i0:i0 + L.ZERO_MAX_TENSORS])):
+            a.dst[i], a.src[i], a.floats[i] = d.data_ptr(), s.data_ptr(), d.numel()
+        L.check(L.lib().sast_copy_tensors(C.byref(a), _stream()), "copy_tensors")
 
 
 @torch.no_grad()

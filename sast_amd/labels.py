@@ -53,6 +53,7 @@ class LabelStreams:
                         max_labels_per_frame)
     ls.load(records, counts, reset=None, check=False)     once per recording and row
     labels, counts, ends_us, labelled = ls.labels(window_idx, out=None)
+    ls.labelled_windows()                                 per row, which windows are label frames (host copy, once after load)
 
     records: int32 [S, capacity, 10] on the device, row s the 40-byte BBOX_DTYPE records of one recording as ten little-endian words
       (`LabelStreams.pack` makes them from a structured array), sorted by t, the first counts[s] (int64 [S]) of them valid.
@@ -201,6 +202,17 @@ class LabelStreams:
                 for bit, name, msg in FLAGS:
                     if v & bit:
                         raise ValueError(f"sast_amd.labels: row {s}: {name}: {msg}")
+
+    def labelled_windows(self) -> List[np.ndarray]:
+        """per row a numpy bool array over its n_windows windows: True where the window ends at a label frame (window_2_frame >= 0),
+        whether or not any of its boxes survives the filters or a later augmentation -- the pairs the training step selects
+        (modules/detection.py:161-171).  ONE synchronising copy, meant to be called once after `load`: a loader then knows the number K
+        of labelled (timestep, sample) pairs of every step (the batch of the PAFPN / head pass, `functional.SelectionTable`'s n_out)
+        without a sync per step."""
+        if self._args is None:
+            raise RuntimeError("sast_amd.labels: call load() before labelled_windows()")
+        both = torch.cat([self.n_windows.view(-1, 1), self.window_2_frame], dim=1).cpu().numpy()
+        return [both[s, 1:1 + int(both[s, 0])] >= 0 for s in range(self.num_streams)]
 
     def labels(self, window_idx: torch.Tensor, out=None):
         S, M = self.num_streams, self.max_labels_per_frame

@@ -96,6 +96,11 @@ class TrainStep:
         self._graphs = None
         self._dw_graphs = None
         self._seg_state = None
+        self._replaying = False    # inside replay(): the side stream runs the captured flush graphs, nothing is parked eagerly
+        self._carry = None         # carry_states: the input state tensors the final states are copied into
+        self.label_counts = None
+        self._sets = {}            # capture(key=...): key -> the captured graph set and what replay(key) restores with it
+        self._pool = None          # the memory pool the keyed sets share (only one of them replays at a time)
         # measure_exposed: every step records (main stream idle, side stream done) event pairs -- how long the step waits for the
         # last bucket's all-reduce + update AFTER its own backward has finished (bench.py: `allreduce_exposed_ms`)
         self.measure_exposed = False
@@ -103,10 +108,33 @@ class TrainStep:
         self._bucket_ev = {}       # bucket -> [(start, end)] event pairs on the stream that runs its all-reduce + update (measure_exposed)
 
     # ---------------------------------------------------------------- forward + backward segments
-    def forward(self, xs: Sequence[torch.Tensor], states=None, labels=None, indices=None, token_masks=None):
+    def forward(self, xs: Sequence[torch.Tensor], states=None, labels=None, indices=None, token_masks=None, *, selection=None, reset=None,
+                carry_states: bool = False, label_counts=None):
         """xs: the event tensors of the sequence (one timestep = BASELINE's metric).  labels None: proxy objective
         sum_k mean(out_k^2) on the PAFPN outputs of the last timestep; else the YOLOX / SimOTA loss on `labels`, with
-        `indices` (per timestep the batch indices that carry labels, modules/detection.py:161-171) or on the last timestep."""
+        `indices` (per timestep the batch indices that carry labels, modules/detection.py:161-171) or on the last timestep.
+
+        The same selection from DEVICE memory, for a step that is captured once and replayed on new label patterns and sequence starts:
+        selection: a `functional.SelectionTable` for (len(xs), B) instead of `indices`; `labels` / `label_counts` are then the full
+          [T, B, M, 5] / [T, B] tensors (as `SpatialAugmentor(yolox=True)` returns them) and are gathered by the table like the feature
+          maps (the gathered counts are left in `self.label_counts`).  The batch of the PAFPN / head pass is the table's n_out.
+        reset: uint8 / bool [B] on the device; the flagged samples of the INPUT state tensors are zeroed in place, in one launch, before
+          the first timestep (RNNStates.reset at is_first_sample).
+        carry_states: the step ends by copying the final states, detached, into the input state tensors (one launch), so that the next
+          step / replay continues the streams (RNNStates.save_states_and_detach + get_states)."""
+        if selection is not None and indices is not None:
+            raise ValueError("sast_amd.TrainStep: `selection` (device table) and `indices` (host lists) are mutually exclusive")
+        if selection is not None and selection.T != len(xs):
+            raise ValueError(f"sast_amd.TrainStep: the selection table is for {selection.T} timesteps, the sequence has {len(xs)}")
+        self._carry = None
+        if reset is not None or carry_states:
+            if states is None or any(s is None for s in states):
+                raise ValueError("sast_amd.TrainStep: `reset` / `carry_states` work on the input state tensors: pass states (zeros for a fresh start)")
+            held = [t for s in states for t in s]
+            if reset is not None:
+                SF.zero_samples_dev(held, reset)
+            if carry_states:
+                self._carry = held
         if self.defer_dw and SF.dw_pending():
             # a backward of an earlier step died between parking and flushing: its jobs point at buffers that are gone -- never run them
             SF.dw_discard()
@@ -120,7 +148,16 @@ class TrainStep:
             feats_seq.append(feats)
             Ps.append(P)
         cut = dict(self.net.last_cuts) if (single and self.net.last_cuts) else None
-        if indices is not None:
+        self.label_counts = None
+        if selection is not None:
+            from .detection.sequence import DeviceFeatureSelector
+            sel = DeviceFeatureSelector(selection)
+            for f in feats_seq:
+                sel.add_backbone_features({k: f[k] for k in self.fpn.in_features})
+            fpn_in = sel.get_batched_backbone_features()
+            if labels is not None:
+                labels, self.label_counts = SF.select_labels(labels, label_counts, selection)
+        elif indices is not None:
             from .detection.sequence import BackboneFeatureSelector
             sel = BackboneFeatureSelector()
             for f, idx in zip(feats_seq, indices):
@@ -237,13 +274,19 @@ class TrainStep:
         """the weight-gradient jobs segment i parked, on the current (side) stream: the captured graph of the flush, or the launches"""
         if not self.defer_dw:
             return
-        if self._dw_graphs is not None:
+        if self._replaying and self._dw_graphs is not None:      # (an eager step between replays flushes its own jobs)
             if self._dw_graphs[i] is not None:
                 self._dw_graphs[i].replay()
         elif self.dw_discard:
             SF.dw_discard()
         else:
             SF.dw_flush()
+
+    def _carry_now(self):
+        """carry_states: the final states into the input state tensors.  Nothing of the step may still read the inputs: the backward is
+        over, and with deferred weight gradients the side stream has run its parked jobs (they read the first timestep's states)"""
+        if self._carry is not None:
+            SF.copy_tensors(self._carry, [t.detach() for s in self.states for t in s])
 
     def flush_pending(self):
         """callers that run forward + backward_segment() themselves (no reduce / update): the parked jobs on the CURRENT stream"""
@@ -280,7 +323,7 @@ class TrainStep:
                 e1.record(self.side)       # ... the side stream still owes the last bucket's reduce + update
                 self._exposed.append((e0, e1))
             main.wait_stream(self.side)
-        if self.defer_dw and self._graphs is None:
+        if self.defer_dw and not self._replaying:
             SF.dw_release()          # eager: the allocating stream is now ordered behind the flushed launches
 
     def exposed_ms(self):
@@ -294,18 +337,25 @@ class TrainStep:
         return sum(v) / len(v)
 
     # ---------------------------------------------------------------- eager step
-    def step(self, xs, states=None, labels=None, indices=None, token_masks=None):
+    def step(self, xs, states=None, labels=None, indices=None, token_masks=None, **device_selection):
+        """**device_selection: selection / reset / carry_states / label_counts of `forward`"""
         self.flat.check_views()
-        self.forward(xs, states, labels, indices, token_masks)
+        self.forward(xs, states, labels, indices, token_masks, **device_selection)
         for i in range(self.n_segments()):
             self.backward_segment(i)
             self._after_segment(i, first=(i == 0))
         self.finish()
+        self._carry_now()
         return self.loss
 
     # ---------------------------------------------------------------- hipGraph: one graph per segment, collectives outside
-    def capture(self, xs, states=None, labels=None, indices=None, token_masks=None):
+    def capture(self, xs, states=None, labels=None, indices=None, token_masks=None, *, key=None, **device_selection):
         """capture the step as hipGraphs (the inputs must be static tensors); `replay()` then runs a whole step.
+        **device_selection: selection / reset / carry_states / label_counts of `forward` -- with them the captured step reads the label
+        pattern, the reset flags and the carried states from device memory, so a replay follows what the caller wrote there.
+        key: None keeps ONE captured step (a new capture replaces it).  Any other hashable value files the captured set under that key
+        beside the others; `replay(key)` runs it.  A caller with device selection keys by K = selection.n_out (the one quantity a graph
+        fixes) and runs `step` for a K it has not captured.  Keyed sets share one memory pool: only one replays at a time.
         segmented: forward + segment A, segment B, segment C as graphs sharing one memory pool, reduce + update between them
         (never captured).  not segmented and world == 1: ONE graph including the optimizer update; not segmented and
         world > 1: one graph for forward + backward, all-reduce + update behind it."""
@@ -323,17 +373,20 @@ class TrainStep:
                 raise RuntimeError("sast_amd.TrainStep.capture: the model was converted with convert_sync_batchnorm and the process group's "
                                    f"backend ({dist.get_backend(grp.group)}) runs its collectives on the host; the statistics all-reduces "
                                    "inside the PAFPN / head passes can only be captured into hipGraphs on RCCL (\"nccl\") -- run step()")
+        if key is not None and self._pool is None:
+            self._pool = torch.cuda.graph_pool_handle()
         if not self._side_path():
             g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                self.forward(xs, states, labels, indices, token_masks)
+            with torch.cuda.graph(g, pool=self._pool if key is not None else None, capture_error_mode="thread_local"):
+                self.forward(xs, states, labels, indices, token_masks, **device_selection)
                 self.backward_segment(0)
                 if self.world == 1:
                     self._after_segment(0, first=True)
             self._graphs = [g]
             self.loss = self.loss.detach()
+            self._file_set(key)
             return
-        pool = torch.cuda.graph_pool_handle()
+        pool = self._pool if key is not None else torch.cuda.graph_pool_handle()
         graphs, dw_graphs = [], []
 
         def flush_graph():
@@ -353,7 +406,7 @@ class TrainStep:
 
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g, pool=pool, capture_error_mode="thread_local"):
-            self.forward(xs, states, labels, indices, token_masks)
+            self.forward(xs, states, labels, indices, token_masks, **device_selection)
             self.backward_segment(0)
         graphs.append(g)
         dw_graphs.append(flush_graph())
@@ -367,8 +420,32 @@ class TrainStep:
         self._dw_graphs = dw_graphs if self.defer_dw else None
         SF.dw_release()
         self.loss = self.loss.detach()
+        self._file_set(key)
 
-    def replay(self):
+    _SET_FIELDS = ("_graphs", "_dw_graphs", "loss", "losses", "P", "states", "label_counts", "_carry")
+
+    def _file_set(self, key):
+        """capture: keep, under `key`, what the capture left in this object -- the graphs and the (static) tensors a replay fills.  Of the
+        autograd state only the segment layout is kept (`n_segments` / `bucket_of_segment` read it while replaying)."""
+        st = {f: getattr(self, f) for f in self._SET_FIELDS}
+        cut = self._seg_state[3]
+        st["_seg_state"] = (None, None, None, None if cut is None else dict.fromkeys(cut))
+        self._sets[key] = st
+
+    def replay(self, key=None):
+        """run the captured step: the one of `capture()` (key None), or the set filed under `key` (KeyError when nothing was captured
+        under it: the caller runs `step`).  Returns the loss tensor of that set."""
+        for f, v in self._sets[key].items():
+            setattr(self, f, v)
+        self._replaying = True
+        try:
+            loss = self._replay()
+        finally:
+            self._replaying = False
+        self._carry_now()
+        return loss
+
+    def _replay(self):
         if not self._side_path():
             self._graphs[0].replay()
             if self.world > 1:
