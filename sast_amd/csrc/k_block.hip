@@ -332,7 +332,8 @@ int sast_select_pair(const float* tok, int B, int H, int W, int ph, int pw, doub
 int sast_score_stp_fwd(const SastScoreArgs* a, sast_stream_t stream) { SAST_ENTRY();
   hipStream_t st = (hipStream_t)stream;
   ProfScope ps_("score_fwd", a ? a->C : 0, a ? a->B * a->L : 0, st);
-  if (!a || a->C % 4) return SAST_EINVAL;
+  // a width the STP row kernel has no instantiation for is refused here, before the scoring GEMM writes s / scale
+  if (!a || a->C % 4 || !row_width_supported(a->C)) return SAST_EINVAL;
   const int M = a->B * a->L, C = a->C;
   // the controls (B*C outputs) ride as side workgroups of the scoring GEMM; 256 is the smallest workgroup of gemm_auto's tiles
   EpBiasReluCtl ep{};

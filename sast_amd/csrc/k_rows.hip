@@ -524,6 +524,12 @@ __global__ __launch_bounds__(ROWB) void ln_bwd_kernel(const float* __restrict__ 
     default: return SAST_EINVAL;                      \
   }
 
+static int row_width_rc(int C) {
+  SAST_DISPATCH_C(C, (void)(GL + VPL));
+  return SAST_OK;
+}
+bool row_width_supported(int C) { return row_width_rc(C) == SAST_OK; }
+
 static inline int bwd_grid(int rows, int rpb) {
   // every block ends with one atomicAdd per channel per parameter-gradient vector: same-address float atomics serialise
   // at the memory side on MI355X, so the block count (not the row count) sets the tail -> keep it small

@@ -13,6 +13,7 @@ int input_prep_dispatch(const void* x, int dtype, float* y, int* ws, float* r, i
                         unsigned* nonexact = nullptr);
 int input_prep_u8(const unsigned char* x, unsigned char* y, int* ws, float* r, int B, int C, int H, int W, int Hp, int Wp, hipStream_t st);
 int nhwc_to_nchw_launch(const float* x, float* y, int B, int C, int HW, hipStream_t st);
+bool row_width_supported(int C);   // the row kernels (LayerNorm, STP weighting) are instantiated for this width (SAST_DISPATCH_C)
 int ln_fwd_launch(const float* x, float* y, const float* gamma, const float* beta, const float* add, int add_rows,
                   float* mean, float* rstd, int rows, int C, float eps, hipStream_t st);
 int ln_bwd_launch(const float* x, const float* dy, const float* gamma, const float* mean, const float* rstd, float* dx,

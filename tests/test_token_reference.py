@@ -1,0 +1,175 @@
+"""CPU tests of the token-path operator sweep's own instruments (no GPU): the stand-alone restatements of tests/token_reference.py
+against the oracle lines they restate, the case table of tests/token_cases.py with the input conditions it is stated under, and the
+committed fp32 bounds (tests/golden/token_operator_bounds.json), which regenerating must reproduce.
+
+One figure of the bounds file is NOT inside the project's bar: the reference LayerNorm in float32 misses the 3e-5 output bar on the
+ill-conditioned MS-WSA case (rows 30 + 0.1 randn: e32 = 3.1e-5; 3.1e-5 .. 4.5e-5 at the widths 32 .. 128) -- the mean of 64 values
+near 30 carries a rounding error of about an ulp of 30 (1.9e-6), which the division by the spread of 0.1 turns into 2e-5 .. 4e-5 of
+the normalised row.  Every other figure is below half its bar, as in the conv suite.
+"""
+import json
+import os
+import subprocess
+import sys
+
+import pytest
+import torch
+
+import token_cases as TC
+import token_reference as R
+from oracle import sast_oracle as O
+
+COND_CASE = "mswsa-c64-dh32-mix-cond"
+
+
+def _close(a, b, rtol, what):
+    assert a.shape == b.shape, (what, a.shape, b.shape)
+    err, scale = float((a - b).abs().max()), max(float(b.abs().max()), 1e-30)
+    assert err <= rtol * scale, f"{what}: {err:.3e} of {scale:.3e}"
+
+
+# ------------------------------------------------------------------------------------------------ the restatements
+@pytest.mark.parametrize("dtype,rtol", [(torch.float32, 2e-6), (torch.float64, 1e-14)])
+@pytest.mark.parametrize("inf_rows", [False, True])
+def test_scoring_expression_reproduces_the_oracle_block(dtype, rtol, inf_rows):
+    """`score_stp` against what O.sast_block computes inline (oracle/sast_oracle.py:339-354): the pre-activation, the token scores
+    (scores_win.sum(-1)) and the weighted x.  The block runs with empty forced selections, so neither attention layer touches the
+    weighted x and the block returns it (in image layout)."""
+    B, H, W, C, part = 2, 8, 10, 32, (4, 5)
+    cfg = O.BackboneCfg(in_res_hw=(32, 40), partition_size=part, embed_dim=C, amp=2e-2)
+    pre = "stages.0.att_blocks.0.att."
+    g = torch.Generator().manual_seed(5)
+    p = {k[len(pre):]: v.to(dtype) for k, v in O.init_backbone_params(cfg, seed=3, ls_init=0.5).items() if k.startswith(pre)}
+    p["to_controls.weight"] = (1 + 0.1 * torch.randn(C, 20, generator=g)).to(dtype)
+    if inf_rows:
+        p["to_controls.weight"][[1, 7]] = -float("inf")
+    x = torch.randn(B, H, W, C, generator=g).to(dtype)
+    pe = O.position_embedding_sine(H, W, C).to(dtype)
+    r = (torch.rand(B, 20, generator=g) * torch.tensor([[0.02], [0.0]])).to(dtype)       # a quiet frame and an empty one
+    empty = [torch.zeros(0, dtype=torch.long)] * 5
+    kl = {}
+    xw_o, _cnt, _lists, scores_win = O.sast_block(x, pe, r, p, "", cfg.attn, first_block=True, return_scores=True,
+                                                  forced_lists=[empty, empty], kink_log=kl)
+    xp = R.add_pos_embedding(x, pe)
+    assert torch.equal(xp, x + pe[:, :H, :W, :].repeat(B, 1, 1, 1))
+    xw, tok = R.score_stp(xp.view(B, H * W, C), r, p["to_scores.weight"], p["to_scores.bias"], p["to_controls.weight"], cfg.amp)
+    assert bool(torch.isfinite(tok).all()) and bool(torch.isfinite(xw).all())
+    N, T = H * W // 20, 20
+    win = lambda t: O.window_partition(t, part).reshape(B, N, T, -1)      # noqa: E731
+    _close(win(R.score_preact(xp, p["to_scores.weight"], p["to_scores.bias"])), kl[""][0]["z"], rtol, "z")
+    _close(win(tok.view(B, H, W, 1))[..., 0], scores_win.sum(-1), rtol, "tok")
+    _close(xw.view(B, H, W, C), xw_o, rtol, "xw")
+    if inf_rows:        # scale = 0 there: no contribution to the token scores, weight 0.5 * sigmoid(s)
+        s = torch.relu(R.score_preact(xp, p["to_scores.weight"], p["to_scores.bias"]))
+        assert float(scores_win[..., [1, 7]].abs().max()) == 0.0
+        assert torch.equal(xw.view(B, H, W, C)[..., [1, 7]], ((0.5 * s.sigmoid()) * xp)[..., [1, 7]])
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
+def test_mask_token_and_pos_emb_expressions_reproduce_the_oracle_lines(dtype):
+    """oracle/sast_oracle.py:428-430 (x[token_mask] = mask_token, before the block) followed by :339 (x + pe): the device order is the
+    other way round (the rows already carry pe, a masked row becomes token + pe) -- the same numbers bit for bit"""
+    B, H, W, C = 2, 4, 5, 8
+    g = torch.Generator().manual_seed(1)
+    x, pe = torch.randn(B, H, W, C, generator=g).to(dtype), torch.randn(1, H, W, C, generator=g).to(dtype)
+    token = torch.randn(1, 1, 1, C, generator=g).to(dtype)
+    mask = torch.rand(B, H, W, generator=g) < 0.3
+    xo = x.clone()
+    xo[mask] = token.to(xo.dtype)
+    assert torch.equal(R.mask_token(x, mask, token), xo)
+    want = xo + pe[:, :H, :W, :].repeat(B, 1, 1, 1)
+    assert torch.equal(R.mask_token(R.add_pos_embedding(x, pe), mask, token, pe), want)
+    assert torch.equal(R.mask_token(R.add_pos_embedding(x, pe), torch.zeros_like(mask), token, pe), x + pe)
+
+
+def test_index_lists_are_the_oracles_selection():
+    """the lists built from explicit kept slots are what oracle.select_tokens builds from scores that keep exactly those slots"""
+    case = TC.BY_ID["mswsa-c64-dh32-mix"]
+    kept = TC.kept_slots(case)
+    iw, it, pad, asy, K = R.index_lists(kept, 20)
+    assert iw.tolist() == sorted(kept) and K.tolist() == [len(kept[w]) for w in sorted(kept)]
+    assert asy.tolist() == [m * 20 + t for m, w in enumerate(sorted(kept)) for t in kept[w]]
+    assert it.numel() == len(kept) * 20 and set(asy.tolist()) <= set(it.tolist())
+    assert sorted(pad.tolist()) == sorted(set(it.tolist()) - set(asy.tolist()))
+
+
+# ------------------------------------------------------------------------------------------------ the case table
+def test_case_table_covers_what_the_sweep_is_about():
+    sc = [c for c in TC.SCORE_CASES if c["kind"] == "exact"]
+    assert {c["C"] for c in sc if (c["B"], c["L"]) == (3, 33)} == set(TC.WIDTHS)
+    assert {c["L"] for c in sc if c["C"] == 32} >= {7, 33, 1030, 8200} and {(c["C"], c["B"]) for c in sc} >= {(96, 1), (768, 1)}
+    assert {c["amp"] for c in sc} == set(TC.AMPS) == {c["amp"] for c in sc if c["C"] == 64}
+    assert {c["C"] for c in TC.SCORE_CASES if c["kind"] == "gauss"} == {64, 192, 1024}
+    assert [c["C"] for c in TC.SCORE_CASES if c["kind"] == "inf"] == [64]
+    ms = TC.MSWSA_CASES
+    plain = [c for c in ms if c["id"].endswith("-mix") and not c["fused"]]
+    assert {c["C"] for c in plain} == set(TC.WIDTHS) and {c["dh"] for c in plain if c["C"] == 64} == {8, 16, 32}
+    assert all(c["inner"] == O.mlp_inner_dim(c["C"]) and c["C"] % c["dh"] == 0 for c in ms)
+    assert {(c["C"], c["dh"]) for c in plain} >= {(48, 24), (96, 16)}
+    assert sorted((c["fused"], c["nograd"]) for c in ms if c["fused"]) == [(True, False), (True, True)]
+    assert {c["C"] for c in ms if c["env"].get("SAST_LN_BLOCKS") == "1"} == {32, 192, 1024}
+    for C in (48, 192):
+        feats = [c for c in ms if c["C"] == C]
+        assert any(not c["ls"] for c in feats) and any(c["cb"] for c in feats) and any(c["drop"] for c in feats) and any(c["act"] == "prelu" for c in feats)
+    assert sum(c["cond"] for c in ms) == 1 and any(c["sel"] == "empty2" for c in ms)
+    assert {(c["C"], c["pattern"]) for c in TC.MASK_CASES if c["pe"]} == {(C, p) for C in (32, 48, 1024) for p in ("none", "all", "every257")}
+    assert any(not c["pe"] for c in TC.MASK_CASES) and {c["C"] for c in TC.ADDPOS_CASES} == {32, 48, 1024}
+    ls = TC.LSTM_CASES
+    assert {(c["C"], c["state"]) for c in ls} >= {(C, s) for C in TC.WIDTHS for s in ("given", "none", "zero")}
+    assert {c["C"] for c in ls if c["two"]} == {48, 256} == {c["C"] for c in ls if c["drop"]}
+
+
+@pytest.mark.parametrize("case", TC.ALL_CASES, ids=[c["id"] for c in TC.ALL_CASES])
+def test_input_conditions_hold(case):
+    """what the cases are stated under (exact-gate inputs: min |z| >= 1/256 on the float64 reference, the r slice, the -inf control rows,
+    the selections, the mask patterns, the row counts)"""
+    TC.check_conditions(case, TC.make_inputs(case))
+
+
+# ------------------------------------------------------------------------------------------------ the committed bounds
+@pytest.fixture(scope="module")
+def bounds(golden_dir):
+    with open(os.path.join(golden_dir, "token_operator_bounds.json")) as f:
+        return json.load(f)
+
+
+def test_regenerating_the_bounds_reproduces_the_committed_file(golden_dir, bounds, tmp_path):
+    """make_token_bounds.py (--threads 1,4, worst of the two) evaluates every case in float32 and float64: the result equals the committed
+    file to the printed precision, so every case holds every quantity its reference produces"""
+    out = tmp_path / "bounds.json"
+    subprocess.run([sys.executable, os.path.join(golden_dir, "make_token_bounds.py"), "--out", str(out)], check=True)
+    with open(out) as f:
+        fresh = json.load(f)
+    assert set(fresh["cases"]) == set(bounds["cases"]) == {TC.bounds_id(c) for c in TC.ALL_CASES}
+    for cid in sorted(fresh["cases"]):
+        assert fresh["cases"][cid] == bounds["cases"][cid], cid
+    assert fresh["operators"] == bounds["operators"]
+
+
+def test_bounds_hold_every_compared_quantity_and_stay_inside_the_project_bars(bounds):
+    for case in TC.ALL_CASES:
+        entry = bounds["cases"][TC.bounds_id(case)]
+        want = {"score": {"exact": {"out:xw", "rel:tok", "grad:xp", "grad:ws_w", "grad:ws_b", "grad:wc"}, "gauss": {"out:xw", "rel:tok", "grad:wc"},
+                          "inf": {"out:xw", "rel:tok"}}.get(case.get("kind")),
+                "mask_token": {"out:y", "grad:x", "grad:token"}, "add_pos": {"out:y", "grad:x"}}.get(case["op"])
+        if case["op"] == "lstm":
+            want = {"out:h1", "out:c1", "grad:x", "grad:w", "grad:b"} | {f"grad:{s}" for s in ("h0", "c0") if
+                                                                         (s == "h0" and case["state"] != "none") or (s == "c0" and case["state"] in ("given", "zero"))}
+        if case["op"] == "mswsa":
+            want = {"out:y", "grad:x"} | {f"grad:{k}" for k in R.MSWSA_NAMES if k != "act_w" and (case["ls"] or k not in ("ls1", "ls2"))}
+            if case["act"] == "prelu":
+                want.add("grad:act_w")
+        assert set(entry) == want, case["id"]
+        assert set(TC.compared(case, entry)) == ({"out:y"} if case.get("nograd") else want)
+        for q, e in entry.items():
+            med = bounds["operators"][case["op"]][TC.pool_key(q)]["median"]
+            assert e >= 0.0 and med >= 0.0
+            exact = q in TC.EXACT.get(case["op"], ()) or (case.get("pattern") == "none" and q == "grad:token")
+            if not exact:       # (copies, single adds and an empty sum: the GPU test asks for bit equality with the float32 reference there)
+                assert e > 0.0, (case["id"], q)
+            if not (TC.bounds_id(case) == COND_CASE and q == "out:y"):
+                assert e < TC.project_bar(q) / 2, (case["id"], q, e)
+    assert 3e-5 < bounds["cases"][COND_CASE]["out:y"] < 4e-5        # the figure of the module docstring
+    for op, qs in bounds["operators"].items():
+        for q, v in qs.items():
+            assert v["median"] <= v["worst"] and v["median"] < TC.project_bar(q) / 2 and v["n"] >= 2, (op, q, v)
