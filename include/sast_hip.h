@@ -578,6 +578,13 @@ int sast_evstreams_correct_time(const void* t, int t_dtype, const int64_t* count
 int sast_evstreams_window_bounds(const int64_t* t, const int64_t* counts, int S, int64_t stream_capacity, const int64_t* ends_us, int T,
                                  int mode, int64_t value, int64_t* bounds, sast_stream_t stream);
 
+/* sast_evstreams_window_bounds through a row map, for the random-access sampler below (csrc/k_events.hip: the same kernel): window w = k * B + b (ends_us int64 [T, B]) is searched in row rows[b] (int32 [B] in
+ * device memory) of the R rows, so a step may hold several windows of one row and rows that no window uses.  A row outside [0, R)
+ * gives the empty range [0, 0): sast_event_frames / sast_mdstack_frames, called unchanged with T * B windows over capacity
+ * R * stream_capacity, leave that frame zero.  R * stream_capacity <= 2^31 - 1.  bounds: int64 [T * B, 2].  1 launch. */
+int sast_rnd_window_bounds(const int64_t* t, const int64_t* counts, int R, int64_t stream_capacity, const int32_t* rows,
+                           const int64_t* ends_us, int B, int T, int mode, int64_t value, int64_t* bounds, sast_stream_t stream);
+
 /* ---- event retention across chunks (csrc/k_events.hip): S rows of [S, capacity] storage keep exactly the events that later windows can
  * still need, so a host pushes chunks cut at arbitrary points (a camera's transfer size) and asks for windows as their ends pass.  The
  * reference has no such stage: it reads a whole recording and windows it offline (scripts/genx/preprocess_dataset.py:476-530); the
@@ -699,6 +706,48 @@ int sast_labels_load(const SastLabelArgs* a, const int32_t* records, const int64
  * 1 launch. */
 int sast_labels_gather(const SastLabelArgs* a, const int64_t* window_idx, int T, float* labels, int32_t* counts, int64_t* ends_us,
                        uint8_t* labelled, sast_stream_t stream);
+
+/* ---- random-access sampler (csrc/k_sampler.hip): training sequences that end at a label frame, over the R = SastLabelArgs.S rows
+ * sast_labels_load has filled.  The reference does this on the CPU: SequenceForRandomAccess (data/genx_utils/sequence_rnd.py:9-75),
+ * torch's ConcatDataset, get_most_recent_objframe (data/utils/augmentor.py:367-378) and get_weighted_random_sampler
+ * (data/genx_utils/dataset_rnd.py:115-149).  Integers equal the reference's, the fp64 weights equal it bit for bit.  With
+ * f2w = frame_2_window[r][0 .. n_frames[r]):  start_idx_offset[r] = the first j with f2w[j] - sequence_length + 1 >= 0, or n_frames[r];
+ * length[r] = n_frames[r] - start_idx_offset[r];  cum[0] = 0, cum[r + 1] = cum[r] + length[r].  Item g of the N = cum[R] items lies in
+ * the row with cum[r] <= g < cum[r + 1]; its label frame is j = g - cum[r] + start_idx_offset[r], its windows are
+ * f2w[j] + 1 - sequence_length ... f2w[j].  Every size is read on the device and every index clamped there; the grids are sized from
+ * R, B, sequence_length, max_frames and max_classes, so the calls replay inside a graph.
+ * status bits (SastRndArgs.status, int32 [R + 1]: one word per row, then one for the pool), cleared by sast_rnd_index: */
+enum {
+  SAST_RND_CLASS_ID = 1,               /* row r: a box of a counted label frame has a class id outside [0, max_classes); left out */
+  SAST_RND_ITEM_INDEX = 2              /* word R: sast_rnd_gather was given an item outside [0, N) */
+};
+typedef struct SastRndArgs {
+  int32_t* start_idx_offset; /* [R] */
+  int32_t* length;           /* [R] */
+  int64_t* cum;              /* [R + 1] */
+  int64_t* class_total;      /* [max_classes]: boxes per class over all items (weighted only; zeroed otherwise) */
+  double* weights;           /* [R * max_frames]: the weight of item g at [g], 0 behind N; may be NULL unless weighted */
+  int32_t* status;           /* [R + 1] */
+  int32_t* ticket;           /* [1], zero before the first call; every call leaves it zero */
+  int32_t sequence_length;   /* 1 .. 65535 */
+  int32_t only_load_end_labels; /* label frames of the last step only (the others read as unlabelled) */
+  int32_t max_classes;       /* 1 .. 256 */
+  int32_t weighted;          /* also class_total and weights */
+} SastRndArgs;
+/* start_idx_offset, length, cum (1 launch: a workgroup per row, the last one to finish scans the lengths); weighted: per item the
+ * boxes per class over the label frames of its windows (only_load_end_labels: of its last window), class_total their sum over all
+ * items (int64 atomics), weight = sum over c ascending of (1.0 / max(class_total[c], 1)) * count[c] in fp64, one rounding per
+ * operation, starting from 0 (2 more launches, a workgroup per possible item). */
+int sast_rnd_index(const SastLabelArgs* a, SastRndArgs* q, sast_stream_t stream);
+/* items int64 [B] (device) -> rows int32 [B], window_idx / ends_us int64 [L, B], labels fp32 [L, B, M, 7], counts int32 [L, B],
+ * labelled uint8 [L, B] (L = sequence_length, M = max_labels_per_frame; per (step, sample) what sast_labels_gather gives for row
+ * rows[b] at that window; only_load_end_labels: steps before the last have counts 0, labelled 0 and zero rows), latest fp32 [B, M, 7]
+ * / latest_count int32 [B]: the rows of the sample's last step with counts > 0, or 0.  An item outside [0, N): rows -1, window_idx
+ * and ends_us -1, counts, labelled, latest_count 0, zero rows, SAST_RND_ITEM_INDEX in status[R].  1 launch, a workgroup per
+ * (step, sample). */
+int sast_rnd_gather(const SastLabelArgs* a, const SastRndArgs* q, const int64_t* items, int B, int32_t* rows, int64_t* window_idx,
+                    int64_t* ends_us, float* labels, int32_t* counts, uint8_t* labelled, float* latest, int32_t* latest_count,
+                    sast_stream_t stream);
 
 /* ---- spatial augmentation of event frames and box labels (csrc/k_augment.hip).  The reference augments on the CPU in its data-loader
  * workers: RandomSpatialAugmentorGenX.__call__ (data/utils/augmentor.py:347-364) -- horizontal flip, then zoom-in (:203-222) or zoom-out

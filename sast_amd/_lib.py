@@ -105,6 +105,11 @@ SastLabelArgs = _struct("SastLabelArgs", [
     (C.c_int64, "capacity base_delta_us align_t_us delta_t_us"), (I32, "S width height class_max"), (F32, "min_diag2 min_side max_width"),
     (I32, "reprs_per_frame downsample_by_2 max_frames max_windows max_labels_per_frame reserved"),
 ])
+RND_CLASS_ID, RND_ITEM_INDEX = 1, 2   # SAST_RND_*: the status bits of a RandomAccessPool (per row; pool-wide)
+RND_MAX_CLASSES = 256
+SastRndArgs = _struct("SastRndArgs", [
+    (P, "start_idx_offset length cum class_total weights status ticket"), (I32, "sequence_length only_load_end_labels max_classes weighted"),
+])
 SastEvalArgs = _struct("SastEvalArgs", [
     (P, "labels counts det n_det"), (I32, "N M A K"), (F32, "min_diag2 min_side"), (I32, "max_images max_labels_per_frame"),
     (C.c_int64, "max_detections"),
@@ -192,6 +197,7 @@ _SIGNATURES = {
     "sast_evstreams_ws_count": (C.c_size_t, [C.c_int]),
     "sast_evstreams_correct_time": (C.c_int, [P, C.c_int, P, C.c_int, C.c_int64, P, P, P, P, P]),
     "sast_evstreams_window_bounds": (C.c_int, [P, P, C.c_int, C.c_int64, P, C.c_int, C.c_int, C.c_int64, P, P]),
+    "sast_rnd_window_bounds": (C.c_int, [P, P, C.c_int, C.c_int64, P, P, C.c_int, C.c_int, C.c_int, C.c_int64, P, P]),
     "sast_evqueue_ws_count": (C.c_size_t, [C.c_int]),
     "sast_evqueue_push": (C.c_int, [C.POINTER(SastEvQueueArgs), P, P, P, P, C.c_int, C.c_int, C.c_int, C.c_int, P, C.c_int64, P, P]),
     "sast_evqueue_window_bounds": (C.c_int, [C.POINTER(SastEvQueueArgs), P, C.c_int, C.c_int, C.c_int64, P, P]),
@@ -199,6 +205,8 @@ _SIGNATURES = {
     "sast_labels_ws_bytes": (C.c_size_t, [C.c_int, C.c_int64, C.c_int]),
     "sast_labels_load": (C.c_int, [C.POINTER(SastLabelArgs), P, P, P, P]),
     "sast_labels_gather": (C.c_int, [C.POINTER(SastLabelArgs), P, C.c_int, P, P, P, P, P]),
+    "sast_rnd_index": (C.c_int, [C.POINTER(SastLabelArgs), C.POINTER(SastRndArgs), P]),
+    "sast_rnd_gather": (C.c_int, [C.POINTER(SastLabelArgs), C.POINTER(SastRndArgs), P, C.c_int] + [P] * 9),
     "sast_augment_frames": (C.c_int, [P, P, P] + [C.c_int] * 5 + [P]),
     "sast_augment_labels": (C.c_int, [P, P, P] + [C.c_int] * 4 + [P, P, P, P]),
     "sast_eval_reset": (C.c_int, [C.POINTER(SastEvalArgs), P]),

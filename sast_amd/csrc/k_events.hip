@@ -407,11 +407,18 @@ __device__ __forceinline__ long long search(const long long* t, long long n, lon
   return lo;
 }
 
+// rows == nullptr: window w = k * S + s belongs to row s.  Otherwise window w = k * cols + b belongs to row rows[b] (int32 [cols], read
+// on the device): several windows of one step may share a row; a row outside [0, S) gives the empty range [0, 0)
 __global__ void ev_bounds_kernel(const long long* t, const long long* counts, int S, long long cap, const long long* ends, int B,
-                                 int mode, long long value, long long* bounds) {
+                                 int mode, long long value, long long* bounds, const int* rows, int cols) {
   const int w = blockIdx.x * blockDim.x + threadIdx.x;     // window k * S + s
   if (w >= B) return;
-  const int s = w % S;
+  const int s = rows ? rows[w % cols] : w % S;
+  if (s < 0 || s >= S) {
+    bounds[2 * w] = 0;
+    bounds[2 * w + 1] = 0;
+    return;
+  }
   const long long n = min(max(counts[s], 0LL), cap), row = (long long)s * cap;
   const long long e = search(t + row, n, ends[w], true);
   const long long b = mode == SAST_EVENT_WINDOW_COUNT ? max(e - value, 0LL) : search(t + row, n, ends[w] - value, false);
@@ -514,14 +521,15 @@ int ev_correct_time(const void* t, int t_dtype, const int64_t* counts, int S, in
 
 // the window search of T windows in each of S rows
 int ev_window_bounds(const int64_t* t, const int64_t* counts, int S, int64_t cap, const int64_t* ends_us, int T, int mode, int64_t value,
-                     int64_t* bounds, sast_stream_t stream) {
-  if (!t || !counts || !ends_us || !bounds || S < 1 || T < 1 || (long long)S * T > INT_MAX || cap < 0 || value < 0 ||
+                     int64_t* bounds, sast_stream_t stream, const int32_t* rows = nullptr, int cols = 0) {
+  if (!rows) cols = S;
+  if (!t || !counts || !ends_us || !bounds || S < 1 || T < 1 || cols < 1 || (long long)cols * T > INT_MAX || cap < 0 || value < 0 ||
       (mode != SAST_EVENT_WINDOW_DURATION && mode != SAST_EVENT_WINDOW_COUNT))
     return SAST_EINVAL;
-  const int B = S * T;
+  const int B = cols * T;
   SAST_LAUNCH(ev_bounds_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, reinterpret_cast<const long long*>(t),
               reinterpret_cast<const long long*>(counts), S, (long long)cap, reinterpret_cast<const long long*>(ends_us), B, mode,
-              (long long)value, reinterpret_cast<long long*>(bounds));
+              (long long)value, reinterpret_cast<long long*>(bounds), rows, cols);
   SAST_CHECK_LAUNCH();
   return SAST_OK;
 }
@@ -743,6 +751,13 @@ int sast_evstreams_window_bounds(const int64_t* t, const int64_t* counts, int S,
                                  int mode, int64_t value, int64_t* bounds, sast_stream_t stream) {
   SAST_ENTRY();
   return sast::ev_window_bounds(t, counts, S, stream_capacity, ends_us, T, mode, value, bounds, stream);
+}
+
+int sast_rnd_window_bounds(const int64_t* t, const int64_t* counts, int R, int64_t stream_capacity, const int32_t* rows,
+                           const int64_t* ends_us, int B, int T, int mode, int64_t value, int64_t* bounds, sast_stream_t stream) {
+  SAST_ENTRY();
+  if (!rows || B < 1 || R < 1 || R > 65535 || stream_capacity < 0 || (long long)R * stream_capacity > INT_MAX) return SAST_EINVAL;
+  return sast::ev_window_bounds(t, counts, R, stream_capacity, ends_us, T, mode, value, bounds, stream, rows, B);
 }
 
 size_t sast_event_frames_ws_bytes(int B, int bins, int height, int width, int downsample_by_2, int64_t window_capacity) {

@@ -1,0 +1,307 @@
+"""Random-access training sequences on the GPU (csrc/k_sampler.hip, and the row-mapped window search of csrc/k_events.hip).
+
+The reference trains with `dataset.train.sampling: 'mixed'`: half of the batches are streamed recordings, the other half random-access
+samples -- `sequence_length` consecutive windows that end at a randomly chosen label frame (data/genx_utils/sequence_rnd.py,
+dataset_rnd.py), every one a first sample of its own (`is_first_sample = True`), with zoom-in placed on the most recent non-empty label
+frame (data/utils/augmentor.py:367-378).  `RandomAccessPool` is that second half for R recordings resident in device memory: the item
+index of `SequenceForRandomAccess` + `ConcatDataset`, the weights of `get_weighted_random_sampler`, the label tensors of an item, and its
+event frames, from raw events and the `LabelStreams` schedule, without the host touching an event or a box.
+
+The pool is a shuffle buffer over the recordings that are resident, not the whole dataset: N, the cumulative sizes and the weights
+(whose class totals run over the pool's items) describe the R rows loaded now.  A caller that wants the reference's global shuffle
+rotates recordings through the rows (`labels.load(..., reset=)`, `load_events(..., reset=)`, `index()`).
+
+The draws stay on the host, as the augmentor's do, with the calls torch's samplers make:
+
+    n, _ = pool.index()
+    items = torch.randperm(n)                                                  # RandomSampler
+    n, _ = pool.index(weighted=True)
+    items = torch.multinomial(pool.weights[:n].cpu(), n, replacement=True)     # WeightedRandomSampler
+
+There is no CPU path: CPU tensors raise the library's "no CPU fallback" error.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import List, NamedTuple, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib as L
+from .events import _Windowed, _dtype_code, _not_capturing
+from .functional import _need_gpu, _stream
+from .labels import LabelStreams
+
+# status bits (include/sast_hip.h, SAST_RND_*): per row, then pool-wide
+ROW_FLAGS = ((L.RND_CLASS_ID, "class_id", "a box of a counted label frame has a class id outside [0, max_classes); it was left out"),)
+POOL_FLAGS = ((L.RND_ITEM_INDEX, "item_index", "batch() was given an item outside [0, N)"),)
+
+
+class RandomAccessBatch(NamedTuple):
+    """what `RandomAccessPool.batch` returns (L = sequence_length, M = the labels' max_labels_per_frame)"""
+    rows: torch.Tensor            # int32 [B]: the pool row of every sample, -1 for an item outside [0, N)
+    window_idx: torch.Tensor      # int64 [L, B]
+    ends_us: torch.Tensor         # int64 [L, B]
+    labels: torch.Tensor          # fp32 [L, B, M, 7]
+    counts: torch.Tensor          # int32 [L, B]
+    labelled: torch.Tensor        # uint8 [L, B]
+    latest: torch.Tensor          # fp32 [B, M, 7]
+    latest_count: torch.Tensor    # int32 [B]
+
+
+class RandomAccessPool(_Windowed):
+    """pool = RandomAccessPool(labels, height, width, sequence_length=L, only_load_end_labels=False, bins=10, count_cutoff=10,
+                               fastmode=True, duration_us=50_000, downsample_by_2=False, representation="stacked_histogram",
+                               window_capacity=None, max_classes=16)
+    pool.load_events(x, y, p, t, counts, reset=None)
+    n, cumulative_sizes = pool.index(weighted=False)
+    out = pool.batch(items, out=None)
+    frames = pool.frames(out, out_frames=None)
+    pool.labelled_pairs(items_host); pool.errors()
+
+    labels: a `LabelStreams` of R rows the caller has `load`ed (or loads before `index`): row r's box records and row r's events are
+      one recording.  The geometry arguments are `EventStreams`'.
+    load_events: x, y, p, t contiguous [R, cap] device tensors (dtypes as in `EventStreams`), counts int64 [R].  The pool keeps the
+      columns by reference (they must stay as they are while batches are drawn) and corrects the timestamps of the rows with
+      reset[r] != 0 (uint8 / bool [R]; default: every row) once, from a carry of 0, into its own int64 [R, cap] buffer `t`; the other
+      rows keep the corrected timestamps and the count they have.  2 launches.
+    index: after `labels.load`.  Device state: start_idx_offset, length int32 [R], cum int64 [R + 1] (cum[0] = 0), and with weighted=True
+      class_total int64 [max_classes] and weights fp64 [R * max_frames] (item g at [g], zeros behind N).  Returns N = cum[R] and
+      ConcatDataset's cumulative_sizes (cum[1:], a list) through ONE synchronising copy.  1 launch, 3 with weighted=True.  It clears
+      the status words.
+    batch: items int64 [B] on the device (ConcatDataset indices) -> `RandomAccessBatch`.  Item g lies in the row r with
+      cum[r] <= g < cum[r + 1]; its label frame is j = g - cum[r] + start_idx_offset[r], its windows are frame_2_window[r][j] + 1 - L ...
+      frame_2_window[r][j].  labels / counts / ends_us / labelled of step k and sample b are what `LabelStreams.labels` gives for row
+      rows[b] at window_idx[k, b]; with only_load_end_labels the steps before the last have counts 0, labelled 0 and zero rows (the
+      reference puts None there), ends_us is still filled.  latest[b] / latest_count[b]: the rows of the sample's last step with
+      counts > 0, unaugmented (get_most_recent_objframe(check_if_nonempty=True)); latest_count 0: none.  The copy of `latest` to the
+      host for `SpatialAugmentor.randomize(latest_labels=)` is the caller's, one per batch.  An item outside [0, N): rows -1,
+      window_idx and ends_us -1, counts 0, zero frames, and item_index in the pool's status.  Two samples of one row are allowed.
+      1 launch.
+    frames: the batch's event frames, [L, B, C, H', W'] uint8 (int8 for mixed_density): frames[k, b] is byte for byte what an
+      `EventStreams(num_streams=R, ...same arguments...)` gives for row rows[b] at window end ends_us[k, b] on the same columns with
+      reset all ones.  5 launches (1 window search through the row map, 4 histogram).  window_capacity: kept events one window may
+      hold (default: cap); `err` / `frame_errors()` as `EventStreams.errors()`.
+    labelled_pairs: host only -- the number K of labelled (step, sample) pairs of a batch of items (the batch of the PAFPN / head pass,
+      `TrainStep(selection=)`), from the host mirrors of `index()` and `labels.labelled_windows()` (fetched once after each `index`).
+    errors: (per row the names of its status bits, the names of the pool's) (synchronises).
+    After one un-captured call of batch and frames with the same B nothing is allocated but the outputs and nothing synchronises:
+    batch + frames (+ augmentor + backbone) can be captured in one graph and replayed with new items written into the same tensor.
+    Limits: the pool covers the resident recordings only; R * cap must stay below 2^31."""
+
+    LOAD_EVENTS_LAUNCHES = 2
+    INDEX_LAUNCHES = 1
+    INDEX_WEIGHTED_LAUNCHES = 3
+    BATCH_LAUNCHES = 1
+    FRAMES_LAUNCHES = 5
+
+    def __init__(self, labels: LabelStreams, height: int, width: int, sequence_length: int, only_load_end_labels: bool = False,
+                 bins: int = 10, count_cutoff: Optional[int] = 10, fastmode: bool = True, duration_us: int = 50_000,
+                 downsample_by_2: bool = False, representation: str = "stacked_histogram", window_capacity: Optional[int] = None,
+                 max_classes: int = 16):
+        if not isinstance(labels, LabelStreams):
+            raise TypeError("sast_amd.sampling: labels must be a LabelStreams")
+        if duration_us is None:
+            raise ValueError("sast_amd.sampling: duration_us is required (the windows of a label schedule are duration windows)")
+        super().__init__(bins, height, width, count_cutoff, fastmode, downsample_by_2, representation, duration_us, None, True,
+                         window_capacity)
+        if isinstance(sequence_length, bool) or not isinstance(sequence_length, int) or not 1 <= sequence_length <= 65535:
+            raise ValueError("sast_amd.sampling: sequence_length must be an int in 1 .. 65535")
+        if isinstance(max_classes, bool) or not isinstance(max_classes, int) or not 1 <= max_classes <= L.RND_MAX_CLASSES:
+            raise ValueError(f"sast_amd.sampling: max_classes must be an int in 1 .. {L.RND_MAX_CLASSES}")
+        if bool(labels.downsample_by_2) != bool(downsample_by_2):
+            raise ValueError("sast_amd.sampling: labels.downsample_by_2 and downsample_by_2 must agree")
+        self.labels = labels
+        self.num_rows = labels.num_streams
+        self.sequence_length, self.only_load_end_labels, self.max_classes = sequence_length, bool(only_load_end_labels), max_classes
+        self.x = self.y = self.p = self.t = self.counts = None
+        self.start_idx_offset = self.length = self.cum = self.class_total = self.weights = self.status = None
+        self._codes = None
+        self._args = None
+        self._host = None          # (cum [R + 1], start_idx_offset [R]) as numpy, from the last index()
+        self._labelled = None      # labels.labelled_windows() of that index, and per row the window of every label frame
+
+    # ---- events
+    def load_events(self, x: torch.Tensor, y: torch.Tensor, p: torch.Tensor, t: torch.Tensor, counts: torch.Tensor,
+                    reset: Optional[torch.Tensor] = None) -> None:
+        R = self.num_rows
+        cols = [x, y, p, t]
+        for c, name in zip(cols, ("x", "y", "p", "t")):
+            if c.dim() != 2 or c.shape[0] != R:
+                raise ValueError(f"sast_amd.sampling: {name} must be [rows={R}, capacity], got shape {tuple(c.shape)}")
+            if not c.is_contiguous():
+                raise ValueError(f"sast_amd.sampling: {name} must be contiguous")
+        if not x.shape == y.shape == p.shape == t.shape:
+            raise ValueError("sast_amd.sampling: x, y, p and t must have the same shape")
+        codes = [_dtype_code(x, "x"), _dtype_code(y, "y"), _dtype_code(p, "p"), _dtype_code(t, "t", (torch.int64, torch.int32))]
+        if counts.dtype != torch.int64 or tuple(counts.shape) != (R,) or not counts.is_contiguous():
+            raise ValueError(f"sast_amd.sampling: counts must be a contiguous int64 tensor of shape [{R}]")
+        if reset is not None and (reset.dtype not in (torch.uint8, torch.bool) or tuple(reset.shape) != (R,) or not reset.is_contiguous()):
+            raise ValueError(f"sast_amd.sampling: reset must be a contiguous uint8 or bool tensor of shape [{R}]")
+        cap = x.shape[1]
+        if cap < 1 or R * cap > 2 ** 31 - 1:
+            raise ValueError("sast_amd.sampling: capacity must be >= 1 and rows * capacity below 2^31")
+        _need_gpu(x, y, p, t, counts, reset)
+        dev = x.device
+        if len({c.device for c in cols + [counts] + ([reset] if reset is not None else [])}) != 1:
+            raise ValueError("sast_amd.sampling: x, y, p, t, counts and reset must be on the same device")
+        if self.t is None or self.t.device != dev or self.t.shape[1] != cap:
+            _not_capturing()
+            self.t = torch.zeros(R, cap, dtype=torch.int64, device=dev)
+            self.counts = torch.zeros(R, dtype=torch.int64, device=dev)
+            self.t_last = None
+            self._carry(dev, (R,))
+            self._state = {"scan": torch.empty(int(L.lib().sast_evstreams_ws_count(R)), dtype=torch.int64, device=dev),
+                           "ones": torch.ones(R, dtype=torch.uint8, device=dev), "bounds": {}}
+            if reset is not None:
+                reset = None           # nothing to keep: every row is new
+        st = self._state
+        if reset is None:
+            now, flags = counts, st["ones"]
+            self.counts.copy_(counts)
+        else:
+            keep = reset == 0
+            now, flags = counts.masked_fill(keep, 0), reset          # a row that is kept: no event, so nothing of it is rewritten
+            self.counts.copy_(torch.where(keep, self.counts, counts))
+        L.check(L.lib().sast_evstreams_correct_time(t.data_ptr(), codes[3], now.data_ptr(), R, cap, self.t.data_ptr(), self.t_last.data_ptr(),
+                                                    flags.data_ptr(), st["scan"].data_ptr(), _stream()), "evstreams_correct_time")
+        self.x, self.y, self.p = x, y, p
+        self._codes = codes[:3] + [L.DT_I64]
+
+    def frame_errors(self) -> Tuple[int, int]:
+        """(invalid events, windows over capacity) of the frames calls since the pool was made (synchronises)"""
+        return _Windowed.errors(self)
+
+    # ---- the item index
+    def _storage(self, dev):
+        la = self.labels._args
+        if la is None:
+            raise RuntimeError("sast_amd.sampling: call labels.load() before index()")
+        if self.labels.status.device != dev:
+            raise ValueError(f"sast_amd.sampling: the labels live on {self.labels.status.device}, the call's tensors on {dev}")
+        if self._args is None:
+            _not_capturing()
+            R, F = self.num_rows, self.labels.max_frames
+            self.start_idx_offset, self.length = (torch.zeros(R, dtype=torch.int32, device=dev) for _ in range(2))
+            self.cum = torch.zeros(R + 1, dtype=torch.int64, device=dev)
+            self.class_total = torch.zeros(self.max_classes, dtype=torch.int64, device=dev)
+            self.weights = torch.zeros(R * F, dtype=torch.float64, device=dev)
+            self.status = torch.zeros(R + 1, dtype=torch.int32, device=dev)
+            self._ticket = torch.zeros(1, dtype=torch.int32, device=dev)
+            a = self._args = L.SastRndArgs()
+            a.start_idx_offset, a.length, a.cum = self.start_idx_offset.data_ptr(), self.length.data_ptr(), self.cum.data_ptr()
+            a.class_total, a.weights, a.status = self.class_total.data_ptr(), self.weights.data_ptr(), self.status.data_ptr()
+            a.ticket = self._ticket.data_ptr()
+            a.sequence_length, a.only_load_end_labels, a.max_classes = self.sequence_length, int(self.only_load_end_labels), self.max_classes
+        return self._args
+
+    def index(self, weighted: bool = False) -> Tuple[int, List[int]]:
+        if self.labels._args is None:
+            raise RuntimeError("sast_amd.sampling: call labels.load() before index()")
+        a = self._storage(self.labels.status.device)
+        a.weighted = int(bool(weighted))
+        L.check(L.lib().sast_rnd_index(C.byref(self.labels._args), C.byref(a), _stream()), "rnd_index")
+        R = self.num_rows
+        both = torch.cat([self.cum, self.start_idx_offset.to(torch.int64)]).cpu().numpy()
+        self._host = (both[:R + 1].copy(), both[R + 1:].copy())
+        self._labelled = None
+        return int(both[R]), [int(v) for v in both[1:R + 1]]
+
+    def errors(self) -> Tuple[List[Tuple[str, ...]], Tuple[str, ...]]:
+        if self.status is None:
+            return [()] * self.num_rows, ()
+        v = [int(s) for s in self.status.tolist()]
+        return ([tuple(n for bit, n, _m in ROW_FLAGS if s & bit) for s in v[:-1]], tuple(n for bit, n, _m in POOL_FLAGS if v[-1] & bit))
+
+    # ---- batches
+    def _want(self, B: int):
+        Ls, M = self.sequence_length, self.labels.max_labels_per_frame
+        return (((B,), torch.int32), ((Ls, B), torch.int64), ((Ls, B), torch.int64), ((Ls, B, M, 7), torch.float32), ((Ls, B), torch.int32),
+                ((Ls, B), torch.uint8), ((B, M, 7), torch.float32), ((B,), torch.int32))
+
+    def batch(self, items: torch.Tensor, out: Optional[Sequence[torch.Tensor]] = None) -> RandomAccessBatch:
+        if items.dtype != torch.int64 or items.dim() != 1 or items.numel() < 1 or not items.is_contiguous():
+            raise ValueError("sast_amd.sampling: items must be a contiguous int64 tensor of shape [B], B >= 1")
+        _need_gpu(items)
+        if self._args is None:
+            raise RuntimeError("sast_amd.sampling: call index() before batch()")
+        dev = items.device
+        if dev != self.status.device:
+            raise ValueError(f"sast_amd.sampling: the pool lives on {self.status.device}, items on {dev}")
+        B = items.numel()
+        if B * self.sequence_length * self.labels.max_labels_per_frame > (2 ** 31 - 1) // 8:
+            raise ValueError("sast_amd.sampling: B * sequence_length * max_labels_per_frame must be <= (2^31 - 1) / 8")
+        want = self._want(B)
+        if out is None:
+            out = RandomAccessBatch(*(torch.empty(sh, dtype=dt, device=dev) for sh, dt in want))
+        else:
+            out = tuple(out)
+            if len(out) != len(want):
+                raise ValueError("sast_amd.sampling: out must be the eight tensors of a RandomAccessBatch")
+            _need_gpu(*out)
+            for t, (sh, dt), name in zip(out, want, RandomAccessBatch._fields):
+                if t.dtype != dt or tuple(t.shape) != sh or not t.is_contiguous() or t.device != dev:
+                    raise ValueError(f"sast_amd.sampling: out's {name} must be a contiguous {str(dt).replace('torch.', '')} tensor of shape "
+                                     f"{sh} on the pool's device")
+            out = RandomAccessBatch(*out)
+        L.check(L.lib().sast_rnd_gather(C.byref(self.labels._args), C.byref(self._args), items.data_ptr(), B, *(t.data_ptr() for t in out),
+                                        _stream()), "rnd_gather")
+        return out
+
+    def frames(self, batch: RandomAccessBatch, out_frames: Optional[torch.Tensor] = None) -> torch.Tensor:
+        rows, ends = batch.rows, batch.ends_us
+        _need_gpu(rows, ends, out_frames)
+        if self.x is None:
+            raise RuntimeError("sast_amd.sampling: call load_events() before frames()")
+        Ls, R, cap = self.sequence_length, self.num_rows, self.t.shape[1]
+        if rows.dtype != torch.int32 or rows.dim() != 1 or rows.numel() < 1 or not rows.is_contiguous():
+            raise ValueError("sast_amd.sampling: batch.rows must be a contiguous int32 tensor of shape [B]")
+        B = rows.numel()
+        if ends.dtype != torch.int64 or tuple(ends.shape) != (Ls, B) or not ends.is_contiguous():
+            raise ValueError(f"sast_amd.sampling: batch.ends_us must be a contiguous int64 tensor of shape [{Ls}, {B}]")
+        wcap = self.window_capacity if self.window_capacity is not None else cap
+        self.ws_bytes(Ls * B, wcap)             # ValueError for more windows than the histogram kernels take
+        dev = self.t.device
+        if rows.device != dev or ends.device != dev:
+            raise ValueError(f"sast_amd.sampling: the events live on {dev}, the batch on {rows.device}")
+        shape = (Ls, B) + self.get_shape()
+        if out_frames is None:
+            out_frames = torch.empty(shape, dtype=self.frame_dtype, device=dev)
+        elif out_frames.dtype != self.frame_dtype or tuple(out_frames.shape) != shape or not out_frames.is_contiguous() \
+                or out_frames.device != dev:
+            raise ValueError(f"sast_amd.sampling: out_frames must be a contiguous {str(self.frame_dtype).replace('torch.', '')} tensor of "
+                             f"shape {shape} on the events' device")
+        st = self._state
+        if Ls * B not in st["bounds"]:
+            _not_capturing("one un-captured warm-up call with the same batch size is needed before graph capture")
+            st["bounds"][Ls * B] = torch.empty(Ls * B, 2, dtype=torch.int64, device=dev)
+        bounds = st["bounds"][Ls * B]
+        L.check(L.lib().sast_rnd_window_bounds(self.t.data_ptr(), self.counts.data_ptr(), R, cap, rows.data_ptr(), ends.data_ptr(),
+                                                          B, Ls, self.mode, self.value, bounds.data_ptr(), _stream()),
+                "rnd_window_bounds")
+        self.launch([self.x, self.y, self.p, self.t], self._codes, R * cap, bounds, out_frames, self.err, wcap, clip_negative_polarity=True)
+        self.last_bounds = bounds
+        return out_frames
+
+    def labelled_pairs(self, items_host) -> int:
+        if self._host is None:
+            raise RuntimeError("sast_amd.sampling: call index() before labelled_pairs()")
+        if isinstance(items_host, torch.Tensor):
+            if items_host.is_cuda:
+                raise ValueError("sast_amd.sampling: labelled_pairs takes the items on the host (the draw is made there)")
+            items_host = items_host.numpy()
+        items = np.asarray(items_host, dtype=np.int64).reshape(-1)
+        cum, offset = self._host
+        if self._labelled is None:
+            lw = self.labels.labelled_windows()
+            self._labelled = (lw, [np.flatnonzero(w) for w in lw])
+        lw, f2w = self._labelled
+        Ls, K = self.sequence_length, 0
+        for g in items.tolist():
+            if not 0 <= g < cum[-1]:
+                continue
+            r = int(np.searchsorted(cum[1:], g, side="right"))
+            end = int(f2w[r][g - int(cum[r]) + int(offset[r])]) + 1
+            K += 1 if self.only_load_end_labels else int(lw[r][end - Ls:end].sum())
+        return K
