@@ -749,6 +749,54 @@ int sast_rnd_gather(const SastLabelArgs* a, const SastRndArgs* q, const int64_t*
                     int64_t* ends_us, float* labels, int32_t* counts, uint8_t* labelled, float* latest, int32_t* latest_count,
                     sast_stream_t stream);
 
+/* ---- streaming sampler (csrc/k_stream.hip): the streamed half of `sampling: 'mixed'` over the R = SastLabelArgs.S rows sast_labels_load
+ * has filled.  The reference does this on the CPU: _get_ev_repr_range_indices, SequenceForIter.get_sequences_with_guaranteed_labels,
+ * __init__ and __getitem__ (data/genx_utils/sequence_for_streaming.py:21-181) and the per-batch-row concatenations of
+ * ConcatStreamingDataPipe / ShardedStreamingDataPipe (data/utils/stream_concat_datapipe.py, stream_sharded_datapipe.py).  With
+ * f2w = frame_2_window[r][0 .. n_frames[r]) and L = sequence_length:  guarantee_labels = 1 -- a new sub-sequence begins at frame 0 and at
+ * every frame j with f2w[j] - f2w[j - 1] > L; sub-sequence (first frame a, last frame b) covers the windows
+ * [max(f2w[a] - L + 1, 0), f2w[b] + 1).  guarantee_labels = 0 -- one sequence per row, [max(f2w[0] - L + 1, 0), n_windows[r]).  A row
+ * without frames has no sequence.  Sequences are numbered row-major, in ascending window order inside a row; sequence s has
+ * seq_samples[s] = ceil((seq_stop[s] - seq_start[s]) / L) samples; step k of sample i is window seq_start[s] + i * L + k, padded when
+ * that window is >= seq_stop[s].  Every size is read on the device and every index clamped there; the grids are sized from R and B, no
+ * kernel waits for another workgroup and none keeps a word between calls, so the calls replay inside a graph.
+ * status bits (SastStreamArgs.status, int32 [1], pool-wide), cleared by sast_stream_index: */
+enum {
+  SAST_STREAM_TRUNCATED = 1,           /* more than max_sequences sequences: the table holds the first max_sequences */
+  SAST_STREAM_SCHEDULE_INDEX = 2       /* sast_stream_next met a schedule entry outside [0, n_seq): a fully padded sample, then skipped */
+};
+typedef struct SastStreamArgs {
+  int32_t* seq_row;          /* [max_sequences] the recording of a sequence */
+  int32_t* seq_start;        /* [max_sequences] its first window */
+  int32_t* seq_stop;         /* [max_sequences] one past its last window */
+  int32_t* seq_samples;      /* [max_sequences] */
+  int32_t* row_first_seq;    /* [R + 1]: row r's sequences are row_first_seq[r] .. row_first_seq[r + 1] - 1 */
+  int32_t* row_count;        /* [R]: scratch between the two launches of sast_stream_index; no initial contents needed */
+  int32_t* n_seq;            /* [1] */
+  int32_t* status;           /* [1] */
+  int32_t* order;            /* [B, order_capacity]: batch row b walks the sequences order[b][0 .. order_len[b]) (sast_stream_next only) */
+  int32_t* order_len;        /* [B] */
+  int32_t* cursor;           /* [B, 2]: (position in order[b], sample inside that sequence); zero starts the schedule */
+  int32_t sequence_length;   /* 1 .. 65535 */
+  int32_t guarantee_labels;  /* 0 / 1 */
+  int32_t max_sequences;     /* >= 1 */
+  int32_t order_capacity;    /* >= 1; B * order_capacity <= 2^31 - 1 */
+} SastStreamArgs;
+/* seq_row, seq_start, seq_stop, seq_samples, row_first_seq, n_seq.  More than max_sequences sequences: the first max_sequences are
+ * kept and SAST_STREAM_TRUNCATED is set.  2 launches, a workgroup per row: the rows' sequence counts; then every row sums the counts
+ * in front of it and writes its sequences.  order, order_len and cursor are not read. */
+int sast_stream_index(const SastLabelArgs* a, const SastStreamArgs* q, sast_stream_t stream);
+/* one sample per batch row b, at cursor[b], then cursor[b] moves on by one sample: rows / seq / sample int32 [B], is_first / exhausted
+ * uint8 [B], step_rows int32 [L, B] (the row on a real step, -1 on a padded one: the row map of sast_rnd_window_bounds with B' = L * B,
+ * T = 1), window_idx / ends_us int64 [L, B] (-1 on padded steps), labels fp32 [L, B, M, 7], counts int32 [L, B], labelled uint8 [L, B]
+ * (per real step what sast_labels_gather gives for that row and window; zeros on padded steps), is_padded uint8 [L, B].  A row whose
+ * schedule is used up: rows, seq, sample -1, is_first 0, exhausted 1, every step padded, the cursor stays.  A schedule entry outside
+ * [0, n_seq): the same with exhausted 0, SAST_STREAM_SCHEDULE_INDEX is set and the cursor moves to the next entry.  1 launch, a
+ * workgroup per batch row; no workgroup reads what another one writes. */
+int sast_stream_next(const SastLabelArgs* a, const SastStreamArgs* q, int B, int32_t* rows, int32_t* step_rows, int32_t* seq, int32_t* sample,
+                     uint8_t* is_first, uint8_t* exhausted, int64_t* window_idx, int64_t* ends_us, float* labels, int32_t* counts,
+                     uint8_t* labelled, uint8_t* is_padded, sast_stream_t stream);
+
 /* ---- spatial augmentation of event frames and box labels (csrc/k_augment.hip).  The reference augments on the CPU in its data-loader
  * workers: RandomSpatialAugmentorGenX.__call__ (data/utils/augmentor.py:347-364) -- horizontal flip, then zoom-in (:203-222) or zoom-out
  * (:134-153) -- with the label transforms of ObjectLabels (data/genx_utils/labels.py:255-339).  Both calls read the per-sample

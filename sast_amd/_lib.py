@@ -110,6 +110,11 @@ RND_MAX_CLASSES = 256
 SastRndArgs = _struct("SastRndArgs", [
     (P, "start_idx_offset length cum class_total weights status ticket"), (I32, "sequence_length only_load_end_labels max_classes weighted"),
 ])
+STREAM_TRUNCATED, STREAM_SCHEDULE_INDEX = 1, 2   # SAST_STREAM_*: the status bits of a StreamingPool (pool-wide)
+SastStreamArgs = _struct("SastStreamArgs", [
+    (P, "seq_row seq_start seq_stop seq_samples row_first_seq row_count n_seq status order order_len cursor"),
+    (I32, "sequence_length guarantee_labels max_sequences order_capacity"),
+])
 SastEvalArgs = _struct("SastEvalArgs", [
     (P, "labels counts det n_det"), (I32, "N M A K"), (F32, "min_diag2 min_side"), (I32, "max_images max_labels_per_frame"),
     (C.c_int64, "max_detections"),
@@ -207,6 +212,8 @@ _SIGNATURES = {
     "sast_labels_gather": (C.c_int, [C.POINTER(SastLabelArgs), P, C.c_int, P, P, P, P, P]),
     "sast_rnd_index": (C.c_int, [C.POINTER(SastLabelArgs), C.POINTER(SastRndArgs), P]),
     "sast_rnd_gather": (C.c_int, [C.POINTER(SastLabelArgs), C.POINTER(SastRndArgs), P, C.c_int] + [P] * 9),
+    "sast_stream_index": (C.c_int, [C.POINTER(SastLabelArgs), C.POINTER(SastStreamArgs), P]),
+    "sast_stream_next": (C.c_int, [C.POINTER(SastLabelArgs), C.POINTER(SastStreamArgs), C.c_int] + [P] * 13),
     "sast_augment_frames": (C.c_int, [P, P, P] + [C.c_int] * 5 + [P]),
     "sast_augment_labels": (C.c_int, [P, P, P] + [C.c_int] * 4 + [P, P, P, P]),
     "sast_eval_reset": (C.c_int, [C.POINTER(SastEvalArgs), P]),

@@ -1,0 +1,299 @@
+// Streamed training / evaluation sequences over R resident recordings (include/sast_hip.h, "streaming sampler").
+//
+// The reference builds them on the CPU: SequenceForIter.get_sequences_with_guaranteed_labels and _get_ev_repr_range_indices
+// (data/genx_utils/sequence_for_streaming.py:21-50, 86-111) cut a recording into sub-sequences wherever two label frames lie more than
+// sequence_length windows apart, SequenceForIter.__init__ / __getitem__ (:53-84, 137-181) chunk a sub-sequence into samples of
+// sequence_length windows and pad the last one, and ConcatStreamingDataPipe / ShardedStreamingDataPipe (data/utils/stream_*_datapipe.py)
+// walk every batch row through a list of sub-sequences, filling finished rows with get_fully_padded_sample (:120-132).  Here all of it
+// reads the state sast_labels_load left in device memory and a per-row schedule + cursor in device memory; every index is formed from
+// sizes read on the device and clamped before it is used, so nothing past a row's frames, windows or label rows is ever read,
+// whatever the schedule, the cursor or the sequence table hold.
+//
+// No kernel here waits for another workgroup and none keeps a ticket or a scratch word between calls: sast_stream_index is two
+// launches (a row's sequence count; every row's own prefix over those counts, then its compaction), sast_stream_next is one launch
+// whose workgroups each own one batch row's cursor.  All of them replay inside a graph.
+#include <climits>
+#include "common.cuh"
+#include "kernels.h"
+
+namespace sast {
+namespace {
+
+constexpr int STREAM_THREADS = 256;
+constexpr int STREAM_NEXT_THREADS = 128;
+
+__device__ __forceinline__ int stream_clamp(int v, int lo, int hi) { return min(max(v, lo), hi); }
+
+// frame_2_window[r][j] clamped into the row's windows
+__device__ __forceinline__ int stream_f2w(const long long* f2w, int j, int nw) {
+  return (int)min(max(f2w[j], 0LL), (long long)(nw - 1));
+}
+
+// frame j > 0 begins a new sub-sequence: np.diff(indices) > max_len (sequence_for_streaming.py:40)
+__device__ __forceinline__ bool stream_break(const long long* f2w, int j, int nw, int L) {
+  return stream_f2w(f2w, j, nw) - stream_f2w(f2w, j - 1, nw) > L;
+}
+
+// the sum of v over the workgroup (STREAM_THREADS threads); sh: STREAM_THREADS / 64 words.  Ends with a barrier, so sh may be reused.
+__device__ __forceinline__ int stream_block_sum(int v, int* sh) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+  if (lane == 0) sh[wave] = v;
+  __syncthreads();
+  int all = 0;
+#pragma unroll
+  for (int k = 0; k < STREAM_THREADS / 64; ++k) all += sh[k];
+  __syncthreads();
+  return all;
+}
+
+// the frames and windows of row r that the sequences are cut from: a row without frames or windows has none
+__device__ __forceinline__ void stream_row_sizes(const SastLabelArgs& a, int r, int& nf, int& nw) {
+  nf = stream_clamp(a.n_frames[r], 0, a.max_frames);
+  nw = stream_clamp(a.n_windows[r], 0, a.max_windows);
+  if (nw == 0) nf = 0;
+}
+
+// sast_stream_index, launch 1: workgroup r counts row r's sequences into row_count[r]
+__global__ __launch_bounds__(STREAM_THREADS) void stream_count_kernel(SastLabelArgs a, SastStreamArgs q) {
+  const int r = blockIdx.x, tid = threadIdx.x;
+  __shared__ int sh[STREAM_THREADS / 64];
+  int nf, nw;
+  stream_row_sizes(a, r, nf, nw);
+  const long long* f2w = reinterpret_cast<const long long*>(a.frame_2_window) + (size_t)r * a.max_frames;
+  int n = 0;
+  if (q.guarantee_labels)
+    for (int j = 1 + tid; j < nf; j += STREAM_THREADS) n += stream_break(f2w, j, nw, q.sequence_length) ? 1 : 0;
+  n = stream_block_sum(n, sh);
+  if (tid == 0) {
+    q.row_count[r] = nf > 0 ? n + 1 : 0;
+    if (r == 0) q.status[0] = 0;
+  }
+}
+
+// sast_stream_index, launch 2: workgroup r sums the counts of the rows before it (its first sequence), then writes its sequences in
+// ascending window order; the last workgroup also writes the total.  Sequence k of the row holds the frames between its k-th and
+// (k+1)-th break: the thread of the first frame writes the start, the thread of the last frame the stop, and after a barrier the
+// sample counts follow from both.
+__global__ __launch_bounds__(STREAM_THREADS) void stream_compact_kernel(SastLabelArgs a, SastStreamArgs q) {
+  const int r = blockIdx.x, tid = threadIdx.x, R = a.S, L = q.sequence_length, cap = q.max_sequences;
+  __shared__ int sh[STREAM_THREADS / 64];
+  __shared__ int sh_wave[STREAM_THREADS / 64];
+  long long before = 0;
+  {
+    int part = 0;                                             // R * max_frames <= INT_MAX: no partial sum overflows
+    for (int i = tid; i < r; i += STREAM_THREADS) part += stream_clamp(q.row_count[i], 0, a.max_frames);
+    before = stream_block_sum(part, sh);
+  }
+  int nf, nw;
+  stream_row_sizes(a, r, nf, nw);
+  const int mine = stream_clamp(q.row_count[r], 0, a.max_frames);
+  const int first = (int)min(before, (long long)cap);
+  if (tid == 0) {
+    q.row_first_seq[r] = first;
+    if (r == R - 1) {
+      const long long total = before + mine;
+      q.row_first_seq[R] = (int)min(total, (long long)cap);
+      q.n_seq[0] = (int)min(total, (long long)cap);
+      if (total > cap) atomicOr(&q.status[0], SAST_STREAM_TRUNCATED);
+    }
+  }
+  if (nf == 0) return;
+  const long long* f2w = reinterpret_cast<const long long*>(a.frame_2_window) + (size_t)r * a.max_frames;
+  const int room = cap - first;                               // sequences of this row that fit into the table
+  if (!q.guarantee_labels) {
+    if (tid == 0 && room > 0) {
+      const int start = max(stream_f2w(f2w, 0, nw) - L + 1, 0);
+      q.seq_row[first] = r;
+      q.seq_start[first] = start;
+      q.seq_stop[first] = nw;
+      q.seq_samples[first] = (nw - start + L - 1) / L;
+    }
+    return;
+  }
+  const int lane = tid & 63, wave = tid >> 6;
+  int carry = 0;                                              // breaks in front of this chunk of frames
+  for (int base = 0; base < nf; base += STREAM_THREADS) {
+    const int j = base + tid;
+    const int brk = (j >= 1 && j < nf && stream_break(f2w, j, nw, L)) ? 1 : 0;
+    int inc = brk;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const int o = __shfl_up(inc, d, 64);
+      if (lane >= d) inc += o;
+    }
+    if (lane == 63) sh_wave[wave] = inc;
+    __syncthreads();
+    int pre = 0, all = 0;
+#pragma unroll
+    for (int k = 0; k < STREAM_THREADS / 64; ++k) {
+      const int t = sh_wave[k];
+      if (k < wave) pre += t;
+      all += t;
+    }
+    __syncthreads();
+    if (j < nf) {
+      const int k = carry + pre + inc;                        // the sequence frame j lies in: the breaks at frames 1 .. j
+      if (k < room) {
+        const int w = stream_f2w(f2w, j, nw);
+        if (j == 0 || brk) {
+          q.seq_row[first + k] = r;
+          q.seq_start[first + k] = max(w - L + 1, 0);
+        }
+        if (j == nf - 1 || stream_break(f2w, j + 1, nw, L)) q.seq_stop[first + k] = w + 1;
+      }
+    }
+    carry += all;
+  }
+  __syncthreads();                                            // the starts and stops of this workgroup's sequences are written
+  const int n = min(mine, room);
+  for (int k = tid; k < n; k += STREAM_THREADS) {
+    const int start = q.seq_start[first + k], stop = q.seq_stop[first + k];
+    q.seq_samples[first + k] = (max(stop - start, 0) + L - 1) / L;
+  }
+}
+
+// sast_stream_next: workgroup b is batch row b
+__global__ __launch_bounds__(STREAM_NEXT_THREADS) void stream_next_kernel(
+    SastLabelArgs a, SastStreamArgs q, int B, int* rows_out, int* step_rows, int* seq_out, int* sample_out, unsigned char* is_first,
+    unsigned char* exhausted, long long* window_idx, long long* ends_out, float* labels, int* counts, unsigned char* labelled,
+    unsigned char* is_padded) {
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int R = a.S, L = q.sequence_length, M = a.max_labels_per_frame;
+  const int Mc = (int)min((long long)M, (long long)a.capacity);          // boxes one frame can hold: never more than the row's label rows
+  __shared__ int sh_row, sh_seq, sh_sample, sh_start, sh_stop, sh_done, sh_pos, sh_next_pos, sh_next_sample;
+  if (tid == 0) {
+    const int len = stream_clamp(q.order_len[b], 0, q.order_capacity);
+    const int nseq = stream_clamp(q.n_seq[0], 0, q.max_sequences);
+    const int pos = stream_clamp(q.cursor[2 * b], 0, len);
+    int sample = max(q.cursor[2 * b + 1], 0);
+    int row = -1, s = -1, start = 0, stop = 0, done = 0, next_pos = pos, next_sample = sample;
+    if (pos >= len) {
+      done = 1;                                               // get_fully_padded_sample: the cursor stays where it is
+      sample = -1;
+    } else {
+      s = q.order[(size_t)b * q.order_capacity + pos];
+      if (s < 0 || s >= nseq) {
+        atomicOr(&q.status[0], SAST_STREAM_SCHEDULE_INDEX);   // a fully padded sample, then the next entry
+        s = -1;
+        sample = -1;
+        next_pos = pos + 1;
+        next_sample = 0;
+      } else {
+        row = stream_clamp(q.seq_row[s], 0, R - 1);
+        const int nw = stream_clamp(a.n_windows[row], 0, a.max_windows);
+        start = stream_clamp(q.seq_start[s], 0, nw);
+        stop = stream_clamp(q.seq_stop[s], start, nw);
+        const int samples = max((stop - start + L - 1) / L, 1);
+        sample = min(sample, samples - 1);
+        if (sample + 1 < samples) {
+          next_sample = sample + 1;
+        } else {
+          next_pos = pos + 1;
+          next_sample = 0;
+        }
+      }
+    }
+    sh_row = row; sh_seq = s; sh_sample = sample; sh_start = start; sh_stop = stop; sh_done = done;
+    sh_pos = pos; sh_next_pos = next_pos; sh_next_sample = next_sample;
+  }
+  __syncthreads();
+  const int row = sh_row, sample = sh_sample;
+  // step k of sample i of a sequence is window start + i * L + k, padded from `stop` on
+  const long long w0 = row >= 0 ? (long long)sh_start + (long long)sample * L : 0;
+  const long long stop = row >= 0 ? sh_stop : 0;              // row < 0: every step is padded
+  const int rr = max(row, 0);
+  const int* w2f = a.window_2_frame + (size_t)rr * a.max_windows;
+  const int* fcount = a.frame_count + (size_t)rr * a.max_frames;
+  const int* fstart = a.frame_start + (size_t)rr * a.max_frames;
+  const long long* ends = reinterpret_cast<const long long*>(a.ends_us) + (size_t)rr * a.max_windows;
+  for (int k = tid; k < L; k += STREAM_NEXT_THREADS) {
+    const long long w = w0 + k;
+    const bool real = w < stop;
+    const size_t o = (size_t)k * B + b;
+    int cnt = 0, lab = 0;
+    if (real) {
+      const int f = w2f[w];
+      if (f >= 0 && f < a.max_frames) {
+        lab = 1;
+        cnt = stream_clamp(fcount[f], 0, Mc);
+      }
+    }
+    step_rows[o] = real ? row : -1;
+    window_idx[o] = real ? w : -1;
+    ends_out[o] = real ? ends[w] : -1;
+    counts[o] = cnt;
+    labelled[o] = (unsigned char)lab;
+    is_padded[o] = real ? 0 : 1;
+  }
+  for (int k = 0; k < L; ++k) {
+    const long long w = w0 + k;
+    int cnt = 0, start = 0;
+    if (w < stop) {
+      const int f = w2f[w];
+      if (f >= 0 && f < a.max_frames) {
+        cnt = stream_clamp(fcount[f], 0, Mc);
+        start = stream_clamp(fstart[f], 0, (int)a.capacity - cnt);
+      }
+    }
+    const float* src = a.labels + ((size_t)rr * a.capacity + start) * 7;
+    float* out = labels + ((size_t)k * B + b) * M * 7;
+    for (int i = tid; i < M * 7; i += STREAM_NEXT_THREADS) out[i] = i < cnt * 7 ? src[i] : 0.f;
+  }
+  if (tid == 0) {
+    rows_out[b] = row;
+    seq_out[b] = sh_seq;
+    sample_out[b] = sample;
+    is_first[b] = row >= 0 && sample == 0 ? 1 : 0;
+    exhausted[b] = (unsigned char)sh_done;
+    q.cursor[2 * b] = sh_next_pos;
+    q.cursor[2 * b + 1] = sh_next_sample;
+  }
+}
+
+bool stream_label_args(const SastLabelArgs* a) {
+  return a && a->ends_us && a->n_windows && a->n_frames && a->frame_2_window && a->window_2_frame && a->labels && a->frame_start &&
+         a->frame_count && a->S >= 1 && a->S <= 65535 && a->capacity >= 1 && (long long)a->S * a->capacity <= INT_MAX / 16 &&
+         a->max_frames >= 1 && a->max_windows >= 1 && a->max_labels_per_frame >= 1 && (long long)a->S * a->max_frames <= INT_MAX &&
+         (long long)a->S * a->max_windows <= INT_MAX;
+}
+
+bool stream_args(const SastStreamArgs* q) {
+  return q && q->seq_row && q->seq_start && q->seq_stop && q->seq_samples && q->row_first_seq && q->row_count && q->n_seq && q->status &&
+         q->sequence_length >= 1 && q->sequence_length <= 65535 && q->max_sequences >= 1 &&
+         (q->guarantee_labels == 0 || q->guarantee_labels == 1);
+}
+}  // namespace
+}  // namespace sast
+
+extern "C" {
+
+int sast_stream_index(const SastLabelArgs* a, const SastStreamArgs* q, sast_stream_t stream) {
+  SAST_ENTRY();
+  if (!sast::stream_label_args(a) || !sast::stream_args(q)) return SAST_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  SAST_LAUNCH(sast::stream_count_kernel, dim3((unsigned)a->S), dim3(sast::STREAM_THREADS), 0, st, *a, *q);
+  SAST_LAUNCH(sast::stream_compact_kernel, dim3((unsigned)a->S), dim3(sast::STREAM_THREADS), 0, st, *a, *q);
+  SAST_CHECK_LAUNCH();
+  return SAST_OK;
+}
+
+int sast_stream_next(const SastLabelArgs* a, const SastStreamArgs* q, int B, int32_t* rows, int32_t* step_rows, int32_t* seq, int32_t* sample,
+                     uint8_t* is_first, uint8_t* exhausted, int64_t* window_idx, int64_t* ends_us, float* labels, int32_t* counts,
+                     uint8_t* labelled, uint8_t* is_padded, sast_stream_t stream) {
+  SAST_ENTRY();
+  if (!sast::stream_label_args(a) || !sast::stream_args(q) || !q->order || !q->order_len || !q->cursor || q->order_capacity < 1 ||
+      !rows || !step_rows || !seq || !sample || !is_first || !exhausted || !window_idx || !ends_us || !labels || !counts || !labelled ||
+      !is_padded || B < 1 || B > 65535)
+    return SAST_EINVAL;
+  if ((long long)B * q->order_capacity > INT_MAX) return SAST_EINVAL;
+  if ((long long)B * q->sequence_length * a->max_labels_per_frame > INT_MAX / 8) return SAST_EINVAL;
+  SAST_LAUNCH(sast::stream_next_kernel, dim3((unsigned)B), dim3(sast::STREAM_NEXT_THREADS), 0, (hipStream_t)stream, *a, *q, B, rows,
+              step_rows, seq, sample, is_first, exhausted, reinterpret_cast<long long*>(window_idx), reinterpret_cast<long long*>(ends_us),
+              labels, counts, labelled, is_padded);
+  SAST_CHECK_LAUNCH();
+  return SAST_OK;
+}
+
+}  // extern "C"

@@ -95,4 +95,6 @@ int mswsa_fused_fwd_launch(const SastMswsaArgs* a, const float* planes, hipStrea
 
 // k_labels.hip: the label front end has no internal launchers either, only the sast_labels_* entry points
 
+// k_sampler.hip, k_stream.hip: the random-access and the streaming sampler have none either, only sast_rnd_* / sast_stream_*
+
 }  // namespace sast

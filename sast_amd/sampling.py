@@ -18,6 +18,11 @@ The draws stay on the host, as the augmentor's do, with the calls torch's sample
     n, _ = pool.index(weighted=True)
     items = torch.multinomial(pool.weights[:n].cpu(), n, replacement=True)     # WeightedRandomSampler
 
+`StreamingPool` is the first half for the same resident recordings (csrc/k_stream.hip): the sub-sequences of
+`SequenceForIter.get_sequences_with_guaranteed_labels`, their samples of `sequence_length` windows with the padded tail, and the
+per-batch-row concatenations of `ConcatStreamingDataPipe` (train) / `ShardedStreamingDataPipe` (val / test), walked by a cursor in
+device memory so that a captured step is simply replayed to move along the streams.  Its draws stay torch's too (`concat_orders`).
+
 There is no CPU path: CPU tensors raise the library's "no CPU fallback" error.
 """
 from __future__ import annotations
@@ -36,6 +41,9 @@ from .labels import LabelStreams
 # status bits (include/sast_hip.h, SAST_RND_*): per row, then pool-wide
 ROW_FLAGS = ((L.RND_CLASS_ID, "class_id", "a box of a counted label frame has a class id outside [0, max_classes); it was left out"),)
 POOL_FLAGS = ((L.RND_ITEM_INDEX, "item_index", "batch() was given an item outside [0, N)"),)
+# status bits of a StreamingPool (SAST_STREAM_*): pool-wide
+STREAM_FLAGS = ((L.STREAM_TRUNCATED, "truncated", "more than max_sequences sequences; the table holds the first max_sequences"),
+                (L.STREAM_SCHEDULE_INDEX, "schedule_index", "next() met a schedule entry outside [0, n_seq); it gave a fully padded sample"))
 
 
 class RandomAccessBatch(NamedTuple):
@@ -50,7 +58,93 @@ class RandomAccessBatch(NamedTuple):
     latest_count: torch.Tensor    # int32 [B]
 
 
-class RandomAccessPool(_Windowed):
+class _PoolEvents(_Windowed):
+    """what `RandomAccessPool` and `StreamingPool` share: the resident event columns of R recordings with their timestamps corrected
+    once (`load_events`), and the frames of windows that are found through a row map (`_mapped_frames`)"""
+
+    _events = None             # another pool whose columns, corrected timestamps and counts this one reads (StreamingPool(events=))
+
+    # ---- events
+    def load_events(self, x: torch.Tensor, y: torch.Tensor, p: torch.Tensor, t: torch.Tensor, counts: torch.Tensor,
+                    reset: Optional[torch.Tensor] = None) -> None:
+        if self._events is not None:
+            raise RuntimeError("sast_amd.sampling: this pool reads the events of the pool given as events=; load them there")
+        R = self.num_rows
+        cols = [x, y, p, t]
+        for c, name in zip(cols, ("x", "y", "p", "t")):
+            if c.dim() != 2 or c.shape[0] != R:
+                raise ValueError(f"sast_amd.sampling: {name} must be [rows={R}, capacity], got shape {tuple(c.shape)}")
+            if not c.is_contiguous():
+                raise ValueError(f"sast_amd.sampling: {name} must be contiguous")
+        if not x.shape == y.shape == p.shape == t.shape:
+            raise ValueError("sast_amd.sampling: x, y, p and t must have the same shape")
+        codes = [_dtype_code(x, "x"), _dtype_code(y, "y"), _dtype_code(p, "p"), _dtype_code(t, "t", (torch.int64, torch.int32))]
+        if counts.dtype != torch.int64 or tuple(counts.shape) != (R,) or not counts.is_contiguous():
+            raise ValueError(f"sast_amd.sampling: counts must be a contiguous int64 tensor of shape [{R}]")
+        if reset is not None and (reset.dtype not in (torch.uint8, torch.bool) or tuple(reset.shape) != (R,) or not reset.is_contiguous()):
+            raise ValueError(f"sast_amd.sampling: reset must be a contiguous uint8 or bool tensor of shape [{R}]")
+        cap = x.shape[1]
+        if cap < 1 or R * cap > 2 ** 31 - 1:
+            raise ValueError("sast_amd.sampling: capacity must be >= 1 and rows * capacity below 2^31")
+        _need_gpu(x, y, p, t, counts, reset)
+        dev = x.device
+        if len({c.device for c in cols + [counts] + ([reset] if reset is not None else [])}) != 1:
+            raise ValueError("sast_amd.sampling: x, y, p, t, counts and reset must be on the same device")
+        if self.t is None or self.t.device != dev or self.t.shape[1] != cap:
+            _not_capturing()
+            self.t = torch.zeros(R, cap, dtype=torch.int64, device=dev)
+            self.counts = torch.zeros(R, dtype=torch.int64, device=dev)
+            self.t_last = None
+            self._carry(dev, (R,))
+            self._state = {"scan": torch.empty(int(L.lib().sast_evstreams_ws_count(R)), dtype=torch.int64, device=dev),
+                           "ones": torch.ones(R, dtype=torch.uint8, device=dev), "bounds": {}}
+            if reset is not None:
+                reset = None           # nothing to keep: every row is new
+        st = self._state
+        if reset is None:
+            now, flags = counts, st["ones"]
+            self.counts.copy_(counts)
+        else:
+            keep = reset == 0
+            now, flags = counts.masked_fill(keep, 0), reset          # a row that is kept: no event, so nothing of it is rewritten
+            self.counts.copy_(torch.where(keep, self.counts, counts))
+        L.check(L.lib().sast_evstreams_correct_time(t.data_ptr(), codes[3], now.data_ptr(), R, cap, self.t.data_ptr(), self.t_last.data_ptr(),
+                                                    flags.data_ptr(), st["scan"].data_ptr(), _stream()), "evstreams_correct_time")
+        self.x, self.y, self.p = x, y, p
+        self._codes = codes[:3] + [L.DT_I64]
+
+    def frame_errors(self) -> Tuple[int, int]:
+        """(invalid events, windows over capacity) of the frames calls since the pool was made (synchronises)"""
+        return _Windowed.errors(self)
+
+    def _mapped_frames(self, src, row_map: torch.Tensor, cols: int, T: int, ends: torch.Tensor, shape, out_frames):
+        """the frames of the T * cols windows ends[k, c] searched in row row_map[c] of `src`'s events (1 + 4 launches)"""
+        R, cap = self.num_rows, src.t.shape[1]
+        wcap = self.window_capacity if self.window_capacity is not None else cap
+        self.ws_bytes(T * cols, wcap)             # ValueError for more windows than the histogram kernels take
+        dev = src.t.device
+        if row_map.device != dev or ends.device != dev:
+            raise ValueError(f"sast_amd.sampling: the events live on {dev}, the batch on {row_map.device}")
+        if out_frames is None:
+            out_frames = torch.empty(shape, dtype=self.frame_dtype, device=dev)
+        elif out_frames.dtype != self.frame_dtype or tuple(out_frames.shape) != shape or not out_frames.is_contiguous() \
+                or out_frames.device != dev:
+            raise ValueError(f"sast_amd.sampling: out_frames must be a contiguous {str(self.frame_dtype).replace('torch.', '')} tensor of "
+                             f"shape {shape} on the events' device")
+        st = self._state
+        if T * cols not in st["bounds"]:
+            _not_capturing("one un-captured warm-up call with the same batch size is needed before graph capture")
+            st["bounds"][T * cols] = torch.empty(T * cols, 2, dtype=torch.int64, device=dev)
+        bounds = st["bounds"][T * cols]
+        L.check(L.lib().sast_rnd_window_bounds(src.t.data_ptr(), src.counts.data_ptr(), R, cap, row_map.data_ptr(), ends.data_ptr(),
+                                                          cols, T, self.mode, self.value, bounds.data_ptr(), _stream()),
+                "rnd_window_bounds")
+        self.launch([src.x, src.y, src.p, src.t], src._codes, R * cap, bounds, out_frames, self.err, wcap, clip_negative_polarity=True)
+        self.last_bounds = bounds
+        return out_frames
+
+
+class RandomAccessPool(_PoolEvents):
     """pool = RandomAccessPool(labels, height, width, sequence_length=L, only_load_end_labels=False, bins=10, count_cutoff=10,
                                fastmode=True, duration_us=50_000, downsample_by_2=False, representation="stacked_histogram",
                                window_capacity=None, max_classes=16)
@@ -121,57 +215,6 @@ class RandomAccessPool(_Windowed):
         self._args = None
         self._host = None          # (cum [R + 1], start_idx_offset [R]) as numpy, from the last index()
         self._labelled = None      # labels.labelled_windows() of that index, and per row the window of every label frame
-
-    # ---- events
-    def load_events(self, x: torch.Tensor, y: torch.Tensor, p: torch.Tensor, t: torch.Tensor, counts: torch.Tensor,
-                    reset: Optional[torch.Tensor] = None) -> None:
-        R = self.num_rows
-        cols = [x, y, p, t]
-        for c, name in zip(cols, ("x", "y", "p", "t")):
-            if c.dim() != 2 or c.shape[0] != R:
-                raise ValueError(f"sast_amd.sampling: {name} must be [rows={R}, capacity], got shape {tuple(c.shape)}")
-            if not c.is_contiguous():
-                raise ValueError(f"sast_amd.sampling: {name} must be contiguous")
-        if not x.shape == y.shape == p.shape == t.shape:
-            raise ValueError("sast_amd.sampling: x, y, p and t must have the same shape")
-        codes = [_dtype_code(x, "x"), _dtype_code(y, "y"), _dtype_code(p, "p"), _dtype_code(t, "t", (torch.int64, torch.int32))]
-        if counts.dtype != torch.int64 or tuple(counts.shape) != (R,) or not counts.is_contiguous():
-            raise ValueError(f"sast_amd.sampling: counts must be a contiguous int64 tensor of shape [{R}]")
-        if reset is not None and (reset.dtype not in (torch.uint8, torch.bool) or tuple(reset.shape) != (R,) or not reset.is_contiguous()):
-            raise ValueError(f"sast_amd.sampling: reset must be a contiguous uint8 or bool tensor of shape [{R}]")
-        cap = x.shape[1]
-        if cap < 1 or R * cap > 2 ** 31 - 1:
-            raise ValueError("sast_amd.sampling: capacity must be >= 1 and rows * capacity below 2^31")
-        _need_gpu(x, y, p, t, counts, reset)
-        dev = x.device
-        if len({c.device for c in cols + [counts] + ([reset] if reset is not None else [])}) != 1:
-            raise ValueError("sast_amd.sampling: x, y, p, t, counts and reset must be on the same device")
-        if self.t is None or self.t.device != dev or self.t.shape[1] != cap:
-            _not_capturing()
-            self.t = torch.zeros(R, cap, dtype=torch.int64, device=dev)
-            self.counts = torch.zeros(R, dtype=torch.int64, device=dev)
-            self.t_last = None
-            self._carry(dev, (R,))
-            self._state = {"scan": torch.empty(int(L.lib().sast_evstreams_ws_count(R)), dtype=torch.int64, device=dev),
-                           "ones": torch.ones(R, dtype=torch.uint8, device=dev), "bounds": {}}
-            if reset is not None:
-                reset = None           # nothing to keep: every row is new
-        st = self._state
-        if reset is None:
-            now, flags = counts, st["ones"]
-            self.counts.copy_(counts)
-        else:
-            keep = reset == 0
-            now, flags = counts.masked_fill(keep, 0), reset          # a row that is kept: no event, so nothing of it is rewritten
-            self.counts.copy_(torch.where(keep, self.counts, counts))
-        L.check(L.lib().sast_evstreams_correct_time(t.data_ptr(), codes[3], now.data_ptr(), R, cap, self.t.data_ptr(), self.t_last.data_ptr(),
-                                                    flags.data_ptr(), st["scan"].data_ptr(), _stream()), "evstreams_correct_time")
-        self.x, self.y, self.p = x, y, p
-        self._codes = codes[:3] + [L.DT_I64]
-
-    def frame_errors(self) -> Tuple[int, int]:
-        """(invalid events, windows over capacity) of the frames calls since the pool was made (synchronises)"""
-        return _Windowed.errors(self)
 
     # ---- the item index
     def _storage(self, dev):
@@ -260,29 +303,7 @@ class RandomAccessPool(_Windowed):
         B = rows.numel()
         if ends.dtype != torch.int64 or tuple(ends.shape) != (Ls, B) or not ends.is_contiguous():
             raise ValueError(f"sast_amd.sampling: batch.ends_us must be a contiguous int64 tensor of shape [{Ls}, {B}]")
-        wcap = self.window_capacity if self.window_capacity is not None else cap
-        self.ws_bytes(Ls * B, wcap)             # ValueError for more windows than the histogram kernels take
-        dev = self.t.device
-        if rows.device != dev or ends.device != dev:
-            raise ValueError(f"sast_amd.sampling: the events live on {dev}, the batch on {rows.device}")
-        shape = (Ls, B) + self.get_shape()
-        if out_frames is None:
-            out_frames = torch.empty(shape, dtype=self.frame_dtype, device=dev)
-        elif out_frames.dtype != self.frame_dtype or tuple(out_frames.shape) != shape or not out_frames.is_contiguous() \
-                or out_frames.device != dev:
-            raise ValueError(f"sast_amd.sampling: out_frames must be a contiguous {str(self.frame_dtype).replace('torch.', '')} tensor of "
-                             f"shape {shape} on the events' device")
-        st = self._state
-        if Ls * B not in st["bounds"]:
-            _not_capturing("one un-captured warm-up call with the same batch size is needed before graph capture")
-            st["bounds"][Ls * B] = torch.empty(Ls * B, 2, dtype=torch.int64, device=dev)
-        bounds = st["bounds"][Ls * B]
-        L.check(L.lib().sast_rnd_window_bounds(self.t.data_ptr(), self.counts.data_ptr(), R, cap, rows.data_ptr(), ends.data_ptr(),
-                                                          B, Ls, self.mode, self.value, bounds.data_ptr(), _stream()),
-                "rnd_window_bounds")
-        self.launch([self.x, self.y, self.p, self.t], self._codes, R * cap, bounds, out_frames, self.err, wcap, clip_negative_polarity=True)
-        self.last_bounds = bounds
-        return out_frames
+        return self._mapped_frames(self, rows, B, Ls, ends, (Ls, B) + self.get_shape(), out_frames)
 
     def labelled_pairs(self, items_host) -> int:
         if self._host is None:
@@ -305,3 +326,316 @@ class RandomAccessPool(_Windowed):
             end = int(f2w[r][g - int(cum[r]) + int(offset[r])]) + 1
             K += 1 if self.only_load_end_labels else int(lw[r][end - Ls:end].sum())
         return K
+
+
+class StreamingBatch(NamedTuple):
+    """what `StreamingPool.next` returns (L = sequence_length, M = the labels' max_labels_per_frame)"""
+    rows: torch.Tensor            # int32 [B]: the pool row (recording) of every batch row, -1: exhausted or a bad schedule entry
+    step_rows: torch.Tensor       # int32 [L, B]: `rows` on a real step, -1 on a padded one (the row map of the frames)
+    seq: torch.Tensor             # int32 [B]: the sequence, -1 as for rows
+    sample: torch.Tensor          # int32 [B]: the sample inside the sequence, -1 as for rows
+    is_first: torch.Tensor        # uint8 [B]: sample == 0 (reset the recurrent states of this row)
+    exhausted: torch.Tensor       # uint8 [B]: the row's schedule is used up
+    window_idx: torch.Tensor      # int64 [L, B], -1 on padded steps
+    ends_us: torch.Tensor         # int64 [L, B], -1 on padded steps
+    labels: torch.Tensor          # fp32 [L, B, M, 7]
+    counts: torch.Tensor          # int32 [L, B]
+    labelled: torch.Tensor        # uint8 [L, B]
+    is_padded: torch.Tensor       # uint8 [L, B]
+
+
+class StreamingPlan(NamedTuple):
+    """what `StreamingPool.plan` returns, host arrays over the steps('longest') steps of the schedule"""
+    K: np.ndarray                 # int64 [n_steps]: labelled (step, sample) pairs of the batch
+    is_first: np.ndarray          # bool [n_steps, B]
+    seq: np.ndarray               # int32 [n_steps, B], -1: the row is exhausted
+
+
+def _pyramid(n: int):
+    """ShardedStreamingDataPipe.yield_pyramid_indices(0, n): 0 .. n-1, n-1 .. 0, 0 .. n-1, ..."""
+    while True:
+        yield from range(n)
+        yield from range(n - 1, -1, -1)
+
+
+class StreamingPool(_PoolEvents):
+    """pool = StreamingPool(labels, height, width, sequence_length=L, guarantee_labels=True, events=None, max_sequences=None,
+                            order_capacity=None, bins=10, count_cutoff=10, fastmode=True, duration_us=50_000, downsample_by_2=False,
+                            representation="stacked_histogram", window_capacity=None)
+    pool.load_events(x, y, p, t, counts, reset=None)          (not with events=)
+    n_seq, sequences = pool.index(check=False)
+    pool.set_schedule(pool.concat_orders(B))                  or pool.sharded_orders(B, total_num_workers, global_worker_id)
+    K, is_first, seq = pool.plan(); pool.steps('shortest' | 'longest')
+    out = pool.next(out=None)
+    frames = pool.frames(out, out_frames=None)
+    pool.errors(); pool.frame_errors()
+
+    labels: a `LabelStreams` of R rows, as for `RandomAccessPool`; the geometry arguments are `EventStreams`'.
+    guarantee_labels: True -- the training split: `SequenceForIter.get_sequences_with_guaranteed_labels`, a recording is cut wherever
+      two label frames lie more than L windows apart; False -- validation / test: one sequence per recording, from L - 1 windows before
+      its first label frame to its last window.
+    events: a `RandomAccessPool` or `StreamingPool` over the same R rows whose `load_events` columns, corrected timestamps and counts
+      this pool reads by reference: in mixed mode the recordings are loaded and time-corrected once.  Without it `load_events` is
+      `RandomAccessPool.load_events` (2 launches).
+    index: after `labels.load`.  Device state: seq_row, seq_start, seq_stop, seq_samples int32 [max_sequences] (default R * max_frames
+      with guarantee_labels, else R), row_first_seq int32 [R + 1], n_seq int32 [1].  Sequences are numbered row-major, in ascending
+      window order inside a row (`datapipes.extend(new_datapipes)` over the recordings); a row without frames (a flagged row of
+      `LabelStreams`) has none.  Returns n_seq and `sequences`, numpy int32 [n_seq, 4] = (row, start, stop, samples), through ONE
+      synchronising copy that also brings the host mirrors `plan` needs.  2 launches.  It clears the status words; check=True raises
+      ValueError naming the status bits.
+    concat_orders / sharded_orders: host only -- B lists of sequence ids.  concat: B times `torch.randperm(n_seq)`, drawn in batch-row
+      order (`ConcatStreamingDataPipe._get_zipped_streams`).  sharded: `ShardedStreamingDataPipe` -- the stable long-to-short sort by
+      samples, the pyramid deal to workers, the second sort, the pyramid deal to batch rows; ValueError where the reference asserts.
+    set_schedule: B sequences of ids, validated on the host against n_seq and order_capacity (default max_sequences) -> order int32
+      [B, order_capacity], order_len int32 [B] and zeroed cursors int32 [B, 2] by stream-ordered copies into tensors that keep their
+      place while B stays the same (a captured `next` follows a new schedule).
+    plan: host only, no sync -- per step K (section 3f's K), is_first [n_steps, B] and seq [n_steps, B] over steps('longest') steps.
+      steps('shortest'): the training Zipper (the epoch ends when the first row runs out); steps('longest'): ZipperLongest.
+    next: -> `StreamingBatch`, then every row's cursor moves on by one sample.  Sample i of sequence s: step k is window
+      seq_start[s] + i * L + k, padded from seq_stop[s] on.  labels / counts / ends_us / labelled of a real step are what
+      `LabelStreams.labels` gives for row rows[b] at window_idx[k, b]; a padded step has window_idx and ends_us -1, zeros elsewhere and
+      is_padded 1 (the reference puts None and the padding representation there).  A row whose schedule is used up gives
+      get_fully_padded_sample: rows -1, is_first 0, exhausted 1, every step padded, and its cursor stays.  A schedule entry outside
+      [0, n_seq) (only a schedule written past set_schedule can hold one) gives the same with exhausted 0, sets schedule_index and is
+      skipped.  1 launch, a workgroup per batch row.
+    frames: [L, B, C, H', W'] uint8 (int8 for mixed_density): a real step is byte for byte what `EventStreams` gives for that row and
+      window end; a padded step is all zero whatever the timestamps are (its row in the row map is -1).  5 launches.
+    After one un-captured call of next and frames with the same B nothing is allocated but the outputs and nothing synchronises:
+    next + frames (+ augmentor + step) are captured in one graph, and every replay advances the streams.
+    Limits: the pool covers the resident recordings only; R * cap must stay below 2^31."""
+
+    LOAD_EVENTS_LAUNCHES = 2
+    INDEX_LAUNCHES = 2
+    NEXT_LAUNCHES = 1
+    FRAMES_LAUNCHES = 5
+
+    def __init__(self, labels: LabelStreams, height: int, width: int, sequence_length: int, guarantee_labels: bool = True,
+                 events: Optional[_PoolEvents] = None, max_sequences: Optional[int] = None, order_capacity: Optional[int] = None,
+                 bins: int = 10, count_cutoff: Optional[int] = 10, fastmode: bool = True, duration_us: int = 50_000,
+                 downsample_by_2: bool = False, representation: str = "stacked_histogram", window_capacity: Optional[int] = None):
+        if not isinstance(labels, LabelStreams):
+            raise TypeError("sast_amd.sampling: labels must be a LabelStreams")
+        if events is not None and not isinstance(events, _PoolEvents):
+            raise TypeError("sast_amd.sampling: events must be a RandomAccessPool or a StreamingPool")
+        if duration_us is None:
+            raise ValueError("sast_amd.sampling: duration_us is required (the windows of a label schedule are duration windows)")
+        super().__init__(bins, height, width, count_cutoff, fastmode, downsample_by_2, representation, duration_us, None, True,
+                         window_capacity)
+        if isinstance(sequence_length, bool) or not isinstance(sequence_length, int) or not 1 <= sequence_length <= 65535:
+            raise ValueError("sast_amd.sampling: sequence_length must be an int in 1 .. 65535")
+        if bool(labels.downsample_by_2) != bool(downsample_by_2):
+            raise ValueError("sast_amd.sampling: labels.downsample_by_2 and downsample_by_2 must agree")
+        R = labels.num_streams
+        if events is not None and events.num_rows != R:
+            raise ValueError(f"sast_amd.sampling: events holds {events.num_rows} rows, the labels {R}")
+        if max_sequences is None:
+            max_sequences = R * labels.max_frames if guarantee_labels else R
+        if isinstance(max_sequences, bool) or not isinstance(max_sequences, int) or not 1 <= max_sequences <= 2 ** 31 - 1:
+            raise ValueError("sast_amd.sampling: max_sequences must be an int in 1 .. 2^31 - 1")
+        if order_capacity is None:
+            order_capacity = max_sequences
+        if isinstance(order_capacity, bool) or not isinstance(order_capacity, int) or not 1 <= order_capacity <= 2 ** 31 - 1:
+            raise ValueError("sast_amd.sampling: order_capacity must be an int in 1 .. 2^31 - 1")
+        self.labels = labels
+        self.num_rows = R
+        self.sequence_length, self.guarantee_labels = sequence_length, bool(guarantee_labels)
+        self.max_sequences, self.order_capacity = max_sequences, order_capacity
+        while events is not None and events._events is not None:          # a pool that shares itself: read its source
+            events = events._events
+        self._events = events
+        self.x = self.y = self.p = self.t = self.counts = None
+        self._codes = None
+        self.seq_row = self.seq_start = self.seq_stop = self.seq_samples = self.row_first_seq = self.n_seq = self.status = None
+        self.order = self.order_len = self.cursor = None
+        self._args = None
+        self._host = None          # (sequences [n_seq, 4], per row the labelled windows) as numpy, from the last index()
+        self._orders = None        # the schedule of the last set_schedule()
+
+    # ---- the sequence table
+    def _storage(self, dev):
+        if self._args is None:
+            _not_capturing()
+            R, n = self.num_rows, self.max_sequences
+            self._table = torch.zeros(4, n, dtype=torch.int32, device=dev)
+            self.seq_row, self.seq_start, self.seq_stop, self.seq_samples = self._table.unbind(0)
+            self.row_first_seq = torch.zeros(R + 1, dtype=torch.int32, device=dev)
+            self._row_count = torch.zeros(R, dtype=torch.int32, device=dev)
+            self._head = torch.zeros(2, dtype=torch.int32, device=dev)          # n_seq, status: one word each, fetched together
+            self.n_seq, self.status = self._head[0:1], self._head[1:2]
+            a = self._args = L.SastStreamArgs()
+            a.seq_row, a.seq_start, a.seq_stop, a.seq_samples = (t.data_ptr() for t in self._table.unbind(0))
+            a.row_first_seq, a.row_count = self.row_first_seq.data_ptr(), self._row_count.data_ptr()
+            a.n_seq, a.status = self.n_seq.data_ptr(), self.status.data_ptr()
+            a.sequence_length, a.guarantee_labels = self.sequence_length, int(self.guarantee_labels)
+            a.max_sequences, a.order_capacity = self.max_sequences, self.order_capacity
+        return self._args
+
+    def index(self, check: bool = False) -> Tuple[int, np.ndarray]:
+        ls = self.labels
+        if ls._args is None:
+            raise RuntimeError("sast_amd.sampling: call labels.load() before index()")
+        a = self._storage(ls.status.device)
+        L.check(L.lib().sast_stream_index(C.byref(ls._args), C.byref(a), _stream()), "stream_index")
+        R, n_max = self.num_rows, self.max_sequences
+        both = torch.cat([self._head, self._table.reshape(-1), ls.n_windows, ls.window_2_frame.reshape(-1)]).cpu().numpy()
+        n, status = int(both[0]), int(both[1])
+        table = both[2:2 + 4 * n_max].reshape(4, n_max)
+        rest = both[2 + 4 * n_max:]
+        n_windows, w2f = rest[:R], rest[R:].reshape(R, ls.max_windows)
+        sequences = np.ascontiguousarray(table[:, :n].T)
+        self._host = (sequences, [w2f[r, :int(n_windows[r])] >= 0 for r in range(R)])
+        self._orders = None
+        if check and status:
+            raise ValueError("sast_amd.sampling: " + "; ".join(f"{name}: {msg}" for bit, name, msg in STREAM_FLAGS if status & bit))
+        return n, sequences
+
+    def errors(self) -> Tuple[str, ...]:
+        """the names of the pool's status bits (synchronises)"""
+        if self.status is None:
+            return ()
+        v = int(self.status.item())
+        return tuple(n for bit, n, _m in STREAM_FLAGS if v & bit)
+
+    # ---- schedules (host only)
+    def _sequences(self) -> np.ndarray:
+        if self._host is None:
+            raise RuntimeError("sast_amd.sampling: call index() before the schedule methods")
+        return self._host[0]
+
+    def concat_orders(self, batch_size: int) -> List[List[int]]:
+        n = len(self._sequences())
+        if isinstance(batch_size, bool) or not isinstance(batch_size, int) or batch_size < 1:
+            raise ValueError("sast_amd.sampling: batch_size must be an int >= 1")
+        return [torch.randperm(n).tolist() for _ in range(batch_size)]
+
+    def sharded_orders(self, batch_size: int, total_num_workers: int = 1, global_worker_id: int = 0) -> List[List[int]]:
+        samples = self._sequences()[:, 3].tolist()
+        for v, name in ((batch_size, "batch_size"), (total_num_workers, "total_num_workers")):
+            if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+                raise ValueError(f"sast_amd.sampling: {name} must be an int >= 1")
+        if not len(samples) >= total_num_workers > global_worker_id >= 0:
+            raise ValueError(f"sast_amd.sampling: {len(samples)} sequences for {total_num_workers} workers (worker {global_worker_id}): "
+                             "every worker needs a sequence")
+        ids = sorted(range(len(samples)), key=lambda s: samples[s], reverse=True)        # stable: long to short
+        mine = [s for s, w in zip(ids, _pyramid(total_num_workers)) if w == global_worker_id]
+        if len(mine) < batch_size:
+            raise ValueError(f"sast_amd.sampling: worker {global_worker_id} gets {len(mine)} sequences, fewer than batch_size = "
+                             f"{batch_size}; decrease the number of workers")
+        mine = sorted(mine, key=lambda s: samples[s], reverse=True)
+        rows: List[List[int]] = [[] for _ in range(batch_size)]
+        for s, b in zip(mine, _pyramid(batch_size)):
+            rows[b].append(s)
+        return rows
+
+    def set_schedule(self, orders: Sequence[Sequence[int]]) -> None:
+        n = len(self._sequences())
+        orders = [[int(s) for s in o] for o in orders]
+        B = len(orders)
+        if not 1 <= B <= 65535:
+            raise ValueError("sast_amd.sampling: the schedule must hold 1 .. 65535 batch rows")
+        longest = max(len(o) for o in orders)
+        if longest > self.order_capacity:
+            raise ValueError(f"sast_amd.sampling: a batch row's schedule holds {longest} sequences, order_capacity is {self.order_capacity}")
+        if B * self.order_capacity > 2 ** 31 - 1:
+            raise ValueError("sast_amd.sampling: batch rows * order_capacity must stay below 2^31")
+        for b, o in enumerate(orders):
+            bad = [s for s in o if not 0 <= s < n]
+            if bad:
+                raise ValueError(f"sast_amd.sampling: batch row {b}'s schedule names sequence {bad[0]}, outside [0, {n})")
+        dev = self.status.device
+        if self.order is None or self.order.shape[0] != B:
+            _not_capturing("set_schedule with a new batch size allocates: call it before graph capture")
+            self.order = torch.full((B, self.order_capacity), -1, dtype=torch.int32, device=dev)
+            self.order_len = torch.zeros(B, dtype=torch.int32, device=dev)
+            self.cursor = torch.zeros(B, 2, dtype=torch.int32, device=dev)
+            a = self._args
+            a.order, a.order_len, a.cursor = self.order.data_ptr(), self.order_len.data_ptr(), self.cursor.data_ptr()
+        if longest:
+            host = np.full((B, longest), -1, np.int32)
+            for b, o in enumerate(orders):
+                host[b, :len(o)] = o
+            self.order[:, :longest].copy_(torch.from_numpy(host))
+        self.order_len.copy_(torch.tensor([len(o) for o in orders], dtype=torch.int32))
+        self.cursor.zero_()
+        self._orders = orders
+
+    def _walk(self):
+        """per batch row the (sequence, sample) of every step of its schedule"""
+        samples = self._sequences()[:, 3]
+        if self._orders is None:
+            raise RuntimeError("sast_amd.sampling: call set_schedule() before plan() / steps()")
+        return [[(s, i) for s in o for i in range(int(samples[s]))] for o in self._orders]
+
+    def steps(self, mode: str = "shortest") -> int:
+        if mode not in ("shortest", "longest"):
+            raise ValueError("sast_amd.sampling: mode must be 'shortest' (Zipper) or 'longest' (ZipperLongest)")
+        n = [len(w) for w in self._walk()]
+        return min(n) if mode == "shortest" else max(n)
+
+    def plan(self) -> StreamingPlan:
+        walk = self._walk()
+        sequences, lw = self._host
+        Ls, B, n = self.sequence_length, len(walk), max(len(w) for w in walk)
+        K, first, seq = np.zeros(n, np.int64), np.zeros((n, B), bool), np.full((n, B), -1, np.int32)
+        for b, w in enumerate(walk):
+            for step, (s, i) in enumerate(w):
+                r, start, stop, _samples = (int(v) for v in sequences[s])
+                lo = start + i * Ls
+                K[step] += int(lw[r][lo:min(lo + Ls, stop)].sum())
+                first[step, b], seq[step, b] = i == 0, s
+        return StreamingPlan(K, first, seq)
+
+    # ---- batches
+    def _want(self, B: int):
+        Ls, M = self.sequence_length, self.labels.max_labels_per_frame
+        i32, u8, i64 = torch.int32, torch.uint8, torch.int64
+        return (((B,), i32), ((Ls, B), i32), ((B,), i32), ((B,), i32), ((B,), u8), ((B,), u8), ((Ls, B), i64), ((Ls, B), i64),
+                ((Ls, B, M, 7), torch.float32), ((Ls, B), i32), ((Ls, B), u8), ((Ls, B), u8))
+
+    def next(self, out: Optional[Sequence[torch.Tensor]] = None) -> StreamingBatch:
+        if out is not None:
+            out = tuple(out)
+            _need_gpu(*out)
+        if self._args is None:
+            raise RuntimeError("sast_amd.sampling: call index() before next()")
+        if self.order is None:
+            raise RuntimeError("sast_amd.sampling: call set_schedule() before next()")
+        dev = self.status.device
+        B = self.order.shape[0]
+        if B * self.sequence_length * self.labels.max_labels_per_frame > (2 ** 31 - 1) // 8:
+            raise ValueError("sast_amd.sampling: B * sequence_length * max_labels_per_frame must be <= (2^31 - 1) / 8")
+        want = self._want(B)
+        if out is None:
+            out = StreamingBatch(*(torch.empty(sh, dtype=dt, device=dev) for sh, dt in want))
+        else:
+            if len(out) != len(want):
+                raise ValueError("sast_amd.sampling: out must be the twelve tensors of a StreamingBatch")
+            for t, (sh, dt), name in zip(out, want, StreamingBatch._fields):
+                if t.dtype != dt or tuple(t.shape) != sh or not t.is_contiguous() or t.device != dev:
+                    raise ValueError(f"sast_amd.sampling: out's {name} must be a contiguous {str(dt).replace('torch.', '')} tensor of shape "
+                                     f"{sh} on the pool's device")
+            out = StreamingBatch(*out)
+        L.check(L.lib().sast_stream_next(C.byref(self.labels._args), C.byref(self._args), B, *(t.data_ptr() for t in out), _stream()),
+                "stream_next")
+        return out
+
+    def frames(self, batch: StreamingBatch, out_frames: Optional[torch.Tensor] = None) -> torch.Tensor:
+        step_rows, ends = batch.step_rows, batch.ends_us
+        _need_gpu(step_rows, ends, out_frames)
+        src = self._events if self._events is not None else self
+        if src.x is None:
+            raise RuntimeError("sast_amd.sampling: call load_events() before frames()" + (" (on the pool given as events=)" if src is not self else ""))
+        Ls = self.sequence_length
+        if step_rows.dtype != torch.int32 or step_rows.dim() != 2 or step_rows.shape[0] != Ls or step_rows.shape[1] < 1 \
+                or not step_rows.is_contiguous():
+            raise ValueError(f"sast_amd.sampling: batch.step_rows must be a contiguous int32 tensor of shape [{Ls}, B]")
+        B = step_rows.shape[1]
+        if ends.dtype != torch.int64 or tuple(ends.shape) != (Ls, B) or not ends.is_contiguous():
+            raise ValueError(f"sast_amd.sampling: batch.ends_us must be a contiguous int64 tensor of shape [{Ls}, {B}]")
+        dev = src.t.device
+        if self.err is None or self.err.device != dev:            # a pool that reads another pool's events keeps its own counters
+            _not_capturing()
+            self.err = torch.zeros(2, dtype=torch.int32, device=dev)
+        self._state.setdefault("bounds", {})
+        # every (step, sample) is a window of its own with its own row: a padded step's row is -1, which gives the empty range
+        return self._mapped_frames(src, step_rows, Ls * B, 1, ends, (Ls, B) + self.get_shape(), out_frames)
