@@ -143,6 +143,31 @@ __device__ __forceinline__ float wave_max(float v) { return group_reduce<64>(v, 
 template <int G>
 __device__ __forceinline__ float group_sum(float v) { return group_reduce<G>(v, OpSum{}); }
 
+// exclusive prefix of v over the workgroup's WAVES * 64 threads in thread order, and the workgroup's total (T: int, long long).
+// sm: T [WAVES] in LDS, free on entry.  Two barriers: the second one frees sm again.
+template <int WAVES, class T>
+__device__ __forceinline__ T block_scan(T v, T* sm, T* total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  T inc = v;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const T o = __shfl_up(inc, d, 64);
+    if (lane >= d) inc += o;
+  }
+  if (lane == 63) sm[wave] = inc;
+  __syncthreads();
+  T before = 0, all = 0;
+#pragma unroll
+  for (int k = 0; k < WAVES; ++k) {
+    const T t = sm[k];
+    if (k < wave) before += t;
+    all += t;
+  }
+  __syncthreads();
+  *total = all;
+  return before + inc - v;
+}
+
 // THE sigmoid of the library (SiLU, LSTM gates, STP weights, the silu / sigmoid GLU gates): on the hardware exp2 path
 // (v_exp_f32 is 1 ulp; the x*log2e pre-multiply adds ~|x|*6e-8 relative) -- measured inside the fp32 parity bars everywhere it is used
 // Round 6: the IEEE division behind `1.0f / x` is ~20 VALU instructions on gfx950 (v_div_scale / v_rcp / 4 x fma / v_div_fmas / v_div_fixup);

@@ -14,6 +14,7 @@
 #include <climits>
 #include "common.cuh"
 #include "kernels.h"
+#include "label_state.cuh"
 
 namespace sast {
 namespace {
@@ -50,30 +51,6 @@ __device__ __forceinline__ LabRow lab_row(const SastLabelArgs& a, int s) {
   r.pair_off = r.fuidx + f;
   r.pair_n = r.pair_off + f;
   return r;
-}
-
-// exclusive prefix of v over the workgroup's threads in thread order, and the workgroup's total; sm: int [LAB_WAVES], free on entry
-// (two barriers: the second one frees sm again)
-__device__ __forceinline__ int block_scan(int v, int* sm, int* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int inc = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int o = __shfl_up(inc, d, 64);
-    if (lane >= d) inc += o;
-  }
-  if (lane == 63) sm[wave] = inc;
-  __syncthreads();
-  int before = 0, all = 0;
-#pragma unroll
-  for (int k = 0; k < LAB_WAVES; ++k) {
-    const int t = sm[k];
-    if (k < wave) before += t;
-    all += t;
-  }
-  __syncthreads();
-  *total = all;
-  return before + inc - v;
 }
 
 // the row's flags as every thread sees them between two phases: nobody writes them between the two barriers
@@ -184,7 +161,7 @@ __global__ __launch_bounds__(LAB_THREADS) void lab_load_kernel(SastLabelArgs a, 
       if (a.max_width >= 0.f) keep = keep && w <= a.max_width;
     }
     int tot;
-    const int pos = nf + block_scan(keep ? 1 : 0, sm, &tot);
+    const int pos = nf + block_scan<LAB_WAVES>(keep ? 1 : 0, sm, &tot);
     if (keep) {
       r.ft[pos] = t;
       float* fb = r.fbox + (size_t)pos * 6;
@@ -203,7 +180,7 @@ __global__ __launch_bounds__(LAB_THREADS) void lab_load_kernel(SastLabelArgs a, 
       const int i = base + tid;
       const bool first = i < nf && (i == 0 || r.ft[i] != r.ft[i - 1]);
       int tot;
-      const int pos = nu + block_scan(first ? 1 : 0, sm, &tot);
+      const int pos = nu + block_scan<LAB_WAVES>(first ? 1 : 0, sm, &tot);
       if (first) { r.uts[pos] = r.ft[i]; r.ustart[pos] = i; }
       nu += tot;
     }
@@ -341,7 +318,7 @@ __global__ __launch_bounds__(LAB_THREADS) void lab_load_kernel(SastLabelArgs a, 
       if (cnt > a.max_labels_per_frame) { cnt = a.max_labels_per_frame; overfull = 1; }
     }
     int tot;
-    const int start = lab_total + block_scan(cnt, sm, &tot);
+    const int start = lab_total + block_scan<LAB_WAVES>(cnt, sm, &tot);
     if (k < nfr) {
       fstart[k] = start;
       fcount[k] = cnt;
@@ -371,38 +348,27 @@ __global__ __launch_bounds__(128) void lab_gather_kernel(SastLabelArgs a, const 
   const int b = blockIdx.x;               // k * S + s
   const int s = b % a.S;
   const long long w = window_idx[b];
-  const int nw = min(max(a.n_windows[s], 0), a.max_windows);
-  const int M = a.max_labels_per_frame;
-  float* out = labels + (size_t)b * M * 7;
-  int cnt = 0, start = 0, lab = 0;
+  const LabelRow row = label_row(a, s);
+  LabelStep st = {0, 0, 0};
   long long e = -1;
-  if (w < 0 || w >= nw) {
+  if (w < 0 || w >= row.nw) {
     if (threadIdx.x == 0) atomicOr(&a.status[s], SAST_LABELS_WINDOW_INDEX);
   } else {
-    e = a.ends_us[(size_t)s * a.max_windows + w];
-    const int f = a.window_2_frame[(size_t)s * a.max_windows + w];
-    if (f >= 0 && f < a.max_frames) {
-      lab = 1;
-      cnt = min(max(a.frame_count[(size_t)s * a.max_frames + f], 0), M);
-      start = min(max(a.frame_start[(size_t)s * a.max_frames + f], 0), (int)a.capacity - cnt);
-    }
+    e = row.ends_us[w];
+    st = row.step(w);
   }
-  const float* src = a.labels + ((size_t)s * a.capacity + start) * 7;
-  for (int i = threadIdx.x; i < M * 7; i += blockDim.x) out[i] = i < cnt * 7 ? src[i] : 0.f;
+  row.copy(st, labels + (size_t)b * a.max_labels_per_frame * 7, a.max_labels_per_frame, threadIdx.x, blockDim.x);
   if (threadIdx.x == 0) {
-    counts[b] = cnt;
+    counts[b] = st.count;
     ends_out[b] = e;
-    labelled[b] = (unsigned char)lab;
+    labelled[b] = (unsigned char)st.labelled;
   }
 }
 
 bool lab_args(const SastLabelArgs* a) {
-  return a && a->ws && a->ends_us && a->n_windows && a->frame_ts_us && a->n_frames && a->frame_2_window && a->window_2_frame && a->labels &&
-         a->frame_start && a->frame_count && a->status && a->S >= 1 && a->S <= 65535 && a->capacity >= 1 &&
-         (long long)a->S * a->capacity <= INT_MAX / 16 && a->max_frames >= 1 && a->max_windows >= 1 && a->max_labels_per_frame >= 1 &&
-         (long long)a->S * a->max_frames <= INT_MAX && (long long)a->S * a->max_windows <= INT_MAX && a->width >= 2 && a->height >= 2 &&
-         a->width <= 65536 && a->height <= 65536 && a->base_delta_us >= 0 && a->delta_t_us >= 1 && a->align_t_us >= 0 &&
-         a->reprs_per_frame >= 1 && a->reprs_per_frame <= 100 && a->min_side >= 0.f && a->min_diag2 >= 0.f;
+  return label_state_ok(a) && a->ws && a->frame_ts_us && a->status && a->width >= 2 && a->height >= 2 && a->width <= 65536 &&
+         a->height <= 65536 && a->base_delta_us >= 0 && a->delta_t_us >= 1 && a->align_t_us >= 0 && a->reprs_per_frame >= 1 &&
+         a->reprs_per_frame <= 100 && a->min_side >= 0.f && a->min_diag2 >= 0.f;
 }
 }  // namespace
 }  // namespace sast

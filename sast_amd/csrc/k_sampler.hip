@@ -13,6 +13,7 @@
 #include <climits>
 #include "common.cuh"
 #include "kernels.h"
+#include "label_state.cuh"
 
 namespace sast {
 namespace {
@@ -20,8 +21,6 @@ namespace {
 constexpr int RND_THREADS = 256;
 constexpr int RND_ITEM_THREADS = 64;
 constexpr int RND_MAX_CLASSES = 256;
-
-__device__ __forceinline__ int rnd_clamp(int v, int lo, int hi) { return min(max(v, lo), hi); }
 
 // sast_rnd_index, launch 1: workgroup r finds row r's start_idx_offset and length; the workgroup that finishes last scans the lengths.
 //
@@ -34,7 +33,7 @@ __global__ __launch_bounds__(RND_THREADS) void rnd_index_kernel(SastLabelArgs a,
   const int r = blockIdx.x, tid = threadIdx.x, R = a.S;
   __shared__ int sh_first, sh_last;
   __shared__ long long sh_wave[RND_THREADS / 64];
-  const int nf = rnd_clamp(a.n_frames[r], 0, a.max_frames);
+  const int nf = clampi(a.n_frames[r], 0, a.max_frames);
   const long long* f2w = reinterpret_cast<const long long*>(a.frame_2_window) + (size_t)r * a.max_frames;
   if (tid == 0) { sh_first = nf; sh_last = 0; }
   __syncthreads();
@@ -63,27 +62,12 @@ __global__ __launch_bounds__(RND_THREADS) void rnd_index_kernel(SastLabelArgs a,
   __threadfence();
   // ConcatDataset.cumsum: cum[0] = 0, cum[r + 1] = cum[r] + length[r], RND_THREADS rows per step with a running carry
   long long carry = 0;
-  const int lane = tid & 63, wave = tid >> 6;
   for (int base = 0; base < R; base += RND_THREADS) {
     const int i = base + tid;
-    long long v = i < R ? (long long)rnd_clamp(__hip_atomic_load(&q.length[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), 0, a.max_frames) : 0LL;
-    long long inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const long long o = __shfl_up(inc, d, 64);
-      if (lane >= d) inc += o;
-    }
-    if (lane == 63) sh_wave[wave] = inc;
-    __syncthreads();
-    long long before = 0, all = 0;
-#pragma unroll
-    for (int k = 0; k < RND_THREADS / 64; ++k) {
-      const long long t = sh_wave[k];
-      if (k < wave) before += t;
-      all += t;
-    }
-    __syncthreads();
-    if (i < R) q.cum[i + 1] = carry + before + inc;
+    const long long v = i < R ? (long long)clampi(__hip_atomic_load(&q.length[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), 0, a.max_frames) : 0LL;
+    long long all;
+    const long long before = block_scan<RND_THREADS / 64>(v, sh_wave, &all);
+    if (i < R) q.cum[i + 1] = carry + before + v;
     carry += all;
   }
   if (tid == 0) {
@@ -96,19 +80,15 @@ __global__ __launch_bounds__(RND_THREADS) void rnd_index_kernel(SastLabelArgs a,
 // words, zero on entry).  Every thread of the workgroup calls it; the counts are complete after the caller's next barrier.
 __device__ __forceinline__ void rnd_item_counts(const SastLabelArgs& a, const SastRndArgs& q, int r, int j, int* cnt) {
   const int L = q.sequence_length;
-  const int nw = rnd_clamp(a.n_windows[r], 0, a.max_windows);
-  const long long end = reinterpret_cast<const long long*>(a.frame_2_window)[(size_t)r * a.max_frames + j] + 1;
-  const int* w2f = a.window_2_frame + (size_t)r * a.max_windows;
+  const LabelRow row = label_row(a, r);
+  const long long end = row.frame_2_window[j] + 1;
   int bad = 0;
   for (int k = (q.only_load_end_labels ? L - 1 : 0) + (int)(threadIdx.x / 8); k < L; k += RND_ITEM_THREADS / 8) {
     const long long w = end - L + k;
-    if (w < 0 || w >= nw) continue;
-    const int f = w2f[w];
-    if (f < 0 || f >= a.max_frames) continue;
-    const int n = rnd_clamp(a.frame_count[(size_t)r * a.max_frames + f], 0, a.max_labels_per_frame);
-    const int start = rnd_clamp(a.frame_start[(size_t)r * a.max_frames + f], 0, (int)a.capacity - n);
-    const float* rows = a.labels + ((size_t)r * a.capacity + start) * 7;
-    for (int i = threadIdx.x % 8; i < n; i += 8) {
+    if (w < 0 || w >= row.nw) continue;
+    const LabelStep st = row.step(w);
+    const float* rows = row.rows(st);
+    for (int i = threadIdx.x % 8; i < st.count; i += 8) {
       const float c = rows[(size_t)i * 7 + 5];
       if (c >= 0.f && c < (float)q.max_classes) atomicAdd(&cnt[(int)c], 1);
       else bad = 1;
@@ -124,8 +104,8 @@ __global__ __launch_bounds__(RND_ITEM_THREADS) void rnd_weight_kernel(SastLabelA
   const int i = blockIdx.x, r = blockIdx.y, tid = threadIdx.x;
   __shared__ int cnt[RND_MAX_CLASSES];
   if (TOTAL && tid == 0) q.weights[(size_t)r * a.max_frames + i] = 0.0;
-  const int nf = rnd_clamp(a.n_frames[r], 0, a.max_frames);
-  const int off = rnd_clamp(q.start_idx_offset[r], 0, nf);
+  const int nf = clampi(a.n_frames[r], 0, a.max_frames);
+  const int off = clampi(q.start_idx_offset[r], 0, nf);
   if (i >= nf - off) return;
   for (int c = tid; c < q.max_classes; c += RND_ITEM_THREADS) cnt[c] = 0;
   __syncthreads();
@@ -161,7 +141,7 @@ __global__ __launch_bounds__(128) void rnd_gather_kernel(SastLabelArgs a, SastRn
   // can only send the search to another row, whose own sizes then bound every index
   int r = -1;
   long long w = -1;
-  int nw = 0;
+  LabelRow row = {};
   if (g >= 0 && g < cum[R]) {
     int lo = 0, hi = R;                       // the first r with cum[r + 1] > g
     while (lo < hi) {
@@ -169,12 +149,11 @@ __global__ __launch_bounds__(128) void rnd_gather_kernel(SastLabelArgs a, SastRn
       if (cum[mid + 1] > g) hi = mid; else lo = mid + 1;
     }
     r = min(lo, R - 1);
-    const int nf = rnd_clamp(a.n_frames[r], 0, a.max_frames);
-    nw = rnd_clamp(a.n_windows[r], 0, a.max_windows);
+    row = label_row(a, r);
     const long long j = g - cum[r] + (long long)q.start_idx_offset[r];
-    if (j >= 0 && j < nf) {
-      const long long end = reinterpret_cast<const long long*>(a.frame_2_window)[(size_t)r * a.max_frames + j] + 1;
-      if (end - L >= 0 && end <= nw) w = end - L + k;
+    if (j >= 0 && j < row.nf) {
+      const long long end = row.frame_2_window[j] + 1;
+      if (end - L >= 0 && end <= row.nw) w = end - L + k;
     }
     if (w < 0) r = -1;
   }
@@ -196,51 +175,29 @@ __global__ __launch_bounds__(128) void rnd_gather_kernel(SastLabelArgs a, SastRn
     }
     return;
   }
-  const int* w2f = a.window_2_frame + (size_t)r * a.max_windows;
-  const int* fcount = a.frame_count + (size_t)r * a.max_frames;
-  const int* fstart = a.frame_start + (size_t)r * a.max_frames;
-  int cnt = 0, start = 0, lab = 0;
-  if (!q.only_load_end_labels || last) {
-    const int f = w2f[w];
-    if (f >= 0 && f < a.max_frames) {
-      lab = 1;
-      cnt = rnd_clamp(fcount[f], 0, M);
-      start = rnd_clamp(fstart[f], 0, (int)a.capacity - cnt);
-    }
-  }
-  const float* src = a.labels + ((size_t)r * a.capacity + start) * 7;
-  for (int i = tid; i < M * 7; i += blockDim.x) out[i] = i < cnt * 7 ? src[i] : 0.f;
+  // only_load_end_labels: the steps before the last read as unlabelled
+  const LabelStep st = (!q.only_load_end_labels || last) ? row.step(w) : LabelStep{0, 0, 0};
+  row.copy(st, out, M, tid, blockDim.x);
   if (tid == 0) {
     window_idx[blk] = w;
-    ends_out[blk] = reinterpret_cast<const long long*>(a.ends_us)[(size_t)r * a.max_windows + w];
-    counts[blk] = cnt;
-    labelled[blk] = (unsigned char)lab;
+    ends_out[blk] = row.ends_us[w];
+    counts[blk] = st.count;
+    labelled[blk] = (unsigned char)st.labelled;
     if (k == 0) rows_out[b] = r;
   }
   if (!last) return;
   // get_most_recent_objframe(check_if_nonempty=True): the last step of the sample whose label frame holds a box (every thread walks
   // the same few windows and finds the same one)
-  int lcnt = 0, lstart = 0;
+  LabelStep lst = {0, 0, 0};
   for (int kk = L - 1; kk >= (q.only_load_end_labels ? L - 1 : 0); --kk) {
-    const int f = w2f[w - (L - 1 - kk)];
-    if (f < 0 || f >= a.max_frames) continue;
-    const int c = rnd_clamp(fcount[f], 0, M);
-    if (c > 0) {
-      lcnt = c;
-      lstart = rnd_clamp(fstart[f], 0, (int)a.capacity - c);
+    const LabelStep c = row.step(w - (L - 1 - kk));
+    if (c.count > 0) {
+      lst = c;
       break;
     }
   }
-  const float* lsrc = a.labels + ((size_t)r * a.capacity + lstart) * 7;
-  for (int i = tid; i < M * 7; i += blockDim.x) latest[(size_t)b * M * 7 + i] = i < lcnt * 7 ? lsrc[i] : 0.f;
-  if (tid == 0) latest_count[b] = lcnt;
-}
-
-bool rnd_label_args(const SastLabelArgs* a) {
-  return a && a->ends_us && a->n_windows && a->n_frames && a->frame_2_window && a->window_2_frame && a->labels && a->frame_start &&
-         a->frame_count && a->S >= 1 && a->S <= 65535 && a->capacity >= 1 && (long long)a->S * a->capacity <= INT_MAX / 16 &&
-         a->max_frames >= 1 && a->max_windows >= 1 && a->max_labels_per_frame >= 1 && (long long)a->S * a->max_frames <= INT_MAX &&
-         (long long)a->S * a->max_windows <= INT_MAX;
+  row.copy(lst, latest + (size_t)b * M * 7, M, tid, blockDim.x);
+  if (tid == 0) latest_count[b] = lst.count;
 }
 
 bool rnd_args(const SastRndArgs* q) {
@@ -254,7 +211,7 @@ extern "C" {
 
 int sast_rnd_index(const SastLabelArgs* a, SastRndArgs* q, sast_stream_t stream) {
   SAST_ENTRY();
-  if (!sast::rnd_label_args(a) || !sast::rnd_args(q) || (q->weighted && !q->weights)) return SAST_EINVAL;
+  if (!sast::label_state_ok(a) || !sast::rnd_args(q) || (q->weighted && !q->weights)) return SAST_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   SAST_LAUNCH(sast::rnd_index_kernel, dim3((unsigned)a->S), dim3(sast::RND_THREADS), 0, st, *a, *q);
   if (q->weighted) {
@@ -270,7 +227,7 @@ int sast_rnd_gather(const SastLabelArgs* a, const SastRndArgs* q, const int64_t*
                     int64_t* ends_us, float* labels, int32_t* counts, uint8_t* labelled, float* latest, int32_t* latest_count,
                     sast_stream_t stream) {
   SAST_ENTRY();
-  if (!sast::rnd_label_args(a) || !sast::rnd_args(q) || !items || !rows || !window_idx || !ends_us || !labels || !counts || !labelled ||
+  if (!sast::label_state_ok(a) || !sast::rnd_args(q) || !items || !rows || !window_idx || !ends_us || !labels || !counts || !labelled ||
       !latest || !latest_count || B < 1)
     return SAST_EINVAL;
   if ((long long)B * q->sequence_length * a->max_labels_per_frame > INT_MAX / 8) return SAST_EINVAL;

@@ -15,6 +15,7 @@
 #include <climits>
 #include "common.cuh"
 #include "kernels.h"
+#include "label_state.cuh"
 
 namespace sast {
 namespace {
@@ -22,52 +23,27 @@ namespace {
 constexpr int STREAM_THREADS = 256;
 constexpr int STREAM_NEXT_THREADS = 128;
 
-__device__ __forceinline__ int stream_clamp(int v, int lo, int hi) { return min(max(v, lo), hi); }
-
 // frame_2_window[r][j] clamped into the row's windows
-__device__ __forceinline__ int stream_f2w(const long long* f2w, int j, int nw) {
-  return (int)min(max(f2w[j], 0LL), (long long)(nw - 1));
+__device__ __forceinline__ int stream_f2w(const int64_t* f2w, int j, int nw) {
+  return (int)min(max((long long)f2w[j], 0LL), (long long)(nw - 1));
 }
 
 // frame j > 0 begins a new sub-sequence: np.diff(indices) > max_len (sequence_for_streaming.py:40)
-__device__ __forceinline__ bool stream_break(const long long* f2w, int j, int nw, int L) {
+__device__ __forceinline__ bool stream_break(const int64_t* f2w, int j, int nw, int L) {
   return stream_f2w(f2w, j, nw) - stream_f2w(f2w, j - 1, nw) > L;
-}
-
-// the sum of v over the workgroup (STREAM_THREADS threads); sh: STREAM_THREADS / 64 words.  Ends with a barrier, so sh may be reused.
-__device__ __forceinline__ int stream_block_sum(int v, int* sh) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-  if (lane == 0) sh[wave] = v;
-  __syncthreads();
-  int all = 0;
-#pragma unroll
-  for (int k = 0; k < STREAM_THREADS / 64; ++k) all += sh[k];
-  __syncthreads();
-  return all;
-}
-
-// the frames and windows of row r that the sequences are cut from: a row without frames or windows has none
-__device__ __forceinline__ void stream_row_sizes(const SastLabelArgs& a, int r, int& nf, int& nw) {
-  nf = stream_clamp(a.n_frames[r], 0, a.max_frames);
-  nw = stream_clamp(a.n_windows[r], 0, a.max_windows);
-  if (nw == 0) nf = 0;
 }
 
 // sast_stream_index, launch 1: workgroup r counts row r's sequences into row_count[r]
 __global__ __launch_bounds__(STREAM_THREADS) void stream_count_kernel(SastLabelArgs a, SastStreamArgs q) {
   const int r = blockIdx.x, tid = threadIdx.x;
   __shared__ int sh[STREAM_THREADS / 64];
-  int nf, nw;
-  stream_row_sizes(a, r, nf, nw);
-  const long long* f2w = reinterpret_cast<const long long*>(a.frame_2_window) + (size_t)r * a.max_frames;
-  int n = 0;
+  const LabelRow row = label_row(a, r);
+  int part = 0, n;
   if (q.guarantee_labels)
-    for (int j = 1 + tid; j < nf; j += STREAM_THREADS) n += stream_break(f2w, j, nw, q.sequence_length) ? 1 : 0;
-  n = stream_block_sum(n, sh);
+    for (int j = 1 + tid; j < row.nf; j += STREAM_THREADS) part += stream_break(row.frame_2_window, j, row.nw, q.sequence_length) ? 1 : 0;
+  block_scan<STREAM_THREADS / 64>(part, sh, &n);
   if (tid == 0) {
-    q.row_count[r] = nf > 0 ? n + 1 : 0;
+    q.row_count[r] = row.nf > 0 ? n + 1 : 0;
     if (r == 0) q.status[0] = 0;
   }
 }
@@ -79,28 +55,27 @@ __global__ __launch_bounds__(STREAM_THREADS) void stream_count_kernel(SastLabelA
 __global__ __launch_bounds__(STREAM_THREADS) void stream_compact_kernel(SastLabelArgs a, SastStreamArgs q) {
   const int r = blockIdx.x, tid = threadIdx.x, R = a.S, L = q.sequence_length, cap = q.max_sequences;
   __shared__ int sh[STREAM_THREADS / 64];
-  __shared__ int sh_wave[STREAM_THREADS / 64];
-  long long before = 0;
+  int before;
   {
     int part = 0;                                             // R * max_frames <= INT_MAX: no partial sum overflows
-    for (int i = tid; i < r; i += STREAM_THREADS) part += stream_clamp(q.row_count[i], 0, a.max_frames);
-    before = stream_block_sum(part, sh);
+    for (int i = tid; i < r; i += STREAM_THREADS) part += clampi(q.row_count[i], 0, a.max_frames);
+    block_scan<STREAM_THREADS / 64>(part, sh, &before);
   }
-  int nf, nw;
-  stream_row_sizes(a, r, nf, nw);
-  const int mine = stream_clamp(q.row_count[r], 0, a.max_frames);
-  const int first = (int)min(before, (long long)cap);
+  const LabelRow row = label_row(a, r);
+  const int nf = row.nf, nw = row.nw;
+  const int64_t* f2w = row.frame_2_window;
+  const int mine = clampi(q.row_count[r], 0, a.max_frames);
+  const int first = min(before, cap);
   if (tid == 0) {
     q.row_first_seq[r] = first;
     if (r == R - 1) {
-      const long long total = before + mine;
+      const long long total = (long long)before + mine;
       q.row_first_seq[R] = (int)min(total, (long long)cap);
       q.n_seq[0] = (int)min(total, (long long)cap);
       if (total > cap) atomicOr(&q.status[0], SAST_STREAM_TRUNCATED);
     }
   }
   if (nf == 0) return;
-  const long long* f2w = reinterpret_cast<const long long*>(a.frame_2_window) + (size_t)r * a.max_frames;
   const int room = cap - first;                               // sequences of this row that fit into the table
   if (!q.guarantee_labels) {
     if (tid == 0 && room > 0) {
@@ -112,29 +87,14 @@ __global__ __launch_bounds__(STREAM_THREADS) void stream_compact_kernel(SastLabe
     }
     return;
   }
-  const int lane = tid & 63, wave = tid >> 6;
   int carry = 0;                                              // breaks in front of this chunk of frames
   for (int base = 0; base < nf; base += STREAM_THREADS) {
     const int j = base + tid;
     const int brk = (j >= 1 && j < nf && stream_break(f2w, j, nw, L)) ? 1 : 0;
-    int inc = brk;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int o = __shfl_up(inc, d, 64);
-      if (lane >= d) inc += o;
-    }
-    if (lane == 63) sh_wave[wave] = inc;
-    __syncthreads();
-    int pre = 0, all = 0;
-#pragma unroll
-    for (int k = 0; k < STREAM_THREADS / 64; ++k) {
-      const int t = sh_wave[k];
-      if (k < wave) pre += t;
-      all += t;
-    }
-    __syncthreads();
+    int all;
+    const int pre = block_scan<STREAM_THREADS / 64>(brk, sh, &all);
     if (j < nf) {
-      const int k = carry + pre + inc;                        // the sequence frame j lies in: the breaks at frames 1 .. j
+      const int k = carry + pre + brk;                        // the sequence frame j lies in: the breaks at frames 1 .. j
       if (k < room) {
         const int w = stream_f2w(f2w, j, nw);
         if (j == 0 || brk) {
@@ -161,12 +121,11 @@ __global__ __launch_bounds__(STREAM_NEXT_THREADS) void stream_next_kernel(
     unsigned char* is_padded) {
   const int b = blockIdx.x, tid = threadIdx.x;
   const int R = a.S, L = q.sequence_length, M = a.max_labels_per_frame;
-  const int Mc = (int)min((long long)M, (long long)a.capacity);          // boxes one frame can hold: never more than the row's label rows
   __shared__ int sh_row, sh_seq, sh_sample, sh_start, sh_stop, sh_done, sh_pos, sh_next_pos, sh_next_sample;
   if (tid == 0) {
-    const int len = stream_clamp(q.order_len[b], 0, q.order_capacity);
-    const int nseq = stream_clamp(q.n_seq[0], 0, q.max_sequences);
-    const int pos = stream_clamp(q.cursor[2 * b], 0, len);
+    const int len = clampi(q.order_len[b], 0, q.order_capacity);
+    const int nseq = clampi(q.n_seq[0], 0, q.max_sequences);
+    const int pos = clampi(q.cursor[2 * b], 0, len);
     int sample = max(q.cursor[2 * b + 1], 0);
     int row = -1, s = -1, start = 0, stop = 0, done = 0, next_pos = pos, next_sample = sample;
     if (pos >= len) {
@@ -181,10 +140,10 @@ __global__ __launch_bounds__(STREAM_NEXT_THREADS) void stream_next_kernel(
         next_pos = pos + 1;
         next_sample = 0;
       } else {
-        row = stream_clamp(q.seq_row[s], 0, R - 1);
-        const int nw = stream_clamp(a.n_windows[row], 0, a.max_windows);
-        start = stream_clamp(q.seq_start[s], 0, nw);
-        stop = stream_clamp(q.seq_stop[s], start, nw);
+        row = clampi(q.seq_row[s], 0, R - 1);
+        const int nw = clampi(a.n_windows[row], 0, a.max_windows);
+        start = clampi(q.seq_start[s], 0, nw);
+        stop = clampi(q.seq_stop[s], start, nw);
         const int samples = max((stop - start + L - 1) / L, 1);
         sample = min(sample, samples - 1);
         if (sample + 1 < samples) {
@@ -203,43 +162,23 @@ __global__ __launch_bounds__(STREAM_NEXT_THREADS) void stream_next_kernel(
   // step k of sample i of a sequence is window start + i * L + k, padded from `stop` on
   const long long w0 = row >= 0 ? (long long)sh_start + (long long)sample * L : 0;
   const long long stop = row >= 0 ? sh_stop : 0;              // row < 0: every step is padded
-  const int rr = max(row, 0);
-  const int* w2f = a.window_2_frame + (size_t)rr * a.max_windows;
-  const int* fcount = a.frame_count + (size_t)rr * a.max_frames;
-  const int* fstart = a.frame_start + (size_t)rr * a.max_frames;
-  const long long* ends = reinterpret_cast<const long long*>(a.ends_us) + (size_t)rr * a.max_windows;
+  const LabelRow view = label_row(a, max(row, 0));
   for (int k = tid; k < L; k += STREAM_NEXT_THREADS) {
     const long long w = w0 + k;
     const bool real = w < stop;
     const size_t o = (size_t)k * B + b;
-    int cnt = 0, lab = 0;
-    if (real) {
-      const int f = w2f[w];
-      if (f >= 0 && f < a.max_frames) {
-        lab = 1;
-        cnt = stream_clamp(fcount[f], 0, Mc);
-      }
-    }
+    const LabelStep st = real ? view.step(w) : LabelStep{0, 0, 0};
     step_rows[o] = real ? row : -1;
     window_idx[o] = real ? w : -1;
-    ends_out[o] = real ? ends[w] : -1;
-    counts[o] = cnt;
-    labelled[o] = (unsigned char)lab;
+    ends_out[o] = real ? view.ends_us[w] : -1;
+    counts[o] = st.count;
+    labelled[o] = (unsigned char)st.labelled;
     is_padded[o] = real ? 0 : 1;
   }
   for (int k = 0; k < L; ++k) {
     const long long w = w0 + k;
-    int cnt = 0, start = 0;
-    if (w < stop) {
-      const int f = w2f[w];
-      if (f >= 0 && f < a.max_frames) {
-        cnt = stream_clamp(fcount[f], 0, Mc);
-        start = stream_clamp(fstart[f], 0, (int)a.capacity - cnt);
-      }
-    }
-    const float* src = a.labels + ((size_t)rr * a.capacity + start) * 7;
-    float* out = labels + ((size_t)k * B + b) * M * 7;
-    for (int i = tid; i < M * 7; i += STREAM_NEXT_THREADS) out[i] = i < cnt * 7 ? src[i] : 0.f;
+    const LabelStep st = w < stop ? view.step(w) : LabelStep{0, 0, 0};
+    view.copy(st, labels + ((size_t)k * B + b) * M * 7, M, tid, STREAM_NEXT_THREADS);
   }
   if (tid == 0) {
     rows_out[b] = row;
@@ -250,13 +189,6 @@ __global__ __launch_bounds__(STREAM_NEXT_THREADS) void stream_next_kernel(
     q.cursor[2 * b] = sh_next_pos;
     q.cursor[2 * b + 1] = sh_next_sample;
   }
-}
-
-bool stream_label_args(const SastLabelArgs* a) {
-  return a && a->ends_us && a->n_windows && a->n_frames && a->frame_2_window && a->window_2_frame && a->labels && a->frame_start &&
-         a->frame_count && a->S >= 1 && a->S <= 65535 && a->capacity >= 1 && (long long)a->S * a->capacity <= INT_MAX / 16 &&
-         a->max_frames >= 1 && a->max_windows >= 1 && a->max_labels_per_frame >= 1 && (long long)a->S * a->max_frames <= INT_MAX &&
-         (long long)a->S * a->max_windows <= INT_MAX;
 }
 
 bool stream_args(const SastStreamArgs* q) {
@@ -271,7 +203,7 @@ extern "C" {
 
 int sast_stream_index(const SastLabelArgs* a, const SastStreamArgs* q, sast_stream_t stream) {
   SAST_ENTRY();
-  if (!sast::stream_label_args(a) || !sast::stream_args(q)) return SAST_EINVAL;
+  if (!sast::label_state_ok(a) || !sast::stream_args(q)) return SAST_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   SAST_LAUNCH(sast::stream_count_kernel, dim3((unsigned)a->S), dim3(sast::STREAM_THREADS), 0, st, *a, *q);
   SAST_LAUNCH(sast::stream_compact_kernel, dim3((unsigned)a->S), dim3(sast::STREAM_THREADS), 0, st, *a, *q);
@@ -283,7 +215,7 @@ int sast_stream_next(const SastLabelArgs* a, const SastStreamArgs* q, int B, int
                      uint8_t* is_first, uint8_t* exhausted, int64_t* window_idx, int64_t* ends_us, float* labels, int32_t* counts,
                      uint8_t* labelled, uint8_t* is_padded, sast_stream_t stream) {
   SAST_ENTRY();
-  if (!sast::stream_label_args(a) || !sast::stream_args(q) || !q->order || !q->order_len || !q->cursor || q->order_capacity < 1 ||
+  if (!sast::label_state_ok(a) || !sast::stream_args(q) || !q->order || !q->order_len || !q->cursor || q->order_capacity < 1 ||
       !rows || !step_rows || !seq || !sample || !is_first || !exhausted || !window_idx || !ends_us || !labels || !counts || !labelled ||
       !is_padded || B < 1 || B > 65535)
     return SAST_EINVAL;

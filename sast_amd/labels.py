@@ -13,7 +13,7 @@ There is no CPU path: CPU tensors raise the library's "no CPU fallback" error.
 from __future__ import annotations
 
 import ctypes as C
-from typing import List, Optional, Tuple
+from typing import List, NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
@@ -46,6 +46,29 @@ FLAGS = (
 
 def flag_names(status: int) -> Tuple[str, ...]:
     return tuple(name for bit, name, _msg in FLAGS if status & bit)
+
+
+def _outputs(cls, want, out, dev, module: str, what: str, owner: str):
+    """the tensors a gather call writes, as a `cls` (a NamedTuple class): allocated as `want` says ((shape, dtype) per field), or the
+    caller's `out` checked against it"""
+    if out is None:
+        return cls(*(torch.empty(sh, dtype=dt, device=dev) for sh, dt in want))
+    out = tuple(out)
+    if len(out) != len(want):
+        raise ValueError(f"sast_amd.{module}: out must be the {what}")
+    _need_gpu(*out)
+    for t, (sh, dt), name in zip(out, want, cls._fields):
+        if t.dtype != dt or tuple(t.shape) != sh or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"sast_amd.{module}: out's {name} must be a contiguous {str(dt).replace('torch.', '')} tensor of shape "
+                             f"{sh} on the {owner}'s device")
+    return cls(*out)
+
+
+class _Labels(NamedTuple):
+    labels: torch.Tensor
+    counts: torch.Tensor
+    ends_us: torch.Tensor
+    labelled: torch.Tensor
 
 
 class LabelStreams:
@@ -230,17 +253,7 @@ class LabelStreams:
             raise ValueError("sast_amd.labels: T * num_streams * max_labels_per_frame must be <= (2^31 - 1) / 8")
         shape = tuple(window_idx.shape)
         want = ((shape + (M, 7), torch.float32), (shape, torch.int32), (shape, torch.int64), (shape, torch.uint8))
-        if out is None:
-            out = tuple(torch.empty(sh, dtype=dt, device=dev) for sh, dt in want)
-        else:
-            out = tuple(out)
-            if len(out) != 4:
-                raise ValueError("sast_amd.labels: out must be the four tensors (labels, counts, ends_us, labelled)")
-            _need_gpu(*out)
-            for t, (sh, dt), name in zip(out, want, ("labels", "counts", "ends_us", "labelled")):
-                if t.dtype != dt or tuple(t.shape) != sh or not t.is_contiguous() or t.device != dev:
-                    raise ValueError(f"sast_amd.labels: out's {name} must be a contiguous {str(dt).replace('torch.', '')} tensor of shape "
-                                     f"{sh} on the state's device")
+        out = tuple(_outputs(_Labels, want, out, dev, "labels", "four tensors (labels, counts, ends_us, labelled)", "state"))
         L.check(L.lib().sast_labels_gather(C.byref(self._args), window_idx.data_ptr(), T, out[0].data_ptr(), out[1].data_ptr(),
                                            out[2].data_ptr(), out[3].data_ptr(), _stream()), "labels_gather")
         return out

@@ -36,7 +36,7 @@ import torch
 from . import _lib as L
 from .events import _Windowed, _dtype_code, _not_capturing
 from .functional import _need_gpu, _stream
-from .labels import LabelStreams
+from .labels import LabelStreams, _outputs
 
 # status bits (include/sast_hip.h, SAST_RND_*): per row, then pool-wide
 ROW_FLAGS = ((L.RND_CLASS_ID, "class_id", "a box of a counted label frame has a class id outside [0, max_classes); it was left out"),)
@@ -63,6 +63,26 @@ class _PoolEvents(_Windowed):
     once (`load_events`), and the frames of windows that are found through a row map (`_mapped_frames`)"""
 
     _events = None             # another pool whose columns, corrected timestamps and counts this one reads (StreamingPool(events=))
+
+    def __init__(self, labels, height, width, sequence_length, bins, count_cutoff, fastmode, duration_us, downsample_by_2, representation,
+                 window_capacity):
+        if not isinstance(labels, LabelStreams):
+            raise TypeError("sast_amd.sampling: labels must be a LabelStreams")
+        if duration_us is None:
+            raise ValueError("sast_amd.sampling: duration_us is required (the windows of a label schedule are duration windows)")
+        super().__init__(bins, height, width, count_cutoff, fastmode, downsample_by_2, representation, duration_us, None, True,
+                         window_capacity)
+        if isinstance(sequence_length, bool) or not isinstance(sequence_length, int) or not 1 <= sequence_length <= 65535:
+            raise ValueError("sast_amd.sampling: sequence_length must be an int in 1 .. 65535")
+        if bool(labels.downsample_by_2) != bool(downsample_by_2):
+            raise ValueError("sast_amd.sampling: labels.downsample_by_2 and downsample_by_2 must agree")
+        self.labels = labels
+        self.num_rows = labels.num_streams
+        self.sequence_length = sequence_length
+        self.x = self.y = self.p = self.t = self.counts = None
+        self._codes = None
+        self._args = None
+        self._host = None          # host mirrors of the last index()
 
     # ---- events
     def load_events(self, x: torch.Tensor, y: torch.Tensor, p: torch.Tensor, t: torch.Tensor, counts: torch.Tensor,
@@ -194,26 +214,13 @@ class RandomAccessPool(_PoolEvents):
                  bins: int = 10, count_cutoff: Optional[int] = 10, fastmode: bool = True, duration_us: int = 50_000,
                  downsample_by_2: bool = False, representation: str = "stacked_histogram", window_capacity: Optional[int] = None,
                  max_classes: int = 16):
-        if not isinstance(labels, LabelStreams):
-            raise TypeError("sast_amd.sampling: labels must be a LabelStreams")
-        if duration_us is None:
-            raise ValueError("sast_amd.sampling: duration_us is required (the windows of a label schedule are duration windows)")
-        super().__init__(bins, height, width, count_cutoff, fastmode, downsample_by_2, representation, duration_us, None, True,
+        super().__init__(labels, height, width, sequence_length, bins, count_cutoff, fastmode, duration_us, downsample_by_2, representation,
                          window_capacity)
-        if isinstance(sequence_length, bool) or not isinstance(sequence_length, int) or not 1 <= sequence_length <= 65535:
-            raise ValueError("sast_amd.sampling: sequence_length must be an int in 1 .. 65535")
         if isinstance(max_classes, bool) or not isinstance(max_classes, int) or not 1 <= max_classes <= L.RND_MAX_CLASSES:
             raise ValueError(f"sast_amd.sampling: max_classes must be an int in 1 .. {L.RND_MAX_CLASSES}")
-        if bool(labels.downsample_by_2) != bool(downsample_by_2):
-            raise ValueError("sast_amd.sampling: labels.downsample_by_2 and downsample_by_2 must agree")
-        self.labels = labels
-        self.num_rows = labels.num_streams
-        self.sequence_length, self.only_load_end_labels, self.max_classes = sequence_length, bool(only_load_end_labels), max_classes
-        self.x = self.y = self.p = self.t = self.counts = None
+        self.only_load_end_labels, self.max_classes = bool(only_load_end_labels), max_classes
         self.start_idx_offset = self.length = self.cum = self.class_total = self.weights = self.status = None
-        self._codes = None
-        self._args = None
-        self._host = None          # (cum [R + 1], start_idx_offset [R]) as numpy, from the last index()
+        # _host: (cum [R + 1], start_idx_offset [R]) as numpy, from the last index()
         self._labelled = None      # labels.labelled_windows() of that index, and per row the window of every label frame
 
     # ---- the item index
@@ -275,19 +282,7 @@ class RandomAccessPool(_PoolEvents):
         B = items.numel()
         if B * self.sequence_length * self.labels.max_labels_per_frame > (2 ** 31 - 1) // 8:
             raise ValueError("sast_amd.sampling: B * sequence_length * max_labels_per_frame must be <= (2^31 - 1) / 8")
-        want = self._want(B)
-        if out is None:
-            out = RandomAccessBatch(*(torch.empty(sh, dtype=dt, device=dev) for sh, dt in want))
-        else:
-            out = tuple(out)
-            if len(out) != len(want):
-                raise ValueError("sast_amd.sampling: out must be the eight tensors of a RandomAccessBatch")
-            _need_gpu(*out)
-            for t, (sh, dt), name in zip(out, want, RandomAccessBatch._fields):
-                if t.dtype != dt or tuple(t.shape) != sh or not t.is_contiguous() or t.device != dev:
-                    raise ValueError(f"sast_amd.sampling: out's {name} must be a contiguous {str(dt).replace('torch.', '')} tensor of shape "
-                                     f"{sh} on the pool's device")
-            out = RandomAccessBatch(*out)
+        out = _outputs(RandomAccessBatch, self._want(B), out, dev, "sampling", "eight tensors of a RandomAccessBatch", "pool")
         L.check(L.lib().sast_rnd_gather(C.byref(self.labels._args), C.byref(self._args), items.data_ptr(), B, *(t.data_ptr() for t in out),
                                         _stream()), "rnd_gather")
         return out
@@ -413,19 +408,11 @@ class StreamingPool(_PoolEvents):
                  events: Optional[_PoolEvents] = None, max_sequences: Optional[int] = None, order_capacity: Optional[int] = None,
                  bins: int = 10, count_cutoff: Optional[int] = 10, fastmode: bool = True, duration_us: int = 50_000,
                  downsample_by_2: bool = False, representation: str = "stacked_histogram", window_capacity: Optional[int] = None):
-        if not isinstance(labels, LabelStreams):
-            raise TypeError("sast_amd.sampling: labels must be a LabelStreams")
+        super().__init__(labels, height, width, sequence_length, bins, count_cutoff, fastmode, duration_us, downsample_by_2, representation,
+                         window_capacity)
         if events is not None and not isinstance(events, _PoolEvents):
             raise TypeError("sast_amd.sampling: events must be a RandomAccessPool or a StreamingPool")
-        if duration_us is None:
-            raise ValueError("sast_amd.sampling: duration_us is required (the windows of a label schedule are duration windows)")
-        super().__init__(bins, height, width, count_cutoff, fastmode, downsample_by_2, representation, duration_us, None, True,
-                         window_capacity)
-        if isinstance(sequence_length, bool) or not isinstance(sequence_length, int) or not 1 <= sequence_length <= 65535:
-            raise ValueError("sast_amd.sampling: sequence_length must be an int in 1 .. 65535")
-        if bool(labels.downsample_by_2) != bool(downsample_by_2):
-            raise ValueError("sast_amd.sampling: labels.downsample_by_2 and downsample_by_2 must agree")
-        R = labels.num_streams
+        R = self.num_rows
         if events is not None and events.num_rows != R:
             raise ValueError(f"sast_amd.sampling: events holds {events.num_rows} rows, the labels {R}")
         if max_sequences is None:
@@ -436,19 +423,14 @@ class StreamingPool(_PoolEvents):
             order_capacity = max_sequences
         if isinstance(order_capacity, bool) or not isinstance(order_capacity, int) or not 1 <= order_capacity <= 2 ** 31 - 1:
             raise ValueError("sast_amd.sampling: order_capacity must be an int in 1 .. 2^31 - 1")
-        self.labels = labels
-        self.num_rows = R
-        self.sequence_length, self.guarantee_labels = sequence_length, bool(guarantee_labels)
+        self.guarantee_labels = bool(guarantee_labels)
         self.max_sequences, self.order_capacity = max_sequences, order_capacity
         while events is not None and events._events is not None:          # a pool that shares itself: read its source
             events = events._events
         self._events = events
-        self.x = self.y = self.p = self.t = self.counts = None
-        self._codes = None
         self.seq_row = self.seq_start = self.seq_stop = self.seq_samples = self.row_first_seq = self.n_seq = self.status = None
         self.order = self.order_len = self.cursor = None
-        self._args = None
-        self._host = None          # (sequences [n_seq, 4], per row the labelled windows) as numpy, from the last index()
+        # _host: (sequences [n_seq, 4], per row the labelled windows) as numpy, from the last index()
         self._orders = None        # the schedule of the last set_schedule()
 
     # ---- the sequence table
@@ -595,7 +577,7 @@ class StreamingPool(_PoolEvents):
     def next(self, out: Optional[Sequence[torch.Tensor]] = None) -> StreamingBatch:
         if out is not None:
             out = tuple(out)
-            _need_gpu(*out)
+            _need_gpu(*out)               # CPU tensors are refused before anything else is looked at
         if self._args is None:
             raise RuntimeError("sast_amd.sampling: call index() before next()")
         if self.order is None:
@@ -604,17 +586,7 @@ class StreamingPool(_PoolEvents):
         B = self.order.shape[0]
         if B * self.sequence_length * self.labels.max_labels_per_frame > (2 ** 31 - 1) // 8:
             raise ValueError("sast_amd.sampling: B * sequence_length * max_labels_per_frame must be <= (2^31 - 1) / 8")
-        want = self._want(B)
-        if out is None:
-            out = StreamingBatch(*(torch.empty(sh, dtype=dt, device=dev) for sh, dt in want))
-        else:
-            if len(out) != len(want):
-                raise ValueError("sast_amd.sampling: out must be the twelve tensors of a StreamingBatch")
-            for t, (sh, dt), name in zip(out, want, StreamingBatch._fields):
-                if t.dtype != dt or tuple(t.shape) != sh or not t.is_contiguous() or t.device != dev:
-                    raise ValueError(f"sast_amd.sampling: out's {name} must be a contiguous {str(dt).replace('torch.', '')} tensor of shape "
-                                     f"{sh} on the pool's device")
-            out = StreamingBatch(*out)
+        out = _outputs(StreamingBatch, self._want(B), out, dev, "sampling", "twelve tensors of a StreamingBatch", "pool")
         L.check(L.lib().sast_stream_next(C.byref(self.labels._args), C.byref(self._args), B, *(t.data_ptr() for t in out), _stream()),
                 "stream_next")
         return out

@@ -7,6 +7,7 @@ hold.  Every device row carries stale, valid-looking records past its count."""
 import ctypes as C
 import functools
 import os
+import subprocess
 import sys
 
 import numpy as np
@@ -232,6 +233,154 @@ def test_generator_reproduces_committed_label_fixture():
     for k in new:
         assert new[k].dtype == old[k].dtype and new[k].shape == old[k].shape, k
         assert np.ascontiguousarray(new[k]).tobytes() == np.ascontiguousarray(old[k]).tobytes(), k
+
+
+_READER_PROGRAM = r"""
+#include <climits>
+#include <cstdio>
+#include <cstdlib>
+#include <initializer_list>
+#include <vector>
+#include "label_state.cuh"
+using namespace sast;
+
+static std::vector<void*> g_heap;
+// an allocation of its own, of exactly n elements: reading one element past it is caught
+template <class T> static T* heap(size_t n, const T* from, T fill) {
+  T* p = (T*)malloc(n * sizeof(T));
+  for (size_t i = 0; i < n; ++i) p[i] = from ? from[i] : fill;
+  g_heap.push_back(p);
+  return p;
+}
+template <class T> static T* heap(std::initializer_list<T> v) { return heap<T>(v.size(), v.begin(), T()); }
+static void check(bool ok, const char* what, int id) {
+  if (!ok) { printf("FAILED %s in state %d\n", what, id); exit(1); }
+}
+static SastLabelArgs sizes(int S, int F, int W, int M, int cap) {
+  SastLabelArgs a = {};
+  a.S = S; a.max_frames = F; a.max_windows = W; a.max_labels_per_frame = M; a.capacity = cap;
+  return a;
+}
+// every (row, window) of the state through the view, the step and the copy; `print`: a line per step
+static void walk(const SastLabelArgs& a, int id, bool print) {
+  check(label_state_ok(&a), "label_state_ok", id);
+  const int M = a.max_labels_per_frame, cap = (int)a.capacity;
+  float* out = heap<float>((size_t)M * 7, nullptr, -1.f);
+  for (int r = 0; r < a.S; ++r) {
+    const LabelRow v = label_row(a, r);
+    check(v.nw >= 0 && v.nw <= a.max_windows && v.nf >= 0 && v.nf <= a.max_frames && (v.nw > 0 || v.nf == 0), "row sizes", id);
+    check(v.Mc <= M && v.Mc <= cap, "Mc", id);
+    long long sum = 0;
+    for (int j = 0; j < v.nf; ++j) sum += v.frame_2_window[j];
+    for (int w = 0; w < v.nw; ++w) {
+      sum += v.ends_us[w];
+      const LabelStep st = v.step(w);
+      check(st.count >= 0 && st.count <= v.Mc, "count <= Mc", id);
+      check(st.start >= 0 && st.start <= cap - st.count, "0 <= start <= capacity - count", id);
+      check(st.labelled == 1 || (st.count == 0 && st.start == 0), "an unlabelled step is empty", id);
+      for (int tid = 0; tid < 5; ++tid) v.copy(st, out, M, tid, 5);
+      if (!print) continue;
+      printf("%d %d %d %d %d", r, w, st.labelled, st.count, st.start);
+      for (int i = 0; i < M * 7; ++i) printf(" %.1f", out[i]);
+      printf("\n");
+    }
+    if (sum == 12345) printf("#\n");
+  }
+}
+// S = 2, max_frames = 4, max_windows = 8: every window a label frame of 2 boxes from row 1 on, but for the one hostile value
+static void hostile(int id, int cap, int M, int fc, int fs, int w2f, int nw, int nf) {
+  SastLabelArgs a = sizes(2, 4, 8, M, cap);
+  int32_t frames[16];
+  for (int i = 0; i < 16; ++i) frames[i] = w2f == 1 << 30 ? i % 4 : w2f;
+  a.n_windows = heap<int32_t>(2, nullptr, nw);
+  a.n_frames = heap<int32_t>(2, nullptr, nf);
+  a.window_2_frame = heap<int32_t>(16, frames, 0);
+  a.frame_count = heap<int32_t>(8, nullptr, fc);
+  a.frame_start = heap<int32_t>(8, nullptr, fs);
+  a.ends_us = heap<int64_t>(16, nullptr, 7);
+  a.frame_2_window = heap<int64_t>(8, nullptr, 3);
+  a.labels = heap<float>((size_t)2 * cap * 7, nullptr, 1.f);
+  walk(a, id, false);
+}
+int main() {
+  {
+    SastLabelArgs a = sizes(@S@, @F@, @W@, @M@, @CAP@);
+    a.n_windows = heap<int32_t>({@n_windows@});
+    a.n_frames = heap<int32_t>({@n_frames@});
+    a.window_2_frame = heap<int32_t>({@window_2_frame@});
+    a.frame_count = heap<int32_t>({@frame_count@});
+    a.frame_start = heap<int32_t>({@frame_start@});
+    a.ends_us = heap<int64_t>({@ends_us@});
+    a.frame_2_window = heap<int64_t>({@frame_2_window@});
+    a.labels = heap<float>({@labels@});
+    walk(a, 0, true);
+  }
+  const int ANY = 1 << 30;      // window_2_frame: every window its own valid frame
+  hostile(1, 2, 3, 3, 1, ANY, 8, 4);                  // capacity 2 < M 3, frame_count 3
+  hostile(2, 6, 3, INT_MAX, 1, ANY, 8, 4);
+  hostile(3, 6, 3, -5, 1, ANY, 8, 4);
+  hostile(4, 6, 3, 2, -1, ANY, 8, 4);
+  hostile(5, 6, 3, 2, 6, ANY, 8, 4);                  // frame_start = capacity
+  hostile(6, 6, 3, 2, INT_MAX, ANY, 8, 4);
+  hostile(7, 6, 3, 2, 1, 4, 8, 4);                    // window_2_frame = max_frames
+  hostile(8, 6, 3, 2, 1, -7, 8, 4);
+  hostile(9, 6, 3, 2, 1, INT_MAX, 8, 4);
+  hostile(10, 6, 3, 2, 1, ANY, -1, 4);
+  hostile(11, 6, 3, 2, 1, ANY, 8 + 9, 4);             // n_windows = max_windows + 9
+  hostile(12, 6, 3, 2, 1, ANY, 8, 4 + 1);             // n_frames = max_frames + 1
+  for (void* p : g_heap) free(p);
+  printf("done\n");
+  return 0;
+}
+"""
+
+
+def test_label_state_reader_under_the_host_sanitizers(tmp_path):
+    """csrc/label_state.cuh, built by the host compiler as it stands and run under ASan + UBSan with every array of the state in a heap
+    allocation of exactly its size: (a) on a valid tiny state `step` and the row copy equal the model's gather at every (row, window);
+    (b) on hostile states -- capacity < max_labels_per_frame with a full frame, counts, starts, frame ids and row sizes far outside
+    their ranges -- nothing outside an array is read, count <= Mc and 0 <= start <= capacity - count"""
+    import sast_amd.build as B
+    S, F, W, Mx, cap = 2, 4, 8, 3, 6
+    n_windows, n_frames = [8, 5], [3, 2]
+    w2f = np.array([[-1, 0, -1, 1, -1, -1, 2, -1], [0, -1, -1, -1, 1, 0, 1, 2]], np.int32)     # row 1: stale frame ids behind its windows
+    fcount = np.array([[0, 3, 2, 3], [1, 3, 3, 3]], np.int32)                                  # no box, exactly M boxes; stale behind n_frames
+    fstart = np.array([[0, 0, 3, 1], [0, 1, 2, 2]], np.int32)
+    ends = np.arange(S * W, dtype=np.int64).reshape(S, W) * 50000 + 100000
+    f2w = np.array([[1, 3, 6, 7], [0, 4, 5, 6]], np.int64)
+    labels = (np.arange(S * cap * 7, dtype=np.float32) + 1).reshape(S, cap, 7)
+    assert (fcount[0, :3] == 0).any() and (fcount[:, :2] == Mx).any() and (w2f[0] < 0).any()
+    src = _READER_PROGRAM
+    for key, v in dict(S=S, F=F, W=W, M=Mx, CAP=cap, n_windows=n_windows, n_frames=n_frames, window_2_frame=w2f, frame_count=fcount,
+                       frame_start=fstart, ends_us=ends, frame_2_window=f2w).items():
+        src = src.replace(f"@{key}@", ", ".join(str(int(x)) for x in np.asarray(v).reshape(-1)))
+    src = src.replace("@labels@", ", ".join(f"{float(x)}f" for x in labels.reshape(-1)))
+    (tmp_path / "reader.cpp").write_text(src)
+    exe = tmp_path / "reader"
+    # the runtimes are linked into the program: it starts whatever else the environment loads into a process
+    r = subprocess.run(["g++", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan",
+                        "-static-libubsan", "-Wall", "-Werror", "-I", B.CSRC, "-o", str(exe), str(tmp_path / "reader.cpp")],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    r = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0 and r.stdout.endswith("done\n"), (r.stdout[-2000:], r.stderr[-4000:])
+    rows = []
+    for s in range(S):
+        row = M.Row()
+        nw, nf = n_windows[s], n_frames[s]
+        row.ends_us, row.window_2_frame, row.frame_2_window = ends[s, :nw], w2f[s, :nw], f2w[s, :nf]
+        row.frame_ts_us, row.frame_count, row.frame_start, row.labels = ends[s, f2w[s, :nf]], fcount[s, :nf], fstart[s, :nf], labels[s]
+        rows.append(row)
+    idx = np.repeat(np.arange(W, dtype=np.int64)[:, None], S, 1)
+    want_labels, want_counts, _ends, want_labelled = M.gather(rows, idx, Mx)
+    lines = [ln.split() for ln in r.stdout.splitlines()[:-1]]
+    assert [(int(ln[0]), int(ln[1])) for ln in lines] == [(s, w) for s in range(S) for w in range(n_windows[s])]
+    for ln in lines:
+        s, w, labelled, count, start = (int(v) for v in ln[:5])
+        assert (labelled, count) == (want_labelled[w, s], want_counts[w, s]), (s, w)
+        assert start == (fstart[s, w2f[s, w]] if labelled else 0), (s, w)
+        assert np.array_equal(np.array(ln[5:], np.float32), want_labels[w, s].reshape(-1)), (s, w)
+    assert want_labelled.sum() == 5 and sorted(want_counts[want_labelled == 1].tolist()) == [0, 1, 2, 3, 3]
 
 
 # ---------------------------------------------------------------------------------------------------------------------------- GPU

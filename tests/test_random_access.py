@@ -23,6 +23,7 @@ import label_streams_model as M  # noqa: E402
 import random_access_model as RM  # noqa: E402
 import make_golden_events as G  # noqa: E402
 import make_golden_random_access as GR  # noqa: E402
+from pool_labels import labels_of  # noqa: E402
 
 gpu = pytest.mark.gpu
 
@@ -383,6 +384,47 @@ def test_batch_equals_the_model(pool, L, end):
     everything = list(range(m.N))
     _same_batch(rp.batch(torch.tensor(everything, dtype=torch.int64, device="cuda")), m.batch(everything, Mx))
     assert ls.errors() == [()] * R
+
+
+@gpu
+@pytest.mark.parametrize("L", [1, 3])
+@pytest.mark.parametrize("end", [False, True])
+def test_batch_reads_the_label_state_as_the_gather_does(L, end):
+    """`batch` and `LabelStreams.labels` (and `StreamingPool.next`, held to the same gather in tests/test_streaming_pool.py) read one
+    state through one reader: frames cut to max_labels_per_frame = 4, and a label frame without boxes.  The loader itself never leaves
+    such a frame (the filters keep w, h >= 5, which scale_(0.5) cannot flatten), so one frame's count is set to 0 in the device state:
+    labelled stays 1, counts is 0, and `latest` has to step over it."""
+    from sast_amd.labels import LabelStreams
+    rows = _words("gen1")
+    R, cap = len(rows), max(len(w) for w in rows) + 5
+    rec = np.stack([np.resize(rows[0][-40:], (cap, 10)) for _ in rows])
+    for s, w in enumerate(rows):
+        rec[s, :len(w)] = w
+    ls = LabelStreams(R, cap, dataset="gen1", split="train", max_frames=128, max_windows=512, max_labels_per_frame=4, downsample_by_2=True)
+    ls.load(torch.from_numpy(rec).cuda(), torch.tensor([len(w) for w in rows], dtype=torch.int64, device="cuda"))
+    assert R == 3 and ls.errors() == [("frame_overfull",)] * R
+    rp = _pool(ls, L, end, downsample_by_2=True)
+    n, sizes = rp.index()
+    items = [0, 5, sizes[1], n - 1]                               # two samples in row 0, two in row 2
+    emptied = rp.start_idx_offset.tolist()[0] + 5                 # the label frame item 5 ends at
+    ls.frame_count[0, emptied] = 0
+    out = rp.batch(torch.tensor(items, dtype=torch.int64, device="cuda"))
+    assert out.rows.tolist() == [0, 0, 2, 2]
+    ref = labels_of(ls, out, R)
+    assert max(int(c.max()) for _l, c, _e, _d in ref) == 4        # a frame cut to the four rows a step holds
+    assert int(ref[1][1][-1]) == 0 and int(ref[1][3][-1]) == 1    # the emptied frame: labelled, no box
+    for b, (labels, counts, ends, labelled) in enumerate(ref):
+        first = L - 1 if end else 0                               # only_load_end_labels: the steps before the last read as unlabelled
+        assert torch.equal(out.ends_us[:, b], ends)
+        for got, exp in ((out.labels[:, b], labels), (out.counts[:, b], counts), (out.labelled[:, b], labelled)):
+            assert torch.equal(got[first:], exp[first:]) and not bool(got[:first].any())
+        full = [k for k in range(first, L) if int(counts[k]) > 0]
+        if full:
+            assert torch.equal(out.latest[b], labels[full[-1]]) and int(out.latest_count[b]) == int(counts[full[-1]]) > 0
+        else:
+            assert not bool(out.latest[b].any()) and int(out.latest_count[b]) == 0
+    assert (int(out.latest_count[1]) > 0) == (L == 3 and not end)  # item 5: an earlier step's frame, or none
+    assert rp.errors() == ([()] * R, ()) and ls.errors() == [("frame_overfull",)] * R
 
 
 @gpu

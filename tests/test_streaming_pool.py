@@ -23,6 +23,7 @@ import streaming_model as SM  # noqa: E402
 import make_golden_events as G  # noqa: E402
 import make_golden_random_access as GR  # noqa: E402
 import make_golden_streaming as GS  # noqa: E402
+from pool_labels import labels_of as _labels_of  # noqa: E402
 
 gpu = pytest.mark.gpu
 
@@ -444,21 +445,6 @@ def test_index_skips_a_flagged_row_and_flags_a_table_that_is_too_small(g):
         small.index(check=True)
     exact = _pool(ls, L, g, max_sequences=n)
     assert exact.index(check=True)[0] == n and exact.errors() == ()
-
-
-def _labels_of(ls, out, R):
-    """LabelStreams.labels at (rows, window_idx) of a batch -> per batch row the four tensors, and which steps are real"""
-    rows, widx = out.rows.tolist(), out.window_idx
-    res = []
-    for b, r in enumerate(rows):
-        if r < 0:
-            res.append(None)
-            continue
-        per_row = torch.zeros(widx.shape[0], R, dtype=torch.int64, device="cuda")
-        per_row[:, r] = widx[:, b].clamp(min=0)
-        labels, counts, ends, labelled = ls.labels(per_row)
-        res.append((labels[:, r], counts[:, r], ends[:, r], labelled[:, r]))
-    return res
 
 
 @gpu
