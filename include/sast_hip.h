@@ -797,6 +797,32 @@ int sast_stream_next(const SastLabelArgs* a, const SastStreamArgs* q, int B, int
                      uint8_t* is_first, uint8_t* exhausted, int64_t* window_idx, int64_t* ends_us, float* labels, int32_t* counts,
                      uint8_t* labelled, uint8_t* is_padded, sast_stream_t stream);
 
+/* ---- mixed sampler (csrc/k_mixed.hip): the merged batch of `sampling: 'mixed'`.  The reference splits the batch size into streamed and
+ * random-access rows (set_mixed_sampling_mode_variables_for_train, modules/data/genx.py:116-129), concatenates the two loaders' batches
+ * along the batch axis, stream rows first (merge_mixed_batches, modules/utils/detection.py:133-161), and trains on the result in one
+ * step.  With B = Bs + Br every output is laid out [L, B, ...] / [B]:
+ *   columns [0, Bs):  exactly what sast_stream_next(a, qs, Bs, ...) writes for batch row b -- the cursor advance, the padded tail, the
+ *     exhausted row and the schedule entry out of range with SAST_STREAM_SCHEDULE_INDEX in qs->status included;
+ *   columns [Bs, B):  exactly what sast_rnd_gather(a, qr, items, Br, ...) writes for items[b - Bs] -- only_load_end_labels and the item
+ *     outside [0, N) with SAST_RND_ITEM_INDEX in qr->status[R] included -- and in the fields only the streaming sampler has: step_rows
+ *     the sample's row at every step (-1 for an item outside [0, N)), seq and sample -1, is_first 1, exhausted 0, is_padded 0.
+ * latest fp32 [Br, M, 7] and latest_count int32 [Br] are sast_rnd_gather's.  step_rows and ends_us are the row map and the window ends
+ * of ONE sast_rnd_window_bounds call over the union batch (B' = L * B, T = 1).  qs and qr must have the same sequence_length.
+ * 1 launch: workgroups [0, Bs) each walk a streamed row's L steps, the other Br * L each take one (step, random sample); the two
+ * bodies are the ones sast_stream_next and sast_rnd_gather run (csrc/sampler_rows.cuh).  No workgroup reads what another one writes,
+ * nothing is kept between calls but the stream cursors, every size is read on the device and every index clamped there: the call
+ * replays inside a graph. */
+int sast_mixed_next(const SastLabelArgs* a, const SastStreamArgs* qs, const SastRndArgs* qr, int Bs, const int64_t* items, int Br, int32_t* rows,
+                    int32_t* step_rows, int32_t* seq, int32_t* sample, uint8_t* is_first, uint8_t* exhausted, int64_t* window_idx,
+                    int64_t* ends_us, float* labels, int32_t* counts, uint8_t* labelled, uint8_t* is_padded, float* latest,
+                    int32_t* latest_count, sast_stream_t stream);
+/* the look-ahead of the merged loop (csrc/k_sampler.hip, whose state it reads; named here because the sast_rnd_ family is closed):
+ * items int64 [B] (device) -> latest fp32 [B, M, 7] and latest_count int32 [B] alone, bit for bit what sast_rnd_gather writes there for
+ * the same items (an item outside [0, N): zero rows, latest_count 0 and SAST_RND_ITEM_INDEX in q->status[R]).  It fetches the label
+ * frames zoom-in is placed on one step before the batch that uses them.  1 launch, a workgroup per sample. */
+int sast_mixed_latest(const SastLabelArgs* a, const SastRndArgs* q, const int64_t* items, int B, float* latest, int32_t* latest_count,
+                      sast_stream_t stream);
+
 /* ---- spatial augmentation of event frames and box labels (csrc/k_augment.hip).  The reference augments on the CPU in its data-loader
  * workers: RandomSpatialAugmentorGenX.__call__ (data/utils/augmentor.py:347-364) -- horizontal flip, then zoom-in (:203-222) or zoom-out
  * (:134-153) -- with the label transforms of ObjectLabels (data/genx_utils/labels.py:255-339).  Both calls read the per-sample

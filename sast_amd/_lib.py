@@ -212,8 +212,10 @@ _SIGNATURES = {
     "sast_labels_gather": (C.c_int, [C.POINTER(SastLabelArgs), P, C.c_int, P, P, P, P, P]),
     "sast_rnd_index": (C.c_int, [C.POINTER(SastLabelArgs), C.POINTER(SastRndArgs), P]),
     "sast_rnd_gather": (C.c_int, [C.POINTER(SastLabelArgs), C.POINTER(SastRndArgs), P, C.c_int] + [P] * 9),
+    "sast_mixed_latest": (C.c_int, [C.POINTER(SastLabelArgs), C.POINTER(SastRndArgs), P, C.c_int, P, P, P]),
     "sast_stream_index": (C.c_int, [C.POINTER(SastLabelArgs), C.POINTER(SastStreamArgs), P]),
     "sast_stream_next": (C.c_int, [C.POINTER(SastLabelArgs), C.POINTER(SastStreamArgs), C.c_int] + [P] * 13),
+    "sast_mixed_next": (C.c_int, [C.POINTER(SastLabelArgs), C.POINTER(SastStreamArgs), C.POINTER(SastRndArgs), C.c_int, P, C.c_int] + [P] * 15),
     "sast_augment_frames": (C.c_int, [P, P, P] + [C.c_int] * 5 + [P]),
     "sast_augment_labels": (C.c_int, [P, P, P] + [C.c_int] * 4 + [P, P, P, P]),
     "sast_eval_reset": (C.c_int, [C.POINTER(SastEvalArgs), P]),

@@ -180,6 +180,7 @@ class SpatialAugmentor:
         self.states: List[AugmentationState] = [AugmentationState() for _ in range(self.batch_size)]
         self._host = np.zeros((self.batch_size, L.AUGMENT_PARAM_WORDS), dtype=np.int32)
         self.params: Optional[torch.Tensor] = None   # int32 [B, AUGMENT_PARAM_WORDS] on the device, made by the first call
+        self._joined: Optional["JoinedAugmentor"] = None   # the JoinedAugmentor this one is a part of
 
     # ------------------------------------------------------------------------------------------------------------------- states
     def _draw(self, latest) -> AugmentationState:
@@ -244,7 +245,7 @@ class SpatialAugmentor:
             raise ValueError(f"sast_amd.augment: {len(states)} states for a batch of {self.batch_size}")
         host = np.stack([self._encode(s) for s in states])
         self.states = list(states)
-        self._host = host
+        self._host[...] = host                                # in place: a JoinedAugmentor's part writes its rows of the joined array
         self._upload()
 
     def _encode(self, st: AugmentationState) -> np.ndarray:
@@ -286,6 +287,9 @@ class SpatialAugmentor:
             self.params.copy_(torch.from_numpy(self._host))   # stream-ordered: later launches and graph replays see the new rows
 
     def _device_params(self, dev) -> torch.Tensor:
+        if self._joined is not None:
+            self._joined._device_params(dev)                  # this part's params are its rows of the joined tensor
+            return self.params
         if self.params is None or self.params.device != dev:
             if torch.cuda.is_current_stream_capturing():
                 raise RuntimeError("sast_amd.augment: one un-captured warm-up call is needed before graph capture")
@@ -336,3 +340,59 @@ class SpatialAugmentor:
                                             cnt_out.data_ptr(), None if head is None else head.data_ptr(), _stream()), "augment_labels")
         self.last_labels = lab_out
         return out, (head if yolox else lab_out), cnt_out
+
+
+class JoinedAugmentor:
+    """One augment call for a batch whose parts are drawn by different configurations.
+
+    The reference augments the streamed rows of a mixed batch with `data_augmentation.stream` (one draw per sub-sequence) and the
+    random-access rows with `data_augmentation.random` (one draw per item, with zoom-in), each in its own loader, before
+    merge_mixed_batches concatenates them.  The kernels read per-sample parameters as params[n % B], so only the host side is needed:
+
+    joined = JoinedAugmentor([stream_aug, random_aug])       SpatialAugmentors with the same dataset_hw, in batch-column order
+    stream_aug.randomize(samples=...); random_aug.randomize(latest_labels=...)      as before: draws, order and validation untouched
+    frames_out, labels_out, counts_out = joined(frames, labels, counts, yolox=False, out=None)
+
+    The joined object owns ONE host array and ONE device tensor `params` [sum B_i, AUGMENT_PARAM_WORDS]; from then on
+    parts[i].randomize(...) and parts[i].set_state(...) rewrite only their own rows of it, by a stream-ordered copy.  The call is
+    `SpatialAugmentor.__call__` over the union batch: 2 launches (1 for frames alone), capturable after one warm-up call.  A part can
+    still be called alone on a batch of its own size; it reads the same rows.  A SpatialAugmentor belongs to one JoinedAugmentor at
+    most."""
+
+    def __init__(self, parts: Sequence[SpatialAugmentor]):
+        parts = list(parts)
+        if not parts or not all(isinstance(p, SpatialAugmentor) for p in parts):
+            raise TypeError("sast_amd.augment: JoinedAugmentor takes a non-empty sequence of SpatialAugmentors")
+        if len({id(p) for p in parts}) != len(parts) or any(p._joined is not None for p in parts):
+            raise ValueError("sast_amd.augment: a SpatialAugmentor can be a part of one JoinedAugmentor, once")
+        if len({p.hw_tuple for p in parts}) != 1:
+            raise ValueError("sast_amd.augment: the parts must have the same dataset_hw")
+        self.parts = parts
+        self.hw_tuple = parts[0].hw_tuple
+        self.batch_size = sum(p.batch_size for p in parts)
+        self.offsets = [sum(p.batch_size for p in parts[:i]) for i in range(len(parts))]
+        self._host = np.concatenate([p._host for p in parts])
+        self.params: Optional[torch.Tensor] = None
+        for p, o in zip(parts, self.offsets):
+            p._host = self._host[o:o + p.batch_size]          # a view: the part's draws land in the joined array
+            p.params = None
+            p._joined = self
+
+    @property
+    def states(self) -> List[AugmentationState]:
+        return [s for p in self.parts for s in p.states]
+
+    def _device_params(self, dev) -> torch.Tensor:
+        if self.params is None or self.params.device != dev:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("sast_amd.augment: one un-captured warm-up call is needed before graph capture")
+            self.params = torch.from_numpy(self._host).to(dev)
+            for p, o in zip(self.parts, self.offsets):
+                p.params = self.params[o:o + p.batch_size]    # a contiguous view: the part's uploads rewrite its rows only
+        return self.params
+
+    def __call__(self, frames: torch.Tensor, labels: Optional[torch.Tensor] = None, counts: Optional[torch.Tensor] = None,
+                 yolox: bool = False, out: Optional[torch.Tensor] = None):
+        return SpatialAugmentor.__call__(self, frames, labels, counts, yolox, out)
+
+    joined = __call__

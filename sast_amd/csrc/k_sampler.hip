@@ -14,13 +14,13 @@
 #include "common.cuh"
 #include "kernels.h"
 #include "label_state.cuh"
+#include "sampler_rows.cuh"
 
 namespace sast {
 namespace {
 
 constexpr int RND_THREADS = 256;
 constexpr int RND_ITEM_THREADS = 64;
-constexpr int RND_MAX_CLASSES = 256;
 
 // sast_rnd_index, launch 1: workgroup r finds row r's start_idx_offset and length; the workgroup that finishes last scans the lengths.
 //
@@ -129,80 +129,21 @@ __global__ __launch_bounds__(RND_ITEM_THREADS) void rnd_weight_kernel(SastLabelA
   }
 }
 
-// sast_rnd_gather: workgroup k * B + b is step k of sample b
-__global__ __launch_bounds__(128) void rnd_gather_kernel(SastLabelArgs a, SastRndArgs q, const long long* items, int B, int* rows_out,
-                                                         long long* window_idx, long long* ends_out, float* labels, int* counts,
-                                                         unsigned char* labelled, float* latest, int* latest_count) {
-  const int blk = blockIdx.x, b = blk % B, k = blk / B, tid = threadIdx.x;
-  const int R = a.S, L = q.sequence_length, M = a.max_labels_per_frame;
-  const long long* cum = reinterpret_cast<const long long*>(q.cum);
-  const long long g = items[b];
-  // ConcatDataset.__getitem__: the row with cum[r] <= g < cum[r + 1]; a cum that does not grow (it always does after sast_rnd_index)
-  // can only send the search to another row, whose own sizes then bound every index
-  int r = -1;
-  long long w = -1;
-  LabelRow row = {};
-  if (g >= 0 && g < cum[R]) {
-    int lo = 0, hi = R;                       // the first r with cum[r + 1] > g
-    while (lo < hi) {
-      const int mid = lo + (hi - lo) / 2;
-      if (cum[mid + 1] > g) hi = mid; else lo = mid + 1;
-    }
-    r = min(lo, R - 1);
-    row = label_row(a, r);
-    const long long j = g - cum[r] + (long long)q.start_idx_offset[r];
-    if (j >= 0 && j < row.nf) {
-      const long long end = row.frame_2_window[j] + 1;
-      if (end - L >= 0 && end <= row.nw) w = end - L + k;
-    }
-    if (w < 0) r = -1;
-  }
-  float* out = labels + (size_t)blk * M * 7;
-  const bool last = k == L - 1;
-  if (r < 0) {
-    for (int i = tid; i < M * 7; i += blockDim.x) out[i] = 0.f;
-    if (last) for (int i = tid; i < M * 7; i += blockDim.x) latest[(size_t)b * M * 7 + i] = 0.f;
-    if (tid == 0) {
-      window_idx[blk] = -1;
-      ends_out[blk] = -1;
-      counts[blk] = 0;
-      labelled[blk] = 0;
-      if (k == 0) rows_out[b] = -1;
-      if (last) {
-        latest_count[b] = 0;
-        atomicOr(&q.status[R], SAST_RND_ITEM_INDEX);
-      }
-    }
-    return;
-  }
-  // only_load_end_labels: the steps before the last read as unlabelled
-  const LabelStep st = (!q.only_load_end_labels || last) ? row.step(w) : LabelStep{0, 0, 0};
-  row.copy(st, out, M, tid, blockDim.x);
-  if (tid == 0) {
-    window_idx[blk] = w;
-    ends_out[blk] = row.ends_us[w];
-    counts[blk] = st.count;
-    labelled[blk] = (unsigned char)st.labelled;
-    if (k == 0) rows_out[b] = r;
-  }
-  if (!last) return;
-  // get_most_recent_objframe(check_if_nonempty=True): the last step of the sample whose label frame holds a box (every thread walks
-  // the same few windows and finds the same one)
-  LabelStep lst = {0, 0, 0};
-  for (int kk = L - 1; kk >= (q.only_load_end_labels ? L - 1 : 0); --kk) {
-    const LabelStep c = row.step(w - (L - 1 - kk));
-    if (c.count > 0) {
-      lst = c;
-      break;
-    }
-  }
-  row.copy(lst, latest + (size_t)b * M * 7, M, tid, blockDim.x);
-  if (tid == 0) latest_count[b] = lst.count;
+// sast_rnd_gather: workgroup k * B + b is step k of sample b (the body is sampler_rows.cuh's, shared with sast_mixed_next)
+__global__ __launch_bounds__(SAMPLER_THREADS) void rnd_gather_kernel(SastLabelArgs a, SastRndArgs q, const long long* items, int B,
+                                                                     RndGatherOut o) {
+  const int b = blockIdx.x % B, k = blockIdx.x / B;
+  rnd_gather_step(a, q, items[b], k, B, b, b, o);
 }
 
-bool rnd_args(const SastRndArgs* q) {
-  return q && q->start_idx_offset && q->length && q->cum && q->status && q->ticket && q->sequence_length >= 1 &&
-         q->sequence_length <= 65535 && q->max_classes >= 1 && q->max_classes <= RND_MAX_CLASSES && q->class_total;
+// sast_mixed_latest: workgroup b is sample b; the `latest` half of the last step of rnd_gather_kernel alone
+__global__ __launch_bounds__(SAMPLER_THREADS) void rnd_latest_kernel(SastLabelArgs a, SastRndArgs q, const long long* items, float* latest,
+                                                                     int* latest_count) {
+  const int b = blockIdx.x, M = a.max_labels_per_frame;
+  LabelRow row = {};
+  long long w0 = 0;
+  const int r = rnd_locate(a, q, items[b], &row, &w0);
+  rnd_latest_rows(q, a.S, r, row, w0, M, latest + (size_t)b * M * 7, latest_count + b);
 }
 }  // namespace
 }  // namespace sast
@@ -230,10 +171,22 @@ int sast_rnd_gather(const SastLabelArgs* a, const SastRndArgs* q, const int64_t*
   if (!sast::label_state_ok(a) || !sast::rnd_args(q) || !items || !rows || !window_idx || !ends_us || !labels || !counts || !labelled ||
       !latest || !latest_count || B < 1)
     return SAST_EINVAL;
-  if ((long long)B * q->sequence_length * a->max_labels_per_frame > INT_MAX / 8) return SAST_EINVAL;
-  SAST_LAUNCH(sast::rnd_gather_kernel, dim3((unsigned)(B * q->sequence_length)), dim3(128), 0, (hipStream_t)stream, *a, *q,
-              reinterpret_cast<const long long*>(items), B, rows, reinterpret_cast<long long*>(window_idx),
-              reinterpret_cast<long long*>(ends_us), labels, counts, labelled, latest, latest_count);
+  if (!sast::sampler_batch_fits(B, q->sequence_length, a->max_labels_per_frame)) return SAST_EINVAL;
+  const sast::RndGatherOut o = {rows, nullptr, reinterpret_cast<long long*>(window_idx), reinterpret_cast<long long*>(ends_us), labels, counts,
+                                labelled, nullptr, latest, latest_count};
+  SAST_LAUNCH(sast::rnd_gather_kernel, dim3((unsigned)(B * q->sequence_length)), dim3(sast::SAMPLER_THREADS), 0, (hipStream_t)stream, *a, *q,
+              reinterpret_cast<const long long*>(items), B, o);
+  SAST_CHECK_LAUNCH();
+  return SAST_OK;
+}
+
+int sast_mixed_latest(const SastLabelArgs* a, const SastRndArgs* q, const int64_t* items, int B, float* latest, int32_t* latest_count,
+                      sast_stream_t stream) {
+  SAST_ENTRY();
+  if (!sast::label_state_ok(a) || !sast::rnd_args(q) || !items || !latest || !latest_count || B < 1) return SAST_EINVAL;
+  if (!sast::sampler_batch_fits(B, 1, a->max_labels_per_frame)) return SAST_EINVAL;
+  SAST_LAUNCH(sast::rnd_latest_kernel, dim3((unsigned)B), dim3(sast::SAMPLER_THREADS), 0, (hipStream_t)stream, *a, *q,
+              reinterpret_cast<const long long*>(items), latest, latest_count);
   SAST_CHECK_LAUNCH();
   return SAST_OK;
 }

@@ -16,12 +16,12 @@
 #include "common.cuh"
 #include "kernels.h"
 #include "label_state.cuh"
+#include "sampler_rows.cuh"
 
 namespace sast {
 namespace {
 
 constexpr int STREAM_THREADS = 256;
-constexpr int STREAM_NEXT_THREADS = 128;
 
 // frame_2_window[r][j] clamped into the row's windows
 __device__ __forceinline__ int stream_f2w(const int64_t* f2w, int j, int nw) {
@@ -114,87 +114,9 @@ __global__ __launch_bounds__(STREAM_THREADS) void stream_compact_kernel(SastLabe
   }
 }
 
-// sast_stream_next: workgroup b is batch row b
-__global__ __launch_bounds__(STREAM_NEXT_THREADS) void stream_next_kernel(
-    SastLabelArgs a, SastStreamArgs q, int B, int* rows_out, int* step_rows, int* seq_out, int* sample_out, unsigned char* is_first,
-    unsigned char* exhausted, long long* window_idx, long long* ends_out, float* labels, int* counts, unsigned char* labelled,
-    unsigned char* is_padded) {
-  const int b = blockIdx.x, tid = threadIdx.x;
-  const int R = a.S, L = q.sequence_length, M = a.max_labels_per_frame;
-  __shared__ int sh_row, sh_seq, sh_sample, sh_start, sh_stop, sh_done, sh_pos, sh_next_pos, sh_next_sample;
-  if (tid == 0) {
-    const int len = clampi(q.order_len[b], 0, q.order_capacity);
-    const int nseq = clampi(q.n_seq[0], 0, q.max_sequences);
-    const int pos = clampi(q.cursor[2 * b], 0, len);
-    int sample = max(q.cursor[2 * b + 1], 0);
-    int row = -1, s = -1, start = 0, stop = 0, done = 0, next_pos = pos, next_sample = sample;
-    if (pos >= len) {
-      done = 1;                                               // get_fully_padded_sample: the cursor stays where it is
-      sample = -1;
-    } else {
-      s = q.order[(size_t)b * q.order_capacity + pos];
-      if (s < 0 || s >= nseq) {
-        atomicOr(&q.status[0], SAST_STREAM_SCHEDULE_INDEX);   // a fully padded sample, then the next entry
-        s = -1;
-        sample = -1;
-        next_pos = pos + 1;
-        next_sample = 0;
-      } else {
-        row = clampi(q.seq_row[s], 0, R - 1);
-        const int nw = clampi(a.n_windows[row], 0, a.max_windows);
-        start = clampi(q.seq_start[s], 0, nw);
-        stop = clampi(q.seq_stop[s], start, nw);
-        const int samples = max((stop - start + L - 1) / L, 1);
-        sample = min(sample, samples - 1);
-        if (sample + 1 < samples) {
-          next_sample = sample + 1;
-        } else {
-          next_pos = pos + 1;
-          next_sample = 0;
-        }
-      }
-    }
-    sh_row = row; sh_seq = s; sh_sample = sample; sh_start = start; sh_stop = stop; sh_done = done;
-    sh_pos = pos; sh_next_pos = next_pos; sh_next_sample = next_sample;
-  }
-  __syncthreads();
-  const int row = sh_row, sample = sh_sample;
-  // step k of sample i of a sequence is window start + i * L + k, padded from `stop` on
-  const long long w0 = row >= 0 ? (long long)sh_start + (long long)sample * L : 0;
-  const long long stop = row >= 0 ? sh_stop : 0;              // row < 0: every step is padded
-  const LabelRow view = label_row(a, max(row, 0));
-  for (int k = tid; k < L; k += STREAM_NEXT_THREADS) {
-    const long long w = w0 + k;
-    const bool real = w < stop;
-    const size_t o = (size_t)k * B + b;
-    const LabelStep st = real ? view.step(w) : LabelStep{0, 0, 0};
-    step_rows[o] = real ? row : -1;
-    window_idx[o] = real ? w : -1;
-    ends_out[o] = real ? view.ends_us[w] : -1;
-    counts[o] = st.count;
-    labelled[o] = (unsigned char)st.labelled;
-    is_padded[o] = real ? 0 : 1;
-  }
-  for (int k = 0; k < L; ++k) {
-    const long long w = w0 + k;
-    const LabelStep st = w < stop ? view.step(w) : LabelStep{0, 0, 0};
-    view.copy(st, labels + ((size_t)k * B + b) * M * 7, M, tid, STREAM_NEXT_THREADS);
-  }
-  if (tid == 0) {
-    rows_out[b] = row;
-    seq_out[b] = sh_seq;
-    sample_out[b] = sample;
-    is_first[b] = row >= 0 && sample == 0 ? 1 : 0;
-    exhausted[b] = (unsigned char)sh_done;
-    q.cursor[2 * b] = sh_next_pos;
-    q.cursor[2 * b + 1] = sh_next_sample;
-  }
-}
-
-bool stream_args(const SastStreamArgs* q) {
-  return q && q->seq_row && q->seq_start && q->seq_stop && q->seq_samples && q->row_first_seq && q->row_count && q->n_seq && q->status &&
-         q->sequence_length >= 1 && q->sequence_length <= 65535 && q->max_sequences >= 1 &&
-         (q->guarantee_labels == 0 || q->guarantee_labels == 1);
+// sast_stream_next: workgroup b is batch row b (the walk itself is sampler_rows.cuh's, shared with sast_mixed_next)
+__global__ __launch_bounds__(SAMPLER_THREADS) void stream_next_kernel(SastLabelArgs a, SastStreamArgs q, int B, StreamNextOut o) {
+  stream_walk_row(a, q, (int)blockIdx.x, B, (int)blockIdx.x, o);
 }
 }  // namespace
 }  // namespace sast
@@ -215,15 +137,13 @@ int sast_stream_next(const SastLabelArgs* a, const SastStreamArgs* q, int B, int
                      uint8_t* is_first, uint8_t* exhausted, int64_t* window_idx, int64_t* ends_us, float* labels, int32_t* counts,
                      uint8_t* labelled, uint8_t* is_padded, sast_stream_t stream) {
   SAST_ENTRY();
-  if (!sast::label_state_ok(a) || !sast::stream_args(q) || !q->order || !q->order_len || !q->cursor || q->order_capacity < 1 ||
-      !rows || !step_rows || !seq || !sample || !is_first || !exhausted || !window_idx || !ends_us || !labels || !counts || !labelled ||
-      !is_padded || B < 1 || B > 65535)
+  if (!sast::label_state_ok(a) || !sast::stream_args(q) || !sast::stream_schedule_args(q, B) || !rows || !step_rows || !seq || !sample ||
+      !is_first || !exhausted || !window_idx || !ends_us || !labels || !counts || !labelled || !is_padded)
     return SAST_EINVAL;
-  if ((long long)B * q->order_capacity > INT_MAX) return SAST_EINVAL;
-  if ((long long)B * q->sequence_length * a->max_labels_per_frame > INT_MAX / 8) return SAST_EINVAL;
-  SAST_LAUNCH(sast::stream_next_kernel, dim3((unsigned)B), dim3(sast::STREAM_NEXT_THREADS), 0, (hipStream_t)stream, *a, *q, B, rows,
-              step_rows, seq, sample, is_first, exhausted, reinterpret_cast<long long*>(window_idx), reinterpret_cast<long long*>(ends_us),
-              labels, counts, labelled, is_padded);
+  if (!sast::sampler_batch_fits(B, q->sequence_length, a->max_labels_per_frame)) return SAST_EINVAL;
+  const sast::StreamNextOut o = {rows, step_rows, seq, sample, is_first, exhausted, reinterpret_cast<long long*>(window_idx),
+                                 reinterpret_cast<long long*>(ends_us), labels, counts, labelled, is_padded};
+  SAST_LAUNCH(sast::stream_next_kernel, dim3((unsigned)B), dim3(sast::SAMPLER_THREADS), 0, (hipStream_t)stream, *a, *q, B, o);
   SAST_CHECK_LAUNCH();
   return SAST_OK;
 }

@@ -18,6 +18,9 @@ The draws stay on the host, as the augmentor's do, with the calls torch's sample
     n, _ = pool.index(weighted=True)
     items = torch.multinomial(pool.weights[:n].cpu(), n, replacement=True)     # WeightedRandomSampler
 
+`MixedPool` merges both halves into the reference's actual training batch (csrc/k_mixed.hip): Bs streamed rows and Br random-access
+samples in one batch, made by one launch, with one frames call over the union.
+
 `StreamingPool` is the first half for the same resident recordings (csrc/k_stream.hip): the sub-sequences of
 `SequenceForIter.get_sequences_with_guaranteed_labels`, their samples of `sequence_length` windows with the padded tail, and the
 per-batch-row concatenations of `ConcatStreamingDataPipe` (train) / `ShardedStreamingDataPipe` (val / test), walked by a cursor in
@@ -54,6 +57,12 @@ class RandomAccessBatch(NamedTuple):
     labels: torch.Tensor          # fp32 [L, B, M, 7]
     counts: torch.Tensor          # int32 [L, B]
     labelled: torch.Tensor        # uint8 [L, B]
+    latest: torch.Tensor          # fp32 [B, M, 7]
+    latest_count: torch.Tensor    # int32 [B]
+
+
+class RandomAccessLatest(NamedTuple):
+    """what `RandomAccessPool.latest` returns: the two zoom-in fields of a `RandomAccessBatch` alone"""
     latest: torch.Tensor          # fp32 [B, M, 7]
     latest_count: torch.Tensor    # int32 [B]
 
@@ -172,6 +181,7 @@ class RandomAccessPool(_PoolEvents):
     n, cumulative_sizes = pool.index(weighted=False)
     out = pool.batch(items, out=None)
     frames = pool.frames(out, out_frames=None)
+    latest, latest_count = pool.latest(items, out=None)
     pool.labelled_pairs(items_host); pool.errors()
 
     labels: a `LabelStreams` of R rows the caller has `load`ed (or loads before `index`): row r's box records and row r's events are
@@ -197,6 +207,8 @@ class RandomAccessPool(_PoolEvents):
       `EventStreams(num_streams=R, ...same arguments...)` gives for row rows[b] at window end ends_us[k, b] on the same columns with
       reset all ones.  5 launches (1 window search through the row map, 4 histogram).  window_capacity: kept events one window may
       hold (default: cap); `err` / `frame_errors()` as `EventStreams.errors()`.
+    latest: items as for batch -> `RandomAccessLatest`: latest / latest_count alone, bit for bit what batch gives for the same items
+      (the look-ahead of `MixedPool.prefetch_latest`).  1 launch, a workgroup per sample.
     labelled_pairs: host only -- the number K of labelled (step, sample) pairs of a batch of items (the batch of the PAFPN / head pass,
       `TrainStep(selection=)`), from the host mirrors of `index()` and `labels.labelled_windows()` (fetched once after each `index`).
     errors: (per row the names of its status bits, the names of the pool's) (synchronises).
@@ -208,6 +220,7 @@ class RandomAccessPool(_PoolEvents):
     INDEX_LAUNCHES = 1
     INDEX_WEIGHTED_LAUNCHES = 3
     BATCH_LAUNCHES = 1
+    LATEST_LAUNCHES = 1
     FRAMES_LAUNCHES = 5
 
     def __init__(self, labels: LabelStreams, height: int, width: int, sequence_length: int, only_load_end_labels: bool = False,
@@ -271,20 +284,33 @@ class RandomAccessPool(_PoolEvents):
                 ((Ls, B), torch.uint8), ((B, M, 7), torch.float32), ((B,), torch.int32))
 
     def batch(self, items: torch.Tensor, out: Optional[Sequence[torch.Tensor]] = None) -> RandomAccessBatch:
-        if items.dtype != torch.int64 or items.dim() != 1 or items.numel() < 1 or not items.is_contiguous():
-            raise ValueError("sast_amd.sampling: items must be a contiguous int64 tensor of shape [B], B >= 1")
-        _need_gpu(items)
-        if self._args is None:
-            raise RuntimeError("sast_amd.sampling: call index() before batch()")
-        dev = items.device
-        if dev != self.status.device:
-            raise ValueError(f"sast_amd.sampling: the pool lives on {self.status.device}, items on {dev}")
-        B = items.numel()
+        B, dev = self._items(items), items.device
         if B * self.sequence_length * self.labels.max_labels_per_frame > (2 ** 31 - 1) // 8:
             raise ValueError("sast_amd.sampling: B * sequence_length * max_labels_per_frame must be <= (2^31 - 1) / 8")
         out = _outputs(RandomAccessBatch, self._want(B), out, dev, "sampling", "eight tensors of a RandomAccessBatch", "pool")
         L.check(L.lib().sast_rnd_gather(C.byref(self.labels._args), C.byref(self._args), items.data_ptr(), B, *(t.data_ptr() for t in out),
                                         _stream()), "rnd_gather")
+        return out
+
+    def _items(self, items: torch.Tensor) -> int:
+        if items.dtype != torch.int64 or items.dim() != 1 or items.numel() < 1 or not items.is_contiguous():
+            raise ValueError("sast_amd.sampling: items must be a contiguous int64 tensor of shape [B], B >= 1")
+        _need_gpu(items)
+        if self._args is None:
+            raise RuntimeError("sast_amd.sampling: call index() before batch() / latest()")
+        if items.device != self.status.device:
+            raise ValueError(f"sast_amd.sampling: the pool lives on {self.status.device}, items on {items.device}")
+        return items.numel()
+
+    def latest(self, items: torch.Tensor, out: Optional[Sequence[torch.Tensor]] = None) -> RandomAccessLatest:
+        B = self._items(items)
+        M = self.labels.max_labels_per_frame
+        if B * M > (2 ** 31 - 1) // 8:
+            raise ValueError("sast_amd.sampling: B * max_labels_per_frame must be <= (2^31 - 1) / 8")
+        out = _outputs(RandomAccessLatest, (((B, M, 7), torch.float32), ((B,), torch.int32)), out, items.device, "sampling",
+                       "two tensors of a RandomAccessLatest", "pool")
+        L.check(L.lib().sast_mixed_latest(C.byref(self.labels._args), C.byref(self._args), items.data_ptr(), B, out.latest.data_ptr(),
+                                          out.latest_count.data_ptr(), _stream()), "mixed_latest")
         return out
 
     def frames(self, batch: RandomAccessBatch, out_frames: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -611,3 +637,204 @@ class StreamingPool(_PoolEvents):
         self._state.setdefault("bounds", {})
         # every (step, sample) is a window of its own with its own row: a padded step's row is -1, which gives the empty range
         return self._mapped_frames(src, step_rows, Ls * B, 1, ends, (Ls, B) + self.get_shape(), out_frames)
+
+
+class MixedBatch(NamedTuple):
+    """what `MixedPool.next` returns (L = sequence_length, M = the labels' max_labels_per_frame, B = Bs + Br: the stream pool's batch
+    rows in columns [0, Bs), the random-access samples in columns [Bs, B))"""
+    rows: torch.Tensor            # int32 [B]: the pool row (recording) of every column, -1: exhausted, a bad schedule entry or a bad item
+    step_rows: torch.Tensor       # int32 [L, B]: the row map of the frames (-1: a padded step or a bad item)
+    seq: torch.Tensor             # int32 [B]: as StreamingBatch.seq; -1 for random columns
+    sample: torch.Tensor          # int32 [B]: as StreamingBatch.sample; -1 for random columns
+    is_first: torch.Tensor        # uint8 [B]: as StreamingBatch.is_first; 1 for random columns (their states are reset every step)
+    exhausted: torch.Tensor       # uint8 [B]: as StreamingBatch.exhausted; 0 for random columns
+    window_idx: torch.Tensor      # int64 [L, B]
+    ends_us: torch.Tensor         # int64 [L, B]
+    labels: torch.Tensor          # fp32 [L, B, M, 7]
+    counts: torch.Tensor          # int32 [L, B]
+    labelled: torch.Tensor        # uint8 [L, B]
+    is_padded: torch.Tensor       # uint8 [L, B]: 0 for random columns
+    latest: torch.Tensor          # fp32 [Br, M, 7]: RandomAccessBatch.latest
+    latest_count: torch.Tensor    # int32 [Br]
+
+
+class MixedPool:
+    """mixed = MixedPool(stream, random)
+    bs_str, bs_rnd = MixedPool.batch_sizes(batch_size, w_stream, w_random)
+    batch = mixed.next(items, out=None)
+    frames = mixed.frames(batch, out_frames=None)
+    mixed.prefetch_latest(next_items); latest_labels = mixed.latest_labels()
+    mixed.labelled_pairs(step, items_host); mixed.steps(Br); mixed.errors(); mixed.frame_errors()
+
+    The reference's actual training batch of `sampling: 'mixed'`: `set_mixed_sampling_mode_variables_for_train`
+    (modules/data/genx.py:116-129) splits the batch size into bs_str streamed and bs_rnd random-access rows, `merge_mixed_batches`
+    (modules/utils/detection.py:133-161) concatenates the two loaders' batches along the batch axis, stream rows first, and
+    `training_step` runs ONE forward and backward over the result; the random rows are reset every step (their is_first_sample is
+    true).  `MixedPool` makes that batch on the device from a `StreamingPool` and a `RandomAccessPool` over the same recordings.
+
+    stream, random: the two pools.  They must share one `LabelStreams`, one sequence_length, one frame geometry and representation,
+      and read the same events (`StreamingPool(events=random)`, or `random` itself being the source of `stream`'s source);
+      ValueError otherwise.  Neither pool's own calls change: both can still be used alone, on the same cursors and index.
+    batch_sizes: host only -- the reference's split, bs_rnd = min(round(batch_size * w_random / (w_stream + w_random)),
+      batch_size - 1), bs_str = batch_size - bs_rnd.  ValueError where the reference asserts (batch_size < 2, a weight <= 0) and where
+      either part would be 0 (the reference would build a loader with batch size 0).
+    next: items int64 [Br] on the device -> `MixedBatch` with Bs = the stream pool's schedule batch.  Columns [0, Bs) are exactly what
+      `stream.next()` gives (and the stream cursors move on as they do there), columns [Bs, B) exactly what `random.batch(items)`
+      gives; both pools' status words are set as by those calls.  1 launch.
+    frames: [L, B, C, H', W'] through ONE row-mapped window search and one histogram pass over step_rows / ends_us: 5 launches for
+      the union batch, byte for byte the concatenation of the two pools' frames.  The pool keeps its own error counters
+      (`frame_errors()`) and buffers.
+    prefetch_latest / latest_labels: zoom-in is drawn on the host from the most recent non-empty label frame of every random sample,
+      and its number of draws depends on the label values, so the draw stays the reference's and stays on the host.  The epoch's item
+      order is known in advance: `prefetch_latest(next_items)` enqueues `random.latest` for the NEXT step's items (1 launch), copies
+      the result into pinned host buffers without blocking and records an event; `latest_labels()` waits on the event of the OLDEST
+      look-ahead not handed out yet and returns what `SpatialAugmentor.randomize(latest_labels=)` takes, per row a CPU tensor [k, 7]
+      or None.  Two look-aheads may be pending (step n + 1's is enqueued before step n's is read; a third raises), so the one host
+      wait per step that remains is on an event recorded a step earlier.  Both stay outside graph capture.  The tensors
+      `latest_labels()` returns are views of pinned buffers that the second `prefetch_latest` after it reuses.
+    labelled_pairs: host only, no sync -- K of the merged batch: stream.plan().K[step] + random.labelled_pairs(items_host).
+    steps: min(stream.steps('shortest'), N // Br) with N the random pool's item count: the epoch stops with the shorter of the two halves.  (How Lightning's
+      CombinedLoader ends an epoch over the two loaders is unpinned: pytorch_lightning is not installed.  Any other policy is the
+      caller's loop.)
+    errors: (stream.errors(), random.errors()).
+    After one un-captured call of next and frames with the same Bs and Br nothing is allocated but the outputs and nothing
+    synchronises: next + frames (+ joined augmentor + step) are captured in one graph; a replay advances the streams and reads the
+    items written into the captured `items` tensor."""
+
+    NEXT_LAUNCHES = 1
+    FRAMES_LAUNCHES = 5
+    PREFETCH_LAUNCHES = 1
+
+    def __init__(self, stream: StreamingPool, random: RandomAccessPool):
+        if not isinstance(stream, StreamingPool) or not isinstance(random, RandomAccessPool):
+            raise TypeError("sast_amd.sampling: MixedPool takes a StreamingPool and a RandomAccessPool")
+        if stream.labels is not random.labels:
+            raise ValueError("sast_amd.sampling: the two pools must share one LabelStreams")
+        if stream.sequence_length != random.sequence_length:
+            raise ValueError(f"sast_amd.sampling: the pools' sequence_length differ ({stream.sequence_length}, {random.sequence_length})")
+        geometry = ("representation", "bins", "height", "width", "count_cutoff", "fastmode", "downsample_by_2", "mode", "value",
+                    "window_capacity")
+        for name in geometry:
+            if getattr(stream, name) != getattr(random, name):
+                raise ValueError(f"sast_amd.sampling: the pools' frames differ in {name} ({getattr(stream, name)!r}, "
+                                 f"{getattr(random, name)!r})")
+        src = stream._events if stream._events is not None else stream
+        if src is not random:
+            raise ValueError("sast_amd.sampling: the pools must read the same events: build the StreamingPool with events=random")
+        self.stream, self.random = stream, random
+        self.labels, self.sequence_length, self.num_rows = stream.labels, stream.sequence_length, stream.num_rows
+        # the frames driver of the union batch: its own workspace, window bounds and error counters over `random`'s events
+        d = self._driver = _PoolEvents(stream.labels, stream.height, stream.width, stream.sequence_length, stream.bins, stream.count_cutoff,
+                                       stream.fastmode, stream.value, stream.downsample_by_2, stream.representation, stream.window_capacity)
+        d._events = random
+        d._state = {"bounds": {}}
+        # Br -> two slots of (latest [Br, M, 7], latest_count [Br] in pinned host memory, their device sources, an event): the look-ahead
+        # of step n + 1 is enqueued while step n's labels are still to be read
+        self._pinned = {}
+        self._turn = 0
+        self._pending = []         # the slots latest_labels() has not handed out yet, oldest first
+
+    # ---- host arithmetic
+    @staticmethod
+    def batch_sizes(batch_size: int, w_stream, w_random) -> Tuple[int, int]:
+        if isinstance(batch_size, bool) or not isinstance(batch_size, int) or batch_size < 2:
+            raise ValueError("sast_amd.sampling: mixed sampling needs an int batch_size >= 2")
+        if not w_random > 0 or not w_stream > 0:
+            raise ValueError("sast_amd.sampling: w_stream and w_random must be > 0")
+        bs_rnd = min(round(batch_size * w_random / (w_stream + w_random)), batch_size - 1)
+        bs_str = batch_size - bs_rnd
+        if bs_rnd < 1 or bs_str < 1:
+            raise ValueError(f"sast_amd.sampling: batch_size {batch_size} with weights {w_stream} : {w_random} leaves {bs_str} streamed and "
+                             f"{bs_rnd} random-access rows; both halves need at least one")
+        return bs_str, bs_rnd
+
+    def labelled_pairs(self, step: int, items_host) -> int:
+        return int(self.stream.plan().K[step]) + self.random.labelled_pairs(items_host)
+
+    def steps(self, random_batch: int) -> int:
+        if isinstance(random_batch, bool) or not isinstance(random_batch, int) or random_batch < 1:
+            raise ValueError("sast_amd.sampling: the random-access batch size must be an int >= 1")
+        if self.random._host is None:
+            raise RuntimeError("sast_amd.sampling: call index() on the random pool before steps()")
+        return min(self.stream.steps("shortest"), int(self.random._host[0][-1]) // random_batch)
+
+    def errors(self):
+        """(the stream pool's status names, the random pool's (per row, pool-wide) status names) (synchronises)"""
+        return self.stream.errors(), self.random.errors()
+
+    def frame_errors(self) -> Tuple[int, int]:
+        """(invalid events, windows over capacity) of this pool's frames calls (synchronises)"""
+        return self._driver.frame_errors()
+
+    # ---- batches
+    def _want(self, Bs: int, Br: int):
+        return self.stream._want(Bs + Br) + self.random._want(Br)[-2:]
+
+    def next(self, items: torch.Tensor, out: Optional[Sequence[torch.Tensor]] = None) -> MixedBatch:
+        sp, rp = self.stream, self.random
+        if out is not None:
+            out = tuple(out)
+            _need_gpu(*out)
+        Br = rp._items(items)
+        if sp._args is None:
+            raise RuntimeError("sast_amd.sampling: call index() on the stream pool before next()")
+        if sp.order is None:
+            raise RuntimeError("sast_amd.sampling: call set_schedule() on the stream pool before next()")
+        dev = items.device
+        if sp.status.device != dev:
+            raise ValueError(f"sast_amd.sampling: the stream pool lives on {sp.status.device}, items on {dev}")
+        Bs = sp.order.shape[0]
+        if (Bs + Br) * self.sequence_length * self.labels.max_labels_per_frame > (2 ** 31 - 1) // 8:
+            raise ValueError("sast_amd.sampling: B * sequence_length * max_labels_per_frame must be <= (2^31 - 1) / 8")
+        out = _outputs(MixedBatch, self._want(Bs, Br), out, dev, "sampling", "fourteen tensors of a MixedBatch", "pool")
+        L.check(L.lib().sast_mixed_next(C.byref(self.labels._args), C.byref(sp._args), C.byref(rp._args), Bs, items.data_ptr(), Br,
+                                        *(t.data_ptr() for t in out), _stream()), "mixed_next")
+        return out
+
+    def frames(self, batch: MixedBatch, out_frames: Optional[torch.Tensor] = None) -> torch.Tensor:
+        step_rows, ends = batch.step_rows, batch.ends_us
+        _need_gpu(step_rows, ends, out_frames)
+        d, src = self._driver, self.random
+        if src.x is None:
+            raise RuntimeError("sast_amd.sampling: call load_events() on the random pool before frames()")
+        Ls = self.sequence_length
+        if step_rows.dtype != torch.int32 or step_rows.dim() != 2 or step_rows.shape[0] != Ls or step_rows.shape[1] < 1 \
+                or not step_rows.is_contiguous():
+            raise ValueError(f"sast_amd.sampling: batch.step_rows must be a contiguous int32 tensor of shape [{Ls}, B]")
+        B = step_rows.shape[1]
+        if ends.dtype != torch.int64 or tuple(ends.shape) != (Ls, B) or not ends.is_contiguous():
+            raise ValueError(f"sast_amd.sampling: batch.ends_us must be a contiguous int64 tensor of shape [{Ls}, {B}]")
+        dev = src.t.device
+        if d.err is None or d.err.device != dev:
+            _not_capturing()
+            d.err = torch.zeros(2, dtype=torch.int32, device=dev)
+        # every (step, column) is a window of its own with its own row, as in StreamingPool.frames
+        return d._mapped_frames(src, step_rows, Ls * B, 1, ends, (Ls, B) + d.get_shape(), out_frames)
+
+    # ---- the zoom-in look-ahead
+    def prefetch_latest(self, next_items: torch.Tensor) -> None:
+        Br = self.random._items(next_items)
+        _not_capturing("prefetch_latest copies to the host: keep it outside graph capture")
+        if len(self._pending) >= 2:
+            raise RuntimeError("sast_amd.sampling: two look-aheads are pending: call latest_labels() before the next prefetch_latest()")
+        M = self.labels.max_labels_per_frame
+        if Br not in self._pinned:
+            dev = next_items.device
+            self._pinned[Br] = [(torch.empty(Br, M, 7, dtype=torch.float32).pin_memory(), torch.empty(Br, dtype=torch.int32).pin_memory(),
+                                 RandomAccessLatest(torch.empty(Br, M, 7, dtype=torch.float32, device=dev),
+                                                    torch.empty(Br, dtype=torch.int32, device=dev)), torch.cuda.Event()) for _ in range(2)]
+        self._turn ^= 1
+        host, host_count, staged, event = slot = self._pinned[Br][self._turn]
+        self.random.latest(next_items, out=staged)
+        host.copy_(staged.latest, non_blocking=True)
+        host_count.copy_(staged.latest_count, non_blocking=True)
+        event.record()
+        self._pending.append(slot)
+
+    def latest_labels(self) -> List[Optional[torch.Tensor]]:
+        if not self._pending:
+            raise RuntimeError("sast_amd.sampling: call prefetch_latest() before latest_labels()")
+        _not_capturing("latest_labels waits for a host copy: keep it outside graph capture")
+        host, host_count, _staged, event = self._pending.pop(0)
+        event.synchronize()
+        return [host[b, :k] if k else None for b, k in enumerate(host_count.tolist())]
