@@ -623,7 +623,9 @@ int sast_head_pred_bwd(const float* draw, const float* reg_feat, const float* cl
                        float* dw_cls, float* db_cls, int B, int H, int W, int hidden, int num_classes, int anchor_offset, int anchors_total,
                        sast_stream_t stream) { SAST_ENTRY();
   hipStream_t st = (hipStream_t)stream;
-  if (!draw || hidden % 4 || num_classes < 1 || num_classes > HEAD_MAX_CLASSES) return SAST_EINVAL;
+  if (!draw || !reg_feat || !cls_feat || hidden % 4 || num_classes < 1 || num_classes > HEAD_MAX_CLASSES || anchor_offset < 0 ||
+      anchor_offset + H * W > anchors_total)
+    return SAST_EINVAL;
   const int HW = H * W;
   const size_t n = (size_t)B * HW * (hidden / 4);
   SAST_LAUNCH(head_pred_bwd_feat_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, draw, w_reg, w_obj, w_cls, d_reg_feat,

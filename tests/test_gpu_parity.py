@@ -637,7 +637,8 @@ def test_yolox_loss_use_l1(golden_dir, dev):
 
 
 def test_yolox_loss_full_size(dev):
-    """1Mpx-sized head (5040 anchors, B=4, up to 24 boxes per image incl. an image without labels): assignment and losses vs the oracle."""
+    """1Mpx-sized head (5040 anchors, B=4, up to 24 boxes per image incl. an image without labels): assignment, losses and the gradients of
+    the three input maps vs the oracle."""
     from sast_amd.detection import YOLOXHead
     chans, nc, B = (128, 256, 512), 3, 4
     params = O.init_head_params(chans, num_classes=nc, seed=9)
@@ -647,10 +648,12 @@ def test_yolox_loss_full_size(dev):
     g = torch.Generator().manual_seed(91)
     feats = [torch.randn(B, c, 48 // (2 ** i), 80 // (2 ** i), generator=g) for i, c in enumerate(chans)]
     labels = O.synthetic_labels(B, (384, 640), nc, max_labels=24, seed=92)
-    assert int((labels[-1].sum(-1) > 0).sum()) >= 0
-    out, losses = head(tuple(f.to(dev).requires_grad_(True) for f in feats), labels.to(dev))
+    assert int((labels[-1].sum(-1) > 0).sum()) == 0
+    dfeats = tuple(f.to(dev).requires_grad_(True) for f in feats)
+    out, losses = head(dfeats, labels.to(dev))
     po = {k: (v.clone().requires_grad_(True) if "running" not in k else v.clone()) for k, v in params.items()}
-    ref = O.yolox_head_train([f.clone().requires_grad_(True) for f in feats], labels, po, num_classes=nc)
+    fo = [f.clone().requires_grad_(True) for f in feats]
+    ref = O.yolox_head_train(fo, labels, po, num_classes=nc)
     fg, mg, piou = head.last_assignment
     mism = 0
     for b, (rfg, rmatched, rpiou) in enumerate(ref["assign"]):
@@ -661,6 +664,10 @@ def test_yolox_loss_full_size(dev):
     assert mism == 0, f"{mism} assignment mismatches"
     for k in ("loss", "iou_loss", "conf_loss", "cls_loss", "num_fg"):
         assert abs(float(losses[k]) - float(ref[k])) <= 1e-4 * max(1.0, abs(float(ref[k]))), (k, float(losses[k]), float(ref[k]))
+    losses["loss"].backward()       # the three input gradients at hidden = 128 and full size
+    ref["loss"].backward()
+    for i, (a, b) in enumerate(zip(dfeats, fo)):
+        maxnorm_close(a.grad, b.grad, GRAD_RTOL, f"din{i}")
 
 
 @pytest.mark.parametrize("A,thr,agnostic", [(420, 0.3, False), (5040, 0.05, False), (420, 0.3, True)])
