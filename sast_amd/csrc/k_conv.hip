@@ -398,13 +398,42 @@ void bn_bwd_reduce_launch(const BnBwdJob& j0, const BnBwdJob& j1, int njobs, int
   SAST_LAUNCH(bn_bwd_reduce_kernel, dim3((M + rpb - 1) / rpb, njobs), dim3(BN_RED_THREADS), sizeof(float4) * 2 * RP * c4n, st, j0, j1, M, C,
                      rpb);
 }
+// float4 loop trips per thread of the BatchNorm-apply kernels: >= 512 blocks while the image allows it; the per-block statistics prologue
+// is 2C*COPIES loads
+inline int bn_apply_iters(size_t n4) {
+  const int iters = (int)(n4 / (256 * 512));
+  return iters < 1 ? 1 : (iters > 8 ? 8 : iters);
+}
+// m_stat: rows behind the sums (all ranks; 0: the M rows of this process)
 void bn_bwd_apply_launch(const BnBwdJob& j0, const BnBwdJob& j1, int njobs, int M, int C, int training, hipStream_t st, int m_stat = 0) {
   const size_t n4 = (size_t)M * (C / 4);
-  int iters = (int)(n4 / (256 * 512));
-  iters = iters < 1 ? 1 : (iters > 8 ? 8 : iters);
+  const int iters = bn_apply_iters(n4);
   SAST_LAUNCH(bn_bwd_apply_kernel, dim3((unsigned)((n4 + 256 * iters - 1) / (256 * iters)), njobs), dim3(256), sizeof(float) * 6 * C, st,
-                     j0, j1, n4, C, 1.0f / (float)(m_stat > 0 ? m_stat : M), training, iters, div_mul_of((unsigned)(C / 4), n4));   // m_stat: rows behind the sums (all ranks)
+                     j0, j1, n4, C, 1.0f / (float)(m_stat > 0 ? m_stat : M), training, iters, div_mul_of((unsigned)(C / 4), n4));
 }
+// y = silu(BN(conv_out)) of `njobs` convs of equal shape (blockIdx.y = job), statistics over m_stat rows
+void bn_fwd_apply_launch(const BnFwdJob& j0, const BnFwdJob& j1, int njobs, int M, int m_stat, int C, int training, hipStream_t st) {
+  const size_t n4 = (size_t)M * (C / 4);
+  const int iters = bn_apply_iters(n4);
+  SAST_LAUNCH(bn_silu_apply_kernel, dim3((unsigned)((n4 + 256 * iters - 1) / (256 * iters)), njobs), dim3(256), sizeof(float) * 2 * C, st, j0, j1,
+                     1.0 / (double)m_stat, bn_unbias(m_stat), n4, C, training, iters, div_mul_of((unsigned)(C / 4), n4));
+}
+// fp64 column sums of conv_out as a row-strip pass of about `target_blocks` blocks
+void bn_stats_launch(const float* conv_out, int M, int C, double* sums, int target_blocks, hipStream_t st) {
+  int rpb = (M + target_blocks - 1) / target_blocks;
+  rpb = rpb < 8 ? 8 : rpb;
+  const int c4n = C / 4, RP = 256 / c4n > 0 ? 256 / c4n : 1;
+  SAST_LAUNCH(bn_stats_kernel, dim3((M + rpb - 1) / rpb), dim3(256), sizeof(double) * 2 * RP * C, st, conv_out, M, C, sums, rpb);
+}
+// the producer behind one source of a conv (SastConvBnArgs.p_* / p2_*): its backward sums are the second block of its reduction scratch
+inline BnProducer producer_of(const float* conv_out, const float* stats, const float* w, const float* b, float* ws, int C) {
+  return BnProducer{conv_out, stats, w, b, ws ? ws + 4 * BN_STAT_COPIES * C : nullptr, C};
+}
+inline bool complete(const BnProducer& p) { return p.stats && p.gamma && p.beta && p.sums; }
+// the dX job of a backward pair with the plain epilogue or, when `fold`, with the one that also reduces the producers' BatchNorm
+// backward sums.  `launch` is a generic lambda: its closure stays on the host, only the epilogue's type reaches a kernel
+template <class EP, class EPR, class F>
+int with_dx_epilogue(bool fold, const EP& plain, const EPR& red, const F& launch) { return fold ? launch(red) : launch(plain); }
 
 inline ConvGeom geom_of(int B, int H, int W, int Cin, int k, int stride, int pad, int replicate, int ldx) {
   ConvGeom g;
@@ -429,6 +458,15 @@ int conv_gemm(const float* x, const ConvGeom& g, const LB& lb, const EP& ep, int
   if (g.Cin % 16 == 0) return gemm_auto(LdIm2colU{{x, g}}, lb, ep, M, NJ, K, st);
   return gemm_auto(LdIm2col{x, g}, lb, ep, M, NJ, K, st);
 }
+// forward GEMM of a conv unit over the source(s) `src` ([x | x2]; x2 may be NULL): the row loaders for a 1x1 stride-1 conv, conv_gemm for
+// everything else.  ROWS1: one source has the loader of its own (LdRows); the stacked pair reads it through LdRows2 as well (false)
+template <bool ROWS1, class LB, class EP>
+int conv_fwd_gemm(const ConvGeom& g, const LdRows2& src, const LB& lb, const EP& ep, int M, int NJ, int K, hipStream_t st) {
+  if (g.KH != 1 || g.stride != 1) return conv_gemm(src.p1, g, lb, ep, M, NJ, K, st);
+  if constexpr (ROWS1)
+    if (!src.p2) return gemm_auto(LdRows{src.p1, src.ld1, nullptr}, lb, ep, M, NJ, K, st);
+  return gemm_auto(src, lb, ep, M, NJ, K, st);
+}
 
 // backward of a k x k convolution.  Stride 2 with a 3x3 kernel (downsample convs of stages 2-4, the two bottom-up PAFPN convs)
 // computes dX through the parity-class form (gemm.cuh: LdConvDxP) unless SAST_CONVDX_PARITY=0; everything else through the
@@ -444,21 +482,16 @@ int conv_bwd_pair(const float* dconv, const float* x, const ConvGeom& g, int Cou
   if (!dx) return gemm_tn(ta, tb, dw, K, Cout, K, M, st);
   const int parity = SAST_KNOB("SAST_CONVDX_PARITY", 1);
   const int Mc = g.B * (g.H / 2) * (g.W / 2);
-  if (prod && prod->x) {   // stride-1 convs only (the caller checks): dX epilogue also reduces the producer's BatchNorm backward sums
-    if (g.stride != 1 || lddx != g.Cin || prod->C != g.Cin) return SAST_EINVAL;
-    if (Cout % 16 == 0)
-      return gemm_pair(ta, tb, dw, K, Cout, K, M, nullptr, nullptr, LdConvDxU{{dconv, g, Cout, Cout, shift}},
-                       LdWeightConvDxU{{w, Cout, k * k, g.Cin, shift}}, EpStoreBnRed{dx, lddx, *prod}, g.B * g.H * g.W, g.Cin, k * k * Cout, nullptr, st, pair_tn_blocks_conv());
-    return gemm_pair(ta, tb, dw, K, Cout, K, M, nullptr, nullptr, LdConvDx{dconv, g, Cout, Cout, shift},
-                     LdWeightConvDx{w, Cout, k * k, g.Cin, shift}, EpStoreBnRed{dx, lddx, *prod}, g.B * g.H * g.W, g.Cin, k * k * Cout, nullptr, st, pair_tn_blocks_conv());
-  }
-  if (!(parity && g.stride == 2 && k == 3 && g.pad == 1 && g.H % 2 == 0 && g.W % 2 == 0 && Mc % 64 == 0)) {
-    if (Cout % 16 == 0)
-      return gemm_pair(ta, tb, dw, K, Cout, K, M, nullptr, nullptr, LdConvDxU{{dconv, g, Cout, Cout, shift}},
-                       LdWeightConvDxU{{w, Cout, k * k, g.Cin, shift}}, EpStore{dx, lddx, nullptr}, g.B * g.H * g.W, g.Cin, k * k * Cout, nullptr, st, pair_tn_blocks_conv());
-    return gemm_pair(ta, tb, dw, K, Cout, K, M, nullptr, nullptr, LdConvDx{dconv, g, Cout, Cout, shift},
-                     LdWeightConvDx{w, Cout, k * k, g.Cin, shift}, EpStore{dx, lddx, nullptr}, g.B * g.H * g.W, g.Cin, k * k * Cout, nullptr, st, pair_tn_blocks_conv());
-  }
+  const bool fold = prod && prod->x;   // stride-1 convs only (the caller checks): dX epilogue also reduces the producer's BatchNorm backward sums
+  if (fold && (g.stride != 1 || lddx != g.Cin || prod->C != g.Cin)) return SAST_EINVAL;
+  if (fold || !(parity && g.stride == 2 && k == 3 && g.pad == 1 && g.H % 2 == 0 && g.W % 2 == 0 && Mc % 64 == 0))
+    return with_dx_epilogue(fold, EpStore{dx, lddx, nullptr}, EpStoreBnRed{dx, lddx, fold ? *prod : BnProducer{}}, [&](const auto& ep) {
+      if (Cout % 16 == 0)      // the uniform-tap loaders (gemm.cuh: LdConvDxU)
+        return gemm_pair(ta, tb, dw, K, Cout, K, M, nullptr, nullptr, LdConvDxU{{dconv, g, Cout, Cout, shift}},
+                         LdWeightConvDxU{{w, Cout, k * k, g.Cin, shift}}, ep, g.B * g.H * g.W, g.Cin, k * k * Cout, nullptr, st, pair_tn_blocks_conv());
+      return gemm_pair(ta, tb, dw, K, Cout, K, M, nullptr, nullptr, LdConvDx{dconv, g, Cout, Cout, shift},
+                       LdWeightConvDx{w, Cout, k * k, g.Cin, shift}, ep, g.B * g.H * g.W, g.Cin, k * k * Cout, nullptr, st, pair_tn_blocks_conv());
+    });
   ConvDxClasses c;
   c.Hc = g.H / 2; c.Wc = g.W / 2; c.Mc = Mc;
   c.mc_mul = div_mul_of((unsigned)c.Mc, 4ull * Mc); c.wc_mul = div_mul_of((unsigned)c.Wc, 4ull * Mc); c.hc_mul = div_mul_of((unsigned)c.Hc, 4ull * Mc);
@@ -575,8 +608,9 @@ int sast_conv_bn_silu_fwd(const SastConvBnArgs* a, sast_stream_t stream) { SAST_
   int rc = SAST_OK;
   const int sep = SAST_KNOB("SAST_BN_STATS_SEPARATE", 0);
   const bool one = k == 1 && a->stride == 1;
-  if (a->x2 && (!one || a->Cin1 % 4 || a->Cin1 <= 0 || a->Cin1 >= a->Cin)) return SAST_EINVAL;
-  const LdRows2 la2{a->x, a->ldx, a->Cin1, a->x2, a->ldx2};    // virtual channel concat [x | x2]
+  if (a->x2 && (!one || a->Cin1 % 4 || a->Cin1 <= 0 || a->Cin1 >= a->Cin)) return SAST_EINVAL;   // (Cin1 == Cin refused here, accepted by the stacked pair)
+  const LdRows2 src{a->x, a->ldx, a->Cin1, a->x2, a->ldx2};    // virtual channel concat [x | x2]
+  const LdWeightNT lw{a->w, K, 0};
   if (!a->training && !a->conv_out) {   // inference: one launch, nothing kept for a backward
     if (!a->run_mean || !a->run_var) return SAST_EINVAL;
     if (dw) {
@@ -587,48 +621,22 @@ int sast_conv_bn_silu_fwd(const SastConvBnArgs* a, sast_stream_t stream) { SAST_
       SAST_CHECK_LAUNCH();
       return SAST_OK;
     }
-    const EpBnSilu ep{a->y, a->ldy, a->run_mean, a->run_var, a->bn_w, a->bn_b, a->eps};
-    return one ? (a->x2 ? gemm_auto(la2, LdWeightNT{a->w, K, 0}, ep, M, C, K, st)
-                        : gemm_auto(LdRows{a->x, a->ldx, nullptr}, LdWeightNT{a->w, K, 0}, ep, M, C, K, st))
-               : conv_gemm(a->x, g, LdWeightNT{a->w, K, 0}, ep, M, C, K, st);
+    return conv_fwd_gemm<true>(g, src, lw, EpBnSilu{a->y, a->ldy, a->run_mean, a->run_var, a->bn_w, a->bn_b, a->eps}, M, C, K, st);
   }
   if (phase == 2) {            // the conv and its sums are phase 1's
   } else if (dw) {             // the stencil, then (training) its column sums as a row-strip pass
     rc = dwconv_fwd_launch(a->x, a->w, nullptr, a->conv_out, a->B, dg, nullptr, st);
-    if (!rc && a->training) {
-      int rpb = (M + 127) / 128;
-      rpb = rpb < 8 ? 8 : rpb;
-      const int c4n = C / 4, RP = 256 / c4n > 0 ? 256 / c4n : 1;
-      SAST_LAUNCH(bn_stats_kernel, dim3((M + rpb - 1) / rpb), dim3(256), sizeof(double) * 2 * RP * C, st, a->conv_out, M, C, sums, rpb);
-    }
+    if (!rc && a->training) bn_stats_launch(a->conv_out, M, C, sums, 128, st);
   } else if (a->training && !sep) {   // conv + per-channel sum / sum-of-squares in one pass
-    const EpStoreStats ep{a->conv_out, C, sums};
-    rc = one ? (a->x2 ? gemm_auto(la2, LdWeightNT{a->w, K, 0}, ep, M, C, K, st)
-                      : gemm_auto(LdRows{a->x, a->ldx, nullptr}, LdWeightNT{a->w, K, 0}, ep, M, C, K, st))
-             : conv_gemm(a->x, g, LdWeightNT{a->w, K, 0}, ep, M, C, K, st);
+    rc = conv_fwd_gemm<true>(g, src, lw, EpStoreStats{a->conv_out, C, sums}, M, C, K, st);
   } else {
-    const EpStore ep{a->conv_out, C, nullptr};
-    rc = one ? (a->x2 ? gemm_auto(la2, LdWeightNT{a->w, K, 0}, ep, M, C, K, st)
-                      : gemm_auto(LdRows{a->x, a->ldx, nullptr}, LdWeightNT{a->w, K, 0}, ep, M, C, K, st))
-             : conv_gemm(a->x, g, LdWeightNT{a->w, K, 0}, ep, M, C, K, st);
+    rc = conv_fwd_gemm<true>(g, src, lw, EpStore{a->conv_out, C, nullptr}, M, C, K, st);
   }
   if (rc) return rc;
-  if (a->training && sep && phase != 2 && !dw) {
-    int rpb = (M + sep - 1) / sep;
-    rpb = rpb < 8 ? 8 : rpb;
-    const int c4n = C / 4, RP = 256 / c4n > 0 ? 256 / c4n : 1;
-    SAST_LAUNCH(bn_stats_kernel, dim3((M + rpb - 1) / rpb), dim3(256), sizeof(double) * 2 * RP * C, st, a->conv_out, M, C, sums, rpb);
-  }
+  if (a->training && sep && phase != 2 && !dw) bn_stats_launch(a->conv_out, M, C, sums, sep, st);
   if (phase == 1) { SAST_CHECK_LAUNCH(); return SAST_OK; }
-  const size_t n4 = (size_t)M * (C / 4);
-  int iters = (int)(n4 / (256 * 512));     // >= 512 blocks while the image allows it; the per-block statistics prologue is 2C*COPIES loads
-  iters = iters < 1 ? 1 : (iters > 8 ? 8 : iters);
-  {
-    const BnFwdJob jb{a->conv_out, sums, a->run_mean, a->run_var, a->stats, a->bn_w, a->bn_b, a->y, a->ldy, a->momentum, a->eps};
-    SAST_LAUNCH(bn_silu_apply_kernel, dim3((unsigned)((n4 + 256 * iters - 1) / (256 * iters)), 1), dim3(256), sizeof(float) * 2 * C, st,
-                       jb, jb, 1.0 / (double)(phase == 2 ? a->m_total : M), bn_unbias(phase == 2 ? a->m_total : M), n4, C, a->training, iters,
-                       div_mul_of((unsigned)(C / 4), n4));
-  }
+  const BnFwdJob jb{a->conv_out, sums, a->run_mean, a->run_var, a->stats, a->bn_w, a->bn_b, a->y, a->ldy, a->momentum, a->eps};
+  bn_fwd_apply_launch(jb, jb, 1, M, phase == 2 ? a->m_total : M, C, a->training, st);
   SAST_CHECK_LAUNCH();
   return SAST_OK;
 }
@@ -658,8 +666,8 @@ int sast_conv_bn_silu_bwd(const SastConvBnArgs* a, sast_stream_t stream) { SAST_
   SAST_CHECK_LAUNCH();
   // producers of x / x2 whose only consumer is this conv: their reductions ride on this conv's dX epilogue
   const int C2 = a->Cin - a->Cin1;
-  BnProducer p1{a->p_conv_out, a->p_stats, a->p_bn_w, a->p_bn_b, a->p_bn_ws ? a->p_bn_ws + 4 * BN_STAT_COPIES * a->Cin1 : nullptr, a->Cin1};
-  BnProducer p2{a->p2_conv_out, a->p2_stats, a->p2_bn_w, a->p2_bn_b, a->p2_bn_ws ? a->p2_bn_ws + 4 * BN_STAT_COPIES * C2 : nullptr, C2};
+  const BnProducer p1 = producer_of(a->p_conv_out, a->p_stats, a->p_bn_w, a->p_bn_b, a->p_bn_ws, a->Cin1);
+  const BnProducer p2 = producer_of(a->p2_conv_out, a->p2_stats, a->p2_bn_w, a->p2_bn_b, a->p2_bn_ws, C2);
   const bool fold = a->training && a->dx && (p1.x || p2.x);
   if (a->groups > 1) {       // depth-wise unit (see the forward): dX / dW of the stencil; no producer folding, no virtual concat
     if (a->groups != a->Cin || a->Cin != C || a->x2 || fold || a->ldx != a->Cin || (a->dx && a->lddx != a->Cin)) return SAST_EINVAL;
@@ -668,29 +676,24 @@ int sast_conv_bn_silu_bwd(const SastConvBnArgs* a, sast_stream_t stream) { SAST_
     SAST_CHECK_LAUNCH();
     return SAST_OK;
   }
-  if (fold && (a->stride != 1 || (p1.x && !(p1.stats && p1.gamma && p1.beta && p1.sums)) || (p2.x && !(a->x2 && p2.stats && p2.gamma && p2.beta && p2.sums))))
-    return SAST_EINVAL;
+  if (fold && (a->stride != 1 || (p1.x && !complete(p1)) || (p2.x && !(a->x2 && complete(p2))))) return SAST_EINVAL;
+  const auto pair_1x1 = [&](const auto& tb, const auto& ep) {   // (dW || dX) of a 1x1 stride-1 conv: dW over the rows tb reads, dX = dconv W
+    return gemm_pair(LdRowsT{dconv, C}, tb, a->dw, K, C, K, M, nullptr, nullptr, LdRows{dconv, C, nullptr}, LdWeightNN{a->w, K}, ep, M, a->Cin, C,
+                     nullptr, st, pair_tn_blocks_1x1());
+  };
   if (k == 1 && a->stride == 1 && a->x2) {   // virtual concat input: dW over [x | x2], dX split into the two gradients
     const LdRowsT2 tb{a->x, a->ldx, a->Cin1, a->x2, a->ldx2};
     if (!a->dx) return gemm_tn(LdRowsT{dconv, C}, tb, a->dw, K, C, K, M, st);
     if (a->lddx != a->Cin1) return SAST_EINVAL;
-    if (fold) {
-      if ((p1.x && a->ldx != a->Cin1) || (p2.x && (a->ldx2 != C2 || !a->dx2))) return SAST_EINVAL;
-      return gemm_pair(LdRowsT{dconv, C}, tb, a->dw, K, C, K, M, nullptr, nullptr, LdRows{dconv, C, nullptr}, LdWeightNN{a->w, K},
-                       EpSplit2BnRed{a->dx, a->dx2, a->Cin1, C2, p1, p2}, M, a->Cin, C, nullptr, st, pair_tn_blocks_1x1());
-    }
-    return gemm_pair(LdRowsT{dconv, C}, tb, a->dw, K, C, K, M, nullptr, nullptr,
-                     LdRows{dconv, C, nullptr}, LdWeightNN{a->w, K}, EpSplit2{a->dx, a->dx2, a->Cin1, C2}, M, a->Cin, C, nullptr, st, pair_tn_blocks_1x1());
+    if (fold && ((p1.x && a->ldx != a->Cin1) || (p2.x && (a->ldx2 != C2 || !a->dx2)))) return SAST_EINVAL;
+    return with_dx_epilogue(fold, EpSplit2{a->dx, a->dx2, a->Cin1, C2}, EpSplit2BnRed{a->dx, a->dx2, a->Cin1, C2, p1, p2},
+                            [&](const auto& ep) { return pair_1x1(tb, ep); });
   }
   if (k == 1 && a->stride == 1) {
     if (!a->dx) return gemm_tn(LdRowsT{dconv, C}, LdRowsT{a->x, a->ldx}, a->dw, K, C, K, M, st);
-    if (fold) {
-      if (a->lddx != a->Cin || a->ldx != a->Cin) return SAST_EINVAL;
-      return gemm_pair(LdRowsT{dconv, C}, LdRowsT{a->x, a->ldx}, a->dw, K, C, K, M, nullptr, nullptr, LdRows{dconv, C, nullptr},
-                       LdWeightNN{a->w, K}, EpStoreBnRed{a->dx, a->lddx, p1}, M, a->Cin, C, nullptr, st, pair_tn_blocks_1x1());
-    }
-    return gemm_pair(LdRowsT{dconv, C}, LdRowsT{a->x, a->ldx}, a->dw, K, C, K, M, nullptr, nullptr,
-                     LdRows{dconv, C, nullptr}, LdWeightNN{a->w, K}, EpStore{a->dx, a->lddx, nullptr}, M, a->Cin, C, nullptr, st, pair_tn_blocks_1x1());
+    if (fold && (a->lddx != a->Cin || a->ldx != a->Cin)) return SAST_EINVAL;
+    return with_dx_epilogue(fold, EpStore{a->dx, a->lddx, nullptr}, EpStoreBnRed{a->dx, a->lddx, p1},
+                            [&](const auto& ep) { return pair_1x1(LdRowsT{a->x, a->ldx}, ep); });
   }
   return conv_bwd_pair(dconv, a->x, g, C, a->w, a->dw, a->dx, a->lddx, st, fold ? &p1 : nullptr);
 }
@@ -698,19 +701,18 @@ int sast_conv_bn_silu_bwd(const SastConvBnArgs* a, sast_stream_t stream) { SAST_
 // ------------------------------------------------------------------ two 1x1 conv + BN + SiLU of the same input
 int sast_conv_bn_silu2_fwd(const SastConvBn2Args* a, sast_stream_t stream) { SAST_ENTRY();
   hipStream_t st = (hipStream_t)stream;
+  // (Cin1 == Cin, one source, accepted here; the single unit refuses it next to an x2)
   if (!a || a->Cin % 4 || a->Cout % 4 || a->Cin1 % 4 || a->Cin1 <= 0 || a->Cin1 > a->Cin || (a->Cin1 < a->Cin && !a->x2)) return SAST_EINVAL;
   ProfScope ps_("convbn2_fwd", a->Cout * 10 + 1, a->B * a->H * a->W, st);
   const int M = a->B * a->H * a->W, C = a->Cout;
+  const LdRows2 src{a->x, a->ldx, a->Cin1, a->Cin1 < a->Cin ? a->x2 : nullptr, a->ldx2};
   if (!a->training) {   // inference: one launch, nothing kept
     if (!a->run_mean0 || !a->run_var0 || !a->run_mean1 || !a->run_var1 || (a->ksize != 1 && a->ksize != 3)) return SAST_EINVAL;
     const EpBnSilu2 ep{a->y0, a->y1, C, a->run_mean0, a->run_var0, a->bn_w0, a->bn_b0, a->eps0, a->run_mean1, a->run_var1, a->bn_w1, a->bn_b1, a->eps1};
-    if (a->ksize == 3) {
-      if (a->Cin1 != a->Cin) return SAST_EINVAL;
-      const ConvGeom g = geom_of(a->B, a->H, a->W, a->Cin, 3, 1, 1, 0, a->ldx);
-      return conv_gemm(a->x, g, LdWeightNT2{a->w0, a->w1, 9 * a->Cin, C}, ep, M, 2 * C, 9 * a->Cin, st);
-    }
-    return gemm_auto(LdRows2{a->x, a->ldx, a->Cin1, a->Cin1 < a->Cin ? a->x2 : nullptr, a->ldx2}, LdWeightNT2{a->w0, a->w1, a->Cin, C}, ep, M,
-                     2 * C, a->Cin, st);
+    if (a->ksize == 3 && a->Cin1 != a->Cin) return SAST_EINVAL;
+    const int K = a->ksize * a->ksize * a->Cin;
+    return conv_fwd_gemm<false>(geom_of(a->B, a->H, a->W, a->Cin, a->ksize, 1, a->ksize / 2, 0, a->ldx), src, LdWeightNT2{a->w0, a->w1, K, C}, ep, M,
+                                2 * C, K, st);
   }
   if (a->ksize != 1 && !(a->ksize == 3 && a->Cin1 == a->Cin)) return SAST_EINVAL;
   const int K = a->ksize * a->ksize * a->Cin;
@@ -718,19 +720,13 @@ int sast_conv_bn_silu2_fwd(const SastConvBn2Args* a, sast_stream_t stream) { SAS
     zero_fill(a->bn_ws0, sizeof(float) * SAST_BN_WS_FLOATS(C), st);
     zero_fill(a->bn_ws1, sizeof(float) * SAST_BN_WS_FLOATS(C), st);
   }
-  const LdRows2 la{a->x, a->ldx, a->Cin1, a->Cin1 < a->Cin ? a->x2 : nullptr, a->ldx2};
   const EpStoreStats2 ep{a->conv_out0, a->conv_out1, C, (double*)a->bn_ws0, (double*)a->bn_ws1};
-  int rc = a->ksize == 3 ? conv_gemm(a->x, geom_of(a->B, a->H, a->W, a->Cin, 3, 1, 1, 0, a->ldx), LdWeightNT2{a->w0, a->w1, K, C}, ep, M,
-                                     2 * C, K, st)
-                         : gemm_auto(la, LdWeightNT2{a->w0, a->w1, K, C}, ep, M, 2 * C, K, st);
+  int rc = conv_fwd_gemm<false>(geom_of(a->B, a->H, a->W, a->Cin, a->ksize, 1, a->ksize / 2, 0, a->ldx), src, LdWeightNT2{a->w0, a->w1, K, C}, ep, M,
+                                2 * C, K, st);
   if (rc) return rc;
-  const size_t n4 = (size_t)M * (C / 4);
-  int iters = (int)(n4 / (256 * 512));
-  iters = iters < 1 ? 1 : (iters > 8 ? 8 : iters);
   const BnFwdJob j0{a->conv_out0, (const double*)a->bn_ws0, a->run_mean0, a->run_var0, a->stats0, a->bn_w0, a->bn_b0, a->y0, C, a->momentum0, a->eps0};
   const BnFwdJob j1{a->conv_out1, (const double*)a->bn_ws1, a->run_mean1, a->run_var1, a->stats1, a->bn_w1, a->bn_b1, a->y1, C, a->momentum1, a->eps1};
-  SAST_LAUNCH(bn_silu_apply_kernel, dim3((unsigned)((n4 + 256 * iters - 1) / (256 * iters)), 2), dim3(256), sizeof(float) * 2 * C, st, j0, j1,
-                     1.0 / (double)M, bn_unbias(M), n4, C, 1, iters, div_mul_of((unsigned)(C / 4), n4));
+  bn_fwd_apply_launch(j0, j1, 2, M, M, C, 1, st);
   SAST_CHECK_LAUNCH();
   return SAST_OK;
 }
@@ -759,7 +755,7 @@ int sast_conv_bn_silu2_bwd(const SastConvBn2Args* a, sast_stream_t stream) { SAS
   // dW of both convs: [dconv0 | dconv1]^T [x | x2] -> (dw0, dw1);  dX = [dconv0 | dconv1] [w0; w1]
   const LdRowsT ta{dconv, 2 * C};
   const EpAtomic2 ep1{a->dw0, a->dw1, K, C};
-  BnProducer p1{a->p_conv_out, a->p_stats, a->p_bn_w, a->p_bn_b, a->p_bn_ws ? a->p_bn_ws + 4 * BN_STAT_COPIES * a->Cin1 : nullptr, a->Cin1};
+  const BnProducer p1 = producer_of(a->p_conv_out, a->p_stats, a->p_bn_w, a->p_bn_b, a->p_bn_ws, a->Cin1);
   if (a->ksize == 3) {   // two 3x3 stride-1 convs (the first convs of the two YOLOX head towers)
     const ConvGeom g = geom_of(a->B, a->H, a->W, a->Cin, 3, 1, 1, 0, a->ldx);
     const LdIm2colT tbc{a->x, g};
@@ -768,28 +764,21 @@ int sast_conv_bn_silu2_bwd(const SastConvBn2Args* a, sast_stream_t stream) { SAS
     if (!shift || !g.cin_mul) return SAST_EINVAL;
     const LdConvDx lac{dconv, g, 2 * C, 2 * C, shift};
     const LdWeightConvDx2 lbc{a->w0, a->w1, 2 * C, C, 9, a->Cin, shift};
-    if (p1.x) {
-      if (a->ldx != a->Cin || !(p1.stats && p1.gamma && p1.beta && p1.sums)) return SAST_EINVAL;
-      return gemm_pair_ep(ta, tbc, ep1, 2 * C, K, M, nullptr, nullptr, lac, lbc, EpStoreBnRed{a->dx, a->Cin, p1}, M, a->Cin, 9 * 2 * C, nullptr, st,
-                          pair_tn_blocks_conv());
-    }
-    return gemm_pair_ep(ta, tbc, ep1, 2 * C, K, M, nullptr, nullptr, lac, lbc, EpStore{a->dx, a->Cin, nullptr}, M, a->Cin, 9 * 2 * C, nullptr, st,
-                        pair_tn_blocks_conv());
+    if (p1.x && (a->ldx != a->Cin || !complete(p1))) return SAST_EINVAL;
+    return with_dx_epilogue(p1.x != nullptr, EpStore{a->dx, a->Cin, nullptr}, EpStoreBnRed{a->dx, a->Cin, p1}, [&](const auto& ep) {
+      return gemm_pair_ep(ta, tbc, ep1, 2 * C, K, M, nullptr, nullptr, lac, lbc, ep, M, a->Cin, 9 * 2 * C, nullptr, st, pair_tn_blocks_conv());
+    });
   }
   const LdRowsT2 tb{a->x, a->ldx, a->Cin1, C2 > 0 ? a->x2 : nullptr, a->ldx2};
   if (!a->dx) return launch_gemm_split<TileSplitR>(ta, tb, ep1, 2 * C, K, M, nullptr, tn_splits(2 * C, K, M), nullptr, st);
   if (C2 > 0 && !a->dx2) return SAST_EINVAL;
   const LdRows la{dconv, 2 * C, nullptr};
   const LdWeightNN2 lb{a->w0, a->w1, K, C};
-  BnProducer p2{a->p2_conv_out, a->p2_stats, a->p2_bn_w, a->p2_bn_b, a->p2_bn_ws ? a->p2_bn_ws + 4 * BN_STAT_COPIES * C2 : nullptr, C2};
-  if (p1.x || p2.x) {
-    if ((p1.x && (a->ldx != a->Cin1 || !(p1.stats && p1.gamma && p1.beta && p1.sums))) ||
-        (p2.x && (C2 <= 0 || a->ldx2 != C2 || !(p2.stats && p2.gamma && p2.beta && p2.sums))))
-      return SAST_EINVAL;
-    return gemm_pair_ep(ta, tb, ep1, 2 * C, K, M, nullptr, nullptr, la, lb, EpSplit2BnRed{a->dx, a->dx2, a->Cin1, C2, p1, p2}, M, K, 2 * C,
-                        nullptr, st, pair_tn_blocks_1x1());
-  }
-  return gemm_pair_ep(ta, tb, ep1, 2 * C, K, M, nullptr, nullptr, la, lb, EpSplit2{a->dx, a->dx2, a->Cin1, C2}, M, K, 2 * C, nullptr, st, pair_tn_blocks_1x1());
+  const BnProducer p2 = producer_of(a->p2_conv_out, a->p2_stats, a->p2_bn_w, a->p2_bn_b, a->p2_bn_ws, C2);
+  if ((p1.x && (a->ldx != a->Cin1 || !complete(p1))) || (p2.x && (C2 <= 0 || a->ldx2 != C2 || !complete(p2)))) return SAST_EINVAL;
+  return with_dx_epilogue(p1.x || p2.x, EpSplit2{a->dx, a->dx2, a->Cin1, C2}, EpSplit2BnRed{a->dx, a->dx2, a->Cin1, C2, p1, p2}, [&](const auto& ep) {
+    return gemm_pair_ep(ta, tb, ep1, 2 * C, K, M, nullptr, nullptr, la, lb, ep, M, K, 2 * C, nullptr, st, pair_tn_blocks_1x1());
+  });
 }
 
 // ------------------------------------------------------------------ upsample / concat

@@ -32,6 +32,11 @@ class BaseConv(nn.Module):
             self.sync_bn = SF.sync_group_for(self.bn.process_group)
         return self.sync_bn
 
+    def unit_args(self):
+        """(weight, bn_weight, bn_bias, running_mean, running_var, momentum, eps): this unit the way functional.conv_bn_silu2 takes it"""
+        bn = self.bn
+        return (self.conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.momentum, bn.eps)
+
     def forward_nhwc(self, x, arena=None, sole=False, two_outputs=False):
         """arena: optional `BnArena` handing out zero-filled reduction scratch (one memset per FPN forward) and
         batching the num_batches_tracked increments.  sole: the caller guarantees this conv is the only consumer of x
@@ -47,24 +52,31 @@ class BaseConv(nn.Module):
             sync.exchange_batch(x0.shape[0], x0.device)
         y = SF.conv_bn_silu(x, self.conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var, self.ksize, self.stride,
                             self.training, bn.momentum, bn.eps, ws, sole_consumer=sole, two_outputs=two_outputs, sync=sync)
-        if self.training and bn.num_batches_tracked is not None:
-            if arena is not None:
-                arena.counters.append(bn.num_batches_tracked)
-            else:
-                bn.num_batches_tracked.add_(1)
+        if self.training:
+            _track_batches((self,), arena)
         return y
 
     def sync_item(self, x, arena=None, sole=False, two_outputs=False):
         """this unit's entry of a `forward_sync_group` call (same arguments as forward_nhwc)"""
-        bn = self.bn
-        return dict(x_nhwc=x, w=self.conv.weight, bn_w=bn.weight, bn_b=bn.bias, run_mean=bn.running_mean, run_var=bn.running_var,
-                    ksize=self.ksize, stride=self.stride, momentum=bn.momentum, eps=bn.eps, sole_consumer=sole, two_outputs=two_outputs,
-                    bn_ws=arena.take(SF.bn_ws_floats(bn.num_features)) if arena is not None else None)
+        return dict(zip(("w", "bn_w", "bn_b", "run_mean", "run_var", "momentum", "eps"), self.unit_args()), x_nhwc=x, ksize=self.ksize,
+                    stride=self.stride, sole_consumer=sole, two_outputs=two_outputs,
+                    bn_ws=arena.take(SF.bn_ws_floats(self.bn.num_features)) if arena is not None else None)
 
     def forward(self, x):
         if isinstance(x, (tuple, list)):
             raise TypeError("sast_amd: the two-source (virtual concat) input is an internal NHWC feature; use forward_nhwc")
         return SF.as_nchw_view(self.forward_nhwc(SF.as_nhwc(x)))
+
+
+def _track_batches(convs, arena):
+    """one more training batch seen by these units' BatchNorms (num_batches_tracked): queued on the pass's arena for its one update,
+    else added now"""
+    counters = [c.bn.num_batches_tracked for c in convs if c.bn.num_batches_tracked is not None]
+    if arena is not None:
+        arena.counters.extend(counters)
+    else:
+        for n in counters:
+            n.add_(1)
 
 
 def forward_sync_group(grp, convs, xs, arena, sole=False):
@@ -78,12 +90,7 @@ def forward_sync_group(grp, convs, xs, arena, sole=False):
         x0 = xs[0][0] if isinstance(xs[0], (tuple, list)) else xs[0]
         grp.exchange_batch(x0.shape[0], x0.device)
     ys = SF.conv_bn_silu_sync_group(grp, [c.sync_item(x, arena, sole=s) for c, x, s in zip(convs, xs, soles)])
-    for c in convs:
-        if c.bn.num_batches_tracked is not None:
-            if arena is not None:
-                arena.counters.append(c.bn.num_batches_tracked)
-            else:
-                c.bn.num_batches_tracked.add_(1)
+    _track_batches(convs, arena)
     return ys
 
 
@@ -209,20 +216,13 @@ class CSPLayer(nn.Module):
         self.m = nn.Sequential(*[Bottleneck(hidden, hidden, shortcut, 1.0, depthwise, act=act) for _ in range(n)])
 
     def _pair_args(self):
-        return tuple((c.conv.weight, c.bn.weight, c.bn.bias, c.bn.running_mean, c.bn.running_var, c.bn.momentum, c.bn.eps)
-                     for c in (self.conv1, self.conv2))
+        return self.conv1.unit_args(), self.conv2.unit_args()
 
     def _conv12(self, x, arena, sole_input):
         cs = (self.conv1, self.conv2)
         ws = tuple(arena.take(SF.bn_ws_floats(c.bn.num_features)) if arena is not None else None for c in cs)
-        args = self._pair_args()
-        ys = SF.conv_bn_silu2(x, args[0], args[1], ws, sole_consumer=sole_input)
-        for c in cs:
-            if c.bn.num_batches_tracked is not None:
-                if arena is not None:
-                    arena.counters.append(c.bn.num_batches_tracked)
-                else:
-                    c.bn.num_batches_tracked.add_(1)
+        ys = SF.conv_bn_silu2(x, *self._pair_args(), ws, sole_consumer=sole_input)
+        _track_batches(cs, arena)
         return ys
 
     def forward_nhwc(self, x, arena=None, sole_input=False, two_outputs=False):
@@ -233,7 +233,7 @@ class CSPLayer(nn.Module):
             # backward whose dX is already the sum of the two input gradients
             x1, x2 = self._conv12(x, arena, sole_input)
         elif not self.training and SF.CONV_PAIR and not torch.is_grad_enabled():
-            x1, x2 = SF.conv_bn_silu2_infer(x, self._pair_args()[0], self._pair_args()[1])     # inference: one launch for both
+            x1, x2 = SF.conv_bn_silu2_infer(x, *self._pair_args())     # inference: one launch for both
         elif self.training and sync_active(self.conv1) and SF.SYNC_BN_GROUPS:
             # SyncBatchNorm: the stacked launch sees one process's rows only; the two units still share ONE statistics all-reduce
             x1, x2 = forward_sync_group(self.conv1.sync_group(), (self.conv1, self.conv2), (x, x), arena)

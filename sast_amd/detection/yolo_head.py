@@ -17,7 +17,7 @@ import torch.nn as nn
 
 from .. import _lib as L
 from .. import functional as SF
-from .network_blocks import BaseConv, BnArena, DWConv, bn_scratch_floats, forward_sync_group, pass_sync_group
+from .network_blocks import BaseConv, BnArena, DWConv, _track_batches, bn_scratch_floats, forward_sync_group, pass_sync_group
 
 
 class _PredConv(nn.Module):
@@ -89,10 +89,9 @@ class YOLOXHead(nn.Module):
                     # the first conv of both towers reads the stem output: one stacked 3x3 GEMM + shared BatchNorm launches, and (sole
                     # consumer of the stem output) the stem's BatchNorm-backward reduction in the pair's dX epilogue
                     c0, r0 = self.cls_convs[k][0], self.reg_convs[k][0]
-                    args = [(c.conv.weight, c.bn.weight, c.bn.bias, c.bn.running_mean, c.bn.running_var, c.bn.momentum, c.bn.eps) for c in (c0, r0)]
                     ws = tuple(ar.take(SF.bn_ws_floats(c.bn.num_features)) for c in (c0, r0))
-                    cf, rf = SF.conv_bn_silu2(x, args[0], args[1], ws, sole_consumer=True, ksize=3)
-                    ar.counters.extend(c.bn.num_batches_tracked for c in (c0, r0) if c.bn.num_batches_tracked is not None)
+                    cf, rf = SF.conv_bn_silu2(x, c0.unit_args(), r0.unit_args(), ws, sole_consumer=True, ksize=3)
+                    _track_batches((c0, r0), ar)
                     first = 1
                 else:
                     cf, rf = x, x          # the stem output feeds both towers; inside a tower every conv has one consumer
@@ -130,8 +129,7 @@ class YOLOXHead(nn.Module):
             x = self.stems[k].forward_nhwc(x)
             if SF.CONV_PAIR and not self.depthwise:     # the first conv of both towers reads the stem output: one launch over the stacked 3x3 weights
                 c0, r0 = self.cls_convs[k][0], self.reg_convs[k][0]
-                cf, rf = SF.conv_bn_silu2_infer(x, *[(c.conv.weight, c.bn.weight, c.bn.bias, c.bn.running_mean, c.bn.running_var,
-                                                     c.bn.momentum, c.bn.eps) for c in (c0, r0)], ksize=3)
+                cf, rf = SF.conv_bn_silu2_infer(x, c0.unit_args(), r0.unit_args(), ksize=3)
                 for conv in list(self.cls_convs[k])[1:]:
                     cf = conv.forward_nhwc(cf)
                 for conv in list(self.reg_convs[k])[1:]:

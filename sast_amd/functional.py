@@ -1185,23 +1185,63 @@ def _bn_ws_blocks(bn_ws, Cout):
     return raw[:4 * n].view(torch.float64), raw[4 * n:]      # write it like the kernels do, outside autograd's version counting
 
 
-def _cbs_fwd_args(x, x2, w, bn_w, bn_b, run_mean, run_var, ksize, stride, training, momentum, eps, bn_ws):
-    """the argument block of one conv + BatchNorm + SiLU forward and what its backward keeps: (SastConvBnArgs, state dict)"""
-    _need_gpu(x, w)
+def _conv_sources(x, x2, weights, ksize, stride):
+    """what every conv + BatchNorm + SiLU entry point checks of its input: contiguous NHWC source(s), channels_last weights, the optional
+    second source of a virtual channel concat [x | x2] (1x1 stride-1 convs: read in place, never materialised)
+    -> (x, x2, B, H, W, Cin, Cin1, Ho, Wo) with Cin1 the channels of x and Cin those of both sources"""
+    _need_gpu(x, *weights)
     x = x.contiguous()
-    if not is_channels_last_weight(w):
+    if not all(is_channels_last_weight(w) for w in weights):
         raise RuntimeError("sast_amd: conv weights must be stored channels_last ([Cout][KH][KW][Cin])")
-    B, H, W, Cin = x.shape
-    Cin1 = Cin
-    if x2 is not None:       # virtual channel concat [x | x2] (1x1 convs): read in place, never materialised
+    B, H, W, Cin1 = x.shape
+    Cin = Cin1
+    if x2 is not None:
         if ksize != 1 or stride != 1 or x2.shape[:3] != x.shape[:3]:
             raise RuntimeError("sast_amd: a two-source input is supported for 1x1 stride-1 convs of equal spatial size")
         x2 = x2.contiguous()
         Cin = Cin1 + x2.shape[-1]
+    pad = (ksize - 1) // 2
+    return x, x2, B, H, W, Cin, Cin1, (H + 2 * pad - ksize) // stride + 1, (W + 2 * pad - ksize) // stride + 1
+
+
+def _fit_producers(producers, x2, Cin1, Cin):
+    """forward side: the producers (BnHandles of x, x2) whose channel counts are those of the source they stand behind"""
+    p1, p2 = producers
+    if p1 is not None and p1.cout != Cin1:
+        p1 = None
+    if p2 is not None and (x2 is None or p2.cout != Cin - Cin1):
+        p2 = None
+    return p1, p2
+
+
+def _live_producers(producers, need, dx2):
+    """backward side: the producers this call's dX epilogue reduces for (an input gradient is computed, nobody reduced them yet)
+    -> ((p1, p2), the p_* / p2_* fields of the argument block)"""
+    p1, p2 = producers if need else (None, None)
+    if p1 is not None and p1.red_done:
+        p1 = None
+    if p2 is not None and (p2.red_done or dx2 is None):
+        p2 = None
+    pk = {}
+    for pre, h in (("p_", p1), ("p2_", p2)):
+        if h is not None:
+            pk.update({pre + "conv_out": h.conv_out, pre + "stats": h.stats, pre + "bn_w": h.bn_w, pre + "bn_b": h.bn_b,
+                       pre + "bn_ws": h.bn_ws})
+    return (p1, p2), pk
+
+
+def _mark_served(handles):
+    """the launches that reduce for these producers are enqueued: their own backward skips its reduction"""
+    for h in handles:
+        if h is not None:
+            h.red_done = True
+
+
+def _cbs_fwd_args(x, x2, w, bn_w, bn_b, run_mean, run_var, ksize, stride, training, momentum, eps, bn_ws):
+    """the argument block of one conv + BatchNorm + SiLU forward and what its backward keeps: (SastConvBnArgs, state dict)"""
+    x, x2, B, H, W, Cin, Cin1, Ho, Wo = _conv_sources(x, x2, (w,), ksize, stride)
     Cout = w.shape[0]
     groups = _conv_groups(w, Cin, x2)
-    pad = (ksize - 1) // 2
-    Ho, Wo = (H + 2 * pad - ksize) // stride + 1, (W + 2 * pad - ksize) // stride + 1
     M = B * Ho * Wo
     dev = x.device
     conv_out = torch.empty(M, Cout, device=dev)
@@ -1223,12 +1263,9 @@ def _cbs_fwd_links(st, training, producers, handle):
     w, bn_w, bn_b = st["params"]
     B, H, W, Cin, Cin1, Cout, ksize, stride = st["meta"][:8]
     own = handle.fill(conv_out, stats, bn_w, bn_b, bn_ws, Cout) if (training and handle is not None) else None
-    p1, p2 = producers if (training and stride == 1 and st["groups"] == 1) else (None, None)   # (the depth-wise stencil has no dX epilogue to fold into)
-    if p1 is not None and p1.cout != Cin1:
-        p1 = None
-    if p2 is not None and (x2 is None or p2.cout != Cin - Cin1):
-        p2 = None
-    return own, (p1, p2)
+    if not (training and stride == 1 and st["groups"] == 1):      # (the depth-wise stencil has no dX epilogue to fold into)
+        return own, (None, None)
+    return own, _fit_producers(producers, x2, Cin1, Cin)
 
 
 def _cbs_bwd_args(saved, params, meta, groups, own, producers, need1, need2, dy, dy2):
@@ -1246,131 +1283,89 @@ def _cbs_bwd_args(saved, params, meta, groups, own, producers, need1, need2, dy,
     dx = torch.empty_like(x) if need else None
     dx2 = torch.empty_like(x2) if (need and x2 is not None) else None
     ws = torch.empty(M * Cout, device=x.device)
-    p1, p2 = producers if need else (None, None)
-    if p1 is not None and p1.red_done:
-        p1 = None
-    if p2 is not None and (p2.red_done or dx2 is None):
-        p2 = None
-    pk = {}
-    for pre, h in (("p_", p1), ("p2_", p2)):
-        if h is not None:
-            pk.update({pre + "conv_out": h.conv_out, pre + "stats": h.stats, pre + "bn_w": h.bn_w, pre + "bn_b": h.bn_b,
-                       pre + "bn_ws": h.bn_ws})
+    served, pk = _live_producers(producers, need, dx2)
     pg = _ParamGrads(w, bn_w, bn_b)
     a = _fill(L.SastConvBnArgs(), B=B, H=H, W=W, Cin=Cin, Cout=Cout, ksize=ksize, stride=stride, training=training, ldx=Cin1,
               ldy=Cout, lddy=Cout, lddx=Cin1, bn_ws_zeroed=1, bn_red_done=int(own is not None and own.red_done), momentum=momentum,
               eps=eps, x=x, w=w, bn_w=bn_w, bn_b=bn_b, conv_out=conv_out, stats=stats, dy=dy, dx=_ptr(dx), dw=pg[0],
               d_bn_w=pg[1], d_bn_b=pg[2], bn_ws=bn_ws, ws=ws, x2=_ptr(x2), dx2=_ptr(dx2), Cin1=Cin1, ldx2=Cin - Cin1, dy2=_ptr(dy2),
               groups=groups, **pk)
-    return a, dx, dx2, pg, (p1, p2), (dy, dy2, ws)
+    return a, dx, dx2, pg, served, (dy, dy2, ws)
 
 
-class _ConvBnSilu(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, x2, w, bn_w, bn_b, run_mean, run_var, ksize, stride, training, momentum, eps, bn_ws, producers, handle, two_y,
-                sync=None):
-        a, st = _cbs_fwd_args(x, x2, w, bn_w, bn_b, run_mean, run_var, ksize, stride, training, momentum, eps, bn_ws)
-        M, B, Cout = st["meta"][11], st["meta"][0], st["meta"][5]
-        bn_ws = st["saved"][4]
-        m_total = 0
-        if sync is not None and training and sync.active():
-            a.sync_phase = 1
-            L.check(L.lib().sast_conv_bn_silu_fwd(C.byref(a), _stream()), "conv_bn_silu_fwd")
-            sync.all_reduce(_bn_ws_blocks(bn_ws, Cout)[0])
-            m_total = sync.rows_total(M, B)
-            a.sync_phase, a.m_total = 2, m_total
-        L.check(L.lib().sast_conv_bn_silu_fwd(C.byref(a), _stream()), "conv_bn_silu_fwd")
-        ctx.sync = (sync, m_total) if m_total else None
-        ctx.save_for_backward(*st["saved"])
-        ctx.params, ctx.meta, ctx.groups = st["params"], st["meta"], st["groups"]
-        ctx.handle, ctx.producers = _cbs_fwd_links(st, training, producers, handle)
-        ctx.two_y = bool(two_y)
-        y = st["y"]
-        return (y, y.view_as(y)) if two_y else y     # two aliases for two consumers: see _LSTM.forward
-
-    @staticmethod
-    def backward(ctx, dy, dy2=None):
-        _consume(ctx, "conv_bn_silu")
-        Cout = ctx.meta[5]
-        a, dx, dx2, pg, served, _keep = _cbs_bwd_args(ctx.saved_tensors, ctx.params, ctx.meta, ctx.groups, ctx.handle, ctx.producers,
-                                                      ctx.needs_input_grad[0], ctx.needs_input_grad[1], dy, dy2)
-        if ctx.sync is not None:
-            sync, m_total = ctx.sync
-            a.sync_phase = 1
-            L.check(L.lib().sast_conv_bn_silu_bwd(C.byref(a), _stream()), "conv_bn_silu_bwd")
-            # (phase 1 also added this process's (sum dz, sum dz * xhat) to d_bn_b / d_bn_w: the affine gradients stay local)
-            sync.all_reduce(_bn_ws_blocks(ctx.saved_tensors[4], Cout)[1])
-            a.sync_phase, a.m_total, a.d_bn_w, a.d_bn_b = 2, m_total, None, None
-        L.check(L.lib().sast_conv_bn_silu_bwd(C.byref(a), _stream()), "conv_bn_silu_bwd")
-        _dw_hold((ctx.saved_tensors, _keep, pg))
-        for h in served:
-            if h is not None:
-                h.red_done = True
-        return (dx, dx2) + pg.out() + (None,) * 12
+def _cbs_fwd(a):
+    L.check(L.lib().sast_conv_bn_silu_fwd(C.byref(a), _stream()), "conv_bn_silu_fwd")
 
 
-_CBS_UNIT_IN = 7      # tensors per unit of _ConvBnSiluSyncGroup.apply: x, x2, w, bn_w, bn_b, running_mean, running_var
+def _cbs_bwd(a):
+    L.check(L.lib().sast_conv_bn_silu_bwd(C.byref(a), _stream()), "conv_bn_silu_bwd")
 
 
-class _ConvBnSiluSyncGroup(torch.autograd.Function):
-    """SEVERAL independent conv + BatchNorm + SiLU units under SyncBatchNorm as one autograd node: phase 1 of every unit, ONE
-    (coalesced) statistics all-reduce, phase 2 of every unit -- forward and backward.  The dependent chain of a multi-rank step is the
-    number of collectives, not of units: CSPLayer.conv1 / conv2 (same input), the three levels of the YOLOX head (stems; first and second
-    3x3 of both towers) are such sets.  `units`: one tuple (ksize, stride, momentum, eps, bn_ws, producers, handle, two_y) per unit;
-    `tensors`: _CBS_UNIT_IN per unit.  Training mode only (the caller checked `sync.active()`)."""
+_CBS_UNIT_IN = 7      # tensors per unit of _ConvBnSiluUnits.apply: x, x2, w, bn_w, bn_b, running_mean, running_var
+_CBS_SAVED = 5        # tensors a unit saves for its backward: x, x2, conv_out, stats, bn_ws
+
+
+class _ConvBnSiluUnits(torch.autograd.Function):
+    """one or SEVERAL independent conv + BatchNorm + SiLU units as one autograd node.  `units`: one tuple (ksize, stride, training,
+    momentum, eps, bn_ws, producers, handle, two_y) per unit; `tensors`: _CBS_UNIT_IN per unit; outputs: y per unit, (y, alias of y)
+    where two_y (two aliases for two consumers: see _LSTM.forward).
+    `sync` None: one forward call and one backward call per unit.
+    `sync` a SyncBatchNormGroup (training mode; the caller checked `sync.active()`): phase 1 of every unit, ONE (coalesced) statistics
+    all-reduce, phase 2 of every unit -- forward and backward.  The dependent chain of a multi-rank step is the number of collectives,
+    not of units: CSPLayer.conv1 / conv2 (same input), the three levels of the YOLOX head (stems; first and second 3x3 of both towers)
+    are such sets."""
 
     @staticmethod
     def forward(ctx, sync, units, *tensors):
-        n = len(units)
-        jobs, saved, outs = [], [], []
-        for i, (ksize, stride, momentum, eps, bn_ws, producers, handle, two_y) in enumerate(units):
-            x, x2, w, bn_w, bn_b, rm, rv = tensors[_CBS_UNIT_IN * i:_CBS_UNIT_IN * (i + 1)]
-            a, st = _cbs_fwd_args(x, x2, w, bn_w, bn_b, rm, rv, ksize, stride, True, momentum, eps, bn_ws)
-            a.sync_phase = 1
-            L.check(L.lib().sast_conv_bn_silu_fwd(C.byref(a), _stream()), "conv_bn_silu_fwd")
+        jobs = []
+        for i, u in enumerate(units):
+            a, st = _cbs_fwd_args(*tensors[_CBS_UNIT_IN * i:_CBS_UNIT_IN * (i + 1)], *u[:6])
+            a.sync_phase = int(sync is not None)
+            _cbs_fwd(a)
             jobs.append((a, st))
-        sync.all_reduce_many([_bn_ws_blocks(st["saved"][4], st["meta"][5])[0] for _a, st in jobs])
-        ctx.units = []
-        for (a, st), (ksize, stride, momentum, eps, bn_ws, producers, handle, two_y) in zip(jobs, units):
-            m_total = sync.rows_total(st["meta"][11], st["meta"][0])
-            a.sync_phase, a.m_total = 2, m_total
-            L.check(L.lib().sast_conv_bn_silu_fwd(C.byref(a), _stream()), "conv_bn_silu_fwd")
-            own, prods = _cbs_fwd_links(st, True, producers, handle)
-            ctx.units.append((st["params"], st["meta"], st["groups"], own, prods, bool(two_y), m_total, [t is not None for t in st["saved"]]))
-            saved.extend(t for t in st["saved"] if t is not None)
+        if sync is not None:
+            sync.all_reduce_many([_bn_ws_blocks(st["saved"][4], st["meta"][5])[0] for _a, st in jobs])
+        ctx.sync, ctx.units = sync, []
+        saved, outs = [], []
+        for (a, st), u in zip(jobs, units):
+            training, (producers, handle, two_y) = u[2], u[6:]
+            m_total = 0
+            if sync is not None:
+                m_total = sync.rows_total(st["meta"][11], st["meta"][0])
+                a.sync_phase, a.m_total = 2, m_total
+                _cbs_fwd(a)
+            ctx.units.append((st["params"], st["meta"], st["groups"]) + _cbs_fwd_links(st, training, producers, handle) + (bool(two_y), m_total))
+            saved.extend(st["saved"])
             y = st["y"]
             outs.extend((y, y.view_as(y)) if two_y else (y,))
-        ctx.sync = sync
         ctx.save_for_backward(*saved)
         return tuple(outs)
 
     @staticmethod
     def backward(ctx, *dys):
-        _consume(ctx, "conv_bn_silu (SyncBatchNorm group)")
-        sv, k, d = list(ctx.saved_tensors), 0, 0
+        _consume(ctx, "conv_bn_silu")
+        sv, sync, d = ctx.saved_tensors, ctx.sync, 0
         jobs = []
-        for i, (params, meta, groups, own, prods, two_y, m_total, present) in enumerate(ctx.units):
-            saved = []
-            for has in present:
-                saved.append(sv[k] if has else None)
-                k += has
+        for i, (params, meta, groups, own, prods, two_y, m_total) in enumerate(ctx.units):
             dy, dy2 = (dys[d], dys[d + 1]) if two_y else (dys[d], None)
             d += 2 if two_y else 1
-            a, dx, dx2, pg, served, keep = _cbs_bwd_args(tuple(saved), params, meta, groups, own, prods,
-                                                         ctx.needs_input_grad[2 + _CBS_UNIT_IN * i], ctx.needs_input_grad[3 + _CBS_UNIT_IN * i], dy, dy2)
-            a.sync_phase = 1
-            L.check(L.lib().sast_conv_bn_silu_bwd(C.byref(a), _stream()), "conv_bn_silu_bwd")
-            jobs.append((a, dx, dx2, pg, served, keep, saved[4], meta[5], m_total))
-        ctx.sync.all_reduce_many([_bn_ws_blocks(ws, cout)[1] for (_a, _dx, _dx2, _pg, _s, _k, ws, cout, _m) in jobs])
+            need1, need2 = ctx.needs_input_grad[2 + _CBS_UNIT_IN * i:4 + _CBS_UNIT_IN * i]
+            a, dx, dx2, pg, served, keep = _cbs_bwd_args(sv[_CBS_SAVED * i:_CBS_SAVED * (i + 1)], params, meta, groups, own, prods,
+                                                         need1, need2, dy, dy2)
+            a.sync_phase = int(sync is not None)
+            _cbs_bwd(a)
+            jobs.append((a, dx, dx2, pg, served, keep, m_total))
+        if sync is not None:
+            # (phase 1 also added this process's (sum dz, sum dz * xhat) to d_bn_b / d_bn_w: the affine gradients stay local)
+            sync.all_reduce_many([_bn_ws_blocks(sv[_CBS_SAVED * i + 4], u[1][5])[1] for i, u in enumerate(ctx.units)])
         grads = [None, None]
-        for a, dx, dx2, pg, served, _keep, _ws, _cout, m_total in jobs:
-            a.sync_phase, a.m_total, a.d_bn_w, a.d_bn_b = 2, m_total, None, None
-            L.check(L.lib().sast_conv_bn_silu_bwd(C.byref(a), _stream()), "conv_bn_silu_bwd")
-            for h in served:
-                if h is not None:
-                    h.red_done = True
+        for a, dx, dx2, pg, served, _keep, m_total in jobs:
+            if sync is not None:
+                a.sync_phase, a.m_total, a.d_bn_w, a.d_bn_b = 2, m_total, None, None
+                _cbs_bwd(a)
+            _mark_served(served)
             grads.extend((dx, dx2) + pg.out() + (None, None))
-        _dw_hold((sv, jobs))
+        _dw_hold((sv, [(keep, pg) for _a, _dx, _dx2, pg, _served, keep, _m in jobs]))
         return tuple(grads)
 
 
@@ -1385,18 +1380,19 @@ def conv_bn_silu_sync_group(sync: "SyncBatchNormGroup", items):
         x, x2 = xin if isinstance(xin, (tuple, list)) else (xin, None)
         two = bool(it.get("two_outputs", False)) and TWO_OUT and torch.is_grad_enabled()
         handle = None if two else BnHandle()
-        units.append((int(it["ksize"]), int(it["stride"]), float(it.get("momentum", 0.1)), float(it.get("eps", 1e-5)), it.get("bn_ws"),
+        units.append((int(it["ksize"]), int(it["stride"]), True, float(it.get("momentum", 0.1)), float(it.get("eps", 1e-5)), it.get("bn_ws"),
                       _producers(x, x2, it.get("sole_consumer", False)), handle, two))
         tensors.extend((x, x2, it["w"], it["bn_w"], it["bn_b"], it["run_mean"], it["run_var"]))
-    flat = _ConvBnSiluSyncGroup.apply(sync, units, *tensors)
+    flat = _ConvBnSiluUnits.apply(sync, units, *tensors)
     outs, k = [], 0
     for it, u in zip(items, units):
-        if u[7]:
+        handle, two = u[7:9]
+        if two:
             outs.append((flat[k], flat[k + 1]))
             k += 2
         else:
             y = flat[k]
-            y._sast_bn = u[6]      # lets a sole consumer of y fold this conv's BatchNorm-backward reduction into its dX epilogue
+            y._sast_bn = handle    # lets a sole consumer of y fold this conv's BatchNorm-backward reduction into its dX epilogue
             k += 1
             outs.append((y, y) if it.get("two_outputs", False) else y)
     return outs
@@ -1423,21 +1419,9 @@ class _ConvBnSilu2(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, x2, w0, bnw0, bnb0, rm0, rv0, w1, bnw1, bnb1, rm1, rv1, mom0, eps0, mom1, eps1, ws0, ws1, producers, handles, ksize):
-        _need_gpu(x, w0, w1)
-        x = x.contiguous()
-        for w in (w0, w1):
-            if not is_channels_last_weight(w):
-                raise RuntimeError("sast_amd: conv weights must be stored channels_last ([Cout][KH][KW][Cin])")
-        B, H, W, Cin1 = x.shape
-        Cin = Cin1
-        if x2 is not None:
-            if x2.shape[:3] != x.shape[:3]:
-                raise RuntimeError("sast_amd: the two sources of a virtual concat need equal spatial size")
-            x2 = x2.contiguous()
-            Cin = Cin1 + x2.shape[-1]
+        x, x2, B, H, W, Cin, Cin1, _Ho, _Wo = _conv_sources(x, x2, (w0, w1), ksize, 1)
         Cout = w0.shape[0]
-        if w1.shape[0] != Cout or tuple(w0.shape[1:]) != (Cin, ksize, ksize) or tuple(w1.shape[1:]) != (Cin, ksize, ksize) or \
-                ksize not in (1, 3) or (ksize == 3 and x2 is not None):
+        if w1.shape[0] != Cout or tuple(w0.shape[1:]) != (Cin, ksize, ksize) or tuple(w1.shape[1:]) != (Cin, ksize, ksize) or ksize not in (1, 3):
             raise RuntimeError("sast_amd: conv_bn_silu2 needs two 1x1 (or 3x3, single-source) convs of the same input with equal Cout")
         M, dev = B * H * W, x.device
         co = [torch.empty(M, Cout, device=dev) for _ in range(2)]
@@ -1454,12 +1438,7 @@ class _ConvBnSilu2(torch.autograd.Function):
         ctx.params = (w0, bnw0, bnb0, w1, bnw1, bnb1)
         ctx.meta = (B, H, W, Cin, Cin1, Cout, mom0, eps0, mom1, eps1, M, ksize)
         ctx.handles = (handles[0].fill(co[0], st[0], bnw0, bnb0, ws0, Cout), handles[1].fill(co[1], st[1], bnw1, bnb1, ws1, Cout))
-        p1, p2 = producers
-        if p1 is not None and p1.cout != Cin1:
-            p1 = None
-        if p2 is not None and (x2 is None or p2.cout != Cin - Cin1):
-            p2 = None
-        ctx.producers = (p1, p2)
+        ctx.producers = _fit_producers(producers, x2, Cin1, Cin)
         return ys[0], ys[1]
 
     @staticmethod
@@ -1474,16 +1453,7 @@ class _ConvBnSilu2(torch.autograd.Function):
         dx = torch.empty_like(x) if need else None
         dx2 = torch.empty_like(x2) if (need and x2 is not None) else None
         dws = torch.empty(M, 2 * Cout, device=x.device)      # rows [dconv0 | dconv1]
-        p1, p2 = ctx.producers if need else (None, None)
-        if p1 is not None and p1.red_done:
-            p1 = None
-        if p2 is not None and (p2.red_done or dx2 is None):
-            p2 = None
-        pk = {}
-        for pre, h in (("p_", p1), ("p2_", p2)):
-            if h is not None:
-                pk.update({pre + "conv_out": h.conv_out, pre + "stats": h.stats, pre + "bn_w": h.bn_w, pre + "bn_b": h.bn_b,
-                           pre + "bn_ws": h.bn_ws})
+        served, pk = _live_producers(ctx.producers, need, dx2)
         h0, h1 = ctx.handles
         pg = _ParamGrads(w0, bnw0, bnb0, w1, bnw1, bnb1)
         a = _fill(L.SastConvBn2Args(), B=B, H=H, W=W, Cin=Cin, Cout=Cout, ldx=Cin1, Cin1=Cin1, ldx2=Cin - Cin1, bn_ws_zeroed=1, training=1, ksize=ksize,
@@ -1493,9 +1463,7 @@ class _ConvBnSilu2(torch.autograd.Function):
                   d_bn_w1=pg[4], d_bn_b0=pg[2], d_bn_b1=pg[5], ws0=dws, dx=_ptr(dx), dx2=_ptr(dx2), **pk)
         L.check(L.lib().sast_conv_bn_silu2_bwd(C.byref(a), _stream()), "conv_bn_silu2_bwd")
         _dw_hold((x, x2, co0, co1, st0, st1, ws0, ws1, dy0, dy1, dws, pg))
-        for h in (p1, p2):
-            if h is not None:
-                h.red_done = True
+        _mark_served(served)
         g = pg.out()        # forward(ctx, x, x2, w0, bnw0, bnb0, rm0, rv0, w1, bnw1, bnb1, rm1, rv1, ... 9 more)
         return (dx, dx2) + g[0:3] + (None, None) + g[3:6] + (None,) * 11
 
@@ -1505,19 +1473,8 @@ def conv_bn_silu2_infer(x_nhwc, conv0, conv1, ksize=1):
     """eval mode, no autograd: two convs (1x1, or 3x3 stride 1) of the same input + BatchNorm(running statistics) + SiLU in ONE
     launch over the stacked weights.  conv0 / conv1 as in conv_bn_silu2."""
     x, x2 = x_nhwc if isinstance(x_nhwc, (tuple, list)) else (x_nhwc, None)
-    _need_gpu(x)
-    x = x.contiguous()
     (w0, g0, b0, rm0, rv0, _m0, e0), (w1, g1, b1, rm1, rv1, _m1, e1) = conv0, conv1
-    for w in (w0, w1):
-        if not is_channels_last_weight(w):
-            raise RuntimeError("sast_amd: conv weights must be stored channels_last ([Cout][KH][KW][Cin])")
-    B, H, W, Cin1 = x.shape
-    Cin = Cin1
-    if x2 is not None:
-        if ksize != 1 or x2.shape[:3] != x.shape[:3]:
-            raise RuntimeError("sast_amd: a two-source input is supported for 1x1 convs of equal spatial size")
-        x2 = x2.contiguous()
-        Cin = Cin1 + x2.shape[-1]
+    x, x2, B, H, W, Cin, Cin1, _Ho, _Wo = _conv_sources(x, x2, (w0, w1), ksize, 1)
     Cout = w0.shape[0]
     if w1.shape[0] != Cout or tuple(w0.shape[1:]) != (Cin, ksize, ksize) or tuple(w1.shape[1:]) != (Cin, ksize, ksize):
         raise RuntimeError("sast_amd: conv_bn_silu2_infer needs two convs of the same input with equal shapes")
@@ -1571,13 +1528,12 @@ def conv_bn_silu(x_nhwc, w, bn_w, bn_b, run_mean, run_var, ksize, stride, traini
     # sole_consumer: the caller guarantees that this conv is the ONLY consumer of its input tensor(s); where such an input
     # is itself a conv_bn_silu output (it carries a BnHandle), that producer's BatchNorm-backward reduction is folded into
     # this conv's dX epilogue (one launch fewer per conv in the backward pass)
-    prods = _producers(x, x2, sole_consumer)
+    handle = BnHandle() if (training and not two_outputs) else None
+    unit = (ksize, stride, bool(training), float(momentum), float(eps), bn_ws, _producers(x, x2, sole_consumer), handle, bool(two_outputs))
+    out = _ConvBnSiluUnits.apply(sync, [unit], x, x2, w, bn_w, bn_b, run_mean, run_var)
     if two_outputs:     # (y, y_alias) for an output with two consumers: their gradients meet inside the BatchNorm-backward kernels
-        return _ConvBnSilu.apply(x, x2, w, bn_w, bn_b, run_mean, run_var, ksize, stride, True, float(momentum), float(eps), bn_ws, prods,
-                                 None, True, sync)
-    handle = BnHandle() if training else None
-    y = _ConvBnSilu.apply(x, x2, w, bn_w, bn_b, run_mean, run_var, ksize, stride, bool(training), float(momentum), float(eps), bn_ws, prods,
-                          handle, False, sync)
+        return out
+    y = out[0]
     if handle is not None:
         y._sast_bn = handle      # lets a sole consumer of y fold this conv's BatchNorm-backward reduction into its dX epilogue
     return y
@@ -1585,20 +1541,8 @@ def conv_bn_silu(x_nhwc, w, bn_w, bn_b, run_mean, run_var, ksize, stride, traini
 
 def _conv_bn_silu_infer(x, x2, w, bn_w, bn_b, run_mean, run_var, ksize, stride, eps):
     """eval mode, no autograd: conv + BatchNorm(running statistics) + SiLU in ONE launch (BN + SiLU in the GEMM epilogue)."""
-    _need_gpu(x, w)
-    x = x.contiguous()
-    if not is_channels_last_weight(w):
-        raise RuntimeError("sast_amd: conv weights must be stored channels_last ([Cout][KH][KW][Cin])")
-    B, H, W, Cin = x.shape
-    Cin1 = Cin
-    if x2 is not None:
-        if ksize != 1 or stride != 1 or x2.shape[:3] != x.shape[:3]:
-            raise RuntimeError("sast_amd: a two-source input is supported for 1x1 stride-1 convs of equal spatial size")
-        x2 = x2.contiguous()
-        Cin = Cin1 + x2.shape[-1]
+    x, x2, B, H, W, Cin, Cin1, Ho, Wo = _conv_sources(x, x2, (w,), ksize, stride)
     Cout = w.shape[0]
-    pad = (ksize - 1) // 2
-    Ho, Wo = (H + 2 * pad - ksize) // stride + 1, (W + 2 * pad - ksize) // stride + 1
     y = torch.empty(B, Ho, Wo, Cout, device=x.device)
     a = _fill(L.SastConvBnArgs(), B=B, H=H, W=W, Cin=Cin, Cout=Cout, ksize=ksize, stride=stride, training=0, ldx=Cin1, ldy=Cout,
               bn_ws_zeroed=1, momentum=0.0, eps=eps, x=x, w=w, bn_w=bn_w, bn_b=bn_b, run_mean=run_mean, run_var=run_var, y=y,
