@@ -866,7 +866,23 @@ int sast_augment_labels(const float* labels, const int32_t* counts, const int32_
  *   precision fp64 [10][101][K][4] (COCOeval.eval['precision'] at maxDets 100), result fp64 [8 + SAST_EVAL_STATE_WORDS]: AP, AP_50, AP_75,
  *          AP_S, AP_M, AP_L, 2 unused, then the state words
  * iou_thr: the 10 doubles of np.linspace(.5, .95, 10); rec_thr: the 101 of np.linspace(0, 1, 101).  A <= 8192, max_labels_per_frame <= 128,
- * K <= 4, max_detections < 2^30. */
+ * K <= 4, max_detections < 2^30.
+ * sast_eval_accumulate cuts every category's sorted records into chunks of SAST_EVAL_ACC_CHUNK records (a knob of the registry below,
+ * default 1024, honoured as an exact count >= 1) and walks the chunks in parallel: counts per chunk, a scan over the chunks, the
+ * precision maximum per chunk, a suffix maximum, and a backward walk per chunk that writes the recall thresholds first reached inside it.
+ * All counts are integers, every precision and recall is the one fp64 division of the sequential walk, the envelope is a maximum: the
+ * table does not depend on the chunk length, bit for bit.  The per-chunk partials (1 KiB per chunk) live in sort_ws after the sort:
+ * sast_eval_sort_ws_bytes returns the larger of the sort's and the chunks' need AT THE KNOB'S CURRENT VALUE, and sast_eval_accumulate
+ * refuses (SAST_EINVAL) a sort_ws_bytes below it -- a host that changes the knob asks for the size again.
+ * sast_evmerge_append(dst, src) appends the buffer `src` to `dst` on the device: afterwards dst is what it would be had it been fed
+ * src's frames after its own (src is left as it was).  Images, img_t, ground-truth rows, detection rows and records are appended, gt_img /
+ * det_img grow by dst's image count, the index bits of rec_key by dst's record count (the index breaks score ties: dst's records keep
+ * going first), state words 0-7, 11 and 12.. are added, and so are src's own refusal counters 8-10.  All counts are read on the device (two
+ * launches, no host synchronisation, replayable in a graph).  All or nothing: when src's images, ground-truth rows, detections or records
+ * do not fit what is left of dst's max_images, max_images * max_labels_per_frame or max_detections, nothing is appended and src's image
+ * count is added to dst's refusal word of every capacity that was exceeded (8, 10, 9 in that order of capacities).  Refused on the host
+ * (SAST_EINVAL): null pointers, dst == src or one state for both, differing K / min_diag2 / min_side, src->max_labels_per_frame >
+ * dst->max_labels_per_frame.  Only the capacities, K, the filter and the state / table / record pointers of the two are read. */
 #define SAST_EVAL_STATE_WORDS 32
 #define SAST_EVAL_MAX_CLASSES 4
 #define SAST_EVAL_IOU_THRS 10
@@ -895,6 +911,7 @@ int sast_eval_reset(const SastEvalArgs* a, sast_stream_t stream);
 int sast_eval_add(const SastEvalArgs* a, sast_stream_t stream);
 size_t sast_eval_sort_ws_bytes(int64_t max_detections);
 int sast_eval_accumulate(const SastEvalArgs* a, sast_stream_t stream);
+int sast_evmerge_append(const SastEvalArgs* dst, const SastEvalArgs* src, sast_stream_t stream);
 
 /* ---- tuning knobs.  Every SAST_* environment variable the library reads (tile / split / launch-shape choices, all defaulting to the
  * measured-best setting: DESIGN.md section 7) goes through one registry: the value is read from the environment at first use and cached;

@@ -222,6 +222,7 @@ _SIGNATURES = {
     "sast_eval_add": (C.c_int, [C.POINTER(SastEvalArgs), P]),
     "sast_eval_sort_ws_bytes": (C.c_size_t, [C.c_int64]),
     "sast_eval_accumulate": (C.c_int, [C.POINTER(SastEvalArgs), P]),
+    "sast_evmerge_append": (C.c_int, [C.POINTER(SastEvalArgs), C.POINTER(SastEvalArgs), P]),
 }
 
 _lib = None
@@ -250,7 +251,11 @@ def lib():
             print(f"[sast_amd] WARNING: SAST_LIB_PATH is set: loading {LIB_PATH} instead of the product library {DEFAULT_LIB_PATH}", file=sys.stderr)
         l = C.CDLL(LIB_PATH)
         for name, (res, args) in _SIGNATURES.items():
-            fn = getattr(l, name)
+            fn = getattr(l, name, None)
+            if fn is None:
+                if is_product_library():
+                    raise AttributeError(f"{LIB_PATH} lacks {name}: rebuild it with `python -m sast_amd.build`")
+                continue           # an A/B library built from another commit (tools only): that entry point raises when it is called
             fn.restype, fn.argtypes = res, args
         _lib = l
     return _lib

@@ -15,8 +15,9 @@
 //                                   (area range, IoU threshold) pair: 40 lanes.  One record per detection: sort key, 40 match bits, 40
 //                                   ignore bits.
 //   sast_eval_accumulate  one device-wide radix sort (rocprim) of the record keys (category, descending score, record index: unique, so
-//                         the order is the stable one), one wave per category that walks the sorted records (forward: totals, backward:
-//                         precision envelope and the 101 recall thresholds), and the six summaries.
+//                         the order is the stable one), the chunk-parallel walk of every category's sorted records (counts, scan over
+//                         the chunks, precision maxima, envelope, backward walk: the 101 recall thresholds), and the six summaries.
+//   sast_evmerge_append   one buffer behind another (two launches, no host synchronisation): what joins the buffers of several ranks
 // Every fp32 / fp64 operation of the reference is repeated one rounding at a time: build.py compiles this file with -ffp-contract=off.
 #include "common.cuh"
 #include "kernels.h"
@@ -334,56 +335,195 @@ __global__ void eval_reset_kernel(SastEvalArgs a) {
   if (i < a.max_detections) a.rec_key[i] = ~0ull;
 }
 
-__global__ void __launch_bounds__(64) eval_accumulate_kernel(SastEvalArgs a) {
+// ---- COCOeval.accumulate, chunk-parallel.  A category's sorted records are cut into chunks of L records; chunk c of category k is the
+// flat chunk q = (chunks of the categories before k) + c, and every per-chunk partial is one row of 64 lanes (40 in use: lane = area * 10
+// + threshold, as in the matching) in the workspace.  Five launches, each ordered behind the one before by the stream:
+//   count    per chunk and lane: true and false positives among its records that are not ignored
+//   scan     per category, over its chunks: the counts become inclusive prefix sums (a chunk's right edge; its left edge is the row
+//            before).  Also the two cases no chunk writes: npig == 0 (-1 everywhere) and a category without records (0 everywhere).
+//   max      per chunk: the largest precision at a record inside it, from the left-edge counts
+//   envelope per category: inclusive suffix maxima of those over the chunks
+//   walk     per chunk, backwards from the right-edge counts and the envelope entering from the right: exactly the sequential walk's
+//            loop.  Recall is monotone in the true-positive count, so the thresholds with recall(left edge) < threshold <= recall(right
+//            edge) are first reached in this chunk and in no other; the walk stops writing at the left edge by itself.  The last chunk
+//            also writes the thresholds above the final recall (0), the first the thresholds no recall is below (threshold 0).
+// Every count is an integer and every precision / recall is the same fp64 division of the same integers as in a sequential walk, the
+// envelope is a maximum of those: the table is the same bits for every L.
+struct AccWs {
+  int* tp;       // [chunks][64]
+  int* fp;       // [chunks][64]
+  double* mx;    // [chunks][64]
+};
+constexpr size_t ACC_WS_PER_CHUNK = 64 * (2 * sizeof(int) + sizeof(double));   // 1 KiB
+
+__host__ __device__ inline long long acc_max_chunks(long long max_detections, int L) { return (max_detections + L - 1) / L + SAST_EVAL_MAX_CLASSES; }
+
+__host__ __device__ inline AccWs acc_ws_carve(void* ws, long long chunks) {
+  AccWs w;
+  w.mx = (double*)ws;                       // the doubles first: 8-byte aligned whatever the chunk count
+  w.tp = (int*)(w.mx + chunks * 64);
+  w.fp = w.tp + chunks * 64;
+  return w;
+}
+
+struct AccCat {
+  int start, n;        // the category's records are sorted[start, start + n)
+  long long q0, nck;   // its chunks are the flat chunks [q0, q0 + nck)
+};
+
+// the category's span, from the device's record counts clamped to the capacity (every index below is formed from these)
+__device__ __forceinline__ AccCat acc_category(const SastEvalArgs& a, int k, int L) {
+  AccCat c{0, 0, 0, 0};
+  long long left = a.max_detections;
+  for (int kk = 0; kk <= k; ++kk) {
+    const int n = (int)min((long long)max(a.state[ST_REC_CAT + kk], 0), left);
+    left -= n;
+    if (kk < k) c.start += n, c.q0 += ((long long)n + L - 1) / L;
+    else c.n = n, c.nck = ((long long)n + L - 1) / L;
+  }
+  return c;
+}
+
+struct AccChunk {
+  int k, lo, cnt;           // category; records sorted[lo, lo + cnt)
+  long long c, nck, q0;     // chunk c of nck; the category's first flat chunk
+};
+
+__device__ __forceinline__ bool acc_chunk(const SastEvalArgs& a, long long q, int L, AccChunk& p) {
+  for (int k = 0; k < a.K; ++k) {
+    const AccCat c = acc_category(a, k, L);
+    if (q >= c.q0 && q < c.q0 + c.nck) {
+      p.k = k, p.c = q - c.q0, p.nck = c.nck, p.q0 = c.q0;
+      const long long off = p.c * L;                     // < n
+      p.lo = c.start + (int)off;
+      p.cnt = (int)min((long long)L, (long long)c.n - off);
+      return true;
+    }
+  }
+  return false;
+}
+
+// one tile of at most 64 records of a chunk: their match / ignore words into LDS
+__device__ __forceinline__ void acc_load_tile(const SastEvalArgs& a, int lo, int cnt, int base, unsigned long long* sm, unsigned long long* si) {
+  const int lane = threadIdx.x;
+  if (base + lane < cnt) {
+    const unsigned long long ro = min(a.sorted[lo + base + lane] & EV_IDX_MASK, (unsigned long long)(a.max_detections - 1));
+    sm[lane] = a.rec_match[ro], si[lane] = a.rec_ign[ro];
+  }
+}
+
+__global__ void __launch_bounds__(64) eval_acc_count_kernel(SastEvalArgs a, int L, AccWs w) {
   __shared__ unsigned long long sm[64], si[64];
-  __shared__ double rthr[EV_R];
+  const int lane = threadIdx.x;
+  AccChunk p;
+  if (!acc_chunk(a, blockIdx.x, L, p)) return;
+  int tp = 0, fp = 0;
+  for (int base = 0; base < p.cnt; base += 64) {
+    acc_load_tile(a, p.lo, p.cnt, base, sm, si);
+    __syncthreads();
+    const int cj = min(64, p.cnt - base);
+    for (int j = 0; j < cj; ++j) {
+      const int m = (int)((sm[j] >> lane) & 1), g = (int)((si[j] >> lane) & 1);
+      tp += m & (g ^ 1), fp += (m ^ 1) & (g ^ 1);
+    }
+    __syncthreads();
+  }
+  w.tp[(size_t)blockIdx.x * 64 + lane] = tp, w.fp[(size_t)blockIdx.x * 64 + lane] = fp;
+}
+
+__global__ void __launch_bounds__(64) eval_acc_scan_kernel(SastEvalArgs a, int L, AccWs w) {
   const int k = blockIdx.x, lane = threadIdx.x;
   const int ar = lane / EV_T, th = lane - ar * EV_T;
   const bool active = lane < EV_LANES;
-  for (int r = lane; r < EV_R; r += 64) rthr[r] = a.rec_thr[r];
-  const int n = a.state[ST_REC_CAT + k];
-  int start = 0;
-  for (int kk = 0; kk < k; ++kk) start += a.state[ST_REC_CAT + kk];
-  const int npig = active ? a.state[ST_NPIG + k * EV_A + ar] : 0;
-  const bool live = active && npig > 0;
+  const AccCat c = acc_category(a, k, L);
+  int tp = 0, fp = 0;
+  for (long long q = c.q0; q < c.q0 + c.nck; ++q) {   // any chunk count: sequential over the chunks, 64 lanes wide
+    tp += w.tp[q * 64 + lane], fp += w.fp[q * 64 + lane];
+    w.tp[q * 64 + lane] = tp, w.fp[q * 64 + lane] = fp;
+  }
+  if (!active) return;
+  const int npig = a.state[ST_NPIG + k * EV_A + ar];
+  if (npig > 0 && c.n > 0) return;                    // the chunks write the column
   double* out = a.precision + (size_t)th * EV_R * a.K * EV_A + k * EV_A + ar;   // [T][R][K][A]
   const size_t rs = (size_t)a.K * EV_A;
-  if (active && !live)
-    for (int r = 0; r < EV_R; ++r) out[r * rs] = -1.0;
-  __syncthreads();
+  const double v = npig > 0 ? 0.0 : -1.0;             // no detection: recall 0 reaches threshold 0 only, with precision 0
+  for (int r = 0; r < EV_R; ++r) out[r * rs] = v;
+}
+
+__global__ void __launch_bounds__(64) eval_acc_max_kernel(SastEvalArgs a, int L, AccWs w) {
+  __shared__ unsigned long long sm[64], si[64];
+  const int lane = threadIdx.x;
+  AccChunk p;
+  if (!acc_chunk(a, blockIdx.x, L, p)) return;
   int tp = 0, fp = 0;
-  for (int base = 0; base < n; base += 64) {
-    if (base + lane < n) {
-      const unsigned long long ro = a.sorted[start + base + lane] & EV_IDX_MASK;
-      sm[lane] = a.rec_match[ro], si[lane] = a.rec_ign[ro];
-    }
-    __syncthreads();
-    if (live) {
-      const int cj = min(64, n - base);
-      for (int j = 0; j < cj; ++j) {
-        const int m = (int)((sm[j] >> lane) & 1), g = (int)((si[j] >> lane) & 1);
-        tp += m & (g ^ 1), fp += (m ^ 1) & (g ^ 1);
-      }
-    }
-    __syncthreads();
-  }
-  // backwards: the precision envelope (the running maximum from the right) at the first record whose recall reaches each threshold
-  const double dn = (double)npig;
-  int ihi = 0;
+  if (p.c > 0) tp = w.tp[((size_t)blockIdx.x - 1) * 64 + lane], fp = w.fp[((size_t)blockIdx.x - 1) * 64 + lane];
   double mx = 0.0;
-  if (live) {
-    const double rc = (double)tp / dn;
-    while (ihi < EV_R && rthr[ihi] <= rc) ++ihi;
-    for (int r = ihi; r < EV_R; ++r) out[r * rs] = 0.0;   // np.searchsorted past the end: the entry stays 0
-  }
-  for (int base = n > 0 ? ((n - 1) / 64) * 64 : -64; base >= 0; base -= 64) {
-    if (base + lane < n) {
-      const unsigned long long ro = a.sorted[start + base + lane] & EV_IDX_MASK;
-      sm[lane] = a.rec_match[ro], si[lane] = a.rec_ign[ro];
+  for (int base = 0; base < p.cnt; base += 64) {
+    acc_load_tile(a, p.lo, p.cnt, base, sm, si);
+    __syncthreads();
+    const int cj = min(64, p.cnt - base);
+    for (int j = 0; j < cj; ++j) {
+      const int m = (int)((sm[j] >> lane) & 1), g = (int)((si[j] >> lane) & 1);
+      if (g) continue;
+      tp += m, fp += m ^ 1;
+      const double s = (double)fp + (double)tp;
+      mx = fmax(mx, (double)tp / (s + 2.220446049250313e-16));
     }
     __syncthreads();
-    if (live) {
-      for (int j = min(64, n - base) - 1; j >= 0; --j) {
+  }
+  w.mx[(size_t)blockIdx.x * 64 + lane] = mx;
+}
+
+__global__ void __launch_bounds__(64) eval_acc_envelope_kernel(SastEvalArgs a, int L, AccWs w) {
+  const int k = blockIdx.x, lane = threadIdx.x;
+  const AccCat c = acc_category(a, k, L);
+  double mx = 0.0;
+  for (long long q = c.q0 + c.nck - 1; q >= c.q0; --q) {
+    mx = fmax(mx, w.mx[q * 64 + lane]);
+    w.mx[q * 64 + lane] = mx;
+  }
+}
+
+__global__ void __launch_bounds__(64) eval_acc_walk_kernel(SastEvalArgs a, int L, AccWs w) {
+  __shared__ unsigned long long sm[64], si[64];
+  __shared__ double rthr[EV_R];
+  const int lane = threadIdx.x;
+  AccChunk p;
+  if (!acc_chunk(a, blockIdx.x, L, p)) return;
+  const int ar = lane / EV_T, th = lane - ar * EV_T;
+  const bool active = lane < EV_LANES;
+  for (int r = lane; r < EV_R; r += 64) rthr[r] = a.rec_thr[r];
+  const int npig = active ? a.state[ST_NPIG + p.k * EV_A + ar] : 0;
+  const bool live = active && npig > 0;
+  double* out = a.precision + (size_t)th * EV_R * a.K * EV_A + p.k * EV_A + ar;   // [T][R][K][A]
+  const size_t rs = (size_t)a.K * EV_A;
+  const size_t row = (size_t)blockIdx.x * 64 + lane;
+  const bool first = p.c == 0, last = p.c == p.nck - 1;
+  int tp = w.tp[row], fp = w.fp[row];                                 // at the chunk's right edge
+  const int tpl = first ? 0 : w.tp[row - 64];                         // at its left edge
+  double mx = last ? 0.0 : w.mx[row + 64];                            // the envelope entering from the right
+  __syncthreads();
+  const double dn = (double)npig;
+  int ihi = 0, ilo = 0;
+  if (live) {
+    const double rc = (double)tp / dn, rcl = (double)tpl / dn;
+    while (ihi < EV_R && rthr[ihi] <= rc) ++ihi;
+    while (ilo < EV_R && rthr[ilo] <= rcl) ++ilo;
+    if (last)
+      for (int r = ihi; r < EV_R; ++r) out[r * rs] = 0.0;             // np.searchsorted past the end: the entry stays 0
+    if (first) {
+      const double all = w.mx[row];                                   // the maximum over the whole category
+      for (int r = 0; r < ilo; ++r) out[r * rs] = all;                // recall threshold 0
+    }
+  }
+  // backwards: the precision envelope (the running maximum from the right) at the first record whose recall reaches each threshold;
+  // thresholds [ilo, ihi) are this chunk's, and the walk ends early once every lane has written its own
+  for (int base = p.cnt > 0 ? ((p.cnt - 1) / 64) * 64 : -64; base >= 0; base -= 64) {
+    if (__syncthreads_or(ihi > ilo) == 0) break;
+    acc_load_tile(a, p.lo, p.cnt, base, sm, si);
+    __syncthreads();
+    if (live && ihi > ilo) {
+      for (int j = min(64, p.cnt - base) - 1; j >= 0; --j) {
         const int m = (int)((sm[j] >> lane) & 1), g = (int)((si[j] >> lane) & 1);
         if (g) continue;   // an ignored detection repeats its left neighbour's recall and precision
         const double s = (double)fp + (double)tp;
@@ -394,10 +534,7 @@ __global__ void __launch_bounds__(64) eval_accumulate_kernel(SastEvalArgs a) {
         while (ihi > 0 && rthr[ihi - 1] > rcp) out[--ihi * rs] = mx;
       }
     }
-    __syncthreads();
   }
-  if (live)
-    while (ihi > 0) out[--ihi * rs] = mx;   // recall threshold 0; mx is 0 when the category has no detection
 }
 
 __global__ void __launch_bounds__(64) eval_summarize_kernel(SastEvalArgs a) {
@@ -422,6 +559,94 @@ __global__ void __launch_bounds__(64) eval_summarize_kernel(SastEvalArgs a) {
   }
   if (s == 0 && lane < SAST_EVAL_STATE_WORDS) a.result[8 + lane] = (double)a.state[lane];   // one host copy brings both
 }
+
+// ---- sast_evmerge_append: the buffer `s` behind the buffer `d`.  Every count is read from the two states on the device and clamped
+// to its buffer's capacity; every index is an offset (dst's count) plus a position below src's count, and `fits` bounds their sum by
+// dst's capacity before anything is written.
+struct MergeCounts {
+  int ni_d, ng_d, nd_d, nr_d;   // dst: images, ground-truth rows, detection rows, records
+  int ni_s, ng_s, nd_s, nr_s;   // src
+  bool over_img, over_gt, over_det;
+  __device__ bool fits() const { return !(over_img || over_gt || over_det); }
+};
+
+__device__ __forceinline__ int clamp_count(int v, long long cap) { return (int)min((long long)max(v, 0), cap); }
+
+__device__ __forceinline__ MergeCounts merge_counts(const SastEvalArgs& d, const SastEvalArgs& s) {
+  const long long gcap_d = (long long)d.max_images * d.max_labels_per_frame, gcap_s = (long long)s.max_images * s.max_labels_per_frame;
+  MergeCounts m;
+  m.ni_d = clamp_count(d.state[ST_IMAGES], d.max_images), m.ng_d = clamp_count(d.state[ST_GT], gcap_d);
+  m.nd_d = clamp_count(d.state[ST_DET], d.max_detections), m.nr_d = clamp_count(d.state[ST_REC], d.max_detections);
+  m.ni_s = clamp_count(s.state[ST_IMAGES], s.max_images), m.ng_s = clamp_count(s.state[ST_GT], gcap_s);
+  m.nd_s = clamp_count(s.state[ST_DET], s.max_detections), m.nr_s = clamp_count(s.state[ST_REC], s.max_detections);
+  m.over_img = (long long)m.ni_d + m.ni_s > d.max_images;
+  m.over_gt = (long long)m.ng_d + m.ng_s > gcap_d;
+  m.over_det = (long long)m.nd_d + m.nd_s > d.max_detections || (long long)m.nr_d + m.nr_s > d.max_detections;
+  return m;
+}
+
+// Ordering across workgroups: the offsets of an append are dst's own counts, and the append ends by raising them.  The two halves are two
+// launches on one stream.  evmerge_copy_kernel only READS the two states (every workgroup computes the same MergeCounts from them) and
+// writes table and record slots at or past dst's counts, which no workgroup of the launch reads; evmerge_publish_kernel, one thread,
+// runs after the copy kernel has ended (stream order, also inside a replayed graph) and is the only writer of a state word.  So no
+// workgroup reads a state word that another workgroup of the same launch writes, and there is no ticket to take.  A refused append (it
+// does not fit) is decided by both kernels from the same unchanged words: the first copies nothing, the second only counts the refusal.
+__global__ void __launch_bounds__(256) evmerge_copy_kernel(SastEvalArgs d, SastEvalArgs s) {
+  const MergeCounts m = merge_counts(d, s);
+  if (!m.fits()) return;
+  const int n = max(max(m.ni_s, m.ng_s), max(m.nd_s, m.nr_s));
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+    if (i < m.ni_s) d.img_t[m.ni_d + i] = s.img_t[i];
+    if (i < m.ng_s) {
+      const size_t o = (size_t)(m.ng_d + i);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) d.gt_box[o * 4 + e] = s.gt_box[(size_t)i * 4 + e];
+      d.gt_cls[o] = s.gt_cls[i];
+      d.gt_img[o] = s.gt_img[i] + m.ni_d;
+    }
+    if (i < m.nd_s) {
+      const size_t o = (size_t)(m.nd_d + i);
+#pragma unroll
+      for (int e = 0; e < 5; ++e) d.det_box[o * 5 + e] = s.det_box[(size_t)i * 5 + e];
+      d.det_cls[o] = s.det_cls[i];
+      d.det_img[o] = s.det_img[i] + m.ni_d;
+    }
+    if (i < m.nr_s) {
+      const size_t o = (size_t)(m.nr_d + i);
+      const unsigned long long key = s.rec_key[i];   // category and score bits stay; the index (the tie-break) moves behind dst's
+      d.rec_key[o] = (key & ~EV_IDX_MASK) | (((key & EV_IDX_MASK) + (unsigned long long)m.nr_d) & EV_IDX_MASK);
+      d.rec_match[o] = s.rec_match[i], d.rec_ign[o] = s.rec_ign[i];
+    }
+  }
+}
+
+__global__ void evmerge_publish_kernel(SastEvalArgs d, SastEvalArgs s) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  const MergeCounts m = merge_counts(d, s);
+  int* st = d.state;
+  const int* ss = s.state;
+  st[ST_ERR_IMAGES] += max(ss[ST_ERR_IMAGES], 0), st[ST_ERR_DETS] += max(ss[ST_ERR_DETS], 0), st[ST_ERR_LABELS] += max(ss[ST_ERR_LABELS], 0);
+  st[ST_ADDS] += max(ss[ST_ADDS], 0);
+  if (!m.fits()) {   // counted, reported by the host at evaluate time; nothing was appended
+    const int lost = max(m.ni_s, 1);
+    if (m.over_img) st[ST_ERR_IMAGES] += lost;
+    if (m.over_gt) st[ST_ERR_LABELS] += lost;
+    if (m.over_det) st[ST_ERR_DETS] += lost;
+    return;
+  }
+  st[ST_IMAGES] = m.ni_d + m.ni_s, st[ST_GT] = m.ng_d + m.ng_s, st[ST_DET] = m.nd_d + m.nd_s, st[ST_REC] = m.nr_d + m.nr_s;
+  for (int k = 0; k < SAST_EVAL_MAX_CLASSES; ++k) st[ST_REC_CAT + k] += max(ss[ST_REC_CAT + k], 0);
+  for (int e = 0; e < SAST_EVAL_MAX_CLASSES * EV_A; ++e) st[ST_NPIG + e] += max(ss[ST_NPIG + e], 0);
+}
+
+bool evmerge_tables_ok(const SastEvalArgs* a) {
+  return a->gt_box && a->gt_cls && a->gt_img && a->img_t && a->det_box && a->det_cls && a->det_img &&
+         (long long)a->max_images * a->max_labels_per_frame <= 0x7fffffffll;
+}
+
+int eval_acc_chunk() { return std::max(SAST_KNOB("SAST_EVAL_ACC_CHUNK", 1024), 1); }
+
+size_t eval_acc_ws_bytes(long long max_detections, int L) { return (size_t)acc_max_chunks(max_detections, L) * ACC_WS_PER_CHUNK; }
 
 bool eval_args_ok(const SastEvalArgs* a) {
   return a && a->state && a->rec_key && a->rec_match && a->rec_ign && a->K >= 1 && a->K <= SAST_EVAL_MAX_CLASSES && a->max_images >= 1 &&
@@ -473,13 +698,17 @@ size_t sast_eval_sort_ws_bytes(int64_t max_detections) {
   size_t bytes = 0;
   unsigned long long* p = nullptr;
   if (rocprim::radix_sort_keys(nullptr, bytes, p, p, (size_t)max_detections, 0, 64, (hipStream_t) nullptr) != hipSuccess) return 0;
-  return std::max<size_t>(bytes, 16);
+  // the accumulate's per-chunk partials take the workspace over once the sort is done
+  return std::max<size_t>(std::max<size_t>(bytes, 16), sast::eval_acc_ws_bytes(max_detections, sast::eval_acc_chunk()));
 }
 
 int sast_eval_accumulate(const SastEvalArgs* a, sast_stream_t stream) {
   SAST_ENTRY();
   using namespace sast;
   if (!eval_args_ok(a) || !a->sorted || !a->sort_ws || !a->rec_thr || !a->precision || !a->result) return SAST_EINVAL;
+  const int L = eval_acc_chunk();
+  const long long chunks = acc_max_chunks(a->max_detections, L);
+  if (a->sort_ws_bytes < eval_acc_ws_bytes(a->max_detections, L) || chunks > 0x7fffffffll) return SAST_EINVAL;
   const hipStream_t st = (hipStream_t)stream;
   size_t bytes = a->sort_ws_bytes;
   // the keys are unique (category, ~score, record index), so the sorted order is the stable descending-score order per category;
@@ -487,8 +716,32 @@ int sast_eval_accumulate(const SastEvalArgs* a, sast_stream_t stream) {
   if (rocprim::radix_sort_keys(a->sort_ws, bytes, (const unsigned long long*)a->rec_key, (unsigned long long*)a->sorted, (size_t)a->max_detections,
                                0, 64, st) != hipSuccess)
     return SAST_ELAUNCH;
-  SAST_LAUNCH(eval_accumulate_kernel, dim3((unsigned)a->K), dim3(64), 0, st, *a);
+  const AccWs w = acc_ws_carve(a->sort_ws, chunks);
+  const dim3 per_chunk((unsigned)chunks), per_cat((unsigned)a->K);   // sized from the capacity: the counts stay on the device
+  SAST_LAUNCH(eval_acc_count_kernel, per_chunk, dim3(64), 0, st, *a, L, w);
+  SAST_LAUNCH(eval_acc_scan_kernel, per_cat, dim3(64), 0, st, *a, L, w);
+  SAST_LAUNCH(eval_acc_max_kernel, per_chunk, dim3(64), 0, st, *a, L, w);
+  SAST_LAUNCH(eval_acc_envelope_kernel, per_cat, dim3(64), 0, st, *a, L, w);
+  SAST_LAUNCH(eval_acc_walk_kernel, per_chunk, dim3(64), 0, st, *a, L, w);
   SAST_LAUNCH(eval_summarize_kernel, dim3(6), dim3(64), 0, st, *a);
+  SAST_CHECK_LAUNCH();
+  return SAST_OK;
+}
+
+int sast_evmerge_append(const SastEvalArgs* dst, const SastEvalArgs* src, sast_stream_t stream) {
+  SAST_ENTRY();
+  using namespace sast;
+  if (!eval_args_ok(dst) || !eval_args_ok(src) || !evmerge_tables_ok(dst) || !evmerge_tables_ok(src)) return SAST_EINVAL;
+  if (dst == src || dst->state == src->state) return SAST_EINVAL;
+  if (dst->K != src->K || dst->min_diag2 != src->min_diag2 || dst->min_side != src->min_side ||
+      src->max_labels_per_frame > dst->max_labels_per_frame)
+    return SAST_EINVAL;
+  const hipStream_t st = (hipStream_t)stream;
+  const long long most = std::max<long long>(std::max<long long>(src->max_detections, src->max_images),
+                                             (long long)src->max_images * src->max_labels_per_frame);
+  const unsigned blocks = (unsigned)std::min<long long>((most + 255) / 256, 4096);   // sized from src's capacities; the kernel strides
+  SAST_LAUNCH(evmerge_copy_kernel, dim3(blocks), dim3(256), 0, st, *dst, *src);
+  SAST_LAUNCH(evmerge_publish_kernel, dim3(1), dim3(64), 0, st, *dst, *src);
   SAST_CHECK_LAUNCH();
   return SAST_OK;
 }

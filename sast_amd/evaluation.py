@@ -13,8 +13,12 @@ on the device: `add` takes the label tensors `SpatialAugmentor` returns and the 
   its detections vanish with it; image ids follow the order of `add` calls and of the rows within a call.
 - What does not fit `max_images`, `max_detections` (filtered detections over the whole buffer) or `max_labels_per_frame` (filtered
   labels of one frame) is counted on the device and raised by `evaluate_buffer`, never dropped silently.
+- `merge` appends another evaluator's buffer on the device (one call, no sync), `export_buffer` / `import_buffer` move a buffer as a
+  dict of trimmed tensors, and `all_gather` joins the buffers of all ranks of a process group in rank order: every rank then computes
+  the numbers of ONE evaluator fed rank 0's frames, then rank 1's, ... -- the dataset's mAP, whatever the number of ranks.  The
+  reference averages per-rank metrics instead, which is not the dataset's AP (precision over recall is not linear in the shards).
 - Not implemented: the multi-timestamp form of _match_times (to_prophesee asserts one timestamp per entry), AR and maxDets 1 / 10
-  (the reference discards them), merging across ranks, visualisation.
+  (the reference discards them), visualisation.
 
 There is no CPU path: CPU tensors raise the library's "no CPU fallback" error.
 """
@@ -46,7 +50,10 @@ class PropheseeEvaluator:
       n_det int32 [N] as `postprocess_padded` returns them for the same N frames.
     ev.evaluate_buffer(img_height, img_width) -> {'AP', 'AP_50', 'AP_75', 'AP_S', 'AP_M', 'AP_L'} as Python floats (one sync, at the end)
     ev.precision() -> fp64 [10, 101, K, 4] of the last evaluate_buffer; ev.tables() -> the flattened image / annotation / result records
-    ev.reset_buffer(), ev.has_data() as in the reference."""
+    ev.reset_buffer(), ev.has_data() as in the reference.
+    ev.merge(other): other's buffer appended, as if its frames had been added here after this one's; ev.export_buffer() -> dict of
+      trimmed device tensors, ev.import_buffer(blob) appends one; ev.all_gather(group=None): every rank ends with the buffers of all
+      ranks in rank order (capacities must hold the union: what does not fit raises OverflowError in evaluate_buffer)."""
 
     def __init__(self, dataset: str, downsample_by_2: bool, max_images: int = 65536, max_detections: int = 1 << 22,
                  max_labels_per_frame: int = 64):
@@ -77,9 +84,7 @@ class PropheseeEvaluator:
         if torch.cuda.is_current_stream_capturing():
             raise RuntimeError("sast_amd.evaluation: one un-captured call is needed before graph capture (it allocates the buffers)")
         K, D, G = len(self.classes), self.max_detections, self.max_images * self.max_labels_per_frame
-        ws_bytes = int(L.lib().sast_eval_sort_ws_bytes(D))
-        if ws_bytes == 0:
-            raise RuntimeError("sast_amd.evaluation: the library refused the sort workspace size")
+        ws_bytes = self._ws_bytes()
 
         def e(shape, dt):
             return torch.empty(shape, dtype=dt, device=dev)
@@ -105,6 +110,12 @@ class PropheseeEvaluator:
         a.max_images, a.max_labels_per_frame, a.max_detections = self.max_images, self.max_labels_per_frame, self.max_detections
         self._dev = dev
         L.check(L.lib().sast_eval_reset(C.byref(a), _stream()), "eval_reset")
+
+    def _ws_bytes(self) -> int:
+        ws_bytes = int(L.lib().sast_eval_sort_ws_bytes(self.max_detections))
+        if ws_bytes == 0:
+            raise RuntimeError("sast_amd.evaluation: the library refused the sort workspace size")
+        return ws_bytes
 
     def reset_buffer(self) -> None:
         """empties the buffer (e.g. in on_validation_epoch_start): one launch, no sync"""
@@ -157,6 +168,10 @@ class PropheseeEvaluator:
         if self._dev is None:
             warn("Attempt to use prophesee evaluation buffer, but it is empty", UserWarning, stacklevel=2)
             return None
+        ws_bytes = self._ws_bytes()                 # the accumulate's share grows when SAST_EVAL_ACC_CHUNK was lowered since
+        if ws_bytes > self._args.sort_ws_bytes:
+            self._t["sort_ws"] = torch.empty(ws_bytes, dtype=torch.uint8, device=self._dev)
+            self._args.sort_ws, self._args.sort_ws_bytes = self._t["sort_ws"].data_ptr(), ws_bytes
         L.check(L.lib().sast_eval_accumulate(C.byref(self._args), _stream()), "eval_accumulate")
         res = self._t["result"].cpu().numpy()        # the one synchronisation
         state = res[8:].astype(np.int64)
@@ -201,3 +216,142 @@ class PropheseeEvaluator:
             "dt_bbox": db[:, :4].copy(),
             "dt_area": (db[:, 2] * db[:, 3]).astype(np.float64),
         }
+
+    # -------------------------------------------------------------------------------------------------------------------- merge
+    def _check_same_task(self, dataset, downsample_by_2) -> None:
+        if dataset != self.dataset or bool(downsample_by_2) != self.downsample_by_2:
+            raise ValueError(f"sast_amd.evaluation: cannot merge a buffer of ({dataset}, downsample_by_2={bool(downsample_by_2)}) into one of "
+                             f"({self.dataset}, downsample_by_2={self.downsample_by_2}): the categories or the box filter differ")
+
+    def merge(self, other: "PropheseeEvaluator") -> None:
+        """appends `other`'s buffer: afterwards this evaluator is what it would be had `other`'s frames been added to it after its
+        own, score ties included.  One call on the device, no sync, can be captured in a graph once both have their buffers.  What does
+        not fit this evaluator's capacities is appended not at all and raises OverflowError in evaluate_buffer.  `other` is unchanged."""
+        if not isinstance(other, PropheseeEvaluator):
+            raise TypeError("sast_amd.evaluation: merge takes a PropheseeEvaluator")
+        if other is self:
+            raise ValueError("sast_amd.evaluation: cannot merge an evaluator into itself")
+        self._check_same_task(other.dataset, other.downsample_by_2)
+        if other._dev is None:           # never allocated: nothing was added
+            return
+        if other.max_labels_per_frame > self.max_labels_per_frame:
+            raise ValueError(f"sast_amd.evaluation: the other buffer's max_labels_per_frame={other.max_labels_per_frame} exceeds this one's "
+                             f"{self.max_labels_per_frame}")
+        if self._dev is None:
+            self._allocate(other._dev)
+        elif other._dev != self._dev:
+            raise ValueError("sast_amd.evaluation: the other buffer lives on another device")
+        L.check(L.lib().sast_evmerge_append(C.byref(self._args), C.byref(other._args), _stream()), "evmerge_append")
+        self._evaluated = False
+        if not other._buffer_empty:      # adds that only a replayed graph made are in the device's count, which was added too
+            self._buffer_empty = False
+
+    _BLOB_TABLES = (("img_t", 0, torch.int64, ()), ("gt_box", 1, torch.float32, (4,)), ("gt_cls", 1, torch.int32, ()), ("gt_img", 1, torch.int32, ()),
+                    ("det_box", 2, torch.float32, (5,)), ("det_cls", 2, torch.int32, ()), ("det_img", 2, torch.int32, ()),
+                    ("rec_key", 3, torch.int64, ()), ("rec_match", 3, torch.int64, ()), ("rec_ign", 3, torch.int64, ()))
+
+    def export_buffer(self) -> Dict[str, object]:
+        """the buffer as a dict: `state` int32 [32] and the tables / records named as in include/sast_hip.h, device tensors cut to the
+        used counts (copies; one read of the state synchronises), plus `dataset`, `downsample_by_2` and `max_labels_per_frame`"""
+        if self._dev is None:
+            raise RuntimeError("sast_amd.evaluation: nothing was added")
+        t = self._t
+        state = t["state"].clone()
+        used = [int(v) for v in state[:4].cpu()]
+        blob: Dict[str, object] = {"state": state, "dataset": self.dataset, "downsample_by_2": self.downsample_by_2,
+                                   "max_labels_per_frame": self.max_labels_per_frame}
+        for name, which, _dt, _tail in self._BLOB_TABLES:
+            blob[name] = t[name][:used[which]].clone()
+        return blob
+
+    def import_buffer(self, blob: Dict[str, object]) -> None:
+        """appends a buffer exported by `export_buffer` (of this or another evaluator, e.g. another rank's): the same device call as
+        `merge`, on a source staged from the blob; no sync"""
+        state = blob["state"]
+        tables = [blob[name] for name, *_ in self._BLOB_TABLES]
+        _need_gpu(state, *tables)
+        self._check_same_task(blob["dataset"], blob["downsample_by_2"])
+        mlpf = int(blob["max_labels_per_frame"])
+        if mlpf > self.max_labels_per_frame:
+            raise ValueError(f"sast_amd.evaluation: the blob's max_labels_per_frame={mlpf} exceeds this evaluator's {self.max_labels_per_frame}")
+        if state.dtype != torch.int32 or tuple(state.shape) != (L.EVAL_STATE_WORDS,):
+            raise TypeError(f"sast_amd.evaluation: blob['state'] must be int32 [{L.EVAL_STATE_WORDS}]")
+        n = [0, 0, 0, 0]
+        for (name, which, dt, tail), v in zip(self._BLOB_TABLES, tables):
+            if v.dtype != dt or tuple(v.shape[1:]) != tail or v.dim() != 1 + len(tail):
+                raise TypeError(f"sast_amd.evaluation: blob['{name}'] must be {dt} [n{''.join(', %d' % d for d in tail)}]")
+            if name in ("img_t", "gt_box", "det_box", "rec_key"):
+                n[which] = int(v.shape[0])
+            elif int(v.shape[0]) != n[which]:
+                raise ValueError(f"sast_amd.evaluation: blob['{name}'] has {int(v.shape[0])} rows, its table has {n[which]}")
+        if n[1] > max(n[0], 1) * mlpf:
+            raise ValueError("sast_amd.evaluation: the blob has more ground-truth rows than its images can hold")
+        if self._dev is None:
+            self._allocate(state.device)
+        dev = self._dev
+        if len({v.device for v in (state, *tables)} | {dev}) != 1:
+            raise ValueError("sast_amd.evaluation: the blob lives on another device")
+        # the padded source: capacities just large enough for the blob's rows (the device clamps the state's counts to them)
+        src = L.SastEvalArgs()
+        src.K, src.min_diag2, src.min_side = self._args.K, self._args.min_diag2, self._args.min_side
+        src.max_images, src.max_labels_per_frame, src.max_detections = max(n[0], 1), mlpf, max(n[2], n[3], 1)
+        rows = (src.max_images, src.max_images * mlpf, src.max_detections, src.max_detections)
+        keep = [state.contiguous()]
+        src.state = keep[0].data_ptr()
+        for (name, which, dt, tail), v in zip(self._BLOB_TABLES, tables):
+            pad = torch.empty((rows[which],) + tail, dtype=dt, device=dev)
+            pad[:n[which]].copy_(v)
+            keep.append(pad)
+            setattr(src, name, pad.data_ptr())
+        L.check(L.lib().sast_evmerge_append(C.byref(self._args), C.byref(src), _stream()), "evmerge_append")
+        del keep                          # freed in stream order, behind the two launches
+        self._evaluated = False           # (has_data() is decided by the device's count of adds, which the blob's was added to)
+
+    def all_gather(self, group=None) -> None:
+        """collective: afterwards every rank's buffer is rank 0's, then rank 1's, ... then the last rank's, so every rank evaluates the
+        same numbers -- those of one evaluator fed all ranks' frames in rank order.  Each rank's capacities must hold the union (otherwise
+        OverflowError in evaluate_buffer).  The blobs travel as device tensors where the group's backend carries them and through host
+        memory otherwise (gloo).  A no-op without an initialised process group or with one rank.  Measured on one GPU shared by two
+        ranks only: no node with several GPUs was available to this project."""
+        import torch.distributed as dist
+        if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
+            return
+        world = dist.get_world_size(group)
+        on_device = "nccl" in str(dist.get_backend(group)).lower()
+        if self._dev is None:
+            self._allocate(torch.device("cuda", torch.cuda.current_device()))
+        dev = self._dev
+        wire = dev if on_device else torch.device("cpu")
+        blob = self.export_buffer()
+        names = ["state"] + [name for name, *_ in self._BLOB_TABLES]
+        order = sorted(names, key=lambda k: -blob[k].element_size())        # 8-byte elements first: every part stays aligned
+        packed = torch.cat([blob[k].reshape(-1).view(torch.uint8) for k in order])
+        head = torch.tensor([int(blob["img_t"].shape[0]), int(blob["gt_cls"].shape[0]), int(blob["det_cls"].shape[0]),
+                             int(blob["rec_key"].shape[0]), self.max_labels_per_frame, int(packed.numel()),
+                             2 * sorted(CLASSES).index(self.dataset) + int(self.downsample_by_2)], dtype=torch.int64, device=wire)
+        heads = [torch.empty_like(head) for _ in range(world)]
+        dist.all_gather(heads, head, group=group)
+        heads = [[int(v) for v in h.cpu()] for h in heads]
+        if any(h[6] != heads[0][6] for h in heads):
+            raise ValueError("sast_amd.evaluation: the ranks' evaluators differ in dataset or downsample_by_2")
+        longest = max(h[5] for h in heads)
+        mine = torch.zeros(longest, dtype=torch.uint8, device=wire)
+        mine[:packed.numel()].copy_(packed)
+        parts = [torch.empty_like(mine) for _ in range(world)]
+        dist.all_gather(parts, mine, group=group)
+        self.reset_buffer()
+        for h, part in zip(heads, parts):
+            part = part.to(dev)
+            rows = {0: h[0], 1: h[1], 2: h[2], 3: h[3]}
+            got: Dict[str, object] = {"dataset": self.dataset, "downsample_by_2": self.downsample_by_2, "max_labels_per_frame": h[4]}
+            shapes = {"state": (torch.int32, (L.EVAL_STATE_WORDS,))}
+            shapes.update({name: (dt, (rows[which],) + tail) for name, which, dt, tail in self._BLOB_TABLES})
+            at = 0
+            for k in order:
+                dt, shape = shapes[k]
+                nbytes = int(np.prod(shape)) * torch.empty(0, dtype=dt).element_size()
+                got[k] = part[at:at + nbytes].view(dt).reshape(shape)
+                at += nbytes
+            if at != h[5]:
+                raise RuntimeError("sast_amd.evaluation: a rank's packed buffer does not have the length its header announces")
+            self.import_buffer(got)

@@ -7,6 +7,9 @@ Per call, all in this one process:
   add       PropheseeEvaluator.add of N = 8 frames with D detections each (three launches, no host sync), for several D
   evaluate  PropheseeEvaluator.evaluate_buffer over a buffer of --frames frames with --dets detections each: the epoch-end sort,
             accumulate and summaries, the final host copy included
+  merge     two evaluators with half of those frames each: PropheseeEvaluator.merge of one into the other (two launches, no host
+            sync; timed once with events, after a warm-up on a small pair), then evaluate_buffer on the merged buffer.  Left out when
+            the loaded library has no sast_evmerge_append (an A/B run against an older build through SAST_LIB_PATH)
 A randomly initialised head puts nearly nothing above the threshold, so the detections that `add` and `evaluate` are timed on are
 synthetic: per frame 1..12 labels, D boxes of which 60 % are jittered copies of a label and the rest random, 64 score levels.  D stands
 for what survives confidence 0.001 and NMS on a trained detector; it is an input of this tool, not a measurement of one.
@@ -16,6 +19,7 @@ for what survives confidence 0.001 and NMS on a trained detector; it is an input
 from __future__ import annotations
 
 import argparse
+import hashlib
 import os
 import statistics
 import sys
@@ -138,10 +142,39 @@ def main():
         t0 = time.perf_counter()
         stats = ev.evaluate_buffer(*HW)
         ms.append((time.perf_counter() - t0) * 1e3)
+    bits = hashlib.sha256(ev.precision().cpu().numpy().tobytes()).hexdigest()[:16]
     st = ev._state
     lines.append(f"evaluate_buffer: {int(st[0])} images, {int(st[1])} ground truths, {int(st[2])} filtered detections, {int(st[3])} records "
                  f"(at most 100 per image and category): {statistics.median(ms):.2f} ms wall (3 calls: {', '.join(f'{v:.2f}' for v in ms)}), "
-                 f"= {statistics.median(ms) / t_fwd:.1f} forward calls;  AP {stats['AP']:.4f}")
+                 f"= {statistics.median(ms) / t_fwd:.1f} forward calls;  AP {stats['AP']:.4f}, precision table sha256 {bits}")
+    from sast_amd import _lib
+    lines.append(f"library {_lib.loaded_path() if not _lib.is_product_library() else 'in-tree product'}; knobs read: {_lib.knobs()}")
+    if hasattr(_lib.lib(), "sast_evmerge_append"):
+        del ev
+        half = (F // chunk // 2) * chunk
+
+        def filled(n_frames, first, max_images, max_detections):
+            e = PropheseeEvaluator("gen1", False, max_images=max_images, max_detections=max_detections, max_labels_per_frame=M)
+            for i in range(first, first + n_frames // chunk):
+                e.add(*pool[i % len(pool)])
+            return e
+
+        small_a, small_b = filled(chunk, 0, 2 * chunk, 2 * chunk * D), filled(chunk, 1, chunk, chunk * D)
+        small_a.merge(small_b)                      # first use of the two kernels
+        dst, src = filled(half, 0, 2 * half, 2 * half * D), filled(half, half // chunk, half, half * D)
+        torch.cuda.synchronize()
+        t_merge = timed(lambda: dst.merge(src), 1)
+        ms = []
+        for _ in range(3):
+            t0 = time.perf_counter()
+            stats_m = dst.evaluate_buffer(*HW)
+            ms.append((time.perf_counter() - t0) * 1e3)
+        st = dst._state
+        bits_m = hashlib.sha256(dst.precision().cpu().numpy().tobytes()).hexdigest()[:16]
+        lines.append(f"merge of {half} frames into {half}: {t_merge:.3f} ms;  evaluate_buffer on the merged buffer: {int(st[0])} images, "
+                     f"{int(st[3])} records: {statistics.median(ms):.2f} ms wall (3 calls: {', '.join(f'{v:.2f}' for v in ms)});  "
+                     f"AP {stats_m['AP']:.4f}, precision table sha256 {bits_m}"
+                     + (" (stats and table equal to the one evaluator's)" if stats_m == stats and bits_m == bits else ""))
     text = "\n".join(lines) + "\n"
     print(text)
     if a.out:
