@@ -5,6 +5,16 @@
  * cited reference lines; the Python modules in sast_amd/ bind them with ctypes (see
  * INTEGRATION.md for the reference-side binding a maintainer would add).
  *
+ * This file is the SINGLE SOURCE of that binding: sast_amd/_header.py reads it at import and sast_amd/_lib.py builds every
+ * ctypes.Structure, every (restype, argtypes) pair and every integer constant from what it finds, so a new entry point, struct field
+ * or constant is written here and nowhere else.  The reader knows plain, regular C only and REFUSES the rest (RuntimeError at import,
+ * with the text it could not place): what it accepts is `#define SAST_X <integer literal>`, `enum { ... };` with explicit values,
+ * `1 << k` or implicit increments, `typedef struct [Tag] { ... } Name;` whose fields are scalars, pointers, arrays sized by a literal
+ * or an earlier constant, or an earlier struct, and prototypes of sast_* functions with named arguments.  Scalar types: int, long,
+ * unsigned long long, float, double, size_t and the <stdint.h> names.  No unions, bit-fields, function pointers, nested struct bodies,
+ * conditional blocks or value macros that are not integer literals; function-like macros are left to C.  tests/test_abi.py has gcc
+ * check every size, offset, value and argument list the reader derives.
+ *
  * Conventions
  *  - all tensors are device pointers owned by the CALLER (PyTorch caching allocator); the library
  *    never allocates, frees or retains pointers;  workspaces are caller-provided.

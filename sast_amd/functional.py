@@ -329,9 +329,6 @@ def as_nchw_view(x_nhwc: torch.Tensor) -> torch.Tensor:
     return x_nhwc.permute(0, 3, 1, 2)
 
 
-MEAN_SQUARE_BLOCKS = 128   # include/sast_hip.h: SAST_MEAN_SQUARE_BLOCKS
-
-
 class _MeanSquares(torch.autograd.Function):
     @staticmethod
     def forward(ctx, *xs):
@@ -340,7 +337,7 @@ class _MeanSquares(torch.autograd.Function):
         k = len(xs)
         ptrs = (C.c_void_p * k)(*[x.data_ptr() for x in xs])
         ns = (C.c_size_t * k)(*[x.numel() for x in xs])
-        partials = torch.empty(k * MEAN_SQUARE_BLOCKS, device=xs[0].device, dtype=torch.float32)
+        partials = torch.empty(k * L.MEAN_SQUARE_BLOCKS, device=xs[0].device, dtype=torch.float32)
         L.check(L.lib().sast_mean_square_fwd(ptrs, ns, k, partials.data_ptr(), _stream()), "mean_square_fwd")
         ctx.save_for_backward(*xs)
         return partials

@@ -112,21 +112,6 @@ def test_merge_entry_point_declared_bound_exported_and_refusing():
     assert lib.sast_eval_sort_ws_bytes(0) == 0 and lib.sast_eval_sort_ws_bytes(1 << 30) == 0
 
 
-def test_eval_args_size_and_offsets_match_a_c_compiler(tmp_path):
-    st = _lib.SastEvalArgs
-    lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{_lib.HEADER_PATH}"', "int main(void) {",
-             '  printf("%zu", sizeof(SastEvalArgs));']
-    lines += [f'  printf(" %zu", offsetof(SastEvalArgs, {f}));' for f, _t in st._fields_]
-    lines += ['  printf("\\n");', "  return 0;", "}"]
-    src, exe = tmp_path / "abi.c", tmp_path / "abi"
-    src.write_text("\n".join(lines))
-    r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-o", str(exe), str(src)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    size, *offs = subprocess.run([str(exe)], capture_output=True, text=True).stdout.split()
-    assert C.sizeof(st) == int(size)
-    assert [getattr(st, f).offset for f, _t in st._fields_] == [int(o) for o in offs]
-
-
 def test_merge_cpu_tensors_and_blobs_raise_no_fallback():
     ev, other = E.PropheseeEvaluator("gen1", False, 8, 64, 4), E.PropheseeEvaluator("gen1", False, 8, 64, 4)
     with pytest.raises(RuntimeError, match="no CPU fallback"):

@@ -2,11 +2,9 @@
 
 GPU tests hold the device front end to bit equality with frames the reference produced (tests/golden/events.npz, written by
 tests/golden/make_golden_events.py); the event streams are regenerated from that module's integer hash, so nothing here reads the
-reference on the GPU box.  CPU tests: argument checks, the ABI of the new struct, and -- where the reference is present -- that the
+reference on the GPU box.  CPU tests: argument checks (the ABI of the struct: tests/test_abi.py), and -- where the reference is present -- that the
 generator reproduces every committed fixture and that the timing tool's ATen restatement of construct equals the reference's."""
-import ctypes as C
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -32,24 +30,6 @@ def _ref_available():
 
 
 # ---------------------------------------------------------------------------------------------------------------------------- CPU
-
-def test_event_args_struct_matches_a_c_compiler(tmp_path):
-    from sast_amd import _lib
-    st = _lib.SastEventArgs
-    lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{_lib.HEADER_PATH}"', "int main(void) {",
-             '  printf("%zu", sizeof(SastEventArgs));']
-    lines += [f'  printf(" %zu", offsetof(SastEventArgs, {f}));' for f, _t in st._fields_]
-    lines += ['  printf(" %d %d %d %d %d\\n", SAST_DT_I64, SAST_DT_I16, SAST_EVENT_WINDOW_DURATION, SAST_EVENT_WINDOW_COUNT, '
-              'SAST_EVENT_SCAN_BLOCKS);', "  return 0;", "}"]
-    (tmp_path / "abi.c").write_text("\n".join(lines))
-    r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-o", str(tmp_path / "abi"), str(tmp_path / "abi.c")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    size, *rest = [int(v) for v in subprocess.run([str(tmp_path / "abi")], capture_output=True, text=True).stdout.split()]
-    offs, consts = rest[:len(st._fields_)], rest[len(st._fields_):]
-    assert C.sizeof(st) == size
-    assert [getattr(st, f).offset for f, _t in st._fields_] == offs
-    assert consts == [_lib.DT_I64, _lib.DT_I16, _lib.EVENT_WINDOW_DURATION, _lib.EVENT_WINDOW_COUNT, _lib.EVENT_SCAN_BLOCKS]
-
 
 def test_event_entry_points_exported_and_bound():
     from sast_amd import _lib

@@ -3,12 +3,11 @@ sast_mdstack_frames of csrc/k_events.hip) and int8 frames into the detector's in
 
 GPU tests hold the device front end to byte equality with frames the reference produced on the CPU (tests/golden/mixed_density.npz,
 written by tests/golden/make_golden_mixed_density.py); the events are regenerated from the golden modules' integer hash.  Everything is
-integer: there is no tolerance anywhere.  CPU tests: the ABI of the new struct and symbols, argument checks, and that the numpy
+integer: there is no tolerance anywhere.  CPU tests: the symbols (the ABI of the struct: tests/test_abi.py), argument checks, and that the numpy
 restatement of the rule equals every fixture frame (which pins the restatement, used by the GPU tests for a few extra cases, to the
 reference)."""
 import ctypes as C
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -36,23 +35,6 @@ def _ref_available():
 
 
 # ---------------------------------------------------------------------------------------------------------------------------- CPU
-
-def test_mdstack_args_struct_matches_a_c_compiler(tmp_path):
-    from sast_amd import _lib
-    st = _lib.SastMdStackArgs
-    lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{_lib.HEADER_PATH}"', "int main(void) {",
-             '  printf("%zu", sizeof(SastMdStackArgs));']
-    lines += [f'  printf(" %zu", offsetof(SastMdStackArgs, {f}));' for f, _t in st._fields_]
-    lines += ['  printf(" %d %d %d\\n", SAST_DT_I8, SAST_DT_U8, SAST_DT_I16);', "  return 0;", "}"]
-    (tmp_path / "abi.c").write_text("\n".join(lines))
-    r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-o", str(tmp_path / "abi"), str(tmp_path / "abi.c")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    size, *rest = [int(v) for v in subprocess.run([str(tmp_path / "abi")], capture_output=True, text=True).stdout.split()]
-    offs, consts = rest[:len(st._fields_)], rest[len(st._fields_):]
-    assert C.sizeof(st) == size
-    assert [getattr(st, f).offset for f, _t in st._fields_] == offs
-    assert consts == [_lib.DT_I8, _lib.DT_U8, _lib.DT_I16]
-
 
 def test_mdstack_entry_points_exported_and_bound():
     from sast_amd import _lib
