@@ -81,7 +81,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
 
 
 def build_variant(out: str, flags, obj_dir=None) -> str:
-    """an A/B build of the product library with extra compile flags (e.g. -DSAST_SINGLE_TILE_ACCS=1) next to the in-tree one;
+    """an A/B build of the product library with extra compile flags (e.g. -DSAST_MFMA_SPLIT3=0) next to the in-tree one;
     run with SAST_LIB_PATH=<out> (tools only: A/B measurements inside one gpurun call)."""
     out = os.path.abspath(out)
     obj_dir = obj_dir or out + ".obj"

@@ -35,7 +35,7 @@ inline bool launch_failed_take() { const bool f = g_launch_failed != 0; g_launch
 
 // Every SAST_* tuning knob of the library is read through SAST_KNOB(name, default): the value comes from the environment, is cached
 // per call site, and is re-read after sast_config_reload() (include/sast_hip.h) -- a host that changes a knob inside the process
-// (tools, tests, A/B scripts) says so instead of being silently ignored by a value latched at first use.  k_prof.hip keeps the
+// (tools, tests, A/B scripts) says so instead of being silently ignored by a value latched at first use.  k_config.hip keeps the
 // registry of the knobs that have been read (sast_config_report).
 namespace sast {
 int knob_read(const char* name, int dflt);
@@ -50,32 +50,18 @@ unsigned knob_generation();
     return v_;                                                                 \
   }())
 
-// Issue priority of the kernels of the backward CHAIN (experiment, round 6: with deferred weight gradients a side stream's workgroups
-// share the SIMDs with the chain's; -DSAST_MAIN_PRIO=n raises the chain's waves over the side stream's, which stay at the default 0)
-#ifndef SAST_MAIN_PRIO
-#define SAST_MAIN_PRIO 0
-#endif
-#if SAST_MAIN_PRIO > 0
-#define SAST_CHAIN_PRIO() __builtin_amdgcn_s_setprio(SAST_MAIN_PRIO)
-#else
-#define SAST_CHAIN_PRIO()
-#endif
-
 // Round 6: kernel-argument warm-up.  hipcc sinks the scalar loads of by-value struct arguments next to their uses, behind the early-exit
 // branches: the prologue of a GEMM workgroup is a chain of ~7 `s_load -> s_waitcnt lgkmcnt(0)` round trips (seen in the ISA), and the
 // first touch of every 64-byte line of the kernel-argument segment is a scalar-cache miss -- paid by the first wave of every CU, i.e. by
 // every workgroup of a one-wave-per-CU launch, one line after the other.  kernarg_warm<BYTES>() requests the lines of the kernel's OWN
 // EXPLICIT arguments (BYTES = sum of their sizes: never past the segment) with back-to-back scalar loads at kernel entry: one miss
-// latency instead of one per line.  Measured -1.3 % of the step (profiles/r06_s).  SAST_KERNARG_WARM: most lines warmed (0 = off; 8
-// measured neutral: lines nobody reads cost what they save).
-#ifndef SAST_KERNARG_WARM
-#define SAST_KERNARG_WARM 5
-#endif
+// latency instead of one per line.  Measured -1.3 % of the step (profiles/r06_s).  KERNARG_WARM_LINES: most lines warmed (8 measured
+// neutral: lines nobody reads cost what they save).
+constexpr int KERNARG_WARM_LINES = 5;
 template <int BYTES>
 __device__ __forceinline__ void kernarg_warm() {
-#if SAST_KERNARG_WARM > 0
   constexpr int LINES_IN = BYTES >= 4 ? (BYTES - 4) / 64 + 1 : 0;                   // lines whose first dword lies inside the explicit arguments
-  constexpr int LINES = LINES_IN < SAST_KERNARG_WARM ? LINES_IN : SAST_KERNARG_WARM;
+  constexpr int LINES = LINES_IN < KERNARG_WARM_LINES ? LINES_IN : KERNARG_WARM_LINES;
   if constexpr (LINES >= 2) {                                                      // a single line is one round trip either way
     using cptr = const __attribute__((address_space(4))) unsigned*;
     cptr ka = (cptr)__builtin_amdgcn_kernarg_segment_ptr();
@@ -84,7 +70,6 @@ __device__ __forceinline__ void kernarg_warm() {
     for (int i = 0; i < LINES; ++i) acc |= ka[16 * i];
     asm volatile("" :: "s"(acc));
   }
-#endif
 }
 // explicit-argument bytes of a kernel from its own type (padding ignored: an underestimate)
 template <class F> struct KernargBytes;
@@ -173,34 +158,13 @@ __device__ __forceinline__ T block_scan(T v, T* sm, T* total) {
 // Round 6: the IEEE division behind `1.0f / x` is ~20 VALU instructions on gfx950 (v_div_scale / v_rcp / 4 x fma / v_div_fmas / v_div_fixup);
 // the gate / activation epilogues evaluate one or more per output element and are VALU-bound there (the 4-gate LSTM epilogue: ~140
 // instructions per cell with libm's tanhf, MFMA pipe 12 % busy).  v_rcp_f32 is 1 ulp -- two orders of magnitude inside the fp32 parity
-// bars.  -DSAST_FAST_DIV=0 restores the divisions and libm's tanhf (A/B builds).
-#ifndef SAST_FAST_DIV
-#define SAST_FAST_DIV 1
-#endif
-__device__ __forceinline__ float rcp_hw(float x) {
-#if SAST_FAST_DIV
-  return __builtin_amdgcn_rcpf(x);
-#else
-  return 1.0f / x;
-#endif
-}
-__device__ __forceinline__ float rsqrt_hw(float x) {       // v_rsq_f32 (1 ulp)
-#if SAST_FAST_DIV
-  return __builtin_amdgcn_rsqf(x);
-#else
-  return 1.0f / sqrtf(x);
-#endif
-}
+// bars.
+__device__ __forceinline__ float rcp_hw(float x) { return __builtin_amdgcn_rcpf(x); }
+__device__ __forceinline__ float rsqrt_hw(float x) { return __builtin_amdgcn_rsqf(x); }       // v_rsq_f32 (1 ulp)
 __device__ __forceinline__ float sigmoid_hw(float x) { return rcp_hw(1.0f + __expf(-x)); }
 // tanh on the same path: 1 - 2 / (1 + e^{2x}) (saturates correctly: e = inf -> 1, e = 0 -> -1; absolute error <= 1.2e-7, the ulp of the
 // 1 it is subtracted from -- libm's tanhf is ~37 instructions with branches)
-__device__ __forceinline__ float tanh_hw(float x) {
-#if SAST_FAST_DIV
-  return 1.0f - 2.0f * rcp_hw(1.0f + __expf(2.0f * x));
-#else
-  return tanhf(x);
-#endif
-}
+__device__ __forceinline__ float tanh_hw(float x) { return 1.0f - 2.0f * rcp_hw(1.0f + __expf(2.0f * x)); }
 
 // erf by Abramowitz-Stegun 7.1.26 (|error| <= 1.5e-7, i.e. fp32 rounding level) instead of libm's branchy erff:
 // the GLU epilogues evaluate it for every (token, inner channel) and were VALU-bound on erff.
@@ -272,27 +236,8 @@ __device__ __forceinline__ float glu_act_grad(float g, int act, float a = 0.0f) 
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 __device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
 __device__ __forceinline__ float4 zero4() { return make_float4(0.f, 0.f, 0.f, 0.f); }
-// stores of activations that ONLY the backward pass reads (milliseconds later): -DSAST_NT_SAVED=1 gives them the non-temporal form
-// (round-5 verdict item 2: do ~0.7 GB per step of write-once data evict the weights and the next layer's operands from L2 / MALL?)
-#ifndef SAST_NT_SAVED
-#define SAST_NT_SAVED 0
-#endif
-__device__ __forceinline__ void st4_saved(float* p, float4 v) {
-#if SAST_NT_SAVED
-  typedef float f4v_ __attribute__((ext_vector_type(4)));
-  f4v_ t; t.x = v.x; t.y = v.y; t.z = v.z; t.w = v.w;
-  __builtin_nontemporal_store(t, reinterpret_cast<f4v_*>(p));
-#else
-  st4(p, v);
-#endif
-}
-__device__ __forceinline__ void st_saved(float* p, float v) {
-#if SAST_NT_SAVED
-  __builtin_nontemporal_store(v, p);
-#else
-  *p = v;
-#endif
-}
+// (activations that ONLY the backward pass reads are stored like everything else: non-temporal stores for them measured 2 % slower, see
+// DESIGN "Retired compile-time switches")
 
 // exact n / d for n * d < 2^32 with mul = 2^32 / d + 1 (one v_mul_hi_u32 instead of the ~35-instruction integer division; the
 // weight-gradient im2col loader ran two of those per load inside its k-loop)

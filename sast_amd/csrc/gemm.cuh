@@ -22,8 +22,8 @@
 //   of selected tokens.
 // * LDS: an RC operand keeps its natural [row][k] order (row stride BK + 4: ds_write_b128 /
 //   ds_read_b128), an IC operand is stored [k][row] (ds_read_b32); both conflict-free.
-// * global loads are branch-free and un-predicated (clamped address + select at LDS-store
-//   time): anything else makes hipcc drain vmcnt(0) before every load of the k-loop.
+// * global loads are branch-free and un-predicated (an invalid slot reads a page of zeros):
+//   anything else makes hipcc drain vmcnt(0) before every load of the k-loop.
 // * split-R form (weight gradients): `nsplit` work items per output tile partition the
 //   reduction, the epilogue accumulates atomically; optionally the column sums of the A
 //   operand (bias gradient) are produced by the same pass so dY is read once.
@@ -73,23 +73,10 @@ using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
 // middle 8 and bottom 8 significand bits; truncation, so the residuals are exact), packed as the 8-element operands of
 // v_mfma_f32_32x32x16_bf16 (element j in bits [16j, 16j+16))
 struct Split3 { bf16x8 h, m, l; };
-// SAST_SPLIT_PK=1 (A/B builds): the two residuals of a PAIR of values as one packed subtraction each (v_pk_add_f32; the residuals are
-// exact, so the packed form gives the same bits) -- 4.5 VALU instructions per value instead of 5.5, and MEASURED SLOWER: +1.2 % on the
-// step (profiles/r06_w_ab_split_pk_and_weight_planes.txt); packed fp32 beside MFMAs costs more than the issue slot it saves.
-#ifndef SAST_SPLIT_PK
-#define SAST_SPLIT_PK 0
-#endif
-using f32x2 = __attribute__((ext_vector_type(2))) float;
 using u32x2 = __attribute__((ext_vector_type(2))) unsigned;
-// x[0..1] -> the packed (element 1 << 16 | element 0) bf16 pairs of the three terms
+// x[0..1] -> the packed (element 1 << 16 | element 0) bf16 pairs of the three terms (scalar residuals: the packed v_pk_add_f32 form
+// measured slower, see DESIGN "Retired compile-time switches")
 __device__ __forceinline__ void split3_pair(float x0, float x1, unsigned& ph, unsigned& pm, unsigned& pl) {
-#if SAST_SPLIT_PK
-  const f32x2 x = {x0, x1};
-  const u32x2 h = __builtin_bit_cast(u32x2, x) & 0xffff0000u;
-  const f32x2 r1 = x - __builtin_bit_cast(f32x2, h);
-  const u32x2 m = __builtin_bit_cast(u32x2, r1) & 0xffff0000u;
-  const u32x2 l = __builtin_bit_cast(u32x2, r1 - __builtin_bit_cast(f32x2, m));   // <= 8 significant bits left: its high half IS the bf16
-#else
   unsigned h[2], m[2], l[2];
   const float xs[2] = {x0, x1};
 #pragma unroll
@@ -99,7 +86,6 @@ __device__ __forceinline__ void split3_pair(float x0, float x1, unsigned& ph, un
     m[i] = __float_as_uint(r1) & 0xffff0000u;
     l[i] = __float_as_uint(r1 - __uint_as_float(m[i]));      // <= 8 significant bits left: its high half IS the bf16
   }
-#endif
   ph = __builtin_amdgcn_perm(h[1], h[0], 0x07060302u);      // (hi16 of element 1) << 16 | hi16 of element 0
   pm = __builtin_amdgcn_perm(m[1], m[0], 0x07060302u);
   pl = __builtin_amdgcn_perm(l[1], l[0], 0x07060302u);
@@ -123,23 +109,6 @@ __device__ __forceinline__ void store_split3(float* dst, int plane_floats, float
   *reinterpret_cast<u32x2*>(dst) = h;
   *reinterpret_cast<u32x2*>(dst + plane_floats) = m;
   *reinterpret_cast<u32x2*>(dst + 2 * plane_floats) = l;
-}
-
-// TIMING PROBE ONLY (-DSAST_PROBE_B_SPLIT_FREE=1, approximate numbers): the B operand of the non-split-R GEMMs -- always a weight -- is
-// stored as its top plane only (middle and bottom planes zero: the products lose ~2^-8 relative, the selection stays where it was --
-// bench.py prints the kept-token fractions), i.e. what staging would cost if the weights arrived already split AT THE SAME LOAD COUNT.
-// Every real layout of pre-split weights in HBM needs 1.5 loads per 4 values and measured slower:
-// profiles/r06_w_ab_split_pk_and_weight_planes.txt, tools/experiments/r06_weight_planes.patch
-#ifndef SAST_PROBE_B_SPLIT_FREE
-#define SAST_PROBE_B_SPLIT_FREE 0
-#endif
-__device__ __forceinline__ void store_split3_probe(float* dst, int plane_floats, float4 v) {
-  const u32x2 h = {__builtin_amdgcn_perm(__float_as_uint(v.y), __float_as_uint(v.x), 0x07060302u),
-                   __builtin_amdgcn_perm(__float_as_uint(v.w), __float_as_uint(v.z), 0x07060302u)};
-  const u32x2 z = {0u, 0u};
-  *reinterpret_cast<u32x2*>(dst) = h;
-  *reinterpret_cast<u32x2*>(dst + plane_floats) = z;
-  *reinterpret_cast<u32x2*>(dst + 2 * plane_floats) = z;
 }
 
 // an operand whose values are EXACTLY one bf16 each (loader trait EXACT_BF16: the stem's event tensor, small integers): its middle and
@@ -183,20 +152,6 @@ __device__ __forceinline__ Split3 psi_read(const float* planes, int c0, int lane
   else return Split3{r[0], r[1], r[2]};
 }
 
-// PF: k-tiles kept in flight in registers per k-group (global-load latency under load is ~2-3 us on MI355X, one k-tile of
-// MFMA work is ~0.2-0.4 us: see tools/gemm_timeline.py).  Must be even (LDS is double-buffered).
-#ifndef SAST_PF_DEFAULT
-#define SAST_PF_DEFAULT 2
-#endif
-// 1: reduce-contiguous operands are split into their bf16 planes once, at the LDS store (see OperandPresplit)
-#ifndef SAST_PRESPLIT_RC
-#define SAST_PRESPLIT_RC 1
-#endif
-// 1: index-contiguous operands too: split at the LDS store into [k][index] bf16 planes, read back through the transposing LDS read
-// (ds_read_b64_tr_b16) straight into MFMA operand order (see OperandPresplitIC)
-#ifndef SAST_PRESPLIT_IC
-#define SAST_PRESPLIT_IC 1
-#endif
 // 1: fp32 products on the bf16 matrix pipe through an exact three-way operand split (gemm_body::compute); 0: v_mfma_f32_32x32x2_f32
 #ifndef SAST_MFMA_SPLIT3
 #define SAST_MFMA_SPLIT3 1
@@ -205,34 +160,15 @@ __device__ __forceinline__ Split3 psi_read(const float* planes, int c0, int lane
 #ifndef SAST_MFMA_BF16
 #define SAST_MFMA_BF16 0
 #endif
-#ifndef SAST_BF16_MFMA_REPEAT
-#define SAST_BF16_MFMA_REPEAT 1
-#endif
 // the loads of a phase are ISSUED before anything else of the phase: without the fence hipcc moves the validity selects / bf16 splits of the
 // register sets loaded in earlier phases (lstore) to the top of the phase, in front of the new loads, and waits for them there with
 // s_waitcnt vmcnt(0) -- no load is then in flight for longer than one phase (seen in the ISA; the k-loops ran at one global-load latency,
 // ~0.65 us, per k-tile whatever the tile shape: tools/gemm_timeline.py)
-#ifndef SAST_SCHED_FENCE
-#define SAST_SCHED_FENCE 1
-#endif
-#if SAST_SCHED_FENCE
 #define SAST_PHASE_FENCE() __builtin_amdgcn_sched_barrier(0)
-#else
-#define SAST_PHASE_FENCE()
-#endif
-#ifndef SAST_WAVE_GROUPS_FREE
-#define SAST_WAVE_GROUPS_FREE 1
-#endif
-// 1: the bias-gradient column sums of a weight-gradient job leave the workgroup as ONE atomic instruction per 64 columns (gemm_body)
-#ifndef SAST_COLSUM_LDS
-#define SAST_COLSUM_LDS 1
-#endif
-// independent accumulators of a wave that owns a single 32x32 output tile (1 = the round-1 kernel; see gemm_body)
-#ifndef SAST_SINGLE_TILE_ACCS
-#define SAST_SINGLE_TILE_ACCS 1
-#endif
+// PF: k-tiles kept in flight in registers per k-group (global-load latency under load is ~2-3 us on MI355X, one k-tile of
+// MFMA work is ~0.2-0.4 us: see tools/gemm_timeline.py).  Must be even (LDS is double-buffered).
 // OCC: blocks per CU the register allocation must leave room for (0 = no constraint beyond the block size).
-template <int BM_, int BN_, int WAVES_M_, int WAVES_N_, int G_, int BK_ = 16, int KS_ = 1, int PF_ = SAST_PF_DEFAULT, int OCC_ = 0>
+template <int BM_, int BN_, int WAVES_M_, int WAVES_N_, int G_, int BK_ = 16, int KS_ = 1, int PF_ = 2, int OCC_ = 0>
 struct Tile {
   static constexpr int BM = BM_, BN = BN_, BK = BK_, WAVES_M = WAVES_M_, WAVES_N = WAVES_N_, G = G_, KS = KS_, PF = PF_;
   static constexpr int MINW = OCC_ > 0 ? OCC_ * ((WAVES_M_ * WAVES_N_ * KS_ + 3) / 4) : 1;   // min waves per SIMD (launch bounds)
@@ -288,7 +224,7 @@ template <class EP> struct EpHasStats<EP, std::void_t<decltype(EP::COLSTATS)>> :
 // 20 floats per row) would push a workgroup beyond 80 KB of LDS, nor for the LSTM tiles (G = 4, and G = 3 of the zero-cell-state form: one wave reads all
 // 128 / 96 B rows there: nothing is shared, and the larger planes made the stage-1/2 LSTM GEMMs 25 % slower).
 template <class T, class L>
-struct OperandPresplitWanted { static constexpr bool value = SAST_MFMA_SPLIT3 && !SAST_MFMA_BF16 && SAST_PRESPLIT_RC && L::RC && (T::BK == 16 || T::BK == 32) && T::KS <= 4 && T::G < 3; };
+struct OperandPresplitWanted { static constexpr bool value = SAST_MFMA_SPLIT3 && !SAST_MFMA_BF16 && L::RC && (T::BK == 16 || T::BK == 32) && T::KS <= 4 && T::G < 3; };
 constexpr int PS_ROW_FLOATS = 3 * 16 / 2;         // 3 planes x 16 bf16 per row, in floats (24)
 // unpadded 32-byte plane rows: the 16-byte chunk (k 0-7 | k 8-15) of a row is XOR-ed with bit 3 of the row index.  ds_read_b128 serves
 // the lane groups {0-3,12-15,20-27} / {4-11,16-19,28-31}: with the swizzle their 16 chunks are 16 different 16-byte bank groups
@@ -303,7 +239,7 @@ constexpr int PS_MAX_FLOATS = 20480;              // a workgroup's LDS with pres
 // banks, so the granule index is XOR-ed with a function of k that moves the 4 rows of a block to 4 different 64-byte bank groups.
 template <class T, class L, int W>
 struct OperandPresplitIC {
-  static constexpr bool value = SAST_MFMA_SPLIT3 && !SAST_MFMA_BF16 && SAST_PRESPLIT_IC && !L::RC && (T::BK == 16 || T::BK == 32) && T::KS <= 4 && T::G < 3 &&
+  static constexpr bool value = SAST_MFMA_SPLIT3 && !SAST_MFMA_BF16 && !L::RC && (T::BK == 16 || T::BK == 32) && T::KS <= 4 && T::G < 3 &&
                                 (W == 32 || W == 64 || W == 128);
 };
 // granule (8 bytes = 4 index values) XOR of row k for a plane row of W values
@@ -477,8 +413,6 @@ __device__ __forceinline__ void gemm_body(const LA& la, const LB& lb, const EP& 
   constexpr bool XA = SAST_MFMA_SPLIT3 && !SAST_MFMA_BF16 && LoaderExactBf16<LA>::value;
   constexpr bool XB = SAST_MFMA_SPLIT3 && !SAST_MFMA_BF16 && LoaderExactBf16<LB>::value;
   static_assert(!(XA && XB), "one exact-bf16 operand per GEMM");
-  // the three-term body accumulates into accs[0] alone: with two accumulator chains the six-term body would round differently
-  static_assert(!(XA || XB) || SAST_SINGLE_TILE_ACCS == 1, "exact-bf16 loaders: three-term == six-term bit for bit needs SAST_SINGLE_TILE_ACCS == 1");
   constexpr bool XALWAYS = (XA && LoaderExactAlways<LA>::value) || (XB && LoaderExactAlways<LB>::value);
   auto lstore = [&](int buf, int set, auto ex) {
     constexpr bool EA = decltype(ex)::value && XA, EB = decltype(ex)::value && XB;
@@ -499,7 +433,6 @@ __device__ __forceinline__ void gemm_body(const LA& la, const LB& lb, const EP& 
     for (int it = 0; it < B_PER; ++it)
       if (B_SLOTS % NT == 0 || tid + it * NT < B_SLOTS) {
         if constexpr (PSB && EB) store_hi(bs + lb_off[it], lb.finish(rb[set][it], ab[set][it], ob[set][it]));
-        else if constexpr (PSB && SAST_PROBE_B_SPLIT_FREE && !SPLIT) store_split3_probe(bs + lb_off[it], BN * 8, lb.finish(rb[set][it], ab[set][it], ob[set][it]));
         else if constexpr (PSB) store_split3(bs + lb_off[it], BN * 8, lb.finish(rb[set][it], ab[set][it], ob[set][it]));
         else st4(bs + lb_off[it], lb.finish(rb[set][it], ab[set][it], ob[set][it]));
       }
@@ -514,22 +447,14 @@ __device__ __forceinline__ void gemm_body(const LA& la, const LB& lb, const EP& 
   constexpr bool EARLY_AUX = T::TM * T::TJ == 1;
   typename EP::Aux eaux[EARLY_AUX ? 16 : 1];
 
-  // a wave with ONE 32x32 accumulator tile issues a chain of MFMAs that each depend on the previous one.  Hypothesis tested in
-  // round 2: whatever the compiler schedules between two of them delays the chain, so two accumulators for the even / odd k-steps
-  // (dependency distance two) should help.  Measured: they do NOT (step 5.83 vs 5.715 ms, the weight-gradient micro-benchmark 2-5 %
-  // slower): back-to-back dependent v_mfma_f32_32x32x2_f32 issue at full rate on gfx950 and the extra 16 VGPRs cost more than the
-  // slack buys.  Kept as a compile-time knob (-DSAST_SINGLE_TILE_ACCS=2).
-  constexpr int NACC = (T::TM * T::TN == 1) ? SAST_SINGLE_TILE_ACCS : 1;
-  f32x16 accs[NACC][T::TM][T::TN];
+  // one accumulator chain per output tile (two chains for a one-tile wave measured slower twice, see DESIGN "Retired compile-time switches")
+  f32x16 acc[T::TM][T::TN];
 #pragma unroll
-  for (int c = 0; c < NACC; ++c)
+  for (int a = 0; a < T::TM; ++a)
 #pragma unroll
-    for (int a = 0; a < T::TM; ++a)
+    for (int b = 0; b < T::TN; ++b)
 #pragma unroll
-      for (int b = 0; b < T::TN; ++b)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) accs[c][a][b][e] = 0.f;
-  f32x16 (&acc)[T::TM][T::TN] = accs[0];
+      for (int e = 0; e < 16; ++e) acc[a][b][e] = 0.f;
   float csum[T::TM];
 #pragma unroll
   for (int a = 0; a < T::TM; ++a) csum[a] = 0.f;
@@ -572,7 +497,7 @@ __device__ __forceinline__ void gemm_body(const LA& la, const LB& lb, const EP& 
               if (!term_live(term, EA, EB)) continue;     // (an exact-bf16 operand: the terms of its zero planes are not issued; same order)
               const bf16x8 x = term == 0 ? sa[ta].l : (term == 2 || term == 3) ? sa[ta].m : sa[ta].h;      // l.h, h.l, m.m, m.h, h.m, h.h: smallest terms first
               const bf16x8 y = term == 1 ? sb[tb].l : (term == 2 || term == 4) ? sb[tb].m : sb[tb].h;
-              accs[0][ta][tb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x, y, accs[0][ta][tb], 0, 0, 0);
+              acc[ta][tb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x, y, acc[ta][tb], 0, 0, 0);
             }
       }
       return;
@@ -637,8 +562,7 @@ __device__ __forceinline__ void gemm_body(const LA& la, const LB& lb, const EP& 
       for (int ta = 0; ta < T::TM; ++ta)
 #pragma unroll
         for (int tb = 0; tb < T::TN; ++tb)
-          for (int rep = 0; rep < SAST_BF16_MFMA_REPEAT; ++rep)     // (experiments: > 1 isolates the cost of the MFMAs from the cost of the split)
-            accs[0][ta][tb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ha[ta], hb[tb], accs[0][ta][tb], 0, 0, 0);
+          acc[ta][tb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ha[ta], hb[tb], acc[ta][tb], 0, 0, 0);
     } else if constexpr (SAST_MFMA_SPLIT3 && HK == 8) {
       // fp32 x fp32 on the bf16 matrix pipe: every operand is split EXACTLY into three bf16 terms, x = h + m + l (8 + 8 + 8
       // significand bits by truncation; the residuals x - h and x - h - m are exact in fp32), and the product is evaluated as the six
@@ -660,31 +584,18 @@ __device__ __forceinline__ void gemm_body(const LA& la, const LB& lb, const EP& 
           else sb[t] = split3(b[t]);
         }
       }
-      // MFMA order: a wave with several output tiles issues term by term ACROSS its tiles, so that consecutive MFMAs do not share an
-      // accumulator.  For a wave with ONE tile two chains (even / odd terms, -DSAST_SINGLE_TILE_ACCS=2) were measured again under the bf16
-      // split: +-0 in the micro-benchmarks, +0.5 % on the step (16 more VGPRs) -- the chain is not what the k-loop waits for
-      if constexpr (NACC > 1 && !(EA || EB)) {
-        f32x16 c0 = accs[0][0][0], c1 = accs[1][0][0];
-        c0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sa[0].l, sb[0].h, c0, 0, 0, 0);     // smallest terms first
-        c1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sa[0].h, sb[0].l, c1, 0, 0, 0);
-        c0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sa[0].m, sb[0].m, c0, 0, 0, 0);
-        c1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sa[0].m, sb[0].h, c1, 0, 0, 0);
-        c0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sa[0].h, sb[0].m, c0, 0, 0, 0);
-        c1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sa[0].h, sb[0].h, c1, 0, 0, 0);
-        accs[0][0][0] = c0; accs[1][0][0] = c1;
-      } else {
+      // MFMA order: term by term ACROSS the wave's output tiles, so that consecutive MFMAs do not share an accumulator
 #pragma unroll
-        for (int term = 0; term < 6; ++term)
+      for (int term = 0; term < 6; ++term)
 #pragma unroll
-          for (int ta = 0; ta < T::TM; ++ta)
+        for (int ta = 0; ta < T::TM; ++ta)
 #pragma unroll
-            for (int tb = 0; tb < T::TN; ++tb) {
-              if (!term_live(term, EA, EB)) continue;
-              const bf16x8 x = term == 0 ? sa[ta].l : (term == 2 || term == 3) ? sa[ta].m : sa[ta].h;      // l.h, h.l, m.m, m.h, h.m, h.h
-              const bf16x8 y = term == 1 ? sb[tb].l : (term == 2 || term == 4) ? sb[tb].m : sb[tb].h;
-              accs[0][ta][tb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x, y, accs[0][ta][tb], 0, 0, 0);
-            }
-      }
+          for (int tb = 0; tb < T::TN; ++tb) {
+            if (!term_live(term, EA, EB)) continue;
+            const bf16x8 x = term == 0 ? sa[ta].l : (term == 2 || term == 3) ? sa[ta].m : sa[ta].h;      // l.h, h.l, m.m, m.h, h.m, h.h
+            const bf16x8 y = term == 1 ? sb[tb].l : (term == 2 || term == 4) ? sb[tb].m : sb[tb].h;
+            acc[ta][tb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x, y, acc[ta][tb], 0, 0, 0);
+          }
     } else {
 #pragma unroll
       for (int ks = 0; ks < HK; ++ks)
@@ -692,13 +603,13 @@ __device__ __forceinline__ void gemm_body(const LA& la, const LB& lb, const EP& 
         for (int ta = 0; ta < T::TM; ++ta)
 #pragma unroll
           for (int tb = 0; tb < T::TN; ++tb)
-            accs[ks % NACC][ta][tb] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[ta][ks], b[tb][ks], accs[ks % NACC][ta][tb], 0, 0, 0);
+            acc[ta][tb] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[ta][ks], b[tb][ks], acc[ta][tb], 0, 0, 0);
     }
   };
 
   // software pipeline: this k-group owns tiles kt0 + kg + KS*i.  At phase p the LDS buffer p%2 holds tile p, register set
   // (p+1)%PF .. (p+PF-1)%PF hold tiles p+1 .. p+PF-1 and set p%PF (stored to LDS one phase ago) is refilled with tile p+PF.
-  // All loads are issued UNCONDITIONALLY (tiles past the end read clamped addresses and become zeros), so the compiler's
+  // All loads are issued UNCONDITIONALLY (tiles past the end read the zero page), so the compiler's
   // s_waitcnt vmcnt(N) before each LDS store counts exactly the PF-1 younger tiles and leaves them in flight; with loads
   // under a validity branch it has to assume the not-taken path and drains everything.  n_it is block-uniform.
   const int n_it = (kt1 - kt0 + KS - 1) / KS;
@@ -706,9 +617,9 @@ __device__ __forceinline__ void gemm_body(const LA& la, const LB& lb, const EP& 
   // the k-loop synchronises the waves that SHARE a stage.  A k-group of one wave shares nothing: its LDS traffic is ordered by the wave's
   // own instruction order (the LDS queue of a wave is in order), so it runs the whole reduction without a workgroup barrier -- the
   // barrier would only keep the k-groups of the workgroup in lockstep (every wave reading LDS, then every wave in its MFMA chain, then
-  // every wave in the split) instead of letting them overlap.  SAST_WAVE_GROUPS_FREE=0 restores the barrier.
+  // every wave in the split) instead of letting them overlap.
   auto group_sync = [&]() {
-    if constexpr (NT > 64 || !SAST_WAVE_GROUPS_FREE) __syncthreads();
+    if constexpr (NT > 64) __syncthreads();
     else { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); }
   };
   // the reduction loop (gemm_kloop.inc).  An instantiation with an exact-bf16 operand carries it twice -- ex = true: one plane of that
@@ -732,12 +643,6 @@ __device__ __forceinline__ void gemm_body(const LA& la, const LB& lb, const EP& 
 #include "gemm_kloop.inc"
   }
 
-  if constexpr (NACC > 1) {
-#pragma unroll
-    for (int c = 1; c < NACC; ++c)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) accs[0][0][0][e] += accs[c][0][0][e];
-  }
   SAST_TL(2);
   // Column sums of an index-contiguous A (the bias gradient of a weight-gradient job).  Every atomic INSTRUCTION aimed at the same
   // 128-byte line costs ~25 ns, serialised chip-wide (measured, profiles/r03_a_tn_colsum_atomics.txt: 192 splits x 4 waves x 4
@@ -747,7 +652,7 @@ __device__ __forceinline__ void gemm_body(const LA& la, const LB& lb, const EP& 
   constexpr int CS_OFF = KS > 1 ? T::WAVES_M * T::WAVES_N * T::TM * T::TN * 16 * 64 : 0;
   constexpr int CS_WAVES = T::WAVES_M * T::WAVES_N;
   constexpr bool CS_FAST = 64 % (BM / 4) == 0 && A_SLOTS % NT == 0;
-  constexpr bool CS_LDS = SAST_COLSUM_LDS && SPLIT && !LA::RC && CS_FAST && CS_OFF + CS_WAVES * BM <= GROUP_FLOATS;
+  constexpr bool CS_LDS = SPLIT && !LA::RC && CS_FAST && CS_OFF + CS_WAVES * BM <= GROUP_FLOATS;
   if constexpr (SPLIT && !LA::RC) {
     if (do_colsum) {
       if constexpr (CS_FAST) {   // a thread's slots all belong to index quad lane % (BM/4): fold the slots, then the lanes that share the quad
@@ -891,10 +796,7 @@ __device__ __forceinline__ void gemm_body(const LA& la, const LB& lb, const EP& 
         }
       }
   };
-#ifndef SAST_EPILOGUE_INSIDE
-#define SAST_EPILOGUE_INSIDE 1
-#endif
-  if (SAST_EPILOGUE_INSIDE && m0 + BM <= Meff && j0 + BJ <= NJ) emit(std::true_type{});      // block-uniform
+  if (m0 + BM <= Meff && j0 + BJ <= NJ) emit(std::true_type{});      // block-uniform
   else emit(std::false_type{});
   if constexpr (STATS) {
 #pragma unroll
@@ -914,7 +816,6 @@ __global__ __launch_bounds__(T::NT, T::MINW) void gemm_kernel(LA la, LB lb, EP e
                                                               float* __restrict__ colsum, int nsplit, int xcd_remap) {
   __shared__ __attribute__((aligned(16))) float smem[GemmSmem<T, LA, LB>::FLOATS];
   kernarg_warm<(int)(sizeof(LA) + sizeof(LB) + sizeof(EP) + 3 * sizeof(int) + 3 * sizeof(void*) + 2 * sizeof(int))>();
-  SAST_CHAIN_PRIO();
   int nmain = gridDim.x;
   if constexpr (EpHasSide<EP>::value) {
     nmain -= ep.side_blocks;
@@ -939,7 +840,6 @@ __global__ __launch_bounds__((J1::T::NT > J2::T::NT ? J1::T::NT : J2::T::NT)) vo
   constexpr int F2 = GemmSmem<typename J2::T, typename J2::LA, typename J2::LB>::FLOATS;
   __shared__ __attribute__((aligned(16))) float smem[F1 > F2 ? F1 : F2];
   kernarg_warm<(int)(sizeof(J1) + sizeof(J2) + sizeof(int))>();
-  SAST_CHAIN_PRIO();
   if ((int)blockIdx.x < n1) {
     SAST_TL_JOB(1);
     if (threadIdx.x >= J1::T::NT) return;   // surplus waves of the larger workgroup shape (block-uniform per wave)
@@ -1138,13 +1038,7 @@ using TileSmallK4 = Tile<64, 64, 2, 2, 1, 16, 4>;   // + 4-way intra-block k spl
 // LDS reads serve two MFMA tiles), 2 k-groups of 2 waves.  Measured under the operand split, A/B in one call: -2.0 % of the step against
 // the 2x2-wave K2 form (8 waves) with 192 workgroups in the paired launches; the 4-k-group form of the same wave tile (8 waves, 70 KB
 // of LDS) is faster alone but 4 % slower in the step -- it costs the paired launches their co-residency with the dX job.
-#ifdef SAST_SPLITR_32X64_K4
-using TileSplitR = Tile<64, 64, 2, 1, 1, 16, 4>;
-#elif defined(SAST_SPLITR_2X2)
-using TileSplitR = Tile<64, 64, 2, 2, 1, 16, 2>;
-#else
 using TileSplitR = Tile<64, 64, 2, 1, 1, 16, 2>;
-#endif
 using TileThinK4  = Tile<32, 64, 1, 2, 1, 16, 4>;   // 32x64 block, 4 k-groups of 2 waves: for grids of < ~1.5 64x64-tiles per CU
 using TileTinyK8 = Tile<32, 32, 1, 1, 1, 16, 8>;   // 32x32 block, 8 single-wave k-groups: grids of < ~half a 32x64-tile per CU with a long reduction
 using TileTiny  = Tile<32, 32, 1, 1, 1>;    // one wave per block: fills the chip when M*N is small (stage 3/4, PAFPN)
@@ -1176,43 +1070,17 @@ __host__ __device__ inline int small_div_mul(int d) { return 65536 / d + 1; }
 // with a select.  (A predicated `cond ? ld4(p) : 0` becomes an exec-masked branch around the global_load; hipcc then
 // cannot count outstanding loads across the join and emits s_waitcnt vmcnt(0) at the top of every k-loop phase, which
 // serialised the two-tile prefetch -- seen in the ISA of the first version of this kernel.)
-// Round 6 (SAST_ZERO_PAGE): an invalid slot used to read a CLAMPED in-bounds address and was replaced by zeros with a select at the
-// LDS store (4 v_cndmask per float4, 11-16 % of the k-loop's VALU instructions, plus the clamps).  Now it reads a 16-byte page of
-// zeros instead: the validity decides the ADDRESS (one 64-bit select), the loaded value needs no select.  Still branch-free.
-#ifndef SAST_ZERO_PAGE
-#define SAST_ZERO_PAGE 1
-#endif
+// An invalid slot reads a 16-byte page of zeros: the validity decides the ADDRESS (one 64-bit select), the loaded value needs no
+// select.  (The older form, a clamped in-bounds address and 4 v_cndmask per float4 at the LDS store, cost 11-16 % of the k-loop's VALU
+// instructions: DESIGN "Retired compile-time switches".)
 static __device__ __attribute__((aligned(16))) float sast_zero_page[4];        // device globals are zero-initialised
-// the load of one slot: `valid` is the address of a slot whose flag is set (it may be out of bounds when the flag is not),
-// `clamped` the always-in-bounds address of the older form
-__device__ __forceinline__ float4 ldz(bool ok, const float* valid, const float* clamped) {
-#if SAST_ZERO_PAGE
-  (void)clamped;
-  return ld4(ok ? valid : sast_zero_page);
-#else
-  (void)ok; (void)valid;
-  return ld4(clamped);
-#endif
-}
-__device__ __forceinline__ float ldz1(bool ok, const void* valid, const void* clamped) {     // the 4-byte form (uint8 event tensors)
-#if SAST_ZERO_PAGE
-  (void)clamped;
+// the load of one slot: `valid` is the address of a slot whose flag is set (it may be out of bounds when the flag is not)
+__device__ __forceinline__ float4 ldz(bool ok, const float* valid) { return ld4(ok ? valid : sast_zero_page); }
+__device__ __forceinline__ float ldz1(bool ok, const void* valid) {     // the 4-byte form (uint8 event tensors)
   return *reinterpret_cast<const float*>(ok ? valid : (const void*)sast_zero_page);
-#else
-  (void)ok; (void)valid;
-  return *reinterpret_cast<const float*>(clamped);
-#endif
-}
-__device__ __forceinline__ float4 sel4(bool ok, float4 v) {
-#if SAST_ZERO_PAGE
-  (void)ok;
-  return v;
-#else
-  return ok ? v : zero4();
-#endif
 }
 #define SAST_DEFAULT_FINISH \
-  __device__ __forceinline__ float4 finish(float4 v, float, bool ok) const { return sel4(ok, v); }
+  __device__ __forceinline__ float4 finish(float4 v, float, bool) const { return v; }
 
 // RC rows: X[i][r] = p[row(i)*ld + r]
 struct LdRows {
@@ -1226,7 +1094,7 @@ struct LdRows {
   }
   __device__ __forceinline__ void load(const Ctx& c, int r, int Reff, float4& v, float& aux, bool& ok) const {
     ok = c.ok && r < Reff;
-    v = ldz(ok, c.row + r, c.row + (ok ? r : 0));
+    v = ldz(ok, c.row + r);
     aux = 0.f;
   }
   SAST_DEFAULT_FINISH
@@ -1245,7 +1113,7 @@ struct LdRows2 {
     const bool second = r >= R1;
     ok = c.ok && r < Reff && (!second || p2 != nullptr);
     const float* q = second ? c.b : c.a;
-    v = ldz(ok, q + r, ok ? q + r : c.a);
+    v = ldz(ok, q + r);
     aux = 0.f;
   }
   SAST_DEFAULT_FINISH
@@ -1261,7 +1129,7 @@ struct LdRowsT {
   __device__ __forceinline__ Ctx prep(int j, int, int NJ) const { return Ctx{j < NJ ? j : 0, j < NJ}; }
   __device__ __forceinline__ void load(const Ctx& c, int r, int Reff, float4& v, float& aux, bool& ok) const {
     ok = c.ok && r < Reff;
-    v = ldz(ok, p + (size_t)r * ld + c.i, p + (size_t)min(r, Reff - 1) * ld + c.i);
+    v = ldz(ok, p + (size_t)r * ld + c.i);
     aux = 0.f;
   }
   SAST_DEFAULT_FINISH
@@ -1274,7 +1142,7 @@ struct LdRowsTG {  // gathered rows: row(r) = idx[r] (a dependent load per k-til
   __device__ __forceinline__ Ctx prep(int j, int, int NJ) const { return Ctx{j < NJ ? j : 0, j < NJ}; }
   __device__ __forceinline__ void load(const Ctx& c, int r, int Reff, float4& v, float& aux, bool& ok) const {
     ok = c.ok && r < Reff;
-    { const float* q = p + (size_t)idx[min(r, Reff - 1)] * ld + c.i; v = ldz(ok, q, q); }
+    v = ldz(ok, p + (size_t)idx[min(r, Reff - 1)] * ld + c.i);
     aux = 0.f;
   }
   SAST_DEFAULT_FINISH
@@ -1291,7 +1159,7 @@ struct LdRowsT2 {  // dual source along j (for d[W_x | W_h])
   __device__ __forceinline__ Ctx prep(int i, int Ieff) const { return prep(i, 0, Ieff); }   // as the A operand
   __device__ __forceinline__ void load(const Ctx& c, int r, int Reff, float4& v, float& aux, bool& ok) const {
     ok = c.ok && r < Reff;
-    v = ldz(ok, c.base + (size_t)r * c.ld, c.base + (size_t)min(r, Reff - 1) * c.ld);
+    v = ldz(ok, c.base + (size_t)r * c.ld);
     aux = 0.f;
   }
   SAST_DEFAULT_FINISH
@@ -1307,7 +1175,7 @@ struct LdWeightNT {
   }
   __device__ __forceinline__ void load(const Ctx& c, int r, int Reff, float4& v, float& aux, bool& ok) const {
     ok = c.ok && r < Reff;
-    v = ldz(ok, c.row + r, c.row + (ok ? r : 0));
+    v = ldz(ok, c.row + r);
     aux = 0.f;
   }
   SAST_DEFAULT_FINISH
@@ -1325,7 +1193,7 @@ struct LdWeightNT2 {
   }
   __device__ __forceinline__ void load(const Ctx& c, int r, int Reff, float4& v, float& aux, bool& ok) const {
     ok = c.ok && r < Reff;
-    v = ldz(ok, c.row + r, c.row + (ok ? r : 0));
+    v = ldz(ok, c.row + r);
     aux = 0.f;
   }
   SAST_DEFAULT_FINISH
@@ -1338,7 +1206,7 @@ struct LdWeightNN {
   __device__ __forceinline__ Ctx prep(int j, int, int NJ) const { return Ctx{w + (j < NJ ? j : 0), j < NJ}; }
   __device__ __forceinline__ void load(const Ctx& c, int r, int Reff, float4& v, float& aux, bool& ok) const {
     ok = c.ok && r < Reff;
-    v = ldz(ok, c.col + (size_t)r * ldw, c.col + (size_t)min(r, Reff - 1) * ldw);
+    v = ldz(ok, c.col + (size_t)r * ldw);
     aux = 0.f;
   }
   SAST_DEFAULT_FINISH
@@ -1353,7 +1221,7 @@ struct LdWeightNN2 {
     ok = c.ok && r < Reff;
     const int rr = min(r, Reff - 1);
     const float* row = rr < R1 ? w1 + (size_t)rr * ldw : w2 + (size_t)(rr - R1) * ldw;   // address select, not a branch
-    v = ldz(ok, row + c.j, row + c.j);
+    v = ldz(ok, row + c.j);
     aux = 0.f;
   }
   SAST_DEFAULT_FINISH
@@ -1367,11 +1235,11 @@ struct LdWeightNNS {
   __device__ __forceinline__ void load(const Ctx& c, int r, int Reff, float4& v, float& aux, bool& ok) const {
     const int rr = min(r, Reff - 1);
     ok = c.ok && r < Reff;
-    v = ldz(ok, c.col + (size_t)rr * ldw, c.col + (size_t)rr * ldw);
+    v = ldz(ok, c.col + (size_t)rr * ldw);
     aux = rscale[rr];
   }
-  __device__ __forceinline__ float4 finish(float4 v, float aux, bool ok) const {
-    return sel4(ok, make_float4(v.x * aux, v.y * aux, v.z * aux, v.w * aux));        // (zero page: v is already zero where !ok, aux is a clamped, finite load)
+  __device__ __forceinline__ float4 finish(float4 v, float aux, bool) const {
+    return make_float4(v.x * aux, v.y * aux, v.z * aux, v.w * aux);        // (zero page: v is already zero where !ok, aux is a clamped, finite load)
   }
 };
 
@@ -1410,7 +1278,7 @@ struct LdIm2col {
     const int iy = c.iy0 + kh, ix = c.ix0 + kw;
     const int cy = min(max(iy, 0), g.H - 1), cx = min(max(ix, 0), g.W - 1);
     ok = c.ok && r < Reff && (g.replicate || (cy == iy && cx == ix));
-    { const float* q = c.img + ((size_t)cy * g.W + cx) * g.ldx + ch; v = ldz(ok, q, q); }
+    v = ldz(ok, c.img + ((size_t)cy * g.W + cx) * g.ldx + ch);
     aux = 0.f;
   }
   SAST_DEFAULT_FINISH
@@ -1438,10 +1306,10 @@ struct LdIm2colQ8 {
     const int iy = c.iy0 + kh, ix = c.ix0 + kw;
     const int cy = min(max(iy, 0), g.H - 1), cx = min(max(ix, 0), g.W - 1);
     ok = c.ok && r < Reff && (g.replicate || (cy == iy && cx == ix));
-    { const unsigned char* q = c.img + ((size_t)cy * g.W + cx) * g.ldx + ch; v.x = ldz1(ok, q, q); }
+    v.x = ldz1(ok, c.img + ((size_t)cy * g.W + cx) * g.ldx + ch);
     aux = 0.f;
   }
-  __device__ __forceinline__ float4 finish(float4 v, float, bool ok) const { return sel4(ok, widen_u8x4(v.x)); }
+  __device__ __forceinline__ float4 finish(float4 v, float, bool) const { return widen_u8x4(v.x); }
 };
 struct LdIm2colTQ8 {
   static constexpr bool RC = false;
@@ -1460,10 +1328,10 @@ struct LdIm2colTQ8 {
     const int iy = oy * g.stride - g.pad + c.kh, ix = ox * g.stride - g.pad + c.kw;
     const int cy = min(max(iy, 0), g.H - 1), cx = min(max(ix, 0), g.W - 1);
     ok = c.ok && r < Reff && (g.replicate || (cy == iy && cx == ix));
-    { const unsigned char* q = x + ((size_t)(b * g.H + cy) * g.W + cx) * g.ldx + c.c; v.x = ldz1(ok, q, q); }
+    v.x = ldz1(ok, x + ((size_t)(b * g.H + cy) * g.W + cx) * g.ldx + c.c);
     aux = 0.f;
   }
-  __device__ __forceinline__ float4 finish(float4 v, float, bool ok) const { return sel4(ok, widen_u8x4(v.x)); }
+  __device__ __forceinline__ float4 finish(float4 v, float, bool) const { return widen_u8x4(v.x); }
 };
 // the same when the channel count is a multiple of the k-tile (every conv of the path except the stem, Cin = 20): a k-tile then lies
 // inside ONE tap, which is decoded from the wave-uniform tile base on the scalar unit -- per lane only the pixel clamp and the
@@ -1478,7 +1346,7 @@ struct LdIm2colU : LdIm2col {
     const int iy = c.iy0 + kh, ix = c.ix0 + kw;
     const int cy = min(max(iy, 0), g.H - 1), cx = min(max(ix, 0), g.W - 1);
     ok = c.ok && r0 < Reff && (g.replicate || (cy == iy && cx == ix));
-    { const float* q = c.img + ((size_t)cy * g.W + cx) * g.ldx + ch0 + off; v = ldz(ok, q, q); }
+    v = ldz(ok, c.img + ((size_t)cy * g.W + cx) * g.ldx + ch0 + off);
     aux = 0.f;
   }
 };
@@ -1500,7 +1368,7 @@ struct LdIm2colT {
     const int iy = oy * g.stride - g.pad + c.kh, ix = ox * g.stride - g.pad + c.kw;
     const int cy = min(max(iy, 0), g.H - 1), cx = min(max(ix, 0), g.W - 1);
     ok = c.ok && r < Reff && (g.replicate || (cy == iy && cx == ix));
-    { const float* q = x + ((size_t)(b * g.H + cy) * g.W + cx) * g.ldx + c.c; v = ldz(ok, q, q); }
+    v = ldz(ok, x + ((size_t)(b * g.H + cy) * g.W + cx) * g.ldx + c.c);
     aux = 0.f;
   }
   SAST_DEFAULT_FINISH
@@ -1551,7 +1419,7 @@ struct LdConvDx {
     int oy, ox;
     const bool vy = src(c.iy, kh, g.Ho, oy), vx = src(c.ix, kw, g.Wo, ox);
     ok = c.ok && r < Reff && vy && vx;
-    { const float* q = c.img + ((size_t)oy * g.Wo + ox) * lddy + co; v = ldz(ok, q, q); }
+    v = ldz(ok, c.img + ((size_t)oy * g.Wo + ox) * lddy + co);
     aux = 0.f;
   }
   SAST_DEFAULT_FINISH
@@ -1565,7 +1433,7 @@ struct LdConvDxU : LdConvDx {   // Cout a multiple of the k-tile: uniform tap, s
     int oy, ox;
     const bool vy = src(c.iy, kh, g.Ho, oy), vx = src(c.ix, kw, g.Wo, ox);
     ok = c.ok && r0 < Reff && vy && vx;
-    { const float* q = c.img + ((size_t)oy * g.Wo + ox) * lddy + co0 + off; v = ldz(ok, q, q); }
+    v = ldz(ok, c.img + ((size_t)oy * g.Wo + ox) * lddy + co0 + off);
     aux = 0.f;
   }
 };
@@ -1579,7 +1447,7 @@ struct LdWeightConvDx {
     const int rr = min(r, Reff - 1);
     const int tap = (int)__umulhi((unsigned)rr, cout_mul), co = rr - tap * Cout;
     ok = c.ok && r < Reff;
-    { const float* q = c.col + ((size_t)co * taps + tap) * Cin; v = ldz(ok, q, q); }
+    v = ldz(ok, c.col + ((size_t)co * taps + tap) * Cin);
     aux = 0.f;
   }
   SAST_DEFAULT_FINISH
@@ -1591,7 +1459,7 @@ struct LdWeightConvDxU : LdWeightConvDx {   // Cout a multiple of the k-tile: th
     const int rc = min(r0, Reff - bk);
     const int tap = (int)__umulhi((unsigned)rc, cout_mul), co0 = rc - tap * Cout;
     ok = c.ok && r0 < Reff;
-    { const float* q = c.col + ((size_t)co0 * taps + tap) * Cin + (size_t)off * (taps * Cin); v = ldz(ok, q, q); }
+    v = ldz(ok, c.col + ((size_t)co0 * taps + tap) * Cin + (size_t)off * (taps * Cin));
     aux = 0.f;
   }
 };
@@ -1606,7 +1474,7 @@ struct LdWeightConvDx2 {
     const int tap = (int)__umulhi((unsigned)rr, cout_mul), co = rr - tap * Cout;
     ok = c.ok && r < Reff;
     const float* row = co < C1 ? w0 + ((size_t)co * taps + tap) * Cin : w1 + ((size_t)(co - C1) * taps + tap) * Cin;   // address select
-    v = ldz(ok, row + c.j, row + c.j);
+    v = ldz(ok, row + c.j);
     aux = 0.f;
   }
   SAST_DEFAULT_FINISH
@@ -1661,7 +1529,7 @@ struct LdConvDxP {
     int oy, ox;
     const bool vy = src(c.iy, kh, g.Ho, oy), vx = src(c.ix, kw, g.Wo, ox);
     ok = c.ok && r < Reff && vy && vx;
-    { const float* q = c.img + ((size_t)oy * g.Wo + ox) * lddy + co; v = ldz(ok, q, q); }
+    v = ldz(ok, c.img + ((size_t)oy * g.Wo + ox) * lddy + co);
     aux = 0.f;
   }
   SAST_DEFAULT_FINISH
@@ -1684,7 +1552,7 @@ struct LdWeightConvDxP {
     const int kh = (c.kh >> (4 * slot)) & 15, kw = (c.kw >> (4 * slot)) & 15;
     const bool empty = kh == 15 || kw == 15;
     ok = c.ok && r < Reff && !empty;
-    { const float* q = c.col + ((size_t)co * taps + (empty ? 0 : kh * KW + kw)) * Cin; v = ldz(ok, q, q); }
+    v = ldz(ok, c.col + ((size_t)co * taps + (empty ? 0 : kh * KW + kw)) * Cin);
     aux = 0.f;
   }
   SAST_DEFAULT_FINISH

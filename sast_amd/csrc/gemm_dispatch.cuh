@@ -21,19 +21,10 @@ bool dw_defer_on();
 bool dw_defer_rows_ok(long R);
 void dw_defer_push(std::function<int(hipStream_t, bool)> job);     // job(stream, run): run == false drops the entry (sast_dw_discard)
 
-// the plain-GEMM tiles gemm_auto / the dX job of a paired launch choose from (overridable for A/B builds)
-#ifndef SAST_TILE_THIN
-#define SAST_TILE_THIN TileThinK4
-#endif
-#ifndef SAST_TILE_K2
-#define SAST_TILE_K2 TileSmallK2
-#endif
-#ifndef SAST_TILE_K1
-#define SAST_TILE_K1 TileSmall
-#endif
-using TileAutoThin = SAST_TILE_THIN;
-using TileAutoK2 = SAST_TILE_K2;
-using TileAutoK1 = SAST_TILE_K1;
+// the plain-GEMM tiles gemm_auto / the dX job of a paired launch choose from
+using TileAutoThin = TileThinK4;
+using TileAutoK2 = TileSmallK2;
+using TileAutoK1 = TileSmall;
 
 inline bool gemm_pair_enabled() { return SAST_KNOB("SAST_GEMM_PAIR", 1) != 0; }
 inline int pair_tn_blocks() { return SAST_KNOB("SAST_TN_BLOCKS", 768); }

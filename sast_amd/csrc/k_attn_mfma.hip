@@ -447,7 +447,6 @@ __global__ __launch_bounds__(64 * NTMAX * (SPLIT ? 2 : 1), SPLIT ? (NTMAX == 2 ?
                                                                    LsFinish f0, LsFinish f1, int fC) {
   SAST_KERNARG_WARM_SELF(attn_bwd_mfma_kernel<NTMAX, SPLIT>);
   __shared__ __attribute__((aligned(16))) char sm[4 * 3 * 32 * NTMAX * 64 + 2 * 32 * NTMAX * 4];
-  SAST_CHAIN_PRIO();
   if (blockIdx.x >= W) {   // side workgroups: the LayerScale'd fc2 / proj gradient finish of the same MS-WSA layer (independent work
     if (blockIdx.y == 0) {  // that used to be a launch of its own), one wave per output channel
       const int row = (blockIdx.x - W) * (NTMAX * (SPLIT ? 2 : 1)) + (threadIdx.x >> 6);

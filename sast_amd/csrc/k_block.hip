@@ -85,8 +85,9 @@ struct EpGluT {  // ops.py:136-137: value = first half, gate = second half
   __device__ __forceinline__ Aux pre(int, int) const { return Aux{}; }
   __device__ __forceinline__ void post(int m, int j, const float (&v)[2], const Col& k, const Aux&) const {
     const float u = v[0] + k.bu, g = v[1] + k.bg;
-    st_saved(ug + (size_t)m * 2 * inner + j, u);             // [u|g]: read by the backward only
-    st_saved(ug + (size_t)m * 2 * inner + inner + j, g);
+    float* ugm = ug + (size_t)m * 2 * inner;                 // [u|g]: read by the backward only
+    ugm[j] = u;
+    (ugm + inner)[j] = g;
     if constexpr (ANY) h[(size_t)m * inner + j] = (u * glu_act(g, act, k.a)) * (drop ? drop[(size_t)m * inner + j] : 1.f);
     else h[(size_t)m * inner + j] = u * gelu_erf(g);
   }
@@ -137,7 +138,7 @@ struct EpLstm {  // rnn.py:57-67
     c1[(size_t)m * C + j] = c;
     h1[(size_t)m * C + j] = o * tanh_hw(c);
     float* gp = gates + (size_t)m * 4 * C + j;
-    st_saved(gp, f); st_saved(gp + C, i); st_saved(gp + 2 * C, o); st_saved(gp + 3 * C, g);     // the gates: read by the backward only
+    gp[0] = f; gp[C] = i; gp[2 * C] = o; gp[3 * C] = g;     // the gates: read by the backward only
   }
 };
 // the same from a ZERO cell state (c0 == NULL): c = f * 0 + i * (g * d) does not depend on the forget gate, so the GEMM runs over the three
@@ -155,7 +156,7 @@ struct EpLstm3 {
     c1[(size_t)m * C + j] = c;
     h1[(size_t)m * C + j] = o * tanh_hw(c);
     float* gp = gates + (size_t)m * 4 * C + j;
-    st_saved(gp + C, i); st_saved(gp + 2 * C, o); st_saved(gp + 3 * C, g);
+    gp[C] = i; gp[2 * C] = o; gp[3 * C] = g;
   }
 };
 // zero cell state + SAST_LSTM_SKIP_DEAD_GATE (default 1): forward and backward run on the three live gates.  The knob must not change

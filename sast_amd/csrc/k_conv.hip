@@ -35,20 +35,10 @@ __global__ __launch_bounds__(256) void bn_silu_apply_kernel(BnFwdJob j0, BnFwdJo
   const int ldy = jb.ldy; const float momentum = jb.momentum, eps = jb.eps;
   extern __shared__ float bn_sm[];   // [2C]: mean, rstd
   // Round 6: the statistics prologue issues all loads of a channel before the first is used (ISA before: two dependent rounds behind a
-  // branch), -0.25 % of the step.  Requesting the first ELEMENT of every thread in front of the prologue as well (-DSAST_BN_EARLY_LOADS=1)
-  // measured the same (profiles/r06_v): off.
+  // branch), -0.25 % of the step.  (Requesting every thread's first element in front of the prologue as well measured the same: DESIGN
+  // "Retired compile-time switches".)
   const int c4 = C / 4;
   const size_t e0 = (size_t)blockIdx.x * 256 * iters + threadIdx.x;
-#ifndef SAST_BN_EARLY_LOADS
-#define SAST_BN_EARLY_LOADS 0
-#endif
-  float4 v0 = zero4(), g0 = zero4(), b0 = zero4();
-  size_t m0 = 0; int cc0 = 0;
-  if (SAST_BN_EARLY_LOADS) {
-    const size_t ec = e0 < n4 ? e0 : 0;                                  // clamped: a thread past the end reads element 0 and stores nothing
-    m0 = fast_div((int)ec, c4, c4_mul); cc0 = (int)(ec - m0 * c4) * 4;
-    v0 = ld4(x + m0 * C + cc0); g0 = ld4(gamma + cc0); b0 = ld4(beta + cc0);
-  }
   for (int c = threadIdx.x; c < C; c += 256) {
     float mu, rs;
     if (training) {
@@ -62,11 +52,7 @@ __global__ __launch_bounds__(256) void bn_silu_apply_kernel(BnFwdJob j0, BnFwdJo
       double var = q * invM - mean * mean;
       if (var < 0) var = 0;
       mu = (float)mean;
-#if SAST_FAST_DIV
       rs = rsqrt_hw((float)var + eps);
-#else
-      rs = (float)(1.0 / sqrt(var + (double)eps));
-#endif
       if (blockIdx.x == 0 && run_mean) {
         const double unb = var * unbias;
         run_mean[c] = (1.f - momentum) * run_mean[c] + momentum * (float)mean;
@@ -83,9 +69,9 @@ __global__ __launch_bounds__(256) void bn_silu_apply_kernel(BnFwdJob j0, BnFwdJo
   for (int it = 0; it < iters; ++it) {
     const size_t e = e0 + (size_t)it * 256;
     if (e >= n4) return;
-    size_t m; int c; float4 v, g, b;
-    if (SAST_BN_EARLY_LOADS && it == 0) { m = m0; c = cc0; v = v0; g = g0; b = b0; }
-    else { m = fast_div((int)e, c4, c4_mul); c = (int)(e - m * c4) * 4; v = ld4(x + m * C + c); g = ld4(gamma + c); b = ld4(beta + c); }
+    const size_t m = fast_div((int)e, c4, c4_mul);
+    const int c = (int)(e - m * c4) * 4;
+    const float4 v = ld4(x + m * C + c), g = ld4(gamma + c), b = ld4(beta + c);
     const float4 mu = *(const float4*)(bn_sm + c), rs = *(const float4*)(bn_sm + C + c);
     float4 z = make_float4((v.x - mu.x) * rs.x * g.x + b.x, (v.y - mu.y) * rs.y * g.y + b.y, (v.z - mu.z) * rs.z * g.z + b.z,
                            (v.w - mu.w) * rs.w * g.w + b.w);
@@ -229,17 +215,10 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(BnBwdJob j0, BnBwdJob
   const float* __restrict__ sums = jb.sums; float* __restrict__ dconv = jb.dconv;
   float* __restrict__ dgamma = jb.dgamma; float* __restrict__ dbeta = jb.dbeta;
   extern __shared__ float bsm[];   // [6][C]: mean, rstd, gamma, beta, mean(dz), mean(dz*xhat)
-  // (round 6, as in bn_silu_apply_kernel: the first element's loads are requested before the statistics prologue, and all 12 loads of a
-  // channel of the prologue are issued before the first is used -- the block-0 publication of the affine gradients sits behind them)
+  // (round 6, as in bn_silu_apply_kernel: all 12 loads of a channel of the prologue are issued before the first is used -- the block-0
+  // publication of the affine gradients sits behind them)
   const int c4 = C / 4;
   const size_t e0 = (size_t)blockIdx.x * 256 * iters + threadIdx.x;
-  float4 v0 = zero4(), d0 = zero4();
-  size_t m0 = 0; int cc0 = 0;
-  if (SAST_BN_EARLY_LOADS) {
-    const size_t ec = e0 < n4 ? e0 : 0;
-    m0 = fast_div((int)ec, c4, c4_mul); cc0 = (int)(ec - m0 * c4) * 4;
-    v0 = ld4(x + m0 * C + cc0); d0 = bn_ld_dy(dy, jb.dy2, m0 * lddy + cc0);
-  }
   for (int c = threadIdx.x; c < C; c += 256) {
     float a1[BN_STAT_COPIES], a2[BN_STAT_COPIES];
 #pragma unroll
@@ -256,9 +235,9 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(BnBwdJob j0, BnBwdJob
   for (int it = 0; it < iters; ++it) {
     const size_t e4 = e0 + (size_t)it * 256;
     if (e4 >= n4) return;
-    size_t m; int c; float4 v, d;
-    if (SAST_BN_EARLY_LOADS && it == 0) { m = m0; c = cc0; v = v0; d = d0; }
-    else { m = fast_div((int)e4, c4, c4_mul); c = (int)(e4 - m * c4) * 4; v = ld4(x + m * C + c); d = bn_ld_dy(dy, jb.dy2, m * lddy + c); }
+    const size_t m = fast_div((int)e4, c4, c4_mul);
+    const int c = (int)(e4 - m * c4) * 4;
+    const float4 v = ld4(x + m * C + c), d = bn_ld_dy(dy, jb.dy2, m * lddy + c);
     float out[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {

@@ -461,10 +461,7 @@ __device__ __forceinline__ void ln_row_bwd(const float4 (&x)[VPL], float4 (&dy)[
 
 // block-level reduction of per-thread channel partials into global accumulators (atomicAdd)
 // threads per workgroup of the backward row kernels (the ones that end in per-channel atomics): few workgroups, many waves each
-#ifndef SAST_ROWB_THREADS
-#define SAST_ROWB_THREADS 1024
-#endif
-constexpr int ROWB = SAST_ROWB_THREADS;
+constexpr int ROWB = 1024;
 
 template <int GL, int VPL>
 __device__ __forceinline__ void flush_channel_partials(float* red /* [ROWB/GL][C] in LDS */, const float4 (&p)[VPL],

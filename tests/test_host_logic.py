@@ -35,6 +35,25 @@ def test_product_never_imports_oracle():
                 assert "sast_oracle" not in txt, os.path.join(d, f)
 
 
+def test_kernel_sources_carry_no_parked_compile_time_switches():
+    """the only SAST_* names a preprocessor conditional under csrc/ may test are the arithmetic classes (builds something uses) and the
+    timeline instrumentation (tools/*timeline*.py, tools/gemm_kloop_cycles.py); see DESIGN "Retired compile-time switches" """
+    kept = {"SAST_MFMA_SPLIT3", "SAST_MFMA_BF16",
+            "SAST_TL", "SAST_TL_ENABLE", "SAST_TL_JOB", "SAST_TLF", "SAST_TLF_ENABLE", "SAST_FUSED_TL"}
+    csrc = os.path.join(ROOT, "sast_amd", "csrc")
+    seen = {}
+    for f in sorted(os.listdir(csrc)):
+        if not f.endswith((".hip", ".cuh", ".h", ".inc")):
+            continue
+        for n, line in enumerate(open(os.path.join(csrc, f)), 1):
+            if re.match(r"\s*#\s*(if|ifdef|ifndef|elif)\b", line):
+                for name in re.findall(r"\bSAST_[A-Z0-9_]+\b", line):
+                    seen.setdefault(name, f"{f}:{n}")
+    parked = {k: v for k, v in seen.items() if k not in kept}
+    assert not parked, (f"compile-time switch(es) {parked} in the kernel sources: experiments are measured in a variant build and then "
+                        "either adopted as plain code or recorded in DESIGN, not parked behind a switch")
+
+
 def test_hot_path_fails_loudly_without_gpu():
     from sast_amd import functional as SF
     with pytest.raises(RuntimeError, match="no CPU fallback"):

@@ -1,6 +1,5 @@
 """Round 6: what do the saved-activation stores cost the one-kernel MS-WSA forward?  Times sast_mswsa_fwd (fused form) on the 1Mpx stage-1
-shape in its inference form (no saves) and its training form (S / QKV / O / Y / [u|g] / h / lse written), replayed from a hipGraph.
-Run with SAST_LIB_PATH=ab/nowait.so for the timing-only build whose weight ring does not wait (wrong results)."""
+shape in its inference form (no saves) and its training form (S / QKV / O / Y / [u|g] / h / lse written), replayed from a hipGraph."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

@@ -1,6 +1,6 @@
 """tile shapes of the GEMM template against each other on the model's shapes: y[M,N] = x[M,K] W[N,K]^T + b through the micro-benchmark entry
 point (csrc/k_test.hip), checked against fp64, HIP-event time per launch.  SAST_TOOLS_LIB_PATH selects a variant build of the tools library
-(-DSAST_MFMA_BF16=1, -DSAST_MFMA_SPLIT3=0, -DSAST_PRESPLIT_RC=0 ...)."""
+(-DSAST_MFMA_BF16=1, -DSAST_MFMA_SPLIT3=0, -DSAST_TLF_ENABLE)."""
 import ctypes as C, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
