@@ -1,7 +1,7 @@
 """The case table of the conv operator sweep (tests/test_conv_operators.py), the inputs of every case and its CPU reference evaluation.
 
-Shared by the GPU test and by tests/golden/make_conv_bounds.py (which evaluates every case in float32 against float64 on the CPU), so
-that both see the same cases, the same numbers and the same quantity names.  CPU only: nothing here imports the library.
+Shared by the GPU test and by the bounds generator (tests/operator_sweep.py, which evaluates every case in float32 against float64 on the
+CPU), so that both see the same cases, the same numbers and the same quantity names.  CPU only: nothing here imports the library.
 
 A case is a dict with an "id", an "op" (the operator family its error statistics are pooled over) and the shape parameters.
 `make_inputs(case)` -> fp32 (uint8 for the stem cases) CPU tensors drawn from a generator seeded by the id.
@@ -16,14 +16,11 @@ until fp32 itself misses the forward bar.
 """
 import math
 import re
-import zlib
 
 import torch
 
 import conv_reference as R
-
-FWD_ATOL = 3e-5       # the project's bars
-GRAD_RTOL = 3e-4
+import operator_sweep as SW
 
 
 def conv_hw(H, W, k, s):
@@ -212,10 +209,6 @@ def bounds_id(case):
 
 
 # ------------------------------------------------------------------------------------------------ inputs
-def _gen(cid):
-    return torch.Generator().manual_seed(zlib.crc32(cid.encode()))
-
-
 def _unit_params(g, cin, cout, k, dw=False, prefix=""):
     fan = k * k * (1 if dw else cin)
     return {prefix + "w": torch.randn(cout, 1 if dw else cin, k, k, generator=g) / math.sqrt(fan),
@@ -223,12 +216,8 @@ def _unit_params(g, cin, cout, k, dw=False, prefix=""):
             prefix + "run_mean": 0.1 * torch.randn(cout, generator=g), prefix + "run_var": 0.5 + torch.rand(cout, generator=g)}
 
 
-def _up(g, *shape):
-    return torch.randn(*shape, generator=g) + 0.5
-
-
 def make_inputs(case):
-    g = _gen(bounds_id(case))
+    g = SW.gen(bounds_id(case))
     op = case["op"]
     B, H, W = case["B"], case["H"], case["W"]
     if op in ("cbs", "cbs_dw"):
@@ -238,9 +227,9 @@ def make_inputs(case):
         if cin1:
             inp["x2"] = torch.randn(B, H, W, cin - cin1, generator=g)
         inp.update(_unit_params(g, cin, cout, k, case["dw"]))
-        inp["g"] = _up(g, B, Ho, Wo, cout)
+        inp["g"] = SW.up(g, B, Ho, Wo, cout)
         if case["two"]:
-            inp["g2"] = _up(g, B, Ho, Wo, cout)
+            inp["g2"] = SW.up(g, B, Ho, Wo, cout)
         return inp
     if op == "chain":
         inp = {"x": torch.randn(B, H, W, case["cin"], generator=g)}
@@ -255,7 +244,7 @@ def make_inputs(case):
             c_prev = c
         if case["join"]:
             assert all(s == 1 for _k, s, _c in case["units"])
-        inp["g"] = _up(g, B, hw[0], hw[1], c_prev)
+        inp["g"] = SW.up(g, B, hw[0], hw[1], c_prev)
         return inp
     if op == "cbs2":
         cin, cout, cin1 = case["cin"], case["cout"], case["cin1"]
@@ -264,7 +253,7 @@ def make_inputs(case):
             inp["x2"] = torch.randn(B, H, W, cin - cin1, generator=g)
         inp.update(_unit_params(g, cin, cout, 1, prefix="u0."))
         inp.update(_unit_params(g, cin, cout, 1, prefix="u1."))
-        inp["g0"], inp["g1"] = _up(g, B, H, W, cout), _up(g, B, H, W, cout)
+        inp["g0"], inp["g1"] = SW.up(g, B, H, W, cout), SW.up(g, B, H, W, cout)
         return inp
     if op == "down":
         f, cin, cout = case["f"], case["cin"], case["cout"]
@@ -279,20 +268,20 @@ def make_inputs(case):
                "ln_w": 1 + 0.1 * torch.randn(cout, generator=g), "ln_b": 0.1 * torch.randn(cout, generator=g)}
         if case["pe"]:
             inp["pe"] = torch.randn(Ho * Wo, cout, generator=g)
-        inp["g"] = _up(g, B, Ho, Wo, cout)
+        inp["g"] = SW.up(g, B, Ho, Wo, cout)
         return inp
     if op == "dwconv":
         k, c, cw = case["k"], case["c"], case["cw"]
         inp = {"x": torch.randn(B, H, W, c, generator=g), "w": torch.randn(cw, 1, k, k, generator=g) / k}
         if case["bias"]:
             inp["b"] = 0.1 * torch.randn(cw, generator=g)
-        inp["g"] = _up(g, B, H, W, c)
+        inp["g"] = SW.up(g, B, H, W, c)
         return inp
     if op in ("upcat", "cat2"):
         c1, c2 = case["c1"], case["c2"]
         up = 2 if op == "upcat" else 1
         return {"a": torch.randn(B, H, W, c1, generator=g), "b": torch.randn(B, up * H, up * W, c2, generator=g),
-                "g": _up(g, B, up * H, up * W, c1 + c2)}
+                "g": SW.up(g, B, up * H, up * W, c1 + c2)}
     raise KeyError(op)
 
 
@@ -301,26 +290,11 @@ NO_GRAD = ("g", "g0", "g1", "g2", "run_mean", "run_var", "pe")
 
 
 def _leaves(inp, dtype, grads=True):
-    out = {}
-    for k, v in inp.items():
-        if v.dtype == torch.uint8:
-            out[k] = v
-            continue
-        t = v.to(dtype).clone()
-        if grads and k.split(".")[-1] not in NO_GRAD:
-            t.requires_grad_(True)
-        out[k] = t
-    return out
+    return SW.leaves(inp, dtype, NO_GRAD, grads)
 
 
 def _unit(p, prefix=""):
     return tuple(p[prefix + n] for n in ("w", "bn_w", "bn_b", "run_mean", "run_var"))
-
-
-def _grads(out, p, mode_prefix):
-    for k, v in p.items():
-        if v.requires_grad:
-            out[f"{mode_prefix}grad:{k}"] = v.grad if v.grad is not None else torch.zeros_like(v)
 
 
 def reference(case, inp, dtype):
@@ -336,7 +310,7 @@ def reference(case, inp, dtype):
             if mode != "infer":
                 loss = (y * p["g"]).sum() + ((y * p["g2"]).sum() if case["two"] else 0)
                 loss.backward()
-                _grads(out, p, mode + "/")
+                SW.grads(out, p, mode + "/")
         return out
     if op == "chain":
         p = _leaves(inp, dtype)
@@ -355,7 +329,7 @@ def reference(case, inp, dtype):
         for i, (m, v) in enumerate(stats):
             out[f"train/stat:u{i}.run_mean"], out[f"train/stat:u{i}.run_var"] = m, v
         (y * p["g"]).sum().backward()
-        _grads(out, p, "train/")
+        SW.grads(out, p, "train/")
         return out
     if op == "cbs2":
         p = _leaves(inp, dtype)
@@ -367,42 +341,30 @@ def reference(case, inp, dtype):
             out[f"train/stat:u{i}.run_mean"], out[f"train/stat:u{i}.run_var"] = m, v
             loss = loss + (y * p[f"g{i}"]).sum()
         loss.backward()
-        _grads(out, p, "train/")
+        SW.grads(out, p, "train/")
         return out
     if op == "down":
         p = _leaves(inp, dtype)
         y = R.downsample_ln(p["x"], p["w"], p["ln_w"], p["ln_b"], p.get("pe"), case["f"])
         out["train/out:y"] = y.detach()
         (y * p["g"]).sum().backward()
-        _grads(out, p, "train/")
+        SW.grads(out, p, "train/")
         return out
     if op == "dwconv":
         p = _leaves(inp, dtype)
         y = R.dwconv(p["x"], p["w"], p.get("b"), case["c0"])
         out["train/out:y"] = y.detach()
         (y * p["g"]).sum().backward()
-        _grads(out, p, "train/")
+        SW.grads(out, p, "train/")
         return out
     if op in ("upcat", "cat2"):
         p = _leaves(inp, dtype)
         y = (R.upsample_cat if op == "upcat" else R.cat2)(p["a"], p["b"])
         out["train/out:y"] = y.detach()
         (y * p["g"]).sum().backward()
-        _grads(out, p, "train/")
+        SW.grads(out, p, "train/")
         return out
     raise KeyError(op)
-
-
-def measure(quantity, got, ref):
-    """(error figure the bounds are stated in, absolute max error, scale): outputs absolute (scale 1), everything else relative to the
-    reference tensor's max-norm"""
-    got, ref = got.detach().double().cpu(), ref.detach().double().cpu()
-    assert got.shape == ref.shape, (quantity, tuple(got.shape), tuple(ref.shape))
-    err = float((got - ref).abs().max()) if ref.numel() else 0.0
-    if "out:" in quantity:
-        return err, err, 1.0
-    scale = float(ref.abs().max()) + 1e-30
-    return err / scale, err, scale
 
 
 def pool_key(quantity):
@@ -410,5 +372,6 @@ def pool_key(quantity):
     return re.sub(r"u\d\.", "u.", quantity)
 
 
-def project_bar(quantity):
-    return FWD_ATOL if "out:" in quantity else GRAD_RTOL
+BOUNDS_CASES = [c for c in ALL_CASES if bounds_id(c) == c["id"]]      # the cases with an entry of their own in the bounds file
+float_quantities = sorted
+DISCRETE = ()

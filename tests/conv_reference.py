@@ -2,7 +2,7 @@
 downsample_ln, dwconv, upsample_cat, cat2).
 
 Every function computes in the dtype of the tensors it is given: float64 for the reference the HIP kernels are compared with
-(tests/test_conv_operators.py), float32 for the error of that very expression in fp32 (tests/golden/make_conv_bounds.py).  Tensors are
+(tests/test_conv_operators.py), float32 for the error of that very expression in fp32 (tests/golden/make_operator_bounds.py).  Tensors are
 NHWC like the library's ("image layout" rows [B*H*W, C]); weights have their logical nn.Conv2d shape [Cout, Cin / groups, k, k].
 Gradients come from autograd through these expressions.  Nothing here knows about the library or the oracle; tests/test_conv_reference.py
 pins it against torch.nn modules.

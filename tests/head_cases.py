@@ -1,6 +1,6 @@
 """The case tables of the YOLOX head sweep (tests/test_head_operators.py), the inputs of every case and its CPU reference.
 
-Shared by the GPU test, by tests/golden/make_head_bounds.py (every case in float32 against float64 on the CPU) and by
+Shared by the GPU test, by the bounds generator (tests/operator_sweep.py: every case in float32 against float64 on the CPU) and by
 tests/test_head_reference.py.  CPU only: nothing here imports the library.
 
 A case is a dict with an "id" and an "op" (the family its error statistics are pooled over).  `make_inputs(case)` -> fp32 CPU tensors
@@ -30,7 +30,6 @@ import numpy as np
 import torch
 
 import head_reference as R
-from conv_cases import FWD_ATOL, GRAD_RTOL, measure, project_bar  # noqa: F401  (re-exported: one definition for all suites)
 
 BASE_LEVELS = ((5, 7, 8.0), (3, 4, 16.0), (2, 2, 32.0))
 COST_GAP, DYNK_GAP, CENTRE_GAP, L1_GAP, NMS_IOU_GAP, NMS_SCORE_GAP = 1e-3, 1e-3, 1e-3, 1e-3, 1e-5, 1e-6
@@ -112,8 +111,13 @@ NMS_CASES = [
 
 ALL_CASES = PRED_CASES + LOSS_CASES + E2E_CASES + NMS_CASES
 FLOAT_CASES = PRED_CASES + LOSS_CASES + E2E_CASES          # the cases with float quantities: they have an entry in the bounds file
+BOUNDS_CASES = FLOAT_CASES
 BY_ID = {c["id"]: c for c in ALL_CASES}
 assert len(BY_ID) == len(ALL_CASES), "duplicate case ids"
+
+
+def bounds_id(case):
+    return case["id"]
 
 
 # ------------------------------------------------------------------------------------------------ inputs
@@ -437,3 +441,4 @@ def check_conditions(case, inp, ref=None):
 
 
 EXACT = ("exact:fg", "exact:matched_gt")
+DISCRETE = EXACT

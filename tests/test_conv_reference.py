@@ -1,14 +1,12 @@
 """CPU tests of the conv operator sweep's own instruments (no GPU): the float64 reference of tests/conv_reference.py against torch.nn
 modules, the case table and its committed fp32 bounds, and the size rule of the downsampling conv (functional.downsample_out_hw)."""
-import json
-import os
-
 import pytest
 import torch
 import torch.nn as nn
 
 import conv_cases as CC
 import conv_reference as R
+import operator_sweep as SW
 
 TOL = 1e-12
 
@@ -215,9 +213,8 @@ def test_case_table_covers_the_classes_the_sweep_is_about():
     assert {c["k"] for c in CC.DWCONV_CASES} == {1, 3, 5, 7} and {c["c"] for c in CC.DWCONV_CASES} >= {4, 48, 64, 256}
 
 
-def test_committed_bounds_hold_every_case_and_stay_inside_the_project_bars(golden_dir):
-    with open(os.path.join(golden_dir, "conv_operator_bounds.json")) as f:
-        doc = json.load(f)
+def test_committed_bounds_hold_every_case_and_stay_inside_the_project_bars():
+    doc = SW.load_bounds("conv")
     want = {CC.bounds_id(c) for c in CC.ALL_CASES}
     assert set(doc["cases"]) == want
     for cid in sorted(want)[::9]:        # a sample is re-evaluated: same quantities, figures of the same size (thread counts move fp32 sums)
@@ -226,9 +223,9 @@ def test_committed_bounds_hold_every_case_and_stay_inside_the_project_bars(golde
         r64, r32 = CC.reference(case, inp, torch.float64), CC.reference(case, inp, torch.float32)
         assert set(r64) == set(doc["cases"][cid]), cid
         for q in r64:
-            e = CC.measure(q, r32[q], r64[q])[0]
+            e = SW.measure(q, r32[q], r64[q])[0]
             floor = doc["operators"][case["op"]][CC.pool_key(q)]["median"]
             assert e <= 8 * max(doc["cases"][cid][q], floor) + 1e-30, (cid, q, e, doc["cases"][cid][q])
     for op, qs in doc["operators"].items():
         for q, v in qs.items():
-            assert v["median"] <= v["worst"] < CC.project_bar(q) / 2, (op, q, v)
+            assert v["median"] <= v["worst"] < SW.project_bar(q) / 2, (op, q, v)

@@ -16,35 +16,19 @@ import ctypes as C
 import pytest
 import torch
 
+import operator_sweep as SW
+from operator_sweep import FACTOR, SAST_EINVAL, dev, restore_knobs  # noqa: F401  (dev, restore_knobs: fixtures)
+
 pytestmark = pytest.mark.gpu
 
-SAST_EINVAL = -22
 KNOB = "SAST_LSTM_SKIP_DEAD_GATE"
 DET = "SAST_TN_BLOCKS_PAIRED"
 
 
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    return torch.device("cuda:0")
-
-
 @pytest.fixture()
 def knobs(monkeypatch):
-    """set(**env) changes SAST_* knobs for the next launches; everything is restored (and re-read by the library) afterwards"""
-    from sast_amd import _lib as SL
-
-    def set_(**env):
-        for k, v in env.items():
-            if v is None:
-                monkeypatch.delenv(k, raising=False)
-            else:
-                monkeypatch.setenv(k, str(v))
-        SL.reload_knobs()
-
-    yield set_
-    monkeypatch.undo()
-    SL.reload_knobs()
+    """knobs(**env) changes SAST_* knobs for the next launches (None: unset); `restore_knobs` puts everything back afterwards"""
+    return lambda **env: SW.set_knobs(monkeypatch, env)
 
 
 def _lstm_inputs(dev, C_, rows, h0_given, drop_given, seed=0):
@@ -188,7 +172,6 @@ def test_lstm_atomic_spread_figures(dev, knobs):
 # with float atomics: made deterministic (SAST_TN_BLOCKS=1: one workgroup per output tile) it must be equal too.
 STEM_KNOB = "SAST_STEM_EXACT_BF16"
 STEM_DET = "SAST_TN_BLOCKS"
-FACTOR = 8.0        # the operator-level factor of tests/test_conv_operators.py on the fp32 error of the reference expression
 
 
 def _stem_params(dev, cin=20, cout=64, f=4, seed=5):
@@ -315,16 +298,13 @@ def test_stem_three_term_body_is_the_one_that_runs(dev, knobs):
 
 
 @pytest.mark.parametrize("kind", ["one_257_i32", "fractional_f32"])
-def test_stem_mixed_input_falls_back_and_matches_fp64(dev, knobs, kind, golden_dir):
+def test_stem_mixed_input_falls_back_and_matches_fp64(dev, knobs, kind):
     """one value that is not a bf16 -> the word is non-zero -> six terms; against the float64 reference of tests/conv_reference.py within
     the bounds tests/golden/conv_operator_bounds.json holds for the stem's shape class (factor 4, overlap, 20 -> 64 channels)"""
-    import json
-    import os
     import conv_cases as CC
     import conv_reference as R
     from sast_amd import functional as SF
-    with open(os.path.join(golden_dir, "conv_operator_bounds.json")) as f:
-        bounds = json.load(f)
+    bounds = SW.load_bounds("conv")
     x = _events(kind, (2, 20, 64, 96)).to(dev)
     P = _stem_params(dev)
     knobs(**{STEM_KNOB: 1})
@@ -344,8 +324,8 @@ def test_stem_mixed_input_falls_back_and_matches_fp64(dev, knobs, kind, golden_d
     ref = {"train/out:y": yr.detach(), "train/grad:w": w.grad, "train/grad:ln_w": lw.grad, "train/grad:ln_b": lb.grad}
     cid = "down-f4o-2x24x40-20to64-pe"
     for q in sorted(ref):
-        rel, err, scale = CC.measure(q, got[q], ref[q])
-        tol = min(CC.project_bar(q), FACTOR * max(bounds["cases"][cid][q], bounds["operators"]["down"][CC.pool_key(q)]["median"]))
+        rel, err, scale = SW.measure(q, got[q], ref[q])
+        tol = min(SW.project_bar(q), FACTOR * max(bounds["cases"][cid][q], bounds["operators"]["down"][CC.pool_key(q)]["median"]))
         print(f"stem mixed input {kind:16s} {q:20s} err {rel:.3e}  bound {tol:.3e}")
         assert rel <= tol, (kind, q, rel, tol)
 

@@ -1,17 +1,14 @@
 """CPU tests of the YOLOX head sweep's references and case tables (tests/head_reference.py, tests/head_cases.py): the references agree with
 the oracle (which head_train.npz pins to the model reference), the case tables reach what the sweep is about, every case meets its input
-conditions and is decided the same way in float32 and float64, and the committed e32 figures are those the references give."""
-import json
-import os
-import subprocess
-import sys
-
+conditions and is decided the same way in float32 and float64, and the committed e32 figures hold the quantities the references give
+(tests/test_operator_bounds.py regenerates them)."""
 import numpy as np
 import pytest
 import torch
 
 import head_cases as HC
 import head_reference as R
+import operator_sweep as SW
 from oracle import sast_oracle as O
 
 _CACHE = {}
@@ -29,8 +26,7 @@ def case(cid):
     return HC.BY_ID[cid]
 
 
-def _ids(cases):
-    return [c["id"] for c in cases]
+_ids = SW.ids
 
 
 # ------------------------------------------------------------------------------------------------ agreement with the oracle
@@ -326,21 +322,7 @@ def test_a_case_without_its_margin_is_refused():
 
 
 # ------------------------------------------------------------------------------------------------ the committed bounds
-@pytest.fixture(scope="module")
-def bounds(golden_dir):
-    with open(os.path.join(golden_dir, "head_operator_bounds.json")) as f:
-        return json.load(f)
-
-
-def test_regenerating_the_bounds_reproduces_the_committed_file(golden_dir, bounds, tmp_path):
-    out = tmp_path / "bounds.json"
-    subprocess.run([sys.executable, os.path.join(golden_dir, "make_head_bounds.py"), "--out", str(out)], check=True)
-    with open(out) as f:
-        fresh = json.load(f)
-    assert set(fresh["cases"]) == set(bounds["cases"]) == {c["id"] for c in HC.FLOAT_CASES}
-    for cid in sorted(fresh["cases"]):
-        assert fresh["cases"][cid] == bounds["cases"][cid], cid
-    assert fresh["operators"] == bounds["operators"]
+bounds = SW.bounds_fixture("head")
 
 
 def test_bounds_hold_every_compared_quantity_and_stay_inside_the_project_bars(bounds):
@@ -360,7 +342,7 @@ def test_bounds_hold_every_compared_quantity_and_stay_inside_the_project_bars(bo
             assert set(entry) == want | {q.replace("grad:", f"grad:L{k}.") for q in grads for k in range(len(c["levels"]))}
         for q, e in entry.items():
             v = bounds["operators"][c["op"]][HC.pool_key(q)]
-            assert 0.0 <= e <= v["worst"] < HC.project_bar(q) / 2, (c["id"], q, e)
+            assert 0.0 <= e <= v["worst"] < SW.project_bar(q) / 2, (c["id"], q, e)
     for op, qs in bounds["operators"].items():
         for q, v in qs.items():
             assert 0.0 < v["median"] <= v["worst"] and v["n"] >= 4, (op, q, v)

@@ -1,20 +1,16 @@
 """CPU tests of the token-path operator sweep's own instruments (no GPU): the stand-alone restatements of tests/token_reference.py
-against the oracle lines they restate, the case table of tests/token_cases.py with the input conditions it is stated under, and the
-committed fp32 bounds (tests/golden/token_operator_bounds.json), which regenerating must reproduce.
+against the oracle lines they restate, the case table of tests/token_cases.py with the input conditions it is stated under, and what
+the committed fp32 bounds (tests/golden/token_operator_bounds.json) hold per case (tests/test_operator_bounds.py regenerates them).
 
 One figure of the bounds file is NOT inside the project's bar: the reference LayerNorm in float32 misses the 3e-5 output bar on the
 ill-conditioned MS-WSA case (rows 30 + 0.1 randn: e32 = 3.1e-5; 3.1e-5 .. 4.5e-5 at the widths 32 .. 128) -- the mean of 64 values
 near 30 carries a rounding error of about an ulp of 30 (1.9e-6), which the division by the spread of 0.1 turns into 2e-5 .. 4e-5 of
 the normalised row.  Every other figure is below half its bar, as in the conv suite.
 """
-import json
-import os
-import subprocess
-import sys
-
 import pytest
 import torch
 
+import operator_sweep as SW
 import token_cases as TC
 import token_reference as R
 from oracle import sast_oracle as O
@@ -127,23 +123,7 @@ def test_input_conditions_hold(case):
 
 
 # ------------------------------------------------------------------------------------------------ the committed bounds
-@pytest.fixture(scope="module")
-def bounds(golden_dir):
-    with open(os.path.join(golden_dir, "token_operator_bounds.json")) as f:
-        return json.load(f)
-
-
-def test_regenerating_the_bounds_reproduces_the_committed_file(golden_dir, bounds, tmp_path):
-    """make_token_bounds.py (--threads 1,4, worst of the two) evaluates every case in float32 and float64: the result equals the committed
-    file to the printed precision, so every case holds every quantity its reference produces"""
-    out = tmp_path / "bounds.json"
-    subprocess.run([sys.executable, os.path.join(golden_dir, "make_token_bounds.py"), "--out", str(out)], check=True)
-    with open(out) as f:
-        fresh = json.load(f)
-    assert set(fresh["cases"]) == set(bounds["cases"]) == {TC.bounds_id(c) for c in TC.ALL_CASES}
-    for cid in sorted(fresh["cases"]):
-        assert fresh["cases"][cid] == bounds["cases"][cid], cid
-    assert fresh["operators"] == bounds["operators"]
+bounds = SW.bounds_fixture("token")
 
 
 def test_bounds_hold_every_compared_quantity_and_stay_inside_the_project_bars(bounds):
@@ -168,8 +148,8 @@ def test_bounds_hold_every_compared_quantity_and_stay_inside_the_project_bars(bo
             if not exact:       # (copies, single adds and an empty sum: the GPU test asks for bit equality with the float32 reference there)
                 assert e > 0.0, (case["id"], q)
             if not (TC.bounds_id(case) == COND_CASE and q == "out:y"):
-                assert e < TC.project_bar(q) / 2, (case["id"], q, e)
+                assert e < SW.project_bar(q) / 2, (case["id"], q, e)
     assert 3e-5 < bounds["cases"][COND_CASE]["out:y"] < 4e-5        # the figure of the module docstring
     for op, qs in bounds["operators"].items():
         for q, v in qs.items():
-            assert v["median"] <= v["worst"] and v["median"] < TC.project_bar(q) / 2 and v["n"] >= 2, (op, q, v)
+            assert v["median"] <= v["worst"] and v["median"] < SW.project_bar(q) / 2 and v["n"] >= 2, (op, q, v)

@@ -1,13 +1,13 @@
 """The case table of the token-path operator sweep (tests/test_token_operators.py), the inputs of every case and its CPU reference.
 
-Shared by the GPU test, by tests/golden/make_token_bounds.py (every case in float32 against float64 on the CPU) and by
+Shared by the GPU test, by the bounds generator (tests/operator_sweep.py: every case in float32 against float64 on the CPU) and by
 tests/test_token_reference.py, so that all three see the same cases, numbers and quantity names.  CPU only: nothing here imports the library.
 
 A case is a dict with an "id", an "op" (the operator family its error statistics are pooled over), shapes and options.
 `make_inputs(case)` -> fp32 CPU tensors from a generator seeded by the id.  `reference(case, inputs, dtype)` -> {quantity: tensor}.
 Quantity names: "out:<name>" (forward results, every one O(1): compared absolutely), "rel:tok" (the token scores: they feed a threshold
 compare and scale with amp, so they are compared like a gradient) and "grad:<name>" (relative to the reference tensor's max-norm).
-`measure`, `pool_key` and `project_bar` are those of tests/conv_cases.py.
+`measure` and `project_bar` are those of tests/operator_sweep.py, `pool_key` is that of tests/conv_cases.py.
 
 Families:
   score       STP scoring.  "exact" inputs put every pre-activation of the scoring linear on an odd multiple of 1/256, computed without
@@ -28,12 +28,12 @@ Families:
               "h0zero" (zero h0 present, c0 None: forget-gate skip with the full reduction; dc0 is never requested without a c0).
 """
 import math
-import zlib
 
 import torch
 
+import operator_sweep as SW
 import token_reference as R
-from conv_cases import FWD_ATOL, GRAD_RTOL, measure, pool_key, project_bar  # noqa: F401  (re-exported: one definition for both suites)
+from conv_cases import pool_key  # noqa: F401  (part of the suite's face: the token quantities have no unit prefixes to pool)
 from oracle import sast_oracle as O
 
 WIDTHS = (32, 48, 64, 96, 128, 192, 256, 384, 512, 768, 1024)       # csrc/k_rows.hip: SAST_DISPATCH_C
@@ -115,18 +115,10 @@ def bounds_id(case):
 
 
 # ------------------------------------------------------------------------------------------------ inputs
-def _gen(cid):
-    return torch.Generator().manual_seed(zlib.crc32(cid.encode()))
-
-
-def _up(g, *shape):
-    return torch.randn(*shape, generator=g) + 0.5
-
-
 def kept_slots(case):
     """{window id: sorted kept slots} of the case's selection (eight windows of T = 20 slots; windows 0-3 are sample 0)"""
     Ks = {"mix": {0: 20, 1: 1, 3: 19, 4: 7, 5: 12, 6: 20, 7: 3}, "empty2": {0: 20, 1: 5, 3: 11}}[case["sel"]]
-    g = _gen("selection-" + case["sel"])
+    g = SW.gen("selection-" + case["sel"])
     return {w: sorted(torch.randperm(case["T"], generator=g)[:k].tolist()) for w, k in Ks.items()}
 
 
@@ -141,7 +133,7 @@ def token_mask(case):
 
 
 def make_inputs(case):
-    g = _gen(bounds_id(case))
+    g = SW.gen(bounds_id(case))
     op, C = case["op"], case["C"]
     if op == "score":
         B, L = case["B"], case["L"]
@@ -156,7 +148,7 @@ def make_inputs(case):
         inp["wc"] = 1 + 0.1 * torch.randn(C, 20, generator=g)
         if case["kind"] == "inf":
             inp["wc"][list(INF_CHANNELS)] = -math.inf
-        inp["g"] = _up(g, B, L, C)
+        inp["g"] = SW.up(g, B, L, C)
         return inp
     if op == "mswsa":
         NW, T, inner = case["B"] * case["N"], case["T"], case["inner"]
@@ -176,7 +168,7 @@ def make_inputs(case):
             inp["drop.d1"] = torch.bernoulli(torch.full((NW * T,), 0.8), generator=g) / 0.8
             inp["drop.d2"] = torch.bernoulli(torch.full((NW * T,), 0.8), generator=g) / 0.8
             inp["drop.mlp"] = torch.bernoulli(torch.full((NW * T, inner), 0.9), generator=g) / 0.9
-        inp["g"] = _up(g, NW, T, C)
+        inp["g"] = SW.up(g, NW, T, C)
         return inp
     if op in ("mask_token", "add_pos"):
         B, (H, W) = case["B"], MAP_HW
@@ -185,7 +177,7 @@ def make_inputs(case):
             inp["token"] = 0.02 * torch.randn(1, 1, 1, C, generator=g)
             if not case["pe"]:
                 del inp["table"]
-        inp["g"] = _up(g, B, H, W, C)
+        inp["g"] = SW.up(g, B, H, W, C)
         return inp
     if op == "lstm":
         B, (H, W) = case["B"], LSTM_HW
@@ -198,9 +190,9 @@ def make_inputs(case):
             inp["h0"], inp["c0"] = torch.zeros(shape), torch.zeros(shape)
         elif case["state"] == "h0zero":
             inp["h0"] = torch.zeros(shape)
-        inp["gh"], inp["gc"] = _up(g, *shape), _up(g, *shape)
+        inp["gh"], inp["gc"] = SW.up(g, *shape), SW.up(g, *shape)
         if case["two"]:
-            inp["gh2"] = _up(g, *shape)
+            inp["gh2"] = SW.up(g, *shape)
         if case["drop"]:
             inp["drop"] = torch.bernoulli(torch.full(shape, 0.75), generator=g) / 0.75
         return inp
@@ -257,19 +249,7 @@ NO_GRAD = ("g", "gh", "gc", "gh2", "r_buf", "table", "drop", "drop.d1", "drop.d2
 
 
 def _leaves(inp, dtype, grads=True):
-    out = {}
-    for k, v in inp.items():
-        t = v.to(dtype).clone()
-        if grads and k not in NO_GRAD:
-            t.requires_grad_(True)
-        out[k] = t
-    return out
-
-
-def _grads(out, p, only=None):
-    for k, v in p.items():
-        if v.requires_grad and (only is None or k in only):
-            out[f"grad:{k}"] = v.grad if v.grad is not None else torch.zeros_like(v)
+    return SW.leaves(inp, dtype, NO_GRAD, grads)
 
 
 def oracle_drop(case, p):
@@ -290,7 +270,7 @@ def reference(case, inp, dtype):
         out["out:xw"], out["rel:tok"] = xw.detach(), tok.detach()
         if not fwd_only:
             (xw * p["g"]).sum().backward()
-            _grads(out, p, ("wc",) if case["kind"] == "gauss" else None)
+            SW.grads(out, p, only=("wc",) if case["kind"] == "gauss" else None)
         return out
     if op == "mswsa":
         p = _leaves(inp, dtype, not case["nograd"])
@@ -301,21 +281,21 @@ def reference(case, inp, dtype):
         out["out:y"] = y.detach()
         if not case["nograd"]:
             (y * p["g"]).sum().backward()
-            _grads(out, p)
+            SW.grads(out, p)
         return out
     if op == "add_pos":
         p = _leaves(inp, dtype)
         y = R.add_pos_embedding(p["x"], p["table"])
         out["out:y"] = y.detach()
         (y * p["g"]).sum().backward()
-        _grads(out, p)
+        SW.grads(out, p)
         return out
     if op == "mask_token":
         p = _leaves(inp, dtype)
         y = R.mask_token(p["x"], token_mask(case), p["token"], p.get("table"))
         out["out:y"] = y.detach()
         (y * p["g"]).sum().backward()
-        _grads(out, p)
+        SW.grads(out, p)
         return out
     if op == "lstm":
         p = _leaves(inp, dtype)
@@ -325,7 +305,7 @@ def reference(case, inp, dtype):
         if case["two"]:
             loss = loss + (h1 * p["gh2"]).sum()
         loss.backward()
-        _grads(out, p)
+        SW.grads(out, p)
         return out
     raise KeyError(op)
 
@@ -336,3 +316,7 @@ def compared(case, quantities):
 
 
 EXACT = {"mask_token": ("out:y", "grad:x"), "add_pos": ("out:y", "grad:x")}      # copies and single adds: bit equality with the fp32 reference
+
+BOUNDS_CASES = [c for c in ALL_CASES if bounds_id(c) == c["id"]]      # the cases with an entry of their own in the bounds file
+float_quantities = sorted
+DISCRETE = ()

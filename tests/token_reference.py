@@ -1,7 +1,7 @@
 """Plain torch expressions of the token-path operators of `sast_amd.functional` (the transformer side of the backbone): STP scoring,
 mask token, position-embedding add, the MS-WSA layer and the ConvLSTM.  CPU only; everything runs in the dtype of its inputs, so the same
 expression is the float64 reference of tests/test_token_operators.py and, evaluated in float32, the yardstick of
-tests/golden/make_token_bounds.py.
+tests/golden/make_operator_bounds.py.
 
 MS-WSA and ConvLSTM are the oracle's functions (oracle/sast_oracle.py: ms_wsa, conv_lstm) behind a parameter-name mapping.  Scoring has no
 stand-alone function there -- it is inline in `sast_block` (oracle/sast_oracle.py:339-354) -- and is written out here; so are the two
