@@ -530,19 +530,11 @@ int sast_mswsa_bwd(const SastMswsaArgs* a, sast_stream_t stream) { SAST_ENTRY();
   if (rc) return rc;
   // raw (gamma-free) fc2 and proj gradients -> parameter gradients incl. the LayerScale gammas: side workgroups of the attention
   // backward launch
-  // (deferred weight gradients: the raw accumulators are only complete once the parked fc2 / proj jobs have run -- the finish is
-  // parked behind them as its own small launch and the attention backward goes without side workgroups)
   {
     const LsFinish f2{a->fc2_w, a->fc2_b, a->ls2, raw2, s2, a->d_fc2_w, a->d_fc2_b, a->d_ls2, inner};
     const LsFinish f1{a->proj_w, a->proj_b, a->ls1, raw1, s1, a->d_proj_w, a->d_proj_b, a->d_ls1, C};
-    const bool parked = dw_defer_rows_ok(R);
-    if (parked)
-      dw_defer_push([=](hipStream_t s, bool run) {
-        return !run ? SAST_OK : ls_linear_finish2_launch(f2.w, f2.b, f2.gamma, f2.raw, f2.s, f2.dw, f2.db, f2.dgamma, f2.K,
-                                        f1.w, f1.b, f1.gamma, f1.raw, f1.s, f1.dw, f1.db, f1.dgamma, f1.K, C, s);
-      });
-    rc = attn_bwd_mfma_launch(a->QKV, dO, a->lse, dQKV, a->sel.row_off, a->sel.K, NW, T, C, dh, st, parked ? nullptr : &f2,
-                              parked ? nullptr : &f1, parked ? 0 : C, a->ws + mswsa_bwd_ws_base(R, C, inner));
+    rc = attn_bwd_mfma_launch(a->QKV, dO, a->lse, dQKV, a->sel.row_off, a->sel.K, NW, T, C, dh, st, &f2, &f1, C,
+                              a->ws + mswsa_bwd_ws_base(R, C, inner));
   }
   if (rc) return rc;
   // qkv: dWqkv / dbqkv, and dS = dY + dQKV Wqkv

@@ -905,15 +905,6 @@ int ls_linear_finish_launch(const float* w, const float* b, const float* gamma, 
   SAST_CHECK_LAUNCH();
   return SAST_OK;
 }
-// both finishes of one MS-WSA layer (same number of output channels C) in one launch
-int ls_linear_finish2_launch(const float* w0, const float* b0, const float* g0, const float* raw0, const float* s0, float* dw0, float* db0,
-                             float* dg0, int K0, const float* w1, const float* b1, const float* g1, const float* raw1, const float* s1,
-                             float* dw1, float* db1, float* dg1, int K1, int C, hipStream_t st) {
-  const LsFinish p0{w0, b0, g0, raw0, s0, dw0, db0, dg0, K0}, p1{w1, b1, g1, raw1, s1, dw1, db1, dg1, K1};
-  SAST_LAUNCH(ls_linear_finish_kernel, dim3(C, 2), dim3(64), 0, st, p0, p1, C);
-  SAST_CHECK_LAUNCH();
-  return SAST_OK;
-}
 
 // ============================================================ mean squares of up to 4 tensors in one launch
 // partials[t * MSQ_BLOCKS + b] = sum over block b's grid-stride share of x_t^2 / n_t  (their sum is sum_t mean(x_t^2), the

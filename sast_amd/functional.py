@@ -55,6 +55,8 @@ def _fill(struct, **kw):
 
 
 AUTOGRAD_GRADS = os.environ.get("SAST_AUTOGRAD_GRADS", "0") == "1"
+# constant since deferred weight gradients were retired; read only by the `dev` fixture of tests/operator_sweep.py
+_DW_DEFER = False
 
 
 def set_autograd_visible_grads(on: bool = True) -> bool:
@@ -159,48 +161,6 @@ class _ParamGrads:
 
     def out(self):
         return tuple(self.ret)
-
-
-# ---- deferred weight gradients (include/sast_hip.h: sast_dw_defer ...; csrc/k_defer.hip).  Owned by training.TrainStep: while deferral is
-# on, the backward entry points park their weight-gradient jobs in the library's queue and the owner flushes them on a side stream.  The
-# parked jobs hold RAW pointers to the upstream gradients, workspaces, saved activations and row counts of the backward call that parked
-# them, so every backward that can park hands its locals to `_dw_hold`; the owner releases them (`dw_release`) once the stream it keeps
-# allocating on is ordered behind the flushed launches.
-_DW_DEFER = False
-_DW_HOLD = []
-
-
-def dw_defer(on: bool, min_rows: int = 0, max_rows: int = 0) -> bool:
-    """switch the library's deferral of weight-gradient jobs on / off (process-wide); returns the previous setting.
-    min_rows / max_rows: only jobs whose reduction runs over that many rows are parked (0 = unbounded)."""
-    global _DW_DEFER
-    prev, _DW_DEFER = _DW_DEFER, bool(on)
-    L.lib().sast_dw_defer_rows(int(min_rows), int(max_rows))
-    L.lib().sast_dw_defer(int(bool(on)))
-    return prev
-
-
-def dw_pending() -> int:
-    return int(L.lib().sast_dw_pending())
-
-
-def dw_flush():
-    """enqueue every parked weight-gradient job on the CURRENT stream (the caller has ordered it behind the backward kernels)"""
-    L.check(L.lib().sast_dw_flush(_stream()), "dw_flush")
-
-
-def dw_discard() -> int:
-    return int(L.lib().sast_dw_discard())
-
-
-def dw_release():
-    """drop the references held for parked jobs (the caller has ordered its allocating stream behind the flushed launches)"""
-    _DW_HOLD.clear()
-
-
-def _dw_hold(objs):
-    if _DW_DEFER:
-        _DW_HOLD.append(objs)
 
 
 def _consume(ctx, what: str):
@@ -454,7 +414,6 @@ class _DownsampleLN(torch.autograd.Function):
                   conv_out=conv_out, mean=stats[0], rstd=stats[1], dy=dy, dx=_ptr(dx), dw=pg[0], d_ln_w=pg[1], d_ln_b=pg[2], ws=ws,
                   x_dtype=xdt, no_overlap=no_overlap, x_nonexact=_ptr(ctx.nonexact))
         L.check(L.lib().sast_downsample_ln_bwd(C.byref(a), _stream()), "downsample_ln_bwd")
-        _dw_hold((x, conv_out, stats, dy, ws, pg, ctx.nonexact))
         return (dx,) + pg.out() + (None, None, None)
 
 
@@ -537,7 +496,6 @@ class _ScoreSTP(torch.autograd.Function):
         a = _fill(L.SastScoreArgs(), B=B, L=Lt, C=Cc, r_stride=r.stride(0), amp=amp, xp=xp, r=r, ws_w=ws_w, ws_b=ws_b, wc=wc,
                   scale=scale, s=s, dxw=dxw, dxp=dxp, d_ws_w=pg[0], d_ws_b=pg[1], d_wc=pg[2], ws=ws, dscale_ws=dscale)
         L.check(L.lib().sast_score_stp_bwd(C.byref(a), _stream()), "score_stp_bwd")
-        _dw_hold((xp, r, scale, s, dscale, dxw, ws, pg))
         return (dxp, None) + pg.out() + (None,)
 
 
@@ -875,7 +833,6 @@ class _MSWSA(torch.autograd.Function):
         pg = _ParamGrads(*params)                          # held until the launch is enqueued (scratch buffers among them)
         _fill(a, **{"d_" + k: _ptr(pg[i]) for i, k in enumerate(_MSWSA_PARAMS)})
         L.check(L.lib().sast_mswsa_bwd(C.byref(a), _stream()), "mswsa_bwd")
-        _dw_hold((xin, stats, big, raw, fws, dout, ws, pg, sel, ctx.drop, ctx.drop_mlp, locals().get("drop_ws"), locals().get("cb_m"), locals().get("cb_sum")))
         return (dxin, None, None, None, None, None, None, None, None) + pg.out()
 
 
@@ -954,7 +911,6 @@ class _LSTM(torch.autograd.Function):
         a = _fill(L.SastLstmArgs(), B=B, L=Lt, C=Cc, x=x, h0=_ptr(h0), c0=_ptr(c0), w=w, b=b, c1=c1, gates=gates, dh1=dh1,
                   dc1=_ptr(dc1), dx=dx, dh0=_ptr(dh0), dc0=_ptr(dc0), dw=pg[0], db=pg[1], ws=ws, dh1b=_ptr(dh1b), drop=_ptr(drop))
         L.check(L.lib().sast_lstm_bwd(C.byref(a), _stream()), "lstm_bwd")
-        _dw_hold((x, h0, c0, c1, gates, drop, dh1, dh1b, dc1, ws, pg))
         return (dx, dh0, dc0) + pg.out() + (None,)
 
 
@@ -1362,7 +1318,6 @@ class _ConvBnSiluUnits(torch.autograd.Function):
                 _cbs_bwd(a)
             _mark_served(served)
             grads.extend((dx, dx2) + pg.out() + (None, None))
-        _dw_hold((sv, [(keep, pg) for _a, _dx, _dx2, pg, _served, keep, _m in jobs]))
         return tuple(grads)
 
 
@@ -1459,7 +1414,6 @@ class _ConvBnSilu2(torch.autograd.Function):
                   stats0=st0, stats1=st1, bn_ws0=ws0, bn_ws1=ws1, dy0=dy0, dy1=dy1, dw0=pg[0], dw1=pg[3], d_bn_w0=pg[1],
                   d_bn_w1=pg[4], d_bn_b0=pg[2], d_bn_b1=pg[5], ws0=dws, dx=_ptr(dx), dx2=_ptr(dx2), **pk)
         L.check(L.lib().sast_conv_bn_silu2_bwd(C.byref(a), _stream()), "conv_bn_silu2_bwd")
-        _dw_hold((x, x2, co0, co1, st0, st1, ws0, ws1, dy0, dy1, dws, pg))
         _mark_served(served)
         g = pg.out()        # forward(ctx, x, x2, w0, bnw0, bnb0, rm0, rv0, w1, bnw1, bnb1, rm1, rv1, ... 9 more)
         return (dx, dx2) + g[0:3] + (None, None) + g[3:6] + (None,) * 11

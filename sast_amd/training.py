@@ -19,18 +19,9 @@ in the middle of the PAFPN / head passes.
 With world == 1 the all-reduce is a no-op and everything else is identical, so a single-GPU run exercises the same path.
 
 For sequences (seq_len > 1, BPTT) the backbone gradients only become final at the end of the backward: segments B and C merge.
-
-Round 6: DEFERRED WEIGHT GRADIENTS (`defer_dw=True`).  Nothing reads a weight gradient before AdamW, yet in the chain above every
-layer's backward launch carries its dW job beside its dX job and the next kernel waits for both.  With deferral the backward entry
-points launch only the dX chain on the main stream and park the dW jobs in the library (include/sast_hip.h: sast_dw_defer); after each
-segment the side stream waits for the segment's event, runs the parked jobs (`SF.dw_flush`; replayed as a hipGraph of its own -- kernel
-nodes of ONE graph never overlap on ROCm 7.2, separately instantiated graphs on two streams do) and then that segment's all-reduce +
-AdamW, while the main stream is already in the next segment's chain.  `dw_cuts` adds segment boundaries before backbone stages
-(more, shorter dW graphs: less weight-gradient work left exposed behind the last segment); buckets and their order are unchanged.
 """
 from __future__ import annotations
 
-import os
 from typing import Dict, List, Optional, Sequence
 
 import torch
@@ -45,11 +36,12 @@ class TrainStep:
     def __init__(self, net, fpn, head=None, *, lr: float = 2e-4, weight_decay: float = 0.0, clip_value: float = 0.0, eps: float = 1e-8,
                  schedule: Optional[OneCycleLR] = None, world: int = 1, group=None, segmented: bool = True, defer_dw: bool = False,
                  dw_rows=(0, 0), dw_discard: bool = False, cuts: Sequence[int] = (3,)):
+        # defer_dw / dw_rows / dw_discard (and flush_pending below) remain only because bench.py's call sites pass them by keyword
+        if defer_dw or dw_discard:
+            raise ValueError("sast_amd.TrainStep: deferred weight gradients were retired after their measurement (DESIGN.md section 3, "
+                             "round 6); tools/experiments/r06_deferred_weight_gradients.patch restores them")
         self.net, self.fpn, self.head = net, fpn, head
         self.world, self.group = world, group
-        # defer_dw: weight gradients off the backward chain (module docstring); dw_rows = (min, max) reduction rows of the jobs that are
-        # parked (0 = unbounded); dw_discard: TIMING PROBE ONLY -- the parked jobs are dropped instead of run (the dX chain alone)
-        self.defer_dw, self.dw_rows, self.dw_discard = bool(defer_dw), tuple(dw_rows), bool(dw_discard)
         stages = list(net.stages)
         first = [fpn] + ([head] if head is not None else [])
         # The segmented backward is written for the topology of the shipped models: four backbone stages, the PAFPN reading stages up to
@@ -76,7 +68,7 @@ class TrainStep:
         self.segmented = segmented
         # cuts: the backbone stages (0-based) whose INPUT is a segment boundary of the single-timestep backward.  (3,) = the three
         # segments of the module docstring; more cuts (e.g. (3, 2, 1)) only add boundaries -- the buckets stay the same three, a bucket
-        # is reduced + updated behind the segment that completes it; with defer_dw every segment's parked weight gradients leave behind it
+        # is reduced + updated behind the segment that completes it
         self.cuts = tuple(sorted({int(c) for c in cuts}, reverse=True))
         if segmented and (not self.cuts or self.cuts[0] != 3 or min(self.cuts) < 1):
             raise ValueError(f"TrainStep(cuts={cuts}): the segmented backward needs the cut before the last stage (3) and cuts in 1 .. 3")
@@ -88,15 +80,11 @@ class TrainStep:
         self.opt = FusedAdamW(self.flat, lr=lr, weight_decay=weight_decay, clip_value=clip_value, eps=eps, schedule=schedule)
         dev = self.flat.flat.device
         self._one = torch.ones((), device=dev)
-        # the side stream carries what the step does NOT wait for (bucket all-reduce + AdamW, deferred weight gradients): lowest priority
-        # with defer_dw, so that the dispatcher serves the backward chain's workgroups first and the parked jobs soak up what is left
-        prio = int(os.environ.get("SAST_SIDE_PRIORITY", "1" if defer_dw else "0"))
-        self.side = torch.cuda.Stream(priority=prio) if dev.type == "cuda" else None
+        # the side stream carries what the step does NOT wait for (bucket all-reduce + AdamW)
+        self.side = torch.cuda.Stream() if dev.type == "cuda" else None
         self.loss = self.P = self.losses = None
         self._graphs = None
-        self._dw_graphs = None
         self._seg_state = None
-        self._replaying = False    # inside replay(): the side stream runs the captured flush graphs, nothing is parked eagerly
         self._carry = None         # carry_states: the input state tensors the final states are copied into
         self.label_counts = None
         self._sets = {}            # capture(key=...): key -> the captured graph set and what replay(key) restores with it
@@ -135,10 +123,6 @@ class TrainStep:
                 SF.zero_samples_dev(held, reset)
             if carry_states:
                 self._carry = held
-        if self.defer_dw and SF.dw_pending():
-            # a backward of an earlier step died between parking and flushing: its jobs point at buffers that are gone -- never run them
-            SF.dw_discard()
-            SF.dw_release()
         self.flat.zero_grad()
         single = len(xs) == 1 and self.segmented
         feats_seq, Ps = [], []
@@ -196,20 +180,10 @@ class TrainStep:
         return 1 + len(self._stage_groups()) if self._seg_state[3] is not None else 2
 
     def _side_path(self) -> bool:
-        """reduce + update (and the parked weight-gradient jobs) run on the side stream"""
-        return self.side is not None and (self.segmented or self.defer_dw)
+        """reduce + update run on the side stream"""
+        return self.side is not None and self.segmented
 
     def backward_segment(self, i: int):
-        if self.defer_dw:
-            prev = SF.dw_defer(True, *self.dw_rows)
-            try:
-                self._backward_segment(i)
-            finally:
-                SF.dw_defer(prev)
-            return
-        self._backward_segment(i)
-
-    def _backward_segment(self, i: int):
         loss, fpn_in, leaves, cut = self._seg_state
         if i == 0:
             loss.backward(gradient=self._one)            # a resident 1.0 instead of a ones_like fill launch per step
@@ -270,36 +244,17 @@ class TrainStep:
         self._bucket_ev = {}
         return out
 
-    def _flush_dw(self, i: int):
-        """the weight-gradient jobs segment i parked, on the current (side) stream: the captured graph of the flush, or the launches"""
-        if not self.defer_dw:
-            return
-        if self._replaying and self._dw_graphs is not None:      # (an eager step between replays flushes its own jobs)
-            if self._dw_graphs[i] is not None:
-                self._dw_graphs[i].replay()
-        elif self.dw_discard:
-            SF.dw_discard()
-        else:
-            SF.dw_flush()
-
     def _carry_now(self):
-        """carry_states: the final states into the input state tensors.  Nothing of the step may still read the inputs: the backward is
-        over, and with deferred weight gradients the side stream has run its parked jobs (they read the first timestep's states)"""
+        """carry_states: the final states into the input state tensors.  Nothing of the step may still read the inputs: the backward is over"""
         if self._carry is not None:
             SF.copy_tensors(self._carry, [t.detach() for s in self.states for t in s])
 
     def flush_pending(self):
-        """callers that run forward + backward_segment() themselves (no reduce / update): the parked jobs on the CURRENT stream"""
-        if self.defer_dw:
-            SF.dw_flush()
-            SF.dw_release()
+        """no-op: nothing is parked between backward_segment() and the optimizer (see __init__)"""
 
     def _after_segment(self, i: int, first: bool):
-        """(the parked weight-gradient jobs of segment i, then) all-reduce + AdamW of the buckets that segment i completed; on the side
-        stream when the step is segmented or defers its weight gradients"""
+        """all-reduce + AdamW of the buckets that segment i completed; on the side stream when the step is segmented"""
         if not self._side_path():
-            if self.defer_dw:
-                self._flush_dw(i)
             if first:
                 self.opt.begin_step()
             self._reduce_update(self.bucket_of_segment(i))
@@ -309,7 +264,6 @@ class TrainStep:
         ev.record(main)
         with torch.cuda.stream(self.side):
             self.side.wait_event(ev)
-            self._flush_dw(i)
             if first:
                 self.opt.begin_step()
             self._reduce_update(self.bucket_of_segment(i))
@@ -323,8 +277,6 @@ class TrainStep:
                 e1.record(self.side)       # ... the side stream still owes the last bucket's reduce + update
                 self._exposed.append((e0, e1))
             main.wait_stream(self.side)
-        if self.defer_dw and not self._replaying:
-            SF.dw_release()          # eager: the allocating stream is now ordered behind the flushed launches
 
     def exposed_ms(self):
         """mean time per step by which the side stream (bucket all-reduce + AdamW) finished AFTER the main stream (0 when it was
@@ -387,42 +339,22 @@ class TrainStep:
             self._file_set(key)
             return
         pool = self._pool if key is not None else torch.cuda.graph_pool_handle()
-        graphs, dw_graphs = [], []
-
-        def flush_graph():
-            """the jobs the segment just captured has parked, as a graph of their own (replayed on the side stream).  Everything they
-            read stays referenced (functional._DW_HOLD) until ALL graphs are captured: no later capture is handed their memory."""
-            if not self.defer_dw:
-                return None
-            if self.dw_discard:
-                SF.dw_discard()
-                return None
-            if SF.dw_pending() == 0:
-                return None
-            d = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(d, pool=pool, capture_error_mode="thread_local"):
-                SF.dw_flush()
-            return d
-
+        graphs = []
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g, pool=pool, capture_error_mode="thread_local"):
             self.forward(xs, states, labels, indices, token_masks, **device_selection)
             self.backward_segment(0)
         graphs.append(g)
-        dw_graphs.append(flush_graph())
         for i in range(1, self.n_segments()):
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, pool=pool, capture_error_mode="thread_local"):
                 self.backward_segment(i)
             graphs.append(g)
-            dw_graphs.append(flush_graph())
         self._graphs = graphs
-        self._dw_graphs = dw_graphs if self.defer_dw else None
-        SF.dw_release()
         self.loss = self.loss.detach()
         self._file_set(key)
 
-    _SET_FIELDS = ("_graphs", "_dw_graphs", "loss", "losses", "P", "states", "label_counts", "_carry")
+    _SET_FIELDS = ("_graphs", "loss", "losses", "P", "states", "label_counts", "_carry")
 
     def _file_set(self, key):
         """capture: keep, under `key`, what the capture left in this object -- the graphs and the (static) tensors a replay fills.  Of the
@@ -437,11 +369,7 @@ class TrainStep:
         under it: the caller runs `step`).  Returns the loss tensor of that set."""
         for f, v in self._sets[key].items():
             setattr(self, f, v)
-        self._replaying = True
-        try:
-            loss = self._replay()
-        finally:
-            self._replaying = False
+        loss = self._replay()
         self._carry_now()
         return loss
 

@@ -19,7 +19,6 @@ PINNED = {
                                       C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, P]),
     "sast_select": (C.c_int, [P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(_lib.SastSel), P]),
     "sast_evqueue_push": (C.c_int, [C.POINTER(_lib.SastEvQueueArgs), P, P, P, P, C.c_int, C.c_int, C.c_int, C.c_int, P, C.c_int64, P, P]),
-    "sast_dw_defer_rows": (C.c_int, [C.c_long, C.c_long]),
     "sast_prof_calibrate": (C.c_float, [P, C.c_int]),
     "sast_launch_count": (C.c_ulonglong, []),
     "sast_config_get": (C.c_int, [C.c_char_p, C.c_int]),
@@ -53,7 +52,7 @@ def _gcc(tmp_path, text):
 
 
 def test_a_c_compiler_agrees_with_every_struct_constant_scalar_and_prototype(tmp_path):
-    assert len(H.structs) >= 20 and len(H.constants) >= 39 and len(H.prototypes) >= 99     # the header only grows
+    assert len(H.structs) >= 20 and len(H.constants) >= 39 and len(H.prototypes) >= 94     # the header only grows (99 before the five sast_dw_* left)
     text = _abi_c()
     for st in H.structs.values():
         assert [f for f, _t in st._fields_] == [f.name for f in st.c_fields] and len(set(f.name for f in st.c_fields)) == len(st.c_fields)

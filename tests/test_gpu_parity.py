@@ -1455,11 +1455,9 @@ def test_sequence_gather_vs_golden(golden_dir, dev):
     assert all(float(h.abs().max()) == 0.0 for h, _ in st.get_states(0))
 
 
-@pytest.mark.parametrize("defer_dw", [False, True], ids=["paired", "deferred-dw"])
-def test_label_sparse_sequence_step(dev, defer_dw):
-    """(deferred-dw: the same with the weight-gradient jobs parked and flushed on the side stream, training.TrainStep(defer_dw=True) --
-    BPTT accumulates several timesteps' jobs into the same gradients, the head and the sample gather take part)
-    the model part of the reference's training step (modules/detection.py:139-177): L = 3 timesteps with carried states, labels
+@pytest.mark.parametrize((), [pytest.param(id="paired")])       # no argument: keeps the id, and with it the parity-record key, of this case
+def test_label_sparse_sequence_step(dev):
+    """the model part of the reference's training step (modules/detection.py:139-177): L = 3 timesteps with carried states, labels
     on a subset of the (timestep, sample) pairs, the labelled features gathered into ONE PAFPN + head + SimOTA call, BPTT through
     everything -- losses, kept-token counts and every gradient against the oracle run the same way; then a second sequence that
     starts from the saved (detached) states with sample 1 reset."""
@@ -1477,7 +1475,7 @@ def test_label_sparse_sequence_step(dev, defer_dw):
     load_params(net, bp)
     load_params(fpn, fp)
     load_params(head, hp)
-    ts = TrainStep(net, fpn, head, lr=0.0, segmented=True, defer_dw=defer_dw)          # lr 0: the parameters stay put, gradients are what is compared
+    ts = TrainStep(net, fpn, head, lr=0.0, segmented=True)          # lr 0: the parameters stay put, gradients are what is compared
     xs = [O.count_events(B, hw, seed=70 + t, density=0.05) for t in range(L)]
     indices = [[0, 2], [], [1, 2, 0]]
     labels = O.synthetic_labels(5, hw, nc, max_labels=5, seed=64)
@@ -1507,9 +1505,11 @@ def test_label_sparse_sequence_step(dev, defer_dw):
     assert abs(float(ts.losses["loss"]) - float(ref2["loss"])) <= 1e-4 * abs(float(ref2["loss"]))
 
 
-def test_segmented_step_matches_monolithic(dev):
-    """training.TrainStep: backward in three segments with per-bucket (all-reduce +) AdamW on a side stream == the monolithic step,
-    eager and as hipGraphs (three graphs sharing a pool, reduce + update between them); OneCycleLR evaluated on the device."""
+@pytest.mark.parametrize("cuts", [(3,), (3, 2, 1)], ids=["segmented", "segment-per-stage"])
+def test_segmented_step_matches_monolithic(dev, cuts):
+    """training.TrainStep: backward in three segments (cuts (3,); (3, 2, 1): one per backbone stage -- the same kernels and sums, only the
+    autograd cut points differ) with per-bucket (all-reduce +) AdamW on a side stream == the monolithic step, eager and as hipGraphs
+    (one graph per segment sharing a pool, reduce + update between them); OneCycleLR evaluated on the device."""
     from sast_amd.config import backbone_config
     from sast_amd.detection import RNNDetector, YOLOPAFPN
     from sast_amd.dist import OneCycleLR
@@ -1517,13 +1517,14 @@ def test_segmented_step_matches_monolithic(dev):
     hw, part, E = (128, 160), (4, 5), 32
     x = O.count_events(2, hw, seed=2, density=0.05).to(dev)
 
-    def rig(segmented):
+    def rig(segmented, cuts=(3,)):
         torch.manual_seed(0)
         net = RNNDetector(backbone_config(hw, part, embed_dim=E, AMP=2e-4, ls_init_value=0.5)).to(dev)
         fpn = YOLOPAFPN(depth=0.67, in_stages=(2, 3, 4), in_channels=(64, 128, 256)).to(dev)
-        return TrainStep(net, fpn, lr=1e-3, eps=1e-3, clip_value=1.0, schedule=OneCycleLR(1e-3, total_steps=20, pct_start=0.25), segmented=segmented)
+        return TrainStep(net, fpn, lr=1e-3, eps=1e-3, clip_value=1.0, schedule=OneCycleLR(1e-3, total_steps=20, pct_start=0.25), segmented=segmented,
+                         cuts=cuts)
 
-    mono, seg, segg = rig(False), rig(True), rig(True)
+    mono, seg, segg = rig(False), rig(True, cuts), rig(True, cuts)
     assert seg.flat.bucket_ranges[0][1] > 0 and seg.flat.bucket_ranges[2][1] == seg.flat.numel
     ref = []
     for _ in range(4):
@@ -1531,7 +1532,7 @@ def test_segmented_step_matches_monolithic(dev):
         ref.append((float(mono.loss), mono.flat.grad.clone(), mono.flat.flat.clone()))
     for k in range(4):
         seg.step([x])
-        assert seg.n_segments() == 3
+        assert seg.n_segments() == 2 + len(cuts)
         torch.cuda.synchronize()
         assert abs(float(seg.loss) - ref[k][0]) <= 1e-5 * abs(ref[k][0])
         maxnorm_close(seg.flat.grad, ref[k][1], (1e-5, 1e-4, 1e-3, 3e-3)[k], f"segmented eager, gradient of step {k}")
@@ -1542,6 +1543,7 @@ def test_segmented_step_matches_monolithic(dev):
         segg.step([x])                                   # eager warm-up == step 0
         torch.cuda.synchronize()
         segg.capture([x])
+        assert len(segg._graphs) == segg.n_segments() == 2 + len(cuts)
         for k in range(1, 4):
             segg.replay()
             torch.cuda.synchronize()
@@ -1551,56 +1553,6 @@ def test_segmented_step_matches_monolithic(dev):
     maxnorm_close(segg.flat.flat, ref[3][2], 1e-4, "segmented graphs, parameters after 4 updates")
     # the device-side schedule advanced with the replays: same step count, and the host closed form agrees with torch (CPU test)
     assert float(segg.opt.lr_step[1]) == 4.0
-
-
-@pytest.mark.parametrize("segmented, cuts", [(True, (3,)), (False, (3,)), (True, (3, 2, 1))], ids=["segmented", "one-segment", "segment-per-stage"])
-def test_deferred_weight_gradients_match_monolithic(dev, segmented, cuts):
-    """training.TrainStep(defer_dw=True): the weight-gradient jobs leave the backward chain (parked in the library, run on the side stream
-    beside the next segment, csrc/k_defer.hip) -- same loss, gradients and parameters as the monolithic step over four updates, eager and as
-    hipGraphs (one graph per segment + one graph per flush); nothing stays parked, nothing stays held."""
-    from sast_amd import functional as SF
-    from sast_amd.config import backbone_config
-    from sast_amd.detection import RNNDetector, YOLOPAFPN
-    from sast_amd.dist import OneCycleLR
-    from sast_amd.training import TrainStep
-    hw, part, E = (128, 160), (4, 5), 32
-    x = O.count_events(2, hw, seed=2, density=0.05).to(dev)
-
-    def rig(**kw):
-        torch.manual_seed(0)
-        net = RNNDetector(backbone_config(hw, part, embed_dim=E, AMP=2e-4, ls_init_value=0.5)).to(dev)
-        fpn = YOLOPAFPN(depth=0.67, in_stages=(2, 3, 4), in_channels=(64, 128, 256)).to(dev)
-        return TrainStep(net, fpn, lr=1e-3, eps=1e-3, clip_value=1.0, schedule=OneCycleLR(1e-3, total_steps=20, pct_start=0.25), **kw)
-
-    mono, dfr, dfrg = rig(segmented=False), rig(segmented=segmented, defer_dw=True, cuts=cuts), rig(segmented=segmented, defer_dw=True, cuts=cuts)
-    ref = []
-    for _ in range(4):
-        mono.step([x])
-        ref.append((float(mono.loss), mono.flat.grad.clone(), mono.flat.flat.clone()))
-    for k in range(4):
-        dfr.step([x])
-        assert dfr.n_segments() == (2 + len(cuts) if segmented else 1)
-        assert SF.dw_pending() == 0 and not SF._DW_HOLD and not SF._DW_DEFER
-        torch.cuda.synchronize()
-        assert abs(float(dfr.loss) - ref[k][0]) <= 1e-5 * abs(ref[k][0])
-        maxnorm_close(dfr.flat.grad, ref[k][1], (1e-5, 1e-4, 1e-3, 3e-3)[k], f"deferred eager, gradient of step {k}")
-    maxnorm_close(dfr.flat.flat, ref[3][2], 1e-4, "deferred eager, parameters after 4 updates")
-    s = torch.cuda.Stream()
-    s.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(s):
-        dfrg.step([x])                                   # eager warm-up == step 0
-        torch.cuda.synchronize()
-        dfrg.capture([x])
-        assert SF.dw_pending() == 0 and not SF._DW_HOLD and not SF._DW_DEFER
-        assert len(dfrg._dw_graphs) == dfrg.n_segments() and all(d is not None for d in dfrg._dw_graphs)
-        for k in range(1, 4):
-            dfrg.replay()
-            torch.cuda.synchronize()
-            assert abs(float(dfrg.loss) - ref[k][0]) <= 1e-5 * abs(ref[k][0]), (k, float(dfrg.loss), ref[k][0])
-            maxnorm_close(dfrg.flat.grad, ref[k][1], (1e-4, 1e-3, 3e-3)[k - 1], f"deferred graphs, gradient of step {k}")
-    torch.cuda.current_stream().wait_stream(s)
-    maxnorm_close(dfrg.flat.flat, ref[3][2], 1e-4, "deferred graphs, parameters after 4 updates")
-    assert float(dfrg.opt.lr_step[1]) == 4.0
 
 
 def test_knob_reload_reaches_the_launch_sites(dev, monkeypatch):
@@ -1711,9 +1663,9 @@ def test_graph_replay_matches_eager(dev):
         maxnorm_close(gr[2].grad, eager[k][1], (1e-4, 1e-3, 3e-3)[k - 1], f"flat gradient after {k} updates, replay vs eager")
 
 
-@pytest.mark.parametrize("defer_dw", [False, True], ids=["paired", "deferred-dw"])
-def test_training_step_with_every_optional_config_branch_as_hipgraphs(dev, defer_dw):
-    """(deferred-dw: the same step with its weight gradients parked and flushed per segment on the side stream, one flush graph per segment)
+@pytest.mark.parametrize("cuts", [(3,), (3, 2)], ids=["paired", "cuts-3-2"])
+def test_training_step_with_every_optional_config_branch_as_hipgraphs(dev, cuts):
+    """(cuts-3-2: the same step with a fourth segment, cut before stage 3)
     the config branches no shipped YAML uses, all at once, through the product's training step: mlp_activation silu, drop_path, drop_mlp,
     cell_update_dropout and a depth-wise ConvLSTM in the backbone (downsampling without overlap / affine), depthwise PAFPN and head, the YOLOX
     loss -- first eagerly, then captured as segmented hipGraphs (the random masks are drawn by torch's graph-safe generator INSIDE the
@@ -1734,7 +1686,7 @@ def test_training_step_with_every_optional_config_branch_as_hipgraphs(dev, defer
     head = YOLOXHead(num_classes=2, strides=(8, 16, 32), in_channels=chans, depthwise=True).to(dev)
     for m in (net, fpn, head):
         m.train()
-    ts = TrainStep(net, fpn, head, lr=2e-3, weight_decay=0.0, clip_value=1.0, eps=1e-3, segmented=True, defer_dw=defer_dw, cuts=(3, 2) if defer_dw else (3,))
+    ts = TrainStep(net, fpn, head, lr=2e-3, weight_decay=0.0, clip_value=1.0, eps=1e-3, segmented=True, cuts=cuts)
     xs = [O.count_events(2, hw, seed=21, density=0.05).to(dev)]
     labels = O.synthetic_labels(2, hw, 2, max_labels=4, seed=22)
     labels[:, 0, :] = torch.tensor([1.0, 70.0, 60.0, 50.0, 40.0])

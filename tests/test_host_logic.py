@@ -637,18 +637,27 @@ def test_library_knobs_registry_and_reload(monkeypatch):
     assert lib.sast_config_get(b"SAST_TN_BLOCKS", 768) == 768
 
 
-def test_deferred_weight_gradient_queue_is_off_and_empty_by_default():
-    """include/sast_hip.h sast_dw_*: deferral is opt-in (training.TrainStep(defer_dw=True) owns the flush); the switch returns its
-    previous setting, nothing is parked without a backward call, flush / discard of an empty queue are no-ops (no GPU needed)"""
-    from sast_amd import _lib as SL, functional as SF
-    lib = SL.lib()
-    assert lib.sast_dw_pending() == 0
-    assert SF.dw_defer(True, 0, 16000) is False and SF._DW_DEFER
-    assert SF.dw_defer(False) is True and not SF._DW_DEFER
-    assert lib.sast_dw_defer(0) == 0
-    assert lib.sast_dw_discard() == 0 and lib.sast_dw_flush(None) == 0 and lib.sast_dw_pending() == 0
-    SF._dw_hold(("x",))
-    assert not SF._DW_HOLD           # nothing is held while deferral is off
+def test_deferred_weight_gradients_are_retired():
+    """deferred weight gradients left the product (tools/experiments/r06_deferred_weight_gradients.patch):
+    no name of the path in the C header, in the package sources or in the built library (its whole image: the dynamic symbol table and
+    the device code objects' kernel names with it), and TrainStep refuses the two keywords bench.py can still pass (no GPU needed)"""
+    from sast_amd import _lib as SL
+    from sast_amd.training import TrainStep
+    needles = ("sast_dw_", "dw_defer", "DwGroup", "gemm_group_kernel")
+    pkg = os.path.join(ROOT, "sast_amd")
+    texts = [os.path.join(ROOT, "include", "sast_hip.h")]
+    for d, dirs, files in os.walk(pkg):
+        dirs[:] = [x for x in dirs if x not in ("build", "__pycache__")]
+        texts += [os.path.join(d, f) for f in files if f.endswith((".py", ".hip", ".cuh", ".h", ".inc"))]
+    assert len(texts) > 40 and os.path.join(pkg, "csrc", "gemm_dispatch.cuh") in texts
+    for path in texts + [SL.lib()._name]:
+        with open(path, "rb") as f:
+            data = f.read()
+        assert not [n for n in needles if n.encode() in data], path
+    assert b"gemm_dual_kernel" in data and b"sast_version" in data       # the search does see kernel and entry-point names
+    for kw in ("defer_dw", "dw_discard"):
+        with pytest.raises(ValueError, match="r06_deferred_weight_gradients.patch"):
+            TrainStep(None, None, **{kw: True})
 
 
 def test_sync_group_forgets_a_destroyed_process_group():
