@@ -450,6 +450,17 @@ typedef struct {
   const uint8_t* flags;                  /* device, [B] */
 } SastSampleZeroDev;
 int sast_zero_samples_dev(const SastSampleZeroDev* a, sast_stream_t stream);
+/* the predicated state commit of a batch whose rows advance at different moments: sample b of dst[i] takes sample b of src[i] where
+ * flags[b] != 0 and keeps every bit otherwise (dst[i], src[i]: [B, sample_floats[i]], n <= 16 pairs in ONE launch).  The flags are read
+ * when the kernel runs.  16-byte copies where both samples are 16-byte aligned, single words otherwise and for the tail. */
+typedef struct {
+  int32_t n, B;
+  float* dst[SAST_ZERO_MAX_TENSORS];
+  const float* src[SAST_ZERO_MAX_TENSORS];
+  size_t sample_floats[SAST_ZERO_MAX_TENSORS];
+  const uint8_t* flags;                  /* device, [B] */
+} SastSampleCommitDev;
+int sast_commit_samples_dev(const SastSampleCommitDev* a, sast_stream_t stream);
 /* dst[i][0 .. floats[i]) = src[i][...] for n <= 16 tensors in ONE launch, a kernel (no memcpy node when captured): the training step
  * hands the final recurrent states back into its input state tensors with it (RNNStates.save_states_and_detach for a replayed step) */
 typedef struct {
@@ -632,6 +643,21 @@ int sast_evqueue_window_bounds(const SastEvQueueArgs* q, const int64_t* ends_us,
  * never drops an event.
  * 2 launches (one thread per row decides and writes the plan; the copy reads only the plan). */
 int sast_evqueue_retire(const SastEvQueueArgs* q, const int64_t* bounds, int T, sast_stream_t stream);
+/* the scheduler contract (2) of the queue assumes, on the device: which of each row's next W duration windows are due, from the row's
+ * carry t_last[s] (call it after sast_evqueue_push on the same stream).  State: next_end int64 [S], the end of the row's next window
+ * (first_end_us >= value at the start of a recording).  Per row s, with D = value and e_k = next_end[s] + k * D:
+ *   reset != NULL and reset[s] != 0: next_end[s] = first_end_us first (the flags given to the push);
+ *   window k is due when t_last[s] > e_k (an event later than its end was pushed), and, with final_flags != NULL and
+ *   final_flags[s] != 0 (the recording is over), also while e_k - D < t_last[s]; due is monotone in k: n_all windows are due, n =
+ *   min(n_all, W) of them are given by this call;
+ *   ends[k * S + s] = e_k for k < n, next_end[s] + (n - 1) * D behind them (the last due end; next_end[s] - D when none is due: the
+ *   window the row gave last, so sast_evqueue_window_bounds / sast_evqueue_retire on `ends` retire nothing new and count no late window);
+ *   due[k * S + s] = k < n;  backlog[s] = n_all - n;  next_end[s] += n * D.
+ * mode must be SAST_EVENT_WINDOW_DURATION and value >= 1 (count windows have no schedule in time: SAST_EINVAL).  ends int64 [W, S],
+ * due uint8 [W, S], backlog int64 [S].  1 launch, one thread per row. */
+int sast_evq_schedule(const SastEvQueueArgs* q, int64_t* next_end, int mode, int64_t value, int64_t first_end_us, int W,
+                          const uint8_t* reset, const uint8_t* final_flags, int64_t* ends, uint8_t* due, int64_t* backlog,
+                          sast_stream_t stream);
 
 /* ---- label front end (csrc/k_labels.hip): the raw Prophesee box records of S recordings side by side -> the filtered labels, the
  * label-frame timestamps, the window-end schedule, the frame -> window map and per-step label tensors, all on the device.  The reference
@@ -904,6 +930,26 @@ int sast_eval_add(const SastEvalArgs* a, sast_stream_t stream);
 size_t sast_eval_sort_ws_bytes(int64_t max_detections);
 int sast_eval_accumulate(const SastEvalArgs* a, sast_stream_t stream);
 int sast_evmerge_append(const SastEvalArgs* dst, const SastEvalArgs* src, sast_stream_t stream);
+
+/* ---- detections as Prophesee box records (csrc/k_eval.hip): what to_prophesee (io/box_loading.py:81-97) makes of one frame's
+ * post-processed detections on the host, written on the device for the S rows of one online step.  A record is 40 bytes, little-endian:
+ *   offset 0 int64 t (the window end), 8 fp32 x = x1, 12 fp32 y = y1, 16 fp32 w = x2 - x1, 20 fp32 h = y2 - y1 (one fp32 subtraction
+ *   each), 24 uint32 class_id (column 6), 28 uint32 track_id = 0, 32 fp32 class_confidence (column 5), 36 four zero bytes.
+ * Row s with due[s] != 0: the first m = min(n_det[s], max_det) rows of det[s] (already by decreasing score) become records
+ * [s][0 .. m), counts[s] = m, and *truncated += n_det[s] - m.  Any other row: counts[s] = 0.  No row of det past n_det[s] is read
+ * (they are uninitialised), no record past counts[s] is written.  1 launch, one wave per row. */
+typedef struct {
+  const float* det;        /* [S, A, 7] (x1, y1, x2, y2, obj_conf, class_conf, class_pred): sast_postprocess's out */
+  const int32_t* n_det;    /* [S] */
+  const int64_t* ends;     /* [S]: the rows' window ends */
+  const uint8_t* due;      /* [S] */
+  uint8_t* records;        /* [S, max_det, 40], 8-byte aligned */
+  int32_t* counts;         /* [S] */
+  int32_t* truncated;      /* [1], ACCUMULATED */
+  int32_t S, A, max_det, reserved;
+} SastDetExportArgs;
+#define SAST_DET_RECORD_BYTES 40
+int sast_detections_export(const SastDetExportArgs* a, sast_stream_t stream);
 
 /* ---- tuning knobs.  Every SAST_* environment variable the library reads (tile / split / launch-shape choices, all defaulting to the
  * measured-best setting: DESIGN.md section 7) goes through one registry: the value is read from the environment at first use and cached;

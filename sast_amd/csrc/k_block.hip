@@ -294,6 +294,12 @@ int sast_zero_samples_dev(const SastSampleZeroDev* a, sast_stream_t stream) { SA
   if (a->n == 0) return SAST_OK;
   return zero_samples_dev_launch(*a, (hipStream_t)stream);
 }
+int sast_commit_samples_dev(const SastSampleCommitDev* a, sast_stream_t stream) { SAST_ENTRY();
+  if (!a || !a->flags || a->n < 0 || a->n > SAST_ZERO_MAX_TENSORS || a->B < 1 || a->B > 256) return SAST_EINVAL;
+  for (int i = 0; i < a->n; ++i) if (!a->dst[i] || !a->src[i] || !a->sample_floats[i]) return SAST_EINVAL;
+  if (a->n == 0) return SAST_OK;
+  return commit_samples_dev_launch(*a, (hipStream_t)stream);
+}
 int sast_copy_tensors(const SastTensorCopy* a, sast_stream_t stream) { SAST_ENTRY();
   if (!a || a->n < 0 || a->n > SAST_ZERO_MAX_TENSORS) return SAST_EINVAL;
   for (int i = 0; i < a->n; ++i) if (!a->dst[i] || !a->src[i] || !a->floats[i]) return SAST_EINVAL;

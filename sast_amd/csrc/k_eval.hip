@@ -654,6 +654,33 @@ bool eval_args_ok(const SastEvalArgs* a) {
          a->max_labels_per_frame <= EV_MAX_LABELS;
 }
 
+// to_prophesee's detection half (io/box_loading.py:81-97) for the rows of one online step, one wave per row: lane j writes records
+// j, j + 64, ... of the row.  A record is five 8-byte words: t | x, y | w, h | class_id, track_id = 0 | class_confidence, 0.
+// w and h are one fp32 subtraction each, as numpy's (this file is built with -ffp-contract=off).  n_det is data: it is clamped to the A
+// rows the detections hold before any of them is read, and no row at or past it is read at all.
+__global__ __launch_bounds__(64) void detections_export_kernel(SastDetExportArgs a) {
+  const int s = blockIdx.x;
+  const int n = min(max(a.n_det[s], 0), a.A);
+  const int m = a.due[s] ? min(n, a.max_det) : 0;
+  const unsigned long long t = (unsigned long long)a.ends[s];
+  const float* __restrict__ det = a.det + (size_t)s * a.A * 7;
+  unsigned long long* __restrict__ rec = reinterpret_cast<unsigned long long*>(a.records + (size_t)s * a.max_det * SAST_DET_RECORD_BYTES);
+  for (int i = threadIdx.x; i < m; i += 64) {
+    const float* r = det + (size_t)i * 7;
+    const float x1 = r[0], y1 = r[1], w = r[2] - x1, h = r[3] - y1;
+    unsigned long long* o = rec + (size_t)i * (SAST_DET_RECORD_BYTES / 8);
+    o[0] = t;
+    o[1] = (unsigned long long)__float_as_uint(x1) | ((unsigned long long)__float_as_uint(y1) << 32);
+    o[2] = (unsigned long long)__float_as_uint(w) | ((unsigned long long)__float_as_uint(h) << 32);
+    o[3] = (unsigned long long)(unsigned)r[6];
+    o[4] = (unsigned long long)__float_as_uint(r[5]);
+  }
+  if (threadIdx.x == 0) {
+    a.counts[s] = m;
+    if (a.due[s] && n > m) atomicAdd(a.truncated, n - m);
+  }
+}
+
 }  // namespace
 }  // namespace sast
 
@@ -742,6 +769,16 @@ int sast_evmerge_append(const SastEvalArgs* dst, const SastEvalArgs* src, sast_s
   const unsigned blocks = (unsigned)std::min<long long>((most + 255) / 256, 4096);   // sized from src's capacities; the kernel strides
   SAST_LAUNCH(evmerge_copy_kernel, dim3(blocks), dim3(256), 0, st, *dst, *src);
   SAST_LAUNCH(evmerge_publish_kernel, dim3(1), dim3(64), 0, st, *dst, *src);
+  SAST_CHECK_LAUNCH();
+  return SAST_OK;
+}
+
+int sast_detections_export(const SastDetExportArgs* a, sast_stream_t stream) {
+  SAST_ENTRY();
+  if (!a || !a->det || !a->n_det || !a->ends || !a->due || !a->records || !a->counts || !a->truncated || a->S < 1 || a->S > 65535 ||
+      a->A < 1 || a->max_det < 1 || (reinterpret_cast<uintptr_t>(a->records) & 7))
+    return SAST_EINVAL;
+  SAST_LAUNCH(sast::detections_export_kernel, dim3((unsigned)a->S), dim3(64), 0, (hipStream_t)stream, *a);
   SAST_CHECK_LAUNCH();
   return SAST_OK;
 }

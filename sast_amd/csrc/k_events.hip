@@ -709,6 +709,30 @@ __global__ __launch_bounds__(EV_THREADS) void evq_move_kernel(SastEvQueueArgs q,
   }
 }
 
+// the scheduler of duration windows, one thread per row: window k of this call ends at e_k = next_end + k * D and is due once an event
+// later than e_k was pushed (t_last > e_k), or, when the recording is over, while it still holds an event time (e_k - D < t_last).
+// Both are monotone in k, so the due windows are counted in closed form: the k >= 0 with lo + k * D < t_last, lo = next_end or
+// next_end - D.  Steps behind the due ones repeat the last end the row gave, which asks the queue for nothing new.
+__global__ void evq_schedule_kernel(SastEvQueueArgs q, long long* next_end, long long D, long long first_end, int W,
+                                    const unsigned char* reset, const unsigned char* final_flags, long long* ends, unsigned char* due,
+                                    long long* backlog) {
+  const int s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= q.S) return;
+  const long long ne = reset && reset[s] ? first_end : next_end[s];
+  const long long tl = (long long)q.t_last[s];
+  const long long lo = final_flags && final_flags[s] ? ne - D : ne;
+  const long long n_all = tl > lo ? (tl - lo - 1) / D + 1 : 0LL;
+  const long long n = min(n_all, (long long)W);
+  const long long held = ne + (n - 1) * D;
+  for (int k = 0; k < W; ++k) {
+    const size_t w = (size_t)k * q.S + s;
+    ends[w] = k < n ? ne + k * D : held;
+    due[w] = k < n ? 1 : 0;
+  }
+  backlog[s] = n_all - n;
+  next_end[s] = ne + n * D;
+}
+
 bool evq_args(const SastEvQueueArgs* q) {
   return q && q->x && q->y && q->p && q->t && q->head && q->count && q->t_last && q->retired && q->retired_t && q->err && q->ws &&
          q->S >= 1 && q->S <= 65535 && q->capacity >= 1 && (long long)q->S * q->capacity <= INT_MAX;
@@ -836,6 +860,21 @@ int sast_evqueue_retire(const SastEvQueueArgs* q, const int64_t* bounds, int T, 
   // at most half a row moves (live <= head)
   SAST_LAUNCH(sast::evq_move_kernel, dim3((unsigned)sast::evq_blocks(q->capacity / 2), (unsigned)q->S), dim3(sast::EV_THREADS), 0, st, *q,
               (const long long*)ws);
+  SAST_CHECK_LAUNCH();
+  return SAST_OK;
+}
+
+int sast_evq_schedule(const SastEvQueueArgs* q, int64_t* next_end, int mode, int64_t value, int64_t first_end_us, int W,
+                          const uint8_t* reset, const uint8_t* final_flags, int64_t* ends, uint8_t* due, int64_t* backlog,
+                          sast_stream_t stream) {
+  SAST_ENTRY();
+  if (!sast::evq_args(q) || !next_end || !ends || !due || !backlog || mode != SAST_EVENT_WINDOW_DURATION || value < 1 ||
+      first_end_us < value || W < 1 || (long long)q->S * W > INT_MAX)
+    return SAST_EINVAL;
+  SAST_LAUNCH(sast::evq_schedule_kernel, dim3((q->S + 63) / 64), dim3(64), 0, (hipStream_t)stream, *q, reinterpret_cast<long long*>(next_end),
+              (long long)value, (long long)first_end_us, W, reinterpret_cast<const unsigned char*>(reset),
+              reinterpret_cast<const unsigned char*>(final_flags), reinterpret_cast<long long*>(ends), reinterpret_cast<unsigned char*>(due),
+              reinterpret_cast<long long*>(backlog));
   SAST_CHECK_LAUNCH();
   return SAST_OK;
 }

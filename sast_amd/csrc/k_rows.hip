@@ -1104,6 +1104,20 @@ int zero_samples_dev_launch(const SastSampleZeroDev& a, hipStream_t st) {
   SAST_CHECK_LAUNCH();
   return SAST_OK;
 }
+// the predicated commit of a batch whose rows advance at different moments (sast_amd/online.py): sample b of dst takes sample b of src
+// where flags[b] != 0.  Same grid as the reset above; the flag is read once per workgroup and the branch is workgroup-uniform.
+__global__ __launch_bounds__(256) void commit_samples_dev_kernel(SastSampleCommitDev a) {
+  if (!a.flags[blockIdx.y]) return;
+  const size_t n = a.sample_floats[blockIdx.z], off = (size_t)blockIdx.y * n;
+  move_row(a.dst[blockIdx.z] + off, a.src[blockIdx.z] + off, n);
+}
+int commit_samples_dev_launch(const SastSampleCommitDev& a, hipStream_t st) {
+  size_t most = 0;
+  for (int i = 0; i < a.n; ++i) most = a.sample_floats[i] > most ? a.sample_floats[i] : most;
+  SAST_LAUNCH(commit_samples_dev_kernel, dim3(row_blocks(most), a.B, a.n), dim3(256), 0, st, a);
+  SAST_CHECK_LAUNCH();
+  return SAST_OK;
+}
 // several whole tensors in one launch (the recurrent states handed back into the step's input tensors): grid (share, tensor)
 __global__ __launch_bounds__(256) void copy_tensors_kernel(SastTensorCopy a) {
   move_row(a.dst[blockIdx.y], a.src[blockIdx.y], a.floats[blockIdx.y]);

@@ -56,6 +56,7 @@ int select_table_launch(const uint8_t* labelled, int T, int B, int n_out, int32_
                         hipStream_t st);
 int sample_gather_dev_launch(const SastSampleGatherDev& a, bool backward, hipStream_t st);
 int zero_samples_dev_launch(const SastSampleZeroDev& a, hipStream_t st);
+int commit_samples_dev_launch(const SastSampleCommitDev& a, hipStream_t st);
 int copy_tensors_launch(const SastTensorCopy& a, hipStream_t st);
 
 // k_select.hip

@@ -1796,6 +1796,39 @@ def zero_samples_dev(tensors, flags: torch.Tensor):
 
 
 @torch.no_grad()
+def commit_samples_dev(dsts, srcs, flags: torch.Tensor):
+    """the predicated commit of a batch whose rows advance at different moments: sample b of every dsts[i] takes sample b of srcs[i] where
+    flags[b] != 0 (uint8 / bool [B]) and keeps every bit otherwise.  The tensors `zero_samples_dev` takes (dense fp32, contiguous or
+    channels-last 4-D, batch outermost, B <= 256), each pair with one shape and memory layout; one launch for up to 16 pairs, the flags
+    are read when the kernel runs (a replayed graph follows the flags of the replay)."""
+    dsts, srcs = list(dsts), list(srcs)
+    if len(dsts) != len(srcs):
+        raise RuntimeError("sast_amd: commit_samples_dev needs as many destinations as sources")
+    if not dsts:
+        return dsts
+    B = dsts[0].shape[0]
+    for d, s in zip(dsts, srcs):
+        if d.dtype != torch.float32 or s.dtype != torch.float32 or d.dim() < 2 or d.shape[0] != B or d[0].numel() < 1 or d.shape != s.shape or \
+                d.stride() != s.stride() or not (d.is_contiguous() or (d.dim() == 4 and d.permute(0, 2, 3, 1).is_contiguous())):
+            raise RuntimeError("sast_amd: commit_samples_dev needs pairs of dense fp32 tensors with one shape and memory layout and the same "
+                               "batch as their outermost dimension")
+    if B > 256:
+        raise RuntimeError("sast_amd: commit_samples_dev supports batch <= 256")
+    _check_flags(flags, B, "commit_samples_dev")
+    _need_gpu(flags, *dsts, *srcs)
+    if any(x.device != flags.device for x in dsts + srcs):
+        raise ValueError("sast_amd: commit_samples_dev needs the tensors and the flags on one device")
+    for i0 in range(0, len(dsts), L.ZERO_MAX_TENSORS):
+        a = L.SastSampleCommitDev()
+        pairs = list(zip(dsts[i0:i0 + L.ZERO_MAX_TENSORS], srcs[i0:i0 + L.ZERO_MAX_TENSORS]))
+        a.n, a.B, a.flags = len(pairs), B, flags.data_ptr()
+        for i, (d, s) in enumerate(pairs):
+            a.dst[i], a.src[i], a.sample_floats[i] = d.data_ptr(), s.data_ptr(), d[0].numel()
+        L.check(L.lib().sast_commit_samples_dev(C.byref(a), _stream()), "commit_samples_dev")
+    return dsts
+
+
+@torch.no_grad()
 def copy_tensors(dsts, srcs) -> None:
     """dsts[i] <- srcs[i] (dense fp32 tensors of equal shapes and memory layouts), one kernel launch for up to 16 pairs"""
     dsts, srcs = list(dsts), list(srcs)
