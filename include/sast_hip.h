@@ -659,6 +659,41 @@ int sast_evq_schedule(const SastEvQueueArgs* q, int64_t* next_end, int mode, int
                           const uint8_t* reset, const uint8_t* final_flags, int64_t* ends, uint8_t* due, int64_t* backlog,
                           sast_stream_t stream);
 
+/* ---- raw sensor words (csrc/k_evt3.hip): Prophesee EVT 3.0, the 16-bit little-endian word stream a Gen4 / 1 Mpx sensor puts on the
+ * wire, decoded on the device into the columns sast_evqueue_push takes.  The reference has no such stage (it reads .dat / .npy
+ * files, utils/evaluation/prophesee/io/); the rule below is this project's contract, and parity with the Metavision SDK's decoder is
+ * unpinned (the SDK is not a dependency).  type = w >> 12, v = w & 0xFFF; per stream the state y, base_x, vpol, low, high, wraps,
+ * have_high, all 0 after a reset:
+ *   0x0 EVT_ADDR_Y    y = v & 0x7FF (bit 11 ignored)
+ *   0x2 EVT_ADDR_X    one event (x = v & 0x7FF, y, p = v >> 11, t)
+ *   0x3 VECT_BASE_X   base_x = v & 0x7FF, vpol = v >> 11
+ *   0x4 VECT_12       for every set bit i of v, ascending: an event (base_x + i, y, vpol, t); then base_x += 12
+ *   0x5 VECT_8        the same over bits 0..7 (bits 8-11 ignored); then base_x += 8
+ *   0x6 EVT_TIME_LOW  low = v
+ *   0x8 EVT_TIME_HIGH have_high and high - v >= 2048: wraps += 1; then high = v, have_high = 1
+ *   0x7, 0xA, 0xE, 0xF  valid, no effect;   0x1, 0x9, 0xB, 0xC, 0xD  no effect, counted as unknown words
+ * t = wraps * 2^24 + high * 4096 + low (microseconds).  An event met while have_high is 0 is not given, it is counted.  Events come
+ * out in word order, inside a vector word by ascending bit.  base_x may run past 2047: it stops growing at 2^30, and x is stored as
+ * int16 with saturation, so such an event stays outside the sensor (the frame kernels count it invalid).  The state after a chunk is
+ * the state before the next one: a stream cut into chunks at any word gives the events, counters and state of the whole stream. */
+#define SAST_EVT3_STATE_WORDS 8       /* a row of `state`: y, base_x, vpol, low, high, wraps, have_high, 0 */
+#define SAST_EVT3_BLOCK_WORDS 2048    /* words a workgroup takes in one step; a row gets ceil(chunk_words / this) workgroups ... */
+#define SAST_EVT3_MAX_BLOCKS 256      /* ... at most this many, which then take several steps each */
+/* bytes of the decode's workspace (one summary per row for the state and for every workgroup).  0: S < 1 or S > 65535.  Host only. */
+size_t sast_evt3_ws_bytes(int S);
+/* per row s: with reset != NULL and reset[s] != 0 the row's state is zeroed first.  Then the first n_s = min(max(counts[s], 0),
+ * chunk_words) words of words[s] (16-bit words [S, chunk_words]) are decoded: the events go to x, y, p (int16) and t (int64)
+ * [S, max_events] from column 0 on, out_counts[s] = min(events, max_events) (of a row with more, the first max_events are kept),
+ * state[s] (int64 [S, SAST_EVT3_STATE_WORDS]) becomes the state after the chunk.  err, int32 [3], ACCUMULATED: [0] events before
+ * the first TIME_HIGH, [1] unknown words, [2] events dropped because the row's staging was full.  max_events = 12 * chunk_words never
+ * drops.  Row s of the workgroup grid (blocks, S) splits its n_s words into `blocks` pieces of a multiple of 8 words.
+ * S * chunk_words and S * max_events <= 2^31 - 1, chunk_words <= (2^31 - 1) / 12, max_events >= 1.  2 launches (one summary per
+ * workgroup; fold the summaries in front + decode + write, the row's last workgroup writes state, count and counters): no workgroup
+ * reads what another one writes in the same launch, and nothing has to be put back for a graph replay. */
+int sast_evt3_decode(const void* words, const int64_t* counts, int64_t chunk_words, int S, const uint8_t* reset, int64_t* state,
+                     void* ws, int16_t* x, int16_t* y, int16_t* p, int64_t* t, int64_t max_events, int64_t* out_counts, int32_t* err,
+                     sast_stream_t stream);
+
 /* ---- label front end (csrc/k_labels.hip): the raw Prophesee box records of S recordings side by side -> the filtered labels, the
  * label-frame timestamps, the window-end schedule, the frame -> window map and per-step label tensors, all on the device.  The reference
  * does this offline, per recording: apply_filters, get_base_delta_ts_for_labels_us and labels_and_ev_repr_timestamps of

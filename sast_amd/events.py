@@ -15,8 +15,9 @@ The reference's second representation, MixedDensityEventStack (representations.p
 binned by the logarithm of their age and accumulated over the bins), is `MixedDensityEventStack` here, and
 `representation="mixed_density"` of `EventFrames` / `EventStreams`: the same windows, carries and error counters, int8 frames.
 
-`EventQueue` keeps the events that later windows still need on the device, so a host pushes chunks cut at arbitrary points (columns, or
-Prophesee's packed Event2D records) and gets the frames `EventStreams` gives for the whole recording.
+`EventQueue` keeps the events that later windows still need on the device, so a host pushes chunks cut at arbitrary points (columns,
+Prophesee's packed Event2D records, or the raw EVT 3.0 words of a sensor) and gets the frames `EventStreams` gives for the whole
+recording.  `Evt3Decoder` is the stateful decode of those words alone (csrc/k_evt3.hip).
 
 There is no CPU path: CPU tensors raise the library's "no CPU fallback" error.
 """
@@ -443,6 +444,107 @@ class EventStreams(_Windowed):
         return out
 
 
+_WORD_DTYPES = tuple(d for d in (torch.int16, getattr(torch, "uint16", None)) if d is not None)
+
+
+class Evt3Decoder:
+    """Prophesee EVT 3.0 sensor words -> event columns on the device (csrc/k_evt3.hip; the format table and the decode rule are in
+    include/sast_hip.h and INTEGRATION.md §3b; parity with the Metavision SDK's decoder is unpinned, the SDK is not a dependency).
+
+    dec = Evt3Decoder(num_streams, max_events=None)
+    x, y, p, t, n = dec(words, counts, reset=None)
+      words: int16 / uint16 [S, chunk_words], the raw little-endian 16-bit words of S sensors side by side, cut anywhere (the caller
+        skips a .raw file's ASCII header); counts: int64 [S], the words at the head of each row; reset: uint8 / bool [S], non-zero for
+        the rows whose decoder state (row, vector base, time) is zeroed before this chunk: a new recording.
+      -> x, y, p int16 [S, max_events], t int64 [S, max_events] (microseconds, wraps of the 24-bit sensor clock unrolled), n int64 [S]
+        the events at the head of each row: what `EventQueue.push` / `EventStreams` take.  The tensors are the decoder's staging
+        columns: the next call overwrites them.
+    The state after a chunk is the state before the next one, per row: a stream decoded in chunks cut at any word gives the events of
+    the stream decoded whole.  max_events: the events one row's chunk may give (default 12 * chunk_words, which can never drop one);
+    of a row with more, the first max_events are kept and the rest counted.  `errors()` -> (events before the first TIME_HIGH, unknown
+    words, events dropped because the staging was full), accumulated until `reset()`; `reset(streams=None)` zeroes the decoder state of
+    the rows (default: all, and the counters).  `state` is int64 [S, 8]: y, base_x, vpol, low, high, wraps, have_high, 0.
+    The state and the staging columns are allocated by the first un-captured call, never during capture; afterwards nothing is
+    allocated and nothing synchronises.  One call is 2 launches whatever S and the sizes are."""
+
+    DECODE_LAUNCHES = 2
+
+    def __init__(self, num_streams: int, max_events: Optional[int] = None):
+        if int(num_streams) < 1 or int(num_streams) > 65535:
+            raise ValueError("sast_amd.events: num_streams must be in 1 .. 65535")
+        if max_events is not None and int(max_events) < 1:
+            raise ValueError("sast_amd.events: max_events must be >= 1 (or None)")
+        self.num_streams = int(num_streams)
+        self.max_events = None if max_events is None else int(max_events)
+        if self.max_events is not None and self.num_streams * self.max_events > 2 ** 31 - 1:
+            raise ValueError("sast_amd.events: num_streams * max_events must be below 2^31")
+        self.state = self.err = self.counts = self.x = self.y = self.p = self.t = self._ws = None
+
+    def _buffers(self, dev, chunk_words: int):
+        S = self.num_streams
+        if self.state is not None and self.state.device != dev:
+            raise ValueError(f"sast_amd.events: the decoder's state lives on {self.state.device}, the call's tensors on {dev}")
+        if self.state is None:
+            _not_capturing()
+            self.state = torch.zeros(S, L.EVT3_STATE_WORDS, dtype=torch.int64, device=dev)
+            self.err = torch.zeros(3, dtype=torch.int32, device=dev)
+            self.counts = torch.zeros(S, dtype=torch.int64, device=dev)
+            self._ws = torch.zeros(int(L.lib().sast_evt3_ws_bytes(S)), dtype=torch.uint8, device=dev)
+        need = self.max_events if self.max_events is not None else max(12 * chunk_words, 1)
+        if self.x is None or self.x.shape[1] < need:
+            _not_capturing()
+            if S * need > 2 ** 31 - 1:
+                raise ValueError("sast_amd.events: num_streams * max_events must be below 2^31")
+            self.x, self.y, self.p = (torch.zeros(S, need, dtype=torch.int16, device=dev) for _ in range(3))
+            self.t = torch.zeros(S, need, dtype=torch.int64, device=dev)
+
+    def errors(self) -> Tuple[int, int, int]:
+        """(events before the first TIME_HIGH, unknown words, events dropped for lack of staging) since the last reset() (synchronises)"""
+        return (0, 0, 0) if self.err is None else tuple(int(v) for v in self.err.tolist())
+
+    def reset(self, streams=None):
+        """new recordings, from the host: the decoder state of `streams` (default: all of them) back to zero; with streams=None the
+        counters are cleared as well"""
+        if self.state is None:
+            return
+        if streams is None:
+            self.state.zero_()
+            self.err.zero_()
+            return
+        idx = [int(s) for s in streams]
+        if any(s < 0 or s >= self.num_streams for s in idx):
+            raise ValueError(f"sast_amd.events: streams must be in 0 .. {self.num_streams - 1}")
+        if idx:
+            self.state[torch.tensor(idx, dtype=torch.int64, device=self.state.device)] = 0
+
+    def __call__(self, words: torch.Tensor, counts: torch.Tensor, reset: Optional[torch.Tensor] = None):
+        S = self.num_streams
+        if not torch.is_tensor(words) or words.dim() != 2 or words.shape[0] != S:
+            raise ValueError(f"sast_amd.events: words must be [num_streams={S}, chunk words], got shape "
+                             f"{tuple(words.shape) if torch.is_tensor(words) else type(words)}")
+        if words.dtype not in _WORD_DTYPES:
+            raise TypeError(f"sast_amd.events: words must be torch.int16 or torch.uint16 (one EVT 3.0 word each), got {words.dtype}")
+        if not words.is_contiguous():
+            raise ValueError("sast_amd.events: words must be contiguous")
+        if counts.dtype != torch.int64 or tuple(counts.shape) != (S,) or not counts.is_contiguous():
+            raise ValueError(f"sast_amd.events: counts must be a contiguous int64 tensor of shape [{S}]")
+        if reset is not None and (reset.dtype not in (torch.uint8, torch.bool) or tuple(reset.shape) != (S,) or not reset.is_contiguous()):
+            raise ValueError(f"sast_amd.events: reset must be a contiguous uint8 or bool tensor of shape [{S}]")
+        chunk_words = words.shape[1]
+        if S * chunk_words > 2 ** 31 - 1 or 12 * chunk_words > 2 ** 31 - 1:
+            raise ValueError("sast_amd.events: num_streams * chunk words and 12 * chunk words must be below 2^31")
+        _need_gpu(words, counts, reset)
+        if len({c.device for c in [words, counts] + ([reset] if reset is not None else [])}) != 1:
+            raise ValueError("sast_amd.events: words, counts and reset must be on the same device")
+        self._buffers(counts.device, chunk_words)
+        # an empty chunk has no storage: any valid device pointer will do, the kernels read no word
+        L.check(L.lib().sast_evt3_decode(words.data_ptr() or self.t.data_ptr(), counts.data_ptr(), chunk_words, S,
+                                         None if reset is None else reset.data_ptr(), self.state.data_ptr(), self._ws.data_ptr(),
+                                         self.x.data_ptr(), self.y.data_ptr(), self.p.data_ptr(), self.t.data_ptr(), self.x.shape[1],
+                                         self.counts.data_ptr(), self.err.data_ptr(), _stream()), "evt3_decode")
+        return self.x, self.y, self.p, self.t, self.counts
+
+
 _QUEUE_ERRORS = ("{} invalid events (x or y outside the sensor, or a polarity outside 0..1); they were skipped",
                  "{} windows hold more events than window_capacity; they were left empty",
                  "{} events were dropped: their row of the queue was full (capacity >= 2 x the row's live events right after a `frames` call + all events pushed between two `frames` calls never drops)",
@@ -462,6 +564,9 @@ class EventQueue(_Windowed):
                                                 kernel: no unpacked copy exists.  The 32-bit clock wraps after ~71.6 minutes; it is
                                                 NOT unwrapped (the reference does not either): after a wrap the time correction holds
                                                 every timestamp at the maximum before it.
+    q.push_evt3(words, counts, reset=None)      int16 / uint16 [S, chunk_words]: raw EVT 3.0 sensor words, counts in words, cut at any
+                                                word (`Evt3Decoder`: the stateful decode runs on the device, 2 launches, in front of
+                                                the append); `evt3_errors()` gives the decoder's three counters.
     frames = q.frames(ends_us, out=None, check=False)    ends_us int64 [S] or [T, S] -> frames as `EventStreams` returns them
     q.reset(streams=None); q.errors(); q.get_shape()
 
@@ -501,6 +606,7 @@ class EventQueue(_Windowed):
     frames (1 window search, 4 frame launches, 2 retire: plan, compaction)."""
 
     PUSH_LAUNCHES = 2
+    PUSH_EVT3_LAUNCHES = Evt3Decoder.DECODE_LAUNCHES + PUSH_LAUNCHES
     FRAMES_LAUNCHES = 7
 
     def __init__(self, num_streams: int, capacity: int, height: int, width: int, bins: int = 10, count_cutoff: Optional[int] = 10,
@@ -519,6 +625,7 @@ class EventQueue(_Windowed):
         self.num_streams, self.capacity = int(num_streams), int(capacity)
         self.x = self.y = self.p = self.t = self.head = self.count = self.retired = self.retired_t = None
         self._args = None
+        self.evt3: Optional[Evt3Decoder] = None       # made by the first push_evt3
 
     def _storage(self, dev):
         """the queue's state on `dev` (allocated by the first ordinary call)"""
@@ -546,6 +653,8 @@ class EventQueue(_Windowed):
     def reset(self, streams=None):
         """new recordings, from the host: rows `streams` (default: all of them) are emptied, their carry and retirement record zeroed;
         with streams=None the error counters are cleared as well"""
+        if self.evt3 is not None:
+            self.evt3.reset(streams)
         if self._args is None:
             return
         state = (self.head, self.count, self.t_last, self.retired, self.retired_t)
@@ -606,6 +715,25 @@ class EventQueue(_Windowed):
             raise ValueError("sast_amd.events: records must be contiguous")
         self._counts_reset(counts, reset)
         self._push([records.data_ptr()] * 4, [L.EVQUEUE_DT_DAT] * 4, records.shape[1], counts, reset, [records])
+
+    def push_evt3(self, words: torch.Tensor, counts: torch.Tensor, reset: Optional[torch.Tensor] = None,
+                  max_events: Optional[int] = None) -> None:
+        """raw EVT 3.0 sensor words (int16 / uint16 [S, chunk_words], counts int64 [S] in WORDS) as `Evt3Decoder` takes them: the
+        decode (2 launches) into the decoder's staging columns, then the append of `push` on those columns and the decoder's device-side
+        event counts (2 launches).  reset[s] != 0 zeroes row s's decoder state and empties its queue row together.  max_events: the
+        decoder's staging per row, fixed by the first call (default 12 * chunk_words: never drops)."""
+        if self.evt3 is None:
+            self.evt3 = Evt3Decoder(self.num_streams, max_events)
+        elif max_events is not None and int(max_events) != self.evt3.max_events:
+            raise ValueError(f"sast_amd.events: the queue's decoder was made with max_events={self.evt3.max_events}, got {max_events}")
+        self._counts_reset(counts, reset)
+        x, y, p, t, n = self.evt3(words, counts, reset)
+        self.push(x, y, p, t, n, reset)
+
+    def evt3_errors(self) -> Tuple[int, int, int]:
+        """the decoder's counters of `push_evt3`: (events before the first TIME_HIGH, unknown words, events dropped for lack of
+        staging) (synchronises); `errors()` keeps the queue's four"""
+        return (0, 0, 0) if self.evt3 is None else self.evt3.errors()
 
     def frames(self, ends_us: torch.Tensor, out: Optional[torch.Tensor] = None, check: bool = False) -> torch.Tensor:
         S, cap = self.num_streams, self.capacity

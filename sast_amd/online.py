@@ -91,10 +91,11 @@ class OnlineDetector:
     """od = OnlineDetector(detector, queue, windows_per_step=W, max_det=100, conf_thre=0.1, nms_thre=0.45, first_end_us=None)
       detector: a `YoloXDetector` in eval mode; queue: an `EventQueue` with duration windows (duration_us = D) for S <= 256 streams;
       first_end_us: the end of every recording's first window (default D, must be >= D).
-    od.push(x, y, p, t, counts, reset=None, final=None) / od.push_dat(records, counts, reset=None, final=None)
-      the chunk of `EventQueue.push` / `push_dat`; reset uint8 / bool [S]: the flagged rows start a new recording with this chunk (queue
-      row, recurrent state and schedule start over); final uint8 / bool [S]: the flagged recordings are over, their last windows are
-      given although no later event will come.
+    od.push(x, y, p, t, counts, reset=None, final=None) / od.push_dat(records, counts, reset=None, final=None) /
+    od.push_evt3(words, counts, reset=None, final=None)
+      the chunk of `EventQueue.push` / `push_dat` / `push_evt3` (raw EVT 3.0 sensor words, counts in words); reset uint8 / bool [S]:
+      the flagged rows start a new recording with this chunk (queue row, recurrent state and schedule start over); final uint8 / bool
+      [S]: the flagged recordings are over, their last windows are given although no later event will come.
     od.poll() -> the finished steps' detections, oldest first: a list of (stream, numpy array of `labels.BBOX_DTYPE`), one entry per due
       window (an empty array for a window without detections; `t` of every record is the window's end).  Never waits: steps whose
       copy has not landed stay pending.  od.drain() waits for all of them.
@@ -103,11 +104,11 @@ class OnlineDetector:
     od.errors() -> (invalid events, windows over capacity, dropped events, late windows, detections cut by max_det, windows due but
       not yet given after the last push) (synchronises).
 
-    One push, whatever the data: queue push (2 launches); `zero_samples_dev` of the held states by `reset`; the schedule (1 launch) ->
-    ends, due [W, S]; `queue.frames(ends)` (7 launches); then for k < W the detector forward on frames[k] with the held states,
-    `commit_samples_dev(held, new, due[k])`, `postprocess_padded` and the record export.  A row whose window k is not due runs on the
-    frame of the last window it gave and its new (h, c) is dropped, so its state is bit for bit what it was.  More than W due windows
-    of a row stay in `backlog` and come out of the following pushes (an empty chunk will do).
+    One push, whatever the data: queue push (2 launches; 4 for push_evt3, the decode in front); `zero_samples_dev` of the held states
+    by `reset`; the schedule (1 launch) -> ends, due [W, S]; `queue.frames(ends)` (7 launches); then for k < W the detector forward on
+    frames[k] with the held states, `commit_samples_dev(held, new, due[k])`, `postprocess_padded` and the record export.  A row whose
+    window k is not due runs on the frame of the last window it gave and its new (h, c) is dropped, so its state is bit for bit what
+    it was.  More than W due windows of a row stay in `backlog` and come out of the following pushes (an empty chunk will do).
     Results: ends, due, counts and records lie in one device buffer that one asynchronous copy moves into one of two pinned host slots,
     with an event behind it.  The copy stays OUTSIDE the captured graph (replay() issues it after the graph), so one graph serves both
     slots.  A third push without a poll in between has no free slot: it waits for the oldest step and keeps its result for the next
@@ -216,6 +217,10 @@ class OnlineDetector:
     def push_dat(self, records: torch.Tensor, counts: torch.Tensor, reset: Optional[torch.Tensor] = None,
                  final: Optional[torch.Tensor] = None) -> None:
         self._step(lambda c, r: self.queue.push_dat(records, c, r), (records,), counts, reset, final)
+
+    def push_evt3(self, words: torch.Tensor, counts: torch.Tensor, reset: Optional[torch.Tensor] = None,
+                  final: Optional[torch.Tensor] = None) -> None:
+        self._step(lambda c, r: self.queue.push_evt3(words, c, r), (words,), counts, reset, final)
 
     # ------------------------------------------------------------------------------------------------------------------ graph
     def capture(self) -> None:
