@@ -24,6 +24,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from ._frontend import not_capturing, same_device
 from .functional import _need_gpu, _stream
 
 NO_LABEL_WARN_MSG = 'No Labels found. This can lead to a crash and should not happen often.'
@@ -291,8 +292,7 @@ class SpatialAugmentor:
             self._joined._device_params(dev)                  # this part's params are its rows of the joined tensor
             return self.params
         if self.params is None or self.params.device != dev:
-            if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("sast_amd.augment: one un-captured warm-up call is needed before graph capture")
+            not_capturing("augment")
             self.params = torch.from_numpy(self._host).to(dev)
         return self.params
 
@@ -326,8 +326,7 @@ class SpatialAugmentor:
             raise TypeError("sast_amd.augment: labels must be fp32 [T, B, M, 7] or [B, M, 7]")
         if counts.dtype != torch.int32 or counts.shape != labels.shape[:-2]:
             raise TypeError("sast_amd.augment: counts must be int32 with the labels' leading shape")
-        if labels.device != frames.device or counts.device != frames.device:
-            raise ValueError("sast_amd.augment: frames, labels and counts must be on the same device")
+        same_device("augment", "frames, labels and counts", frames, labels, counts)
         labels, counts = labels.contiguous(), counts.contiguous()
         M = labels.shape[-2]
         NL = counts.numel()
@@ -384,8 +383,7 @@ class JoinedAugmentor:
 
     def _device_params(self, dev) -> torch.Tensor:
         if self.params is None or self.params.device != dev:
-            if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("sast_amd.augment: one un-captured warm-up call is needed before graph capture")
+            not_capturing("augment")
             self.params = torch.from_numpy(self._host).to(dev)
             for p, o in zip(self.parts, self.offsets):
                 p.params = self.params[o:o + p.batch_size]    # a contiguous view: the part's uploads rewrite its rows only

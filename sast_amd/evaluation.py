@@ -32,6 +32,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from ._frontend import not_capturing, same_device
 from .functional import _need_gpu, _stream
 
 OUT_KEYS = ('AP', 'AP_50', 'AP_75', 'AP_S', 'AP_M', 'AP_L')   # coco_eval.py:109
@@ -81,8 +82,7 @@ class PropheseeEvaluator:
 
     # ------------------------------------------------------------------------------------------------------------------ buffers
     def _allocate(self, dev: torch.device):
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("sast_amd.evaluation: one un-captured call is needed before graph capture (it allocates the buffers)")
+        not_capturing("evaluation", "one un-captured call is needed before graph capture (it allocates the buffers)")
         K, D, G = len(self.classes), self.max_detections, self.max_images * self.max_labels_per_frame
         ws_bytes = self._ws_bytes()
 
@@ -146,8 +146,7 @@ class PropheseeEvaluator:
             raise TypeError("sast_amd.evaluation: n_det must be int32 [N]")
         if not 1 <= N <= 65535 or M < 1 or not 1 <= A <= MAX_ANCHORS:
             raise ValueError(f"sast_amd.evaluation: need 1 <= N <= 65535 frames, M >= 1 label rows and 1 <= A <= {MAX_ANCHORS} detection rows")
-        if len({labels.device, counts.device, det.device, n_det.device}) != 1:
-            raise ValueError("sast_amd.evaluation: labels, counts, det and n_det must be on the same device")
+        same_device("evaluation", "labels, counts, det and n_det", labels, counts, det, n_det)
         if self._dev is None:
             self._allocate(labels.device)
         elif labels.device != self._dev:

@@ -28,16 +28,9 @@ from typing import Optional, Tuple
 
 import torch
 
+from . import _frontend as F
 from . import _lib as L
 from .functional import _need_gpu, _stream
-
-_EV_DT = {torch.int64: L.DT_I64, torch.int32: L.DT_I32, torch.int16: L.DT_I16}
-
-
-def _dtype_code(t: torch.Tensor, name: str, allowed=(torch.int64, torch.int32, torch.int16)) -> int:
-    if t.dtype not in allowed:
-        raise TypeError(f"sast_amd.events: {name} must be one of {[str(d) for d in allowed]}, got {t.dtype}")
-    return _EV_DT[t.dtype]
 
 
 def _columns(x, y, pol, time):
@@ -49,10 +42,9 @@ def _columns(x, y, pol, time):
         cols.append(t.contiguous())
     if not x.numel() == y.numel() == pol.numel() == time.numel():
         raise ValueError("sast_amd.events: x, y, pol and time must hold the same number of events")
-    if len({t.device for t in cols}) != 1:
-        raise ValueError("sast_amd.events: x, y, pol and time must be on the same device")
-    codes = [_dtype_code(cols[0], "x"), _dtype_code(cols[1], "y"), _dtype_code(cols[2], "pol"),
-             _dtype_code(cols[3], "time", (torch.int64, torch.int32))]
+    F.same_device("events", "x, y, pol and time", *cols)
+    codes = [F.dtype_code(cols[0], "x", "events"), F.dtype_code(cols[1], "y", "events"), F.dtype_code(cols[2], "pol", "events"),
+             F.dtype_code(cols[3], "time", "events", (torch.int64, torch.int32))]
     return cols, codes
 
 
@@ -75,12 +67,6 @@ def _md_cutoff(count_cutoff: Optional[int]) -> Optional[int]:
 
 
 REPRESENTATIONS = ("stacked_histogram", "mixed_density")
-
-
-def _not_capturing(what: str = "one un-captured warm-up call is needed before graph capture"):
-    """buffers are allocated outside graph capture only: the first call with new sizes must be an ordinary one"""
-    if torch.cuda.is_current_stream_capturing():
-        raise RuntimeError("sast_amd.events: " + what)
 
 
 class _Frames:
@@ -124,7 +110,7 @@ class _Frames:
         key = (device, B)
         ws = self._ws.get(key)
         if ws is None or ws.numel() < need:
-            _not_capturing()
+            F.not_capturing("events")
             self._ws.clear()
             ws = self._ws[key] = torch.zeros(need, dtype=torch.uint8, device=device)
         return ws
@@ -215,8 +201,11 @@ class MixedDensityEventStack(_Frames):
 
 class _Windowed(_Frames):
     """what `EventFrames` and `EventStreams` share: the window rule (duration or count), the time-correction carry `t_last`, the error
-    counters `err`, and the buffers kept between calls.  Those are allocated by ordinary calls only: one un-captured warm-up call with
-    the same sizes is needed before a call can be captured in a graph."""
+    counters `err`, and the buffers kept between calls (among them one `bounds` tensor per number of windows asked for).  Those are
+    allocated by ordinary calls only: one un-captured warm-up call with the same sizes is needed before a call can be captured in a
+    graph."""
+
+    _module = "events"         # the module named in front of this object's messages
 
     def __init__(self, bins: int, height: int, width: int, count_cutoff: Optional[int], fastmode: bool, downsample_by_2: bool,
                  representation: str, duration_us: Optional[int], num_events: Optional[int], correct_time: bool,
@@ -240,9 +229,24 @@ class _Windowed(_Frames):
             self.t_last = torch.zeros(shape, dtype=torch.int64, device=dev)
             self.err = torch.zeros(2, dtype=torch.int32, device=dev)
 
+    def _bounds(self, windows: int, dev, hint: str = "number of windows") -> torch.Tensor:
+        """the int64 [windows, 2] tensor the window search writes, kept per window count so that a captured call finds it again"""
+        kept = self._state.setdefault("bounds", {})
+        if windows not in kept:
+            F.not_capturing(self._module, f"one un-captured warm-up call with the same {hint} is needed before graph capture")
+            kept[windows] = torch.empty(windows, 2, dtype=torch.int64, device=dev)
+        return kept[windows]
+
+    def _frames_shape(self, ends_us: torch.Tensor, S: int, cap: int) -> Tuple[int, int, tuple]:
+        """ends_us int64 [S] or [T, S] -> (T, the window capacity of a call on rows of `cap` events, the frames' shape)"""
+        T = F.window_ends(ends_us, S, "events")
+        wcap = self.window_capacity if self.window_capacity is not None else max(cap, 1)
+        self.ws_bytes(T * S, wcap)              # ValueError for more windows than the frame kernels take
+        return T, wcap, tuple(ends_us.shape) + self.get_shape()
+
     def errors(self) -> Tuple[int, int]:
         """(invalid events, windows over capacity) since the last reset() (synchronises)"""
-        return (0, 0) if self.err is None else tuple(int(v) for v in self.err.tolist())
+        return F.counters(self.err, 2)
 
 
 class EventFrames(_Windowed):
@@ -273,7 +277,7 @@ class EventFrames(_Windowed):
     def _buffers(self, dev, capacity: int):
         st = self._state.get("cap")
         if st is None or st[0] != dev or st[1] < capacity:
-            _not_capturing()
+            F.not_capturing("events")
             self._state = {"cap": (dev, capacity), "t": torch.empty(max(capacity, 1), dtype=torch.int64, device=dev),
                            "scan": torch.empty(L.EVENT_SCAN_BLOCKS + 1, dtype=torch.int64, device=dev)}
         self._carry(dev, ())
@@ -281,9 +285,7 @@ class EventFrames(_Windowed):
 
     def reset(self):
         """a new recording: the time-correction carry back to 0, the error counters cleared"""
-        if self.t_last is not None:
-            self.t_last.zero_()
-            self.err.zero_()
+        F.reset_rows((self.t_last,), self.err, None, 1, "events")
 
     def __call__(self, x: torch.Tensor, y: torch.Tensor, p: torch.Tensor, t: torch.Tensor, ends_us: torch.Tensor,
                  n: Optional[torch.Tensor] = None, check: bool = False) -> torch.Tensor:
@@ -297,7 +299,7 @@ class EventFrames(_Windowed):
         if n is None:
             n = st.get("n")
             if n is None or int(st["n_val"]) != cap:
-                _not_capturing("pass n (a device tensor) when capturing, or warm up with the same buffer length")
+                F.not_capturing("events", "pass n (a device tensor) when capturing, or warm up with the same buffer length")
                 n = st["n"] = torch.full((1,), cap, dtype=torch.int64, device=dev)
                 st["n_val"] = cap
         elif n.dtype != torch.int64 or n.numel() != 1:
@@ -352,77 +354,40 @@ class EventStreams(_Windowed):
                  correct_time: bool = True, window_capacity: Optional[int] = None, representation: str = "stacked_histogram"):
         super().__init__(bins, height, width, count_cutoff, fastmode, downsample_by_2, representation, duration_us, num_events,
                          correct_time, window_capacity)
-        if int(num_streams) < 1 or int(num_streams) > 65535:
-            raise ValueError("sast_amd.events: num_streams must be in 1 .. 65535")
-        self.num_streams = int(num_streams)
+        self.num_streams = F.stream_count(num_streams, "events")
 
-    def _buffers(self, dev, cap: int, windows: int):
+    def _buffers(self, dev, cap: int):
         S = self.num_streams
         st = self._state
         if st.get("cap") is None or st["cap"][0] != dev or st["cap"][1] < cap:
-            _not_capturing()
+            F.not_capturing("events")
             st = self._state = {"cap": (dev, cap), "t": torch.empty(max(S * cap, 1), dtype=torch.int64, device=dev),
-                                "scan": torch.empty(int(L.lib().sast_evstreams_ws_count(S)), dtype=torch.int64, device=dev), "bounds": {}}
-        if windows not in st["bounds"]:
-            _not_capturing("one un-captured warm-up call with the same number of windows is needed before graph capture")
-            st["bounds"][windows] = torch.empty(windows, 2, dtype=torch.int64, device=dev)
+                                "scan": torch.empty(int(L.lib().sast_evstreams_ws_count(S)), dtype=torch.int64, device=dev)}
         self._carry(dev, (S,))
         return st
 
     def reset(self, streams=None):
         """new recordings, from the host: the time-correction carry of `streams` (default: all of them) back to 0; with streams=None the
         error counters are cleared as well"""
-        if self.t_last is None:
-            return
-        if streams is None:
-            self.t_last.zero_()
-            self.err.zero_()
-            return
-        idx = [int(s) for s in streams]
-        if any(s < 0 or s >= self.num_streams for s in idx):
-            raise ValueError(f"sast_amd.events: streams must be in 0 .. {self.num_streams - 1}")
-        if idx:
-            self.t_last[torch.tensor(idx, dtype=torch.int64, device=self.t_last.device)] = 0
+        F.reset_rows((self.t_last,), self.err, streams, self.num_streams, "events")
 
     def __call__(self, x: torch.Tensor, y: torch.Tensor, p: torch.Tensor, t: torch.Tensor, counts: torch.Tensor, ends_us: torch.Tensor,
                  reset: Optional[torch.Tensor] = None, check: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         S = self.num_streams
-        cols = [x, y, p, t]
-        for c, name in zip(cols, ("x", "y", "p", "t")):
-            if c.dim() != 2 or c.shape[0] != S:
-                raise ValueError(f"sast_amd.events: {name} must be [num_streams={S}, capacity], got shape {tuple(c.shape)}")
-            if not c.is_contiguous():
-                raise ValueError(f"sast_amd.events: {name} must be contiguous")
-        if not x.shape == y.shape == p.shape == t.shape:
-            raise ValueError("sast_amd.events: x, y, p and t must have the same shape")
-        codes = [_dtype_code(x, "x"), _dtype_code(y, "y"), _dtype_code(p, "p"), _dtype_code(t, "t", (torch.int64, torch.int32))]
+        codes = F.event_columns(x, y, p, t, S, "events")
         if not self.correct_time and t.dtype != torch.int64:
             raise TypeError("sast_amd.events: correct_time=False needs int64 timestamps")
-        if counts.dtype != torch.int64 or tuple(counts.shape) != (S,) or not counts.is_contiguous():
-            raise ValueError(f"sast_amd.events: counts must be a contiguous int64 tensor of shape [{S}]")
-        if ends_us.dtype != torch.int64 or ends_us.dim() not in (1, 2) or ends_us.shape[-1] != S or ends_us.numel() < 1 \
-                or not ends_us.is_contiguous():
-            raise ValueError(f"sast_amd.events: ends_us must be a contiguous int64 tensor of shape [{S}] or [T, {S}], T >= 1")
-        if reset is not None and (reset.dtype not in (torch.uint8, torch.bool) or tuple(reset.shape) != (S,) or not reset.is_contiguous()):
-            raise ValueError(f"sast_amd.events: reset must be a contiguous uint8 or bool tensor of shape [{S}]")
+        F.counts_reset(counts, reset, S, "events")
         dev = x.device
         cap = x.shape[1]
         if S * cap > 2 ** 31 - 1:
             raise ValueError("sast_amd.events: num_streams * capacity must be below 2^31")
-        T = ends_us.shape[0] if ends_us.dim() == 2 else 1
-        B = T * S
-        wcap = self.window_capacity if self.window_capacity is not None else max(cap, 1)
-        self.ws_bytes(B, wcap)                  # ValueError for more windows than the histogram kernels take
+        T, wcap, shape = self._frames_shape(ends_us, S, cap)
         _need_gpu(x, y, p, t, counts, ends_us, reset, out)
-        if len({c.device for c in cols + [counts, ends_us] + ([reset] if reset is not None else [])}) != 1:
-            raise ValueError("sast_amd.events: x, y, p, t, counts, ends_us and reset must be on the same device")
-        shape = tuple(ends_us.shape) + self.get_shape()
-        if out is None:
-            out = torch.empty(shape, dtype=self.frame_dtype, device=dev)
-        elif out.dtype != self.frame_dtype or tuple(out.shape) != tuple(shape) or not out.is_contiguous() or out.device != dev:
-            raise ValueError(f"sast_amd.events: out must be a contiguous {str(self.frame_dtype).replace('torch.', '')} tensor of shape "
-                             f"{tuple(shape)} on the events' device")
-        st = self._buffers(dev, cap, B)
+        F.same_device("events", "x, y, p, t, counts, ends_us and reset", x, y, p, t, counts, ends_us, reset)
+        out = F.frames_out(out, shape, self.frame_dtype, dev, "events", "out", "the events'")
+        st = self._buffers(dev, cap)
+        bounds = self._bounds(T * S, dev)
         if check:
             self.err.zero_()
         lib = L.lib()
@@ -434,7 +399,6 @@ class EventStreams(_Windowed):
             tcol, codes = tc, codes[:3] + [L.DT_I64]
         else:
             tcol = t
-        bounds = st["bounds"][B]
         L.check(lib.sast_evstreams_window_bounds(tcol.data_ptr() or tc.data_ptr(), counts.data_ptr(), S, cap, ends_us.data_ptr(), T,
                                                  self.mode, self.value, bounds.data_ptr(), _stream()), "evstreams_window_bounds")
         self.launch([x, y, p, tcol], codes, S * cap, bounds, out, self.err, wcap, clip_negative_polarity=True)
@@ -470,11 +434,9 @@ class Evt3Decoder:
     DECODE_LAUNCHES = 2
 
     def __init__(self, num_streams: int, max_events: Optional[int] = None):
-        if int(num_streams) < 1 or int(num_streams) > 65535:
-            raise ValueError("sast_amd.events: num_streams must be in 1 .. 65535")
+        self.num_streams = F.stream_count(num_streams, "events")
         if max_events is not None and int(max_events) < 1:
             raise ValueError("sast_amd.events: max_events must be >= 1 (or None)")
-        self.num_streams = int(num_streams)
         self.max_events = None if max_events is None else int(max_events)
         if self.max_events is not None and self.num_streams * self.max_events > 2 ** 31 - 1:
             raise ValueError("sast_amd.events: num_streams * max_events must be below 2^31")
@@ -482,17 +444,16 @@ class Evt3Decoder:
 
     def _buffers(self, dev, chunk_words: int):
         S = self.num_streams
-        if self.state is not None and self.state.device != dev:
-            raise ValueError(f"sast_amd.events: the decoder's state lives on {self.state.device}, the call's tensors on {dev}")
         if self.state is None:
-            _not_capturing()
+            F.not_capturing("events")
             self.state = torch.zeros(S, L.EVT3_STATE_WORDS, dtype=torch.int64, device=dev)
             self.err = torch.zeros(3, dtype=torch.int32, device=dev)
             self.counts = torch.zeros(S, dtype=torch.int64, device=dev)
             self._ws = torch.zeros(int(L.lib().sast_evt3_ws_bytes(S)), dtype=torch.uint8, device=dev)
+        F.lives_on("the decoder's state", self.state.device, "the call's tensors", dev, "events")
         need = self.max_events if self.max_events is not None else max(12 * chunk_words, 1)
         if self.x is None or self.x.shape[1] < need:
-            _not_capturing()
+            F.not_capturing("events")
             if S * need > 2 ** 31 - 1:
                 raise ValueError("sast_amd.events: num_streams * max_events must be below 2^31")
             self.x, self.y, self.p = (torch.zeros(S, need, dtype=torch.int16, device=dev) for _ in range(3))
@@ -500,42 +461,23 @@ class Evt3Decoder:
 
     def errors(self) -> Tuple[int, int, int]:
         """(events before the first TIME_HIGH, unknown words, events dropped for lack of staging) since the last reset() (synchronises)"""
-        return (0, 0, 0) if self.err is None else tuple(int(v) for v in self.err.tolist())
+        return F.counters(self.err, 3)
 
     def reset(self, streams=None):
         """new recordings, from the host: the decoder state of `streams` (default: all of them) back to zero; with streams=None the
         counters are cleared as well"""
-        if self.state is None:
-            return
-        if streams is None:
-            self.state.zero_()
-            self.err.zero_()
-            return
-        idx = [int(s) for s in streams]
-        if any(s < 0 or s >= self.num_streams for s in idx):
-            raise ValueError(f"sast_amd.events: streams must be in 0 .. {self.num_streams - 1}")
-        if idx:
-            self.state[torch.tensor(idx, dtype=torch.int64, device=self.state.device)] = 0
+        F.reset_rows((self.state,), self.err, streams, self.num_streams, "events")
 
     def __call__(self, words: torch.Tensor, counts: torch.Tensor, reset: Optional[torch.Tensor] = None):
         S = self.num_streams
-        if not torch.is_tensor(words) or words.dim() != 2 or words.shape[0] != S:
-            raise ValueError(f"sast_amd.events: words must be [num_streams={S}, chunk words], got shape "
-                             f"{tuple(words.shape) if torch.is_tensor(words) else type(words)}")
-        if words.dtype not in _WORD_DTYPES:
-            raise TypeError(f"sast_amd.events: words must be torch.int16 or torch.uint16 (one EVT 3.0 word each), got {words.dtype}")
-        if not words.is_contiguous():
-            raise ValueError("sast_amd.events: words must be contiguous")
-        if counts.dtype != torch.int64 or tuple(counts.shape) != (S,) or not counts.is_contiguous():
-            raise ValueError(f"sast_amd.events: counts must be a contiguous int64 tensor of shape [{S}]")
-        if reset is not None and (reset.dtype not in (torch.uint8, torch.bool) or tuple(reset.shape) != (S,) or not reset.is_contiguous()):
-            raise ValueError(f"sast_amd.events: reset must be a contiguous uint8 or bool tensor of shape [{S}]")
+        F.tensor_arg(words, "words", "events", _WORD_DTYPES, (("num_streams", S), "chunk words"), "(one EVT 3.0 word each)",
+                     empty_ok=True, dtype_error=TypeError)
+        F.counts_reset(counts, reset, S, "events")
         chunk_words = words.shape[1]
         if S * chunk_words > 2 ** 31 - 1 or 12 * chunk_words > 2 ** 31 - 1:
             raise ValueError("sast_amd.events: num_streams * chunk words and 12 * chunk words must be below 2^31")
         _need_gpu(words, counts, reset)
-        if len({c.device for c in [words, counts] + ([reset] if reset is not None else [])}) != 1:
-            raise ValueError("sast_amd.events: words, counts and reset must be on the same device")
+        F.same_device("events", "words, counts and reset", words, counts, reset)
         self._buffers(counts.device, chunk_words)
         # an empty chunk has no storage: any valid device pointer will do, the kernels read no word
         L.check(L.lib().sast_evt3_decode(words.data_ptr() or self.t.data_ptr(), counts.data_ptr(), chunk_words, S,
@@ -616,8 +558,7 @@ class EventQueue(_Windowed):
                          window_capacity)
         if int(height) > 32767 or int(width) > 32767:
             raise ValueError("sast_amd.events: EventQueue keeps x and y as int16: height and width must be <= 32767")
-        if int(num_streams) < 1 or int(num_streams) > 65535:
-            raise ValueError("sast_amd.events: num_streams must be in 1 .. 65535")
+        F.stream_count(num_streams, "events")
         if int(capacity) < 1:
             raise ValueError("sast_amd.events: capacity must be >= 1")
         if int(num_streams) * int(capacity) > 2 ** 31 - 1:
@@ -629,16 +570,16 @@ class EventQueue(_Windowed):
 
     def _storage(self, dev):
         """the queue's state on `dev` (allocated by the first ordinary call)"""
-        if self._args is not None and self.t.device != dev:
-            raise ValueError(f"sast_amd.events: the queue's state lives on {self.t.device}, the call's tensors on {dev}")
-        if self._args is None:
-            _not_capturing()
+        if self._args is not None:
+            F.lives_on("the queue's state", self.t.device, "the call's tensors", dev, "events")
+        else:
+            F.not_capturing("events")
             S, cap = self.num_streams, self.capacity
             self.x, self.y, self.p = (torch.zeros(S, cap, dtype=torch.int16, device=dev) for _ in range(3))
             self.t = torch.zeros(S, cap, dtype=torch.int64, device=dev)
             self.head, self.count, self.t_last, self.retired, self.retired_t = (torch.zeros(S, dtype=torch.int64, device=dev) for _ in range(5))
             self.err = torch.zeros(4, dtype=torch.int32, device=dev)
-            self._state = {"ws": torch.zeros(int(L.lib().sast_evqueue_ws_count(S)), dtype=torch.int64, device=dev), "bounds": {}}
+            self._state = {"ws": torch.zeros(int(L.lib().sast_evqueue_ws_count(S)), dtype=torch.int64, device=dev)}
             a = self._args = L.SastEvQueueArgs()
             a.x, a.y, a.p, a.t = self.x.data_ptr(), self.y.data_ptr(), self.p.data_ptr(), self.t.data_ptr()
             a.head, a.count, a.t_last = self.head.data_ptr(), self.count.data_ptr(), self.t_last.data_ptr()
@@ -648,40 +589,19 @@ class EventQueue(_Windowed):
 
     def errors(self) -> Tuple[int, int, int, int]:
         """(invalid events, windows over capacity, dropped events, late windows) since they were last cleared (synchronises)"""
-        return (0, 0, 0, 0) if self.err is None else tuple(int(v) for v in self.err.tolist())
+        return F.counters(self.err, 4)
 
     def reset(self, streams=None):
         """new recordings, from the host: rows `streams` (default: all of them) are emptied, their carry and retirement record zeroed;
         with streams=None the error counters are cleared as well"""
         if self.evt3 is not None:
             self.evt3.reset(streams)
-        if self._args is None:
-            return
-        state = (self.head, self.count, self.t_last, self.retired, self.retired_t)
-        if streams is None:
-            for v in state:
-                v.zero_()
-            self.err.zero_()
-            return
-        idx = [int(s) for s in streams]
-        if any(s < 0 or s >= self.num_streams for s in idx):
-            raise ValueError(f"sast_amd.events: streams must be in 0 .. {self.num_streams - 1}")
-        if idx:
-            sel = torch.tensor(idx, dtype=torch.int64, device=self.head.device)
-            for v in state:
-                v[sel] = 0
-
-    def _counts_reset(self, counts, reset):
-        S = self.num_streams
-        if counts.dtype != torch.int64 or tuple(counts.shape) != (S,) or not counts.is_contiguous():
-            raise ValueError(f"sast_amd.events: counts must be a contiguous int64 tensor of shape [{S}]")
-        if reset is not None and (reset.dtype not in (torch.uint8, torch.bool) or tuple(reset.shape) != (S,) or not reset.is_contiguous()):
-            raise ValueError(f"sast_amd.events: reset must be a contiguous uint8 or bool tensor of shape [{S}]")
+        F.reset_rows((self.head, self.count, self.t_last, self.retired, self.retired_t), self.err, streams, self.num_streams, "events")
 
     def _push(self, ptrs, codes, chunk_cap, counts, reset, tensors):
+        F.counts_reset(counts, reset, self.num_streams, "events")
         _need_gpu(*tensors, counts, reset)
-        if len({c.device for c in tensors + [counts] + ([reset] if reset is not None else [])}) != 1:
-            raise ValueError("sast_amd.events: the chunk, counts and reset must be on the same device")
+        F.same_device("events", "the chunk, counts and reset", *tensors, counts, reset)
         if self.num_streams * chunk_cap > 2 ** 31 - 1:
             raise ValueError("sast_amd.events: num_streams * chunk capacity must be below 2^31")
         a = self._storage(counts.device)
@@ -692,28 +612,12 @@ class EventQueue(_Windowed):
 
     def push(self, x: torch.Tensor, y: torch.Tensor, p: torch.Tensor, t: torch.Tensor, counts: torch.Tensor,
              reset: Optional[torch.Tensor] = None) -> None:
-        S = self.num_streams
-        cols = [x, y, p, t]
-        for c, name in zip(cols, ("x", "y", "p", "t")):
-            if c.dim() != 2 or c.shape[0] != S:
-                raise ValueError(f"sast_amd.events: {name} must be [num_streams={S}, chunk capacity], got shape {tuple(c.shape)}")
-            if not c.is_contiguous():
-                raise ValueError(f"sast_amd.events: {name} must be contiguous")
-        if not x.shape == y.shape == p.shape == t.shape:
-            raise ValueError("sast_amd.events: x, y, p and t must have the same shape")
-        codes = [_dtype_code(x, "x"), _dtype_code(y, "y"), _dtype_code(p, "p"), _dtype_code(t, "t", (torch.int64, torch.int32))]
-        self._counts_reset(counts, reset)
-        self._push([c.data_ptr() for c in cols], codes, x.shape[1], counts, reset, cols)
+        codes = F.event_columns(x, y, p, t, self.num_streams, "events", cap_name="chunk capacity")
+        self._push([c.data_ptr() for c in (x, y, p, t)], codes, x.shape[1], counts, reset, [x, y, p, t])
 
     def push_dat(self, records: torch.Tensor, counts: torch.Tensor, reset: Optional[torch.Tensor] = None) -> None:
-        S = self.num_streams
-        if records.dim() != 3 or records.shape[0] != S or records.shape[2] != 2:
-            raise ValueError(f"sast_amd.events: records must be [num_streams={S}, chunk capacity, 2], got shape {tuple(records.shape)}")
-        if records.dtype != torch.int32:
-            raise TypeError(f"sast_amd.events: records must be torch.int32 (two words per Event2D record), got {records.dtype}")
-        if not records.is_contiguous():
-            raise ValueError("sast_amd.events: records must be contiguous")
-        self._counts_reset(counts, reset)
+        F.tensor_arg(records, "records", "events", (torch.int32,), (("num_streams", self.num_streams), "chunk capacity", 2),
+                     "(two words per Event2D record)", empty_ok=True, dtype_error=TypeError)
         self._push([records.data_ptr()] * 4, [L.EVQUEUE_DT_DAT] * 4, records.shape[1], counts, reset, [records])
 
     def push_evt3(self, words: torch.Tensor, counts: torch.Tensor, reset: Optional[torch.Tensor] = None,
@@ -726,7 +630,7 @@ class EventQueue(_Windowed):
             self.evt3 = Evt3Decoder(self.num_streams, max_events)
         elif max_events is not None and int(max_events) != self.evt3.max_events:
             raise ValueError(f"sast_amd.events: the queue's decoder was made with max_events={self.evt3.max_events}, got {max_events}")
-        self._counts_reset(counts, reset)
+        F.counts_reset(counts, reset, self.num_streams, "events")
         x, y, p, t, n = self.evt3(words, counts, reset)
         self.push(x, y, p, t, n, reset)
 
@@ -737,27 +641,12 @@ class EventQueue(_Windowed):
 
     def frames(self, ends_us: torch.Tensor, out: Optional[torch.Tensor] = None, check: bool = False) -> torch.Tensor:
         S, cap = self.num_streams, self.capacity
-        if ends_us.dtype != torch.int64 or ends_us.dim() not in (1, 2) or ends_us.shape[-1] != S or ends_us.numel() < 1 \
-                or not ends_us.is_contiguous():
-            raise ValueError(f"sast_amd.events: ends_us must be a contiguous int64 tensor of shape [{S}] or [T, {S}], T >= 1")
-        T = ends_us.shape[0] if ends_us.dim() == 2 else 1
-        B = T * S
-        wcap = self.window_capacity if self.window_capacity is not None else cap
-        self.ws_bytes(B, wcap)                  # ValueError for more windows than the frame kernels take
+        T, wcap, shape = self._frames_shape(ends_us, S, cap)
         _need_gpu(ends_us, out)
         dev = ends_us.device
-        shape = tuple(ends_us.shape) + self.get_shape()
-        if out is None:
-            out = torch.empty(shape, dtype=self.frame_dtype, device=dev)
-        elif out.dtype != self.frame_dtype or tuple(out.shape) != tuple(shape) or not out.is_contiguous() or out.device != dev:
-            raise ValueError(f"sast_amd.events: out must be a contiguous {str(self.frame_dtype).replace('torch.', '')} tensor of shape "
-                             f"{tuple(shape)} on the queue's device")
+        out = F.frames_out(out, shape, self.frame_dtype, dev, "events", "out", "the queue's")
         a = self._storage(dev)
-        st = self._state
-        if B not in st["bounds"]:
-            _not_capturing("one un-captured warm-up call with the same number of windows is needed before graph capture")
-            st["bounds"][B] = torch.empty(B, 2, dtype=torch.int64, device=dev)
-        bounds = st["bounds"][B]
+        bounds = self._bounds(T * S, dev)
         lib = L.lib()
         L.check(lib.sast_evqueue_window_bounds(C.byref(a), ends_us.data_ptr(), T, self.mode, self.value, bounds.data_ptr(), _stream()),
                 "evqueue_window_bounds")

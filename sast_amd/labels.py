@@ -18,6 +18,7 @@ from typing import List, NamedTuple, Optional, Tuple
 import numpy as np
 import torch
 
+from . import _frontend as F
 from . import _lib as L
 from .functional import _need_gpu, _stream
 
@@ -46,22 +47,6 @@ FLAGS = (
 
 def flag_names(status: int) -> Tuple[str, ...]:
     return tuple(name for bit, name, _msg in FLAGS if status & bit)
-
-
-def _outputs(cls, want, out, dev, module: str, what: str, owner: str):
-    """the tensors a gather call writes, as a `cls` (a NamedTuple class): allocated as `want` says ((shape, dtype) per field), or the
-    caller's `out` checked against it"""
-    if out is None:
-        return cls(*(torch.empty(sh, dtype=dt, device=dev) for sh, dt in want))
-    out = tuple(out)
-    if len(out) != len(want):
-        raise ValueError(f"sast_amd.{module}: out must be the {what}")
-    _need_gpu(*out)
-    for t, (sh, dt), name in zip(out, want, cls._fields):
-        if t.dtype != dt or tuple(t.shape) != sh or not t.is_contiguous() or t.device != dev:
-            raise ValueError(f"sast_amd.{module}: out's {name} must be a contiguous {str(dt).replace('torch.', '')} tensor of shape "
-                             f"{sh} on the {owner}'s device")
-    return cls(*out)
 
 
 class _Labels(NamedTuple):
@@ -121,8 +106,7 @@ class LabelStreams:
             raise ValueError("sast_amd.labels: ts_step_ev_repr_ms must be > 0 and divide 100")
         if align_t_ms < 0:
             raise ValueError("sast_amd.labels: align_t_ms must be >= 0")
-        if int(num_streams) < 1 or int(num_streams) > 65535:
-            raise ValueError("sast_amd.labels: num_streams must be in 1 .. 65535")
+        F.stream_count(num_streams, "labels")
         if int(capacity) < 1 or int(num_streams) * int(capacity) > (2 ** 31 - 1) // 16:
             raise ValueError("sast_amd.labels: capacity must be >= 1 and num_streams * capacity <= (2^31 - 1) / 16")
         for v, name in ((max_frames, "max_frames"), (max_windows, "max_windows"), (max_labels_per_frame, "max_labels_per_frame")):
@@ -160,19 +144,18 @@ class LabelStreams:
 
     def _storage(self, dev):
         """the state on `dev` (allocated by the first ordinary call)"""
-        if self._args is not None and self.status.device != dev:
-            raise ValueError(f"sast_amd.labels: the state lives on {self.status.device}, the call's tensors on {dev}")
-        if self._args is None:
-            if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("sast_amd.labels: one un-captured warm-up call is needed before graph capture")
-            S, cap, F, W = self.num_streams, self.capacity, self.max_frames, self.max_windows
+        if self._args is not None:
+            F.lives_on("the state", self.status.device, "the call's tensors", dev, "labels")
+        else:
+            F.not_capturing("labels")
+            S, cap, Fr, W = self.num_streams, self.capacity, self.max_frames, self.max_windows
             i32, i64 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.int64, device=dev)
             self.ends_us, self.n_windows = torch.zeros(S, W, **i64), torch.zeros(S, **i32)
-            self.frame_ts_us, self.n_frames = torch.zeros(S, F, **i64), torch.zeros(S, **i32)
-            self.frame_2_window, self.window_2_frame = torch.zeros(S, F, **i64), torch.full((S, W), -1, **i32)
+            self.frame_ts_us, self.n_frames = torch.zeros(S, Fr, **i64), torch.zeros(S, **i32)
+            self.frame_2_window, self.window_2_frame = torch.zeros(S, Fr, **i64), torch.full((S, W), -1, **i32)
             self.label_rows = torch.zeros(S, cap, 7, dtype=torch.float32, device=dev)
-            self.frame_start, self.frame_count, self.status = torch.zeros(S, F, **i32), torch.zeros(S, F, **i32), torch.zeros(S, **i32)
-            nbytes = int(L.lib().sast_labels_ws_bytes(S, cap, F))
+            self.frame_start, self.frame_count, self.status = torch.zeros(S, Fr, **i32), torch.zeros(S, Fr, **i32), torch.zeros(S, **i32)
+            nbytes = int(L.lib().sast_labels_ws_bytes(S, cap, Fr))
             if nbytes == 0:
                 raise ValueError("sast_amd.labels: unsupported sizes")
             self._ws = torch.zeros((nbytes + 7) // 8, **i64)
@@ -195,7 +178,7 @@ class LabelStreams:
             faulty = self.split == 'train' and self.apply_faulty_bbox_filter     # :282-283
             a.max_width = float((9 * self.width) // 10) if faulty else -1.0
             a.downsample_by_2 = int(self.downsample_by_2)
-            a.max_frames, a.max_windows, a.max_labels_per_frame = F, W, self.max_labels_per_frame
+            a.max_frames, a.max_windows, a.max_labels_per_frame = Fr, W, self.max_labels_per_frame
         return self._args
 
     def errors(self) -> List[Tuple[str, ...]]:
@@ -206,17 +189,10 @@ class LabelStreams:
 
     def load(self, records: torch.Tensor, counts: torch.Tensor, reset: Optional[torch.Tensor] = None, check: bool = False) -> None:
         S, cap = self.num_streams, self.capacity
-        if records.dtype != torch.int32:
-            raise TypeError(f"sast_amd.labels: records must be torch.int32 (ten words per box record), got {records.dtype}")
-        if tuple(records.shape) != (S, cap, 10) or not records.is_contiguous():
-            raise ValueError(f"sast_amd.labels: records must be a contiguous tensor of shape [{S}, {cap}, 10], got {tuple(records.shape)}")
-        if counts.dtype != torch.int64 or tuple(counts.shape) != (S,) or not counts.is_contiguous():
-            raise ValueError(f"sast_amd.labels: counts must be a contiguous int64 tensor of shape [{S}]")
-        if reset is not None and (reset.dtype not in (torch.uint8, torch.bool) or tuple(reset.shape) != (S,) or not reset.is_contiguous()):
-            raise ValueError(f"sast_amd.labels: reset must be a contiguous uint8 or bool tensor of shape [{S}]")
+        F.tensor_arg(records, "records", "labels", (torch.int32,), (S, cap, 10), "(ten words per box record)", dtype_error=TypeError)
+        F.counts_reset(counts, reset, S, "labels")
         _need_gpu(records, counts, reset)
-        if len({t.device for t in (records, counts) + ((reset,) if reset is not None else ())}) != 1:
-            raise ValueError("sast_amd.labels: records, counts and reset must be on the same device")
+        F.same_device("labels", "records, counts and reset", records, counts, reset)
         a = self._storage(records.device)
         L.check(L.lib().sast_labels_load(C.byref(a), records.data_ptr(), counts.data_ptr(), None if reset is None else reset.data_ptr(),
                                          _stream()), "labels_load")
@@ -239,21 +215,17 @@ class LabelStreams:
 
     def labels(self, window_idx: torch.Tensor, out=None):
         S, M = self.num_streams, self.max_labels_per_frame
-        if window_idx.dtype != torch.int64 or window_idx.dim() not in (1, 2) or window_idx.shape[-1] != S or window_idx.numel() < 1 \
-                or not window_idx.is_contiguous():
-            raise ValueError(f"sast_amd.labels: window_idx must be a contiguous int64 tensor of shape [{S}] or [T, {S}], T >= 1")
+        T = F.window_ends(window_idx, S, "labels", "window_idx")
         _need_gpu(window_idx)
         if self._args is None:
             raise RuntimeError("sast_amd.labels: call load() before labels()")
         dev = window_idx.device
-        if dev != self.status.device:
-            raise ValueError(f"sast_amd.labels: the state lives on {self.status.device}, window_idx on {dev}")
-        T = window_idx.shape[0] if window_idx.dim() == 2 else 1
+        F.lives_on("the state", self.status.device, "window_idx", dev, "labels")
         if T * S * M > (2 ** 31 - 1) // 8:
             raise ValueError("sast_amd.labels: T * num_streams * max_labels_per_frame must be <= (2^31 - 1) / 8")
         shape = tuple(window_idx.shape)
         want = ((shape + (M, 7), torch.float32), (shape, torch.int32), (shape, torch.int64), (shape, torch.uint8))
-        out = tuple(_outputs(_Labels, want, out, dev, "labels", "four tensors (labels, counts, ends_us, labelled)", "state"))
+        out = tuple(F.outputs(_Labels, want, out, dev, "labels", "four tensors (labels, counts, ends_us, labelled)", "the state's"))
         L.check(L.lib().sast_labels_gather(C.byref(self._args), window_idx.data_ptr(), T, out[0].data_ptr(), out[1].data_ptr(),
                                            out[2].data_ptr(), out[3].data_ptr(), _stream()), "labels_gather")
         return out

@@ -17,6 +17,7 @@ from typing import List, Optional, Tuple
 import numpy as np
 import torch
 
+from . import _frontend as F
 from . import _lib as L
 from . import functional as SF
 from .events import EventQueue
@@ -25,11 +26,6 @@ from .labels import BBOX_DTYPE
 
 RECORD_BYTES = L.DET_RECORD_BYTES
 assert BBOX_DTYPE.itemsize == RECORD_BYTES
-
-
-def _flags(t: Optional[torch.Tensor], S: int, name: str):
-    if t is not None and (not torch.is_tensor(t) or t.dtype not in (torch.uint8, torch.bool) or tuple(t.shape) != (S,) or not t.is_contiguous()):
-        raise ValueError(f"sast_amd.online: {name} must be a contiguous uint8 or bool tensor of shape [{S}]")
 
 
 def schedule_windows(queue: EventQueue, next_end: torch.Tensor, first_end_us: int, ends: torch.Tensor, due: torch.Tensor,
@@ -45,16 +41,13 @@ def schedule_windows(queue: EventQueue, next_end: torch.Tensor, first_end_us: in
         raise ValueError("sast_amd.online: the window schedule needs a queue with duration windows (duration_us >= 1)")
     if int(first_end_us) < queue.value:
         raise ValueError(f"sast_amd.online: first_end_us must be >= duration_us ({queue.value}), got {first_end_us}")
-    if ends.dtype != torch.int64 or ends.dim() != 2 or ends.shape[1] != S or ends.shape[0] < 1 or not ends.is_contiguous():
-        raise ValueError(f"sast_amd.online: ends must be a contiguous int64 tensor of shape [W, {S}], W >= 1")
+    F.tensor_arg(ends, "ends", "online", (torch.int64,), ("W", S))
     W = ends.shape[0]
-    if due.dtype != torch.uint8 or tuple(due.shape) != (W, S) or not due.is_contiguous():
-        raise ValueError(f"sast_amd.online: due must be a contiguous uint8 tensor of shape [{W}, {S}]")
-    for t, name in ((next_end, "next_end"), (backlog, "backlog")):
-        if t.dtype != torch.int64 or tuple(t.shape) != (S,) or not t.is_contiguous():
-            raise ValueError(f"sast_amd.online: {name} must be a contiguous int64 tensor of shape [{S}]")
-    _flags(reset, S, "reset")
-    _flags(final, S, "final")
+    F.tensor_arg(due, "due", "online", (torch.uint8,), (W, S))
+    F.tensor_arg(next_end, "next_end", "online", (torch.int64,), (S,))
+    F.tensor_arg(backlog, "backlog", "online", (torch.int64,), (S,))
+    F.flags(reset, "reset", S, "online")
+    F.flags(final, "final", S, "online")
     _need_gpu(next_end, ends, due, backlog, reset, final)
     a = queue._storage(next_end.device)
     L.check(L.lib().sast_evq_schedule(C.byref(a), next_end.data_ptr(), queue.mode, queue.value, int(first_end_us), W,
@@ -69,16 +62,12 @@ def export_detections(det: torch.Tensor, n_det: torch.Tensor, ends: torch.Tensor
     [S, max_det, 40]) with t = ends[s] (int64 [S]), x, y = x1, y1, w, h = x2 - x1, y2 - y1 in fp32, class_id = column 6, track_id = 0,
     class_confidence = column 5; counts int32 [S] is the number written (0 for a row that is not due), truncated (int32 [1]) grows by
     what max_det cut off.  One launch, no synchronisation."""
-    if det.dtype != torch.float32 or det.dim() != 3 or det.shape[2] != 7 or det.shape[1] < 1 or not det.is_contiguous():
-        raise ValueError("sast_amd.online: det must be a contiguous fp32 tensor of shape [S, A, 7]")
+    F.tensor_arg(det, "det", "online", (torch.float32,), ("S", "A", 7))
     S, A = det.shape[0], det.shape[1]
-    if records.dtype != torch.uint8 or records.dim() != 3 or records.shape[0] != S or records.shape[1] < 1 or records.shape[2] != RECORD_BYTES \
-            or not records.is_contiguous():
-        raise ValueError(f"sast_amd.online: records must be a contiguous uint8 tensor of shape [{S}, max_det, {RECORD_BYTES}]")
+    F.tensor_arg(records, "records", "online", (torch.uint8,), (S, "max_det", RECORD_BYTES))
     for t, dt, n, name in ((n_det, torch.int32, S, "n_det"), (ends, torch.int64, S, "ends"), (due, torch.uint8, S, "due"),
                            (counts, torch.int32, S, "counts"), (truncated, torch.int32, 1, "truncated")):
-        if t.dtype != dt or tuple(t.shape) != (n,) or not t.is_contiguous():
-            raise ValueError(f"sast_amd.online: {name} must be a contiguous {str(dt).replace('torch.', '')} tensor of shape [{n}]")
+        F.tensor_arg(t, name, "online", (dt,), (n,))
     _need_gpu(det, n_det, ends, due, records, counts, truncated)
     a = L.SastDetExportArgs()
     a.det, a.n_det, a.ends, a.due = det.data_ptr(), n_det.data_ptr(), ends.data_ptr(), due.data_ptr()
@@ -146,8 +135,7 @@ class OnlineDetector:
 
     # ------------------------------------------------------------------------------------------------------------------ buffers
     def _allocate(self, dev: torch.device):
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("sast_amd.online: one un-captured call is needed before graph capture (it allocates the buffers)")
+        F.not_capturing("online", "one un-captured call is needed before graph capture (it allocates the buffers)")
         W, S, M = self.W, self.S, self.max_det
         n = W * S
         sizes = (8 * n, RECORD_BYTES * M * n, 4 * n, n)           # ends, records, counts, due: every offset a multiple of 8
@@ -172,13 +160,12 @@ class OnlineDetector:
     # ------------------------------------------------------------------------------------------------------------------ one push
     def _device_step(self, push, counts, reset, final):
         q, S, W = self.queue, self.S, self.W
-        _flags(final, S, "final")
+        F.flags(final, "final", S, "online")
         _need_gpu(final)
         push(counts, reset)                                       # validates the chunk, counts and reset; 2 launches
         if self._buf is None:
             self._allocate(counts.device)
-        if final is not None and final.device != counts.device:
-            raise ValueError("sast_amd.online: final must be on the chunk's device")
+        F.same_device("online", "final and the chunk", final, counts)
         held = None if self.states is None else [t for s in self.states for t in s]
         if held is not None and reset is not None:
             SF.zero_samples_dev(held, reset)

@@ -36,10 +36,11 @@ from typing import List, NamedTuple, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
+from . import _frontend as F
 from . import _lib as L
-from .events import _Windowed, _dtype_code, _not_capturing
+from .events import _Windowed
 from .functional import _need_gpu, _stream
-from .labels import LabelStreams, _outputs
+from .labels import LabelStreams
 
 # status bits (include/sast_hip.h, SAST_RND_*): per row, then pool-wide
 ROW_FLAGS = ((L.RND_CLASS_ID, "class_id", "a box of a counted label frame has a class id outside [0, max_classes); it was left out"),)
@@ -69,12 +70,14 @@ class RandomAccessLatest(NamedTuple):
 
 class _PoolEvents(_Windowed):
     """what `RandomAccessPool` and `StreamingPool` share: the resident event columns of R recordings with their timestamps corrected
-    once (`load_events`), and the frames of windows that are found through a row map (`_mapped_frames`)"""
+    once (`load_events`), and the frames of windows that are found through a row map (`_mapped_frames`).  Made with events=, it is a
+    frames driver over another pool's events: that pool's columns, corrected timestamps and counts, read by reference, with a
+    workspace, window bounds and error counters of its own (`StreamingPool(events=)`, and the union batch of `MixedPool`)."""
 
-    _events = None             # another pool whose columns, corrected timestamps and counts this one reads (StreamingPool(events=))
+    _module = "sampling"
 
     def __init__(self, labels, height, width, sequence_length, bins, count_cutoff, fastmode, duration_us, downsample_by_2, representation,
-                 window_capacity):
+                 window_capacity, events=None, events_name="the pool given as events="):
         if not isinstance(labels, LabelStreams):
             raise TypeError("sast_amd.sampling: labels must be a LabelStreams")
         if duration_us is None:
@@ -85,6 +88,13 @@ class _PoolEvents(_Windowed):
             raise ValueError("sast_amd.sampling: sequence_length must be an int in 1 .. 65535")
         if bool(labels.downsample_by_2) != bool(downsample_by_2):
             raise ValueError("sast_amd.sampling: labels.downsample_by_2 and downsample_by_2 must agree")
+        if events is not None and not isinstance(events, _PoolEvents):
+            raise TypeError("sast_amd.sampling: events must be a RandomAccessPool or a StreamingPool")
+        if events is not None and events.num_rows != labels.num_streams:
+            raise ValueError(f"sast_amd.sampling: events holds {events.num_rows} rows, the labels {labels.num_streams}")
+        while events is not None and events._events is not None:          # a pool that shares itself: read its source
+            events = events._events
+        self._events, self._events_name = events, events_name
         self.labels = labels
         self.num_rows = labels.num_streams
         self.sequence_length = sequence_length
@@ -99,34 +109,22 @@ class _PoolEvents(_Windowed):
         if self._events is not None:
             raise RuntimeError("sast_amd.sampling: this pool reads the events of the pool given as events=; load them there")
         R = self.num_rows
-        cols = [x, y, p, t]
-        for c, name in zip(cols, ("x", "y", "p", "t")):
-            if c.dim() != 2 or c.shape[0] != R:
-                raise ValueError(f"sast_amd.sampling: {name} must be [rows={R}, capacity], got shape {tuple(c.shape)}")
-            if not c.is_contiguous():
-                raise ValueError(f"sast_amd.sampling: {name} must be contiguous")
-        if not x.shape == y.shape == p.shape == t.shape:
-            raise ValueError("sast_amd.sampling: x, y, p and t must have the same shape")
-        codes = [_dtype_code(x, "x"), _dtype_code(y, "y"), _dtype_code(p, "p"), _dtype_code(t, "t", (torch.int64, torch.int32))]
-        if counts.dtype != torch.int64 or tuple(counts.shape) != (R,) or not counts.is_contiguous():
-            raise ValueError(f"sast_amd.sampling: counts must be a contiguous int64 tensor of shape [{R}]")
-        if reset is not None and (reset.dtype not in (torch.uint8, torch.bool) or tuple(reset.shape) != (R,) or not reset.is_contiguous()):
-            raise ValueError(f"sast_amd.sampling: reset must be a contiguous uint8 or bool tensor of shape [{R}]")
+        codes = F.event_columns(x, y, p, t, R, "sampling", rows_name="rows")
+        F.counts_reset(counts, reset, R, "sampling")
         cap = x.shape[1]
         if cap < 1 or R * cap > 2 ** 31 - 1:
             raise ValueError("sast_amd.sampling: capacity must be >= 1 and rows * capacity below 2^31")
         _need_gpu(x, y, p, t, counts, reset)
         dev = x.device
-        if len({c.device for c in cols + [counts] + ([reset] if reset is not None else [])}) != 1:
-            raise ValueError("sast_amd.sampling: x, y, p, t, counts and reset must be on the same device")
+        F.same_device("sampling", "x, y, p, t, counts and reset", x, y, p, t, counts, reset)
         if self.t is None or self.t.device != dev or self.t.shape[1] != cap:
-            _not_capturing()
+            F.not_capturing("sampling")
             self.t = torch.zeros(R, cap, dtype=torch.int64, device=dev)
             self.counts = torch.zeros(R, dtype=torch.int64, device=dev)
             self.t_last = None
             self._carry(dev, (R,))
             self._state = {"scan": torch.empty(int(L.lib().sast_evstreams_ws_count(R)), dtype=torch.int64, device=dev),
-                           "ones": torch.ones(R, dtype=torch.uint8, device=dev), "bounds": {}}
+                           "ones": torch.ones(R, dtype=torch.uint8, device=dev)}
             if reset is not None:
                 reset = None           # nothing to keep: every row is new
         st = self._state
@@ -146,25 +144,44 @@ class _PoolEvents(_Windowed):
         """(invalid events, windows over capacity) of the frames calls since the pool was made (synchronises)"""
         return _Windowed.errors(self)
 
+    def _source(self) -> "_PoolEvents":
+        """the pool whose loaded events this one's frames read: itself, or the one it was made over"""
+        src = self._events if self._events is not None else self
+        if src.x is None:
+            raise RuntimeError("sast_amd.sampling: call load_events() before frames()" + (f" (on {self._events_name})" if src is not self else ""))
+        return src
+
+    def _label_elems_guard(self, B: int) -> None:
+        """the label tensors of a batch of B columns are indexed in 32 bits, eight floats a row"""
+        if B * self.sequence_length * self.labels.max_labels_per_frame > (2 ** 31 - 1) // 8:
+            raise ValueError("sast_amd.sampling: B * sequence_length * max_labels_per_frame must be <= (2^31 - 1) / 8")
+
+    def _step_frames(self, batch, out_frames: Optional[torch.Tensor]) -> torch.Tensor:
+        """the frames of a batch that carries its row map per step (`step_rows` int32 [L, B], `ends_us` int64 [L, B]): every (step,
+        column) is a window of its own with its own row; a padded step's row is -1, which gives the empty range"""
+        step_rows, ends = batch.step_rows, batch.ends_us
+        _need_gpu(step_rows, ends, out_frames)
+        src = self._source()
+        Ls = self.sequence_length
+        F.tensor_arg(step_rows, "batch.step_rows", "sampling", (torch.int32,), (Ls, "B"))
+        B = step_rows.shape[1]
+        F.tensor_arg(ends, "batch.ends_us", "sampling", (torch.int64,), (Ls, B))
+        dev = src.t.device
+        if self.err is None or self.err.device != dev:            # a pool that reads another pool's events keeps its own counters
+            F.not_capturing("sampling")
+            self.err = torch.zeros(2, dtype=torch.int32, device=dev)
+        return self._mapped_frames(src, step_rows, Ls * B, 1, ends, (Ls, B) + self.get_shape(), out_frames)
+
     def _mapped_frames(self, src, row_map: torch.Tensor, cols: int, T: int, ends: torch.Tensor, shape, out_frames):
         """the frames of the T * cols windows ends[k, c] searched in row row_map[c] of `src`'s events (1 + 4 launches)"""
         R, cap = self.num_rows, src.t.shape[1]
         wcap = self.window_capacity if self.window_capacity is not None else cap
         self.ws_bytes(T * cols, wcap)             # ValueError for more windows than the histogram kernels take
         dev = src.t.device
-        if row_map.device != dev or ends.device != dev:
-            raise ValueError(f"sast_amd.sampling: the events live on {dev}, the batch on {row_map.device}")
-        if out_frames is None:
-            out_frames = torch.empty(shape, dtype=self.frame_dtype, device=dev)
-        elif out_frames.dtype != self.frame_dtype or tuple(out_frames.shape) != shape or not out_frames.is_contiguous() \
-                or out_frames.device != dev:
-            raise ValueError(f"sast_amd.sampling: out_frames must be a contiguous {str(self.frame_dtype).replace('torch.', '')} tensor of "
-                             f"shape {shape} on the events' device")
-        st = self._state
-        if T * cols not in st["bounds"]:
-            _not_capturing("one un-captured warm-up call with the same batch size is needed before graph capture")
-            st["bounds"][T * cols] = torch.empty(T * cols, 2, dtype=torch.int64, device=dev)
-        bounds = st["bounds"][T * cols]
+        for t in (row_map, ends):
+            F.lives_on("the pool's event storage", dev, "the batch", t.device, "sampling")
+        out_frames = F.frames_out(out_frames, shape, self.frame_dtype, dev, "sampling", "out_frames", "the events'")
+        bounds = self._bounds(T * cols, dev, "batch size")
         L.check(L.lib().sast_rnd_window_bounds(src.t.data_ptr(), src.counts.data_ptr(), R, cap, row_map.data_ptr(), ends.data_ptr(),
                                                           cols, T, self.mode, self.value, bounds.data_ptr(), _stream()),
                 "rnd_window_bounds")
@@ -238,18 +255,13 @@ class RandomAccessPool(_PoolEvents):
 
     # ---- the item index
     def _storage(self, dev):
-        la = self.labels._args
-        if la is None:
-            raise RuntimeError("sast_amd.sampling: call labels.load() before index()")
-        if self.labels.status.device != dev:
-            raise ValueError(f"sast_amd.sampling: the labels live on {self.labels.status.device}, the call's tensors on {dev}")
         if self._args is None:
-            _not_capturing()
-            R, F = self.num_rows, self.labels.max_frames
+            F.not_capturing("sampling")
+            R, Fr = self.num_rows, self.labels.max_frames
             self.start_idx_offset, self.length = (torch.zeros(R, dtype=torch.int32, device=dev) for _ in range(2))
             self.cum = torch.zeros(R + 1, dtype=torch.int64, device=dev)
             self.class_total = torch.zeros(self.max_classes, dtype=torch.int64, device=dev)
-            self.weights = torch.zeros(R * F, dtype=torch.float64, device=dev)
+            self.weights = torch.zeros(R * Fr, dtype=torch.float64, device=dev)
             self.status = torch.zeros(R + 1, dtype=torch.int32, device=dev)
             self._ticket = torch.zeros(1, dtype=torch.int32, device=dev)
             a = self._args = L.SastRndArgs()
@@ -285,21 +297,18 @@ class RandomAccessPool(_PoolEvents):
 
     def batch(self, items: torch.Tensor, out: Optional[Sequence[torch.Tensor]] = None) -> RandomAccessBatch:
         B, dev = self._items(items), items.device
-        if B * self.sequence_length * self.labels.max_labels_per_frame > (2 ** 31 - 1) // 8:
-            raise ValueError("sast_amd.sampling: B * sequence_length * max_labels_per_frame must be <= (2^31 - 1) / 8")
-        out = _outputs(RandomAccessBatch, self._want(B), out, dev, "sampling", "eight tensors of a RandomAccessBatch", "pool")
+        self._label_elems_guard(B)
+        out = F.outputs(RandomAccessBatch, self._want(B), out, dev, "sampling", "eight tensors of a RandomAccessBatch", "the pool's")
         L.check(L.lib().sast_rnd_gather(C.byref(self.labels._args), C.byref(self._args), items.data_ptr(), B, *(t.data_ptr() for t in out),
                                         _stream()), "rnd_gather")
         return out
 
     def _items(self, items: torch.Tensor) -> int:
-        if items.dtype != torch.int64 or items.dim() != 1 or items.numel() < 1 or not items.is_contiguous():
-            raise ValueError("sast_amd.sampling: items must be a contiguous int64 tensor of shape [B], B >= 1")
+        F.tensor_arg(items, "items", "sampling", (torch.int64,), ("B",))
         _need_gpu(items)
         if self._args is None:
             raise RuntimeError("sast_amd.sampling: call index() before batch() / latest()")
-        if items.device != self.status.device:
-            raise ValueError(f"sast_amd.sampling: the pool lives on {self.status.device}, items on {items.device}")
+        F.lives_on("the pool", self.status.device, "items", items.device, "sampling")
         return items.numel()
 
     def latest(self, items: torch.Tensor, out: Optional[Sequence[torch.Tensor]] = None) -> RandomAccessLatest:
@@ -307,8 +316,8 @@ class RandomAccessPool(_PoolEvents):
         M = self.labels.max_labels_per_frame
         if B * M > (2 ** 31 - 1) // 8:
             raise ValueError("sast_amd.sampling: B * max_labels_per_frame must be <= (2^31 - 1) / 8")
-        out = _outputs(RandomAccessLatest, (((B, M, 7), torch.float32), ((B,), torch.int32)), out, items.device, "sampling",
-                       "two tensors of a RandomAccessLatest", "pool")
+        out = F.outputs(RandomAccessLatest, (((B, M, 7), torch.float32), ((B,), torch.int32)), out, items.device, "sampling",
+                        "two tensors of a RandomAccessLatest", "the pool's")
         L.check(L.lib().sast_mixed_latest(C.byref(self.labels._args), C.byref(self._args), items.data_ptr(), B, out.latest.data_ptr(),
                                           out.latest_count.data_ptr(), _stream()), "mixed_latest")
         return out
@@ -316,15 +325,11 @@ class RandomAccessPool(_PoolEvents):
     def frames(self, batch: RandomAccessBatch, out_frames: Optional[torch.Tensor] = None) -> torch.Tensor:
         rows, ends = batch.rows, batch.ends_us
         _need_gpu(rows, ends, out_frames)
-        if self.x is None:
-            raise RuntimeError("sast_amd.sampling: call load_events() before frames()")
-        Ls, R, cap = self.sequence_length, self.num_rows, self.t.shape[1]
-        if rows.dtype != torch.int32 or rows.dim() != 1 or rows.numel() < 1 or not rows.is_contiguous():
-            raise ValueError("sast_amd.sampling: batch.rows must be a contiguous int32 tensor of shape [B]")
+        src, Ls = self._source(), self.sequence_length
+        F.tensor_arg(rows, "batch.rows", "sampling", (torch.int32,), ("B",))
         B = rows.numel()
-        if ends.dtype != torch.int64 or tuple(ends.shape) != (Ls, B) or not ends.is_contiguous():
-            raise ValueError(f"sast_amd.sampling: batch.ends_us must be a contiguous int64 tensor of shape [{Ls}, {B}]")
-        return self._mapped_frames(self, rows, B, Ls, ends, (Ls, B) + self.get_shape(), out_frames)
+        F.tensor_arg(ends, "batch.ends_us", "sampling", (torch.int64,), (Ls, B))
+        return self._mapped_frames(src, rows, B, Ls, ends, (Ls, B) + self.get_shape(), out_frames)
 
     def labelled_pairs(self, items_host) -> int:
         if self._host is None:
@@ -435,12 +440,8 @@ class StreamingPool(_PoolEvents):
                  bins: int = 10, count_cutoff: Optional[int] = 10, fastmode: bool = True, duration_us: int = 50_000,
                  downsample_by_2: bool = False, representation: str = "stacked_histogram", window_capacity: Optional[int] = None):
         super().__init__(labels, height, width, sequence_length, bins, count_cutoff, fastmode, duration_us, downsample_by_2, representation,
-                         window_capacity)
-        if events is not None and not isinstance(events, _PoolEvents):
-            raise TypeError("sast_amd.sampling: events must be a RandomAccessPool or a StreamingPool")
+                         window_capacity, events=events)
         R = self.num_rows
-        if events is not None and events.num_rows != R:
-            raise ValueError(f"sast_amd.sampling: events holds {events.num_rows} rows, the labels {R}")
         if max_sequences is None:
             max_sequences = R * labels.max_frames if guarantee_labels else R
         if isinstance(max_sequences, bool) or not isinstance(max_sequences, int) or not 1 <= max_sequences <= 2 ** 31 - 1:
@@ -451,9 +452,6 @@ class StreamingPool(_PoolEvents):
             raise ValueError("sast_amd.sampling: order_capacity must be an int in 1 .. 2^31 - 1")
         self.guarantee_labels = bool(guarantee_labels)
         self.max_sequences, self.order_capacity = max_sequences, order_capacity
-        while events is not None and events._events is not None:          # a pool that shares itself: read its source
-            events = events._events
-        self._events = events
         self.seq_row = self.seq_start = self.seq_stop = self.seq_samples = self.row_first_seq = self.n_seq = self.status = None
         self.order = self.order_len = self.cursor = None
         # _host: (sequences [n_seq, 4], per row the labelled windows) as numpy, from the last index()
@@ -462,7 +460,7 @@ class StreamingPool(_PoolEvents):
     # ---- the sequence table
     def _storage(self, dev):
         if self._args is None:
-            _not_capturing()
+            F.not_capturing("sampling")
             R, n = self.num_rows, self.max_sequences
             self._table = torch.zeros(4, n, dtype=torch.int32, device=dev)
             self.seq_row, self.seq_start, self.seq_stop, self.seq_samples = self._table.unbind(0)
@@ -552,7 +550,7 @@ class StreamingPool(_PoolEvents):
                 raise ValueError(f"sast_amd.sampling: batch row {b}'s schedule names sequence {bad[0]}, outside [0, {n})")
         dev = self.status.device
         if self.order is None or self.order.shape[0] != B:
-            _not_capturing("set_schedule with a new batch size allocates: call it before graph capture")
+            F.not_capturing("sampling", "set_schedule with a new batch size allocates: call it before graph capture")
             self.order = torch.full((B, self.order_capacity), -1, dtype=torch.int32, device=dev)
             self.order_len = torch.zeros(B, dtype=torch.int32, device=dev)
             self.cursor = torch.zeros(B, 2, dtype=torch.int32, device=dev)
@@ -610,33 +608,14 @@ class StreamingPool(_PoolEvents):
             raise RuntimeError("sast_amd.sampling: call set_schedule() before next()")
         dev = self.status.device
         B = self.order.shape[0]
-        if B * self.sequence_length * self.labels.max_labels_per_frame > (2 ** 31 - 1) // 8:
-            raise ValueError("sast_amd.sampling: B * sequence_length * max_labels_per_frame must be <= (2^31 - 1) / 8")
-        out = _outputs(StreamingBatch, self._want(B), out, dev, "sampling", "twelve tensors of a StreamingBatch", "pool")
+        self._label_elems_guard(B)
+        out = F.outputs(StreamingBatch, self._want(B), out, dev, "sampling", "twelve tensors of a StreamingBatch", "the pool's")
         L.check(L.lib().sast_stream_next(C.byref(self.labels._args), C.byref(self._args), B, *(t.data_ptr() for t in out), _stream()),
                 "stream_next")
         return out
 
     def frames(self, batch: StreamingBatch, out_frames: Optional[torch.Tensor] = None) -> torch.Tensor:
-        step_rows, ends = batch.step_rows, batch.ends_us
-        _need_gpu(step_rows, ends, out_frames)
-        src = self._events if self._events is not None else self
-        if src.x is None:
-            raise RuntimeError("sast_amd.sampling: call load_events() before frames()" + (" (on the pool given as events=)" if src is not self else ""))
-        Ls = self.sequence_length
-        if step_rows.dtype != torch.int32 or step_rows.dim() != 2 or step_rows.shape[0] != Ls or step_rows.shape[1] < 1 \
-                or not step_rows.is_contiguous():
-            raise ValueError(f"sast_amd.sampling: batch.step_rows must be a contiguous int32 tensor of shape [{Ls}, B]")
-        B = step_rows.shape[1]
-        if ends.dtype != torch.int64 or tuple(ends.shape) != (Ls, B) or not ends.is_contiguous():
-            raise ValueError(f"sast_amd.sampling: batch.ends_us must be a contiguous int64 tensor of shape [{Ls}, {B}]")
-        dev = src.t.device
-        if self.err is None or self.err.device != dev:            # a pool that reads another pool's events keeps its own counters
-            _not_capturing()
-            self.err = torch.zeros(2, dtype=torch.int32, device=dev)
-        self._state.setdefault("bounds", {})
-        # every (step, sample) is a window of its own with its own row: a padded step's row is -1, which gives the empty range
-        return self._mapped_frames(src, step_rows, Ls * B, 1, ends, (Ls, B) + self.get_shape(), out_frames)
+        return self._step_frames(batch, out_frames)
 
 
 class MixedBatch(NamedTuple):
@@ -724,10 +703,9 @@ class MixedPool:
         self.stream, self.random = stream, random
         self.labels, self.sequence_length, self.num_rows = stream.labels, stream.sequence_length, stream.num_rows
         # the frames driver of the union batch: its own workspace, window bounds and error counters over `random`'s events
-        d = self._driver = _PoolEvents(stream.labels, stream.height, stream.width, stream.sequence_length, stream.bins, stream.count_cutoff,
-                                       stream.fastmode, stream.value, stream.downsample_by_2, stream.representation, stream.window_capacity)
-        d._events = random
-        d._state = {"bounds": {}}
+        self._driver = _PoolEvents(stream.labels, stream.height, stream.width, stream.sequence_length, stream.bins, stream.count_cutoff,
+                                   stream.fastmode, stream.value, stream.downsample_by_2, stream.representation, stream.window_capacity,
+                                   events=random, events_name="the random pool")
         # Br -> two slots of (latest [Br, M, 7], latest_count [Br] in pinned host memory, their device sources, an event): the look-ahead
         # of step n + 1 is enqueued while step n's labels are still to be read
         self._pinned = {}
@@ -781,40 +759,21 @@ class MixedPool:
         if sp.order is None:
             raise RuntimeError("sast_amd.sampling: call set_schedule() on the stream pool before next()")
         dev = items.device
-        if sp.status.device != dev:
-            raise ValueError(f"sast_amd.sampling: the stream pool lives on {sp.status.device}, items on {dev}")
+        F.lives_on("the stream pool", sp.status.device, "items", dev, "sampling")
         Bs = sp.order.shape[0]
-        if (Bs + Br) * self.sequence_length * self.labels.max_labels_per_frame > (2 ** 31 - 1) // 8:
-            raise ValueError("sast_amd.sampling: B * sequence_length * max_labels_per_frame must be <= (2^31 - 1) / 8")
-        out = _outputs(MixedBatch, self._want(Bs, Br), out, dev, "sampling", "fourteen tensors of a MixedBatch", "pool")
+        sp._label_elems_guard(Bs + Br)
+        out = F.outputs(MixedBatch, self._want(Bs, Br), out, dev, "sampling", "fourteen tensors of a MixedBatch", "the pool's")
         L.check(L.lib().sast_mixed_next(C.byref(self.labels._args), C.byref(sp._args), C.byref(rp._args), Bs, items.data_ptr(), Br,
                                         *(t.data_ptr() for t in out), _stream()), "mixed_next")
         return out
 
     def frames(self, batch: MixedBatch, out_frames: Optional[torch.Tensor] = None) -> torch.Tensor:
-        step_rows, ends = batch.step_rows, batch.ends_us
-        _need_gpu(step_rows, ends, out_frames)
-        d, src = self._driver, self.random
-        if src.x is None:
-            raise RuntimeError("sast_amd.sampling: call load_events() on the random pool before frames()")
-        Ls = self.sequence_length
-        if step_rows.dtype != torch.int32 or step_rows.dim() != 2 or step_rows.shape[0] != Ls or step_rows.shape[1] < 1 \
-                or not step_rows.is_contiguous():
-            raise ValueError(f"sast_amd.sampling: batch.step_rows must be a contiguous int32 tensor of shape [{Ls}, B]")
-        B = step_rows.shape[1]
-        if ends.dtype != torch.int64 or tuple(ends.shape) != (Ls, B) or not ends.is_contiguous():
-            raise ValueError(f"sast_amd.sampling: batch.ends_us must be a contiguous int64 tensor of shape [{Ls}, {B}]")
-        dev = src.t.device
-        if d.err is None or d.err.device != dev:
-            _not_capturing()
-            d.err = torch.zeros(2, dtype=torch.int32, device=dev)
-        # every (step, column) is a window of its own with its own row, as in StreamingPool.frames
-        return d._mapped_frames(src, step_rows, Ls * B, 1, ends, (Ls, B) + d.get_shape(), out_frames)
+        return self._driver._step_frames(batch, out_frames)
 
     # ---- the zoom-in look-ahead
     def prefetch_latest(self, next_items: torch.Tensor) -> None:
         Br = self.random._items(next_items)
-        _not_capturing("prefetch_latest copies to the host: keep it outside graph capture")
+        F.not_capturing("sampling", "prefetch_latest copies to the host: keep it outside graph capture")
         if len(self._pending) >= 2:
             raise RuntimeError("sast_amd.sampling: two look-aheads are pending: call latest_labels() before the next prefetch_latest()")
         M = self.labels.max_labels_per_frame
@@ -834,7 +793,7 @@ class MixedPool:
     def latest_labels(self) -> List[Optional[torch.Tensor]]:
         if not self._pending:
             raise RuntimeError("sast_amd.sampling: call prefetch_latest() before latest_labels()")
-        _not_capturing("latest_labels waits for a host copy: keep it outside graph capture")
+        F.not_capturing("sampling", "latest_labels waits for a host copy: keep it outside graph capture")
         host, host_count, _staged, event = self._pending.pop(0)
         event.synchronize()
         return [host[b, :k] if k else None for b, k in enumerate(host_count.tolist())]
