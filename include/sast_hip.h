@@ -659,8 +659,8 @@ int sast_evq_schedule(const SastEvQueueArgs* q, int64_t* next_end, int mode, int
                           const uint8_t* reset, const uint8_t* final_flags, int64_t* ends, uint8_t* due, int64_t* backlog,
                           sast_stream_t stream);
 
-/* ---- raw sensor words (csrc/k_evt3.hip): Prophesee EVT 3.0, the 16-bit little-endian word stream a Gen4 / 1 Mpx sensor puts on the
- * wire, decoded on the device into the columns sast_evqueue_push takes.  The reference has no such stage (it reads .dat / .npy
+/* ---- raw sensor words (csrc/k_evt3.hip): Prophesee EVT 3.0, the 16-bit little-endian word stream IMX636 / GenX320 kits put on the
+ * wire by default (other kits of the Gen4 family send EVT 2.0: the next section), decoded on the device into the columns sast_evqueue_push takes.  The reference has no such stage (it reads .dat / .npy
  * files, utils/evaluation/prophesee/io/); the rule below is this project's contract, and parity with the Metavision SDK's decoder is
  * unpinned (the SDK is not a dependency).  type = w >> 12, v = w & 0xFFF; per stream the state y, base_x, vpol, low, high, wraps,
  * have_high, all 0 after a reset:
@@ -693,6 +693,48 @@ size_t sast_evt3_ws_bytes(int S);
 int sast_evt3_decode(const void* words, const int64_t* counts, int64_t chunk_words, int S, const uint8_t* reset, int64_t* state,
                      void* ws, int16_t* x, int16_t* y, int16_t* p, int64_t* t, int64_t max_events, int64_t* out_counts, int32_t* err,
                      sast_stream_t stream);
+
+/* ---- raw sensor words, EVT 2.0 and EVT 2.1 (csrc/k_evt2.hip): the 32-bit word stream the VGA (Gen3.1) and 720p Gen4 / Gen4.1
+ * evaluation kits send by default (one word is at most one event), and the 64-bit word stream IMX636 / GenX320 kits can be set to
+ * (one word is a 32-pixel vector), decoded on the device into the columns sast_evqueue_push takes.  As for EVT 3.0 the rule below is
+ * this project's contract: parity with the Metavision SDK's decoder is unpinned (the SDK is not a dependency); what is pinned is the
+ * sequential model of tests/evt2_model.py.  Per stream the state high, wraps, have_high, all 0 after a reset.
+ * EVT 2.0, 32-bit little-endian words, type = w >> 28:
+ *   0x0 CD_OFF, 0x1 CD_ON   one event (x = (w >> 11) & 0x7FF, y = w & 0x7FF, p = type, t) with ts6 = (w >> 22) & 0x3F
+ *   0x8 EVT_TIME_HIGH       v = w & 0x0FFFFFFF; have_high and high - v >= 2^27: wraps += 1; then high = v, have_high = 1
+ *   0xA EXT_TRIGGER, 0xE OTHERS, 0xF CONTINUED  valid, no effect;   0x2-0x7, 0x9, 0xB, 0xC, 0xD  no effect, counted as unknown words
+ * EVT 2.1, 64-bit little-endian words, type = w >> 60:
+ *   0x0 EVT_NEG, 0x1 EVT_POS   ts6 = (w >> 54) & 0x3F, x_base = (w >> 43) & 0x7FF, y = (w >> 32) & 0x7FF, valid = w & 0xFFFFFFFF: for
+ *                              every set bit i of valid, ascending, an event (x_base + i, y, p = type, t); valid == 0 gives nothing
+ *   0x8 EVT_TIME_HIGH          v = (w >> 32) & 0x0FFFFFFF, then as in EVT 2.0;   every other type as in EVT 2.0
+ * t = wraps * 2^34 + high * 64 + ts6 (microseconds).  A TIME_HIGH lower than its predecessor by less than 2^27 is taken as written:
+ * time steps back (the queue's running maximum holds it).  An event met while have_high is 0 is not given, it is counted.  Events
+ * come out in word order, inside an EVT 2.1 word by ascending bit.  x_base + i can reach 2078 and is stored as written: such an event
+ * stays outside the sensor (the frame kernels count it invalid).  An EVT 2.1 word is the 64-bit little-endian integer; a stream whose
+ * 32-bit halves arrive in the other order is the caller's to swap.  The state after a chunk is the state before the next one: a
+ * stream cut into chunks at any word gives the events, counters and state of the whole stream. */
+#define SAST_EVT2_V20 0
+#define SAST_EVT2_V21 1
+#define SAST_EVT2_STATE_WORDS 4       /* a row of `state`: high, wraps, have_high, 0 */
+#define SAST_EVT2_THREAD_WORDS 4      /* words a thread takes in one step: a row's pieces are multiples of this */
+#define SAST_EVT2_BLOCK_WORDS 1024    /* words a workgroup takes in one step; a row gets ceil(chunk_words / this) workgroups ... */
+#define SAST_EVT2_MAX_BLOCKS 256      /* ... at most this many, which then take several steps each */
+/* bytes of the decode's workspace (one summary per row for the state and for every workgroup).  0: S < 1 or S > 65535.  Host only. */
+size_t sast_evt2_ws_bytes(int S);
+/* per row s: with reset != NULL and reset[s] != 0 the row's state is zeroed first.  Then the first n_s = min(max(counts[s], 0),
+ * chunk_words) words of words[s] (version SAST_EVT2_V20: 32-bit words, SAST_EVT2_V21: 64-bit words, [S, chunk_words]) are decoded:
+ * the events go to x, y, p (int16) and t (int64) [S, max_events] from column 0 on, out_counts[s] = min(events, max_events) (of a row
+ * with more, the first max_events are kept), state[s] (int64 [S, SAST_EVT2_STATE_WORDS]) becomes the state after the chunk.  err,
+ * int32 [3], ACCUMULATED, with the meaning and order of sast_evt3_decode: [0] events before the first TIME_HIGH, [1] unknown words,
+ * [2] events dropped because the row's staging was full.  max_events = chunk_words (2.0) or 32 * chunk_words (2.1) never drops.
+ * SAST_EINVAL before any launch: a null pointer, S outside 1 .. 65535, an unknown version, chunk_words < 0, S * chunk_words or
+ * S * max_events > 2^31 - 1, for 2.1 chunk_words > (2^31 - 1) / 32, max_events < 1, words not aligned to its word size.  Loads are
+ * 16 bytes wide when words and every row of it are 16-byte aligned.  2 launches (one summary per workgroup; fold the summaries in
+ * front + decode + write, the row's last workgroup writes state, count and counters): no workgroup reads what another one writes in
+ * the same launch, and nothing has to be put back for a graph replay. */
+int sast_evt2_decode(const void* words, const int64_t* counts, int64_t chunk_words, int S, int version, const uint8_t* reset,
+                     int64_t* state, void* ws, int16_t* x, int16_t* y, int16_t* p, int64_t* t, int64_t max_events, int64_t* out_counts,
+                     int32_t* err, sast_stream_t stream);
 
 /* ---- label front end (csrc/k_labels.hip): the raw Prophesee box records of S recordings side by side -> the filtered labels, the
  * label-frame timestamps, the window-end schedule, the frame -> window map and per-step label tensors, all on the device.  The reference

@@ -16,15 +16,16 @@ binned by the logarithm of their age and accumulated over the bins), is `MixedDe
 `representation="mixed_density"` of `EventFrames` / `EventStreams`: the same windows, carries and error counters, int8 frames.
 
 `EventQueue` keeps the events that later windows still need on the device, so a host pushes chunks cut at arbitrary points (columns,
-Prophesee's packed Event2D records, or the raw EVT 3.0 words of a sensor) and gets the frames `EventStreams` gives for the whole
-recording.  `Evt3Decoder` is the stateful decode of those words alone (csrc/k_evt3.hip).
+Prophesee's packed Event2D records, or the raw EVT 3.0 / EVT 2.0 / EVT 2.1 words of a sensor) and gets the frames `EventStreams`
+gives for the whole recording.  `Evt3Decoder` (csrc/k_evt3.hip) and `Evt2Decoder` (csrc/k_evt2.hip) are the stateful decodes of those
+words alone; `raw_header` (host only) reads the format, the geometry and the end of a .raw file's ASCII header.
 
 There is no CPU path: CPU tensors raise the library's "no CPU fallback" error.
 """
 from __future__ import annotations
 
 import ctypes as C
-from typing import Optional, Tuple
+from typing import Dict, NamedTuple, Optional, Tuple
 
 import torch
 
@@ -417,8 +418,8 @@ class Evt3Decoder:
 
     dec = Evt3Decoder(num_streams, max_events=None)
     x, y, p, t, n = dec(words, counts, reset=None)
-      words: int16 / uint16 [S, chunk_words], the raw little-endian 16-bit words of S sensors side by side, cut anywhere (the caller
-        skips a .raw file's ASCII header); counts: int64 [S], the words at the head of each row; reset: uint8 / bool [S], non-zero for
+      words: int16 / uint16 [S, chunk_words], the raw little-endian 16-bit words of S sensors side by side, cut anywhere (`raw_header`
+        finds the end of a .raw file's ASCII header); counts: int64 [S], the words at the head of each row; reset: uint8 / bool [S], non-zero for
         the rows whose decoder state (row, vector base, time) is zeroed before this chunk: a new recording.
       -> x, y, p int16 [S, max_events], t int64 [S, max_events] (microseconds, wraps of the 24-bit sensor clock unrolled), n int64 [S]
         the events at the head of each row: what `EventQueue.push` / `EventStreams` take.  The tensors are the decoder's staging
@@ -487,6 +488,169 @@ class Evt3Decoder:
         return self.x, self.y, self.p, self.t, self.counts
 
 
+# version -> (the library's code, word dtypes, events one word can give, the words in the dtype message)
+_EVT2_VERSIONS = {
+    "2.0": (L.EVT2_V20, tuple(d for d in (torch.int32, getattr(torch, "uint32", None)) if d is not None), 1, "(one EVT 2.0 word each)"),
+    "2.1": (L.EVT2_V21, (torch.int64,), 32, "(one EVT 2.1 word each)"),
+}
+
+
+def _evt2_version(version) -> str:
+    if version not in _EVT2_VERSIONS:
+        raise ValueError(f"sast_amd.events: version must be one of {tuple(_EVT2_VERSIONS)}, got {version!r}")
+    return version
+
+
+class Evt2Decoder:
+    """Prophesee EVT 2.0 / EVT 2.1 sensor words -> event columns on the device (csrc/k_evt2.hip; the format tables and the decode rule
+    are in include/sast_hip.h and INTEGRATION.md §3b; parity with the Metavision SDK's decoder is unpinned, the SDK is not a
+    dependency: what is pinned is the sequential model of tests/evt2_model.py).
+
+    dec = Evt2Decoder(num_streams, max_events=None, version="2.0")
+    x, y, p, t, n = dec(words, counts, reset=None)
+      words: version "2.0": int32 (uint32 where torch has it) [S, chunk_words], one word is at most one event; version "2.1": int64
+        [S, chunk_words], one word is a 32-pixel vector, the 64-bit word as a little-endian integer (a stream whose 32-bit halves
+        arrive in the other order is the caller's to swap: `words.view(torch.int32).view(S, -1, 2).flip(-1)`).  The raw words of S
+        sensors side by side, cut anywhere (`raw_header` finds the end of a .raw file's ASCII header); counts: int64 [S], the words
+        at the head of each row; reset: uint8 / bool [S], non-zero for the rows whose decoder state (the time base) is zeroed before
+        this chunk: a new recording.
+      -> x, y, p int16 [S, max_events], t int64 [S, max_events] (microseconds, wraps of the 34-bit sensor clock unrolled), n int64 [S]
+        the events at the head of each row: what `EventQueue.push` / `EventStreams` take.  The tensors are the decoder's staging
+        columns: the next call overwrites them.  An EVT 2.1 vector may reach past column 2047 (x up to 2078): x is stored as written.
+    The state after a chunk is the state before the next one, per row: a stream decoded in chunks cut at any word gives the events of
+    the stream decoded whole.  max_events: the events one row's chunk may give (default chunk_words for "2.0", 32 * chunk_words for
+    "2.1", which can never drop one); of a row with more, the first max_events are kept and the rest counted.  `errors()`, `reset()`
+    and the counters' meaning and order are `Evt3Decoder`'s.  `state` is int64 [S, 4]: high, wraps, have_high, 0.
+    The state and the staging columns are allocated by the first un-captured call, never during capture; afterwards nothing is
+    allocated and nothing synchronises.  One call is 2 launches whatever S and the sizes are."""
+
+    DECODE_LAUNCHES = 2
+
+    def __init__(self, num_streams: int, max_events: Optional[int] = None, version: str = "2.0"):
+        self.num_streams = F.stream_count(num_streams, "events")
+        self.version = _evt2_version(version)
+        self._code, self._dtypes, self.fanout, self._what = _EVT2_VERSIONS[self.version]
+        if max_events is not None and int(max_events) < 1:
+            raise ValueError("sast_amd.events: max_events must be >= 1 (or None)")
+        self.max_events = None if max_events is None else int(max_events)
+        if self.max_events is not None and self.num_streams * self.max_events > 2 ** 31 - 1:
+            raise ValueError("sast_amd.events: num_streams * max_events must be below 2^31")
+        self.state = self.err = self.counts = self.x = self.y = self.p = self.t = self._ws = None
+
+    def _buffers(self, dev, chunk_words: int):
+        S = self.num_streams
+        if self.state is None:
+            F.not_capturing("events")
+            self.state = torch.zeros(S, L.EVT2_STATE_WORDS, dtype=torch.int64, device=dev)
+            self.err = torch.zeros(3, dtype=torch.int32, device=dev)
+            self.counts = torch.zeros(S, dtype=torch.int64, device=dev)
+            self._ws = torch.zeros(int(L.lib().sast_evt2_ws_bytes(S)), dtype=torch.uint8, device=dev)
+        F.lives_on("the decoder's state", self.state.device, "the call's tensors", dev, "events")
+        need = self.max_events if self.max_events is not None else max(self.fanout * chunk_words, 1)
+        if self.x is None or self.x.shape[1] < need:
+            F.not_capturing("events")
+            if S * need > 2 ** 31 - 1:
+                raise ValueError("sast_amd.events: num_streams * max_events must be below 2^31")
+            self.x, self.y, self.p = (torch.zeros(S, need, dtype=torch.int16, device=dev) for _ in range(3))
+            self.t = torch.zeros(S, need, dtype=torch.int64, device=dev)
+
+    def errors(self) -> Tuple[int, int, int]:
+        """(events before the first TIME_HIGH, unknown words, events dropped for lack of staging) since the last reset() (synchronises)"""
+        return F.counters(self.err, 3)
+
+    def reset(self, streams=None):
+        """new recordings, from the host: the decoder state of `streams` (default: all of them) back to zero; with streams=None the
+        counters are cleared as well"""
+        F.reset_rows((self.state,), self.err, streams, self.num_streams, "events")
+
+    def __call__(self, words: torch.Tensor, counts: torch.Tensor, reset: Optional[torch.Tensor] = None):
+        S = self.num_streams
+        F.tensor_arg(words, "words", "events", self._dtypes, (("num_streams", S), "chunk words"), self._what, empty_ok=True,
+                     dtype_error=TypeError)
+        F.counts_reset(counts, reset, S, "events")
+        chunk_words = words.shape[1]
+        if S * chunk_words > 2 ** 31 - 1 or self.fanout * chunk_words > 2 ** 31 - 1:
+            raise ValueError(f"sast_amd.events: num_streams * chunk words and {self.fanout} * chunk words must be below 2^31")
+        _need_gpu(words, counts, reset)
+        F.same_device("events", "words, counts and reset", words, counts, reset)
+        self._buffers(counts.device, chunk_words)
+        # an empty chunk has no storage: any valid device pointer will do, the kernels read no word
+        L.check(L.lib().sast_evt2_decode(words.data_ptr() or self.t.data_ptr(), counts.data_ptr(), chunk_words, S, self._code,
+                                         None if reset is None else reset.data_ptr(), self.state.data_ptr(), self._ws.data_ptr(),
+                                         self.x.data_ptr(), self.y.data_ptr(), self.p.data_ptr(), self.t.data_ptr(), self.x.shape[1],
+                                         self.counts.data_ptr(), self.err.data_ptr(), _stream()), "evt2_decode")
+        return self.x, self.y, self.p, self.t, self.counts
+
+
+class RawHeader(NamedTuple):
+    """what `raw_header` reads: format "evt2" / "evt21" / "evt3" / None, width and height (None where the header names none), offset the
+    index of the first data byte, fields {key: the rest of the line} of every header line"""
+    format: Optional[str]
+    width: Optional[int]
+    height: Optional[int]
+    offset: int
+    fields: Dict[str, str]
+
+
+_RAW_FORMATS = {"EVT2": "evt2", "EVT20": "evt2", "EVT21": "evt21", "EVT3": "evt3", "EVT30": "evt3",
+                "2": "evt2", "20": "evt2", "21": "evt21", "3": "evt3", "30": "evt3"}
+
+
+def _to_int(text: str) -> Optional[int]:
+    text = text.strip()
+    return int(text) if text.isdigit() else None
+
+
+def raw_header(data) -> RawHeader:
+    """The ASCII header of a Prophesee .raw file -> RawHeader(format, width, height, offset, fields).  Host only: `data` is bytes, a
+    bytearray or a memoryview holding the head of the file; the sensor words start at data[offset:].
+
+    The header is the run of lines starting with '%' at the head of the file.  The line "% end" ends it right after its newline,
+    whatever byte follows (a data byte may be 0x25, '%'); without a "% end" line it ends at the first line that does not start with
+    '%'.  A '\\r' before the newline is dropped.  `fields` maps each line's key (its first word behind the '%') to the rest of the
+    line; the "% end" line is no field.  format: from "% format EVT3;height=720;width=1280" (the value up to the first ';', then
+    key=value pairs), failing that from "% evt 3.0"; width and height: from the pairs of the format field, failing that from
+    "% geometry 1280x720", else None.  A buffer that ends inside the header (in the middle of a line, or behind a header line that
+    is not "% end" with nothing after it to tell whether another follows) raises ValueError: more bytes are needed.
+    This is this project's reading of such files; parity with the Metavision SDK's reader is unpinned (the SDK is not a dependency)."""
+    if not isinstance(data, (bytes, bytearray, memoryview)):
+        raise TypeError(f"sast_amd.events: raw_header takes bytes, a bytearray or a memoryview, got a {type(data).__name__}")
+    buf = bytes(data)
+    more = "sast_amd.events: the buffer ends inside the .raw header: more bytes are needed"
+    fields: Dict[str, str] = {}
+    at = 0
+    while True:
+        if at >= len(buf):
+            raise ValueError(more)
+        if buf[at] != 0x25:
+            break
+        nl = buf.find(b"\n", at)
+        if nl < 0:
+            raise ValueError(more)
+        line = buf[at + 1:nl]
+        at = nl + 1
+        if line.endswith(b"\r"):
+            line = line[:-1]
+        key, _sep, rest = line.decode("latin-1").strip().partition(" ")
+        if key == "end" and not rest.strip():
+            break
+        if key:
+            fields[key] = rest.strip()
+    fmt = width = height = None
+    if "format" in fields:
+        name, *pairs = fields["format"].split(";")
+        fmt = _RAW_FORMATS.get(name.strip().upper().replace(".", ""))
+        geo = dict(pair.split("=", 1) for pair in pairs if "=" in pair)
+        width, height = _to_int(geo.get("width", "")), _to_int(geo.get("height", ""))
+    if fmt is None and "evt" in fields:
+        fmt = _RAW_FORMATS.get(fields["evt"].strip().replace(".", ""))
+    if (width is None or height is None) and "geometry" in fields:
+        w, _x, h = fields["geometry"].lower().partition("x")
+        if _to_int(w) is not None and _to_int(h) is not None:
+            width, height = _to_int(w), _to_int(h)
+    return RawHeader(fmt, width, height, at, fields)
+
+
 _QUEUE_ERRORS = ("{} invalid events (x or y outside the sensor, or a polarity outside 0..1); they were skipped",
                  "{} windows hold more events than window_capacity; they were left empty",
                  "{} events were dropped: their row of the queue was full (capacity >= 2 x the row's live events right after a `frames` call + all events pushed between two `frames` calls never drops)",
@@ -509,6 +673,10 @@ class EventQueue(_Windowed):
     q.push_evt3(words, counts, reset=None)      int16 / uint16 [S, chunk_words]: raw EVT 3.0 sensor words, counts in words, cut at any
                                                 word (`Evt3Decoder`: the stateful decode runs on the device, 2 launches, in front of
                                                 the append); `evt3_errors()` gives the decoder's three counters.
+    q.push_evt2(words, counts, reset=None, max_events=None, version="2.0")
+                                                int32 [S, chunk_words] raw EVT 2.0 words, or with version="2.1" int64 [S, chunk_words]
+                                                raw EVT 2.1 words (`Evt2Decoder`, 2 launches in front of the append);
+                                                `evt2_errors()` gives that decoder's three counters.
     frames = q.frames(ends_us, out=None, check=False)    ends_us int64 [S] or [T, S] -> frames as `EventStreams` returns them
     q.reset(streams=None); q.errors(); q.get_shape()
 
@@ -549,6 +717,7 @@ class EventQueue(_Windowed):
 
     PUSH_LAUNCHES = 2
     PUSH_EVT3_LAUNCHES = Evt3Decoder.DECODE_LAUNCHES + PUSH_LAUNCHES
+    PUSH_EVT2_LAUNCHES = Evt2Decoder.DECODE_LAUNCHES + PUSH_LAUNCHES
     FRAMES_LAUNCHES = 7
 
     def __init__(self, num_streams: int, capacity: int, height: int, width: int, bins: int = 10, count_cutoff: Optional[int] = 10,
@@ -567,6 +736,7 @@ class EventQueue(_Windowed):
         self.x = self.y = self.p = self.t = self.head = self.count = self.retired = self.retired_t = None
         self._args = None
         self.evt3: Optional[Evt3Decoder] = None       # made by the first push_evt3
+        self.evt2: Optional[Evt2Decoder] = None       # made by the first push_evt2
 
     def _storage(self, dev):
         """the queue's state on `dev` (allocated by the first ordinary call)"""
@@ -596,6 +766,8 @@ class EventQueue(_Windowed):
         with streams=None the error counters are cleared as well"""
         if self.evt3 is not None:
             self.evt3.reset(streams)
+        if self.evt2 is not None:
+            self.evt2.reset(streams)
         F.reset_rows((self.head, self.count, self.t_last, self.retired, self.retired_t), self.err, streams, self.num_streams, "events")
 
     def _push(self, ptrs, codes, chunk_cap, counts, reset, tensors):
@@ -638,6 +810,28 @@ class EventQueue(_Windowed):
         """the decoder's counters of `push_evt3`: (events before the first TIME_HIGH, unknown words, events dropped for lack of
         staging) (synchronises); `errors()` keeps the queue's four"""
         return (0, 0, 0) if self.evt3 is None else self.evt3.errors()
+
+    def push_evt2(self, words: torch.Tensor, counts: torch.Tensor, reset: Optional[torch.Tensor] = None,
+                  max_events: Optional[int] = None, version: str = "2.0") -> None:
+        """raw EVT 2.0 (int32 [S, chunk_words]) or, with version="2.1", EVT 2.1 (int64 [S, chunk_words]) sensor words, counts int64 [S]
+        in WORDS, as `Evt2Decoder` takes them: the decode (2 launches) into the decoder's staging columns, then the append of `push` on
+        those columns and the decoder's device-side event counts (2 launches).  reset[s] != 0 zeroes row s's decoder state and empties
+        its queue row together.  version and max_events (the decoder's staging per row; default chunk_words / 32 * chunk_words: never
+        drops) are fixed by the first call: a later call with another of either raises ValueError."""
+        if self.evt2 is None:
+            self.evt2 = Evt2Decoder(self.num_streams, max_events, version)
+        elif _evt2_version(version) != self.evt2.version:
+            raise ValueError(f"sast_amd.events: the queue's decoder was made with version={self.evt2.version!r}, got {version!r}")
+        elif max_events is not None and int(max_events) != self.evt2.max_events:
+            raise ValueError(f"sast_amd.events: the queue's decoder was made with max_events={self.evt2.max_events}, got {max_events}")
+        F.counts_reset(counts, reset, self.num_streams, "events")
+        x, y, p, t, n = self.evt2(words, counts, reset)
+        self.push(x, y, p, t, n, reset)
+
+    def evt2_errors(self) -> Tuple[int, int, int]:
+        """the decoder's counters of `push_evt2`: (events before the first TIME_HIGH, unknown words, events dropped for lack of
+        staging) (synchronises); `errors()` keeps the queue's four"""
+        return (0, 0, 0) if self.evt2 is None else self.evt2.errors()
 
     def frames(self, ends_us: torch.Tensor, out: Optional[torch.Tensor] = None, check: bool = False) -> torch.Tensor:
         S, cap = self.num_streams, self.capacity

@@ -81,8 +81,9 @@ class OnlineDetector:
       detector: a `YoloXDetector` in eval mode; queue: an `EventQueue` with duration windows (duration_us = D) for S <= 256 streams;
       first_end_us: the end of every recording's first window (default D, must be >= D).
     od.push(x, y, p, t, counts, reset=None, final=None) / od.push_dat(records, counts, reset=None, final=None) /
-    od.push_evt3(words, counts, reset=None, final=None)
-      the chunk of `EventQueue.push` / `push_dat` / `push_evt3` (raw EVT 3.0 sensor words, counts in words); reset uint8 / bool [S]:
+    od.push_evt3(words, counts, reset=None, final=None) / od.push_evt2(words, counts, reset=None, final=None, version="2.0")
+      the chunk of `EventQueue.push` / `push_dat` / `push_evt3` (raw EVT 3.0 sensor words, counts in words) / `push_evt2` (raw EVT 2.0
+      or, with version="2.1", EVT 2.1 sensor words, counts in words); reset uint8 / bool [S]:
       the flagged rows start a new recording with this chunk (queue row, recurrent state and schedule start over); final uint8 / bool
       [S]: the flagged recordings are over, their last windows are given although no later event will come.
     od.poll() -> the finished steps' detections, oldest first: a list of (stream, numpy array of `labels.BBOX_DTYPE`), one entry per due
@@ -93,7 +94,7 @@ class OnlineDetector:
     od.errors() -> (invalid events, windows over capacity, dropped events, late windows, detections cut by max_det, windows due but
       not yet given after the last push) (synchronises).
 
-    One push, whatever the data: queue push (2 launches; 4 for push_evt3, the decode in front); `zero_samples_dev` of the held states
+    One push, whatever the data: queue push (2 launches; 4 for push_evt3 / push_evt2, the decode in front); `zero_samples_dev` of the held states
     by `reset`; the schedule (1 launch) -> ends, due [W, S]; `queue.frames(ends)` (7 launches); then for k < W the detector forward on
     frames[k] with the held states, `commit_samples_dev(held, new, due[k])`, `postprocess_padded` and the record export.  A row whose
     window k is not due runs on the frame of the last window it gave and its new (h, c) is dropped, so its state is bit for bit what
@@ -208,6 +209,10 @@ class OnlineDetector:
     def push_evt3(self, words: torch.Tensor, counts: torch.Tensor, reset: Optional[torch.Tensor] = None,
                   final: Optional[torch.Tensor] = None) -> None:
         self._step(lambda c, r: self.queue.push_evt3(words, c, r), (words,), counts, reset, final)
+
+    def push_evt2(self, words: torch.Tensor, counts: torch.Tensor, reset: Optional[torch.Tensor] = None,
+                  final: Optional[torch.Tensor] = None, version: str = "2.0") -> None:
+        self._step(lambda c, r: self.queue.push_evt2(words, c, r, version=version), (words,), counts, reset, final)
 
     # ------------------------------------------------------------------------------------------------------------------ graph
     def capture(self) -> None:
