@@ -953,7 +953,7 @@ int sast_augment_labels(const float* labels, const int32_t* counts, const int32_
  * summarize.  Nothing synchronises with the host; what does not fit a capacity is counted in the state words, never dropped silently.
  *   state  int32 [SAST_EVAL_STATE_WORDS]: 0 images, 1 ground-truth rows, 2 detection rows, 3 records, 4..7 records per category,
  *          8 frames refused for max_images, 9 for max_detections, 10 for max_labels_per_frame, 11 sast_eval_add calls since the reset,
- *          12.. non-ignored ground truths [K][4]
+ *          12..27 non-ignored ground truths [K][4], 28 images refused for sast_evrec_add's max_window, 29 rows it refused as unsorted
  *   tables gt_box fp32 [max_images * max_labels_per_frame][4] (x, y, w, h), gt_cls / gt_img int32; det_box fp32 [max_detections][5]
  *          (x, y, w, h, score), det_cls / det_img int32; img_t int64 [max_images]: image i is the i-th frame that kept a label
  *   records rec_key / rec_match / rec_ign uint64 [max_detections]: bit (area * 10 + threshold) of match / ignore; key = category << 62 |
@@ -972,7 +972,7 @@ int sast_augment_labels(const float* labels, const int32_t* counts, const int32_
  * sast_evmerge_append(dst, src) appends the buffer `src` to `dst` on the device: afterwards dst is what it would be had it been fed
  * src's frames after its own (src is left as it was).  Images, img_t, ground-truth rows, detection rows and records are appended, gt_img /
  * det_img grow by dst's image count, the index bits of rec_key by dst's record count (the index breaks score ties: dst's records keep
- * going first), state words 0-7, 11 and 12.. are added, and so are src's own refusal counters 8-10.  All counts are read on the device (two
+ * going first), state words 0-7, 11 and 12-27 are added, and so are src's own refusal counters 8-10, 28 and 29.  All counts are read on the device (two
  * launches, no host synchronisation, replayable in a graph).  All or nothing: when src's images, ground-truth rows, detections or records
  * do not fit what is left of dst's max_images, max_images * max_labels_per_frame or max_detections, nothing is appended and src's image
  * count is added to dst's refusal word of every capacity that was exceeded (8, 10, 9 in that order of capacities).  Refused on the host
@@ -1008,6 +1008,41 @@ size_t sast_eval_sort_ws_bytes(int64_t max_detections);
 int sast_eval_accumulate(const SastEvalArgs* a, sast_stream_t stream);
 int sast_evmerge_append(const SastEvalArgs* dst, const SastEvalArgs* src, sast_stream_t stream);
 
+/* ---- whole recordings into the evaluation buffer (csrc/k_eval.hip): the Prophesee protocol itself, one label file against one
+ * detection file per recording -- evaluate_list(apply_bbox_filters=True) (evaluation.py:5-42) and evaluate_detection's loop over files
+ * with _match_times (metrics/coco_eval.py:42-90).  gt / dt: int32 [S, Gcap, 10] / [S, Dcap, 10], the 40-byte BBOX_DTYPE records as ten
+ * words (the layout sast_labels_load takes and sast_detections_export writes), the first n_gt[s] / n_dt[s] (int64, clamped to the
+ * capacity on the device) of a row valid and sorted by t.  Per row, in row order:
+ *   filter   a record passes when t > 500 000, w*w + h*h >= min_diag2, w >= min_side and h >= min_side (fp32, as sast_eval_add); labels
+ *            and detections alike, each detection on its own t;
+ *   images   the unique t of the passing labels, ascending; an image's ground truth is the passing labels of that t in record order,
+ *            its detections the passing detections with t - time_tol_us <= t_det <= t + time_tol_us in record order (a detection
+ *            inside several windows is a result row and a record in each); x, y, w, h, class_confidence and class_id are taken from
+ *            the record as they are;
+ *   then     sast_eval_add's cut to 100 per (image, category), IoU, matching and records: the same kernels, instantiated on record
+ *            ranges instead of padded frames.  The two calls may be mixed in one buffer; both count in state word 11.
+ * Refusals, counted in the state and never silent: max_images and max_detections (memberships) per image as for sast_eval_add;
+ * max_labels_per_frame per timestamp, on the passing labels; an image whose window holds more than max_window records BEFORE the filter
+ * (1 <= max_window <= 8192: it sizes the LDS sort) in word 28; a row whose valid records are not sorted by t, labels or detections,
+ * adds nothing and counts in word 29.
+ * 4 launches, no host synchronisation, every grid sized from S, Gcap and K: (1) one workgroup per row -- the sorted check and the row's
+ * image starts, compacted by a workgroup scan; (2) one wave per image slot -- the two binary searches, the counts; (3) one thread -- the
+ * offsets, walking the images of the rows in order (not the S * Gcap slots); (4) one wave per (image slot, category) -- tables and
+ * matching.  Refused on the host (SAST_EINVAL): null pointers, S outside 1 .. 65535, Gcap or Dcap < 1, S * Gcap > (2^31 - 1) / 16,
+ * S * Dcap > 2^31 - 1, max_window outside 1 .. 8192, time_tol_us < 0, gt / dt not 8-byte aligned, ws_bytes < sast_evrec_ws_bytes. */
+typedef struct {
+  const int32_t* gt;       /* [S, Gcap, 10] */
+  const int64_t* n_gt;     /* [S] */
+  const int32_t* dt;       /* [S, Dcap, 10] */
+  const int64_t* n_dt;     /* [S] */
+  int32_t S, Gcap, Dcap, max_window;
+  int64_t time_tol_us;
+  void* ws;                /* scratch of one call, sast_evrec_ws_bytes(S, Gcap) bytes; no initial contents needed */
+  size_t ws_bytes;
+} SastEvRecArgs;
+size_t sast_evrec_ws_bytes(int S, int Gcap);   /* 0: an argument out of range.  Host only. */
+int sast_evrec_add(const SastEvalArgs* buf, const SastEvRecArgs* rec, sast_stream_t stream);
+
 /* ---- detections as Prophesee box records (csrc/k_eval.hip): what to_prophesee (io/box_loading.py:81-97) makes of one frame's
  * post-processed detections on the host, written on the device for the S rows of one online step.  A record is 40 bytes, little-endian:
  *   offset 0 int64 t (the window end), 8 fp32 x = x1, 12 fp32 y = y1, 16 fp32 w = x2 - x1, 20 fp32 h = y2 - y1 (one fp32 subtraction
@@ -1027,6 +1062,19 @@ typedef struct {
 } SastDetExportArgs;
 #define SAST_DET_RECORD_BYTES 40
 int sast_detections_export(const SastDetExportArgs* a, sast_stream_t stream);
+/* the detection log of an online run: what sast_evrec_add takes as dt / n_dt.  Row s appends the counts[s] (clamped to [0, max_det])
+ * records sast_detections_export wrote for one step behind its log_counts[s] records and raises the count.  A step's records that do not
+ * fit the row's capacity are dropped WHOLE and *dropped += 1; a row with counts[s] == 0 is left alone.  1 launch, one wave per row. */
+typedef struct {
+  const uint8_t* records;  /* [S, max_det, 40] of one step, 8-byte aligned */
+  const int32_t* counts;   /* [S] */
+  int32_t* log;            /* [S, capacity, 10], 8-byte aligned */
+  int64_t* log_counts;     /* [S] */
+  int32_t* dropped;        /* [1], ACCUMULATED */
+  int64_t capacity;
+  int32_t S, max_det;
+} SastDetLogArgs;
+int sast_detlog_append(const SastDetLogArgs* a, sast_stream_t stream);
 
 /* ---- tuning knobs.  Every SAST_* environment variable the library reads (tile / split / launch-shape choices, all defaulting to the
  * measured-best setting: DESIGN.md section 7) goes through one registry: the value is read from the environment at first use and cached;

@@ -18,10 +18,21 @@
 //                         the order is the stable one), the chunk-parallel walk of every category's sorted records (counts, scan over
 //                         the chunks, precision maxima, envelope, backward walk: the 101 recall thresholds), and the six summaries.
 //   sast_evmerge_append   one buffer behind another (two launches, no host synchronisation): what joins the buffers of several ranks
+//   sast_evrec_add        S whole recordings as sorted 40-byte box records, labels and detections: evaluate_detection's loop over
+//                         "files" (coco_eval.py:42-51) with _match_times' windows.  Four launches, no host synchronisation
+//                           images  one 1024-thread workgroup per row: the sorted check, then the first passing label of every
+//                                   timestamp, compacted by a workgroup scan into the row's list of image starts
+//                           count, scan, match   the kernels of sast_eval_add, instantiated on record ranges: an image's labels are the
+//                                   records of its timestamp, its detections the records with t - tol <= t_det <= t + tol (two
+//                                   binary searches), each filtered on its own; the scan walks the images, not the label slots
+//   sast_detlog_append    the exported records of one online step behind the per-stream logs sast_evrec_add reads (one launch)
+// The count and match kernels read an image's rows through a SOURCE they are parameterised on: FrameRows (padded [N, M, 7] /
+// [N, A, 7] rows, one frame per image) or RecordRows (ranges of records).  There is one matching.
 // Every fp32 / fp64 operation of the reference is repeated one rounding at a time: build.py compiles this file with -ffp-contract=off.
 #include "common.cuh"
 #include "kernels.h"
 
+#include <climits>
 #include <cstring>
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -40,9 +51,13 @@ constexpr unsigned long long EV_IDX_MASK = (1ull << 30) - 1;
 constexpr int EV_MAX_ANCHORS = 8192, EV_MAX_LABELS = 128;
 
 // state words
-enum { ST_IMAGES = 0, ST_GT = 1, ST_DET = 2, ST_REC = 3, ST_REC_CAT = 4, ST_ERR_IMAGES = 8, ST_ERR_DETS = 9, ST_ERR_LABELS = 10, ST_ADDS = 11, ST_NPIG = 12 };
-// info words of a frame
-enum { IN_VALID = 0, IN_NGT = 1, IN_NDT = 2, IN_NREC = 3, IN_IMG = 8, IN_GT_OFF = 9, IN_DET_OFF = 10, IN_REC_OFF = 11 };
+enum { ST_IMAGES = 0, ST_GT = 1, ST_DET = 2, ST_REC = 3, ST_REC_CAT = 4, ST_ERR_IMAGES = 8, ST_ERR_DETS = 9, ST_ERR_LABELS = 10, ST_ADDS = 11, ST_NPIG = 12,
+       ST_ERR_WINDOW = 28, ST_ERR_UNSORTED = 29 };
+// info words of a frame (an image candidate); 12..15 are RecordRows' alone
+enum { IN_VALID = 0, IN_NGT = 1, IN_NDT = 2, IN_NREC = 3, IN_IMG = 8, IN_GT_OFF = 9, IN_DET_OFF = 10, IN_REC_OFF = 11,
+       IN_GHI = 12, IN_DLO = 13, IN_DHI = 14, IN_OVER = 15 };
+constexpr int REC_WORDS = SAST_DET_RECORD_BYTES / 4;   // a BBOX_DTYPE record as int32 words: 0-1 t, 2-5 x y w h, 6 class_id, 8 score
+constexpr int EV_MAX_WINDOW = 8192;
 
 __device__ __forceinline__ bool box_passes(float w, float h, float diag2, float side) {
   const float d = w * w + h * h;   // fp32, one rounding each (box_filtering.py:34)
@@ -55,8 +70,6 @@ __device__ __forceinline__ bool label_passes(const float* r, float diag2, float 
   return (long long)r[0] > EV_SKIP_US && box_passes(r[3], r[4], diag2, side);
 }
 
-__device__ __forceinline__ bool det_passes(const float* r, float diag2, float side) { return box_passes(r[2] - r[0], r[3] - r[1], diag2, side); }
-
 // ascending on the result = ascending on the float (-0 == +0)
 __device__ __forceinline__ unsigned score_key(float s) {
   if (s == 0.f) s = 0.f;
@@ -67,29 +80,151 @@ __device__ __forceinline__ unsigned score_key(float s) {
 __device__ __forceinline__ int frame_labels(const SastEvalArgs& a, int n) { return min(max(a.counts[n], 0), a.M); }
 __device__ __forceinline__ int frame_dets(const SastEvalArgs& a, int n) { return min(max(a.n_det[n], 0), a.A); }
 
-__global__ void __launch_bounds__(64) eval_count_kernel(SastEvalArgs a) {
+// ---- the two sources of an image's rows.  A source answers: how many label / detection rows the image has, whether row i passes
+// filter_boxes and what its box is, whether the detections count at all, and the image's timestamp.  `open` is the count kernel's
+// (it may leave what it found in the image's info words), `reopen` the match kernel's.
+struct Box {
+  float x, y, w, h, score;
+  unsigned cls;
+};
+
+// sast_eval_add: frame n of padded label rows [N, M, 7] and padded detections [N, A, 7]
+struct FrameRows {
+  struct Args {};
+  const float* lab;
+  const float* dt;
+  int cnt, nd;
+  __device__ __forceinline__ void bind(const SastEvalArgs& a, int n) {
+    lab = a.labels + (size_t)n * a.M * 7, dt = a.det + (size_t)n * a.A * 7;
+    cnt = frame_labels(a, n), nd = frame_dets(a, n);
+  }
+  __device__ __forceinline__ bool open(const SastEvalArgs& a, const Args&, int n, int*, int) {
+    bind(a, n);
+    return true;
+  }
+  __device__ __forceinline__ void reopen(const SastEvalArgs& a, const Args&, int n, const int*) { bind(a, n); }
+  __device__ __forceinline__ int labels_n() const { return cnt; }
+  __device__ __forceinline__ int dets_n() const { return nd; }
+  __device__ __forceinline__ bool dets_live() const { return (long long)lab[0] > EV_SKIP_US; }   // the detections carry the frame's one timestamp (box_loading.py:90)
+  __device__ __forceinline__ long long time() const { return (long long)lab[0]; }
+  __device__ __forceinline__ bool label(const SastEvalArgs& a, int i, Box& b) const {
+    const float* r = lab + i * 7;
+    b.x = r[1], b.y = r[2], b.w = r[3], b.h = r[4], b.score = r[6], b.cls = class_of(r[5]);
+    return label_passes(r, a.min_diag2, a.min_side);
+  }
+  __device__ __forceinline__ bool det(const SastEvalArgs& a, int i, Box& b) const {
+    const float* r = dt + (size_t)i * 7;
+    b.x = r[0], b.y = r[1], b.w = r[2] - r[0], b.h = r[3] - r[1], b.score = r[5], b.cls = class_of(r[6]);
+    return box_passes(b.w, b.h, a.min_diag2, a.min_side);
+  }
+};
+
+__device__ __forceinline__ long long rec_time(const int* row, long long i) { return *reinterpret_cast<const long long*>(row + i * REC_WORDS); }
+
+__device__ __forceinline__ bool rec_box(const int* row, long long i, float diag2, float side, Box& b) {
+  const int* r = row + i * REC_WORDS;
+  b.x = __int_as_float(r[2]), b.y = __int_as_float(r[3]), b.w = __int_as_float(r[4]), b.h = __int_as_float(r[5]);
+  b.cls = (unsigned)r[6], b.score = __int_as_float(r[8]);
+  return rec_time(row, i) > EV_SKIP_US && box_passes(b.w, b.h, diag2, side);
+}
+
+// first index in [lo, hi) of a sorted row whose t is >= v (strict: > v)
+__device__ __forceinline__ int rec_bound(const int* row, int lo, int hi, long long v, bool strict) {
+  while (lo < hi) {
+    const int m = lo + ((hi - lo) >> 1);
+    const long long t = rec_time(row, m);
+    if (strict ? t <= v : t < v) lo = m + 1;
+    else hi = m;
+  }
+  return lo;
+}
+
+__device__ __forceinline__ int rec_rows(const long long* n, int s, int cap) { return (int)min(max(n[s], 0ll), (long long)cap); }
+
+// sast_evrec_add: image j of row s (n = s * Gcap + j) is the j-th entry of the row's list of image starts.  Its labels are the records
+// of that timestamp, its detections the records inside [t - tol, t + tol]; both rows were found sorted by evrec_images_kernel.
+struct RecordRows {
+  struct Args {
+    const int* gt;
+    const long long* n_gt;
+    const int* dt;
+    const long long* n_dt;
+    int* starts;     // [S][Gcap] label index of a row's images, ascending
+    int* nimg;       // [S]
+    int* unsorted;   // [S]
+    int S, Gcap, Dcap, max_window;
+    long long tol;
+  };
+  const int* g;
+  const int* d;
+  int cnt, nd;
+  long long t;
+  bool over;
+  __device__ __forceinline__ int first(const Args& r, int n, int s, const int*& grow) {
+    grow = r.gt + (size_t)s * r.Gcap * REC_WORDS;
+    return min(max(r.starts[n], 0), max(rec_rows(r.n_gt, s, r.Gcap) - 1, 0));
+  }
+  __device__ __forceinline__ bool open(const SastEvalArgs&, const Args& r, int n, int* info, int lane) {
+    const int s = n / r.Gcap, j = n - s * r.Gcap;
+    if (j >= min(r.nimg[s], r.Gcap)) return false;
+    const int ng = rec_rows(r.n_gt, s, r.Gcap), ndt = rec_rows(r.n_dt, s, r.Dcap);
+    const int* grow;
+    const int i0 = first(r, n, s, grow);
+    const int* drow = r.dt + (size_t)s * r.Dcap * REC_WORDS;
+    t = rec_time(grow, i0);
+    const int ghi = rec_bound(grow, i0, ng, t, true);
+    const long long lo_t = t < LLONG_MIN + r.tol ? LLONG_MIN : t - r.tol, hi_t = t > LLONG_MAX - r.tol ? LLONG_MAX : t + r.tol;
+    const int dlo = rec_bound(drow, 0, ndt, lo_t, false), dhi = rec_bound(drow, dlo, ndt, hi_t, true);
+    over = dhi - dlo > r.max_window;
+    if (lane == 0) info[IN_GHI] = ghi, info[IN_DLO] = dlo, info[IN_DHI] = dhi, info[IN_OVER] = over;
+    g = grow + (size_t)i0 * REC_WORDS, cnt = ghi - i0;
+    d = drow + (size_t)dlo * REC_WORDS, nd = dhi - dlo;
+    return true;
+  }
+  __device__ __forceinline__ void reopen(const SastEvalArgs&, const Args& r, int n, const int* info) {
+    const int s = n / r.Gcap;
+    const int* grow;
+    const int i0 = first(r, n, s, grow);
+    t = rec_time(grow, i0), over = false;
+    g = grow + (size_t)i0 * REC_WORDS, cnt = info[IN_GHI] - i0;
+    d = r.dt + ((size_t)s * r.Dcap + info[IN_DLO]) * REC_WORDS, nd = info[IN_DHI] - info[IN_DLO];
+  }
+  __device__ __forceinline__ int labels_n() const { return cnt; }
+  __device__ __forceinline__ int dets_n() const { return nd; }
+  __device__ __forceinline__ bool dets_live() const { return !over; }   // a window over max_window is refused by the scan
+  __device__ __forceinline__ long long time() const { return t; }
+  __device__ __forceinline__ bool label(const SastEvalArgs& a, int i, Box& b) const { return rec_box(g, i, a.min_diag2, a.min_side, b); }
+  __device__ __forceinline__ bool det(const SastEvalArgs& a, int i, Box& b) const { return rec_box(d, i, a.min_diag2, a.min_side, b); }
+};
+
+template <class Src>
+__global__ void __launch_bounds__(64) eval_count_kernel(SastEvalArgs a, typename Src::Args sa) {
   const int n = blockIdx.x, lane = threadIdx.x;
-  const int cnt = frame_labels(a, n);
-  const float* lab = a.labels + (size_t)n * a.M * 7;
-  const float* det = a.det + (size_t)n * a.A * 7;
+  int* info = a.info + n * EV_INFO;
+  Src src;
+  if (!src.open(a, sa, n, info, lane)) {   // no image behind this slot
+    if (lane == 0) info[IN_VALID] = 0;
+    return;
+  }
+  const int cnt = src.labels_n();
+  Box b;
   int ngt = 0, ndt = 0, c[SAST_EVAL_MAX_CLASSES] = {0, 0, 0, 0};
   for (int base = 0; base < cnt; base += 64) {
     const int i = base + lane;
-    ngt += __popcll(__ballot(i < cnt && label_passes(lab + i * 7, a.min_diag2, a.min_side)));
+    ngt += __popcll(__ballot(i < cnt && src.label(a, i, b)));
   }
-  if (ngt > 0 && (long long)lab[0] > EV_SKIP_US) {   // the detections carry the frame's one timestamp (box_loading.py:90)
-    const int nd = frame_dets(a, n);
+  if (ngt > 0 && src.dets_live()) {
+    const int nd = src.dets_n();
     for (int base = 0; base < nd; base += 64) {
       const int i = base + lane;
-      const bool keep = i < nd && det_passes(det + (size_t)i * 7, a.min_diag2, a.min_side);
-      const unsigned cls = keep ? class_of(det[(size_t)i * 7 + 6]) : 0u;
+      const bool keep = i < nd && src.det(a, i, b);
+      const unsigned cls = keep ? b.cls : 0u;
       ndt += __popcll(__ballot(keep));
 #pragma unroll
       for (int k = 0; k < SAST_EVAL_MAX_CLASSES; ++k) c[k] += __popcll(__ballot(keep && cls == (unsigned)k));
     }
   }
   if (lane == 0) {
-    int* info = a.info + n * EV_INFO;
     info[IN_VALID] = ngt > 0;
     info[IN_NGT] = ngt;
     info[IN_NDT] = ndt;
@@ -98,30 +233,114 @@ __global__ void __launch_bounds__(64) eval_count_kernel(SastEvalArgs a) {
   }
 }
 
+// the sequential part of an add: image / table / record offsets in image order, capacity checks that count instead of dropping
+struct ScanCursor {
+  int img, gt, dt, rec;
+};
+
+__device__ __forceinline__ void scan_image(const SastEvalArgs& a, int* info, ScanCursor& c) {
+  int* st = a.state;
+  int nrec = 0;
+  for (int k = 0; k < a.K; ++k) nrec += info[IN_NREC + k];
+  int* err = nullptr;
+  if (info[IN_NGT] > a.max_labels_per_frame) err = st + ST_ERR_LABELS;
+  else if (c.img >= a.max_images) err = st + ST_ERR_IMAGES;
+  else if ((long long)c.dt + info[IN_NDT] > a.max_detections) err = st + ST_ERR_DETS;
+  if (err) {   // counted, reported by the host at evaluate time; the frame writes nothing
+    *err += 1;
+    info[IN_VALID] = 0;
+    return;
+  }
+  info[IN_IMG] = c.img, info[IN_GT_OFF] = c.gt, info[IN_DET_OFF] = c.dt, info[IN_REC_OFF] = c.rec;
+  c.img += 1, c.gt += info[IN_NGT], c.dt += info[IN_NDT], c.rec += nrec;
+  for (int k = 0; k < a.K; ++k) st[ST_REC_CAT + k] += info[IN_NREC + k];
+}
+
+__device__ __forceinline__ ScanCursor scan_begin(const int* st) { return ScanCursor{st[ST_IMAGES], st[ST_GT], st[ST_DET], st[ST_REC]}; }
+
+__device__ __forceinline__ void scan_end(int* st, const ScanCursor& c) {
+  st[ST_IMAGES] = c.img, st[ST_GT] = c.gt, st[ST_DET] = c.dt, st[ST_REC] = c.rec;
+  st[ST_ADDS] += 1;   // a replayed graph adds without the host's knowledge: "has data" is decided from this word
+}
+
 __global__ void eval_scan_kernel(SastEvalArgs a) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  int* st = a.state;
-  int img = st[ST_IMAGES], gt = st[ST_GT], dt = st[ST_DET], rec = st[ST_REC];
+  ScanCursor c = scan_begin(a.state);
   for (int n = 0; n < a.N; ++n) {
     int* info = a.info + n * EV_INFO;
-    if (!info[IN_VALID]) continue;
-    int nrec = 0;
-    for (int k = 0; k < a.K; ++k) nrec += info[IN_NREC + k];
-    int* err = nullptr;
-    if (info[IN_NGT] > a.max_labels_per_frame) err = st + ST_ERR_LABELS;
-    else if (img >= a.max_images) err = st + ST_ERR_IMAGES;
-    else if ((long long)dt + info[IN_NDT] > a.max_detections) err = st + ST_ERR_DETS;
-    if (err) {   // counted, reported by the host at evaluate time; the frame writes nothing
-      *err += 1;
-      info[IN_VALID] = 0;
+    if (info[IN_VALID]) scan_image(a, info, c);
+  }
+  scan_end(a.state, c);
+}
+
+// rows in order, and within a row its images: the walk is as long as the images, whatever Gcap is
+__global__ void evrec_scan_kernel(SastEvalArgs a, RecordRows::Args r) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  ScanCursor c = scan_begin(a.state);
+  for (int s = 0; s < r.S; ++s) {
+    if (r.unsorted[s]) {   // the reference asserts (coco_eval.py:43-44): the row adds nothing
+      a.state[ST_ERR_UNSORTED] += 1;
       continue;
     }
-    info[IN_IMG] = img, info[IN_GT_OFF] = gt, info[IN_DET_OFF] = dt, info[IN_REC_OFF] = rec;
-    img += 1, gt += info[IN_NGT], dt += info[IN_NDT], rec += nrec;
-    for (int k = 0; k < a.K; ++k) st[ST_REC_CAT + k] += info[IN_NREC + k];
+    const int ni = min(max(r.nimg[s], 0), r.Gcap);
+    for (int j = 0; j < ni; ++j) {
+      int* info = a.info + (s * r.Gcap + j) * EV_INFO;
+      if (!info[IN_VALID]) continue;
+      if (info[IN_OVER]) {   // more records in the window than the LDS sort was sized for
+        a.state[ST_ERR_WINDOW] += 1;
+        info[IN_VALID] = 0;
+        continue;
+      }
+      scan_image(a, info, c);
+    }
   }
-  st[ST_IMAGES] = img, st[ST_GT] = gt, st[ST_DET] = dt, st[ST_REC] = rec;
-  st[ST_ADDS] += 1;   // a replayed graph adds without the host's knowledge: "has data" is decided from this word
+  scan_end(a.state, c);
+}
+
+// One workgroup per row.  A row with a record whose t is below its predecessor's, labels or detections, gets no image.  Otherwise
+// label i starts an image when it passes the filter and no passing label of the same t lies before it; the starts are compacted in
+// order: per tile of 1024 slots a ballot per wave, the waves' counts through LDS.
+__global__ void __launch_bounds__(1024) evrec_images_kernel(SastEvalArgs a, RecordRows::Args r) {
+  __shared__ int wcount[16];
+  const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int ng = rec_rows(r.n_gt, s, r.Gcap), nd = rec_rows(r.n_dt, s, r.Dcap);
+  const int* grow = r.gt + (size_t)s * r.Gcap * REC_WORDS;
+  const int* drow = r.dt + (size_t)s * r.Dcap * REC_WORDS;
+  int bad = 0;
+  for (int i = tid + 1; i < ng; i += 1024) bad |= rec_time(grow, i) < rec_time(grow, i - 1);
+  for (int i = tid + 1; i < nd; i += 1024) bad |= rec_time(drow, i) < rec_time(drow, i - 1);
+  bad = __syncthreads_or(bad);
+  if (bad) {
+    if (tid == 0) r.nimg[s] = 0, r.unsorted[s] = 1;
+    return;
+  }
+  int* starts = r.starts + (size_t)s * r.Gcap;
+  int total = 0;
+  Box b;
+  for (int base = 0; base < ng; base += 1024) {   // ng is the workgroup's: every thread takes every turn
+    const int i = base + tid;
+    bool start = i < ng && rec_box(grow, i, a.min_diag2, a.min_side, b);
+    if (start) {
+      const long long t = rec_time(grow, i);
+      for (int j = i - 1; j >= 0 && rec_time(grow, j) == t; --j)
+        if (rec_box(grow, j, a.min_diag2, a.min_side, b)) {
+          start = false;
+          break;
+        }
+    }
+    const unsigned long long m = __ballot(start);
+    if (lane == 0) wcount[wave] = __popcll(m);
+    __syncthreads();
+    int before = 0, tile = 0;
+    for (int w = 0; w < 16; ++w) {
+      before += w < wave ? wcount[w] : 0;
+      tile += wcount[w];
+    }
+    if (start) starts[total + before + __popcll(m & ((1ull << lane) - 1))] = i;   // < ng <= Gcap: one slot per start
+    total += tile;
+    __syncthreads();
+  }
+  if (tid == 0) r.nimg[s] = total, r.unsorted[s] = 0;
 }
 
 struct MatchLds {
@@ -170,7 +389,8 @@ __device__ __forceinline__ void area_range(int ar, double& lo, double& hi) {
   hi = ar == 1 ? 1024.0 : ar == 2 ? 9216.0 : 1e10;      // (1e5)^2
 }
 
-__global__ void __launch_bounds__(64) eval_match_kernel(SastEvalArgs a, int P) {
+template <class Src>
+__global__ void __launch_bounds__(64) eval_match_kernel(SastEvalArgs a, typename Src::Args sa, int P) {
   extern __shared__ __align__(16) unsigned char lds_raw[];
   const int n = blockIdx.x, k = blockIdx.y, lane = threadIdx.x;
   const int* info = a.info + n * EV_INFO;
@@ -179,55 +399,53 @@ __global__ void __launch_bounds__(64) eval_match_kernel(SastEvalArgs a, int P) {
   MatchLds l;
   match_lds_carve(lds_raw, P, G, &l);
   const unsigned long long lt = (1ull << lane) - 1;
-  const int cnt = frame_labels(a, n), nd_all = info[IN_NDT] > 0 ? frame_dets(a, n) : 0;
-  const float* lab = a.labels + (size_t)n * a.M * 7;
-  const float* det = a.det + (size_t)n * a.A * 7;
+  Src src;
+  src.reopen(a, sa, n, info);
+  const int cnt = src.labels_n(), nd_all = info[IN_NDT] > 0 ? src.dets_n() : 0;
   const int img = info[IN_IMG];
+  Box b;
 
   // ---- the flattened tables, in frame order (category 0's wave)
   if (k == 0) {
     int go = info[IN_GT_OFF], dofs = info[IN_DET_OFF];
     for (int base = 0; base < cnt; base += 64) {
       const int i = base + lane;
-      const float* r = lab + i * 7;
-      const bool keep = i < cnt && label_passes(r, a.min_diag2, a.min_side);
+      const bool keep = i < cnt && src.label(a, i, b);
       const unsigned long long m = __ballot(keep);
       if (keep) {
         const int p = go + __popcll(m & lt);
-        a.gt_box[(size_t)p * 4 + 0] = r[1], a.gt_box[(size_t)p * 4 + 1] = r[2], a.gt_box[(size_t)p * 4 + 2] = r[3], a.gt_box[(size_t)p * 4 + 3] = r[4];
-        a.gt_cls[p] = (int)class_of(r[5]);
+        a.gt_box[(size_t)p * 4 + 0] = b.x, a.gt_box[(size_t)p * 4 + 1] = b.y, a.gt_box[(size_t)p * 4 + 2] = b.w, a.gt_box[(size_t)p * 4 + 3] = b.h;
+        a.gt_cls[p] = (int)b.cls;
         a.gt_img[p] = img;
       }
       go += __popcll(m);
     }
     for (int base = 0; base < nd_all; base += 64) {
       const int i = base + lane;
-      const float* r = det + (size_t)i * 7;
-      const bool keep = i < nd_all && det_passes(r, a.min_diag2, a.min_side);
+      const bool keep = i < nd_all && src.det(a, i, b);
       const unsigned long long m = __ballot(keep);
       if (keep) {
         const int p = dofs + __popcll(m & lt);
         float* o = a.det_box + (size_t)p * 5;
-        o[0] = r[0], o[1] = r[1], o[2] = r[2] - r[0], o[3] = r[3] - r[1], o[4] = r[5];
-        a.det_cls[p] = (int)class_of(r[6]);
+        o[0] = b.x, o[1] = b.y, o[2] = b.w, o[3] = b.h, o[4] = b.score;
+        a.det_cls[p] = (int)b.cls;
         a.det_img[p] = img;
       }
       dofs += __popcll(m);
     }
-    if (lane == 0) a.img_t[img] = (long long)lab[0];
+    if (lane == 0) a.img_t[img] = src.time();
   }
 
   // ---- ground truth of category k, in label order
   int ng = 0;
   for (int base = 0; base < cnt; base += 64) {
     const int i = base + lane;
-    const float* r = lab + i * 7;
-    const bool keep = i < cnt && label_passes(r, a.min_diag2, a.min_side) && class_of(r[5]) == (unsigned)k;
+    const bool keep = i < cnt && src.label(a, i, b) && b.cls == (unsigned)k;
     const unsigned long long m = __ballot(keep);
     if (keep) {
       const int p = ng + __popcll(m & lt);   // < G: the scan refused frames with more boxes than that
-      l.gbox[p * 4 + 0] = r[1], l.gbox[p * 4 + 1] = r[2], l.gbox[p * 4 + 2] = r[3], l.gbox[p * 4 + 3] = r[4];
-      l.garea[p] = (double)(r[3] * r[4]);    // the fp32 product, widened (coco_eval.py:167, :172)
+      l.gbox[p * 4 + 0] = b.x, l.gbox[p * 4 + 1] = b.y, l.gbox[p * 4 + 2] = b.w, l.gbox[p * 4 + 3] = b.h;
+      l.garea[p] = (double)(b.w * b.h);      // the fp32 product, widened (coco_eval.py:167, :172)
     }
     ng += __popcll(m);
   }
@@ -235,14 +453,13 @@ __global__ void __launch_bounds__(64) eval_match_kernel(SastEvalArgs a, int P) {
   int c = 0;
   for (int base = 0; base < nd_all; base += 64) {
     const int i = base + lane;
-    const float* r = det + (size_t)i * 7;
-    const bool keep = i < nd_all && det_passes(r, a.min_diag2, a.min_side) && class_of(r[6]) == (unsigned)k;
+    const bool keep = i < nd_all && src.det(a, i, b) && b.cls == (unsigned)k;
     const unsigned long long m = __ballot(keep);
-    if (keep) l.keys[c + __popcll(m & lt)] = ((unsigned long long)(~score_key(r[5])) << 32) | (unsigned)i;
+    if (keep) l.keys[c + __popcll(m & lt)] = ((unsigned long long)(~score_key(b.score)) << 32) | (unsigned)i;
     c += __popcll(m);
   }
   int P2 = 1;
-  while (P2 < c) P2 <<= 1;   // <= P: c <= A
+  while (P2 < c) P2 <<= 1;   // <= P: c <= A (FrameRows), c <= max_window (RecordRows)
   for (int i = c + lane; i < P2; i += 64) l.keys[i] = ~0ull;
   __syncthreads();
   for (int size = 2; size <= P2; size <<= 1)
@@ -258,11 +475,10 @@ __global__ void __launch_bounds__(64) eval_match_kernel(SastEvalArgs a, int P) {
   for (int d = lane; d < nd; d += 64) l.dsel[d] = (int)(l.keys[d] & 0xffffffffu);
   __syncthreads();   // the key region becomes the IoU tile
   for (int d = lane; d < nd; d += 64) {
-    const float* r = det + (size_t)l.dsel[d] * 7;
-    const float w = r[2] - r[0], h = r[3] - r[1];
-    l.dbox[d * 4 + 0] = r[0], l.dbox[d * 4 + 1] = r[1], l.dbox[d * 4 + 2] = w, l.dbox[d * 4 + 3] = h;
-    l.darea[d] = (double)(w * h);
-    l.dscore[d] = r[5];
+    src.det(a, l.dsel[d], b);
+    l.dbox[d * 4 + 0] = b.x, l.dbox[d * 4 + 1] = b.y, l.dbox[d * 4 + 2] = b.w, l.dbox[d * 4 + 3] = b.h;
+    l.darea[d] = (double)(b.w * b.h);
+    l.dscore[d] = b.score;
   }
   for (int e = lane; e < ng * 64; e += 64) l.gm[e] = 0;
   if (lane < EV_A) {   // per area range: ignore flags, and the ground truths not ignored first, stably
@@ -627,6 +843,7 @@ __global__ void evmerge_publish_kernel(SastEvalArgs d, SastEvalArgs s) {
   const int* ss = s.state;
   st[ST_ERR_IMAGES] += max(ss[ST_ERR_IMAGES], 0), st[ST_ERR_DETS] += max(ss[ST_ERR_DETS], 0), st[ST_ERR_LABELS] += max(ss[ST_ERR_LABELS], 0);
   st[ST_ADDS] += max(ss[ST_ADDS], 0);
+  st[ST_ERR_WINDOW] += max(ss[ST_ERR_WINDOW], 0), st[ST_ERR_UNSORTED] += max(ss[ST_ERR_UNSORTED], 0);   // sast_evrec_add's refusals
   if (!m.fits()) {   // counted, reported by the host at evaluate time; nothing was appended
     const int lost = max(m.ni_s, 1);
     if (m.over_img) st[ST_ERR_IMAGES] += lost;
@@ -681,6 +898,51 @@ __global__ __launch_bounds__(64) void detections_export_kernel(SastDetExportArgs
   }
 }
 
+// One workgroup per row: the m = counts[s] records of one step go behind the row's log, or nowhere when they do not fit.  Every
+// thread reads the log's count before the barrier, thread 0 raises it behind it.  Records move as five 8-byte words.
+__global__ __launch_bounds__(64) void detlog_append_kernel(SastDetLogArgs a) {
+  const int s = blockIdx.x;
+  const int m = min(max(a.counts[s], 0), a.max_det);
+  const long long n = min(max((long long)a.log_counts[s], 0ll), (long long)a.capacity);
+  if (m == 0) return;
+  if (n + m > a.capacity) {   // the step is dropped whole, and counted
+    if (threadIdx.x == 0) atomicAdd(a.dropped, 1);
+    return;
+  }
+  const unsigned long long* __restrict__ src = reinterpret_cast<const unsigned long long*>(a.records + (size_t)s * a.max_det * SAST_DET_RECORD_BYTES);
+  unsigned long long* __restrict__ dst = reinterpret_cast<unsigned long long*>(a.log) + ((size_t)s * a.capacity + n) * (SAST_DET_RECORD_BYTES / 8);
+  for (int i = threadIdx.x; i < m * (SAST_DET_RECORD_BYTES / 8); i += 64) dst[i] = src[i];
+  __syncthreads();
+  if (threadIdx.x == 0) a.log_counts[s] = n + m;
+}
+
+// the dynamic LDS a match instantiation may ask for (grown monotonically; racing callers set the same attribute)
+template <class Src>
+bool match_lds_allow(size_t lds) {
+  static size_t allowed = 0;
+  if (lds > allowed) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(eval_match_kernel<Src>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+      return false;
+    allowed = lds;
+  }
+  return true;
+}
+
+constexpr long long EVREC_MAX_SLOTS = 0x7fffffffll / EV_INFO;   // S * Gcap: an info index stays an int
+
+struct EvRecWs {
+  int* info;       // [S * Gcap][16]
+  int* starts;     // [S * Gcap]
+  int* nimg;       // [S]
+  int* unsorted;   // [S]
+};
+
+size_t evrec_ws_carve(void* ws, long long S, long long Gcap, EvRecWs* w) {
+  int* p = (int*)ws;
+  if (w) w->info = p, w->starts = p + S * Gcap * EV_INFO, w->nimg = p + S * Gcap * (EV_INFO + 1), w->unsorted = p + S * Gcap * (EV_INFO + 1) + S;
+  return sizeof(int) * (size_t)(S * Gcap * (EV_INFO + 1) + 2 * S);
+}
+
 }  // namespace
 }  // namespace sast
 
@@ -706,16 +968,57 @@ int sast_eval_add(const SastEvalArgs* a, sast_stream_t stream) {
   int P = 64;
   while (P < a->A) P <<= 1;
   const size_t lds = match_lds_carve(nullptr, P, a->max_labels_per_frame, nullptr);
-  static size_t lds_allowed = 0;   // (grown monotonically; racing callers set the same attribute)
-  if (lds > lds_allowed) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(eval_match_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-      return SAST_EINVAL;
-    lds_allowed = lds;
-  }
+  if (!match_lds_allow<FrameRows>(lds)) return SAST_EINVAL;
   const hipStream_t st = (hipStream_t)stream;
-  SAST_LAUNCH(eval_count_kernel, dim3((unsigned)a->N), dim3(64), 0, st, *a);
+  const FrameRows::Args rows{};
+  SAST_LAUNCH(eval_count_kernel<FrameRows>, dim3((unsigned)a->N), dim3(64), 0, st, *a, rows);
   SAST_LAUNCH(eval_scan_kernel, dim3(1), dim3(64), 0, st, *a);
-  SAST_LAUNCH(eval_match_kernel, dim3((unsigned)a->N, (unsigned)a->K), dim3(64), lds, st, *a, P);
+  SAST_LAUNCH(eval_match_kernel<FrameRows>, dim3((unsigned)a->N, (unsigned)a->K), dim3(64), lds, st, *a, rows, P);
+  SAST_CHECK_LAUNCH();
+  return SAST_OK;
+}
+
+size_t sast_evrec_ws_bytes(int S, int Gcap) {
+  if (S < 1 || S > 65535 || Gcap < 1 || (long long)S * Gcap > sast::EVREC_MAX_SLOTS) return 0;
+  return sast::evrec_ws_carve(nullptr, S, Gcap, nullptr);
+}
+
+int sast_evrec_add(const SastEvalArgs* buf, const SastEvRecArgs* rec, sast_stream_t stream) {
+  SAST_ENTRY();
+  using namespace sast;
+  if (!eval_args_ok(buf) || !evmerge_tables_ok(buf) || !buf->iou_thr || !rec || !rec->gt || !rec->n_gt || !rec->dt || !rec->n_dt || !rec->ws)
+    return SAST_EINVAL;
+  if (rec->S < 1 || rec->S > 65535 || rec->Gcap < 1 || rec->Dcap < 1 || (long long)rec->S * rec->Gcap > EVREC_MAX_SLOTS ||
+      (long long)rec->S * rec->Dcap > 0x7fffffffll || rec->max_window < 1 || rec->max_window > EV_MAX_WINDOW || rec->time_tol_us < 0 ||
+      rec->ws_bytes < evrec_ws_carve(nullptr, rec->S, rec->Gcap, nullptr) || ((reinterpret_cast<uintptr_t>(rec->gt) | reinterpret_cast<uintptr_t>(rec->dt)) & 7) ||
+      (reinterpret_cast<uintptr_t>(rec->ws) & 3))
+    return SAST_EINVAL;
+  EvRecWs w;
+  evrec_ws_carve(rec->ws, rec->S, rec->Gcap, &w);
+  SastEvalArgs a = *buf;   // the buffer, with this call's scratch as the per-image info; the frame fields are not read
+  a.info = w.info;
+  a.N = rec->S * rec->Gcap;
+  const RecordRows::Args rows{rec->gt, (const long long*)rec->n_gt, rec->dt, (const long long*)rec->n_dt, w.starts, w.nimg, w.unsorted,
+                              rec->S, rec->Gcap, rec->Dcap, rec->max_window, (long long)rec->time_tol_us};
+  int P = 64;
+  while (P < rec->max_window) P <<= 1;
+  const size_t lds = match_lds_carve(nullptr, P, a.max_labels_per_frame, nullptr);
+  if (!match_lds_allow<RecordRows>(lds)) return SAST_EINVAL;
+  const hipStream_t st = (hipStream_t)stream;
+  SAST_LAUNCH(evrec_images_kernel, dim3((unsigned)rec->S), dim3(1024), 0, st, a, rows);
+  SAST_LAUNCH(eval_count_kernel<RecordRows>, dim3((unsigned)a.N), dim3(64), 0, st, a, rows);
+  SAST_LAUNCH(evrec_scan_kernel, dim3(1), dim3(64), 0, st, a, rows);
+  SAST_LAUNCH(eval_match_kernel<RecordRows>, dim3((unsigned)a.N, (unsigned)a.K), dim3(64), lds, st, a, rows, P);
+  SAST_CHECK_LAUNCH();
+  return SAST_OK;
+}
+
+int sast_detlog_append(const SastDetLogArgs* a, sast_stream_t stream) {
+  SAST_ENTRY();
+  if (!a || !a->records || !a->counts || !a->log || !a->log_counts || !a->dropped || a->S < 1 || a->S > 65535 || a->max_det < 1 ||
+      a->capacity < 1 || ((reinterpret_cast<uintptr_t>(a->records) | reinterpret_cast<uintptr_t>(a->log)) & 7))
+    return SAST_EINVAL;
+  SAST_LAUNCH(sast::detlog_append_kernel, dim3((unsigned)a->S), dim3(64), 0, (hipStream_t)stream, *a);
   SAST_CHECK_LAUNCH();
   return SAST_OK;
 }

@@ -12,13 +12,17 @@ on the device: `add` takes the label tensors `SpatialAugmentor` returns and the 
 - Each added frame is its own "file" of the reference's _match_times: a frame none of whose labels passes the filter is no image and
   its detections vanish with it; image ids follow the order of `add` calls and of the rows within a call.
 - What does not fit `max_images`, `max_detections` (filtered detections over the whole buffer) or `max_labels_per_frame` (filtered
-  labels of one frame) is counted on the device and raised by `evaluate_buffer`, never dropped silently.
+  labels of one frame) is counted on the device and raised by `evaluate_buffer`, never dropped silently; so are `add_recordings`'
+  windows over `max_window_detections` and its unsorted rows.
 - `merge` appends another evaluator's buffer on the device (one call, no sync), `export_buffer` / `import_buffer` move a buffer as a
   dict of trimmed tensors, and `all_gather` joins the buffers of all ranks of a process group in rank order: every rank then computes
   the numbers of ONE evaluator fed rank 0's frames, then rank 1's, ... -- the dataset's mAP, whatever the number of ranks.  The
   reference averages per-rank metrics instead, which is not the dataset's AP (precision over recall is not linear in the shards).
-- Not implemented: the multi-timestamp form of _match_times (to_prophesee asserts one timestamp per entry), AR and maxDets 1 / 10
-  (the reference discards them), visualisation.
+- `add_recordings` is the protocol's own form: whole recordings as sorted box records, one label "file" against one detection "file"
+  per row, every unique label timestamp an image with the detections within +-time_tol_us (_match_times, metrics/coco_eval.py:55-90).
+  It feeds the same count, scan and match kernels through a second row source and may be mixed with `add` in one buffer.
+- Not implemented: AR and maxDets 1 / 10 (the reference discards them), visualisation.  Parity with pycocotools and with the
+  Metavision toolbox is not pinned by a test: neither is installed where this project is built (tests/coco_reference.py is the yardstick).
 
 There is no CPU path: CPU tensors raise the library's "no CPU fallback" error.
 """
@@ -32,14 +36,14 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from ._frontend import not_capturing, same_device
+from ._frontend import not_capturing, same_device, tensor_arg
 from .functional import _need_gpu, _stream
 
 OUT_KEYS = ('AP', 'AP_50', 'AP_75', 'AP_S', 'AP_M', 'AP_L')   # coco_eval.py:109
 CLASSES = {'gen1': ("car", "pedestrian"), 'gen4': ("pedestrian", "two-wheeler", "car")}   # evaluation.py:15-18
 IOU_THRS = np.linspace(.5, 0.95, int(np.round((0.95 - .5) / .05)) + 1, endpoint=True)      # pycocotools Params.setDetParams
 REC_THRS = np.linspace(.0, 1.00, int(np.round((1.00 - .0) / .01)) + 1, endpoint=True)
-MAX_ANCHORS, MAX_LABELS_PER_FRAME = 8192, 128
+MAX_ANCHORS, MAX_LABELS_PER_FRAME, MAX_WINDOW_DETECTIONS = 8192, 128, 8192
 
 
 class PropheseeEvaluator:
@@ -49,6 +53,9 @@ class PropheseeEvaluator:
     ev.add(labels, counts, det, n_det)
       labels fp32 [N, M, 7] rows (t, x, y, w, h, class_id, class_confidence), counts int32 [N] (0: not a frame), det fp32 [N, A, 7] and
       n_det int32 [N] as `postprocess_padded` returns them for the same N frames.
+    ev.add_recordings(gt, n_gt, dt, n_dt, time_tol_us=50_000, max_window_detections=1024)
+      whole recordings: label records int32 [S, Gcap, 10] / int64 [S] against detection records int32 [S, Dcap, 10] / int64 [S], matched
+      by timestamp (see the method).
     ev.evaluate_buffer(img_height, img_width) -> {'AP', 'AP_50', 'AP_75', 'AP_S', 'AP_M', 'AP_L'} as Python floats (one sync, at the end)
     ev.precision() -> fp64 [10, 101, K, 4] of the last evaluate_buffer; ev.tables() -> the flattened image / annotation / result records
     ev.reset_buffer(), ev.has_data() as in the reference.
@@ -74,6 +81,7 @@ class PropheseeEvaluator:
             min_box_diag //= 2
             min_box_side //= 2
         self.min_box_diag, self.min_box_side = min_box_diag, min_box_side
+        self.max_window_detections: Optional[int] = None      # of the last add_recordings
         self._buffer_empty = True
         self._dev: Optional[torch.device] = None
         self._t: Dict[str, torch.Tensor] = {}
@@ -160,6 +168,50 @@ class PropheseeEvaluator:
         self._buffer_empty = False
         self._evaluated = False
 
+    def add_recordings(self, gt: torch.Tensor, n_gt: torch.Tensor, dt: torch.Tensor, n_dt: torch.Tensor, time_tol_us: int = 50_000,
+                       max_window_detections: int = 1024) -> None:
+        """S whole recordings, each one label "file" against one detection "file" as evaluate_list(apply_bbox_filters=True) scores them
+        (evaluation.py:5-42, _match_times of metrics/coco_eval.py:55-90).
+          gt int32 [S, Gcap, 10], n_gt int64 [S]: the label records of the recordings, ten words per `labels.BBOX_DTYPE` record (what
+            `LabelStreams.pack` makes), the first n_gt[s] of a row valid and sorted by t; dt int32 [S, Dcap, 10], n_dt int64 [S]: the
+            detection records of the same recordings, sorted by t (e.g. `online.DetectionLog.records` / `.counts`).
+        Per row, in row order: both sides pass filter_boxes (t > 500 000 and the size rule; each detection on its own t); every unique
+        t of the labels left is an image, numbered behind the images already in the buffer; its detections are the ones with
+        t - time_tol_us <= t_det <= t + time_tol_us, so one detection may belong to several images (max_detections counts memberships).
+        Everything behind that is `add`'s, and the two may be mixed in one buffer.  max_labels_per_frame is the limit per label
+        timestamp; an image whose window holds more than max_window_detections records before the filter (1 .. 8192: it sizes the
+        sort) is refused, a row whose records are not sorted by t adds nothing; both are counted on the device and raised by
+        `evaluate_buffer` (OverflowError / ValueError).  Four launches, no synchronisation: capturable after one eager call, and a
+        replay evaluates the records and counts then in the same tensors."""
+        tensor_arg(gt, "gt", "evaluation", (torch.int32,), ("S", "Gcap", 10), "(ten words per box record)", dtype_error=TypeError)
+        S, Gcap = int(gt.shape[0]), int(gt.shape[1])
+        tensor_arg(n_gt, "n_gt", "evaluation", (torch.int64,), (S,), dtype_error=TypeError)
+        tensor_arg(dt, "dt", "evaluation", (torch.int32,), (("S", S), "Dcap", 10), "(ten words per box record)", dtype_error=TypeError)
+        Dcap = int(dt.shape[1])
+        tensor_arg(n_dt, "n_dt", "evaluation", (torch.int64,), (S,), dtype_error=TypeError)
+        if int(time_tol_us) < 0:
+            raise ValueError(f"sast_amd.evaluation: time_tol_us must be >= 0, got {time_tol_us}")
+        if not 1 <= int(max_window_detections) <= MAX_WINDOW_DETECTIONS:
+            raise ValueError(f"sast_amd.evaluation: max_window_detections must be in 1 .. {MAX_WINDOW_DETECTIONS}, got {max_window_detections}")
+        if S > 65535 or S * Gcap > ((1 << 31) - 1) // 16 or S * Dcap > (1 << 31) - 1:
+            raise ValueError("sast_amd.evaluation: need S <= 65535 recordings, S * Gcap <= (2^31 - 1) / 16 and S * Dcap <= 2^31 - 1 records")
+        _need_gpu(gt, n_gt, dt, n_dt)
+        same_device("evaluation", "gt, n_gt, dt and n_dt", gt, n_gt, dt, n_dt)
+        if self._dev is None:
+            self._allocate(gt.device)
+        elif gt.device != self._dev:
+            raise ValueError("sast_amd.evaluation: the buffer lives on another device")
+        r = L.SastEvRecArgs()
+        r.gt, r.n_gt, r.dt, r.n_dt = gt.data_ptr(), n_gt.data_ptr(), dt.data_ptr(), n_dt.data_ptr()
+        r.S, r.Gcap, r.Dcap, r.max_window, r.time_tol_us = S, Gcap, Dcap, int(max_window_detections), int(time_tol_us)
+        r.ws_bytes = int(L.lib().sast_evrec_ws_bytes(S, Gcap))
+        ws = torch.empty(r.ws_bytes, dtype=torch.uint8, device=self._dev)       # freed in stream order, behind the four launches
+        r.ws = ws.data_ptr()
+        L.check(L.lib().sast_evrec_add(C.byref(self._args), C.byref(r), _stream()), "evrec_add")
+        self.max_window_detections = int(max_window_detections)
+        self._buffer_empty = False
+        self._evaluated = False
+
     # ----------------------------------------------------------------------------------------------------------------- evaluate
     def evaluate_buffer(self, img_height: int, img_width: int) -> Optional[Dict[str, float]]:
         """the six COCO numbers of everything added since the last reset (e.g. in on_validation_epoch_end).  img_height / img_width
@@ -178,7 +230,11 @@ class PropheseeEvaluator:
         if self._buffer_empty and state[11] == 0:    # no add by the host and none by a replayed graph (the device counts them)
             warn("Attempt to use prophesee evaluation buffer, but it is empty", UserWarning, stacklevel=2)
             return None
-        refused = {"max_images": int(state[8]), "max_detections": int(state[9]), "max_labels_per_frame": int(state[10])}
+        if state[29]:
+            raise ValueError(f"sast_amd.evaluation: {int(state[29])} recording(s) given to add_recordings were not sorted by t (labels or "
+                             "detections) and were not evaluated")
+        refused = {"max_images": int(state[8]), "max_detections": int(state[9]), "max_labels_per_frame": int(state[10]),
+                   "max_window_detections": int(state[28])}
         if any(refused.values()):
             raise OverflowError("sast_amd.evaluation: frames did not fit the buffer and were not evaluated -- "
                                 + ", ".join(f"{v} frame(s) refused for {k}={getattr(self, k)}" for k, v in refused.items() if v))
@@ -242,6 +298,7 @@ class PropheseeEvaluator:
             raise ValueError("sast_amd.evaluation: the other buffer lives on another device")
         L.check(L.lib().sast_evmerge_append(C.byref(self._args), C.byref(other._args), _stream()), "evmerge_append")
         self._evaluated = False
+        self.max_window_detections = self.max_window_detections or other.max_window_detections
         if not other._buffer_empty:      # adds that only a replayed graph made are in the device's count, which was added too
             self._buffer_empty = False
 

@@ -76,10 +76,54 @@ def export_detections(det: torch.Tensor, n_det: torch.Tensor, ends: torch.Tensor
     L.check(L.lib().sast_detections_export(C.byref(a), _stream()), "detections_export")
 
 
+class DetectionLog:
+    """log = DetectionLog(num_streams, capacity): the detections of an online run, kept on the device as `PropheseeEvaluator.
+    add_recordings` takes them (`dt=log.records, n_dt=log.counts`), so a run is scored without its records visiting the host.
+      records int32 [S, capacity, 10] (ten words per `labels.BBOX_DTYPE` record), counts int64 [S], dropped int32 [1]; allocated by the
+      first, un-captured `append`.
+    log.append(records, counts): sast_detlog_append -- row s puts the counts[s] (int32 [S]) records of one step (uint8 [S, max_det, 40],
+      what `export_detections` wrote) behind its log.  A step's records that do not fit are dropped whole and counted in `dropped`.
+      One launch, no synchronisation.
+    log.clear(streams=None): from the host, the rows `streams` (default: all, and `dropped`) start over.
+    A row's log is ONE recording: clear it before the stream is reset.  Otherwise its timestamps go backwards and `add_recordings`
+    refuses the row as unsorted -- loudly, in `evaluate_buffer`."""
+
+    def __init__(self, num_streams: int, capacity: int):
+        self.num_streams = F.stream_count(num_streams, "online")
+        self.capacity = int(capacity)
+        if self.capacity < 1 or self.num_streams * self.capacity > (1 << 31) - 1:
+            raise ValueError("sast_amd.online: the log's capacity must be >= 1 and num_streams * capacity <= 2^31 - 1")
+        self.records = self.counts = self.dropped = None
+
+    def append(self, records: torch.Tensor, counts: torch.Tensor) -> None:
+        S = self.num_streams
+        F.tensor_arg(records, "records", "online", (torch.uint8,), (("num_streams", S), "max_det", RECORD_BYTES))
+        F.tensor_arg(counts, "counts", "online", (torch.int32,), (S,))
+        _need_gpu(records, counts)
+        F.same_device("online", "records and counts", records, counts)
+        if self.records is None:
+            F.not_capturing("online", "one un-captured call is needed before graph capture (it allocates the log)")
+            dev = records.device
+            self.records = torch.zeros(S, self.capacity, RECORD_BYTES // 4, dtype=torch.int32, device=dev)
+            self.counts = torch.zeros(S, dtype=torch.int64, device=dev)
+            self.dropped = torch.zeros(1, dtype=torch.int32, device=dev)
+        else:
+            F.lives_on("the log", self.records.device, "the step's records", records.device, "online")
+        a = L.SastDetLogArgs()
+        a.records, a.counts, a.log, a.log_counts, a.dropped = (records.data_ptr(), counts.data_ptr(), self.records.data_ptr(),
+                                                               self.counts.data_ptr(), self.dropped.data_ptr())
+        a.capacity, a.S, a.max_det = self.capacity, S, records.shape[1]
+        L.check(L.lib().sast_detlog_append(C.byref(a), _stream()), "detlog_append")
+
+    def clear(self, streams=None) -> None:
+        F.reset_rows((self.counts,), self.dropped, streams, self.num_streams, "online")
+
+
 class OnlineDetector:
-    """od = OnlineDetector(detector, queue, windows_per_step=W, max_det=100, conf_thre=0.1, nms_thre=0.45, first_end_us=None)
+    """od = OnlineDetector(detector, queue, windows_per_step=W, max_det=100, conf_thre=0.1, nms_thre=0.45, first_end_us=None, log=None)
       detector: a `YoloXDetector` in eval mode; queue: an `EventQueue` with duration windows (duration_us = D) for S <= 256 streams;
-      first_end_us: the end of every recording's first window (default D, must be >= D).
+      first_end_us: the end of every recording's first window (default D, must be >= D); log: a `DetectionLog` for the same S
+      streams: every step then appends its exported records to it, inside the push (and its graph) -- one more launch per step.
     od.push(x, y, p, t, counts, reset=None, final=None) / od.push_dat(records, counts, reset=None, final=None) /
     od.push_evt3(words, counts, reset=None, final=None) / od.push_evt2(words, counts, reset=None, final=None, version="2.0")
       the chunk of `EventQueue.push` / `push_dat` / `push_evt3` (raw EVT 3.0 sensor words, counts in words) / `push_evt2` (raw EVT 2.0
@@ -107,7 +151,7 @@ class OnlineDetector:
     per-call tensors of the detector are taken."""
 
     def __init__(self, detector, queue: EventQueue, windows_per_step: int, max_det: int = 100, conf_thre: float = 0.1, nms_thre: float = 0.45,
-                 first_end_us: Optional[int] = None, class_agnostic: bool = False):
+                 first_end_us: Optional[int] = None, class_agnostic: bool = False, log: Optional[DetectionLog] = None):
         if not isinstance(queue, EventQueue):
             raise ValueError("sast_amd.online: queue must be a sast_amd.events.EventQueue")
         if queue.mode != L.EVENT_WINDOW_DURATION or queue.value < 1:
@@ -125,6 +169,9 @@ class OnlineDetector:
             raise ValueError(f"sast_amd.online: first_end_us must be >= duration_us ({self.D}), got {first_end_us}")
         if getattr(detector, "training", False):
             raise ValueError("sast_amd.online: the detector must be in eval mode (detector.eval())")
+        if log is not None and (not isinstance(log, DetectionLog) or log.num_streams != self.S):
+            raise ValueError(f"sast_amd.online: log must be a DetectionLog for the queue's {self.S} streams")
+        self.log = log
         self.num_classes = int(detector.yolox_head.num_classes)
         self.conf_thre, self.nms_thre, self.class_agnostic = float(conf_thre), float(nms_thre), bool(class_agnostic)
         self.states = None                 # [(h, c)] per stage: the held recurrent states
@@ -181,6 +228,8 @@ class OnlineDetector:
             SF.commit_samples_dev(held, [t for s in new for t in s], self.due[k])
             det, n_det = SF.postprocess_padded(out, self.num_classes, self.conf_thre, self.nms_thre, self.class_agnostic)
             export_detections(det, n_det, self.ends[k], self.due[k], self.records[k], self.counts[k], self.truncated)
+            if self.log is not None:
+                self.log.append(self.records[k], self.counts[k])
             self.predictions.append(out)
 
     def _copy_out(self):
