@@ -1,4 +1,5 @@
-// micro-benchmark / unit-test entry points for the GEMM template (not used by the product path)
+// micro-benchmark / unit-test entry points for the GEMM template, and the window-attention launchers on their own
+// (sast_test_attn_fwd / sast_test_attn_bwd: tests/test_attn_operators.py); not used by the product path
 #include <hip/hip_runtime.h>
 // phase timestamps (100 MHz wall clock) of every block of the LAST instrumented launch: only the kernel instantiations of
 // this translation unit carry them (they use the test-only epilogues below, so no product kernel is affected)
@@ -259,6 +260,18 @@ extern "C" int sast_test_mfma_peak(float* out, int mode, int blocks, int iters, 
   return SAST_OK;
 }
 
+
+// ---- the window-attention launchers of k_attn_mfma.hip on their own (tests/test_attn_operators.py): qkv [rows, 3C] with head h at
+// column 3 h dh as [q | k | v], o / dout [rows, C], lse [rows, heads], row_off the exclusive prefix sum of Kw; the backward runs
+// without LayerScale-finish side workgroups; dbuf [rows, heads] is needed for T > 128.  Both return the launcher's code.
+extern "C" int sast_test_attn_fwd(const float* qkv, float* o, float* lse, const int* row_off, const int* Kw, int W, int T, int C, int dh,
+                                  sast_stream_t stream) {
+  return attn_fwd_mfma_launch(qkv, o, lse, row_off, Kw, W, T, C, dh, (hipStream_t)stream);
+}
+extern "C" int sast_test_attn_bwd(const float* qkv, const float* dout, const float* lse, float* dqkv, const int* row_off, const int* Kw,
+                                  int W, int T, int C, int dh, float* dbuf, sast_stream_t stream) {
+  return attn_bwd_mfma_launch(qkv, dout, lse, dqkv, row_off, Kw, W, T, C, dh, (hipStream_t)stream, nullptr, nullptr, 0, dbuf);
+}
 
 // ---- launch-error latching (common.cuh: SAST_LAUNCH / SAST_CHECK_LAUNCH): a failed launch followed by good ones inside one entry
 // point must still be reported by the single check at the end.  bad != 0: the first launch asks for 2048 threads per workgroup.

@@ -108,6 +108,20 @@ def test_case_table_covers_what_the_sweep_is_about():
         feats = [c for c in ms if c["C"] == C]
         assert any(not c["ls"] for c in feats) and any(c["cb"] for c in feats) and any(c["drop"] for c in feats) and any(c["act"] == "prelu" for c in feats)
     assert sum(c["cond"] for c in ms) == 1 and any(c["sel"] == "empty2" for c in ms)
+    pt = TC.PART_CASES
+    assert all(c["op"] == "mswsa_part" and c["B"] == 1 for c in pt) and all(c["op"] == "mswsa" and c["T"] == 20 for c in ms)
+    assert {c["T"] for c in pt} == {60, 80, 120, 240} == set(TC.PART_KS) and all(max(TC.PART_KS[T]) == T for T in TC.PART_KS)
+    for T in TC.PART_KS:        # every tile count up to the partition's, through the class's own kernels; two widths
+        tiles = {(K + 31) // 32 for K in TC.PART_KS[T]}
+        assert tiles >= ({1, 2} if T == 60 else {1, 2, 3} if T == 80 else {1, 3, 4} if T == 120 else {2, 4, 5, 8}), T
+        assert len({c["C"] for c in pt if c["T"] == T and not c["shares"]}) == 2, T
+        knob = {c["C"] for c in pt if c["T"] == T and c["env"] == TC.NOSPLIT}
+        assert knob == ({c["C"] for c in pt if c["T"] == T} if T <= 96 else set()), T
+    assert any((2 * c["C"]) % 6 and (2 * c["C"]) % 3 for c in pt if c["T"] == 80)          # a ragged last side block: wpb2 = 6, wpb = 3
+    assert sorted((c["T"], c["nograd"]) for c in pt if c["fused"]) == [(80, False), (80, True), (120, False), (120, True)]
+    assert all(c["C"] == 64 and c["dh"] == 32 and TC.BY_ID[c["shares"]]["C"] == 64 for c in pt if c["fused"])
+    assert [(c["T"], c["C"]) for c in pt if c["peaked"]] == [(240, 64)] and not any(c.get("peaked") for c in ms)
+    assert all(TC.BY_ID[c["shares"]]["T"] == c["T"] and not TC.BY_ID[c["shares"]]["shares"] for c in pt if c["shares"])
     assert {(c["C"], c["pattern"]) for c in TC.MASK_CASES if c["pe"]} == {(C, p) for C in (32, 48, 1024) for p in ("none", "all", "every257")}
     assert any(not c["pe"] for c in TC.MASK_CASES) and {c["C"] for c in TC.ADDPOS_CASES} == {32, 48, 1024}
     ls = TC.LSTM_CASES
@@ -135,7 +149,7 @@ def test_bounds_hold_every_compared_quantity_and_stay_inside_the_project_bars(bo
         if case["op"] == "lstm":
             want = {"out:h1", "out:c1", "grad:x", "grad:w", "grad:b"} | {f"grad:{s}" for s in ("h0", "c0") if
                                                                          (s == "h0" and case["state"] != "none") or (s == "c0" and case["state"] in ("given", "zero"))}
-        if case["op"] == "mswsa":
+        if case["op"] in TC.MSWSA_OPS:
             want = {"out:y", "grad:x"} | {f"grad:{k}" for k in R.MSWSA_NAMES if k != "act_w" and (case["ls"] or k not in ("ls1", "ls2"))}
             if case["act"] == "prelu":
                 want.add("grad:act_w")

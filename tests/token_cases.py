@@ -22,6 +22,13 @@ Families:
               windows per sample, 160 rows), inner = mlp_inner_dim(C), dim_head 32 (24 at C = 48; 8 and 16 as well at C = 64, 16 at C = 96).
               "mix": K per window = 20, 1, dropped, 19 | 7, 12, 20, 3.  "empty2": the second sample keeps
               nothing.  "cond": input rows 30 + 0.1 randn (mean far above the spread).
+  mswsa_part  the same layer at the partition sizes the attention launchers dispatch on (csrc/k_attn_mfma.hip: T <= 64, <= 96, <= 128,
+              <= 256), with an operator of its own so that the medians of `mswsa` stay what they were: B = 1, one dropped window,
+              T = 60 with K = 60, 33, 32, 1, 17; T = 80 with 80, 65, 64, 3; T = 120 with 120, 97, 96, 31; T = 240 with 240, 129, 128, 33.
+              What the stand-alone attention suite (tests/attn_cases.py) does not run: the LayerScale-finish side workgroups of the
+              attention backward (2 C rows in blocks of 4 | 2 (T = 60, split | sequential), 6 | 3 (T = 80: ragged at C = 32 and 64),
+              4 (T = 120) and 8 (T = 240) rows) and the one-kernel forward with three and four waves (C = 64 at T = 80 and 120).
+              T = 60 and 80 again with SAST_ATTN_BWD_SPLIT=0; "peaked": the q and k rows of qkv_w times 2 (logit std about 4) at T = 240.
   mask_token / add_pos   B = 3 on an 11 x 25 map (825 rows: three blocks of 256 and a partial one), the table has one row per position.
   lstm        ConvLSTM at B = 2, 5 x 7 (M = 70: a partial 64-row tile).  States: "given", "none" (h0 = c0 = None: the reduction drops
               the h half and the forget gate is skipped), "zero" (all-zero tensors, present: the full path, dh0 / dc0 requested),
@@ -82,6 +89,30 @@ MSWSA_CASES = (
        for tag, opt in (("nols", dict(ls=False)), ("cb", dict(cb=True)), ("drop", dict(drop=True)), ("prelu", dict(act="prelu")))]
     + [_mswsa(64, tag="cond", cond=True)])
 
+PART_KS = {60: [60, 33, 32, 1, 17], 80: [80, 65, 64, 3], 120: [120, 97, 96, 31], 240: [240, 129, 128, 33]}
+PART_DROPPED = 2        # the window of a partition case that keeps nothing
+NOSPLIT = {"SAST_ATTN_BWD_SPLIT": "0"}
+
+
+def _part(T, C, tag="", **opt):
+    return _mswsa(C, sel=f"part{T}", tag=tag, **dict(dict(op="mswsa_part", B=1, N=len(PART_KS[T]) + 1, T=T, peaked=False), **opt))
+
+
+def _part_family():
+    out = []
+    for T, widths in ((60, (32, 64)), (80, (32, 64)), (120, (48, 64)), (240, (48, 64))):
+        for C in widths:
+            plain = _part(T, C)
+            out.append(plain)
+            if T <= 96:
+                out.append(_part(T, C, "nosplit", env=dict(NOSPLIT), shares=plain["id"]))
+            if C == 64 and T in (80, 120):      # the one-kernel forward: ntw = 3 and 4
+                out += [_part(T, C, "fused", fused=True, shares=plain["id"]), _part(T, C, "fused-nograd", fused=True, nograd=True, shares=plain["id"])]
+    return out + [_part(240, 64, "peaked", peaked=True)]
+
+
+PART_CASES = _part_family()
+
 MAP_HW = (11, 25)       # 275 positions, 825 rows at B = 3
 
 
@@ -104,7 +135,7 @@ def _lstm(C, state, two=False, drop=False):
 LSTM_CASES = ([_lstm(C, st) for C in WIDTHS for st in ("given", "none", "zero", "h0zero")]
               + [_lstm(C, st, two, drop) for C in (48, 256) for st, two, drop in (("given", True, True), ("none", False, True), ("h0zero", True, False))])
 
-ALL_CASES = SCORE_CASES + MSWSA_CASES + MASK_CASES + ADDPOS_CASES + LSTM_CASES
+ALL_CASES = SCORE_CASES + MSWSA_CASES + PART_CASES + MASK_CASES + ADDPOS_CASES + LSTM_CASES
 BY_ID = {c["id"]: c for c in ALL_CASES}
 assert len(BY_ID) == len(ALL_CASES), "duplicate case ids"
 
@@ -116,8 +147,12 @@ def bounds_id(case):
 
 # ------------------------------------------------------------------------------------------------ inputs
 def kept_slots(case):
-    """{window id: sorted kept slots} of the case's selection (eight windows of T = 20 slots; windows 0-3 are sample 0)"""
-    Ks = {"mix": {0: 20, 1: 1, 3: 19, 4: 7, 5: 12, 6: 20, 7: 3}, "empty2": {0: 20, 1: 5, 3: 11}}[case["sel"]]
+    """{window id: sorted kept slots} of the case's selection: "mix" / "empty2" on eight windows of T = 20 slots (windows 0-3 are sample
+    0), "part<T>" the K list of PART_KS[T] on consecutive windows of T slots with window PART_DROPPED left out"""
+    if case["sel"].startswith("part"):
+        Ks = dict(zip([w for w in range(case["N"]) if w != PART_DROPPED], PART_KS[case["T"]]))
+    else:
+        Ks = {"mix": {0: 20, 1: 1, 3: 19, 4: 7, 5: 12, 6: 20, 7: 3}, "empty2": {0: 20, 1: 5, 3: 11}}[case["sel"]]
     g = SW.gen("selection-" + case["sel"])
     return {w: sorted(torch.randperm(case["T"], generator=g)[:k].tolist()) for w, k in Ks.items()}
 
@@ -150,7 +185,7 @@ def make_inputs(case):
             inp["wc"][list(INF_CHANNELS)] = -math.inf
         inp["g"] = SW.up(g, B, L, C)
         return inp
-    if op == "mswsa":
+    if op in MSWSA_OPS:
         NW, T, inner = case["B"] * case["N"], case["T"], case["inner"]
         x = torch.randn(NW, T, C, generator=g)
         if case["cond"]:
@@ -160,6 +195,8 @@ def make_inputs(case):
                "qkv_w": rn(3 * C, C, sc=C ** -0.5), "qkv_b": rn(3 * C, sc=0.1), "proj_w": rn(C, C, sc=C ** -0.5), "proj_b": rn(C, sc=0.1),
                "ls1": 0.5 + rn(C, sc=0.1), "fc1_w": rn(2 * inner, C, sc=C ** -0.5), "fc1_b": rn(2 * inner, sc=0.1),
                "fc2_w": rn(C, inner, sc=inner ** -0.5), "fc2_b": rn(C, sc=0.1), "ls2": 0.5 + rn(C, sc=0.1)}
+        if case.get("peaked"):
+            inp["qkv_w"].view(C // case["dh"], 3, case["dh"], C)[:, :2] *= 2.0
         if not case["ls"]:
             del inp["ls1"], inp["ls2"]
         if case["act"] == "prelu":
@@ -221,13 +258,23 @@ def check_conditions(case, inp):
         if case["kind"] == "inf":
             assert bool(torch.isneginf(inp["wc"][list(INF_CHANNELS)]).all()) and int(torch.isinf(inp["wc"]).sum()) == 20 * len(INF_CHANNELS)
             assert float(torch.exp(inp["wc"][list(INF_CHANNELS)]).abs().max()) == 0.0
-    elif op == "mswsa":
+    elif op in MSWSA_OPS:
         kept = kept_slots(case)
-        assert case["B"] * case["N"] * case["T"] == 160
+        assert all(0 <= w < case["B"] * case["N"] and v == sorted(set(v)) and 0 <= v[0] and v[-1] < case["T"] for w, v in kept.items())
+        if op == "mswsa":
+            assert case["B"] * case["N"] * case["T"] == 160
         if case["sel"] == "mix":
             assert sorted(len(v) for v in kept.values()) == [1, 3, 7, 12, 19, 20, 20] and 2 not in kept
-        else:
+        elif case["sel"] == "empty2":
             assert all(w < case["N"] for w in kept), "the second sample keeps nothing"
+        else:
+            Ks = [len(kept[w]) for w in sorted(kept)]
+            assert op == "mswsa_part" and case["B"] == 1 and Ks == PART_KS[case["T"]] and max(Ks) == case["T"] and PART_DROPPED not in kept
+            assert sorted(kept) == [w for w in range(case["N"]) if w != PART_DROPPED] and case["C"] % case["dh"] == 0
+            assert case["env"] in ({}, NOSPLIT) and (not case["env"] or case["T"] <= 96) and (not case["fused"] or case["C"] == 64)
+            w = inp["qkv_w"].double().view(case["C"] // case["dh"], 3, case["dh"], case["C"])
+            gain = float((w[:, :2].std() / w[:, 2].std()))
+            assert (1.8 < gain < 2.2) if case["peaked"] else (0.9 < gain < 1.1), gain
         if case["cond"]:
             rows = inp["x"].double().reshape(-1, case["C"])
             assert float((rows.mean(1) / rows.std(1)).min()) > 100
@@ -245,6 +292,7 @@ def check_conditions(case, inp):
 
 
 # ------------------------------------------------------------------------------------------------ reference evaluation
+MSWSA_OPS = ("mswsa", "mswsa_part")
 NO_GRAD = ("g", "gh", "gc", "gh2", "r_buf", "table", "drop", "drop.d1", "drop.d2", "drop.mlp")
 
 
@@ -272,7 +320,7 @@ def reference(case, inp, dtype):
             (xw * p["g"]).sum().backward()
             SW.grads(out, p, only=("wc",) if case["kind"] == "gauss" else None)
         return out
-    if op == "mswsa":
+    if op in MSWSA_OPS:
         p = _leaves(inp, dtype, not case["nograd"])
         params = {k: p[k] for k in R.MSWSA_NAMES if k in p}
         lists = R.index_lists(kept_slots(case), case["T"])
