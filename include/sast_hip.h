@@ -694,6 +694,59 @@ int sast_evt3_decode(const void* words, const int64_t* counts, int64_t chunk_wor
                      void* ws, int16_t* x, int16_t* y, int16_t* p, int64_t* t, int64_t max_events, int64_t* out_counts, int32_t* err,
                      sast_stream_t stream);
 
+/* ---- events -> raw sensor words (csrc/k_evt3_enc.hip): the inverse of the section above, event columns (the dtypes of
+ * sast_evqueue_push) or packed Event2D records (SAST_EVQUEUE_DT_DAT's layout) -> EVT 3.0 words that sast_evt3_decode turns back into the
+ * events.  The rule is canonical and deterministic; it is this project's (parity with the Metavision SDK's encoder is unpinned, the SDK
+ * is not a dependency; what is pinned is the sequential model of tests/evt3_encoder_model.py).  Per stream the state have, t_last,
+ * y_last, all 0 after a reset.  One row's chunk of n events:
+ *   1. normalised: t the running maximum over the row, from t_last when have is set and from 0 otherwise; x and y clamped to
+ *      0 .. 2047; p = p != 0.  An event changed by this is counted (err[0]: t raised, err[1]: x, y or p changed), never dropped.
+ *   2. groups: event j continues the group of event j - 1 iff both are in this chunk, have the same t, y and p, x[j-1] < x[j] and
+ *      x[j-1] / 12 == x[j] / 12; every other event, and a chunk's first, is a leader.  A cut ends a group: the words depend on the cuts,
+ *      the decoded events do not.
+ *   3. only leaders send words.  Leader i, with "the event in front" the state for i == 0, in this order:
+ *        0x8 EVT_TIME_HIGH  !have: (t >> 12) & 0xFFF.  Else, with H = t >> 12 and Hp = t_front >> 12: floor((H - Hp - 1) / 1024) keep-alives
+ *                           (Hp + 1024 q) & 0xFFF, q = 1 .., so that the decoder sees every wrap of the 12 bits; then H & 0xFFF if H != Hp
+ *        0x6 EVT_TIME_LOW   t & 0xFFF, behind every TIME_HIGH (a decoder that clears the low bits there still agrees), or when the low
+ *                           bits differ from those of the event in front
+ *        0x0 EVT_ADDR_Y     y, bit 11 clear: !have, or y differs from the y in front
+ *        a group of two or more events:
+ *        0x3 VECT_BASE_X    12 * (x / 12) | p << 11 -- unless the group is chained: events i - 2 and i - 1 are in this chunk and end a
+ *                           group, i - 1 -> i is ascending with the same t, y, p and x[i] / 12 == x[i-1] / 12 + 1: the decoder's base
+ *                           and polarity already stand there
+ *        0x4 VECT_12        one bit x % 12 per member
+ *        a single event:
+ *        0x2 EVT_ADDR_X     x | p << 11
+ *      No VECT_8, CONTINUED, OTHERS or trigger word is sent.  Without keep-alives an event gives at most 5 words.
+ *   4. the state after the chunk is (1, t, y) of its last event; an empty chunk leaves it alone.
+ * A fresh decoder starts with wraps = 0: it returns t - ((t0 >> 24) << 24), t0 the row's first event.  That is the format's. */
+#define SAST_EVT3_ENC_STATE_WORDS 4     /* a row of `state`: have, t_last, y_last, 0 */
+#define SAST_EVT3_ENC_BLOCK_EVENTS 1024 /* events a workgroup takes in one step; a row gets ceil(chunk_events / this) workgroups ... */
+#define SAST_EVT3_ENC_MAX_BLOCKS 256    /* ... at most this many, which then take several steps each */
+/* bytes of the encode's workspace (per row the state and one summary per workgroup).  0: S < 1 or S > 65535.  Host only. */
+size_t sast_evt3enc_ws_bytes(int S);
+/* per row s: with reset != NULL and reset[s] != 0 the row's state is zeroed first.  Then the first n_s = min(max(counts[s], 0),
+ * chunk_events) events of row s are encoded: x, y, p SAST_DT_I64 / I32 / I16 [S, chunk_events], t SAST_DT_I64 / I32.  The words go to
+ * words[s] (16-bit words [S, max_words]) from column 0 on, n_words[s] is their number, state[s] (int64 [S, SAST_EVT3_ENC_STATE_WORDS])
+ * becomes the state after the chunk.  A row whose words exceed max_words is refused whole (the rule of sast_evmerge_append):
+ * n_words[s] = 0, its state as it was (zero if its reset flag was set), one count in err[2], nothing in err[0] and err[1].  err, int32 [4], ACCUMULATED: [0] times
+ * raised to the running maximum, [1] events whose x, y or p was clamped, [2] rows refused for lack of room, [3] spare.
+ * max_words = 5 * chunk_events + (the keep-alives: one per 2^22 us of silence) never refuses.  SAST_EINVAL before any launch: a null
+ * pointer (reset may be), S outside 1 .. 65535, an unknown dtype, chunk_events < 0, S * chunk_events or S * max_words > 2^31 - 1,
+ * max_words < 1, words not 2-byte or ws not 8-byte aligned.
+ * 2 launches whatever S and the sizes are (one summary per workgroup: words, largest t, raised and clamped events; fold the summaries +
+ * scan + write, the row's last workgroup writes state, n_words and counters): no workgroup reads what another one writes in the same
+ * launch, nothing has to be put back for a graph replay, every store is a plain vector store.  A row with a raised time (unsorted
+ * input, counted in err[0]) is walked whole by its last workgroup: the normalised times of a piece then depend on every event before. */
+int sast_evt3enc_encode(const void* x, const void* y, const void* p, const void* t, int x_dtype, int y_dtype, int p_dtype, int t_dtype,
+                     const int64_t* counts, int64_t chunk_events, int S, const uint8_t* reset, int64_t* state, void* ws, void* words,
+                     int64_t max_words, int64_t* n_words, int32_t* err, sast_stream_t stream);
+/* the same from packed records: int32 [S, chunk_events, 2], Prophesee's Event2D as sast_evqueue_push takes it with
+ * SAST_EVQUEUE_DT_DAT (t the unsigned word 0, x = w & 16383, y = (w >> 14) & 16383, p = (w >> 28) & 1 of word 1); records 8-byte
+ * aligned.  DAT -> EVT 3.0 without an unpacked copy. */
+int sast_evt3enc_encode_dat(const void* records, const int64_t* counts, int64_t chunk_events, int S, const uint8_t* reset, int64_t* state,
+                         void* ws, void* words, int64_t max_words, int64_t* n_words, int32_t* err, sast_stream_t stream);
+
 /* ---- raw sensor words, EVT 2.0 and EVT 2.1 (csrc/k_evt2.hip): the 32-bit word stream the VGA (Gen3.1) and 720p Gen4 / Gen4.1
  * evaluation kits send by default (one word is at most one event), and the 64-bit word stream IMX636 / GenX320 kits can be set to
  * (one word is a 32-pixel vector), decoded on the device into the columns sast_evqueue_push takes.  As for EVT 3.0 the rule below is

@@ -9,7 +9,8 @@ The chunks are already in device memory: the copy over PCIe is not part of any f
 Every push is bracketed by device events; a figure is the median (min .. max over --rounds sessions of the session's median) time
 of one push of one chunk, eager and replayed from a graph captured on the same tensors.  The decoder's staging holds the largest
 chunk's events (max_events), as a host that knows its sensor's rate would set it.  Before anything is timed the three queues are
-checked to hold the same events.
+checked to hold the same events.  The "encode" row is the way back, in the same job: `Evt3Encoder` (csrc/k_evt3_enc.hip) on the
+column chunks of the push row, beside a device copy of the same column tensors ("copy") for scale.
 
   python tools/evt3_bench.py [--streams 1,8] [--chunks 4] [--events 125000] [--rounds 5] [--out FILE]
 """
@@ -58,6 +59,72 @@ def synthetic_chunk(rng, events: int, vectors: float, step: int, t0: int, first:
     return words, x0[g] + bit, y[g], p[g], t[g], int(t[-1])
 
 
+def cell(v):
+    return f"{statistics.median(v):.3f} ({min(v):.3f} .. {max(v):.3f})"
+
+
+def encode_rows(S, chunks, rounds, lib):
+    """the "encode" row: `Evt3Encoder` on the column chunks of the push rows (the events the stream was synthesised with), and the "copy"
+    row: a device copy of the same input bytes, for scale -> (form, words per row and chunk, eager ms, replayed ms, launches) each.
+    The sessions are the push rows': the encoder's state is reset, then the chunks are encoded one after the other.  Before anything
+    is timed `Evt3Decoder` is checked to give the columns back from the encoder's words."""
+    from sast_amd.events import Evt3Decoder, Evt3Encoder
+    enc, dec = Evt3Encoder(S), Evt3Decoder(S, max_events=chunks[0][0][0].shape[1])
+    words_out = []
+    for cols, n in chunks:
+        words, n_words = enc(*cols, n)
+        got = dec(words, n_words)
+        assert torch.equal(got[4], n) and enc.errors() == (0, 0, 0, 0), enc.errors()
+        for s in range(S):
+            k = int(n[s])
+            assert all(torch.equal(g[s, :k].to(torch.int64), c[s, :k].to(torch.int64)) for g, c in zip(got[:4], cols))
+        words_out.append(float(n_words.sum()) / S)
+    del dec
+    static, static_n = [t.clone() for t in chunks[0][0]], chunks[0][1].clone()
+    sink = [torch.empty_like(t) for t in static]
+
+    def copy():
+        for d, s in zip(sink, static):
+            d.copy_(s)
+
+    rows = []
+    for form, call in (("encode", lambda: enc(*static, static_n)), ("copy", copy)):
+        enc.reset()
+        before = lib.sast_launch_count()
+        call()
+        launches = lib.sast_launch_count() - before
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            call()
+        torch.cuda.current_stream().wait_stream(side)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            call()
+        res = {"eager": [], "replayed": []}
+        for mode in ("eager", "replayed"):
+            for _ in range(rounds + 1):                                  # the first session warms up
+                enc.reset()
+                marks = []
+                for ts, n in chunks:
+                    for dst, src in zip(static + [static_n], ts + [n]):
+                        dst.copy_(src)
+                    m = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    m[0].record()
+                    if mode == "eager":
+                        call()
+                    else:
+                        g.replay()
+                    m[1].record()
+                    marks.append(m)
+                torch.cuda.synchronize()
+                res[mode].append(statistics.median(u.elapsed_time(v) for u, v in marks))
+                assert enc.errors() == (0, 0, 0, 0) and float(enc.n_words.sum()) / S == words_out[-1], form
+            res[mode] = res[mode][1:]
+        rows.append((form, statistics.mean(words_out) if form == "encode" else 0, res["eager"], res["replayed"], launches))
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--streams", default="1,8")
@@ -81,6 +148,8 @@ def main():
              f"chunk over {a.rounds} sessions; chunks already in device memory",
              "# push: int16 x / y / p + int32 t columns;  push_dat: packed Event2D records;  push_evt3: the raw 16-bit words, decoded on the "
              "device;  B/ev: bytes in per event;  launches: library kernel launches per push",
+             "# encode: Evt3Encoder on the columns of the push row, ms per call, `words` the words it gives per row and chunk;  copy: a device "
+             "copy of the same four column tensors, for scale (no library launch)",
              f"{'S':>3}{'form':>11}{'ev/chunk':>10}{'words':>9}{'B/ev':>7}  {'eager ms':<26}{'replayed ms':<26}{'launches':>9}"]
     kw = dict(height=H, width=W, bins=10, count_cutoff=10, duration_us=WINDOW_US, downsample_by_2=True)
     for S in (int(v) for v in a.streams.split(",")):
@@ -165,11 +234,11 @@ def main():
                     assert torch.equal(q.count, ref.count), (form, mode)     # the session stored what the checked one stored
                 res[mode] = res[mode][1:]
 
-            def cell(v):
-                return f"{statistics.median(v):.3f} ({min(v):.3f} .. {max(v):.3f})"
-
             lines.append(f"{S:>3}{form:>11}{n_events:>10.0f}{n_words if form == 'push_evt3' else 0:>9.0f}{bytes_in[form]:>7.2f}  "
                          f"{cell(res['eager']):<26}{cell(res['replayed']):<26}{launches:>9}")
+            print(lines[-1], flush=True)
+        for row in encode_rows(S, chunks["push"], a.rounds, lib):
+            lines.append(f"{S:>3}{row[0]:>11}{n_events:>10.0f}{row[1]:>9.0f}{10.0:>7.2f}  {cell(row[2]):<26}{cell(row[3]):<26}{row[4]:>9}")
             print(lines[-1], flush=True)
         del queues, chunks
         torch.cuda.empty_cache()
