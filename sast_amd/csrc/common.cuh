@@ -162,12 +162,15 @@ __device__ __forceinline__ T block_scan(T v, T* sm, T* total) {
 __device__ __forceinline__ float rcp_hw(float x) { return __builtin_amdgcn_rcpf(x); }
 __device__ __forceinline__ float rsqrt_hw(float x) { return __builtin_amdgcn_rsqf(x); }       // v_rsq_f32 (1 ulp)
 __device__ __forceinline__ float sigmoid_hw(float x) { return rcp_hw(1.0f + __expf(-x)); }
-// tanh on the same path: 1 - 2 / (1 + e^{2x}) (saturates correctly: e = inf -> 1, e = 0 -> -1; absolute error <= 1.2e-7, the ulp of the
-// 1 it is subtracted from -- libm's tanhf is ~37 instructions with branches)
+// tanh on the same path: 1 - 2 / (1 + e^{2x}) (saturates correctly: e = inf -> 1, e = 0 -> -1; libm's tanhf is ~37 instructions with
+// branches).  Absolute error measured on the device against float64 (tests/test_act_operators.py): 1.9e-7 on |x| <= 4, worst near
+// |x| = 2.9, and 4.1e-8 x |x| beyond; the ulp of the 1 it is subtracted from, 1.2e-7, is the floor of the form, not its bound.
 __device__ __forceinline__ float tanh_hw(float x) { return 1.0f - 2.0f * rcp_hw(1.0f + __expf(2.0f * x)); }
 
-// erf by Abramowitz-Stegun 7.1.26 (|error| <= 1.5e-7, i.e. fp32 rounding level) instead of libm's branchy erff:
-// the GLU epilogues evaluate it for every (token, inner channel) and were VALU-bound on erff.
+// erf by Abramowitz-Stegun 7.1.26 instead of libm's branchy erff: the GLU epilogues evaluate it for every (token, inner channel) and
+// were VALU-bound on erff.  The published approximation bound of 7.1.26 is |error| <= 1.5e-7 in exact arithmetic; this fp32 evaluation
+// adds its own rounding (a float32 restatement on the CPU is at 4.2e-7 on [-4, 4]).  Measured on the device against float64 through its
+// two users (tests/test_act_operators.py, |x| <= 4): gelu_erf 4.5e-7, gelu_erf_grad 2.2e-7 absolute.
 __device__ __forceinline__ float erf_as(float x) {
   const float ax = fabsf(x);
   const float t = rcp_hw(fmaf(0.3275911f, ax, 1.0f));
@@ -227,7 +230,7 @@ __device__ __forceinline__ float glu_act_grad(float g, int act, float a = 0.0f) 
     case 8: return g > 0.0f ? 1.0f : expf(g);
     case 9: return g > 0.0f ? SELU_SCALE : SELU_SCALE * SELU_ALPHA * expf(g);
     case 10: return (g > -3.0f && g < 3.0f) ? (1.0f / 6.0f) : 0.0f;
-    case 11: return g < -3.0f ? 0.0f : (g <= 3.0f ? g / 3.0f + 0.5f : 1.0f);      // hardswish_backward
+    case 11: return g <= -3.0f ? 0.0f : (g < 3.0f ? g / 3.0f + 0.5f : 1.0f);      // hardswish_backward of torch 2.10: 0 at -3, 1 at +3
     case 12: return g < -2.0f ? 0.0f : (g <= 0.0f ? g + 1.0f : 1.0f);             // activations_me.py: hard_mish_jit_bwd
     default: return gelu_erf_grad(g);
   }

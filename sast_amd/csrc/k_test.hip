@@ -1,5 +1,6 @@
-// micro-benchmark / unit-test entry points for the GEMM template, and the window-attention launchers on their own
-// (sast_test_attn_fwd / sast_test_attn_bwd: tests/test_attn_operators.py); not used by the product path
+// micro-benchmark / unit-test entry points for the GEMM template, the window-attention launchers on their own
+// (sast_test_attn_fwd / sast_test_attn_bwd: tests/test_attn_operators.py) and the elementwise helpers of common.cuh on their own
+// (sast_test_glu_act / sast_test_unary: tests/test_act_operators.py); not used by the product path
 #include <hip/hip_runtime.h>
 // phase timestamps (100 MHz wall clock) of every block of the LAST instrumented launch: only the kernel instantiations of
 // this translation unit carry them (they use the test-only epilogues below, so no product kernel is affected)
@@ -271,6 +272,51 @@ extern "C" int sast_test_attn_fwd(const float* qkv, float* o, float* lse, const 
 extern "C" int sast_test_attn_bwd(const float* qkv, const float* dout, const float* lse, float* dqkv, const int* row_off, const int* Kw,
                                   int W, int T, int C, int dh, float* dbuf, sast_stream_t stream) {
   return attn_bwd_mfma_launch(qkv, dout, lse, dqkv, row_off, Kw, W, T, C, dh, (hipStream_t)stream, nullptr, nullptr, 0, dbuf);
+}
+
+// ---- the elementwise arithmetic of common.cuh on its own (tests/test_act_operators.py): the 14-way gate activation of the GLU-MLP
+// epilogues with its derivative, and the fast-math helpers the conv, ConvLSTM, STP and GLU kernels share.  Both call the functions
+// of common.cuh themselves; y / dy / x hold n floats.
+__global__ __launch_bounds__(256) void test_glu_act_kernel(const float* __restrict__ g, float* __restrict__ y, float* __restrict__ dy, int n,
+                                                           int act, float slope) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    const float v = g[i];
+    y[i] = glu_act(v, act, slope);
+    dy[i] = glu_act_grad(v, act, slope);
+  }
+}
+extern "C" int sast_test_glu_act(const float* g, float* y, float* dy, int n, int act, float slope, sast_stream_t stream) {
+  if (act < 0 || act >= GLU_ACT_COUNT || n < 0 || n > (1 << 30) || !g || !y || !dy) return SAST_EINVAL;      // (int index + grid stride)
+  if (n == 0) return SAST_OK;
+  const int blocks = (n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024;
+  SAST_LAUNCH(test_glu_act_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, g, y, dy, n, act, slope);
+  SAST_CHECK_LAUNCH();
+  return SAST_OK;
+}
+// fn: 0 sigmoid_hw  1 tanh_hw  2 gelu_erf  3 gelu_erf_grad  4 softplus_t20  5 rsqrt_hw (positive inputs)  6 x * sigmoid_hw(x), the SiLU
+// as the conv epilogues write it
+constexpr int TEST_UNARY_COUNT = 7;
+__device__ __forceinline__ float test_unary(float x, int fn) {
+  switch (fn) {
+    case 0: return sigmoid_hw(x);
+    case 1: return tanh_hw(x);
+    case 2: return gelu_erf(x);
+    case 3: return gelu_erf_grad(x);
+    case 4: return softplus_t20(x);
+    case 5: return rsqrt_hw(x);
+    default: return x * sigmoid_hw(x);
+  }
+}
+__global__ __launch_bounds__(256) void test_unary_kernel(const float* __restrict__ x, float* __restrict__ y, int n, int fn) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) y[i] = test_unary(x[i], fn);
+}
+extern "C" int sast_test_unary(const float* x, float* y, int n, int fn, sast_stream_t stream) {
+  if (fn < 0 || fn >= TEST_UNARY_COUNT || n < 0 || n > (1 << 30) || !x || !y) return SAST_EINVAL;
+  if (n == 0) return SAST_OK;
+  const int blocks = (n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024;
+  SAST_LAUNCH(test_unary_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, y, n, fn);
+  SAST_CHECK_LAUNCH();
+  return SAST_OK;
 }
 
 // ---- launch-error latching (common.cuh: SAST_LAUNCH / SAST_CHECK_LAUNCH): a failed launch followed by good ones inside one entry

@@ -13,6 +13,9 @@ BatchNorm / LayerNorm weight 1 + 0.1 randn, bias 0.1 randn; running mean 0.1 ran
 ignored statistic shows; upstream gradient randn + 0.5 (a symmetric one makes the per-channel sums cancel and the bias gradients
 ill-conditioned).  Training-mode rows have M = B * Ho * Wo >= 8: with two rows per channel batch-statistics BatchNorm amplifies rounding
 until fp32 itself misses the forward bar.
+The "sat" cases (k = 1 and k = 3) multiply bn_w by 8 and set bn_b to +4 / -4 on alternating channels: the SiLU of the unit and its backward
+see arguments of standard deviation about 9 around +-4, |x| up to 29 (k = 3) and 48 (k = 1), a quarter of them beyond 10, where the
+Gaussian recipe never leaves O(1).
 """
 import math
 import re
@@ -35,7 +38,8 @@ def _cbs(k, s, bhw, cin, cout, modes="tei", cin1=0, two=False, env=None, tag="")
     Ho, Wo = conv_hw(H, W, k, s)
     modes = tuple({"t": "train", "e": "eval", "i": "infer"}[m] for m in modes)
     assert "train" not in modes or B * Ho * Wo >= 8, cid
-    return dict(id=cid, op="cbs", k=k, s=s, B=B, H=H, W=W, cin=cin, cout=cout, cin1=cin1, two=two, modes=modes, env=env or {}, dw=False)
+    return dict(id=cid, op="cbs", k=k, s=s, B=B, H=H, W=W, cin=cin, cout=cout, cin1=cin1, two=two, modes=modes, env=env or {}, dw=False,
+                sat=tag == "sat")
 
 
 def _dw(s, bhw, c, modes="tei"):
@@ -69,6 +73,7 @@ CBS_CASES = [
     _cbs(1, 1, (2, 5, 9), 32, 48, "t", two=True),
     _cbs(1, 1, (2, 5, 9), 32, 48),
     _cbs(1, 1, (2, 5, 9), 32, 48, "t", env={"SAST_BN_STATS_SEPARATE": "8"}, tag="statsep"),
+    _cbs(1, 1, (3, 13, 20), 20, 36, tag="sat"),  # saturated SiLU
     # ---- 3x3 stride 1
     _cbs(3, 1, (1, 16, 16), 64, 64),            # tiny tile forward
     _cbs(3, 1, (2, 24, 40), 32, 128),           # thin tile
@@ -86,6 +91,7 @@ CBS_CASES = [
     _cbs(3, 1, (1, 16, 16), 64, 64, "ti", env=ENV_THIN, tag="forceThin"),
     _cbs(3, 1, (2, 24, 40), 32, 128, "ti", env=ENV_K1, tag="forceK1"),
     _cbs(3, 1, (3, 13, 20), 20, 36, "t", env={"SAST_GEMM_PAIR": "0"}, tag="nopair"),
+    _cbs(3, 1, (2, 5, 9), 4, 12, tag="sat"),     # (a short reduction: the gain of 8 multiplies the rounding of the conv sum as well)
     # ---- 3x3 stride 2: the parity-class dX (even H, W and Mc = B (H/2) (W/2) a multiple of 64) and the generic gather (everything else)
     _cbs(3, 2, (2, 16, 32), 32, 48),            # Mc = 256
     _cbs(3, 2, (1, 32, 48), 12, 36),            # Mc = 384
@@ -227,6 +233,9 @@ def make_inputs(case):
         if cin1:
             inp["x2"] = torch.randn(B, H, W, cin - cin1, generator=g)
         inp.update(_unit_params(g, cin, cout, k, case["dw"]))
+        if case.get("sat"):
+            inp["bn_w"] = inp["bn_w"] * 8.0
+            inp["bn_b"] = 4.0 * (1 - 2 * (torch.arange(cout) % 2)).float()
         inp["g"] = SW.up(g, B, Ho, Wo, cout)
         if case["two"]:
             inp["g2"] = SW.up(g, B, Ho, Wo, cout)

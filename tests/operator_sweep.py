@@ -1,8 +1,8 @@
-"""What the five fp64 operator sweeps (conv, token path, YOLOX head, optimizer, window attention) share: the project's bars and the error measure, the helpers of
+"""What the six fp64 operator sweeps (conv, token path, YOLOX head, optimizer, window attention, elementwise arithmetic) share: the project's bars and the error measure, the helpers of
 the case modules, the generator of the fp32 bounds files, the GPU-side fixtures and the one `check` every device result goes through.
 
-A suite is its case module (tests/conv_cases.py, token_cases.py, head_cases.py, optim_cases.py, attn_cases.py), reached by name through
-`suite("conv" | "token" | "head" | "optim" | "attn")`.
+A suite is its case module (tests/conv_cases.py, token_cases.py, head_cases.py, optim_cases.py, attn_cases.py, act_cases.py), reached by name
+through `suite("conv" | "token" | "head" | "optim" | "attn" | "act")`.
 Generic code asks a suite for: ALL_CASES, BY_ID, make_inputs(case), reference(case, inputs, dtype), pool_key(quantity), bounds_id(case)
 (the case whose bounds entry this one shares), BOUNDS_CASES (the cases with an entry of their own), float_quantities(reference) (the
 compared float quantities, sorted) and DISCRETE (quantities that hold assignments, equal in every precision).
@@ -26,7 +26,7 @@ GRAD_RTOL = 3e-4
 FACTOR = 8.0          # over max(fp32 error of the reference, operator median): another summation order of the same expression
 SAST_EINVAL = -22
 
-SUITES = ("conv", "token", "head", "optim", "attn")
+SUITES = ("conv", "token", "head", "optim", "attn", "act")
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 

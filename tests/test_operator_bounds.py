@@ -1,4 +1,4 @@
-"""CPU tests of the five fp32 bounds files (tests/golden/{conv,token,head,optim,attn}_operator_bounds.json) and of the `check` the GPU sweeps hold
+"""CPU tests of the six fp32 bounds files (tests/golden/{conv,token,head,optim,attn,act}_operator_bounds.json) and of the `check` the GPU sweeps hold
 the kernels to with them (tests/operator_sweep.py).
 
 What a bounds file must satisfy, on whichever machine the test runs:
@@ -84,7 +84,7 @@ def test_regenerating_the_bounds_reproduces_the_committed_file(suite_name, commi
 
 # ------------------------------------------------------------------------------------------------ `check` bites
 BITE_CASES = {"conv": ("cbs-k3s1-2x5x9-4to12",), "token": ("addpos-c32", "mswsa-c64-dh32-mix"), "head": ("loss-base-nc3",),
-              "optim": ("adamw-onecycle-n3076", "adamw-clipscale-n1020"), "attn": ("attn-t80-c24-dh8", "attn-peaked-t240-c64-dh32")}
+              "optim": ("adamw-onecycle-n3076", "adamw-clipscale-n1020"), "attn": ("attn-t80-c24-dh8", "attn-peaked-t240-c64-dh32"), "act": ("act-mish", "unary-tanh_hw")}
 
 
 def _check_kwargs(S, suite_name, case, ref, r32):

@@ -29,10 +29,20 @@ Families:
               attention backward (2 C rows in blocks of 4 | 2 (T = 60, split | sequential), 6 | 3 (T = 80: ragged at C = 32 and 64),
               4 (T = 120) and 8 (T = 240) rows) and the one-kernel forward with three and four waves (C = 64 at T = 80 and 120).
               T = 60 and 80 again with SAST_ATTN_BWD_SPLIT=0; "peaked": the q and k rows of qkv_w times 2 (logit std about 4) at T = 240.
+  mswsa_act   the twelve gate activations the `mswsa` family does not run (every code of csrc/common.cuh: glu_act but gelu and prelu)
+              through the layer, forward and backward, on the "mix" selection at C = 48 (dim_head 24) and C = 192, with an operator of its
+              own.  `gate_gain` multiplies the gate half of fc1_w and fc1_b so that the gate pre-activations of the kept rows have a
+              standard deviation of about 3: `check_conditions` asserts on the float64 reference that at least 1 % of them lie on each
+              side of every kink of the case's activation (ACT_KINKS: 0, the clamp of relu6 at 6, the +-3 ends of hard_sigmoid and
+              hard_swish, the -2 end of hard_mish) and that none lies within KINK_BAND x max|gate| of one, so that a derivative jump
+              cannot land on different sides in fp32 and fp64.  The seed tag of an id ("-s<n>") is the first for which the band is empty.
   mask_token / add_pos   B = 3 on an 11 x 25 map (825 rows: three blocks of 256 and a partial one), the table has one row per position.
   lstm        ConvLSTM at B = 2, 5 x 7 (M = 70: a partial 64-row tile).  States: "given", "none" (h0 = c0 = None: the reduction drops
               the h half and the forget gate is skipped), "zero" (all-zero tensors, present: the full path, dh0 / dc0 requested),
               "h0zero" (zero h0 present, c0 None: forget-gate skip with the full reduction; dc0 is never requested without a c0).
+              "sat" (state given, C = 48 and 256): w times 8 and c0 times 4, so that the gate pre-activations have a standard deviation
+              of about 6 (a tenth of them beyond |z| = 10, where sigmoid_hw and tanh_hw are saturated to the last bit) and tanh_hw(c1)
+              runs on |c| up to about 15.
 """
 import math
 
@@ -40,6 +50,7 @@ import torch
 
 import operator_sweep as SW
 import token_reference as R
+from parity_helpers import KINK_BAND
 from conv_cases import pool_key  # noqa: F401  (part of the suite's face: the token quantities have no unit prefixes to pool)
 from oracle import sast_oracle as O
 
@@ -71,7 +82,7 @@ def dim_head_of(C):
 def _mswsa(C, dh=None, sel="mix", tag="", **opt):
     dh = dh or dim_head_of(C)
     c = dict(id=f"mswsa-c{C}-dh{dh}-{sel}" + (f"-{tag}" if tag else ""), op="mswsa", C=C, dh=dh, sel=sel, inner=O.mlp_inner_dim(C), B=2, N=4,
-             T=20, fused=False, nograd=False, ls=True, cb=False, drop=False, act="gelu", cond=False, env={}, shares=None)
+             T=20, fused=False, nograd=False, ls=True, cb=False, drop=False, act="gelu", cond=False, gate_gain=1.0, env={}, shares=None)
     c.update(opt)
     return c
 
@@ -88,6 +99,20 @@ MSWSA_CASES = (
     + [_mswsa(C, tag=tag, **opt) for C in (48, 192)
        for tag, opt in (("nols", dict(ls=False)), ("cb", dict(cb=True)), ("drop", dict(drop=True)), ("prelu", dict(act="prelu")))]
     + [_mswsa(64, tag="cond", cond=True)])
+
+# the gate activations beside gelu and prelu, and where the derivative of each jumps or its formula changes branch
+ACT_KINKS = {"relu": (0.0,), "silu": (), "sigmoid": (), "tanh": (), "mish": (), "relu6": (0.0, 6.0), "leaky_relu": (0.0,), "elu": (0.0,), "selu": (0.0,),
+             "hard_sigmoid": (-3.0, 3.0), "hard_swish": (-3.0, 3.0), "hard_mish": (-2.0, 0.0)}
+GATE_GAIN = 3.0
+ACT_SEEDS = {(192, "relu6"): 10, (48, "leaky_relu"): 4, (192, "leaky_relu"): 1, (192, "elu"): 7, (48, "selu"): 1, (192, "selu"): 2,
+             (192, "hard_sigmoid"): 1, (48, "hard_swish"): 1, (192, "hard_swish"): 3, (48, "hard_mish"): 1}      # (default 0)
+
+
+def _mswsa_act(C, act):
+    return _mswsa(C, tag=f"{act}-s{ACT_SEEDS.get((C, act), 0)}", op="mswsa_act", act=act, gate_gain=GATE_GAIN)
+
+
+MSWSA_ACT_CASES = [_mswsa_act(C, act) for act in ACT_KINKS for C in (48, 192)]
 
 PART_KS = {60: [60, 33, 32, 1, 17], 80: [80, 65, 64, 3], 120: [120, 97, 96, 31], 240: [240, 129, 128, 33]}
 PART_DROPPED = 2        # the window of a partition case that keeps nothing
@@ -127,15 +152,16 @@ ADDPOS_CASES = [dict(id=f"addpos-c{C}", op="add_pos", C=C, B=3, env={}) for C in
 LSTM_HW = (5, 7)
 
 
-def _lstm(C, state, two=False, drop=False):
-    return dict(id=f"lstm-c{C}-{state}" + ("-two" if two else "") + ("-drop" if drop else ""), op="lstm", C=C, B=2, state=state, two=two,
-                drop=drop, env={})
+def _lstm(C, state, two=False, drop=False, sat=False):
+    return dict(id=f"lstm-c{C}-{state}" + ("-two" if two else "") + ("-drop" if drop else "") + ("-sat" if sat else ""), op="lstm", C=C, B=2,
+                state=state, two=two, drop=drop, sat=sat, env={})
 
 
 LSTM_CASES = ([_lstm(C, st) for C in WIDTHS for st in ("given", "none", "zero", "h0zero")]
-              + [_lstm(C, st, two, drop) for C in (48, 256) for st, two, drop in (("given", True, True), ("none", False, True), ("h0zero", True, False))])
+              + [_lstm(C, st, two, drop) for C in (48, 256) for st, two, drop in (("given", True, True), ("none", False, True), ("h0zero", True, False))]
+              + [_lstm(C, "given", sat=True) for C in (48, 256)])
 
-ALL_CASES = SCORE_CASES + MSWSA_CASES + PART_CASES + MASK_CASES + ADDPOS_CASES + LSTM_CASES
+ALL_CASES = SCORE_CASES + MSWSA_CASES + MSWSA_ACT_CASES + PART_CASES + MASK_CASES + ADDPOS_CASES + LSTM_CASES
 BY_ID = {c["id"]: c for c in ALL_CASES}
 assert len(BY_ID) == len(ALL_CASES), "duplicate case ids"
 
@@ -195,6 +221,9 @@ def make_inputs(case):
                "qkv_w": rn(3 * C, C, sc=C ** -0.5), "qkv_b": rn(3 * C, sc=0.1), "proj_w": rn(C, C, sc=C ** -0.5), "proj_b": rn(C, sc=0.1),
                "ls1": 0.5 + rn(C, sc=0.1), "fc1_w": rn(2 * inner, C, sc=C ** -0.5), "fc1_b": rn(2 * inner, sc=0.1),
                "fc2_w": rn(C, inner, sc=inner ** -0.5), "fc2_b": rn(C, sc=0.1), "ls2": 0.5 + rn(C, sc=0.1)}
+        if case["gate_gain"] != 1.0:      # (val, gate) = the two halves of the fc1 output
+            inp["fc1_w"][inner:] *= case["gate_gain"]
+            inp["fc1_b"][inner:] *= case["gate_gain"]
         if case.get("peaked"):
             inp["qkv_w"].view(C // case["dh"], 3, case["dh"], C)[:, :2] *= 2.0
         if not case["ls"]:
@@ -221,6 +250,8 @@ def make_inputs(case):
         shape = (B, H, W, C)
         inp = {"x": torch.randn(*shape, generator=g), "w": torch.randn(4 * C, 2 * C, 1, 1, generator=g) * (2 * C) ** -0.5, "b": 0.1 * torch.randn(4 * C, generator=g)}
         h0, c0 = 0.5 * torch.randn(*shape, generator=g), torch.randn(*shape, generator=g)
+        if case["sat"]:
+            inp["w"], c0 = inp["w"] * 8.0, c0 * 4.0
         if case["state"] == "given":
             inp["h0"], inp["c0"] = h0, c0
         elif case["state"] == "zero":
@@ -261,8 +292,15 @@ def check_conditions(case, inp):
     elif op in MSWSA_OPS:
         kept = kept_slots(case)
         assert all(0 <= w < case["B"] * case["N"] and v == sorted(set(v)) and 0 <= v[0] and v[-1] < case["T"] for w, v in kept.items())
-        if op == "mswsa":
+        if op in ("mswsa", "mswsa_act"):
             assert case["B"] * case["N"] * case["T"] == 160
+        if op == "mswsa_act":
+            assert case["sel"] == "mix" and case["act"] in ACT_KINKS and case["gate_gain"] == GATE_GAIN
+            gate = gate_preactivations(case, inp)
+            assert gate.shape == (sum(len(v) for v in kept.values()), case["inner"]) and 2.5 < float(gate.std()) < 3.5, float(gate.std())
+            for k in ACT_KINKS[case["act"]]:
+                assert min(float((gate < k).double().mean()), float((gate > k).double().mean())) >= 0.01, (k, float((gate > k).double().mean()))
+                assert float((gate - k).abs().min()) > KINK_BAND * float(gate.abs().max()), (k, float((gate - k).abs().min()))
         if case["sel"] == "mix":
             assert sorted(len(v) for v in kept.values()) == [1, 3, 7, 12, 19, 20, 20] and 2 not in kept
         elif case["sel"] == "empty2":
@@ -289,10 +327,14 @@ def check_conditions(case, inp):
         assert M == 70 and M % 64
         if case["state"] in ("zero", "h0zero"):
             assert float(inp["h0"].abs().max()) == 0.0
+        if case["sat"]:
+            z = torch.nn.functional.conv2d(R.nchw(torch.cat([inp["x"], inp["h0"]], -1).double()), inp["w"].double(), inp["b"].double())
+            c1 = reference(case, inp, torch.float64)["out:c1"]
+            assert 5.0 < float(z.std()) < 8.0 and float((z.abs() > 10).double().mean()) > 0.08 and float(c1.abs().max()) > 8.0
 
 
 # ------------------------------------------------------------------------------------------------ reference evaluation
-MSWSA_OPS = ("mswsa", "mswsa_part")
+MSWSA_OPS = ("mswsa", "mswsa_part", "mswsa_act")
 NO_GRAD = ("g", "gh", "gc", "gh2", "r_buf", "table", "drop", "drop.d1", "drop.d2", "drop.mlp")
 
 
@@ -306,6 +348,18 @@ def oracle_drop(case, p):
         return None
     n = sum(len(v) for v in kept_slots(case).values())
     return p["drop.d1"][:n], p["drop.d2"][:n], p["drop.mlp"][:n]
+
+
+def gate_preactivations(case, inp):
+    """the gate half of the fc1 output on the kept rows, float64: the argument of the case's activation in the reference evaluation"""
+    seen, act = [], O.GLU_ACTS[case["act"]]
+    O.GLU_ACTS[case["act"]] = lambda gate: (seen.append(gate.detach().clone()), act(gate))[1]
+    try:
+        reference(dict(case, nograd=True), inp, torch.float64)
+    finally:
+        O.GLU_ACTS[case["act"]] = act
+    assert len(seen) == 1
+    return seen[0]
 
 
 def reference(case, inp, dtype):
