@@ -25,6 +25,10 @@
  *    stay on the device in SastSel.counts.
  *  - return 0 on success, negative errno-style code otherwise (-22 bad argument, -5 launch failure).
  *  - *_bwd calls ACCUMULATE (+=) into parameter-gradient buffers and OVERWRITE activation gradients.
+ *  - size limit of every entry point that runs on the GEMM template (linear layers, convolutions, ConvLSTM, MS-WSA, the heads): an
+ *    operand tensor a GEMM reads -- activations, weights, incoming gradients, the tensor a row gather reads from -- spans less than
+ *    2^31 bytes from its base pointer (rows x row stride x 4; index-contiguous operands: 64 rows more).  The loaders address operands
+ *    with 32-bit byte offsets; a call with a larger operand returns -22 before anything is enqueued.  (B = 32 at 1 Mpx reaches 629 MB.)
  */
 #ifndef SAST_HIP_H
 #define SAST_HIP_H

@@ -22,8 +22,9 @@
 //   of selected tokens.
 // * LDS: an RC operand keeps its natural [row][k] order (row stride BK + 4: ds_write_b128 /
 //   ds_read_b128), an IC operand is stored [k][row] (ds_read_b32); both conflict-free.
-// * global loads are branch-free and un-predicated (an invalid slot reads a page of zeros):
-//   anything else makes hipcc drain vmcnt(0) before every load of the k-loop.
+// * global loads are branch-free and un-predicated (an invalid slot reads through a buffer resource at an out-of-range offset, which
+//   the hardware answers with zeros; the dual-source loaders read a page of zeros): anything else makes hipcc drain vmcnt(0) before
+//   every load of the k-loop.
 // * split-R form (weight gradients): `nsplit` work items per output tile partition the
 //   reduction, the epilogue accumulates atomically; optionally the column sums of the A
 //   operand (bias gradient) are produced by the same pass so dY is read once.
@@ -215,6 +216,51 @@ template <class L> struct LoaderExactAlways<L, std::void_t<decltype(L::EXACT_BF1
 template <class EP, class = void> struct EpHasStats : std::false_type {};
 template <class EP> struct EpHasStats<EP, std::void_t<decltype(EP::COLSTATS)>> : std::bool_constant<EP::COLSTATS> {};
 
+// BUFFERED loaders (BUFFERED = true) read through a 128-bit buffer resource instead of a 64-bit address: a slot is a 32-bit BYTE OFFSET
+// from the operand's base, and the hardware range check of the resource stands in for the address select -- an offset at or beyond
+// num_records reads zeros and cannot fault.  The loads stay branch-free and unpredicated, exactly as above.
+//   Desc desc(int Rl) const             once per workgroup, from block-uniform values only (the resource lives in SGPRs)
+//   Ctx prep(...)                       index validity (i < Ieff, j < NJ, a null second source) is folded into the slot's base offset HERE:
+//                                       an invalid slot gets BUF_INVALID, which stays out of range whatever the loop adds to it
+//   void load(desc, ctx, r0, off, Rl, bk, raw, aux, ok)   r0: the k-tile's base (wave-uniform, <= Rl), off: the slot's r inside the
+//                                       tile, bk: the k-tile's width
+// Reduction tail r >= Rl.  Index-contiguous operand (r is the slow index): num_records = the bytes of the first Rl reduction rows, the
+// tail is out of range in hardware, no compare and no select in the loop.  Reduce-contiguous operand: one compare and one 32-bit select.
+// Every valid offset is below 2^31 (host: gemm_span_ok refuses larger operands before any launch), BUF_INVALID + any valid offset
+// stays in [2^31, 2^32): the 32-bit sums never wrap into range.  The k-tile offset is added on the vector unit (one v_add of an SGPR):
+// the soffset operand stays 0, nothing here depends on whether it takes part in the range check.
+using buf_rsrc = __amdgpu_buffer_rsrc_t;
+constexpr unsigned BUF_INVALID = 0x80000000u;
+constexpr unsigned BUF_MAX_BYTES = 0x80000000u;      // num_records of a resource whose validity is all in the offsets
+// the resource of `bytes` bytes at p; p and bytes must be workgroup-uniform (readfirstlane makes that provable: without it hipcc wraps
+// every load in a waterfall loop)
+__device__ __forceinline__ buf_rsrc make_buf(const void* p, unsigned bytes) {
+  const unsigned long long a = reinterpret_cast<unsigned long long>(p);
+  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a), hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
+  return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((unsigned long long)hi << 32) | lo), 0,
+                                           __builtin_amdgcn_readfirstlane(bytes), 0x00020000);
+}
+__device__ __forceinline__ float4 ldb(buf_rsrc d, unsigned off) {
+  return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(d, off, 0, 0));
+}
+__device__ __forceinline__ float ldb1(buf_rsrc d, unsigned off) {     // the 4-byte form (uint8 event tensors)
+  return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(d, off, 0, 0));
+}
+struct BufDesc { buf_rsrc d; };
+template <class L, class = void> struct LoaderBuffered : std::false_type {};
+template <class L> struct LoaderBuffered<L, std::void_t<decltype(L::BUFFERED)>> : std::bool_constant<L::BUFFERED> {};
+struct NoDesc {};
+template <class L> __device__ __forceinline__ auto loader_desc(const L& l, int Rl) {
+  if constexpr (LoaderBuffered<L>::value) return l.desc(Rl); else return NoDesc{};
+}
+// host: the largest byte span a launch may address from one operand base.  BUF_SPAN_SLACK_ROWS: reduction rows past R that a slot's
+// offset may be formed for (the k-tile base is clamped to Rl, a slot adds at most BK - 1 <= 63 rows)
+constexpr unsigned long long BUF_SPAN_LIMIT = 0x80000000ull;
+constexpr int BUF_SPAN_SLACK_ROWS = 64;
+template <class L> inline bool loader_span_ok(const L& l, int I, int G, int R) {
+  if constexpr (LoaderBuffered<L>::value) return l.span_bytes(I, G, R) < BUF_SPAN_LIMIT; else return true;
+}
+
 // LDS floats one workgroup of an instantiation needs
 // PRESPLIT (bf16x3 build): a reduce-contiguous (RC) operand is split into its three bf16 planes ONCE, by the thread that stores it to
 // LDS, instead of by every wave that reads it (in a 2x2-wave tile each element is read by two waves: the split VALU work of such an
@@ -386,18 +432,25 @@ __device__ __forceinline__ void gemm_body(const LA& la, const LB& lb, const EP& 
 
   // a loader with UNIFORM_TILE gets the k-tile base r0 (wave-uniform) and the lane's offset inside the tile separately: whatever it
   // decodes from r0 alone (the tap of an implicit-GEMM convolution whose channel count is a multiple of BK) runs on the scalar unit
+  // a buffered loader (see "loaders" below) reads through a buffer resource built once per workgroup; it takes the k-tile base clamped
+  // to Rl (a tile past the end of the range is out of range at Rl already, and the 32-bit offsets stay inside the span the host checked)
+  const auto da = loader_desc(la, Rl);
+  const auto db = loader_desc(lb, Rl);
   auto gload = [&](int kt, int set) {
     const int r0 = kt * BK;
+    const int r0c = min(r0, Rl);
 #pragma unroll
     for (int it = 0; it < A_PER; ++it)
       if (A_SLOTS % NT == 0 || tid + it * NT < A_SLOTS) {
-        if constexpr (LoaderUniformTile<LA>::value) la.load_u(ca[it], r0, ra_off[it], Rl, BK, ra[set][it], aa[set][it], oa[set][it]);
+        if constexpr (LoaderBuffered<LA>::value) la.load(da, ca[it], r0c, ra_off[it], Rl, BK, ra[set][it], aa[set][it], oa[set][it]);
+        else if constexpr (LoaderUniformTile<LA>::value) la.load_u(ca[it], r0, ra_off[it], Rl, BK, ra[set][it], aa[set][it], oa[set][it]);
         else la.load(ca[it], r0 + ra_off[it], Rl, ra[set][it], aa[set][it], oa[set][it]);
       }
 #pragma unroll
     for (int it = 0; it < B_PER; ++it)
       if (B_SLOTS % NT == 0 || tid + it * NT < B_SLOTS) {
-        if constexpr (LoaderUniformTile<LB>::value) lb.load_u(cb[it], r0, rb_off[it], Rl, BK, rb[set][it], ab[set][it], ob[set][it]);
+        if constexpr (LoaderBuffered<LB>::value) lb.load(db, cb[it], r0c, rb_off[it], Rl, BK, rb[set][it], ab[set][it], ob[set][it]);
+        else if constexpr (LoaderUniformTile<LB>::value) lb.load_u(cb[it], r0, rb_off[it], Rl, BK, rb[set][it], ab[set][it], ob[set][it]);
         else lb.load(cb[it], r0 + rb_off[it], Rl, rb[set][it], ab[set][it], ob[set][it]);
       }
   };
@@ -609,7 +662,7 @@ __device__ __forceinline__ void gemm_body(const LA& la, const LB& lb, const EP& 
 
   // software pipeline: this k-group owns tiles kt0 + kg + KS*i.  At phase p the LDS buffer p%2 holds tile p, register set
   // (p+1)%PF .. (p+PF-1)%PF hold tiles p+1 .. p+PF-1 and set p%PF (stored to LDS one phase ago) is refilled with tile p+PF.
-  // All loads are issued UNCONDITIONALLY (tiles past the end read the zero page), so the compiler's
+  // All loads are issued UNCONDITIONALLY (tiles past the end read out of range / the zero page), so the compiler's
   // s_waitcnt vmcnt(N) before each LDS store counts exactly the PF-1 younger tiles and leaves them in flight; with loads
   // under a validity branch it has to assume the not-taken path and drains everything.  n_it is block-uniform.
   const int n_it = (kt1 - kt0 + KS - 1) / KS;
@@ -883,10 +936,18 @@ struct ProfScope {
   ~ProfScope() { if (on) prof_scope(n, c, m, st, false); }
 };
 
+// buffered loaders address an operand with 32-bit byte offsets: a launch whose operand spans 2^31 bytes or more from its base is refused
+// before anything is enqueued (include/sast_hip.h, "Size limits")
+template <class T, class LA, class LB>
+inline bool gemm_span_ok(const LA& la, const LB& lb, int M, int NJ, int R) {
+  return loader_span_ok(la, M, 1, R) && loader_span_ok(lb, NJ, T::G, R);
+}
+
 template <class T, class LA, class LB, class EP>
 inline int launch_gemm(const LA& la, const LB& lb, const EP& ep, int M, int NJ, int R, const int* dM,
                        const int* dR, hipStream_t st) {
   if (M <= 0 || NJ <= 0 || R <= 0) return SAST_OK;
+  if (!gemm_span_ok<T>(la, lb, M, NJ, R)) return SAST_EINVAL;
   const int nb = ((M + T::BM - 1) / T::BM) * ((NJ + T::BJ - 1) / T::BJ);
   const int remap = xcd_remap_enabled() && nb >= 16;
   const int grid = remap ? (nb + 7) / 8 * 8 : nb;
@@ -911,6 +972,7 @@ inline int launch_gemm_split(const LA& la, const LB& lb, const EP& ep, int M, in
   if (M <= 0 || NJ <= 0 || R <= 0) return SAST_OK;
   // the column sums of a reduce-contiguous A are taken from its fp32 LDS image; a PRESPLIT one has none (gemm_body would add zeros)
   if (colsum != nullptr && LA::RC && GemmSmem<T, LA, LB>::PSA) return SAST_EINVAL;
+  if (!gemm_span_ok<T>(la, lb, M, NJ, R)) return SAST_EINVAL;
   const int nb = ((M + T::BM - 1) / T::BM) * ((NJ + T::BJ - 1) / T::BJ);
   if (splits < 1) splits = 1;
   const int remap = xcd_remap_enabled() && nb * splits >= 16;
@@ -946,6 +1008,7 @@ inline int launch_gemm_dual(const LA1& la1, const LB1& lb1, const EP1& ep1, int 
   using J1 = GemmJob<TS, LA1, LB1, EP1, true>;
   using J2 = GemmJob<TP, LA2, LB2, EP2, false>;
   if (colsum != nullptr && LA1::RC && GemmSmem<TS, LA1, LB1>::PSA) return SAST_EINVAL;   // see launch_gemm_split
+  if (!gemm_span_ok<TS>(la1, lb1, M1, NJ1, R1) || !gemm_span_ok<TP>(la2, lb2, M2, NJ2, R2)) return SAST_EINVAL;
   if (splits < 1) splits = 1;
   const int nt1 = ((M1 + TS::BM - 1) / TS::BM) * ((NJ1 + TS::BJ - 1) / TS::BJ);
   const int nt2 = ((M2 + TP::BM - 1) / TP::BM) * ((NJ2 + TP::BJ - 1) / TP::BJ);
@@ -989,7 +1052,9 @@ using TileG2Tiny = Tile<32, 64, 1, 1, 2>;   // one wave: 32 rows x (32 ch x 2 gr
 using TileG2K2  = Tile<64, 64, 2, 1, 2, 16, 2>;   // GLU with 2-way k split: 64 rows x (32 ch x 2 groups)
 using TileG2K4  = Tile<32, 64, 1, 1, 2, 16, 4>;   // GLU, 4 single-wave k-groups: 32 rows x (32 ch x 2 groups)
 using TileG4K4  = Tile<32, 128, 1, 1, 4, 16, 4>;  // LSTM, 4 single-wave k-groups: 32 rows x (32 ch x 4 gates)
-using TileG4    = Tile<64, 128, 2, 1, 4>;   // LSTM: 64 rows x (32 ch x 4 gates); 2 waves
+// (OCC = 2: with the buffered B loader hipcc's allocation of the four-gate forward went from 251 to 259 registers, one wave per SIMD
+// instead of two and +6 % on the kernel; the bound keeps it at two, without scratch)
+using TileG4    = Tile<64, 128, 2, 1, 4, 16, 1, 2, 2>;   // LSTM: 64 rows x (32 ch x 4 gates); 2 waves
 using TileG4Big = Tile<128, 128, 4, 1, 4>;  // 128 rows x (32 ch x 4 gates)
 using TileG4Tiny = Tile<32, 128, 1, 1, 4>;  // one wave: 32 rows x (32 ch x 4 gates)
 // the ConvLSTM from a zero cell state: the forget gate multiplies zero, three live gates (i|o|g) per output channel.  BN = 96: nothing in
@@ -1005,6 +1070,7 @@ __host__ __device__ inline int small_div_mul(int d) { return 65536 / d + 1; }
 // concept:  struct Ctx;  A side: Ctx prep(int i, int Ieff);  B side: Ctx prep(int j, int g, int NJ);
 //           void load(const Ctx&, int r, int Reff, float4& raw, float& aux, bool& ok)   (raw registers untouched until ...)
 //           float4 finish(float4 raw, float aux, bool ok)                              (... the LDS store: zeros if !ok)
+//           BUFFERED loaders: Desc desc(Rl) and load(desc, ctx, r0, off, Rl, bk, raw, aux, ok) instead (above gemm_body)
 
 // All loads are BRANCH-FREE: an out-of-range slot reads a safe in-bounds address and the result is replaced by zeros
 // with a select.  (A predicated `cond ? ld4(p) : 0` becomes an exec-masked branch around the global_load; hipcc then
@@ -1012,7 +1078,9 @@ __host__ __device__ inline int small_div_mul(int d) { return 65536 / d + 1; }
 // serialised the two-tile prefetch -- seen in the ISA of the first version of this kernel.)
 // An invalid slot reads a 16-byte page of zeros: the validity decides the ADDRESS (one 64-bit select), the loaded value needs no
 // select.  (The older form, a clamped in-bounds address and 4 v_cndmask per float4 at the LDS store, cost 11-16 % of the k-loop's VALU
-// instructions: DESIGN "Retired compile-time switches".)
+// instructions: DESIGN "Retired compile-time switches".)  Since the buffer-load change this is the form of the
+// DUAL-SOURCE loaders only (LdRows2, LdRowsT2, LdWeightNT2, LdWeightNN2, LdWeightConvDx2): which source a slot reads is decided per
+// lane, a buffer resource is wave-uniform, and one load cannot choose between two.  Every other loader is BUFFERED (above gemm_body).
 static __device__ __attribute__((aligned(16))) float sast_zero_page[4];        // device globals are zero-initialised
 // the load of one slot: `valid` is the address of a slot whose flag is set (it may be out of bounds when the flag is not)
 __device__ __forceinline__ float4 ldz(bool ok, const float* valid) { return ld4(ok ? valid : sast_zero_page); }
@@ -1022,19 +1090,22 @@ __device__ __forceinline__ float ldz1(bool ok, const void* valid) {     // the 4
 #define SAST_DEFAULT_FINISH \
   __device__ __forceinline__ float4 finish(float4 v, float, bool) const { return v; }
 
-// RC rows: X[i][r] = p[row(i)*ld + r]
+// RC rows: X[i][r] = p[row(i)*ld + r].  nsrc: rows of the tensor a gather (idx) reads from, for the host's span check
 struct LdRows {
-  static constexpr bool RC = true;
-  const float* p; int ld; const int* idx;
-  struct Ctx { const float* row; bool ok; };
+  static constexpr bool RC = true, BUFFERED = true;
+  const float* p; int ld; const int* idx; int nsrc = 0;
+  unsigned long long span_bytes(int I, int, int R) const { return 4ull * ((unsigned long long)((idx ? nsrc : I) - 1) * ld + R); }
+  struct Ctx { unsigned row; };
+  using Desc = BufDesc;
+  __device__ __forceinline__ Desc desc(int) const { return Desc{make_buf(p, BUF_MAX_BYTES)}; }
   __device__ __forceinline__ Ctx prep(int i, int Ieff) const {
     const bool ok = i < Ieff;
     const int ii = ok ? i : 0;
-    return Ctx{p + (size_t)(idx ? idx[ii] : ii) * ld, ok};
+    return Ctx{ok ? 4u * (unsigned)(idx ? idx[ii] : ii) * (unsigned)ld : BUF_INVALID};
   }
-  __device__ __forceinline__ void load(const Ctx& c, int r, int Reff, float4& v, float& aux, bool& ok) const {
-    ok = c.ok && r < Reff;
-    v = ldz(ok, c.row + r);
+  __device__ __forceinline__ void load(const Desc& d, const Ctx& c, int r0, int off, int Rl, int, float4& v, float& aux, bool& ok) const {
+    ok = off < Rl - r0;
+    v = ldb(d.d, ok ? (c.row + 4u * off) + 4u * r0 : BUF_INVALID);
     aux = 0.f;
   }
   SAST_DEFAULT_FINISH
@@ -1062,27 +1133,36 @@ struct LdRows2 {
 // `idx ? idx[r] : r` inside load() is a branch around a global load, after which hipcc drains vmcnt(0) before EVERY load of
 // the k-loop (seen in the ISA: no two loads of a wave were ever in flight together in the weight-gradient kernels).
 struct LdRowsT {
-  static constexpr bool RC = false;
+  static constexpr bool RC = false, BUFFERED = true;
   const float* p; int ld;
-  struct Ctx { int i; bool ok; };
-  __device__ __forceinline__ Ctx prep(int i, int Ieff) const { return Ctx{i < Ieff ? i : 0, i < Ieff}; }
-  __device__ __forceinline__ Ctx prep(int j, int, int NJ) const { return Ctx{j < NJ ? j : 0, j < NJ}; }
-  __device__ __forceinline__ void load(const Ctx& c, int r, int Reff, float4& v, float& aux, bool& ok) const {
-    ok = c.ok && r < Reff;
-    v = ldz(ok, p + (size_t)r * ld + c.i);
+  unsigned long long span_bytes(int, int, int R) const { return 4ull * (unsigned long long)(R + BUF_SPAN_SLACK_ROWS) * ld; }
+  struct Ctx { unsigned col; };
+  using Desc = BufDesc;
+  // the first Rl rows: a slot of a valid column ends inside its row, a row at or beyond Rl starts at or beyond num_records
+  __device__ __forceinline__ Desc desc(int Rl) const { return Desc{make_buf(p, 4u * (unsigned)Rl * (unsigned)ld)}; }
+  __device__ __forceinline__ Ctx prep(int i, int Ieff) const { return Ctx{i < Ieff ? 4u * i : BUF_INVALID}; }
+  __device__ __forceinline__ Ctx prep(int j, int, int NJ) const { return Ctx{j < NJ ? 4u * j : BUF_INVALID}; }
+  __device__ __forceinline__ void load(const Desc& d, const Ctx& c, int r0, int off, int, int, float4& v, float& aux, bool& ok) const {
+    ok = true;
+    v = ldb(d.d, (c.col + 4u * (unsigned)(off * ld)) + 4u * (unsigned)(r0 * ld));
     aux = 0.f;
   }
   SAST_DEFAULT_FINISH
 };
-struct LdRowsTG {  // gathered rows: row(r) = idx[r] (a dependent load per k-tile)
-  static constexpr bool RC = false;
-  const float* p; int ld; const int* idx;
-  struct Ctx { int i; bool ok; };
-  __device__ __forceinline__ Ctx prep(int i, int Ieff) const { return Ctx{i < Ieff ? i : 0, i < Ieff}; }
-  __device__ __forceinline__ Ctx prep(int j, int, int NJ) const { return Ctx{j < NJ ? j : 0, j < NJ}; }
-  __device__ __forceinline__ void load(const Ctx& c, int r, int Reff, float4& v, float& aux, bool& ok) const {
-    ok = c.ok && r < Reff;
-    v = ldz(ok, p + (size_t)idx[min(r, Reff - 1)] * ld + c.i);
+struct LdRowsTG {  // gathered rows: row(r) = idx[r] (a dependent load per k-tile); nsrc: rows of the gathered tensor (host span check)
+  static constexpr bool RC = false, BUFFERED = true;
+  const float* p; int ld; const int* idx; int nsrc;
+  unsigned long long span_bytes(int, int, int) const { return 4ull * (unsigned long long)nsrc * ld; }
+  struct Ctx { unsigned col; };
+  using Desc = BufDesc;
+  // the rows of a gather are in no order: the tail is a compare and a 32-bit select on the offset, not the resource's size
+  __device__ __forceinline__ Desc desc(int) const { return Desc{make_buf(p, BUF_MAX_BYTES)}; }
+  __device__ __forceinline__ Ctx prep(int i, int Ieff) const { return Ctx{i < Ieff ? 4u * i : BUF_INVALID}; }
+  __device__ __forceinline__ Ctx prep(int j, int, int NJ) const { return Ctx{j < NJ ? 4u * j : BUF_INVALID}; }
+  __device__ __forceinline__ void load(const Desc& d, const Ctx& c, int r0, int off, int Rl, int, float4& v, float& aux, bool& ok) const {
+    const int r = r0 + off;
+    ok = r < Rl;
+    v = ldb(d.d, ok ? c.col + 4u * (unsigned)idx[min(r, Rl - 1)] * (unsigned)ld : BUF_INVALID);
     aux = 0.f;
   }
   SAST_DEFAULT_FINISH
@@ -1106,16 +1186,18 @@ struct LdRowsT2 {  // dual source along j (for d[W_x | W_h])
 };
 // weights [G*gs rows][ldw], reduce-contiguous (y = x W^T)
 struct LdWeightNT {
-  static constexpr bool RC = true;
+  static constexpr bool RC = true, BUFFERED = true;
   const float* w; int ldw; int gs;
-  struct Ctx { const float* row; bool ok; };
+  unsigned long long span_bytes(int NJ, int G, int R) const { return 4ull * ((unsigned long long)((G - 1) * (long long)gs + NJ - 1) * ldw + R); }
+  struct Ctx { unsigned row; };
+  using Desc = BufDesc;
+  __device__ __forceinline__ Desc desc(int) const { return Desc{make_buf(w, BUF_MAX_BYTES)}; }
   __device__ __forceinline__ Ctx prep(int j, int g, int NJ) const {
-    const bool ok = j < NJ;
-    return Ctx{w + (size_t)(g * gs + (ok ? j : 0)) * ldw, ok};
+    return Ctx{j < NJ ? 4u * (unsigned)(g * gs + j) * (unsigned)ldw : BUF_INVALID};
   }
-  __device__ __forceinline__ void load(const Ctx& c, int r, int Reff, float4& v, float& aux, bool& ok) const {
-    ok = c.ok && r < Reff;
-    v = ldz(ok, c.row + r);
+  __device__ __forceinline__ void load(const Desc& d, const Ctx& c, int r0, int off, int Rl, int, float4& v, float& aux, bool& ok) const {
+    ok = off < Rl - r0;
+    v = ldb(d.d, ok ? (c.row + 4u * off) + 4u * r0 : BUF_INVALID);
     aux = 0.f;
   }
   SAST_DEFAULT_FINISH
@@ -1140,13 +1222,16 @@ struct LdWeightNT2 {
 };
 // weights used as B[r][j] = w[r*ldw + j]  (dx = dy W)
 struct LdWeightNN {
-  static constexpr bool RC = false;
+  static constexpr bool RC = false, BUFFERED = true;
   const float* w; int ldw;
-  struct Ctx { const float* col; bool ok; };
-  __device__ __forceinline__ Ctx prep(int j, int, int NJ) const { return Ctx{w + (j < NJ ? j : 0), j < NJ}; }
-  __device__ __forceinline__ void load(const Ctx& c, int r, int Reff, float4& v, float& aux, bool& ok) const {
-    ok = c.ok && r < Reff;
-    v = ldz(ok, c.col + (size_t)r * ldw);
+  unsigned long long span_bytes(int, int, int R) const { return 4ull * (unsigned long long)(R + BUF_SPAN_SLACK_ROWS) * ldw; }
+  struct Ctx { unsigned col; };
+  using Desc = BufDesc;
+  __device__ __forceinline__ Desc desc(int Rl) const { return Desc{make_buf(w, 4u * (unsigned)Rl * (unsigned)ldw)}; }   // see LdRowsT
+  __device__ __forceinline__ Ctx prep(int j, int, int NJ) const { return Ctx{j < NJ ? 4u * j : BUF_INVALID}; }
+  __device__ __forceinline__ void load(const Desc& d, const Ctx& c, int r0, int off, int, int, float4& v, float& aux, bool& ok) const {
+    ok = true;
+    v = ldb(d.d, (c.col + 4u * (unsigned)(off * ldw)) + 4u * (unsigned)(r0 * ldw));
     aux = 0.f;
   }
   SAST_DEFAULT_FINISH
@@ -1168,18 +1253,20 @@ struct LdWeightNN2 {
 };
 // same with a per-row scale (LayerScale gamma folded into the weight rows); separate type, see LdRowsT
 struct LdWeightNNS {
-  static constexpr bool RC = false;
+  static constexpr bool RC = false, BUFFERED = true;
   const float* w; int ldw; const float* rscale;
-  struct Ctx { const float* col; bool ok; };
-  __device__ __forceinline__ Ctx prep(int j, int, int NJ) const { return Ctx{w + (j < NJ ? j : 0), j < NJ}; }
-  __device__ __forceinline__ void load(const Ctx& c, int r, int Reff, float4& v, float& aux, bool& ok) const {
-    const int rr = min(r, Reff - 1);
-    ok = c.ok && r < Reff;
-    v = ldz(ok, c.col + (size_t)rr * ldw);
-    aux = rscale[rr];
+  unsigned long long span_bytes(int, int, int R) const { return 4ull * (unsigned long long)(R + BUF_SPAN_SLACK_ROWS) * ldw; }
+  struct Ctx { unsigned col; };
+  using Desc = BufDesc;
+  __device__ __forceinline__ Desc desc(int Rl) const { return Desc{make_buf(w, 4u * (unsigned)Rl * (unsigned)ldw)}; }   // see LdRowsT
+  __device__ __forceinline__ Ctx prep(int j, int, int NJ) const { return Ctx{j < NJ ? 4u * j : BUF_INVALID}; }
+  __device__ __forceinline__ void load(const Desc& d, const Ctx& c, int r0, int off, int Rl, int, float4& v, float& aux, bool& ok) const {
+    ok = true;
+    v = ldb(d.d, (c.col + 4u * (unsigned)(off * ldw)) + 4u * (unsigned)(r0 * ldw));
+    aux = rscale[min(r0 + off, Rl - 1)];
   }
   __device__ __forceinline__ float4 finish(float4 v, float aux, bool) const {
-    return make_float4(v.x * aux, v.y * aux, v.z * aux, v.w * aux);        // (zero page: v is already zero where !ok, aux is a clamped, finite load)
+    return make_float4(v.x * aux, v.y * aux, v.z * aux, v.w * aux);        // (v is already zero where the slot is out of range, aux is a clamped, finite load)
   }
 };
 
@@ -1202,23 +1289,27 @@ __device__ __forceinline__ void split_tap(const ConvGeom& g, int chans, unsigned
 }
 // RC: A[m = (b,oy,ox)][r = (kh,kw,c)]
 struct LdIm2col {
-  static constexpr bool RC = true;
+  static constexpr bool RC = true, BUFFERED = true;
   double src_bytes() const { return 4.0 * g.B * g.H * g.W * g.Cin; }   // host: the image is read once, not k*k times
   const float* x; ConvGeom g;
-  struct Ctx { const float* img; int iy0, ix0; bool ok; };
+  unsigned long long span_bytes(int, int, int) const { return 4ull * g.B * g.H * g.W * g.ldx; }
+  struct Ctx { unsigned img; int iy0, ix0; };      // img: byte offset of the row's image (BUF_INVALID: no such row)
+  using Desc = BufDesc;
+  __device__ __forceinline__ Desc desc(int) const { return Desc{make_buf(x, BUF_MAX_BYTES)}; }
   __device__ __forceinline__ Ctx prep(int i, int Ieff) const {
     const bool ok = i < Ieff;
     const int ii = ok ? i : 0;
     const int t = fast_div(ii, g.Wo, g.wo_mul), ox = ii - t * g.Wo, b = fast_div(t, g.Ho, g.ho_mul), oy = t - b * g.Ho;
-    return Ctx{x + (size_t)b * g.H * g.W * g.ldx, oy * g.stride - g.pad, ox * g.stride - g.pad, ok};
+    return Ctx{ok ? 4u * (unsigned)(b * g.H * g.W) * (unsigned)g.ldx : BUF_INVALID, oy * g.stride - g.pad, ox * g.stride - g.pad};
   }
-  __device__ __forceinline__ void load(const Ctx& c, int r, int Reff, float4& v, float& aux, bool& ok) const {
+  __device__ __forceinline__ void load(const Desc& d, const Ctx& c, int r0, int off, int Rl, int, float4& v, float& aux, bool& ok) const {
+    const int r = r0 + off;
     int kh, kw, ch;
-    split_tap(g, g.Cin, g.cin_mul, min(r, Reff - 4), kh, kw, ch);   // r and Reff are multiples of 4: the clamped float4 stays inside one pixel
+    split_tap(g, g.Cin, g.cin_mul, min(r, Rl - 4), kh, kw, ch);   // r and Rl are multiples of 4: the clamped float4 stays inside one pixel
     const int iy = c.iy0 + kh, ix = c.ix0 + kw;
     const int cy = min(max(iy, 0), g.H - 1), cx = min(max(ix, 0), g.W - 1);
-    ok = c.ok && r < Reff && (g.replicate || (cy == iy && cx == ix));
-    v = ldz(ok, c.img + ((size_t)cy * g.W + cx) * g.ldx + ch);
+    ok = (r < Rl) & ((g.replicate != 0) | ((cy == iy) & (cx == ix)));   // bitwise: no branch in the k-loop
+    v = ldb(d.d, ok ? c.img + 4u * (unsigned)((cy * g.W + cx) * g.ldx + ch) : BUF_INVALID);
     aux = 0.f;
   }
   SAST_DEFAULT_FINISH
@@ -1230,45 +1321,53 @@ __device__ __forceinline__ float4 widen_u8x4(float raw) {
   return make_float4((float)(w & 255u), (float)((w >> 8) & 255u), (float)((w >> 16) & 255u), (float)(w >> 24));
 }
 struct LdIm2colQ8 {
-  static constexpr bool RC = true;
+  static constexpr bool RC = true, BUFFERED = true;
   double src_bytes() const { return 1.0 * g.B * g.H * g.W * g.Cin; }
   const unsigned char* x; ConvGeom g;          // g.ldx = bytes per pixel (= Cin, a multiple of 4)
-  struct Ctx { const unsigned char* img; int iy0, ix0; bool ok; };
+  unsigned long long span_bytes(int, int, int) const { return 1ull * g.B * g.H * g.W * g.ldx; }
+  struct Ctx { unsigned img; int iy0, ix0; };
+  using Desc = BufDesc;
+  __device__ __forceinline__ Desc desc(int) const { return Desc{make_buf(x, BUF_MAX_BYTES)}; }
   __device__ __forceinline__ Ctx prep(int i, int Ieff) const {
     const bool ok = i < Ieff;
     const int ii = ok ? i : 0;
     const int t = fast_div(ii, g.Wo, g.wo_mul), ox = ii - t * g.Wo, b = fast_div(t, g.Ho, g.ho_mul), oy = t - b * g.Ho;
-    return Ctx{x + (size_t)b * g.H * g.W * g.ldx, oy * g.stride - g.pad, ox * g.stride - g.pad, ok};
+    return Ctx{ok ? (unsigned)(b * g.H * g.W) * (unsigned)g.ldx : BUF_INVALID, oy * g.stride - g.pad, ox * g.stride - g.pad};
   }
-  __device__ __forceinline__ void load(const Ctx& c, int r, int Reff, float4& v, float& aux, bool& ok) const {
+  __device__ __forceinline__ void load(const Desc& d, const Ctx& c, int r0, int off, int Rl, int, float4& v, float& aux, bool& ok) const {
+    const int r = r0 + off;
     int kh, kw, ch;
-    split_tap(g, g.Cin, g.cin_mul, min(r, Reff - 4), kh, kw, ch);
+    split_tap(g, g.Cin, g.cin_mul, min(r, Rl - 4), kh, kw, ch);
     const int iy = c.iy0 + kh, ix = c.ix0 + kw;
     const int cy = min(max(iy, 0), g.H - 1), cx = min(max(ix, 0), g.W - 1);
-    ok = c.ok && r < Reff && (g.replicate || (cy == iy && cx == ix));
-    v.x = ldz1(ok, c.img + ((size_t)cy * g.W + cx) * g.ldx + ch);
+    ok = (r < Rl) & ((g.replicate != 0) | ((cy == iy) & (cx == ix)));   // bitwise: no branch in the k-loop
+    v.x = ldb1(d.d, ok ? c.img + (unsigned)((cy * g.W + cx) * g.ldx + ch) : BUF_INVALID);
     aux = 0.f;
   }
   __device__ __forceinline__ float4 finish(float4 v, float, bool) const { return widen_u8x4(v.x); }
 };
 struct LdIm2colTQ8 {
-  static constexpr bool RC = false;
+  static constexpr bool RC = false, BUFFERED = true;
   double src_bytes() const { return 1.0 * g.B * g.H * g.W * g.Cin; }
   const unsigned char* x; ConvGeom g;
-  struct Ctx { int kh, kw, c; bool ok; };
+  unsigned long long span_bytes(int, int, int) const { return 1ull * g.B * g.H * g.W * g.ldx; }
+  struct Ctx { int kh, kw; unsigned c; };          // c: byte offset of the channel inside a pixel (BUF_INVALID: no such column)
+  using Desc = BufDesc;
+  __device__ __forceinline__ Desc desc(int) const { return Desc{make_buf(x, BUF_MAX_BYTES)}; }
   __device__ __forceinline__ Ctx prep(int j, int, int NJ) const {
     Ctx c;
-    c.ok = j < NJ;
-    split_tap(g, g.Cin, g.cin_mul, c.ok ? j : 0, c.kh, c.kw, c.c);
+    int ch;
+    split_tap(g, g.Cin, g.cin_mul, j < NJ ? j : 0, c.kh, c.kw, ch);
+    c.c = j < NJ ? (unsigned)ch : BUF_INVALID;
     return c;
   }
-  __device__ __forceinline__ void load(const Ctx& c, int r, int Reff, float4& v, float& aux, bool& ok) const {
-    const int rr = min(r, Reff - 1);
+  __device__ __forceinline__ void load(const Desc& d, const Ctx& c, int r0, int off, int Rl, int, float4& v, float& aux, bool& ok) const {
+    const int r = r0 + off, rr = min(r, Rl - 1);
     const int t = fast_div(rr, g.Wo, g.wo_mul), ox = rr - t * g.Wo, b = fast_div(t, g.Ho, g.ho_mul), oy = t - b * g.Ho;
     const int iy = oy * g.stride - g.pad + c.kh, ix = ox * g.stride - g.pad + c.kw;
     const int cy = min(max(iy, 0), g.H - 1), cx = min(max(ix, 0), g.W - 1);
-    ok = c.ok && r < Reff && (g.replicate || (cy == iy && cx == ix));
-    v.x = ldz1(ok, x + ((size_t)(b * g.H + cy) * g.W + cx) * g.ldx + c.c);
+    ok = (r < Rl) & ((g.replicate != 0) | ((cy == iy) & (cx == ix)));   // bitwise: no branch in the k-loop
+    v.x = ldb1(d.d, ok ? c.c + (unsigned)(((b * g.H + cy) * g.W + cx) * g.ldx) : BUF_INVALID);
     aux = 0.f;
   }
   __device__ __forceinline__ float4 finish(float4 v, float, bool) const { return widen_u8x4(v.x); }
@@ -1279,36 +1378,40 @@ struct LdIm2colTQ8 {
 // sharing a SIMD the VALU port, not the MFMA pipe, bounded the paired conv kernels: tools/conv_timeline.py)
 struct LdIm2colU : LdIm2col {
   static constexpr bool UNIFORM_TILE = true;
-  __device__ __forceinline__ void load_u(const Ctx& c, int r0, int off, int Reff, int bk, float4& v, float& aux, bool& ok) const {
-    const int rc = min(r0, Reff - bk);           // uniform; Reff and r0 are multiples of bk
+  __device__ __forceinline__ void load(const Desc& d, const Ctx& c, int r0, int off, int Rl, int bk, float4& v, float& aux, bool& ok) const {
+    const int rc = min(r0, Rl - bk);             // uniform; Rl and r0 are multiples of bk
     int kh, kw, ch0;
     split_tap(g, g.Cin, g.cin_mul, rc, kh, kw, ch0);
     const int iy = c.iy0 + kh, ix = c.ix0 + kw;
     const int cy = min(max(iy, 0), g.H - 1), cx = min(max(ix, 0), g.W - 1);
-    ok = c.ok && r0 < Reff && (g.replicate || (cy == iy && cx == ix));
-    v = ldz(ok, c.img + ((size_t)cy * g.W + cx) * g.ldx + ch0 + off);
+    ok = (r0 < Rl) & ((g.replicate != 0) | ((cy == iy) & (cx == ix)));
+    v = ldb(d.d, ok ? c.img + 4u * (unsigned)((cy * g.W + cx) * g.ldx + ch0 + off) : BUF_INVALID);
     aux = 0.f;
   }
 };
 // IC: B(t)[r = (b,oy,ox)][j = (kh,kw,c)]   (weight gradient)
 struct LdIm2colT {
-  static constexpr bool RC = false;
+  static constexpr bool RC = false, BUFFERED = true;
   double src_bytes() const { return 4.0 * g.B * g.H * g.W * g.Cin; }
   const float* x; ConvGeom g;
-  struct Ctx { int kh, kw, c; bool ok; };
+  unsigned long long span_bytes(int, int, int) const { return 4ull * g.B * g.H * g.W * g.ldx; }
+  struct Ctx { int kh, kw; unsigned c; };          // c: byte offset of the channel inside a pixel (BUF_INVALID: no such column)
+  using Desc = BufDesc;
+  __device__ __forceinline__ Desc desc(int) const { return Desc{make_buf(x, BUF_MAX_BYTES)}; }
   __device__ __forceinline__ Ctx prep(int j, int, int NJ) const {
     Ctx c;
-    c.ok = j < NJ;
-    split_tap(g, g.Cin, g.cin_mul, c.ok ? j : 0, c.kh, c.kw, c.c);
+    int ch;
+    split_tap(g, g.Cin, g.cin_mul, j < NJ ? j : 0, c.kh, c.kw, ch);
+    c.c = j < NJ ? 4u * (unsigned)ch : BUF_INVALID;
     return c;
   }
-  __device__ __forceinline__ void load(const Ctx& c, int r, int Reff, float4& v, float& aux, bool& ok) const {
-    const int rr = min(r, Reff - 1);
+  __device__ __forceinline__ void load(const Desc& d, const Ctx& c, int r0, int off, int Rl, int, float4& v, float& aux, bool& ok) const {
+    const int r = r0 + off, rr = min(r, Rl - 1);
     const int t = fast_div(rr, g.Wo, g.wo_mul), ox = rr - t * g.Wo, b = fast_div(t, g.Ho, g.ho_mul), oy = t - b * g.Ho;
     const int iy = oy * g.stride - g.pad + c.kh, ix = ox * g.stride - g.pad + c.kw;
     const int cy = min(max(iy, 0), g.H - 1), cx = min(max(ix, 0), g.W - 1);
-    ok = c.ok && r < Reff && (g.replicate || (cy == iy && cx == ix));
-    v = ldz(ok, x + ((size_t)(b * g.H + cy) * g.W + cx) * g.ldx + c.c);
+    ok = (r < Rl) & ((g.replicate != 0) | ((cy == iy) & (cx == ix)));   // bitwise: no branch in the k-loop
+    v = ldb(d.d, ok ? c.c + 4u * (unsigned)(((b * g.H + cy) * g.W + cx) * g.ldx) : BUF_INVALID);
     aux = 0.f;
   }
   SAST_DEFAULT_FINISH
@@ -1334,15 +1437,18 @@ using LdIm2colTQ8X = LdExactBf16Always<LdIm2colTQ8>;
 // RC: backward-data gather  A[m = (b,iy,ix)][r = (kh,kw,co)] = dY[b,(iy+p-kh)/s,(ix+p-kw)/s,co]
 // replicate padding: the clamped taps (kh < pad at iy == 0, same for x) fold onto output row/col 0.
 struct LdConvDx {
-  static constexpr bool RC = true;
+  static constexpr bool RC = true, BUFFERED = true;
   double src_bytes() const { return 4.0 * g.B * g.Ho * g.Wo * Cout; }   // host: dY is read once, not once per tap
   const float* dy; ConvGeom g; int Cout; int lddy; unsigned cout_mul;   // cout_mul = div_mul_of(Cout, reduce length), never 0
-  struct Ctx { const float* img; int iy, ix; bool ok; };
+  unsigned long long span_bytes(int, int, int) const { return 4ull * g.B * g.Ho * g.Wo * lddy; }
+  struct Ctx { unsigned img; int iy, ix; };        // img: byte offset of the row's dY image (BUF_INVALID: no such row)
+  using Desc = BufDesc;
+  __device__ __forceinline__ Desc desc(int) const { return Desc{make_buf(dy, BUF_MAX_BYTES)}; }
   __device__ __forceinline__ Ctx prep(int i, int Ieff) const {
     const bool ok = i < Ieff;
     const int ii = ok ? i : 0;
     const int t = fast_div(ii, g.W, g.w_mul), ix = ii - t * g.W, b = fast_div(t, g.H, g.h_mul), iy = t - b * g.H;
-    return Ctx{dy + (size_t)b * g.Ho * g.Wo * lddy, iy, ix, ok};
+    return Ctx{ok ? 4u * (unsigned)(b * g.Ho * g.Wo) * (unsigned)lddy : BUF_INVALID, iy, ix};
   }
   // source output coordinate of input coordinate i under tap k (returns validity; o is always in range)
   __device__ __forceinline__ bool src(int i, int k, int n_out, int& o) const {
@@ -1353,41 +1459,46 @@ struct LdConvDx {
     o = hit ? q : 0;
     return hit || rep;
   }
-  __device__ __forceinline__ void load(const Ctx& c, int r, int Reff, float4& v, float& aux, bool& ok) const {
+  __device__ __forceinline__ void load(const Desc& d, const Ctx& c, int r0, int off, int Rl, int, float4& v, float& aux, bool& ok) const {
+    const int r = r0 + off;
     int kh, kw, co;
-    split_tap(g, Cout, cout_mul, min(r, Reff - 4), kh, kw, co);
+    split_tap(g, Cout, cout_mul, min(r, Rl - 4), kh, kw, co);
     int oy, ox;
     const bool vy = src(c.iy, kh, g.Ho, oy), vx = src(c.ix, kw, g.Wo, ox);
-    ok = c.ok && r < Reff && vy && vx;
-    v = ldz(ok, c.img + ((size_t)oy * g.Wo + ox) * lddy + co);
+    ok = (r < Rl) & vy & vx;
+    v = ldb(d.d, ok ? c.img + 4u * (unsigned)((oy * g.Wo + ox) * lddy + co) : BUF_INVALID);
     aux = 0.f;
   }
   SAST_DEFAULT_FINISH
 };
 struct LdConvDxU : LdConvDx {   // Cout a multiple of the k-tile: uniform tap, see LdIm2colU
   static constexpr bool UNIFORM_TILE = true;
-  __device__ __forceinline__ void load_u(const Ctx& c, int r0, int off, int Reff, int bk, float4& v, float& aux, bool& ok) const {
-    const int rc = min(r0, Reff - bk);
+  __device__ __forceinline__ void load(const Desc& d, const Ctx& c, int r0, int off, int Rl, int bk, float4& v, float& aux, bool& ok) const {
+    const int rc = min(r0, Rl - bk);
     int kh, kw, co0;
     split_tap(g, Cout, cout_mul, rc, kh, kw, co0);
     int oy, ox;
     const bool vy = src(c.iy, kh, g.Ho, oy), vx = src(c.ix, kw, g.Wo, ox);
-    ok = c.ok && r0 < Reff && vy && vx;
-    v = ldz(ok, c.img + ((size_t)oy * g.Wo + ox) * lddy + co0 + off);
+    ok = (r0 < Rl) & vy & vx;
+    v = ldb(d.d, ok ? c.img + 4u * (unsigned)((oy * g.Wo + ox) * lddy + co0 + off) : BUF_INVALID);
     aux = 0.f;
   }
 };
 // IC: B[r = (tap,co)][j = ci] = w[co][tap][ci]   (weights stored channels-last: [Cout][KH][KW][Cin])
 struct LdWeightConvDx {
-  static constexpr bool RC = false;
+  static constexpr bool RC = false, BUFFERED = true;
   const float* w; int Cout, taps, Cin; unsigned cout_mul;
-  struct Ctx { const float* col; bool ok; };
-  __device__ __forceinline__ Ctx prep(int j, int, int NJ) const { return Ctx{w + (j < NJ ? j : 0), j < NJ}; }
-  __device__ __forceinline__ void load(const Ctx& c, int r, int Reff, float4& v, float& aux, bool& ok) const {
-    const int rr = min(r, Reff - 1);
+  unsigned long long span_bytes(int, int, int) const { return 4ull * Cout * taps * Cin; }
+  struct Ctx { unsigned col; };
+  using Desc = BufDesc;
+  // r runs over (tap, co) while the rows are stored (co, tap): the tail is a compare and a 32-bit select, not the resource's size
+  __device__ __forceinline__ Desc desc(int) const { return Desc{make_buf(w, BUF_MAX_BYTES)}; }
+  __device__ __forceinline__ Ctx prep(int j, int, int NJ) const { return Ctx{j < NJ ? 4u * j : BUF_INVALID}; }
+  __device__ __forceinline__ void load(const Desc& d, const Ctx& c, int r0, int off, int Rl, int, float4& v, float& aux, bool& ok) const {
+    const int r = r0 + off, rr = min(r, Rl - 1);
     const int tap = (int)__umulhi((unsigned)rr, cout_mul), co = rr - tap * Cout;
-    ok = c.ok && r < Reff;
-    v = ldz(ok, c.col + ((size_t)co * taps + tap) * Cin);
+    ok = r < Rl;
+    v = ldb(d.d, ok ? c.col + 4u * (unsigned)((co * taps + tap) * Cin) : BUF_INVALID);
     aux = 0.f;
   }
   SAST_DEFAULT_FINISH
@@ -1395,11 +1506,11 @@ struct LdWeightConvDx {
 
 struct LdWeightConvDxU : LdWeightConvDx {   // Cout a multiple of the k-tile: the tap of the tile comes from the uniform base
   static constexpr bool UNIFORM_TILE = true;
-  __device__ __forceinline__ void load_u(const Ctx& c, int r0, int off, int Reff, int bk, float4& v, float& aux, bool& ok) const {
-    const int rc = min(r0, Reff - bk);
+  __device__ __forceinline__ void load(const Desc& d, const Ctx& c, int r0, int off, int Rl, int bk, float4& v, float& aux, bool& ok) const {
+    const int rc = min(r0, Rl - bk);
     const int tap = (int)__umulhi((unsigned)rc, cout_mul), co0 = rc - tap * Cout;
-    ok = c.ok && r0 < Reff;
-    v = ldz(ok, c.col + ((size_t)co0 * taps + tap) * Cin + (size_t)off * (taps * Cin));
+    ok = r0 < Rl;
+    v = ldb(d.d, ok ? (c.col + 4u * (unsigned)(off * (taps * Cin))) + 4u * (unsigned)((co0 * taps + tap) * Cin) : BUF_INVALID);
     aux = 0.f;
   }
 };
@@ -1439,10 +1550,13 @@ struct ConvDxClasses {
   }
 };
 struct LdConvDxP {
-  static constexpr bool RC = true;
+  static constexpr bool RC = true, BUFFERED = true;
   double src_bytes() const { return 4.0 * g.B * g.Ho * g.Wo * Cout; }
   const float* dy; ConvGeom g; int Cout; int lddy; unsigned cout_mul; ConvDxClasses k;
-  struct Ctx { const float* img; int iy, ix; unsigned kh, kw; bool ok; };
+  unsigned long long span_bytes(int, int, int) const { return 4ull * g.B * g.Ho * g.Wo * lddy; }
+  struct Ctx { unsigned img; int iy, ix; unsigned kh, kw; };
+  using Desc = BufDesc;
+  __device__ __forceinline__ Desc desc(int) const { return Desc{make_buf(dy, BUF_MAX_BYTES)}; }
   __device__ __forceinline__ Ctx prep(int i, int Ieff) const {
     const bool ok = i < Ieff;
     const int ii = ok ? i : 0;
@@ -1450,7 +1564,7 @@ struct LdConvDxP {
     const int t = fast_div(ic, k.Wc, k.wc_mul), xx = ic - t * k.Wc, b = fast_div(t, k.Hc, k.hc_mul), yy = t - b * k.Hc;
     Ctx c;
     const int q = 3 - cls;   // the classes are laid out heaviest first (odd-odd pixels see 4 taps, even-even 1): parity = 3 - position
-    c.img = dy + (size_t)b * g.Ho * g.Wo * lddy; c.iy = 2 * yy + (q >> 1); c.ix = 2 * xx + (q & 1); c.ok = ok;
+    c.img = ok ? 4u * (unsigned)(b * g.Ho * g.Wo) * (unsigned)lddy : BUF_INVALID; c.iy = 2 * yy + (q >> 1); c.ix = 2 * xx + (q & 1);
     k.packs(cls, c.kh, c.kw);
     return c;
   }
@@ -1462,37 +1576,40 @@ struct LdConvDxP {
     o = hit ? q : 0;
     return hit || rep;
   }
-  __device__ __forceinline__ void load(const Ctx& c, int r, int Reff, float4& v, float& aux, bool& ok) const {
-    const int rr = min(r, Reff - 4);
+  __device__ __forceinline__ void load(const Desc& d, const Ctx& c, int r0, int off, int Rl, int, float4& v, float& aux, bool& ok) const {
+    const int r = r0 + off, rr = min(r, Rl - 4);
     const int slot = (int)__umulhi((unsigned)rr, cout_mul), co = rr - slot * Cout;
     const int kh = (c.kh >> (4 * slot)) & 15, kw = (c.kw >> (4 * slot)) & 15;
     int oy, ox;
     const bool vy = src(c.iy, kh, g.Ho, oy), vx = src(c.ix, kw, g.Wo, ox);
-    ok = c.ok && r < Reff && vy && vx;
-    v = ldz(ok, c.img + ((size_t)oy * g.Wo + ox) * lddy + co);
+    ok = (r < Rl) & vy & vx;
+    v = ldb(d.d, ok ? c.img + 4u * (unsigned)((oy * g.Wo + ox) * lddy + co) : BUF_INVALID);
     aux = 0.f;
   }
   SAST_DEFAULT_FINISH
 };
 struct LdWeightConvDxP {
-  static constexpr bool RC = false;
+  static constexpr bool RC = false, BUFFERED = true;
   static constexpr bool WANTS_M0 = true;
   const float* w; int Cout, taps, Cin; unsigned cout_mul; int KW; ConvDxClasses k;
-  struct Ctx { const float* col; unsigned kh, kw; bool ok; };
+  unsigned long long span_bytes(int, int, int) const { return 4ull * Cout * taps * Cin; }
+  struct Ctx { unsigned col; unsigned kh, kw; };
+  using Desc = BufDesc;
+  __device__ __forceinline__ Desc desc(int) const { return Desc{make_buf(w, BUF_MAX_BYTES)}; }
   __device__ __forceinline__ Ctx prep(int j, int, int NJ, int m0) const {
     Ctx c;
-    c.col = w + (j < NJ ? j : 0); c.ok = j < NJ;
+    c.col = j < NJ ? 4u * j : BUF_INVALID;
     k.packs(m0 / k.Mc, c.kh, c.kw);
     return c;
   }
   __device__ __forceinline__ int reduce_len(int m0) const { return k.slots(m0 / k.Mc) * Cout; }
-  __device__ __forceinline__ void load(const Ctx& c, int r, int Reff, float4& v, float& aux, bool& ok) const {
-    const int rr = min(r, Reff - 1);
+  __device__ __forceinline__ void load(const Desc& d, const Ctx& c, int r0, int off, int Rl, int, float4& v, float& aux, bool& ok) const {
+    const int r = r0 + off, rr = min(r, Rl - 1);
     const int slot = (int)__umulhi((unsigned)rr, cout_mul), co = rr - slot * Cout;
     const int kh = (c.kh >> (4 * slot)) & 15, kw = (c.kw >> (4 * slot)) & 15;
     const bool empty = kh == 15 || kw == 15;
-    ok = c.ok && r < Reff && !empty;
-    v = ldz(ok, c.col + ((size_t)co * taps + (empty ? 0 : kh * KW + kw)) * Cin);
+    ok = (r < Rl) & !empty;
+    v = ldb(d.d, ok ? c.col + 4u * (unsigned)((co * taps + (empty ? 0 : kh * KW + kw)) * Cin) : BUF_INVALID);
     aux = 0.f;
   }
   SAST_DEFAULT_FINISH

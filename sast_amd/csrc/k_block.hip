@@ -490,14 +490,14 @@ int sast_mswsa_bwd(const SastMswsaArgs* a, sast_stream_t stream) { SAST_ENTRY();
   // with the GLU backward: dUG from the saved pre-activations
   auto fc2_bwd = [&](auto ep) {
     if (dz_tok && a->ls2)
-      return gemm_pair(LdRowsTG{dz, C, dz_tok}, LdRowsT{a->Hh, inner}, raw2, inner, C, inner, R, dR, s2,
-                       LdRows{dz, C, dz_tok}, LdWeightNNS{a->fc2_w, inner, a->ls2}, ep, R, inner, C, dR, st);
+      return gemm_pair(LdRowsTG{dz, C, dz_tok, R}, LdRowsT{a->Hh, inner}, raw2, inner, C, inner, R, dR, s2,
+                       LdRows{dz, C, dz_tok, R}, LdWeightNNS{a->fc2_w, inner, a->ls2}, ep, R, inner, C, dR, st);
     // Context Broadcasting (compact dZ') or LayerScale disabled: the rarely used combinations stay two launches
-    int r = dz_tok ? gemm_tn(LdRowsTG{dz, C, dz_tok}, LdRowsT{a->Hh, inner}, raw2, inner, C, inner, R, dR, s2, st)
+    int r = dz_tok ? gemm_tn(LdRowsTG{dz, C, dz_tok, R}, LdRowsT{a->Hh, inner}, raw2, inner, C, inner, R, dR, s2, st)
                    : gemm_tn(LdRowsT{dz, C}, LdRowsT{a->Hh, inner}, raw2, inner, C, inner, R, dR, s2, st);
     if (r) return r;
-    return a->ls2 ? gemm_auto(LdRows{dz, C, dz_tok}, LdWeightNNS{a->fc2_w, inner, a->ls2}, ep, R, inner, C, dR, st)
-                  : gemm_auto(LdRows{dz, C, dz_tok}, LdWeightNN{a->fc2_w, inner}, ep, R, inner, C, dR, st);
+    return a->ls2 ? gemm_auto(LdRows{dz, C, dz_tok, R}, LdWeightNNS{a->fc2_w, inner, a->ls2}, ep, R, inner, C, dR, st)
+                  : gemm_auto(LdRows{dz, C, dz_tok, R}, LdWeightNN{a->fc2_w, inner}, ep, R, inner, C, dR, st);
   };
   const bool prelu = a->mlp_act == GLU_ACT_PRELU;
   float* slope_slots = (prelu && a->d_act_w) ? a->ws + mswsa_bwd_ws_base(R, C, inner) + (size_t)R * (C / 4) : nullptr;
