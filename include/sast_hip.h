@@ -793,6 +793,60 @@ int sast_evt2_decode(const void* words, const int64_t* counts, int64_t chunk_wor
                      int64_t* state, void* ws, int16_t* x, int16_t* y, int16_t* p, int64_t* t, int64_t max_events, int64_t* out_counts,
                      int32_t* err, sast_stream_t stream);
 
+/* ---- events -> raw sensor words, EVT 2.0 and EVT 2.1 (csrc/k_evt2_enc.hip): the inverse of the section above, event columns (the
+ * dtypes of sast_evqueue_push) or packed Event2D records (SAST_EVQUEUE_DT_DAT's layout) -> EVT 2.0 / 2.1 words that sast_evt2_decode
+ * turns back into the events.  The contract, the chunking rule and the two launches are those of sast_evt3enc_encode (the driver,
+ * csrc/evt_enc.cuh, is shared).  The rule is canonical and deterministic; it is this project's (parity with the Metavision SDK's
+ * encoder is unpinned, the SDK is not a dependency; what is pinned is the sequential model of tests/evt2_encoder_model.py).  Per
+ * stream the state have, t_last, all 0 after a reset.  One row's chunk of n events:
+ *   1. normalised: t the running maximum over the row, from t_last when have is set and from 0 otherwise; x and y clamped to
+ *      0 .. 2047; p = p != 0.  An event changed by this is counted (err[0]: t raised, err[1]: x, y or p changed), never dropped.
+ *   2. groups: EVT 2.0: every event is a leader.  EVT 2.1: event j continues the group of event j - 1 iff both are in this chunk, have
+ *      the same t, y and p, x[j-1] < x[j] and x[j-1] >> 5 == x[j] >> 5; every other event, and a chunk's first, is a leader.  A group
+ *      has at most 32 members.  A cut ends a group: the words depend on the cuts, the decoded events do not.
+ *   3. only leaders send words.  Leader i, with "the event in front" the state for i == 0, H = t >> 6 and Hp = t_front >> 6, in
+ *      this order:
+ *        0x8 EVT_TIME_HIGH  (2.0: value in bits 0..27; 2.1: value in bits 32..59)  !have: H & 0x0FFFFFFF.  have and H > Hp:
+ *                           floor((H - Hp - 1) / 2^26) keep-alives (Hp + 2^26 q) & 0x0FFFFFFF, q = 1 .., then H & 0x0FFFFFFF: two
+ *                           neighbouring TIME_HIGHs are 1 .. 2^26 steps apart, so the decoder's high - v >= 2^27 test sees every
+ *                           wrap of the 28 bits exactly once.  No TIME_HIGH otherwise
+ *        the event word, type p (0x0 / 0x1), ts6 = t & 63:
+ *          EVT 2.0  ts6 in bits 22..27, x in bits 11..21, y in bits 0..10
+ *          EVT 2.1  one 64-bit little-endian word: ts6 in bits 54..59, x_base = 32 * (x >> 5) in bits 43..53 (as a sensor aligns it:
+ *                   never past column 2047), y in bits 32..42, valid = one bit x & 31 per member
+ *      No EXT_TRIGGER, OTHERS or CONTINUED word is sent.  Without keep-alives an event gives at most 2 words.
+ *   4. the state after the chunk is (1, t) of its last event; an empty chunk leaves it alone.
+ * A fresh decoder starts with wraps = 0: it returns t - ((t0 >> 34) << 34), t0 the row's first event.  That is the format's 34-bit
+ * clock. */
+#define SAST_EVT2_ENC_STATE_WORDS 4     /* a row of `state`: have, t_last, 0, 0 */
+#define SAST_EVT2_ENC_BLOCK_EVENTS 1024 /* events a workgroup takes in one step; a row gets ceil(chunk_events / this) workgroups ... */
+#define SAST_EVT2_ENC_MAX_BLOCKS 256    /* ... at most this many, which then take several steps each */
+/* bytes of the encode's workspace (per row the state and one summary per workgroup).  0: S < 1 or S > 65535.  Host only. */
+size_t sast_evt2enc_ws_bytes(int S);
+/* as sast_evt3enc_encode, with version SAST_EVT2_V20 / SAST_EVT2_V21: per row s, with reset != NULL and reset[s] != 0 the row's state
+ * is zeroed first.  Then the first n_s = min(max(counts[s], 0), chunk_events) events of row s are encoded: x, y, p SAST_DT_I64 / I32 /
+ * I16 [S, chunk_events], t SAST_DT_I64 / I32.  The words go to words[s] (2.0: 32-bit words, 2.1: 64-bit words, [S, max_words]) from
+ * column 0 on, n_words[s] is their number, state[s] (int64 [S, SAST_EVT2_ENC_STATE_WORDS]) becomes the state after the chunk.  A row
+ * whose words exceed max_words is refused whole: n_words[s] = 0, its state as it was (zero if its reset flag was set), one count in
+ * err[2], nothing in err[0] and err[1].  err, int32 [4], ACCUMULATED: [0] times raised to the running maximum, [1] events whose x, y
+ * or p was clamped, [2] rows refused for lack of room, [3] spare.  max_words = 2 * chunk_events + (the keep-alives: one per 2^32 us
+ * of silence) never refuses.  SAST_EINVAL before any launch: a null pointer (reset may be), S outside 1 .. 65535, an unknown version
+ * or dtype, chunk_events < 0, S * chunk_events or S * max_words > 2^31 - 1, max_words < 1, words not aligned to its word size, ws not
+ * 8-byte aligned.
+ * 2 launches whatever S and the sizes are (one summary per workgroup: words, largest t, raised and clamped events; fold the summaries +
+ * scan + write, the row's last workgroup writes state, n_words and counters): no workgroup reads what another one writes in the same
+ * launch, nothing has to be put back for a graph replay, every store is a plain vector store.  A row with a raised time (unsorted
+ * input, counted in err[0]) is walked whole by its last workgroup: the normalised times of a piece then depend on every event before. */
+int sast_evt2enc_encode(const void* x, const void* y, const void* p, const void* t, int x_dtype, int y_dtype, int p_dtype, int t_dtype,
+                        const int64_t* counts, int64_t chunk_events, int S, int version, const uint8_t* reset, int64_t* state, void* ws,
+                        void* words, int64_t max_words, int64_t* n_words, int32_t* err, sast_stream_t stream);
+/* the same from packed records: int32 [S, chunk_events, 2], Prophesee's Event2D as sast_evqueue_push takes it with
+ * SAST_EVQUEUE_DT_DAT (t the unsigned word 0, x = w & 16383, y = (w >> 14) & 16383, p = (w >> 28) & 1 of word 1); records 8-byte
+ * aligned.  DAT -> EVT 2.0 / 2.1 without an unpacked copy. */
+int sast_evt2enc_encode_dat(const void* records, const int64_t* counts, int64_t chunk_events, int S, int version, const uint8_t* reset,
+                            int64_t* state, void* ws, void* words, int64_t max_words, int64_t* n_words, int32_t* err,
+                            sast_stream_t stream);
+
 /* ---- label front end (csrc/k_labels.hip): the raw Prophesee box records of S recordings side by side -> the filtered labels, the
  * label-frame timestamps, the window-end schedule, the frame -> window map and per-step label tensors, all on the device.  The reference
  * does this offline, per recording: apply_filters, get_base_delta_ts_for_labels_us and labels_and_ev_repr_timestamps of

@@ -19,8 +19,8 @@ binned by the logarithm of their age and accumulated over the bins), is `MixedDe
 Prophesee's packed Event2D records, or the raw EVT 3.0 / EVT 2.0 / EVT 2.1 words of a sensor) and gets the frames `EventStreams`
 gives for the whole recording.  `Evt3Decoder` (csrc/k_evt3.hip) and `Evt2Decoder` (csrc/k_evt2.hip) are the stateful decodes of those
 words alone; `raw_header` (host only) reads the format, the geometry and the end of a .raw file's ASCII header.  `Evt3Encoder`
-(csrc/k_evt3_enc.hip) is the way back, columns or Event2D records -> EVT 3.0 words, and `evt3_raw_header` (host only) writes the
-header such a file starts with.
+(csrc/k_evt3_enc.hip) and `Evt2Encoder` (csrc/k_evt2_enc.hip) are the way back, columns or Event2D records -> EVT 3.0 / 2.0 / 2.1
+words, and `evt3_raw_header` / `evt2_raw_header` (host only) write the header such a file starts with.
 
 There is no CPU path: CPU tensors raise the library's "no CPU fallback" error.
 """
@@ -490,7 +490,80 @@ class Evt3Decoder:
         return self.x, self.y, self.p, self.t, self.counts
 
 
-class Evt3Encoder:
+class _EventEncoder:
+    """what `Evt3Encoder` and `Evt2Encoder` share (the device side shares csrc/evt_enc.cuh): the buffers, the argument rules, the
+    counters and the call.  A subclass names its entry points, its word dtype and the room a chunk needs by default."""
+
+    ENCODE_LAUNCHES = 2
+    _STATE_WORDS = _WS_BYTES = _ENCODE = _ENCODE_DAT = _word_dtype = None
+    _EXTRA = ()                                                      # the arguments between S and reset: EVT 2's version code
+
+    def __init__(self, num_streams: int, max_words: Optional[int] = None):
+        self.num_streams = F.stream_count(num_streams, "events")
+        if max_words is not None and int(max_words) < 1:
+            raise ValueError("sast_amd.events: max_words must be >= 1 (or None)")
+        self.max_words = None if max_words is None else int(max_words)
+        if self.max_words is not None and self.num_streams * self.max_words > 2 ** 31 - 1:
+            raise ValueError("sast_amd.events: num_streams * max_words must be below 2^31")
+        self.state = self.err = self.n_words = self.words = self._ws = None
+
+    def _room(self, chunk_events: int) -> int:
+        raise NotImplementedError
+
+    def _buffers(self, dev, chunk_events: int):
+        S = self.num_streams
+        if self.state is None:
+            F.not_capturing("events")
+            self.state = torch.zeros(S, getattr(L, self._STATE_WORDS), dtype=torch.int64, device=dev)
+            self.err = torch.zeros(4, dtype=torch.int32, device=dev)
+            self.n_words = torch.zeros(S, dtype=torch.int64, device=dev)
+            self._ws = torch.zeros(int(getattr(L.lib(), self._WS_BYTES)(S)), dtype=torch.uint8, device=dev)
+        F.lives_on("the encoder's state", self.state.device, "the call's tensors", dev, "events")
+        need = self.max_words if self.max_words is not None else self._room(chunk_events)
+        if self.words is None or self.words.shape[1] < need:
+            F.not_capturing("events")
+            if S * need > 2 ** 31 - 1:
+                raise ValueError("sast_amd.events: num_streams * max_words must be below 2^31")
+            self.words = torch.zeros(S, need, dtype=self._word_dtype, device=dev)
+
+    def errors(self) -> Tuple[int, int, int, int]:
+        """(times raised to the running maximum, events with x, y or p clamped, rows refused for lack of room, 0) since the last
+        reset() (synchronises)"""
+        return F.counters(self.err, 4)
+
+    def reset(self, streams=None):
+        """new recordings, from the host: the encoder state of `streams` (default: all of them) back to zero; with streams=None the
+        counters are cleared as well"""
+        F.reset_rows((self.state,), self.err, streams, self.num_streams, "events")
+
+    def _encode(self, entry, head, chunk_events, counts, reset, tensors):
+        S = self.num_streams
+        F.counts_reset(counts, reset, S, "events")
+        if S * chunk_events > 2 ** 31 - 1:
+            raise ValueError("sast_amd.events: num_streams * chunk events must be below 2^31")
+        _need_gpu(*tensors, counts, reset)
+        F.same_device("events", "the chunk, counts and reset", *tensors, counts, reset)
+        self._buffers(counts.device, chunk_events)
+        # an empty chunk has no storage: any valid device pointer will do, the kernels read no event
+        head = [h or counts.data_ptr() for h in head[:len(tensors)]] + list(head[len(tensors):])
+        L.check(getattr(L.lib(), entry)(*head, counts.data_ptr(), chunk_events, S, *self._EXTRA,
+                                        None if reset is None else reset.data_ptr(), self.state.data_ptr(), self._ws.data_ptr(),
+                                        self.words.data_ptr(), self.words.shape[1], self.n_words.data_ptr(), self.err.data_ptr(),
+                                        _stream()), entry[len("sast_"):])
+        return self.words, self.n_words
+
+    def __call__(self, x: torch.Tensor, y: torch.Tensor, p: torch.Tensor, t: torch.Tensor, counts: torch.Tensor,
+                 reset: Optional[torch.Tensor] = None):
+        codes = F.event_columns(x, y, p, t, self.num_streams, "events", cap_name="chunk events")
+        return self._encode(self._ENCODE, [c.data_ptr() for c in (x, y, p, t)] + list(codes), x.shape[1], counts, reset, [x, y, p, t])
+
+    def encode_dat(self, records: torch.Tensor, counts: torch.Tensor, reset: Optional[torch.Tensor] = None):
+        F.tensor_arg(records, "records", "events", (torch.int32,), (("num_streams", self.num_streams), "chunk events", 2),
+                     "(two words per Event2D record)", empty_ok=True, dtype_error=TypeError)
+        return self._encode(self._ENCODE_DAT, [records.data_ptr()], records.shape[1], counts, reset, [records])
+
+
+class Evt3Encoder(_EventEncoder):
     """Event columns or packed Event2D records -> Prophesee EVT 3.0 sensor words on the device (csrc/k_evt3_enc.hip; the word table and
     the canonical rule are in include/sast_hip.h and INTEGRATION.md §3b; parity with the Metavision SDK's encoder is unpinned, the SDK
     is not a dependency: what is pinned is the sequential model of tests/evt3_encoder_model.py, and that `Evt3Decoder` gives the events
@@ -519,70 +592,11 @@ class Evt3Encoder:
     The state and the staging are allocated by the first un-captured call, never during capture; afterwards nothing is allocated and
     nothing synchronises.  One call is 2 launches whatever S and the sizes are."""
 
-    ENCODE_LAUNCHES = 2
+    _STATE_WORDS, _WS_BYTES, _ENCODE, _ENCODE_DAT = "EVT3_ENC_STATE_WORDS", "sast_evt3enc_ws_bytes", "sast_evt3enc_encode", "sast_evt3enc_encode_dat"
+    _word_dtype = torch.int16
 
-    def __init__(self, num_streams: int, max_words: Optional[int] = None):
-        self.num_streams = F.stream_count(num_streams, "events")
-        if max_words is not None and int(max_words) < 1:
-            raise ValueError("sast_amd.events: max_words must be >= 1 (or None)")
-        self.max_words = None if max_words is None else int(max_words)
-        if self.max_words is not None and self.num_streams * self.max_words > 2 ** 31 - 1:
-            raise ValueError("sast_amd.events: num_streams * max_words must be below 2^31")
-        self.state = self.err = self.n_words = self.words = self._ws = None
-
-    def _buffers(self, dev, chunk_events: int):
-        S = self.num_streams
-        if self.state is None:
-            F.not_capturing("events")
-            self.state = torch.zeros(S, L.EVT3_ENC_STATE_WORDS, dtype=torch.int64, device=dev)
-            self.err = torch.zeros(4, dtype=torch.int32, device=dev)
-            self.n_words = torch.zeros(S, dtype=torch.int64, device=dev)
-            self._ws = torch.zeros(int(L.lib().sast_evt3enc_ws_bytes(S)), dtype=torch.uint8, device=dev)
-        F.lives_on("the encoder's state", self.state.device, "the call's tensors", dev, "events")
-        need = self.max_words if self.max_words is not None else 5 * chunk_events + 1024
-        if self.words is None or self.words.shape[1] < need:
-            F.not_capturing("events")
-            if S * need > 2 ** 31 - 1:
-                raise ValueError("sast_amd.events: num_streams * max_words must be below 2^31")
-            self.words = torch.zeros(S, need, dtype=torch.int16, device=dev)
-
-    def errors(self) -> Tuple[int, int, int, int]:
-        """(times raised to the running maximum, events with x, y or p clamped, rows refused for lack of room, 0) since the last
-        reset() (synchronises)"""
-        return F.counters(self.err, 4)
-
-    def reset(self, streams=None):
-        """new recordings, from the host: the encoder state of `streams` (default: all of them) back to zero; with streams=None the
-        counters are cleared as well"""
-        F.reset_rows((self.state,), self.err, streams, self.num_streams, "events")
-
-    def _encode(self, call, what, chunk_events, counts, reset, tensors):
-        S = self.num_streams
-        F.counts_reset(counts, reset, S, "events")
-        if S * chunk_events > 2 ** 31 - 1:
-            raise ValueError("sast_amd.events: num_streams * chunk events must be below 2^31")
-        _need_gpu(*tensors, counts, reset)
-        F.same_device("events", "the chunk, counts and reset", *tensors, counts, reset)
-        self._buffers(counts.device, chunk_events)
-        L.check(call(counts.data_ptr(), chunk_events, S, None if reset is None else reset.data_ptr(), self.state.data_ptr(),
-                     self._ws.data_ptr(), self.words.data_ptr(), self.words.shape[1], self.n_words.data_ptr(), self.err.data_ptr(),
-                     _stream()), what)
-        return self.words, self.n_words
-
-    def __call__(self, x: torch.Tensor, y: torch.Tensor, p: torch.Tensor, t: torch.Tensor, counts: torch.Tensor,
-                 reset: Optional[torch.Tensor] = None):
-        codes = F.event_columns(x, y, p, t, self.num_streams, "events", cap_name="chunk events")
-        # an empty chunk has no storage: any valid device pointer will do, the kernels read no event
-        ptrs = [c.data_ptr() or counts.data_ptr() for c in (x, y, p, t)]
-        return self._encode(lambda *rest: L.lib().sast_evt3enc_encode(*ptrs, *codes, *rest), "evt3_encode", x.shape[1], counts, reset,
-                            [x, y, p, t])
-
-    def encode_dat(self, records: torch.Tensor, counts: torch.Tensor, reset: Optional[torch.Tensor] = None):
-        F.tensor_arg(records, "records", "events", (torch.int32,), (("num_streams", self.num_streams), "chunk events", 2),
-                     "(two words per Event2D record)", empty_ok=True, dtype_error=TypeError)
-        ptr = records.data_ptr() or counts.data_ptr()
-        return self._encode(lambda *rest: L.lib().sast_evt3enc_encode_dat(ptr, *rest), "evt3_encode_dat", records.shape[1], counts, reset,
-                            [records])
+    def _room(self, chunk_events: int) -> int:
+        return 5 * chunk_events + 1024
 
 
 def evt3_raw_header(height: int, width: int) -> bytes:
@@ -689,6 +703,60 @@ class Evt2Decoder:
                                          self.x.data_ptr(), self.y.data_ptr(), self.p.data_ptr(), self.t.data_ptr(), self.x.shape[1],
                                          self.counts.data_ptr(), self.err.data_ptr(), _stream()), "evt2_decode")
         return self.x, self.y, self.p, self.t, self.counts
+
+
+class Evt2Encoder(_EventEncoder):
+    """Event columns or packed Event2D records -> Prophesee EVT 2.0 / EVT 2.1 sensor words on the device (csrc/k_evt2_enc.hip; the word
+    tables and the canonical rule are in include/sast_hip.h and INTEGRATION.md §3b; parity with the Metavision SDK's encoder is
+    unpinned, the SDK is not a dependency: what is pinned is the sequential model of tests/evt2_encoder_model.py, and that
+    `Evt2Decoder` gives the events back).
+
+    enc = Evt2Encoder(num_streams, max_words=None, version="2.0")
+    words, n_words = enc(x, y, p, t, counts, reset=None)
+      x, y, p: int64 / int32 / int16 [S, chunk_events], t: int64 / int32 (microseconds), the columns `EventQueue.push` takes; counts:
+        int64 [S], the events at the head of each row; reset: uint8 / bool [S], non-zero for the rows whose encoder state is zeroed
+        before this chunk: a new recording.
+      -> words [S, max_words], int32 for version "2.0" (one word per event) and int64 for "2.1" (one word per group of up to 32 events
+        of one time, row and polarity inside 32 aligned columns): what `Evt2Decoder` and `push_evt2` take; n_words int64 [S] the words
+        at the head of each row.  The tensors are the encoder's staging: the next call overwrites them.
+    words, n_words = enc.encode_dat(records, counts, reset=None)
+      records: int32 [S, chunk_events, 2], Prophesee's packed Event2D records as `EventQueue.push_dat` takes them: DAT -> EVT 2.x.
+    Nothing is dropped: a time below the row's running maximum is raised to it, x and y are clamped to 0 .. 2047, p becomes p != 0,
+    and each such event is counted.  The state after a chunk (have, t_last) is the state before the next one, per row: the words of
+    the chunks of a recording, one after the other, decode to its events wherever it was cut (the words of "2.1" depend on the cuts: a
+    cut ends a group).  A fresh decoder starts its wrap count at 0, so it returns t - ((t0 >> 34) << 34) with t0 the row's first
+    event: inherent to the format's 34-bit clock.
+    max_words: the words one row's chunk may give.  The default, 2 * chunk_events + 16, covers the 2 words an event can need and the
+    TIME_HIGH keep-alives (one per 2^32 us) of about 19 hours of silence per chunk; a longer gap needs an explicit max_words.  A row
+    that does not fit is refused whole: n_words 0, its state as it was, and `errors()` reports it.
+    `errors()`, `reset(streams=None)` and the counters are `Evt3Encoder`'s.  `state` is int64 [S, 4]: have, t_last, 0, 0.
+    The state and the staging are allocated by the first un-captured call, never during capture; afterwards nothing is allocated and
+    nothing synchronises.  There is no CPU fallback.  One call is 2 launches whatever S and the sizes are."""
+
+    _STATE_WORDS, _WS_BYTES, _ENCODE, _ENCODE_DAT = "EVT2_ENC_STATE_WORDS", "sast_evt2enc_ws_bytes", "sast_evt2enc_encode", "sast_evt2enc_encode_dat"
+
+    def __init__(self, num_streams: int, max_words: Optional[int] = None, version: str = "2.0"):
+        self.version = _evt2_version(version)
+        self._EXTRA = (_EVT2_VERSIONS[self.version][0],)
+        self._word_dtype = torch.int32 if self.version == "2.0" else torch.int64
+        super().__init__(num_streams, max_words)
+
+    def _room(self, chunk_events: int) -> int:
+        return 2 * chunk_events + 16
+
+
+def evt2_raw_header(height: int, width: int, version: str = "2.0") -> bytes:
+    """The ASCII header of a Prophesee .raw file of EVT 2.0 / EVT 2.1 words for a sensor of `height` x `width` pixels.  Host only.  The
+    bytes, followed by the little-endian bytes of `words[s, :n_words[s]]` of `Evt2Encoder` chunk after chunk, are a .raw file;
+    `raw_header` reads them back as format "evt2" / "evt21", that geometry and the offset of the first word.  The lines are this
+    project's choice of the fields such files carry (parity with the Metavision SDK's writer is unpinned)."""
+    version = _evt2_version(version)
+    height, width = int(height), int(width)
+    if not (1 <= height <= 2048 and 1 <= width <= 2048):
+        raise ValueError("sast_amd.events: an EVT 2 sensor has 1 .. 2048 rows and columns")
+    name = "EVT2" if version == "2.0" else "EVT21"
+    return (f"% evt {version}\n% format {name};height={height};width={width}\n% geometry {width}x{height}\n"
+            f"% generator sast_amd.events.Evt2Encoder\n% end\n").encode("ascii")
 
 
 class RawHeader(NamedTuple):

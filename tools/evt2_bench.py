@@ -13,6 +13,12 @@ replayed from a graph captured on the same tensors, after a warm-up session.  Th
 (max_events), as a host that knows its sensor's rate would set it.  Before anything is timed the queues are checked to hold the same
 events.
 
+The "encode 2.0" / "encode 2.1" rows are the way back, in the same job: `Evt2Encoder` (csrc/k_evt2_enc.hip) on the column chunks of the
+push row, one call per chunk, `words` the words it gives per row and chunk (its canonical rule aligns an EVT 2.1 base to 32 columns, so
+it gives more words than the stream above, whose base is the run's first column); before it is timed `Evt2Decoder` is checked to give
+the columns back from its words.  The "copy" row is a device copy of the same four column tensors, for scale.  The decode rows keep
+their host-built words, so they stay comparable with earlier records.
+
   python tools/evt2_bench.py [--streams 1,8] [--chunks 4] [--events 125000] [--rounds 5] [--out FILE]
 """
 from __future__ import annotations
@@ -28,7 +34,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
-from evt3_bench import H, W, WINDOW_US, synthetic_chunk  # noqa: E402
+from evt3_bench import H, W, WINDOW_US, cell, encode_rows, synthetic_chunk  # noqa: E402
 
 TIME_HIGH = 0x8
 FORMS = ("push", "push_dat", "push_evt3", "push_evt2 2.0", "push_evt2 2.1")
@@ -82,7 +88,7 @@ def main():
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     from sast_amd import _lib
-    from sast_amd.events import EventQueue
+    from sast_amd.events import EventQueue, Evt2Decoder, Evt2Encoder
     if not torch.cuda.is_available():
         raise SystemExit("tools/evt2_bench.py needs a GPU: nothing is measured without one")
     dev = torch.device("cuda")
@@ -95,6 +101,8 @@ def main():
              "# push: int16 x / y / p + int32 t columns;  push_dat: packed Event2D records;  push_evt3 / push_evt2 2.0 / push_evt2 2.1: the raw "
              "16- / 32- / 64-bit words, decoded on the device;  B/ev: bytes in per event, counted from the streams;  launches: library kernel "
              "launches per push",
+             "# encode 2.0 / encode 2.1: Evt2Encoder on the columns of the push row, ms per call, `words` the words it gives per row and chunk;  "
+             "copy: a device copy of the same four column tensors, for scale (no library launch)",
              f"{'S':>3}{'form':>15}{'ev/chunk':>10}{'words':>9}{'B/ev':>7}  {'eager ms':<26}{'replayed ms':<26}{'launches':>9}"]
     kw = dict(height=H, width=W, bins=10, count_cutoff=10, duration_us=WINDOW_US, downsample_by_2=True)
     word_np = {"push_evt3": np.uint16, "push_evt2 2.0": np.uint32, "push_evt2 2.1": np.uint64}
@@ -186,11 +194,16 @@ def main():
                     assert torch.equal(q.count, ref.count), (form, mode)     # the session stored what the checked one stored
                 res[mode] = res[mode][1:]
 
-            def cell(v):
-                return f"{statistics.median(v):.3f} ({min(v):.3f} .. {max(v):.3f})"
-
             lines.append(f"{S:>3}{form:>15}{n_events:>10.0f}{n_words.get(form, 0):>9.0f}{bytes_in[form]:>7.2f}  "
                          f"{cell(res['eager']):<26}{cell(res['replayed']):<26}{launches:>9}")
+            print(lines[-1], flush=True)
+        extra = []
+        for version in ("2.0", "2.1"):
+            coders = Evt2Encoder(S, version=version), Evt2Decoder(S, max_events=ev_cap, version=version)
+            extra = [r for r in extra if r[0] != "copy"] + encode_rows(S, chunks["push"], a.rounds, lib, coders, f"encode {version}")
+        for form, words, eager, replayed, launches in extra:
+            b_ev = f"{bytes_in['push']:>7.2f}"
+            lines.append(f"{S:>3}{form:>15}{n_events:>10.0f}{words:>9.0f}{b_ev}  {cell(eager):<26}{cell(replayed):<26}{launches:>9}")
             print(lines[-1], flush=True)
         del queues, chunks
         torch.cuda.empty_cache()

@@ -63,13 +63,14 @@ def cell(v):
     return f"{statistics.median(v):.3f} ({min(v):.3f} .. {max(v):.3f})"
 
 
-def encode_rows(S, chunks, rounds, lib):
+def encode_rows(S, chunks, rounds, lib, coders=None, form="encode"):
     """the "encode" row: `Evt3Encoder` on the column chunks of the push rows (the events the stream was synthesised with), and the "copy"
     row: a device copy of the same input bytes, for scale -> (form, words per row and chunk, eager ms, replayed ms, launches) each.
     The sessions are the push rows': the encoder's state is reset, then the chunks are encoded one after the other.  Before anything
-    is timed `Evt3Decoder` is checked to give the columns back from the encoder's words."""
+    is timed `Evt3Decoder` is checked to give the columns back from the encoder's words.  coders: another (encoder, decoder) pair with
+    the same calls (tools/evt2_bench.py: `Evt2Encoder` and `Evt2Decoder`), its row named `form`."""
     from sast_amd.events import Evt3Decoder, Evt3Encoder
-    enc, dec = Evt3Encoder(S), Evt3Decoder(S, max_events=chunks[0][0][0].shape[1])
+    enc, dec = coders or (Evt3Encoder(S), Evt3Decoder(S, max_events=chunks[0][0][0].shape[1]))
     words_out = []
     for cols, n in chunks:
         words, n_words = enc(*cols, n)
@@ -88,7 +89,7 @@ def encode_rows(S, chunks, rounds, lib):
             d.copy_(s)
 
     rows = []
-    for form, call in (("encode", lambda: enc(*static, static_n)), ("copy", copy)):
+    for form, call in ((form, lambda: enc(*static, static_n)), ("copy", copy)):
         enc.reset()
         before = lib.sast_launch_count()
         call()
@@ -121,7 +122,7 @@ def encode_rows(S, chunks, rounds, lib):
                 res[mode].append(statistics.median(u.elapsed_time(v) for u, v in marks))
                 assert enc.errors() == (0, 0, 0, 0) and float(enc.n_words.sum()) / S == words_out[-1], form
             res[mode] = res[mode][1:]
-        rows.append((form, statistics.mean(words_out) if form == "encode" else 0, res["eager"], res["replayed"], launches))
+        rows.append((form, statistics.mean(words_out) if form != "copy" else 0, res["eager"], res["replayed"], launches))
     return rows
 
 
