@@ -4,8 +4,10 @@
 //
 // * fp32 in, fp32 out, fp32-accurate products -- required because the block output feeds the next stage's index-exact
 //   token selection.  Default (SAST_MFMA_SPLIT3=1): every operand is split exactly into three bf16 terms and a
-//   product is six v_mfma_f32_32x32x16_bf16 with fp32 accumulation (error <= 2^-23 |x||y| per product, one fp32 rounding; 2.7x
-//   the MFMA rate of the f32-input instruction); -DSAST_MFMA_SPLIT3=0 selects v_mfma_f32_32x32x2_f32 (bit-identical to an fmaf chain).
+//   product is six v_mfma_f32_32x32x16_bf16 with fp32 accumulation (per product: the three dropped terms are below 2^-21 |x||y|,
+//   about four fp32 roundings of the product in the worst case and about 0.3 * 2^-23 in the median; with the adds, at most
+//   1.5 * 2^-21 |x||y|, held by tests/test_gemm_exact.py on the `prod` operands of tests/gemm_cases.py; 2.7x the MFMA rate of the
+//   f32-input instruction); -DSAST_MFMA_SPLIT3=0 selects v_mfma_f32_32x32x2_f32 (bit-identical to an fmaf chain).
 // * operands come through LOADER functors, so the same kernel serves linear layers,
 //   implicit-GEMM convolutions (im2col / backward-data gathers on NHWC), row gathers
 //   of the compacted token list, dual-source rows ([x|h] of the ConvLSTM) and the
@@ -619,8 +621,10 @@ __device__ __forceinline__ void gemm_body(const LA& la, const LB& lb, const EP& 
     } else if constexpr (SAST_MFMA_SPLIT3 && HK == 8) {
       // fp32 x fp32 on the bf16 matrix pipe: every operand is split EXACTLY into three bf16 terms, x = h + m + l (8 + 8 + 8
       // significand bits by truncation; the residuals x - h and x - h - m are exact in fp32), and the product is evaluated as the six
-      // terms hh + hm + mh + mm + hl + lh with fp32 accumulation; the dropped terms ml + lm + ll are <= 2^-23 |x||y|, the size of one
-      // fp32 rounding of the product.  A lane's 8 k-values of a k-tile are exactly one v_mfma_f32_32x32x16_bf16 operand (k = 8 *
+      // terms hh + hm + mh + mm + hl + lh with fp32 accumulation; the dropped terms ml + lm + ll are below 2^-21 |x||y| (|m| < 2^-7 |h|,
+      // |l| < 2^-15 |h|: ml and lm just under 2^-22 each), about four fp32 roundings of the product -- about 0.3 * 2^-23 in the median
+      // over random significands, 3.7 * 2^-23 at worst in 2M of them; with the adds a product is within 1.5 * 2^-21 |x||y|
+      // (tests/test_gemm_exact.py, the `prod` family of tests/gemm_cases.py).  A lane's 8 k-values of a k-tile are exactly one v_mfma_f32_32x32x16_bf16 operand (k = 8 *
       // (lane / 32) + j), so the loaders, the LDS layouts and the operand reads are those of the fp32 path; 6 MFMAs of 32 cycles
       // replace 8 of 64 per 32 x 32 x 16 tile step, at the price of ~90 VALU operations per lane for the split.
       if constexpr (!PSA) {

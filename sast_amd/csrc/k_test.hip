@@ -27,6 +27,7 @@ __device__ unsigned long long sast_tlf_buf[8 * 8192];
   } while (0)
 #endif
 #include "gemm.cuh"
+#include "gemm_dispatch.cuh"
 #include "kernels.h"
 using namespace sast;
 #ifdef SAST_TLF_ENABLE
@@ -57,9 +58,10 @@ struct EpAtomicNT {  // c += v (grid-level split of the reduction of a plain GEM
   __device__ __forceinline__ void post(int m, int j, const float (&v)[1], const Col&, const Aux&) const { atomicAdd(c + (size_t)m * ldc + j, v[0]); }
 };
 
-extern "C" int sast_test_gemm_nt(const float* a, const float* w, const float* bias, float* c, int M, int N, int K, int tile,
-                                 sast_stream_t stream) {
-  hipStream_t st = (hipStream_t)stream;
+// dM (optional): the device-side row count of gemm.cuh; the grid-split kinds (tile >= 600) have none
+static int test_gemm_nt(const float* a, const float* w, const float* bias, float* c, int M, int N, int K, int tile, const int* dM,
+                        hipStream_t st) {
+  if (dM && tile >= 600) return SAST_EINVAL;
   const LdRows la{a, K, nullptr};
   const LdWeightNT lb{w, K, 0};
   const EpStoreT ep(c, N, bias);
@@ -80,52 +82,60 @@ extern "C" int sast_test_gemm_nt(const float* a, const float* w, const float* bi
     }
   }
   switch (tile) {
-    case 0: return launch_gemm<TileSmall>(la, lb, ep, M, N, K, nullptr, nullptr, st);
-    case 1: return launch_gemm<TileMid>(la, lb, ep, M, N, K, nullptr, nullptr, st);
-    case 2: return launch_gemm<TileBig>(la, lb, ep, M, N, K, nullptr, nullptr, st);
-    case 3: return launch_gemm<TileN64>(la, lb, ep, M, N, K, nullptr, nullptr, st);
-    case 4: return launch_gemm<Tile<64, 64, 2, 2, 1, 32>>(la, lb, ep, M, N, K, nullptr, nullptr, st);
-    case 5: return launch_gemm<Tile<64, 128, 2, 2, 1, 32>>(la, lb, ep, M, N, K, nullptr, nullptr, st);
-    case 6: return launch_gemm<Tile<128, 128, 2, 2, 1, 32>>(la, lb, ep, M, N, K, nullptr, nullptr, st);
-    case 7: return launch_gemm<Tile<128, 64, 2, 2, 1, 32>>(la, lb, ep, M, N, K, nullptr, nullptr, st);
-    case 8: return launch_gemm<Tile<128, 64, 2, 2, 1, 16>>(la, lb, ep, M, N, K, nullptr, nullptr, st);
-    case 9: return launch_gemm<TileTiny>(la, lb, ep, M, N, K, nullptr, nullptr, st);
-    case 10: return launch_gemm<Tile<32, 64, 1, 2, 1, 16>>(la, lb, ep, M, N, K, nullptr, nullptr, st);
-    case 11: return launch_gemm<Tile<64, 32, 2, 1, 1, 16>>(la, lb, ep, M, N, K, nullptr, nullptr, st);
-    case 13: return launch_gemm<TileSmallK2>(la, lb, ep, M, N, K, nullptr, nullptr, st);
-    case 14: return launch_gemm<TileSmallK4>(la, lb, ep, M, N, K, nullptr, nullptr, st);
-    case 15: return launch_gemm<Tile<64, 64, 2, 2, 1, 32, 2>>(la, lb, ep, M, N, K, nullptr, nullptr, st);
-    case 16: return launch_gemm<Tile<64, 64, 2, 2, 1, 32, 4>>(la, lb, ep, M, N, K, nullptr, nullptr, st);
-    case 17: return launch_gemm<Tile<32, 32, 1, 1, 1, 16, 4>>(la, lb, ep, M, N, K, nullptr, nullptr, st);
-    case 18: return launch_gemm<Tile<32, 32, 1, 1, 1, 16, 8>>(la, lb, ep, M, N, K, nullptr, nullptr, st);
-    case 19: return launch_gemm<Tile<32, 64, 1, 2, 1, 16, 4>>(la, lb, ep, M, N, K, nullptr, nullptr, st);
-    case 12: return launch_gemm<Tile<32, 32, 1, 1, 1, 32>>(la, lb, ep, M, N, K, nullptr, nullptr, st);
+    case 0: return launch_gemm<TileSmall>(la, lb, ep, M, N, K, dM, nullptr, st);
+    case 1: return launch_gemm<TileMid>(la, lb, ep, M, N, K, dM, nullptr, st);
+    case 2: return launch_gemm<TileBig>(la, lb, ep, M, N, K, dM, nullptr, st);
+    case 3: return launch_gemm<TileN64>(la, lb, ep, M, N, K, dM, nullptr, st);
+    case 4: return launch_gemm<Tile<64, 64, 2, 2, 1, 32>>(la, lb, ep, M, N, K, dM, nullptr, st);
+    case 5: return launch_gemm<Tile<64, 128, 2, 2, 1, 32>>(la, lb, ep, M, N, K, dM, nullptr, st);
+    case 6: return launch_gemm<Tile<128, 128, 2, 2, 1, 32>>(la, lb, ep, M, N, K, dM, nullptr, st);
+    case 7: return launch_gemm<Tile<128, 64, 2, 2, 1, 32>>(la, lb, ep, M, N, K, dM, nullptr, st);
+    case 8: return launch_gemm<Tile<128, 64, 2, 2, 1, 16>>(la, lb, ep, M, N, K, dM, nullptr, st);
+    case 9: return launch_gemm<TileTiny>(la, lb, ep, M, N, K, dM, nullptr, st);
+    case 10: return launch_gemm<Tile<32, 64, 1, 2, 1, 16>>(la, lb, ep, M, N, K, dM, nullptr, st);
+    case 11: return launch_gemm<Tile<64, 32, 2, 1, 1, 16>>(la, lb, ep, M, N, K, dM, nullptr, st);
+    case 13: return launch_gemm<TileSmallK2>(la, lb, ep, M, N, K, dM, nullptr, st);
+    case 14: return launch_gemm<TileSmallK4>(la, lb, ep, M, N, K, dM, nullptr, st);
+    case 15: return launch_gemm<Tile<64, 64, 2, 2, 1, 32, 2>>(la, lb, ep, M, N, K, dM, nullptr, st);
+    case 16: return launch_gemm<Tile<64, 64, 2, 2, 1, 32, 4>>(la, lb, ep, M, N, K, dM, nullptr, st);
+    case 17: return launch_gemm<Tile<32, 32, 1, 1, 1, 16, 4>>(la, lb, ep, M, N, K, dM, nullptr, st);
+    case 18: return launch_gemm<Tile<32, 32, 1, 1, 1, 16, 8>>(la, lb, ep, M, N, K, dM, nullptr, st);
+    case 19: return launch_gemm<Tile<32, 64, 1, 2, 1, 16, 4>>(la, lb, ep, M, N, K, dM, nullptr, st);
+    case 12: return launch_gemm<Tile<32, 32, 1, 1, 1, 32>>(la, lb, ep, M, N, K, dM, nullptr, st);
     // deeper register prefetch for the small grids (<= one workgroup per CU: occupancy is not what the registers cost there)
-    case 50: return launch_gemm<Tile<32, 64, 1, 2, 1, 16, 4, 4>>(la, lb, ep, M, N, K, nullptr, nullptr, st);
-    case 51: return launch_gemm<Tile<32, 64, 1, 2, 1, 16, 4, 6>>(la, lb, ep, M, N, K, nullptr, nullptr, st);
-    case 52: return launch_gemm<Tile<32, 64, 1, 2, 1, 16, 4, 8>>(la, lb, ep, M, N, K, nullptr, nullptr, st);
-    case 53: return launch_gemm<Tile<32, 32, 1, 1, 1, 16, 8, 4>>(la, lb, ep, M, N, K, nullptr, nullptr, st);
-    case 54: return launch_gemm<Tile<32, 32, 1, 1, 1, 16, 8, 6>>(la, lb, ep, M, N, K, nullptr, nullptr, st);
-    case 55: return launch_gemm<Tile<64, 64, 2, 2, 1, 16, 2, 4>>(la, lb, ep, M, N, K, nullptr, nullptr, st);
-    case 56: return launch_gemm<Tile<64, 64, 2, 2, 1, 16, 2, 6>>(la, lb, ep, M, N, K, nullptr, nullptr, st);
-    case 57: return launch_gemm<Tile<64, 64, 2, 2, 1, 16, 1, 4>>(la, lb, ep, M, N, K, nullptr, nullptr, st);
-    case 58: return launch_gemm<Tile<64, 64, 2, 2, 1, 16, 4, 4>>(la, lb, ep, M, N, K, nullptr, nullptr, st);
+    case 50: return launch_gemm<Tile<32, 64, 1, 2, 1, 16, 4, 4>>(la, lb, ep, M, N, K, dM, nullptr, st);
+    case 51: return launch_gemm<Tile<32, 64, 1, 2, 1, 16, 4, 6>>(la, lb, ep, M, N, K, dM, nullptr, st);
+    case 52: return launch_gemm<Tile<32, 64, 1, 2, 1, 16, 4, 8>>(la, lb, ep, M, N, K, dM, nullptr, st);
+    case 53: return launch_gemm<Tile<32, 32, 1, 1, 1, 16, 8, 4>>(la, lb, ep, M, N, K, dM, nullptr, st);
+    case 54: return launch_gemm<Tile<32, 32, 1, 1, 1, 16, 8, 6>>(la, lb, ep, M, N, K, dM, nullptr, st);
+    case 55: return launch_gemm<Tile<64, 64, 2, 2, 1, 16, 2, 4>>(la, lb, ep, M, N, K, dM, nullptr, st);
+    case 56: return launch_gemm<Tile<64, 64, 2, 2, 1, 16, 2, 6>>(la, lb, ep, M, N, K, dM, nullptr, st);
+    case 57: return launch_gemm<Tile<64, 64, 2, 2, 1, 16, 1, 4>>(la, lb, ep, M, N, K, dM, nullptr, st);
+    case 58: return launch_gemm<Tile<64, 64, 2, 2, 1, 16, 4, 4>>(la, lb, ep, M, N, K, dM, nullptr, st);
     // 32-wide k-tiles on presplit operands (two k16 steps per phase)
-    case 40: return launch_gemm<Tile<64, 64, 2, 2, 1, 32, 1>>(la, lb, ep, M, N, K, nullptr, nullptr, st);
-    case 41: return launch_gemm<Tile<64, 64, 2, 2, 1, 32, 2>>(la, lb, ep, M, N, K, nullptr, nullptr, st);
-    case 42: return launch_gemm<Tile<32, 64, 1, 2, 1, 32, 2>>(la, lb, ep, M, N, K, nullptr, nullptr, st);
-    case 43: return launch_gemm<Tile<32, 64, 1, 2, 1, 32, 4>>(la, lb, ep, M, N, K, nullptr, nullptr, st);
-    case 44: return launch_gemm<Tile<64, 128, 2, 2, 1, 32, 1>>(la, lb, ep, M, N, K, nullptr, nullptr, st);
+    case 40: return launch_gemm<Tile<64, 64, 2, 2, 1, 32, 1>>(la, lb, ep, M, N, K, dM, nullptr, st);
+    case 41: return launch_gemm<Tile<64, 64, 2, 2, 1, 32, 2>>(la, lb, ep, M, N, K, dM, nullptr, st);
+    case 42: return launch_gemm<Tile<32, 64, 1, 2, 1, 32, 2>>(la, lb, ep, M, N, K, dM, nullptr, st);
+    case 43: return launch_gemm<Tile<32, 64, 1, 2, 1, 32, 4>>(la, lb, ep, M, N, K, dM, nullptr, st);
+    case 44: return launch_gemm<Tile<64, 128, 2, 2, 1, 32, 1>>(la, lb, ep, M, N, K, dM, nullptr, st);
     // wave-private tiles: one wave per k-group, no barrier in the k-loop
-    case 30: return launch_gemm<Tile<64, 64, 1, 1, 1, 16, 1>>(la, lb, ep, M, N, K, nullptr, nullptr, st);
-    case 31: return launch_gemm<Tile<64, 64, 1, 1, 1, 16, 2>>(la, lb, ep, M, N, K, nullptr, nullptr, st);
-    case 32: return launch_gemm<Tile<64, 64, 1, 1, 1, 16, 4>>(la, lb, ep, M, N, K, nullptr, nullptr, st);
-    case 33: return launch_gemm<Tile<32, 64, 1, 1, 1, 16, 1>>(la, lb, ep, M, N, K, nullptr, nullptr, st);
-    case 34: return launch_gemm<Tile<32, 64, 1, 1, 1, 16, 2>>(la, lb, ep, M, N, K, nullptr, nullptr, st);
-    case 35: return launch_gemm<Tile<32, 64, 1, 1, 1, 16, 4>>(la, lb, ep, M, N, K, nullptr, nullptr, st);
-    case 36: return launch_gemm<Tile<32, 32, 1, 1, 1, 16, 2>>(la, lb, ep, M, N, K, nullptr, nullptr, st);
+    case 30: return launch_gemm<Tile<64, 64, 1, 1, 1, 16, 1>>(la, lb, ep, M, N, K, dM, nullptr, st);
+    case 31: return launch_gemm<Tile<64, 64, 1, 1, 1, 16, 2>>(la, lb, ep, M, N, K, dM, nullptr, st);
+    case 32: return launch_gemm<Tile<64, 64, 1, 1, 1, 16, 4>>(la, lb, ep, M, N, K, dM, nullptr, st);
+    case 33: return launch_gemm<Tile<32, 64, 1, 1, 1, 16, 1>>(la, lb, ep, M, N, K, dM, nullptr, st);
+    case 34: return launch_gemm<Tile<32, 64, 1, 1, 1, 16, 2>>(la, lb, ep, M, N, K, dM, nullptr, st);
+    case 35: return launch_gemm<Tile<32, 64, 1, 1, 1, 16, 4>>(la, lb, ep, M, N, K, dM, nullptr, st);
+    case 36: return launch_gemm<Tile<32, 32, 1, 1, 1, 16, 2>>(la, lb, ep, M, N, K, dM, nullptr, st);
     default: return SAST_EINVAL;
   }
+}
+extern "C" int sast_test_gemm_nt(const float* a, const float* w, const float* bias, float* c, int M, int N, int K, int tile,
+                                 sast_stream_t stream) {
+  return test_gemm_nt(a, w, bias, c, M, N, K, tile, nullptr, (hipStream_t)stream);
+}
+extern "C" int sast_test_gemm_nt_dev(const float* a, const float* w, const float* bias, float* c, int M, int N, int K, int tile,
+                                     const int* dM, sast_stream_t stream) {
+  return test_gemm_nt(a, w, bias, c, M, N, K, tile, dM, (hipStream_t)stream);
 }
 
 struct EpNull {  // discards the result (measures the kernel without the atomic epilogue)
@@ -162,58 +172,109 @@ struct LdNullT {
   SAST_DEFAULT_FINISH
 };
 
-extern "C" int sast_test_gemm_tn(const float* dy, const float* x, float* out, float* colsum, int Mo, int NJ, int R, int tile, int splits,
-                                 int null_ep, sast_stream_t stream) {
-  hipStream_t st = (hipStream_t)stream;
+// dR (optional): the device-side length of the reduction
+static int test_gemm_tn(const float* dy, const float* x, float* out, float* colsum, int Mo, int NJ, int R, int tile, int splits,
+                        int null_ep, const int* dR, hipStream_t st) {
   const LdRowsT la{dy, Mo};
   const LdRowsT lb{x, NJ};
   if (null_ep) {
     const EpNull ep{out};
     switch (tile) {
-      case 0: return launch_gemm_split<TileSmall>(la, lb, ep, Mo, NJ, R, nullptr, splits, colsum, st);
-      case 1: return launch_gemm_split<TileSmallK2>(la, lb, ep, Mo, NJ, R, nullptr, splits, colsum, st);
-      case 2: return launch_gemm_split<TileSmallK4>(la, lb, ep, Mo, NJ, R, nullptr, splits, colsum, st);
+      case 0: return launch_gemm_split<TileSmall>(la, lb, ep, Mo, NJ, R, dR, splits, colsum, st);
+      case 1: return launch_gemm_split<TileSmallK2>(la, lb, ep, Mo, NJ, R, dR, splits, colsum, st);
+      case 2: return launch_gemm_split<TileSmallK4>(la, lb, ep, Mo, NJ, R, dR, splits, colsum, st);
     }
   }
   const EpAtomicT ep{out, NJ};
-  if (tile == 50) return launch_gemm_split<Tile<64, 64, 2, 1, 1, 16, 2>>(la, lb, ep, Mo, NJ, R, nullptr, splits, colsum, st);   // wave tile 32x64, 2 k-groups, 4 waves
-  if (tile == 51) return launch_gemm_split<Tile<64, 64, 2, 1, 1, 16, 4>>(la, lb, ep, Mo, NJ, R, nullptr, splits, colsum, st);   // wave tile 32x64, 4 k-groups, 8 waves
-  if (tile == 52) return launch_gemm_split<Tile<64, 64, 1, 2, 1, 16, 4>>(la, lb, ep, Mo, NJ, R, nullptr, splits, colsum, st);   // wave tile 64x32, 4 k-groups
-  if (tile == 53) return launch_gemm_split<Tile<64, 64, 1, 1, 1, 16, 4>>(la, lb, ep, Mo, NJ, R, nullptr, splits, colsum, st);   // wave tile 64x64, 4 k-groups, 4 waves
-  if (tile == 54) return launch_gemm_split<Tile<64, 64, 1, 1, 1, 16, 8>>(la, lb, ep, Mo, NJ, R, nullptr, splits, colsum, st);   // wave tile 64x64, 8 k-groups, 8 waves
-  if (tile == 40) return launch_gemm_split<Tile<64, 64, 2, 2, 1, 32, 2>>(la, lb, ep, Mo, NJ, R, nullptr, splits, colsum, st);   // BK = 32
-  if (tile == 41) return launch_gemm_split<Tile<64, 64, 2, 2, 1, 32, 1>>(la, lb, ep, Mo, NJ, R, nullptr, splits, colsum, st);
-  if (tile == 42) return launch_gemm_split<Tile<64, 64, 2, 2, 1, 64, 1>>(la, lb, ep, Mo, NJ, R, nullptr, splits, colsum, st);   // BK = 64
-  if (tile == 43) return launch_gemm_split<Tile<64, 64, 2, 2, 1, 64, 2>>(la, lb, ep, Mo, NJ, R, nullptr, splits, colsum, st);
-  if (tile == 100) return launch_gemm_split<TileSmallK2>(LdNullT{}, LdNullT{}, ep, Mo, NJ, R, nullptr, splits, colsum, st);   // no global loads
-  if (tile == 101) return launch_gemm_split<TileSmall>(LdNullT{}, LdNullT{}, ep, Mo, NJ, R, nullptr, splits, colsum, st);
-  if (tile == 102) return launch_gemm_split<TileSmallK2>(la, LdNullT{}, ep, Mo, NJ, R, nullptr, splits, colsum, st);          // A only
+  if (tile == 50) return launch_gemm_split<Tile<64, 64, 2, 1, 1, 16, 2>>(la, lb, ep, Mo, NJ, R, dR, splits, colsum, st);   // wave tile 32x64, 2 k-groups, 4 waves
+  if (tile == 51) return launch_gemm_split<Tile<64, 64, 2, 1, 1, 16, 4>>(la, lb, ep, Mo, NJ, R, dR, splits, colsum, st);   // wave tile 32x64, 4 k-groups, 8 waves
+  if (tile == 52) return launch_gemm_split<Tile<64, 64, 1, 2, 1, 16, 4>>(la, lb, ep, Mo, NJ, R, dR, splits, colsum, st);   // wave tile 64x32, 4 k-groups
+  if (tile == 53) return launch_gemm_split<Tile<64, 64, 1, 1, 1, 16, 4>>(la, lb, ep, Mo, NJ, R, dR, splits, colsum, st);   // wave tile 64x64, 4 k-groups, 4 waves
+  if (tile == 54) return launch_gemm_split<Tile<64, 64, 1, 1, 1, 16, 8>>(la, lb, ep, Mo, NJ, R, dR, splits, colsum, st);   // wave tile 64x64, 8 k-groups, 8 waves
+  if (tile == 40) return launch_gemm_split<Tile<64, 64, 2, 2, 1, 32, 2>>(la, lb, ep, Mo, NJ, R, dR, splits, colsum, st);   // BK = 32
+  if (tile == 41) return launch_gemm_split<Tile<64, 64, 2, 2, 1, 32, 1>>(la, lb, ep, Mo, NJ, R, dR, splits, colsum, st);
+  if (tile == 42) return launch_gemm_split<Tile<64, 64, 2, 2, 1, 64, 1>>(la, lb, ep, Mo, NJ, R, dR, splits, colsum, st);   // BK = 64
+  if (tile == 43) return launch_gemm_split<Tile<64, 64, 2, 2, 1, 64, 2>>(la, lb, ep, Mo, NJ, R, dR, splits, colsum, st);
+  if (tile == 100) return launch_gemm_split<TileSmallK2>(LdNullT{}, LdNullT{}, ep, Mo, NJ, R, dR, splits, colsum, st);   // no global loads
+  if (tile == 101) return launch_gemm_split<TileSmall>(LdNullT{}, LdNullT{}, ep, Mo, NJ, R, dR, splits, colsum, st);
+  if (tile == 102) return launch_gemm_split<TileSmallK2>(la, LdNullT{}, ep, Mo, NJ, R, dR, splits, colsum, st);          // A only
   switch (tile) {
-    case 0: return launch_gemm_split<TileSmall>(la, lb, ep, Mo, NJ, R, nullptr, splits, colsum, st);
-    case 1: return launch_gemm_split<TileSmallK2>(la, lb, ep, Mo, NJ, R, nullptr, splits, colsum, st);
-    case 2: return launch_gemm_split<TileSmallK4>(la, lb, ep, Mo, NJ, R, nullptr, splits, colsum, st);
-    case 20: return launch_gemm_split<Tile<64, 64, 2, 2, 1, 16, 2, 4, 2>>(la, lb, ep, Mo, NJ, R, nullptr, splits, colsum, st);
-    case 21: return launch_gemm_split<Tile<64, 64, 2, 2, 1, 16, 2, 4, 3>>(la, lb, ep, Mo, NJ, R, nullptr, splits, colsum, st);
-    case 22: return launch_gemm_split<Tile<64, 64, 2, 2, 1, 16, 2, 6, 2>>(la, lb, ep, Mo, NJ, R, nullptr, splits, colsum, st);
-    case 23: return launch_gemm_split<Tile<64, 64, 2, 2, 1, 16, 2, 8, 1>>(la, lb, ep, Mo, NJ, R, nullptr, splits, colsum, st);
-    case 24: return launch_gemm_split<Tile<64, 64, 2, 2, 1, 16, 1, 4, 4>>(la, lb, ep, Mo, NJ, R, nullptr, splits, colsum, st);
-    case 25: return launch_gemm_split<Tile<64, 64, 2, 2, 1, 16, 1, 8, 3>>(la, lb, ep, Mo, NJ, R, nullptr, splits, colsum, st);
-    case 26: return launch_gemm_split<Tile<64, 64, 2, 2, 1, 16, 4, 4, 1>>(la, lb, ep, Mo, NJ, R, nullptr, splits, colsum, st);
-    case 27: return launch_gemm_split<Tile<64, 64, 2, 2, 1, 16, 2, 2, 4>>(la, lb, ep, Mo, NJ, R, nullptr, splits, colsum, st);
-    case 28: return launch_gemm_split<Tile<64, 64, 2, 2, 1, 16, 1, 2, 8>>(la, lb, ep, Mo, NJ, R, nullptr, splits, colsum, st);
-    case 30: return launch_gemm_split<Tile<128, 64, 2, 2, 1, 16, 1, 2>>(la, lb, ep, Mo, NJ, R, nullptr, splits, colsum, st);
-    case 32: return launch_gemm_split<Tile<64, 128, 2, 2, 1, 16, 1, 2>>(la, lb, ep, Mo, NJ, R, nullptr, splits, colsum, st);
-    case 33: return launch_gemm_split<Tile<128, 128, 2, 2, 1, 16, 1, 2>>(la, lb, ep, Mo, NJ, R, nullptr, splits, colsum, st);
-    case 34: return launch_gemm_split<Tile<192, 64, 2, 2, 1, 16, 1, 2>>(la, lb, ep, Mo, NJ, R, nullptr, splits, colsum, st);
-    case 35: return launch_gemm_split<Tile<128, 64, 4, 1, 1, 16, 1, 2>>(la, lb, ep, Mo, NJ, R, nullptr, splits, colsum, st);
-    case 36: return launch_gemm_split<Tile<128, 64, 4, 2, 1, 16, 1, 2>>(la, lb, ep, Mo, NJ, R, nullptr, splits, colsum, st);
-    case 3: return launch_gemm_split<Tile<128, 128, 2, 2, 1>>(la, lb, ep, Mo, NJ, R, nullptr, splits, colsum, st);
-    case 4: return launch_gemm_split<Tile<192, 64, 2, 2, 1>>(la, lb, ep, Mo, NJ, R, nullptr, splits, colsum, st);
-    case 5: return launch_gemm_split<Tile<320, 64, 2, 2, 1>>(la, lb, ep, Mo, NJ, R, nullptr, splits, colsum, st);
-    case 6: return launch_gemm_split<Tile<64, 192, 2, 2, 1>>(la, lb, ep, Mo, NJ, R, nullptr, splits, colsum, st);
-    case 7: return launch_gemm_split<Tile<192, 128, 2, 2, 1>>(la, lb, ep, Mo, NJ, R, nullptr, splits, colsum, st);
-    case 8: return launch_gemm_split<Tile<128, 64, 2, 2, 1>>(la, lb, ep, Mo, NJ, R, nullptr, splits, colsum, st);
+    case 0: return launch_gemm_split<TileSmall>(la, lb, ep, Mo, NJ, R, dR, splits, colsum, st);
+    case 1: return launch_gemm_split<TileSmallK2>(la, lb, ep, Mo, NJ, R, dR, splits, colsum, st);
+    case 2: return launch_gemm_split<TileSmallK4>(la, lb, ep, Mo, NJ, R, dR, splits, colsum, st);
+    case 20: return launch_gemm_split<Tile<64, 64, 2, 2, 1, 16, 2, 4, 2>>(la, lb, ep, Mo, NJ, R, dR, splits, colsum, st);
+    case 21: return launch_gemm_split<Tile<64, 64, 2, 2, 1, 16, 2, 4, 3>>(la, lb, ep, Mo, NJ, R, dR, splits, colsum, st);
+    case 22: return launch_gemm_split<Tile<64, 64, 2, 2, 1, 16, 2, 6, 2>>(la, lb, ep, Mo, NJ, R, dR, splits, colsum, st);
+    case 23: return launch_gemm_split<Tile<64, 64, 2, 2, 1, 16, 2, 8, 1>>(la, lb, ep, Mo, NJ, R, dR, splits, colsum, st);
+    case 24: return launch_gemm_split<Tile<64, 64, 2, 2, 1, 16, 1, 4, 4>>(la, lb, ep, Mo, NJ, R, dR, splits, colsum, st);
+    case 25: return launch_gemm_split<Tile<64, 64, 2, 2, 1, 16, 1, 8, 3>>(la, lb, ep, Mo, NJ, R, dR, splits, colsum, st);
+    case 26: return launch_gemm_split<Tile<64, 64, 2, 2, 1, 16, 4, 4, 1>>(la, lb, ep, Mo, NJ, R, dR, splits, colsum, st);
+    case 27: return launch_gemm_split<Tile<64, 64, 2, 2, 1, 16, 2, 2, 4>>(la, lb, ep, Mo, NJ, R, dR, splits, colsum, st);
+    case 28: return launch_gemm_split<Tile<64, 64, 2, 2, 1, 16, 1, 2, 8>>(la, lb, ep, Mo, NJ, R, dR, splits, colsum, st);
+    case 30: return launch_gemm_split<Tile<128, 64, 2, 2, 1, 16, 1, 2>>(la, lb, ep, Mo, NJ, R, dR, splits, colsum, st);
+    case 32: return launch_gemm_split<Tile<64, 128, 2, 2, 1, 16, 1, 2>>(la, lb, ep, Mo, NJ, R, dR, splits, colsum, st);
+    case 33: return launch_gemm_split<Tile<128, 128, 2, 2, 1, 16, 1, 2>>(la, lb, ep, Mo, NJ, R, dR, splits, colsum, st);
+    case 34: return launch_gemm_split<Tile<192, 64, 2, 2, 1, 16, 1, 2>>(la, lb, ep, Mo, NJ, R, dR, splits, colsum, st);
+    case 35: return launch_gemm_split<Tile<128, 64, 4, 1, 1, 16, 1, 2>>(la, lb, ep, Mo, NJ, R, dR, splits, colsum, st);
+    case 36: return launch_gemm_split<Tile<128, 64, 4, 2, 1, 16, 1, 2>>(la, lb, ep, Mo, NJ, R, dR, splits, colsum, st);
+    case 3: return launch_gemm_split<Tile<128, 128, 2, 2, 1>>(la, lb, ep, Mo, NJ, R, dR, splits, colsum, st);
+    case 4: return launch_gemm_split<Tile<192, 64, 2, 2, 1>>(la, lb, ep, Mo, NJ, R, dR, splits, colsum, st);
+    case 5: return launch_gemm_split<Tile<320, 64, 2, 2, 1>>(la, lb, ep, Mo, NJ, R, dR, splits, colsum, st);
+    case 6: return launch_gemm_split<Tile<64, 192, 2, 2, 1>>(la, lb, ep, Mo, NJ, R, dR, splits, colsum, st);
+    case 7: return launch_gemm_split<Tile<192, 128, 2, 2, 1>>(la, lb, ep, Mo, NJ, R, dR, splits, colsum, st);
+    case 8: return launch_gemm_split<Tile<128, 64, 2, 2, 1>>(la, lb, ep, Mo, NJ, R, dR, splits, colsum, st);
     default: return SAST_EINVAL;
+  }
+}
+extern "C" int sast_test_gemm_tn(const float* dy, const float* x, float* out, float* colsum, int Mo, int NJ, int R, int tile, int splits,
+                                 int null_ep, sast_stream_t stream) {
+  return test_gemm_tn(dy, x, out, colsum, Mo, NJ, R, tile, splits, null_ep, nullptr, (hipStream_t)stream);
+}
+extern "C" int sast_test_gemm_tn_dev(const float* dy, const float* x, float* out, float* colsum, int Mo, int NJ, int R, int tile, int splits,
+                                     const int* dR, sast_stream_t stream) {
+  return test_gemm_tn(dy, x, out, colsum, Mo, NJ, R, tile, splits, 0, dR, (hipStream_t)stream);
+}
+
+// ---- the host-side dispatch of gemm_dispatch.cuh on its own (tests/test_gemm_exact.py): the knobs pick the tile
+// c[M, N] = a[M, K] w[N, K]^T + bias through gemm_auto, with the product's loaders and epilogue
+extern "C" int sast_test_gemm_auto(const float* a, const float* w, const float* bias, float* c, int M, int N, int K, const int* dM,
+                                   sast_stream_t stream) {
+  return gemm_auto(LdRows{a, K, nullptr}, LdWeightNT{w, K, 0}, EpStore{c, N, bias}, M, N, K, dM, (hipStream_t)stream);
+}
+// the backward of y[R, N] = x[R, K] w[N, K]^T as sast_mswsa_bwd issues it for `proj`: dw[N, K] += dy^T x, db[N] += column sums of dy (both
+// zero on entry) and dx[R, K] = dy w, one paired launch (two with SAST_GEMM_PAIR=0); dcount: the device-side row count of both jobs
+extern "C" int sast_test_gemm_pair(const float* dy, const float* x, const float* w, float* dw, float* db, float* dx, int R, int N, int K,
+                                   const int* dcount, sast_stream_t stream) {
+  return gemm_pair(LdRowsT{dy, N}, LdRowsT{x, K}, dw, K, N, K, R, dcount, db, LdRows{dy, N, nullptr}, LdWeightNN{w, K}, EpStore{dx, K, nullptr},
+                   R, K, N, dcount, (hipStream_t)stream);
+}
+// the group tiles: c[m][g][j] = sum_k a[m][k] w[g * NJ + j][k], the weight [G * NJ, K] with group stride NJ.  tile: 0 TileG2, 1 TileG2K2,
+// 2 TileG2K4, 3 TileG3, 4 TileG3K4, 5 TileG4, 6 TileG4K4 (the ones the product launches); G must be the tile's
+template <int G>
+struct EpGroupsT {  // c[m * G * NJ + g * NJ + j] = v[g]
+  float* c; int NJ;
+  using Col = EpNone; using Aux = EpNone;
+  __device__ __forceinline__ Col col(int) const { return Col{}; }
+  __device__ __forceinline__ Aux pre(int, int) const { return Aux{}; }
+  __device__ __forceinline__ void post(int m, int j, const float (&v)[G], const Col&, const Aux&) const {
+#pragma unroll
+    for (int g = 0; g < G; ++g) c[((size_t)m * G + g) * NJ + j] = v[g];
+  }
+};
+extern "C" int sast_test_gemm_groups(const float* a, const float* w, float* c, int M, int NJ, int K, int G, int tile, const int* dM,
+                                     sast_stream_t stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (tile < 0 || tile > 6 || G != (tile < 3 ? 2 : tile < 5 ? 3 : 4)) return SAST_EINVAL;
+  const LdRows la{a, K, nullptr};
+  const LdWeightNT lb{w, K, NJ};
+  switch (tile) {
+    case 0: return launch_gemm<TileG2>(la, lb, EpGroupsT<2>{c, NJ}, M, NJ, K, dM, nullptr, st);
+    case 1: return launch_gemm<TileG2K2>(la, lb, EpGroupsT<2>{c, NJ}, M, NJ, K, dM, nullptr, st);
+    case 2: return launch_gemm<TileG2K4>(la, lb, EpGroupsT<2>{c, NJ}, M, NJ, K, dM, nullptr, st);
+    case 3: return launch_gemm<TileG3>(la, lb, EpGroupsT<3>{c, NJ}, M, NJ, K, dM, nullptr, st);
+    case 4: return launch_gemm<TileG3K4>(la, lb, EpGroupsT<3>{c, NJ}, M, NJ, K, dM, nullptr, st);
+    case 5: return launch_gemm<TileG4>(la, lb, EpGroupsT<4>{c, NJ}, M, NJ, K, dM, nullptr, st);
+    default: return launch_gemm<TileG4K4>(la, lb, EpGroupsT<4>{c, NJ}, M, NJ, K, dM, nullptr, st);
   }
 }
 

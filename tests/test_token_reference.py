@@ -136,6 +136,13 @@ def test_case_table_covers_what_the_sweep_is_about():
     assert {(c["C"], c["state"]) for c in ls} >= {(C, s) for C in TC.WIDTHS for s in ("given", "none", "zero")}
     assert {c["C"] for c in ls if c["two"]} == {48, 256} == {c["C"] for c in ls if c["drop"]}
     assert [(c["C"], c["state"]) for c in ls if c["sat"]] == [(48, "given"), (256, "given")]
+    # the k-split group tiles through the operators: same inputs and bounds entry as the plain case
+    assert {c["C"] for c in ms if c["env"] == TC.GLU_TILE} == {256, 512}
+    assert {(c["C"], c["state"]) for c in ls if c["env"] == TC.LSTM_TILE} == {(256, "given"), (256, "none")}
+    for c in ms + ls:
+        if c["env"] in (TC.GLU_TILE, TC.LSTM_TILE):
+            plain = TC.BY_ID[c["shares"]]
+            assert not plain["env"] and not plain.get("shares") and all(torch.equal(a, b) for a, b in zip(TC.make_inputs(c).values(), TC.make_inputs(plain).values()))
 
 
 @pytest.mark.parametrize("case", TC.ALL_CASES, ids=[c["id"] for c in TC.ALL_CASES])

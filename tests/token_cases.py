@@ -43,6 +43,9 @@ Families:
               "sat" (state given, C = 48 and 256): w times 8 and c0 times 4, so that the gate pre-activations have a standard deviation
               of about 6 (a tenth of them beyond |z| = 10, where sigmoid_hw and tanh_hw are saturated to the last bit) and tanh_hw(c1)
               runs on |c| up to about 15.
+  "glutile" (mswsa, C = 256 and 512) and "lstmtile" (lstm, C = 256, states "given" and "none") run the plain case under SAST_GLU_TILE=1 /
+  SAST_LSTM_TILE=1: the k-split group tiles TileG2K4, TileG4K4 and TileG3K4 through the operator's own wiring; same arithmetic, so
+  they share the plain case's bounds entry (tests/test_gemm_exact.py runs those tiles on exact operands).
 """
 import math
 
@@ -79,6 +82,10 @@ def dim_head_of(C):
     return 32 if C % 32 == 0 else {48: 24}[C]
 
 
+GLU_TILE = {"SAST_GLU_TILE": "1"}
+LSTM_TILE = {"SAST_LSTM_TILE": "1"}
+
+
 def _mswsa(C, dh=None, sel="mix", tag="", **opt):
     dh = dh or dim_head_of(C)
     c = dict(id=f"mswsa-c{C}-dh{dh}-{sel}" + (f"-{tag}" if tag else ""), op="mswsa", C=C, dh=dh, sel=sel, inner=O.mlp_inner_dim(C), B=2, N=4,
@@ -98,7 +105,9 @@ MSWSA_CASES = (
     + [_mswsa(C, tag="lnblocks1", env={"SAST_LN_BLOCKS": "1"}, shares=f"mswsa-c{C}-dh32-mix") for C in (32, 192, 1024)]
     + [_mswsa(C, tag=tag, **opt) for C in (48, 192)
        for tag, opt in (("nols", dict(ls=False)), ("cb", dict(cb=True)), ("drop", dict(drop=True)), ("prelu", dict(act="prelu")))]
-    + [_mswsa(64, tag="cond", cond=True)])
+    + [_mswsa(64, tag="cond", cond=True)]
+    # the k-split GLU tile of fc1 (csrc/k_block.hip: SAST_GLU_TILE, C >= 256: TileG2K4 at this grid)
+    + [_mswsa(C, tag="glutile", env=dict(GLU_TILE), shares=f"mswsa-c{C}-dh32-mix") for C in (256, 512)])
 
 # the gate activations beside gelu and prelu, and where the derivative of each jumps or its formula changes branch
 ACT_KINKS = {"relu": (0.0,), "silu": (), "sigmoid": (), "tanh": (), "mish": (), "relu6": (0.0, 6.0), "leaky_relu": (0.0,), "elu": (0.0,), "selu": (0.0,),
@@ -159,7 +168,9 @@ def _lstm(C, state, two=False, drop=False, sat=False):
 
 LSTM_CASES = ([_lstm(C, st) for C in WIDTHS for st in ("given", "none", "zero", "h0zero")]
               + [_lstm(C, st, two, drop) for C in (48, 256) for st, two, drop in (("given", True, True), ("none", False, True), ("h0zero", True, False))]
-              + [_lstm(C, "given", sat=True) for C in (48, 256)])
+              + [_lstm(C, "given", sat=True) for C in (48, 256)]
+              # the k-split gate tiles (csrc/k_block.hip: SAST_LSTM_TILE, reduction >= 256): TileG4K4 with a state, TileG3K4 without
+              + [dict(_lstm(256, st), id=f"lstm-c256-{st}-lstmtile", env=dict(LSTM_TILE), shares=f"lstm-c256-{st}") for st in ("given", "none")])
 
 ALL_CASES = SCORE_CASES + MSWSA_CASES + MSWSA_ACT_CASES + PART_CASES + MASK_CASES + ADDPOS_CASES + LSTM_CASES
 BY_ID = {c["id"]: c for c in ALL_CASES}
