@@ -1068,7 +1068,10 @@ int sast_augment_labels(const float* labels, const int32_t* counts, const int32_
  *   tables gt_box fp32 [max_images * max_labels_per_frame][4] (x, y, w, h), gt_cls / gt_img int32; det_box fp32 [max_detections][5]
  *          (x, y, w, h, score), det_cls / det_img int32; img_t int64 [max_images]: image i is the i-th frame that kept a label
  *   records rec_key / rec_match / rec_ign uint64 [max_detections]: bit (area * 10 + threshold) of match / ignore; key = category << 62 |
- *          ~(order-preserving bits of the score) << 30 | record index
+ *          ~(order-preserving bits of the score) << 30 | record index.  rec_ign bits 40..46: the detection's rank (0 .. 99) in its
+ *          (image, category) group after the stable descending sort on the score -- what a cut to maxDets 1 or 10 needs
+ *          (sast_evsum_accumulate); lanes 40..63 set no match or ignore bit, and only bits 0..39 of either word enter a result.
+ *          sast_evmerge_append copies both words whole, so the rank travels with a merged, exported or gathered buffer
  *   precision fp64 [10][101][K][4] (COCOeval.eval['precision'] at maxDets 100), result fp64 [8 + SAST_EVAL_STATE_WORDS]: AP, AP_50, AP_75,
  *          AP_S, AP_M, AP_L, 2 unused, then the state words
  * iou_thr: the 10 doubles of np.linspace(.5, .95, 10); rec_thr: the 101 of np.linspace(0, 1, 101).  A <= 8192, max_labels_per_frame <= 128,
@@ -1118,6 +1121,40 @@ int sast_eval_add(const SastEvalArgs* a, sast_stream_t stream);
 size_t sast_eval_sort_ws_bytes(int64_t max_detections);
 int sast_eval_accumulate(const SastEvalArgs* a, sast_stream_t stream);
 int sast_evmerge_append(const SastEvalArgs* dst, const SastEvalArgs* src, sast_stream_t stream);
+
+/* ---- the whole of COCOeval.accumulate / summarize at maxDets [1, 10, 100] (csrc/k_eval.hip): the tables of COCOeval.eval and the
+ * twelve numbers of COCOeval.stats.  sast_evsum_accumulate runs BEHIND sast_eval_accumulate on the same stream and buffer: it reads the
+ * `sorted` array that call leaves, the records and the state, and writes only what SastEvSumArgs names (buf->precision, buf->result
+ * and buf->sort_ws are not touched).
+ *   kept     for maxDet m an image contributes its first m detections per category: the records of rank < m (rec_ign bits 40..46).
+ *            They are a subsequence of the sorted order, so there is no second sort: a record of rank >= m counts as ignored in every
+ *            lane, and the chunk walk of sast_eval_accumulate (count, scan, maximum, envelope, walk) runs once more with the maxDet
+ *            as a second grid dimension.  The m = 100 slice of `precision` is buf->precision bit for bit
+ *   recall   [t][k][a][m]: the true positives at the category's right edge / the non-ignored ground truths; 0 when the category has
+ *            no record, -1 when it has no non-ignored ground truth
+ *   scores   [t][r][k][a][m]: the fp32 score, widened, of the record at which recall threshold r is first reached (where the walk
+ *            writes the precision entry), recovered from the score bits of the sort key (a score of -0 reads +0); 0 where the
+ *            threshold is never reached, -1 where precision is -1.  Threshold 0 is reached at the category's first kept record
+ *            whether or not it is ignored in that area range (np.searchsorted, side='left'): sorted[start] for every m
+ *   stats    COCOeval.stats: AP, AP_50, AP_75, AP_S, AP_M, AP_L (m = 100), AR_1, AR_10, AR_100 (all areas), AR_S, AR_M, AR_L (m = 100),
+ *            each the mean over the entries > -1 of its slice or -1; the first six are buf->result[0..5] bit for bit
+ *   per_class [k][4]: AP, AP_50, AP_75 and AR_100 of category k alone over all areas at m = 100, by the same rule
+ * No table depends on SAST_EVAL_ACC_CHUNK, bit for bit.  Six launches, no host synchronisation, every grid sized from max_detections
+ * and K.  ws: sast_evsum_ws_bytes(max_detections) bytes AT THE KNOB'S CURRENT VALUE (3 KiB per chunk), 8-byte aligned, no initial
+ * contents needed.  Refused on the host (SAST_EINVAL): null pointers, a buffer sast_eval_accumulate would refuse, ws misaligned or
+ * ws_bytes too small. */
+#define SAST_EVSUM_MAXDETS 3
+#define SAST_EVSUM_STATS 12
+typedef struct {
+  double* precision;       /* [10][101][K][4][3] */
+  double* scores;          /* [10][101][K][4][3] */
+  double* recall;          /* [10][K][4][3] */
+  double* stats;           /* [12] */
+  double* per_class;       /* [K][4] */
+  void* ws; size_t ws_bytes;
+} SastEvSumArgs;
+size_t sast_evsum_ws_bytes(int64_t max_detections);   /* 0: max_detections out of range.  Host only. */
+int sast_evsum_accumulate(const SastEvalArgs* buf, const SastEvSumArgs* sum, sast_stream_t stream);
 
 /* ---- whole recordings into the evaluation buffer (csrc/k_eval.hip): the Prophesee protocol itself, one label file against one
  * detection file per recording -- evaluate_list(apply_bbox_filters=True) (evaluation.py:5-42) and evaluate_detection's loop over files

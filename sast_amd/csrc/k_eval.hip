@@ -13,10 +13,13 @@
 //                                   ranked by a stable descending sort on the score (bitonic network in LDS on (score, index) keys),
 //                                   cut to 100, the fp64 IoU tile in LDS, then COCOeval's greedy matching with one lane per
 //                                   (area range, IoU threshold) pair: 40 lanes.  One record per detection: sort key, 40 match bits, 40
-//                                   ignore bits.
+//                                   ignore bits and, above them, the detection's rank in its (image, category) group.
 //   sast_eval_accumulate  one device-wide radix sort (rocprim) of the record keys (category, descending score, record index: unique, so
 //                         the order is the stable one), the chunk-parallel walk of every category's sorted records (counts, scan over
 //                         the chunks, precision maxima, envelope, backward walk: the 101 recall thresholds), and the six summaries.
+//   sast_evsum_accumulate behind sast_eval_accumulate, on the `sorted` array it leaves: the same five launches at maxDets 1, 10 and 100
+//                         at once (a record whose rank is past the maxDet counts as ignored), which also write COCOeval's recall and
+//                         score tables, then the twelve stats and the per-category numbers.  Six launches, no host synchronisation
 //   sast_evmerge_append   one buffer behind another (two launches, no host synchronisation): what joins the buffers of several ranks
 //   sast_evrec_add        S whole recordings as sorted 40-byte box records, labels and detections: evaluate_detection's loop over
 //                         "files" (coco_eval.py:42-51) with _match_times' windows.  Four launches, no host synchronisation
@@ -45,6 +48,9 @@ constexpr int EV_R = SAST_EVAL_REC_THRS;      // 101
 constexpr int EV_A = SAST_EVAL_AREAS;         // 4
 constexpr int EV_LANES = EV_T * EV_A;         // 40: lane = area * 10 + threshold
 constexpr int EV_MAXDET = 100;
+constexpr int EV_M = SAST_EVSUM_MAXDETS;      // 3: maxDets 1, 10, 100
+constexpr unsigned long long EV_LANE_MASK = (1ull << EV_LANES) - 1;
+constexpr int EV_RANK_SHIFT = 40;             // rec_ign bits 40..46: the record's rank in its (image, category) group
 constexpr int EV_INFO = 16;                   // int32 words of per-frame scratch
 constexpr long long EV_SKIP_US = 500000;
 constexpr unsigned long long EV_IDX_MASK = (1ull << 30) - 1;
@@ -539,7 +545,7 @@ __global__ void __launch_bounds__(64) eval_match_kernel(SastEvalArgs a, typename
     const unsigned long long mb = __ballot(m > -1), ib = __ballot(ign);
     if (lane == 0) {
       const int ro = rec + d;
-      a.rec_match[ro] = mb, a.rec_ign[ro] = ib;
+      a.rec_match[ro] = mb, a.rec_ign[ro] = ib | ((unsigned long long)d << EV_RANK_SHIFT);   // d <= 99: the rank in the group
       a.rec_key[ro] = ((unsigned long long)k << 62) | ((unsigned long long)(~score_key(l.dscore[d])) << 30) | (unsigned long long)ro;
     }
   }
@@ -619,23 +625,62 @@ __device__ __forceinline__ bool acc_chunk(const SastEvalArgs& a, long long q, in
   return false;
 }
 
-// one tile of at most 64 records of a chunk: their match / ignore words into LDS
-__device__ __forceinline__ void acc_load_tile(const SastEvalArgs& a, int lo, int cnt, int base, unsigned long long* sm, unsigned long long* si) {
+// ---- the five launches are templates on SUM.  SUM = false is sast_eval_accumulate: maxDets 100, the table a.precision [T][R][K][A].
+// SUM = true is sast_evsum_accumulate: blockIdx.y picks the maxDet (1, 10, 100), the tables are [T][R][K][A][3] plus scores and recall,
+// and the partials of maxDet mi are the rows [mi * chunks, (mi + 1) * chunks) of the workspace.  For maxDet m a record of rank >= m in
+// its (image, category) group is not among the image's first m detections (cocoeval.py cuts every image to [0:maxDet]); the records
+// left are a subsequence of the sorted order, so such a record only has to count for nothing: it is loaded as ignored in all 40 lanes.
+struct AccSum {
+  double* precision;   // [T][R][K][A][3]
+  double* scores;      // [T][R][K][A][3]
+  double* recall;      // [T][K][A][3]
+  long long chunks;    // workspace rows of one maxDet
+};
+
+__device__ __forceinline__ int sum_maxdet(int mi) { return mi == 0 ? 1 : mi == 1 ? 10 : EV_MAXDET; }
+
+// the first element of column (threshold th, category k, area ar, maxDet mi) of a [T][R][K][A](x [3]) table; rs: its stride over R
+template <bool SUM>
+__device__ __forceinline__ size_t acc_column(const SastEvalArgs& a, int th, int k, int ar, int mi, size_t& rs) {
+  const size_t M = SUM ? EV_M : 1;
+  rs = (size_t)a.K * EV_A * M;
+  return ((size_t)th * EV_R * a.K * EV_A + k * EV_A + ar) * M + (SUM ? mi : 0);
+}
+
+// bits 30..61 of a sort key, ~score_key(score), back to the score (-0 was sorted, and comes back, as +0)
+__device__ __forceinline__ double key_score(unsigned inv) {
+  const unsigned key = ~inv;
+  return (double)__uint_as_float((key & 0x80000000u) ? (key & 0x7fffffffu) : ~key);
+}
+
+// one tile of at most 64 records of a chunk: their match / ignore words (and with sk their score bits) into LDS
+template <bool SUM>
+__device__ __forceinline__ void acc_load_tile(const SastEvalArgs& a, int lo, int cnt, int base, int md, unsigned long long* sm, unsigned long long* si,
+                                              unsigned* sk = nullptr) {
   const int lane = threadIdx.x;
   if (base + lane < cnt) {
-    const unsigned long long ro = min(a.sorted[lo + base + lane] & EV_IDX_MASK, (unsigned long long)(a.max_detections - 1));
-    sm[lane] = a.rec_match[ro], si[lane] = a.rec_ign[ro];
+    const unsigned long long key = a.sorted[lo + base + lane];
+    const unsigned long long ro = min(key & EV_IDX_MASK, (unsigned long long)(a.max_detections - 1));
+    unsigned long long ig = a.rec_ign[ro];
+    if (SUM) {
+      if ((int)((ig >> EV_RANK_SHIFT) & 127) >= md) ig = EV_LANE_MASK;   // not among its image's first md detections
+      if (sk) sk[lane] = (unsigned)(key >> 30);
+    }
+    sm[lane] = a.rec_match[ro], si[lane] = ig;
   }
 }
 
-__global__ void __launch_bounds__(64) eval_acc_count_kernel(SastEvalArgs a, int L, AccWs w) {
+template <bool SUM>
+__global__ void __launch_bounds__(64) eval_acc_count_kernel(SastEvalArgs a, int L, AccWs w, AccSum s) {
   __shared__ unsigned long long sm[64], si[64];
   const int lane = threadIdx.x;
+  const int mi = SUM ? blockIdx.y : 0, md = SUM ? sum_maxdet(mi) : EV_MAXDET;
+  const size_t row = ((SUM ? (size_t)mi * s.chunks : 0) + blockIdx.x) * 64 + lane;
   AccChunk p;
   if (!acc_chunk(a, blockIdx.x, L, p)) return;
   int tp = 0, fp = 0;
   for (int base = 0; base < p.cnt; base += 64) {
-    acc_load_tile(a, p.lo, p.cnt, base, sm, si);
+    acc_load_tile<SUM>(a, p.lo, p.cnt, base, md, sm, si);
     __syncthreads();
     const int cj = min(64, p.cnt - base);
     for (int j = 0; j < cj; ++j) {
@@ -644,38 +689,49 @@ __global__ void __launch_bounds__(64) eval_acc_count_kernel(SastEvalArgs a, int 
     }
     __syncthreads();
   }
-  w.tp[(size_t)blockIdx.x * 64 + lane] = tp, w.fp[(size_t)blockIdx.x * 64 + lane] = fp;
+  w.tp[row] = tp, w.fp[row] = fp;
 }
 
-__global__ void __launch_bounds__(64) eval_acc_scan_kernel(SastEvalArgs a, int L, AccWs w) {
+template <bool SUM>
+__global__ void __launch_bounds__(64) eval_acc_scan_kernel(SastEvalArgs a, int L, AccWs w, AccSum s) {
   const int k = blockIdx.x, lane = threadIdx.x;
+  const int mi = SUM ? blockIdx.y : 0;
+  const long long qb = SUM ? mi * s.chunks : 0;
   const int ar = lane / EV_T, th = lane - ar * EV_T;
   const bool active = lane < EV_LANES;
   const AccCat c = acc_category(a, k, L);
   int tp = 0, fp = 0;
-  for (long long q = c.q0; q < c.q0 + c.nck; ++q) {   // any chunk count: sequential over the chunks, 64 lanes wide
+  for (long long q = qb + c.q0; q < qb + c.q0 + c.nck; ++q) {   // any chunk count: sequential over the chunks, 64 lanes wide
     tp += w.tp[q * 64 + lane], fp += w.fp[q * 64 + lane];
     w.tp[q * 64 + lane] = tp, w.fp[q * 64 + lane] = fp;
   }
   if (!active) return;
   const int npig = a.state[ST_NPIG + k * EV_A + ar];
+  if (SUM)   // COCOeval's recall: the true positives at the category's right edge over npig; 0 without a record, -1 without a label
+    s.recall[(((size_t)th * a.K + k) * EV_A + ar) * EV_M + mi] = npig > 0 ? (c.n > 0 ? (double)tp / (double)npig : 0.0) : -1.0;
   if (npig > 0 && c.n > 0) return;                    // the chunks write the column
-  double* out = a.precision + (size_t)th * EV_R * a.K * EV_A + k * EV_A + ar;   // [T][R][K][A]
-  const size_t rs = (size_t)a.K * EV_A;
+  size_t rs;
+  const size_t o = acc_column<SUM>(a, th, k, ar, mi, rs);
+  double* out = (SUM ? s.precision : a.precision) + o;
   const double v = npig > 0 ? 0.0 : -1.0;             // no detection: recall 0 reaches threshold 0 only, with precision 0
   for (int r = 0; r < EV_R; ++r) out[r * rs] = v;
+  if (SUM)
+    for (int r = 0; r < EV_R; ++r) s.scores[o + r * rs] = v;
 }
 
-__global__ void __launch_bounds__(64) eval_acc_max_kernel(SastEvalArgs a, int L, AccWs w) {
+template <bool SUM>
+__global__ void __launch_bounds__(64) eval_acc_max_kernel(SastEvalArgs a, int L, AccWs w, AccSum s) {
   __shared__ unsigned long long sm[64], si[64];
   const int lane = threadIdx.x;
+  const int mi = SUM ? blockIdx.y : 0, md = SUM ? sum_maxdet(mi) : EV_MAXDET;
+  const size_t row = ((SUM ? (size_t)mi * s.chunks : 0) + blockIdx.x) * 64 + lane;
   AccChunk p;
   if (!acc_chunk(a, blockIdx.x, L, p)) return;
   int tp = 0, fp = 0;
-  if (p.c > 0) tp = w.tp[((size_t)blockIdx.x - 1) * 64 + lane], fp = w.fp[((size_t)blockIdx.x - 1) * 64 + lane];
+  if (p.c > 0) tp = w.tp[row - 64], fp = w.fp[row - 64];
   double mx = 0.0;
   for (int base = 0; base < p.cnt; base += 64) {
-    acc_load_tile(a, p.lo, p.cnt, base, sm, si);
+    acc_load_tile<SUM>(a, p.lo, p.cnt, base, md, sm, si);
     __syncthreads();
     const int cj = min(64, p.cnt - base);
     for (int j = 0; j < cj; ++j) {
@@ -687,23 +743,31 @@ __global__ void __launch_bounds__(64) eval_acc_max_kernel(SastEvalArgs a, int L,
     }
     __syncthreads();
   }
-  w.mx[(size_t)blockIdx.x * 64 + lane] = mx;
+  w.mx[row] = mx;
 }
 
-__global__ void __launch_bounds__(64) eval_acc_envelope_kernel(SastEvalArgs a, int L, AccWs w) {
+template <bool SUM>
+__global__ void __launch_bounds__(64) eval_acc_envelope_kernel(SastEvalArgs a, int L, AccWs w, AccSum s) {
   const int k = blockIdx.x, lane = threadIdx.x;
+  const long long qb = SUM ? blockIdx.y * s.chunks : 0;
   const AccCat c = acc_category(a, k, L);
   double mx = 0.0;
-  for (long long q = c.q0 + c.nck - 1; q >= c.q0; --q) {
+  for (long long q = qb + c.q0 + c.nck - 1; q >= qb + c.q0; --q) {
     mx = fmax(mx, w.mx[q * 64 + lane]);
     w.mx[q * 64 + lane] = mx;
   }
 }
 
-__global__ void __launch_bounds__(64) eval_acc_walk_kernel(SastEvalArgs a, int L, AccWs w) {
+// SUM also writes scores: beside every precision entry the score of the record at which the walk writes it -- the first record whose
+// recall reaches the threshold (np.searchsorted, side='left').  Threshold 0 is reached at index 0 of the kept records whether or not
+// that record is ignored; it is sorted[start] for every maxDet, since a category's top-scored record has rank 0 in its own group.
+template <bool SUM>
+__global__ void __launch_bounds__(64) eval_acc_walk_kernel(SastEvalArgs a, int L, AccWs w, AccSum s) {
   __shared__ unsigned long long sm[64], si[64];
+  __shared__ unsigned sk[SUM ? 64 : 1];
   __shared__ double rthr[EV_R];
   const int lane = threadIdx.x;
+  const int mi = SUM ? blockIdx.y : 0, md = SUM ? sum_maxdet(mi) : EV_MAXDET;
   AccChunk p;
   if (!acc_chunk(a, blockIdx.x, L, p)) return;
   const int ar = lane / EV_T, th = lane - ar * EV_T;
@@ -711,9 +775,11 @@ __global__ void __launch_bounds__(64) eval_acc_walk_kernel(SastEvalArgs a, int L
   for (int r = lane; r < EV_R; r += 64) rthr[r] = a.rec_thr[r];
   const int npig = active ? a.state[ST_NPIG + p.k * EV_A + ar] : 0;
   const bool live = active && npig > 0;
-  double* out = a.precision + (size_t)th * EV_R * a.K * EV_A + p.k * EV_A + ar;   // [T][R][K][A]
-  const size_t rs = (size_t)a.K * EV_A;
-  const size_t row = (size_t)blockIdx.x * 64 + lane;
+  size_t rs;
+  const size_t col = acc_column<SUM>(a, th, p.k, ar, mi, rs);
+  double* out = (SUM ? s.precision : a.precision) + col;
+  double* sc = SUM ? s.scores + col : nullptr;
+  const size_t row = ((SUM ? (size_t)mi * s.chunks : 0) + blockIdx.x) * 64 + lane;
   const bool first = p.c == 0, last = p.c == p.nck - 1;
   int tp = w.tp[row], fp = w.fp[row];                                 // at the chunk's right edge
   const int tpl = first ? 0 : w.tp[row - 64];                         // at its left edge
@@ -726,17 +792,24 @@ __global__ void __launch_bounds__(64) eval_acc_walk_kernel(SastEvalArgs a, int L
     while (ihi < EV_R && rthr[ihi] <= rc) ++ihi;
     while (ilo < EV_R && rthr[ilo] <= rcl) ++ilo;
     if (last)
-      for (int r = ihi; r < EV_R; ++r) out[r * rs] = 0.0;             // np.searchsorted past the end: the entry stays 0
+      for (int r = ihi; r < EV_R; ++r) {                              // np.searchsorted past the end: the entry stays 0
+        out[r * rs] = 0.0;
+        if (SUM) sc[r * rs] = 0.0;
+      }
     if (first) {
       const double all = w.mx[row];                                   // the maximum over the whole category
-      for (int r = 0; r < ilo; ++r) out[r * rs] = all;                // recall threshold 0
+      const double top = SUM ? key_score((unsigned)(a.sorted[p.lo] >> 30)) : 0.0;   // p.lo is the category's start: cnt >= 1
+      for (int r = 0; r < ilo; ++r) {                                 // recall threshold 0
+        out[r * rs] = all;
+        if (SUM) sc[r * rs] = top;
+      }
     }
   }
   // backwards: the precision envelope (the running maximum from the right) at the first record whose recall reaches each threshold;
   // thresholds [ilo, ihi) are this chunk's, and the walk ends early once every lane has written its own
   for (int base = p.cnt > 0 ? ((p.cnt - 1) / 64) * 64 : -64; base >= 0; base -= 64) {
     if (__syncthreads_or(ihi > ilo) == 0) break;
-    acc_load_tile(a, p.lo, p.cnt, base, sm, si);
+    acc_load_tile<SUM>(a, p.lo, p.cnt, base, md, sm, si, SUM ? sk : nullptr);
     __syncthreads();
     if (live && ihi > ilo) {
       for (int j = min(64, p.cnt - base) - 1; j >= 0; --j) {
@@ -747,7 +820,10 @@ __global__ void __launch_bounds__(64) eval_acc_walk_kernel(SastEvalArgs a, int L
         mx = fmax(mx, pr);
         tp -= m, fp -= m ^ 1;
         const double rcp = (double)tp / dn;
-        while (ihi > 0 && rthr[ihi - 1] > rcp) out[--ihi * rs] = mx;
+        while (ihi > 0 && rthr[ihi - 1] > rcp) {
+          out[--ihi * rs] = mx;
+          if (SUM) sc[ihi * rs] = key_score(sk[j]);                   // record j is where this recall is first reached
+        }
       }
     }
   }
@@ -774,6 +850,42 @@ __global__ void __launch_bounds__(64) eval_summarize_kernel(SastEvalArgs a) {
     a.result[s] = cnt > 0 ? sum / (double)cnt : -1.0;
   }
   if (s == 0 && lane < SAST_EVAL_STATE_WORDS) a.result[8 + lane] = (double)a.state[lane];   // one host copy brings both
+}
+
+// COCOeval.summarize and the per-category numbers: one workgroup per number, each the mean over the entries > -1 of a slice of the
+// precision or the recall table (-1 when there is none).  Workgroups 0..11 are COCOeval.stats in its order; workgroup 12 + 4 k + j is
+// category k's AP, AP_50, AP_75 (all areas, maxDets 100) and AR_100.  The summation order of the first six is eval_summarize_kernel's
+// over the same values, so they are its six numbers bit for bit.
+__global__ void __launch_bounds__(64) evsum_stats_kernel(SastEvalArgs a, AccSum s, double* stats, double* per_class) {
+  __shared__ double ssum[64];
+  __shared__ int scnt[64];
+  const int b = blockIdx.x, lane = threadIdx.x;
+  bool rec;                                   // the recall table, not the precision table
+  int ar = 0, t0 = 0, nt = EV_T, k0 = 0, nk = a.K, mi = EV_M - 1;
+  if (b < 6) rec = false, ar = b < 3 ? 0 : b - 2, t0 = b == 2 ? 5 : 0, nt = (b == 1 || b == 2) ? 1 : EV_T;
+  else if (b < 9) rec = true, mi = b - 6;     // AR_1, AR_10, AR_100 over all areas
+  else if (b < 12) rec = true, ar = b - 8;    // AR_S, AR_M, AR_L at maxDets 100
+  else {
+    const int j = (b - 12) & 3;
+    k0 = (b - 12) >> 2, nk = 1, rec = j == 3, t0 = j == 2 ? 5 : 0, nt = (j == 1 || j == 2) ? 1 : EV_T;
+  }
+  const int per_t = (rec ? 1 : EV_R) * nk;
+  double sum = 0.0;
+  int cnt = 0;
+  for (int e = lane; e < nt * per_t; e += 64) {
+    const int t = t0 + e / per_t, rr = e % per_t, r = rr / nk, k = k0 + rr % nk;
+    const double v = rec ? s.recall[(((size_t)t * a.K + k) * EV_A + ar) * EV_M + mi]
+                         : s.precision[((((size_t)t * EV_R + r) * a.K + k) * EV_A + ar) * EV_M + mi];
+    if (v > -1.0) sum += v, ++cnt;
+  }
+  ssum[lane] = sum, scnt[lane] = cnt;
+  __syncthreads();
+  if (lane == 0) {
+    for (int i = 1; i < 64; ++i) sum += ssum[i], cnt += scnt[i];
+    const double v = cnt > 0 ? sum / (double)cnt : -1.0;
+    if (b < SAST_EVSUM_STATS) stats[b] = v;
+    else per_class[b - SAST_EVSUM_STATS] = v;
+  }
 }
 
 // ---- sast_evmerge_append: the buffer `s` behind the buffer `d`.  Every count is read from the two states on the device and clamped
@@ -1048,12 +1160,41 @@ int sast_eval_accumulate(const SastEvalArgs* a, sast_stream_t stream) {
     return SAST_ELAUNCH;
   const AccWs w = acc_ws_carve(a->sort_ws, chunks);
   const dim3 per_chunk((unsigned)chunks), per_cat((unsigned)a->K);   // sized from the capacity: the counts stay on the device
-  SAST_LAUNCH(eval_acc_count_kernel, per_chunk, dim3(64), 0, st, *a, L, w);
-  SAST_LAUNCH(eval_acc_scan_kernel, per_cat, dim3(64), 0, st, *a, L, w);
-  SAST_LAUNCH(eval_acc_max_kernel, per_chunk, dim3(64), 0, st, *a, L, w);
-  SAST_LAUNCH(eval_acc_envelope_kernel, per_cat, dim3(64), 0, st, *a, L, w);
-  SAST_LAUNCH(eval_acc_walk_kernel, per_chunk, dim3(64), 0, st, *a, L, w);
+  const AccSum none{nullptr, nullptr, nullptr, 0};
+  SAST_LAUNCH(eval_acc_count_kernel<false>, per_chunk, dim3(64), 0, st, *a, L, w, none);
+  SAST_LAUNCH(eval_acc_scan_kernel<false>, per_cat, dim3(64), 0, st, *a, L, w, none);
+  SAST_LAUNCH(eval_acc_max_kernel<false>, per_chunk, dim3(64), 0, st, *a, L, w, none);
+  SAST_LAUNCH(eval_acc_envelope_kernel<false>, per_cat, dim3(64), 0, st, *a, L, w, none);
+  SAST_LAUNCH(eval_acc_walk_kernel<false>, per_chunk, dim3(64), 0, st, *a, L, w, none);
   SAST_LAUNCH(eval_summarize_kernel, dim3(6), dim3(64), 0, st, *a);
+  SAST_CHECK_LAUNCH();
+  return SAST_OK;
+}
+
+size_t sast_evsum_ws_bytes(int64_t max_detections) {
+  if (max_detections < 1 || (unsigned long long)max_detections > sast::EV_IDX_MASK) return 0;
+  return sast::EV_M * sast::eval_acc_ws_bytes(max_detections, sast::eval_acc_chunk());
+}
+
+int sast_evsum_accumulate(const SastEvalArgs* a, const SastEvSumArgs* sum, sast_stream_t stream) {
+  SAST_ENTRY();
+  using namespace sast;
+  if (!eval_args_ok(a) || !a->sorted || !a->rec_thr || !sum || !sum->precision || !sum->scores || !sum->recall || !sum->stats ||
+      !sum->per_class || !sum->ws || (reinterpret_cast<uintptr_t>(sum->ws) & 7))
+    return SAST_EINVAL;
+  const int L = eval_acc_chunk();
+  const long long chunks = acc_max_chunks(a->max_detections, L);
+  if (sum->ws_bytes < EV_M * eval_acc_ws_bytes(a->max_detections, L) || chunks > 0x7fffffffll) return SAST_EINVAL;
+  const hipStream_t st = (hipStream_t)stream;
+  const AccWs w = acc_ws_carve(sum->ws, EV_M * chunks);
+  const AccSum s{sum->precision, sum->scores, sum->recall, chunks};
+  const dim3 per_chunk((unsigned)chunks, EV_M), per_cat((unsigned)a->K, EV_M);   // sized from the capacity: the counts stay on the device
+  SAST_LAUNCH(eval_acc_count_kernel<true>, per_chunk, dim3(64), 0, st, *a, L, w, s);
+  SAST_LAUNCH(eval_acc_scan_kernel<true>, per_cat, dim3(64), 0, st, *a, L, w, s);
+  SAST_LAUNCH(eval_acc_max_kernel<true>, per_chunk, dim3(64), 0, st, *a, L, w, s);
+  SAST_LAUNCH(eval_acc_envelope_kernel<true>, per_cat, dim3(64), 0, st, *a, L, w, s);
+  SAST_LAUNCH(eval_acc_walk_kernel<true>, per_chunk, dim3(64), 0, st, *a, L, w, s);
+  SAST_LAUNCH(evsum_stats_kernel, dim3((unsigned)(SAST_EVSUM_STATS + 4 * a->K)), dim3(64), 0, st, *a, s, sum->stats, sum->per_class);
   SAST_CHECK_LAUNCH();
   return SAST_OK;
 }

@@ -21,8 +21,12 @@ on the device: `add` takes the label tensors `SpatialAugmentor` returns and the 
 - `add_recordings` is the protocol's own form: whole recordings as sorted box records, one label "file" against one detection "file"
   per row, every unique label timestamp an image with the detections within +-time_tol_us (_match_times, metrics/coco_eval.py:55-90).
   It feeds the same count, scan and match kernels through a second row source and may be mixed with `add` in one buffer.
-- Not implemented: AR and maxDets 1 / 10 (the reference discards them), visualisation.  Parity with pycocotools and with the
-  Metavision toolbox is not pinned by a test: neither is installed where this project is built (tests/coco_reference.py is the yardstick).
+- `summary`, `coco_eval` and `per_class` follow an `evaluate_buffer` and give the rest of COCOeval: the twelve numbers of its stats
+  (AP and AR at maxDets 1 / 10 / 100, which the reference discards in coco_eval.py:109), the precision, recall and score tables of
+  COCOeval.eval at maxDets [1, 10, 100] and the numbers per category.  Every record carries its rank inside its (image, category)
+  group, so the cut to an image's first 1 or 10 detections needs no second matching or sort; `scores` is how a `conf_thre` is picked.
+- Not implemented: visualisation.  Parity with pycocotools and with the Metavision toolbox is not pinned by a test: neither is
+  installed where this project is built (tests/coco_reference.py and tests/coco_reference_full.py are the yardsticks).
 
 There is no CPU path: CPU tensors raise the library's "no CPU fallback" error.
 """
@@ -40,6 +44,9 @@ from ._frontend import not_capturing, same_device, tensor_arg
 from .functional import _need_gpu, _stream
 
 OUT_KEYS = ('AP', 'AP_50', 'AP_75', 'AP_S', 'AP_M', 'AP_L')   # coco_eval.py:109
+SUMMARY_KEYS = OUT_KEYS + ('AR_1', 'AR_10', 'AR_100', 'AR_S', 'AR_M', 'AR_L')   # COCOeval.stats, in its order
+CLASS_KEYS = ('AP', 'AP_50', 'AP_75', 'AR_100')
+MAX_DETS = (1, 10, 100)                                        # pycocotools Params.setDetParams
 CLASSES = {'gen1': ("car", "pedestrian"), 'gen4': ("pedestrian", "two-wheeler", "car")}   # evaluation.py:15-18
 IOU_THRS = np.linspace(.5, 0.95, int(np.round((0.95 - .5) / .05)) + 1, endpoint=True)      # pycocotools Params.setDetParams
 REC_THRS = np.linspace(.0, 1.00, int(np.round((1.00 - .0) / .01)) + 1, endpoint=True)
@@ -58,6 +65,9 @@ class PropheseeEvaluator:
       by timestamp (see the method).
     ev.evaluate_buffer(img_height, img_width) -> {'AP', 'AP_50', 'AP_75', 'AP_S', 'AP_M', 'AP_L'} as Python floats (one sync, at the end)
     ev.precision() -> fp64 [10, 101, K, 4] of the last evaluate_buffer; ev.tables() -> the flattened image / annotation / result records
+    ev.summary() -> the twelve numbers of COCOeval.stats (AP .. AP_L, AR_1, AR_10, AR_100, AR_S, AR_M, AR_L); ev.coco_eval() ->
+      {'precision', 'scores' fp64 [10, 101, K, 4, 3], 'recall' fp64 [10, K, 4, 3]} for maxDets [1, 10, 100], on the device;
+      ev.per_class() -> {class name: {'AP', 'AP_50', 'AP_75', 'AR_100'}}.  All three follow a successful evaluate_buffer.
     ev.reset_buffer(), ev.has_data() as in the reference.
     ev.merge(other): other's buffer appended, as if its frames had been added here after this one's; ev.export_buffer() -> dict of
       trimmed device tensors, ev.import_buffer(blob) appends one; ev.all_gather(group=None): every rank ends with the buffers of all
@@ -87,6 +97,7 @@ class PropheseeEvaluator:
         self._t: Dict[str, torch.Tensor] = {}
         self._args = L.SastEvalArgs()
         self._evaluated = False
+        self._sum: Optional[Dict[str, object]] = None         # the full summary of the last evaluate_buffer, made on demand
 
     # ------------------------------------------------------------------------------------------------------------------ buffers
     def _allocate(self, dev: torch.device):
@@ -224,6 +235,7 @@ class PropheseeEvaluator:
             self._t["sort_ws"] = torch.empty(ws_bytes, dtype=torch.uint8, device=self._dev)
             self._args.sort_ws, self._args.sort_ws_bytes = self._t["sort_ws"].data_ptr(), ws_bytes
         L.check(L.lib().sast_eval_accumulate(C.byref(self._args), _stream()), "eval_accumulate")
+        self._sum = None
         res = self._t["result"].cpu().numpy()        # the one synchronisation
         state = res[8:].astype(np.int64)
         self._state = state
@@ -248,6 +260,59 @@ class PropheseeEvaluator:
         if not self._evaluated:
             raise RuntimeError("sast_amd.evaluation: precision() follows a successful evaluate_buffer()")
         return self._t["precision"].clone()
+
+    # ------------------------------------------------------------------------------------------------ the full COCO summary
+    def _summarized(self) -> Dict[str, torch.Tensor]:
+        """COCOeval's tables at maxDets [1, 10, 100], the twelve stats and the per-category numbers of the last evaluate_buffer: one
+        library call (six launches, no sync) behind it, on the sorted records it left; made once per evaluate_buffer"""
+        if not self._evaluated:
+            raise RuntimeError("sast_amd.evaluation: summary(), coco_eval() and per_class() follow a successful evaluate_buffer()")
+        if self._sum is None:
+            K, dev = len(self.classes), self._dev
+            shape = (L.EVAL_IOU_THRS, L.EVAL_REC_THRS, K, L.EVAL_AREAS, L.EVSUM_MAXDETS)
+            t = {"precision": torch.empty(shape, dtype=torch.float64, device=dev), "scores": torch.empty(shape, dtype=torch.float64, device=dev),
+                 "recall": torch.empty(shape[:1] + shape[2:], dtype=torch.float64, device=dev),
+                 "numbers": torch.empty(L.EVSUM_STATS + 4 * K, dtype=torch.float64, device=dev)}    # stats, then per_class [K][4]
+            s = L.SastEvSumArgs()
+            s.precision, s.scores, s.recall = t["precision"].data_ptr(), t["scores"].data_ptr(), t["recall"].data_ptr()
+            s.stats = t["numbers"].data_ptr()
+            s.per_class = s.stats + 8 * L.EVSUM_STATS
+            s.ws_bytes = int(L.lib().sast_evsum_ws_bytes(self.max_detections))
+            if s.ws_bytes == 0:
+                raise RuntimeError("sast_amd.evaluation: the library refused the summary workspace size")
+            ws = torch.empty(s.ws_bytes, dtype=torch.uint8, device=dev)            # freed in stream order, behind the six launches
+            s.ws = ws.data_ptr()
+            L.check(L.lib().sast_evsum_accumulate(C.byref(self._args), C.byref(s), _stream()), "evsum_accumulate")
+            self._sum = t
+        return self._sum
+
+    def _numbers(self) -> np.ndarray:
+        t = self._summarized()
+        if "host" not in t:
+            t["host"] = t["numbers"].cpu().numpy()       # the one host copy: twelve stats and 4 K per-category numbers
+        return t["host"]
+
+    def summary(self) -> Dict[str, float]:
+        """COCOeval.stats of the last evaluate_buffer, in its order: AP, AP_50, AP_75, AP_S, AP_M, AP_L (maxDets 100), AR_1, AR_10, AR_100
+        (all areas), AR_S, AR_M, AR_L (maxDets 100); twelve zeros when no image has a detection (coco_eval.py:112-115).  The first six
+        are evaluate_buffer's numbers.  One host copy."""
+        v = self._numbers()
+        if self._state[2] == 0:
+            return {k: 0.0 for k in SUMMARY_KEYS}
+        return {k: float(v[i]) for i, k in enumerate(SUMMARY_KEYS)}
+
+    def coco_eval(self) -> Dict[str, torch.Tensor]:
+        """COCOeval.eval's tables of the last evaluate_buffer for maxDets [1, 10, 100], fp64 on the device: `precision` and `scores`
+        [T=10, R=101, K, A=4, M=3], `recall` [10, K, 4, 3].  scores[t, r, k, a, m] is the detection score at which recall REC_THRS[r] is
+        first reached at IoU IOU_THRS[t] (0: never reached, -1: no label of that category and size)."""
+        t = self._summarized()
+        return {k: t[k].clone() for k in ("precision", "recall", "scores")}
+
+    def per_class(self) -> Dict[str, Dict[str, float]]:
+        """per name of `self.classes`: AP, AP_50, AP_75 and AR_100 of that category alone over all areas (maxDets 100), each the mean
+        over the entries > -1, or -1 when the category has no label"""
+        v = self._numbers()[L.EVSUM_STATS:].reshape(len(self.classes), 4)
+        return {name: {k: float(v[i, j]) for j, k in enumerate(CLASS_KEYS)} for i, name in enumerate(self.classes)}
 
     def tables(self) -> Dict[str, np.ndarray]:
         """the flattened records of _to_coco_format (coco_eval.py:143-194) as numpy arrays (synchronises):

@@ -7,6 +7,8 @@ Per call, all in this one process:
   add       PropheseeEvaluator.add of N = 8 frames with D detections each (three launches, no host sync), for several D
   evaluate  PropheseeEvaluator.evaluate_buffer over a buffer of --frames frames with --dets detections each: the epoch-end sort,
             accumulate and summaries, the final host copy included
+  summary   PropheseeEvaluator.summary behind an evaluate_buffer on that buffer: the accumulate at maxDets 1 / 10 / 100 with the recall
+            and score tables, the twelve stats and its host copy.  Left out when the loaded library has no sast_evsum_accumulate
   merge     two evaluators with half of those frames each: PropheseeEvaluator.merge of one into the other (two launches, no host
             sync; timed once with events, after a warm-up on a small pair), then evaluate_buffer on the merged buffer.  Left out when
             the loaded library has no sast_evmerge_append (an A/B run against an older build through SAST_LIB_PATH)
@@ -14,7 +16,7 @@ A randomly initialised head puts nearly nothing above the threshold, so the dete
 synthetic: per frame 1..12 labels, D boxes of which 60 % are jittered copies of a label and the rest random, 64 score levels.  D stands
 for what survives confidence 0.001 and NMS on a trained detector; it is an input of this tool, not a measurement of one.
 
-  python tools/eval_bench.py [--reps 20] [--rounds 5] [--frames 20000] [--dets 300] [--out FILE]
+  python tools/eval_bench.py [--reps 20] [--rounds 5] [--frames 20000] [--dets 300] [--no-summary] [--out FILE]
 """
 from __future__ import annotations
 
@@ -78,6 +80,7 @@ def main():
     ap.add_argument("--frames", type=int, default=20000)
     ap.add_argument("--dets", type=int, default=300)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--no-summary", action="store_true", help="leave summary() out (what a library without it runs)")
     a = ap.parse_args()
     from sast_amd.config import backbone_config
     from sast_amd.detection import RNNDetector, YOLOPAFPN, YOLOXHead
@@ -148,6 +151,23 @@ def main():
                  f"(at most 100 per image and category): {statistics.median(ms):.2f} ms wall (3 calls: {', '.join(f'{v:.2f}' for v in ms)}), "
                  f"= {statistics.median(ms) / t_fwd:.1f} forward calls;  AP {stats['AP']:.4f}, precision table sha256 {bits}")
     from sast_amd import _lib
+    if hasattr(_lib.lib(), "sast_evsum_accumulate") and not a.no_summary:
+        ms_sum, ms_both = [], []
+        for _ in range(3):
+            t0 = time.perf_counter()
+            ev.evaluate_buffer(*HW)
+            t1 = time.perf_counter()
+            full = ev.summary()
+            t2 = time.perf_counter()
+            ms_sum.append((t2 - t1) * 1e3)
+            ms_both.append((t2 - t0) * 1e3)
+        tabs = ev.coco_eval()
+        bits_s = hashlib.sha256(b"".join(tabs[k].cpu().numpy().tobytes() for k in ("precision", "recall", "scores"))).hexdigest()[:16]
+        same = bool(torch.equal(tabs["precision"][..., 2], ev.precision())) and all(full[k] == stats[k] for k in stats)
+        lines.append(f"summary() behind it (maxDets 1 / 10 / 100: precision, recall and score tables, twelve stats, per class; its host copy "
+                     f"included): {statistics.median(ms_sum):.2f} ms wall (3 calls: {', '.join(f'{v:.2f}' for v in ms_sum)});  evaluate_buffer + "
+                     f"summary(): {statistics.median(ms_both):.2f} ms;  AR_1 {full['AR_1']:.4f}, AR_10 {full['AR_10']:.4f}, AR_100 "
+                     f"{full['AR_100']:.4f}, tables sha256 {bits_s}" + (" (maxDets-100 slice and first six equal evaluate_buffer's)" if same else ""))
     lines.append(f"library {_lib.loaded_path() if not _lib.is_product_library() else 'in-tree product'}; knobs read: {_lib.knobs()}")
     if hasattr(_lib.lib(), "sast_evmerge_append"):
         del ev
