@@ -29,6 +29,26 @@
  *    operand tensor a GEMM reads -- activations, weights, incoming gradients, the tensor a row gather reads from -- spans less than
  *    2^31 bytes from its base pointer (rows x row stride x 4; index-contiguous operands: 64 rows more).  The loaders address operands
  *    with 32-bit byte offsets; a call with a larger operand returns -22 before anything is enqueued.  (B = 32 at 1 Mpx reaches 629 MB.)
+ *
+ * Non-finite values (pinned by tests/test_nonfinite_operators.py on the recipes of tests/nonfinite_cases.py, and by the NaN / Inf tests
+ * of tests/test_optim_operators.py and tests/test_act_operators.py)
+ *  - what a call is told to ignore is never read into a result: the tokens a selection does not keep (sast_mswsa_*: every kept row and
+ *    every parameter gradient but d(norm1.weight) -- an unkept row leaves the layer as LN1(x), so its own output row, its dx and that
+ *    one gradient carry whatever it holds), the rows under the mask token, the samples a gather does not select, a reset does not flag
+ *    or a commit does not move.  A zeroed state is exact zeros whatever it held, NaN included; data movement is bit for bit.
+ *  - samples are independent outside batch-statistics BatchNorm: a NaN or Inf in one sample of x reaches the outputs and the input
+ *    gradients of that sample only (conv + BatchNorm in eval mode, downsample + LayerNorm, the depth-wise conv, the ConvLSTM), and inside
+ *    a sample only the pixels whose window holds it.  In training mode the batch statistics carry it to every row, as in torch.
+ *  - it is not swallowed either: every result that depends on the poisoned value is non-finite, parameter gradients included.  A NaN
+ *    in a gradient reaches the parameter: sast_adamw* clip by value like torch's clamp_ (NaN stays NaN, +-Inf clips to +-clip), so p, m
+ *    and v turn NaN there instead of taking a finite step of -clip.  The clamps of the gate activations (relu, relu6, hard_sigmoid,
+ *    hard_swish, hard_mish) keep NaN as torch's do.
+ *  - where the expression itself multiplies a non-finite value by an exact zero the result may be NaN or clean: the weight-gradient
+ *    rows of the ConvLSTM that an absent state skips, a weight-gradient tap that only meets padding.  An Inf in a GEMM operand may
+ *    surface as NaN where fp32 arithmetic would give Inf or a saturated gate: the operand split computes Inf - Inf.
+ *  - not covered: kernels whose control flow follows float values (STP scoring -> selection, the YOLOX loss / SimOTA, NMS, the
+ *    evaluator, the event, label and augment kernels) expect finite input.  sast_nzratio* / sast_input_prep* pool with fmaxf, which
+ *    ignores a NaN pixel where max_pool2d counts it; event tensors are integer counts.
  */
 #ifndef SAST_HIP_H
 #define SAST_HIP_H

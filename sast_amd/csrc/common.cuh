@@ -199,21 +199,25 @@ constexpr int GLU_ACT_COUNT = 14;
 constexpr int GLU_ACT_PRELU = 13;
 constexpr float SELU_ALPHA = 1.6732632423543772848170429916717f, SELU_SCALE = 1.0507009873554804934193349852946f;
 __device__ __forceinline__ float softplus_t20(float x) { return x > 20.0f ? x : log1pf(expf(x)); }      // F.softplus(beta 1, threshold 20)
+// clamp to [lo, hi] that keeps NaN, like torch's clamp / relu / hardtanh: both compares are false for a NaN, which falls through.  fminf /
+// fmaxf return the OTHER operand for a NaN one (IEEE minNum / maxNum), so a clamp written with them turns NaN into a bound.  hi = INFINITY:
+// a one-sided clamp (the second compare folds away)
+__device__ __forceinline__ float clamp_keep_nan(float v, float lo, float hi) { return v < lo ? lo : (v > hi ? hi : v); }
 __device__ __forceinline__ float glu_act(float g, int act, float a = 0.0f) {
   switch (act) {
     case GLU_ACT_PRELU: return g > 0.0f ? g : a * g;
-    case 1: return fmaxf(g, 0.0f);
+    case 1: return clamp_keep_nan(g, 0.0f, INFINITY);
     case 2: return g * sigmoid_hw(g);
     case 3: return sigmoid_hw(g);
     case 4: return tanh_hw(g);
     case 5: return g * tanh_hw(softplus_t20(g));
-    case 6: return fminf(fmaxf(g, 0.0f), 6.0f);
+    case 6: return clamp_keep_nan(g, 0.0f, 6.0f);
     case 7: return g > 0.0f ? g : 0.01f * g;
     case 8: return g > 0.0f ? g : expm1f(g);
     case 9: return SELU_SCALE * (g > 0.0f ? g : SELU_ALPHA * expm1f(g));
-    case 10: return fminf(fmaxf(g + 3.0f, 0.0f), 6.0f) / 6.0f;
-    case 11: return g * fminf(fmaxf(g + 3.0f, 0.0f), 6.0f) / 6.0f;
-    case 12: return 0.5f * g * fminf(fmaxf(g + 2.0f, 0.0f), 2.0f);
+    case 10: return clamp_keep_nan(g + 3.0f, 0.0f, 6.0f) / 6.0f;
+    case 11: return g * clamp_keep_nan(g + 3.0f, 0.0f, 6.0f) / 6.0f;
+    case 12: return 0.5f * g * clamp_keep_nan(g + 2.0f, 0.0f, 2.0f);
     default: return gelu_erf(g);
   }
 }

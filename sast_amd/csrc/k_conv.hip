@@ -358,7 +358,7 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     float gr = gp[k] * gscale;
-    if (clip > 0.f) gr = fminf(fmaxf(gr, -clip), clip);
+    if (clip > 0.f) gr = clamp_keep_nan(gr, -clip, clip);      // clamp_ of clip_grad_value_: a NaN gradient reaches m, v and p
     pp[k] *= 1.f - lr * wd;
     mp[k] = b1 * mp[k] + omb1 * gr;
     vp[k] = b2 * vp[k] + omb2 * gr * gr;

@@ -23,6 +23,8 @@ eps there, m and v stay 0).  Sizes n = 4 (one float4), 1020 (a partial block of 
   onecycle-late      max_lr 2e-4 over 400 000 steps, the step counter preset to 399 990, 8 steps; p0 = 0 (the lr is 2e-8 there: any other
                      p0 would swallow the update); both bias corrections are 1 in float32
 """
+import sys
+
 import torch
 
 import operator_sweep as SW
@@ -139,6 +141,46 @@ def run_fused(case, inp, device):
         if first is None:
             first = (fp.flat.clone(), opt.m.clone(), opt.v.clone())
     return quantities(inp["p0"], first, (fp.flat, opt.m, opt.v)), opt.lr_step.detach().cpu()
+
+
+# ------------------------------------------------------------------------------------------------ non-finite gradients
+# torch clips by value with clamp_, which keeps NaN; IEEE fminf / fmaxf return the other operand and would turn a NaN gradient into an
+# update of -clip that leaves m and v finite.  Three cases (no clip, clip after the scale, the schedule on the device) with NaN, +Inf and
+# -Inf written over a few elements of the SECOND gradient: the first float4 (all three in one vector), the first float4 of the second
+# block and the last float4 -- which at these sizes is, or lies in, the partial last block.  None is a multiple of 7 (the exact zeros).
+NONFINITE_NAMES = ("plain", "clipscale", "onecycle")
+NONFINITE_STEP = 1          # index into inp["grads"]: optimizer step 2
+
+
+def nonfinite_gradients(case, inp):
+    """(the inputs with the poisoned second gradient, {index: the value written there})"""
+    n, vals = case["n"], (float("nan"), float("inf"), -float("inf"))
+    last = [i for i in range(n - 4, n) if i % 7][-3:]
+    where = dict(zip([1, 2, 3] + last, vals + vals))
+    where[257] = vals[0]
+    assert len(last) == 3 and all(i % 7 and 0 < i < n for i in where) and n - 4 >= (n - 1) // 1024 * 1024 and (n // 4) % 256
+    grads = [g.clone() for g in inp["grads"]]
+    for i, val in where.items():
+        grads[NONFINITE_STEP][i] = val
+    return dict(inp, grads=grads), where
+
+
+def check_nonfinite(case, got, ref, where, bounds):
+    """the non-finite mask of every quantity equals the float64 reference's (empty after the first step; after the last every poisoned
+    element, but the +-Inf ones of a clipping case, which clip to +-clip); every other element passes the case's `check`"""
+    hit = torch.zeros(case["n"], dtype=torch.bool)
+    hit[[i for i, val in where.items() if not (case["clip"] > 0 and val == val)]] = True
+    assert bool(hit.any())
+    for q in QUANTITIES:
+        bad = ~torch.isfinite(ref[q])
+        assert torch.equal(bad, hit if "@" not in q else torch.zeros_like(hit)), (case["id"], q, bad.nonzero().view(-1).tolist())
+        mine = ~torch.isfinite(got[q])
+        assert torch.equal(mine, bad), f"{case['id']}: {q} is non-finite at {mine.nonzero().view(-1).tolist()}, the reference at {bad.nonzero().view(-1).tolist()}"
+        if "@" not in q and "rel:m" in q:       # where a value is defined it is the reference's: NaN stays NaN, an infinite moment keeps its sign
+            inf = bad & ~torch.isnan(ref[q])
+            assert torch.equal(torch.isnan(got[q]), torch.isnan(ref[q])) and torch.equal(got[q][inf].double(), ref[q][inf].double())
+    keep = ~hit
+    SW.check(sys.modules[__name__], case, {q: got[q][keep] for q in QUANTITIES}, {q: ref[q][keep] for q in QUANTITIES}, bounds)
 
 
 BOUNDS_CASES = ALL_CASES

@@ -91,6 +91,34 @@ def test_function(case, dev, bounds, tools, references):
     check(AC, case, got, ref, bounds, bit_equal=AC.bit_equal(case, r32))
 
 
+# ------------------------------------------------------------------------------------------------ NaN and the infinities
+def test_functions_at_nan_and_the_infinities(dev, bounds, tools):
+    """NaN, +Inf and -Inf through all 14 activation codes and the helpers (rsqrt_hw aside: its callers pass a variance plus eps) against
+    torch in float64: NaN where torch gives NaN (a clamp written with fminf / fmaxf returns the bound instead), non-finite where torch is
+    non-finite, and where torch is finite (a saturated gate, the clamps at an infinity) the same value within the case's `out:y@tail`
+    bound.  The derivatives are not compared at these points: torch's own conventions at NaN are not uniform."""
+    pts = torch.tensor([float("nan"), float("inf"), -float("inf")])
+    misses = []
+    for case in AC.ALL_CASES:
+        if case["fn"] == "rsqrt_hw":
+            continue
+        want, _dy = AC.evaluate_reference(case, pts.double())
+        y, _dy = run_case(tools, case, {"g": pts}, dev)
+        e32, med = bounds["cases"][case["id"]]["out:y@tail"], bounds["operators"][case["op"]]["out:y@tail"]["median"]
+        tol = min(SW.project_bar("out:y@tail"), SW.FACTOR * max(e32, med))
+        for g, a, b in zip(pts.tolist(), y.tolist(), want.tolist()):
+            print(f"{case['id']:24s} g = {g!r:5}  y = {a!r}  torch {b!r}")
+            if b != b:
+                ok = a != a
+            elif abs(b) == float("inf"):
+                ok = a == b
+            else:
+                ok = abs(a - b) <= tol
+            if not ok:
+                misses.append(f"{case['id']} at {g!r}: {a!r}, torch gives {b!r}")
+    assert not misses, "\n  ".join(misses)
+
+
 # ------------------------------------------------------------------------------------------------ refusals
 def test_entry_points_refuse_codes_outside_their_tables(dev, tools):
     from sast_amd import functional as SF

@@ -38,6 +38,20 @@ def test_fused_adamw(case, dev, bounds):
     assert float(zero.abs().max()) == 0.0 and float(got["rel:v"][::7].abs().max()) == 0.0       # a zero gradient leaves the moments at zero
 
 
+NONFINITE_CASES = [c for c in OC.ALL_CASES if c["name"] in OC.NONFINITE_NAMES]
+
+
+@pytest.mark.parametrize("case", NONFINITE_CASES, ids=ids(NONFINITE_CASES))
+def test_fused_adamw_carries_a_nonfinite_gradient_into_the_parameter(case, dev, bounds):
+    """NaN, +Inf and -Inf in the second gradient (first float4, second block, last float4): the non-finite elements of the update and of
+    both moments are the float64 reference's after the first and the last step -- a clip by fminf / fmaxf would turn the NaN into an
+    update of -clip and leave m and v finite -- and every other element stays inside the case's bounds"""
+    inp, where = OC.nonfinite_gradients(case, OC.make_inputs(case))
+    got, lr_step = OC.run_fused(case, inp, dev)
+    OC.check_nonfinite(case, got, OC.reference(case, inp, torch.float64), where, bounds)
+    assert float(lr_step[1]) == case["t0"] + case["steps"]
+
+
 def _three_modules(dev):
     torch.manual_seed(3)
     return [torch.nn.Linear(5, 3).to(dev), torch.nn.Linear(7, 2).to(dev), torch.nn.Linear(3, 3, bias=False).to(dev)]

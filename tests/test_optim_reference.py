@@ -83,6 +83,25 @@ def test_cpu_branch_of_fused_adamw_meets_the_rule_of_the_gpu_run(cid, bounds):
     assert float(lr_step[1]) == case["t0"] + case["steps"]
 
 
+@pytest.mark.parametrize("name", OC.NONFINITE_NAMES)
+def test_cpu_branch_of_fused_adamw_carries_a_nonfinite_gradient_into_the_parameter(name, bounds):
+    """the rule of the GPU run's non-finite test on the torch-ops branch, and on torch.optim.AdamW with clip_grad_value_ (clamp_ keeps NaN)"""
+    case = next(c for c in OC.ALL_CASES if c["name"] == name)
+    inp, where = OC.nonfinite_gradients(case, OC.make_inputs(case))
+    assert {v != v or v for v in where.values()} == {True, math.inf, -math.inf} and {1, 2, 3, 257, case["n"] - 1} <= set(where)
+    ref = OC.reference(case, inp, torch.float64)
+    got, _lr_step = OC.run_fused(case, inp, torch.device("cpu"))
+    OC.check_nonfinite(case, got, ref, where, bounds)
+    want = OC.quantities(inp["p0"], *_torch_adamw(case, inp))
+    for q in OC.QUANTITIES:
+        assert torch.equal(torch.isfinite(want[q]), torch.isfinite(ref[q])), q       # (torch's lerp_ turns an infinite moment into NaN a step later)
+    swallowed = {q: t.clone() for q, t in got.items()}      # what a clip that drops NaN leaves behind: refused
+    for q in ("rel:dp", "rel:m", "rel:v"):
+        swallowed[q][list(where)] = 0.0
+    with pytest.raises(AssertionError, match="non-finite at"):
+        OC.check_nonfinite(case, swallowed, ref, where, bounds)
+
+
 def test_case_table_covers_what_the_sweep_is_about():
     cs = OC.ALL_CASES
     assert {c["n"] for c in cs} == {4, 1020, 1028, 3076} and all(c["op"] == "adamw" for c in cs)
