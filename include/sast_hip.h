@@ -1244,6 +1244,78 @@ typedef struct {
 } SastDetLogArgs;
 int sast_detlog_append(const SastDetLogArgs* a, sast_stream_t stream);
 
+/* ---- track ids for the exported detections (csrc/k_track.hip): a greedy IoU tracker without a motion model, one launch per online
+ * step, between sast_detections_export and sast_detlog_append.  The reference has no tracker: the rule below is this project's own,
+ * pinned by the sequential model tests/tracker_model.py; parity with any external tracker is not claimed.
+ * State per stream s (device memory, the caller's): T = max_tracks slots -- ids int32 [S, T] (0: a free slot), box fp32 [S, T, 4]
+ * (x, y, w, h), cls int32 [S, T], last_t int64 [S, T], hits int32 [S, T]; a FREE slot is zero in all five -- next_id int32 [S] (1 at
+ * the start) and counters int32 [4], ACCUMULATED: 0 detections that found no free slot, 1 runs cut by max_det (sast_tracker_run),
+ * 2 unsorted rows (sast_tracker_run), 3 reserved.
+ * One step of row s, in this order:
+ *   1 reset    reset[s] != 0: every slot of the row is freed and next_id[s] = 1, whether or not the row is due.
+ *   2 due      due[s] == 0: nothing else of the row is read or written.  Otherwise t = ends[s], m = clamp(counts[s], 0, max_det); only
+ *              the first m records of the row are read.
+ *   3 expire   a live slot with t - last_t > max_age_us (int64, no wrap-around) is freed; a t that went backwards expires nothing.
+ *   4 pairs    (live slot i, detection j) with equal class id (any class with class_agnostic != 0) is a candidate when its IoU passes:
+ *              fp32, one rounding per operation (the file is built with -ffp-contract=off, the division is the correctly rounded one):
+ *              ax2 = ax + aw, ay2, bx2, by2 likewise; iw = max(0, min(ax2, bx2) - max(ax, bx)), ih likewise, min and max giving NaN
+ *              when either side is NaN; inter = iw * ih; uni = aw * ah + bw * bh - inter (left to right); iou = inter / uni if
+ *              uni > 0, else 0; candidate if and only if iou >= iou_thre is true.  A box with a NaN is never a candidate.
+ *   5 match    greedy over the candidates in the strict total order (IoU descending, detection index ascending, slot ascending): the
+ *              first remaining pair is taken, its slot and its detection leave.  Matched slot: box := the detection's (x, y, w, h),
+ *              last_t := t, hits += 1 (cls stays).  Matched record: its track_id word (offset 28) := ids[s, i].
+ *   6 birth    the unmatched detections in index order: class_confidence >= new_score_thre and a free slot left (slots freed in 3
+ *              count) -> the lowest free slot gets ids = next_id[s]++, hits = 1 and the detection's box, class and t, and the record the
+ *              id; class_confidence >= new_score_thre and no free slot -> track_id = 0 and counter 0 is raised; otherwise (a NaN
+ *              confidence too) track_id = 0 and nothing is counted.
+ *   7 nothing else: unmatched live slots stay as they are (only time frees them), no other byte of a record and nothing at or past
+ *              record m is touched.
+ * Ids are unique within a row between two resets; wrap-around after 2^31 births is not handled.
+ * The kernel does not run min(T, m) dependent argmax rounds: the order is strict, so the greedy matching equals repeated rounds in which
+ * every live slot and every detection pick their best remaining candidate (one 64-bit maximum over the key IoU bits | ~detection |
+ * ~slot) and the pairs that chose each other are fixed.  IoUs are recomputed, not kept: LDS holds 32 bytes per detection (box, class,
+ * best key, match) and 40 per slot.  One workgroup of 256 threads per stream.
+ * sast_tracker_step: 1 launch, no allocation, no synchronisation.  sast_tracker_run: whole recordings, records int32 [S, Dcap, 10] with
+ * the first n[s] (int64, clamped to [0, Dcap]) of a row valid and sorted by t.  Every row starts from the reset state (its table is
+ * cleared first, also when the row is then refused), a step is a maximal run of equal t, the runs are walked in order under the rule
+ * above and the final table is left behind: the result is what sast_tracker_step gives on the same runs one call at a time.  A run
+ * longer than max_det: its records past the first max_det get track_id = 0 and counter 1 is raised once.  A row whose t decreases
+ * anywhere keeps every track_id word it had and raises counter 2.  1 launch, one workgroup per row.
+ * Refused on the host (SAST_EINVAL, no launch): null pointers (reset may be), S outside 1 .. 65535, max_tracks outside 1 ..
+ * SAST_TRACK_MAX_TRACKS, max_det outside 1 .. SAST_TRACK_MAX_DET (32 bytes of LDS per detection: 56 KiB), max_tracks * max_det >
+ * SAST_TRACK_MAX_PAIRS (the pairs one round of the matching sweeps), iou_thre not in (0, 1], a NaN new_score_thre, max_age_us < 0,
+ * records or last_t not 8-byte aligned, box not 16-byte aligned (a slot's box moves as one 16-byte word), Dcap < 1 or
+ * S * Dcap > 2^31 - 1. */
+#define SAST_TRACK_MAX_TRACKS 128
+#define SAST_TRACK_MAX_DET 1792
+#define SAST_TRACK_MAX_PAIRS 65536
+typedef struct {
+  int32_t* ids;            /* [S, max_tracks] */
+  float* box;              /* [S, max_tracks, 4] */
+  int32_t* cls;            /* [S, max_tracks] */
+  int64_t* last_t;         /* [S, max_tracks] */
+  int32_t* hits;           /* [S, max_tracks] */
+  int32_t* next_id;        /* [S] */
+  int32_t* counters;       /* [4], ACCUMULATED */
+  int32_t S, max_tracks, max_det, class_agnostic;
+  float iou_thre, new_score_thre;
+  int64_t max_age_us;
+} SastTrackerArgs;
+typedef struct {
+  uint8_t* records;        /* [S, max_det, 40] of one step (sast_detections_export's), 8-byte aligned */
+  const int32_t* counts;   /* [S] */
+  const int64_t* ends;     /* [S] */
+  const uint8_t* due;      /* [S] */
+  const uint8_t* reset;    /* [S] or NULL */
+} SastTrackStepArgs;
+typedef struct {
+  int32_t* records;        /* [S, Dcap, 10], 8-byte aligned */
+  const int64_t* n;        /* [S] */
+  int64_t Dcap;
+} SastTrackRunArgs;
+int sast_tracker_step(const SastTrackerArgs* tr, const SastTrackStepArgs* step, sast_stream_t stream);
+int sast_tracker_run(const SastTrackerArgs* tr, const SastTrackRunArgs* run, sast_stream_t stream);
+
 /* ---- tuning knobs.  Every SAST_* environment variable the library reads (tile / split / launch-shape choices, all defaulting to the
  * measured-best setting: DESIGN.md section 7) goes through one registry: the value is read from the environment at first use and cached;
  * sast_config_reload() makes every call site re-read its knob at its next use (a host that sets os.environ inside the process calls

@@ -7,6 +7,11 @@ device which of each stream's next windows are due, the detector runs a FIXED nu
 keep their recurrent state -- so S cameras whose windows fall due at different moments share one batch, and the whole push is one
 sequence of launches that does not depend on the data: it can be captured in a graph.
 
+The records can leave with track ids: with `tracker=` a `tracking.DetectionTracker` (csrc/k_track.hip: a greedy IoU tracker, this
+project's own rule -- the reference has none) every step runs one more launch between the record export and the log, which writes the
+`track_id` word of the exported records in place; the log, the pinned slots and `poll()` then carry the ids.  Without one every byte is
+what it was: `track_id = 0`.
+
 There is no CPU path: CPU tensors raise the library's "no CPU fallback" error.
 """
 from __future__ import annotations
@@ -23,6 +28,7 @@ from . import functional as SF
 from .events import EventQueue
 from .functional import _need_gpu, _stream
 from .labels import BBOX_DTYPE
+from .tracking import DetectionTracker
 
 RECORD_BYTES = L.DET_RECORD_BYTES
 assert BBOX_DTYPE.itemsize == RECORD_BYTES
@@ -120,10 +126,14 @@ class DetectionLog:
 
 
 class OnlineDetector:
-    """od = OnlineDetector(detector, queue, windows_per_step=W, max_det=100, conf_thre=0.1, nms_thre=0.45, first_end_us=None, log=None)
+    """od = OnlineDetector(detector, queue, windows_per_step=W, max_det=100, conf_thre=0.1, nms_thre=0.45, first_end_us=None, log=None,
+    tracker=None)
       detector: a `YoloXDetector` in eval mode; queue: an `EventQueue` with duration windows (duration_us = D) for S <= 256 streams;
       first_end_us: the end of every recording's first window (default D, must be >= D); log: a `DetectionLog` for the same S
-      streams: every step then appends its exported records to it, inside the push (and its graph) -- one more launch per step.
+      streams: every step then appends its exported records to it, inside the push (and its graph) -- one more launch per step;
+      tracker: a `tracking.DetectionTracker` for the same S streams and at least max_det records: every step then writes the track_id of
+      its exported records, in front of the log, inside the push (and its graph) -- one more launch per step.  The tracker follows `reset`;
+      its counters are read from the tracker (`tracker.errors()`).
     od.push(x, y, p, t, counts, reset=None, final=None) / od.push_dat(records, counts, reset=None, final=None) /
     od.push_evt3(words, counts, reset=None, final=None) / od.push_evt2(words, counts, reset=None, final=None, version="2.0")
       the chunk of `EventQueue.push` / `push_dat` / `push_evt3` (raw EVT 3.0 sensor words, counts in words) / `push_evt2` (raw EVT 2.0
@@ -140,7 +150,8 @@ class OnlineDetector:
 
     One push, whatever the data: queue push (2 launches; 4 for push_evt3 / push_evt2, the decode in front); `zero_samples_dev` of the held states
     by `reset`; the schedule (1 launch) -> ends, due [W, S]; `queue.frames(ends)` (7 launches); then for k < W the detector forward on
-    frames[k] with the held states, `commit_samples_dev(held, new, due[k])`, `postprocess_padded` and the record export.  A row whose
+    frames[k] with the held states, `commit_samples_dev(held, new, due[k])`, `postprocess_padded`, the record export and, where given,
+    the tracker's step and the log's append (1 launch each).  A row whose
     window k is not due runs on the frame of the last window it gave and its new (h, c) is dropped, so its state is bit for bit what
     it was.  More than W due windows of a row stay in `backlog` and come out of the following pushes (an empty chunk will do).
     Results: ends, due, counts and records lie in one device buffer that one asynchronous copy moves into one of two pinned host slots,
@@ -151,7 +162,8 @@ class OnlineDetector:
     per-call tensors of the detector are taken."""
 
     def __init__(self, detector, queue: EventQueue, windows_per_step: int, max_det: int = 100, conf_thre: float = 0.1, nms_thre: float = 0.45,
-                 first_end_us: Optional[int] = None, class_agnostic: bool = False, log: Optional[DetectionLog] = None):
+                 first_end_us: Optional[int] = None, class_agnostic: bool = False, log: Optional[DetectionLog] = None,
+                 tracker: Optional[DetectionTracker] = None):
         if not isinstance(queue, EventQueue):
             raise ValueError("sast_amd.online: queue must be a sast_amd.events.EventQueue")
         if queue.mode != L.EVENT_WINDOW_DURATION or queue.value < 1:
@@ -172,6 +184,9 @@ class OnlineDetector:
         if log is not None and (not isinstance(log, DetectionLog) or log.num_streams != self.S):
             raise ValueError(f"sast_amd.online: log must be a DetectionLog for the queue's {self.S} streams")
         self.log = log
+        if tracker is not None and (not isinstance(tracker, DetectionTracker) or tracker.num_streams != self.S or tracker.max_det < self.max_det):
+            raise ValueError(f"sast_amd.online: tracker must be a DetectionTracker for the queue's {self.S} streams and max_det >= {self.max_det}")
+        self.tracker = tracker
         self.num_classes = int(detector.yolox_head.num_classes)
         self.conf_thre, self.nms_thre, self.class_agnostic = float(conf_thre), float(nms_thre), bool(class_agnostic)
         self.states = None                 # [(h, c)] per stage: the held recurrent states
@@ -228,6 +243,8 @@ class OnlineDetector:
             SF.commit_samples_dev(held, [t for s in new for t in s], self.due[k])
             det, n_det = SF.postprocess_padded(out, self.num_classes, self.conf_thre, self.nms_thre, self.class_agnostic)
             export_detections(det, n_det, self.ends[k], self.due[k], self.records[k], self.counts[k], self.truncated)
+            if self.tracker is not None:                          # a push is one recording step per row: `reset` acts once, at its first step
+                self.tracker.step(self.records[k], self.counts[k], self.ends[k], self.due[k], reset if k == 0 else None)
             if self.log is not None:
                 self.log.append(self.records[k], self.counts[k])
             self.predictions.append(out)
