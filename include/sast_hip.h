@@ -683,7 +683,7 @@ int sast_evq_schedule(const SastEvQueueArgs* q, int64_t* next_end, int mode, int
                           const uint8_t* reset, const uint8_t* final_flags, int64_t* ends, uint8_t* due, int64_t* backlog,
                           sast_stream_t stream);
 
-/* ---- raw sensor words (csrc/k_evt3.hip): Prophesee EVT 3.0, the 16-bit little-endian word stream IMX636 / GenX320 kits put on the
+/* ---- raw sensor words (csrc/k_evt3.hip, a format policy on the decoder driver csrc/evt_dec.cuh): Prophesee EVT 3.0, the 16-bit little-endian word stream IMX636 / GenX320 kits put on the
  * wire by default (other kits of the Gen4 family send EVT 2.0: the next section), decoded on the device into the columns sast_evqueue_push takes.  The reference has no such stage (it reads .dat / .npy
  * files, utils/evaluation/prophesee/io/); the rule below is this project's contract, and parity with the Metavision SDK's decoder is
  * unpinned (the SDK is not a dependency).  type = w >> 12, v = w & 0xFFF; per stream the state y, base_x, vpol, low, high, wraps,
@@ -808,7 +808,8 @@ size_t sast_evt2_ws_bytes(int S);
  * S * max_events > 2^31 - 1, for 2.1 chunk_words > (2^31 - 1) / 32, max_events < 1, words not aligned to its word size.  Loads are
  * 16 bytes wide when words and every row of it are 16-byte aligned.  2 launches (one summary per workgroup; fold the summaries in
  * front + decode + write, the row's last workgroup writes state, count and counters): no workgroup reads what another one writes in
- * the same launch, and nothing has to be put back for a graph replay. */
+ * the same launch, and nothing has to be put back for a graph replay.  The chunking rule and the two launches are those of
+ * sast_evt3_decode (the driver, csrc/evt_dec.cuh, is shared). */
 int sast_evt2_decode(const void* words, const int64_t* counts, int64_t chunk_words, int S, int version, const uint8_t* reset,
                      int64_t* state, void* ws, int16_t* x, int16_t* y, int16_t* p, int64_t* t, int64_t max_events, int64_t* out_counts,
                      int32_t* err, sast_stream_t stream);

@@ -18,8 +18,8 @@ binned by the logarithm of their age and accumulated over the bins), is `MixedDe
 `EventQueue` keeps the events that later windows still need on the device, so a host pushes chunks cut at arbitrary points (columns,
 Prophesee's packed Event2D records, or the raw EVT 3.0 / EVT 2.0 / EVT 2.1 words of a sensor) and gets the frames `EventStreams`
 gives for the whole recording.  `Evt3Decoder` (csrc/k_evt3.hip) and `Evt2Decoder` (csrc/k_evt2.hip) are the stateful decodes of those
-words alone; `raw_header` (host only) reads the format, the geometry and the end of a .raw file's ASCII header.  `Evt3Encoder`
-(csrc/k_evt3_enc.hip) and `Evt2Encoder` (csrc/k_evt2_enc.hip) are the way back, columns or Event2D records -> EVT 3.0 / 2.0 / 2.1
+words alone (one driver, csrc/evt_dec.cuh, and a small policy per format; here `_EventDecoder` and two subclasses); `raw_header`
+(host only) reads the format, the geometry and the end of a .raw file's ASCII header.  `Evt3Encoder` (csrc/k_evt3_enc.hip) and `Evt2Encoder` (csrc/k_evt2_enc.hip) are the way back, columns or Event2D records -> EVT 3.0 / 2.0 / 2.1
 words, and `evt3_raw_header` / `evt2_raw_header` (host only) write the header such a file starts with.
 
 There is no CPU path: CPU tensors raise the library's "no CPU fallback" error.
@@ -414,7 +414,75 @@ class EventStreams(_Windowed):
 _WORD_DTYPES = tuple(d for d in (torch.int16, getattr(torch, "uint16", None)) if d is not None)
 
 
-class Evt3Decoder:
+class _EventDecoder:
+    """what `Evt3Decoder` and `Evt2Decoder` share (the device side shares csrc/evt_dec.cuh): the buffers, the argument rules, the
+    counters and the call.  A subclass names its entry points, the width of its state, its word dtypes with the words of their
+    message and `fanout`, the events one word can give."""
+
+    DECODE_LAUNCHES = 2
+    _STATE_WORDS = _WS_BYTES = _DECODE = _dtypes = _what = fanout = None
+    _EXTRA = ()                                                      # the arguments between S and reset: EVT 2's version code
+
+    def __init__(self, num_streams: int, max_events: Optional[int] = None):
+        self.num_streams = F.stream_count(num_streams, "events")
+        if max_events is not None and int(max_events) < 1:
+            raise ValueError("sast_amd.events: max_events must be >= 1 (or None)")
+        self.max_events = None if max_events is None else int(max_events)
+        if self.max_events is not None and self.num_streams * self.max_events > 2 ** 31 - 1:
+            raise ValueError("sast_amd.events: num_streams * max_events must be below 2^31")
+        self.state = self.err = self.counts = self.x = self.y = self.p = self.t = self._ws = None
+
+    def _room(self, chunk_words: int) -> int:
+        """the staging columns one row needs for a chunk of chunk_words"""
+        return self.max_events if self.max_events is not None else max(self.fanout * chunk_words, 1)
+
+    def _buffers(self, dev, chunk_words: int):
+        S = self.num_streams
+        if self.state is None:
+            F.not_capturing("events")
+            self.state = torch.zeros(S, getattr(L, self._STATE_WORDS), dtype=torch.int64, device=dev)
+            self.err = torch.zeros(3, dtype=torch.int32, device=dev)
+            self.counts = torch.zeros(S, dtype=torch.int64, device=dev)
+            self._ws = torch.zeros(int(getattr(L.lib(), self._WS_BYTES)(S)), dtype=torch.uint8, device=dev)
+        F.lives_on("the decoder's state", self.state.device, "the call's tensors", dev, "events")
+        need = self._room(chunk_words)
+        if self.x is None or self.x.shape[1] < need:
+            F.not_capturing("events")
+            if S * need > 2 ** 31 - 1:
+                raise ValueError("sast_amd.events: num_streams * max_events must be below 2^31")
+            self.x, self.y, self.p = (torch.zeros(S, need, dtype=torch.int16, device=dev) for _ in range(3))
+            self.t = torch.zeros(S, need, dtype=torch.int64, device=dev)
+
+    def errors(self) -> Tuple[int, int, int]:
+        """(events before the first TIME_HIGH, unknown words, events dropped for lack of staging) since the last reset() (synchronises)"""
+        return F.counters(self.err, 3)
+
+    def reset(self, streams=None):
+        """new recordings, from the host: the decoder state of `streams` (default: all of them) back to zero; with streams=None the
+        counters are cleared as well"""
+        F.reset_rows((self.state,), self.err, streams, self.num_streams, "events")
+
+    def __call__(self, words: torch.Tensor, counts: torch.Tensor, reset: Optional[torch.Tensor] = None):
+        S = self.num_streams
+        F.tensor_arg(words, "words", "events", self._dtypes, (("num_streams", S), "chunk words"), self._what, empty_ok=True,
+                     dtype_error=TypeError)
+        F.counts_reset(counts, reset, S, "events")
+        chunk_words = words.shape[1]
+        if S * chunk_words > 2 ** 31 - 1 or self.fanout * chunk_words > 2 ** 31 - 1:
+            raise ValueError(f"sast_amd.events: num_streams * chunk words and {self.fanout} * chunk words must be below 2^31")
+        _need_gpu(words, counts, reset)
+        F.same_device("events", "words, counts and reset", words, counts, reset)
+        self._buffers(counts.device, chunk_words)
+        # an empty chunk has no storage: any valid device pointer will do, the kernels read no word
+        L.check(getattr(L.lib(), self._DECODE)(words.data_ptr() or self.t.data_ptr(), counts.data_ptr(), chunk_words, S, *self._EXTRA,
+                                               None if reset is None else reset.data_ptr(), self.state.data_ptr(), self._ws.data_ptr(),
+                                               self.x.data_ptr(), self.y.data_ptr(), self.p.data_ptr(), self.t.data_ptr(),
+                                               self.x.shape[1], self.counts.data_ptr(), self.err.data_ptr(), _stream()),
+                self._DECODE[len("sast_"):])
+        return self.x, self.y, self.p, self.t, self.counts
+
+
+class Evt3Decoder(_EventDecoder):
     """Prophesee EVT 3.0 sensor words -> event columns on the device (csrc/k_evt3.hip; the format table and the decode rule are in
     include/sast_hip.h and INTEGRATION.md §3b; parity with the Metavision SDK's decoder is unpinned, the SDK is not a dependency).
 
@@ -434,60 +502,8 @@ class Evt3Decoder:
     The state and the staging columns are allocated by the first un-captured call, never during capture; afterwards nothing is
     allocated and nothing synchronises.  One call is 2 launches whatever S and the sizes are."""
 
-    DECODE_LAUNCHES = 2
-
-    def __init__(self, num_streams: int, max_events: Optional[int] = None):
-        self.num_streams = F.stream_count(num_streams, "events")
-        if max_events is not None and int(max_events) < 1:
-            raise ValueError("sast_amd.events: max_events must be >= 1 (or None)")
-        self.max_events = None if max_events is None else int(max_events)
-        if self.max_events is not None and self.num_streams * self.max_events > 2 ** 31 - 1:
-            raise ValueError("sast_amd.events: num_streams * max_events must be below 2^31")
-        self.state = self.err = self.counts = self.x = self.y = self.p = self.t = self._ws = None
-
-    def _buffers(self, dev, chunk_words: int):
-        S = self.num_streams
-        if self.state is None:
-            F.not_capturing("events")
-            self.state = torch.zeros(S, L.EVT3_STATE_WORDS, dtype=torch.int64, device=dev)
-            self.err = torch.zeros(3, dtype=torch.int32, device=dev)
-            self.counts = torch.zeros(S, dtype=torch.int64, device=dev)
-            self._ws = torch.zeros(int(L.lib().sast_evt3_ws_bytes(S)), dtype=torch.uint8, device=dev)
-        F.lives_on("the decoder's state", self.state.device, "the call's tensors", dev, "events")
-        need = self.max_events if self.max_events is not None else max(12 * chunk_words, 1)
-        if self.x is None or self.x.shape[1] < need:
-            F.not_capturing("events")
-            if S * need > 2 ** 31 - 1:
-                raise ValueError("sast_amd.events: num_streams * max_events must be below 2^31")
-            self.x, self.y, self.p = (torch.zeros(S, need, dtype=torch.int16, device=dev) for _ in range(3))
-            self.t = torch.zeros(S, need, dtype=torch.int64, device=dev)
-
-    def errors(self) -> Tuple[int, int, int]:
-        """(events before the first TIME_HIGH, unknown words, events dropped for lack of staging) since the last reset() (synchronises)"""
-        return F.counters(self.err, 3)
-
-    def reset(self, streams=None):
-        """new recordings, from the host: the decoder state of `streams` (default: all of them) back to zero; with streams=None the
-        counters are cleared as well"""
-        F.reset_rows((self.state,), self.err, streams, self.num_streams, "events")
-
-    def __call__(self, words: torch.Tensor, counts: torch.Tensor, reset: Optional[torch.Tensor] = None):
-        S = self.num_streams
-        F.tensor_arg(words, "words", "events", _WORD_DTYPES, (("num_streams", S), "chunk words"), "(one EVT 3.0 word each)",
-                     empty_ok=True, dtype_error=TypeError)
-        F.counts_reset(counts, reset, S, "events")
-        chunk_words = words.shape[1]
-        if S * chunk_words > 2 ** 31 - 1 or 12 * chunk_words > 2 ** 31 - 1:
-            raise ValueError("sast_amd.events: num_streams * chunk words and 12 * chunk words must be below 2^31")
-        _need_gpu(words, counts, reset)
-        F.same_device("events", "words, counts and reset", words, counts, reset)
-        self._buffers(counts.device, chunk_words)
-        # an empty chunk has no storage: any valid device pointer will do, the kernels read no word
-        L.check(L.lib().sast_evt3_decode(words.data_ptr() or self.t.data_ptr(), counts.data_ptr(), chunk_words, S,
-                                         None if reset is None else reset.data_ptr(), self.state.data_ptr(), self._ws.data_ptr(),
-                                         self.x.data_ptr(), self.y.data_ptr(), self.p.data_ptr(), self.t.data_ptr(), self.x.shape[1],
-                                         self.counts.data_ptr(), self.err.data_ptr(), _stream()), "evt3_decode")
-        return self.x, self.y, self.p, self.t, self.counts
+    _STATE_WORDS, _WS_BYTES, _DECODE = "EVT3_STATE_WORDS", "sast_evt3_ws_bytes", "sast_evt3_decode"
+    _dtypes, _what, fanout = _WORD_DTYPES, "(one EVT 3.0 word each)", 12
 
 
 class _EventEncoder:
@@ -624,7 +640,7 @@ def _evt2_version(version) -> str:
     return version
 
 
-class Evt2Decoder:
+class Evt2Decoder(_EventDecoder):
     """Prophesee EVT 2.0 / EVT 2.1 sensor words -> event columns on the device (csrc/k_evt2.hip; the format tables and the decode rule
     are in include/sast_hip.h and INTEGRATION.md §3b; parity with the Metavision SDK's decoder is unpinned, the SDK is not a
     dependency: what is pinned is the sequential model of tests/evt2_model.py).
@@ -647,62 +663,13 @@ class Evt2Decoder:
     The state and the staging columns are allocated by the first un-captured call, never during capture; afterwards nothing is
     allocated and nothing synchronises.  One call is 2 launches whatever S and the sizes are."""
 
-    DECODE_LAUNCHES = 2
+    _STATE_WORDS, _WS_BYTES, _DECODE = "EVT2_STATE_WORDS", "sast_evt2_ws_bytes", "sast_evt2_decode"
 
     def __init__(self, num_streams: int, max_events: Optional[int] = None, version: str = "2.0"):
-        self.num_streams = F.stream_count(num_streams, "events")
         self.version = _evt2_version(version)
-        self._code, self._dtypes, self.fanout, self._what = _EVT2_VERSIONS[self.version]
-        if max_events is not None and int(max_events) < 1:
-            raise ValueError("sast_amd.events: max_events must be >= 1 (or None)")
-        self.max_events = None if max_events is None else int(max_events)
-        if self.max_events is not None and self.num_streams * self.max_events > 2 ** 31 - 1:
-            raise ValueError("sast_amd.events: num_streams * max_events must be below 2^31")
-        self.state = self.err = self.counts = self.x = self.y = self.p = self.t = self._ws = None
-
-    def _buffers(self, dev, chunk_words: int):
-        S = self.num_streams
-        if self.state is None:
-            F.not_capturing("events")
-            self.state = torch.zeros(S, L.EVT2_STATE_WORDS, dtype=torch.int64, device=dev)
-            self.err = torch.zeros(3, dtype=torch.int32, device=dev)
-            self.counts = torch.zeros(S, dtype=torch.int64, device=dev)
-            self._ws = torch.zeros(int(L.lib().sast_evt2_ws_bytes(S)), dtype=torch.uint8, device=dev)
-        F.lives_on("the decoder's state", self.state.device, "the call's tensors", dev, "events")
-        need = self.max_events if self.max_events is not None else max(self.fanout * chunk_words, 1)
-        if self.x is None or self.x.shape[1] < need:
-            F.not_capturing("events")
-            if S * need > 2 ** 31 - 1:
-                raise ValueError("sast_amd.events: num_streams * max_events must be below 2^31")
-            self.x, self.y, self.p = (torch.zeros(S, need, dtype=torch.int16, device=dev) for _ in range(3))
-            self.t = torch.zeros(S, need, dtype=torch.int64, device=dev)
-
-    def errors(self) -> Tuple[int, int, int]:
-        """(events before the first TIME_HIGH, unknown words, events dropped for lack of staging) since the last reset() (synchronises)"""
-        return F.counters(self.err, 3)
-
-    def reset(self, streams=None):
-        """new recordings, from the host: the decoder state of `streams` (default: all of them) back to zero; with streams=None the
-        counters are cleared as well"""
-        F.reset_rows((self.state,), self.err, streams, self.num_streams, "events")
-
-    def __call__(self, words: torch.Tensor, counts: torch.Tensor, reset: Optional[torch.Tensor] = None):
-        S = self.num_streams
-        F.tensor_arg(words, "words", "events", self._dtypes, (("num_streams", S), "chunk words"), self._what, empty_ok=True,
-                     dtype_error=TypeError)
-        F.counts_reset(counts, reset, S, "events")
-        chunk_words = words.shape[1]
-        if S * chunk_words > 2 ** 31 - 1 or self.fanout * chunk_words > 2 ** 31 - 1:
-            raise ValueError(f"sast_amd.events: num_streams * chunk words and {self.fanout} * chunk words must be below 2^31")
-        _need_gpu(words, counts, reset)
-        F.same_device("events", "words, counts and reset", words, counts, reset)
-        self._buffers(counts.device, chunk_words)
-        # an empty chunk has no storage: any valid device pointer will do, the kernels read no word
-        L.check(L.lib().sast_evt2_decode(words.data_ptr() or self.t.data_ptr(), counts.data_ptr(), chunk_words, S, self._code,
-                                         None if reset is None else reset.data_ptr(), self.state.data_ptr(), self._ws.data_ptr(),
-                                         self.x.data_ptr(), self.y.data_ptr(), self.p.data_ptr(), self.t.data_ptr(), self.x.shape[1],
-                                         self.counts.data_ptr(), self.err.data_ptr(), _stream()), "evt2_decode")
-        return self.x, self.y, self.p, self.t, self.counts
+        code, self._dtypes, self.fanout, self._what = _EVT2_VERSIONS[self.version]
+        self._EXTRA = (code,)
+        super().__init__(num_streams, max_events)
 
 
 class Evt2Encoder(_EventEncoder):
@@ -941,10 +908,9 @@ class EventQueue(_Windowed):
     def reset(self, streams=None):
         """new recordings, from the host: rows `streams` (default: all of them) are emptied, their carry and retirement record zeroed;
         with streams=None the error counters are cleared as well"""
-        if self.evt3 is not None:
-            self.evt3.reset(streams)
-        if self.evt2 is not None:
-            self.evt2.reset(streams)
+        for dec in (self.evt3, self.evt2):
+            if dec is not None:
+                dec.reset(streams)
         F.reset_rows((self.head, self.count, self.t_last, self.retired, self.retired_t), self.err, streams, self.num_streams, "events")
 
     def _push(self, ptrs, codes, chunk_cap, counts, reset, tensors):
@@ -969,19 +935,29 @@ class EventQueue(_Windowed):
                      "(two words per Event2D record)", empty_ok=True, dtype_error=TypeError)
         self._push([records.data_ptr()] * 4, [L.EVQUEUE_DT_DAT] * 4, records.shape[1], counts, reset, [records])
 
+    def _push_words(self, name, cls, fixed, max_events, words, counts, reset):
+        """raw words through the queue's decoder `name`, made by the first call with the parameters `fixed` and max_events, which a
+        later call may not change; then the append of `push` on its staging columns and device-side event counts"""
+        dec = getattr(self, name)
+        if dec is None:
+            dec = cls(self.num_streams, max_events, **fixed)
+            setattr(self, name, dec)
+        for key, value in fixed.items():
+            if value != getattr(dec, key):
+                raise ValueError(f"sast_amd.events: the queue's decoder was made with {key}={getattr(dec, key)!r}, got {value!r}")
+        if max_events is not None and int(max_events) != dec.max_events:
+            raise ValueError(f"sast_amd.events: the queue's decoder was made with max_events={dec.max_events}, got {max_events}")
+        F.counts_reset(counts, reset, self.num_streams, "events")
+        x, y, p, t, n = dec(words, counts, reset)
+        self.push(x, y, p, t, n, reset)
+
     def push_evt3(self, words: torch.Tensor, counts: torch.Tensor, reset: Optional[torch.Tensor] = None,
                   max_events: Optional[int] = None) -> None:
         """raw EVT 3.0 sensor words (int16 / uint16 [S, chunk_words], counts int64 [S] in WORDS) as `Evt3Decoder` takes them: the
         decode (2 launches) into the decoder's staging columns, then the append of `push` on those columns and the decoder's device-side
         event counts (2 launches).  reset[s] != 0 zeroes row s's decoder state and empties its queue row together.  max_events: the
         decoder's staging per row, fixed by the first call (default 12 * chunk_words: never drops)."""
-        if self.evt3 is None:
-            self.evt3 = Evt3Decoder(self.num_streams, max_events)
-        elif max_events is not None and int(max_events) != self.evt3.max_events:
-            raise ValueError(f"sast_amd.events: the queue's decoder was made with max_events={self.evt3.max_events}, got {max_events}")
-        F.counts_reset(counts, reset, self.num_streams, "events")
-        x, y, p, t, n = self.evt3(words, counts, reset)
-        self.push(x, y, p, t, n, reset)
+        self._push_words("evt3", Evt3Decoder, {}, max_events, words, counts, reset)
 
     def evt3_errors(self) -> Tuple[int, int, int]:
         """the decoder's counters of `push_evt3`: (events before the first TIME_HIGH, unknown words, events dropped for lack of
@@ -995,15 +971,7 @@ class EventQueue(_Windowed):
         those columns and the decoder's device-side event counts (2 launches).  reset[s] != 0 zeroes row s's decoder state and empties
         its queue row together.  version and max_events (the decoder's staging per row; default chunk_words / 32 * chunk_words: never
         drops) are fixed by the first call: a later call with another of either raises ValueError."""
-        if self.evt2 is None:
-            self.evt2 = Evt2Decoder(self.num_streams, max_events, version)
-        elif _evt2_version(version) != self.evt2.version:
-            raise ValueError(f"sast_amd.events: the queue's decoder was made with version={self.evt2.version!r}, got {version!r}")
-        elif max_events is not None and int(max_events) != self.evt2.max_events:
-            raise ValueError(f"sast_amd.events: the queue's decoder was made with max_events={self.evt2.max_events}, got {max_events}")
-        F.counts_reset(counts, reset, self.num_streams, "events")
-        x, y, p, t, n = self.evt2(words, counts, reset)
-        self.push(x, y, p, t, n, reset)
+        self._push_words("evt2", Evt2Decoder, {"version": _evt2_version(version)}, max_events, words, counts, reset)
 
     def evt2_errors(self) -> Tuple[int, int, int]:
         """the decoder's counters of `push_evt2`: (events before the first TIME_HIGH, unknown words, events dropped for lack of

@@ -268,6 +268,19 @@ def test_evt2_python_limits_of_two_to_the_31():
         Evt2Decoder(8, 2 ** 28, version=M.V21)
 
 
+def test_the_decoders_are_one_python_path_and_keep_their_fanouts():
+    """`Evt3Decoder` and `Evt2Decoder` only name their format: the buffers, the counters, the reset and the call are `_EventDecoder`'s;
+    the default staging of a row is 12, 1 and 32 events per word"""
+    from sast_amd.events import Evt2Decoder, Evt3Decoder, _EventDecoder
+    for cls in (Evt3Decoder, Evt2Decoder):
+        assert issubclass(cls, _EventDecoder)
+        assert not {"_buffers", "errors", "reset", "__call__"} & set(vars(cls))
+    decoders = (Evt3Decoder(S), Evt2Decoder(S, version=M.V20), Evt2Decoder(S, version=M.V21))
+    assert [d.fanout for d in decoders] == [12, 1, 32]
+    assert [d._room(16) for d in decoders] == [12 * 16, 16, 32 * 16]
+    assert Evt2Decoder(S, 7, version=M.V21)._room(16) == 7           # an explicit max_events is the staging
+
+
 HEADER = (b"% camera_integrator_name Prophesee\r\n% date 2023-03-29 16:37:46\n% evt 3.0\n% format EVT3;height=720;width=1280\n"
           b"% generation 4.2\n% geometry 1280x720\n% end\n")
 

@@ -262,9 +262,17 @@ def test_tracker_rejects_bad_arguments_before_any_launch():
     from sast_amd import _lib
     lib = _lib.lib()
 
+    # every call below is refused: one that passed the checks would launch a kernel on these made-up addresses
+    def step(**kw):
+        tr, st, _ru = _args(_lib, **kw)
+        return lib.sast_tracker_step(C.byref(tr), C.byref(st), None)
+
+    def run(**kw):
+        tr, _st, ru = _args(_lib, **kw)
+        return lib.sast_tracker_run(C.byref(tr), C.byref(ru), None)
+
     def both(**kw):
-        tr, st, ru = _args(_lib, **kw)
-        return lib.sast_tracker_step(C.byref(tr), C.byref(st), None), lib.sast_tracker_run(C.byref(tr), C.byref(ru), None)
+        return step(**kw), run(**kw)
 
     for name in ("ids", "box", "cls", "last_t", "hits", "next_id", "counters"):
         assert both(**{name: None}) == (-22, -22), name
@@ -273,12 +281,12 @@ def test_tracker_rejects_bad_arguments_before_any_launch():
                dict(iou_thre=1.0000001), dict(iou_thre=float("nan")), dict(new_score_thre=float("nan")), dict(max_age_us=-1)):
         assert both(**kw) == (-22, -22), kw
     for name in ("counts", "ends", "due"):
-        assert both(**{name: None})[0] == -22, name
-    assert both(n=None)[1] == -22
-    assert both(**{"SastTrackStepArgs.records": None})[0] == -22 and both(**{"SastTrackRunArgs.records": None})[1] == -22
-    assert both(**{"SastTrackStepArgs.records": 0x1004})[0] == -22 and both(**{"SastTrackRunArgs.records": 0x1004})[1] == -22
+        assert step(**{name: None}) == -22, name
+    assert run(n=None) == -22
+    assert step(**{"SastTrackStepArgs.records": None}) == -22 and run(**{"SastTrackRunArgs.records": None}) == -22
+    assert step(**{"SastTrackStepArgs.records": 0x1004}) == -22 and run(**{"SastTrackRunArgs.records": 0x1004}) == -22
     for kw in (dict(Dcap=0), dict(Dcap=-5), dict(S=3, Dcap=(2 ** 31 - 1) // 3 + 1), dict(S=1, Dcap=2 ** 31)):
-        assert both(**kw)[1] == -22, kw
+        assert run(**kw) == -22, kw
     tr, st, ru = _args(_lib)
     assert lib.sast_tracker_step(None, C.byref(st), None) == -22 and lib.sast_tracker_step(C.byref(tr), None, None) == -22
     assert lib.sast_tracker_run(None, C.byref(ru), None) == -22 and lib.sast_tracker_run(C.byref(tr), None, None) == -22
