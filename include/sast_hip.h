@@ -1077,6 +1077,42 @@ int sast_augment_frames(const uint8_t* in, uint8_t* out, const int32_t* params, 
 int sast_augment_labels(const float* labels, const int32_t* counts, const int32_t* params, int N, int B, int M, int W, float* out,
                         int32_t* counts_out, float* yolox, sast_stream_t stream);
 
+/* the same augmentation with rotation (csrc/k_rotaug.hip): flip, then rotate, then zoom-in or zoom-out, the reference's order
+ * (augmentor.py:355-363).  Named sast_rotaug_ because the sast_augment_ family is closed at the two entry points above (their set of
+ * names and SAST_AUGMENT_PARAM_WORDS are pinned by tests); the rotation parameters live in a SECOND device tensor read beside `params`:
+ * rot_params int32 [B][SAST_ROTAUG_PARAM_WORDS], frame n uses row n % B.  Words of one sample:
+ *   0 active (0 / 1)   1..4 fp32 bits of a, b, c, d (frames)   5, 6 fp32 bits of cos, sin (labels)   7 reserved
+ * A sample with active == 0 gets exactly what sast_augment_frames / sast_augment_labels give it.
+ * Frames: torchvision's tensor rotate (NEAREST, expand=False, center=None, fill=None: affine_grid + grid_sample, align_corners=False)
+ * restated with one fp32 rounding per operation.  Host, for angle_deg: r = radians(-angle_deg) in double; m = (cos r, sin r, -sin r,
+ * cos r), each rounded to fp32 once; then in fp32 a = m0 / f32(0.5 W), b = m1 / f32(0.5 W), c = m2 / f32(0.5 H), d = m3 / f32(0.5 H).
+ * Device, for pixel (y, x) of the rotated image, every operation rounded to nearest:
+ *   bx = (float)x + (0.5f - 0.5f * W),  by = (float)y + (0.5f - 0.5f * H)          (exact)
+ *   gx = (bx * a) + (by * b),  gy = (bx * c) + (by * d)                             (no FMA)
+ *   ix = (((gx + 1) * W) - 1) / 2,  iy = (((gy + 1) * H) - 1) / 2
+ *   sx = rintf(ix),  sy = rintf(iy)  (ties to even: grid_sample's nearbyint);  inside iff 0 <= sx < W && 0 <= sy < H, else the pixel is 0.
+ * It is a nearest gather: bytes are copied.  torch's own matrix product need not round the same way on every build, so the contract is
+ * this rule (tests/augment_rotation_model.py), not byte equality with torch; parity with torchvision's rotate itself is unpinned
+ * (torchvision is not a dependency).
+ * Labels: ObjectLabels.rotate_ (labels.py:210-248) after flip_lr_, before the zooms.  Host: cos, sin of angle_deg / 180 * pi in double,
+ * each rounded to fp32 once.  Device, with cx = W / 2, cy = H / 2 (integer division: NOT the frames' centre (W - 1) / 2; the reference
+ * is inconsistent here and that is kept), for each corner (X, Y) of (x | x + w, y | y + h), the sums fp32 adds:
+ *   px = X - cx,  py = Y - cy;   rx = ((cos * px) + (sin * py)) + cx;   ry = ((-sin * px) + (cos * py)) + cy
+ * then min and max over the corners, clamped to [0, W - 1] and [0, H - 1], w = x1 - x0, h = y1 - y0, the box kept iff w > 0 && h > 0.
+ * This is the plain (unfused) form torch's CPU einsum computes for small frames; for frames of 64 boxes and more torch switches to a
+ * fused form that differs by up to 1.3e-4 px. */
+#define SAST_ROTAUG_PARAM_WORDS 8
+/* in, out, params: as sast_augment_frames.  One launch for all N frames, rotated or not: out[n, c, y, x] = in[n, c, ry, W - 1 - rx] (rx
+ * without flip) with (ry, rx) the rotation map of (sy(y), sx(x)); 0 on the zoom-out border and where the rotation map leaves the frame.
+ * The source pixels of a 64 x 64 output tile are computed once and reused for its channels; per channel the box that holds them is
+ * staged in LDS (or, where it does not fit, read from global memory); no atomics, no workspace.  W a multiple of 16 takes 16-byte
+ * stores where out is 16-byte aligned and 16-byte loads where in is; anything else a byte path with the same result. */
+int sast_rotaug_frames(const uint8_t* in, uint8_t* out, const int32_t* params, const int32_t* rot_params, int N, int B, int C, int H, int W,
+                       sast_stream_t stream);
+/* as sast_augment_labels, with H (rotate_ needs the frame height) and rot_params. */
+int sast_rotaug_labels(const float* labels, const int32_t* counts, const int32_t* params, const int32_t* rot_params, int N, int B, int M, int H,
+                       int W, float* out, int32_t* counts_out, float* yolox, sast_stream_t stream);
+
 /* ---- Prophesee mAP evaluation of detections (csrc/k_eval.hip).  The reference converts every validation step's labels and detections
  * to numpy (to_prophesee, utils/evaluation/prophesee/io/box_loading.py:58-99), buffers them in PropheseeEvaluator and at epoch end runs
  * filter_boxes (io/box_filtering.py), _match_times / _to_coco_format (metrics/coco_eval.py) and pycocotools' COCOeval (bbox, useCats,

@@ -12,11 +12,10 @@
 //                        survivors compacted to the front in their order; optionally the head's (class, cx, cy, w, h) layout.
 // The per-sample parameters are read from device memory (SAST_AUGMENT_PARAM_WORDS int32 words per sample), so a captured graph is
 // replayed with new parameters by rewriting that tensor.  The host validates them; the kernels still clamp every index they form.
-#include "common.cuh"
-#include "kernels.h"
+#include "aug_map.cuh"
 
 // hipcc contracts a * b + c into an FMA by default (-ffp-contract=fast) and its __fmul_rn / __fadd_rn are plain operators, while the
-// label arithmetic below must round every product first, as the reference's separate tensor operations do: build.py compiles this
+// label arithmetic (aug_map.cuh) must round every product first, as the reference's separate tensor operations do: build.py compiles this
 // file with -ffp-contract=off (SOURCE_FLAGS)
 
 namespace sast {
@@ -25,49 +24,9 @@ namespace {
 constexpr int AUG_THREADS = 256;
 constexpr int AUG_MAX_ROWS = 16;       // output rows of one band (fewer for very wide frames: the LDS budget below)
 constexpr int AUG_LDS_BUDGET = 49152;  // bytes of dynamic LDS one workgroup may ask for
-constexpr int AUG_MAX_HW = 4096;
 constexpr int AUG_TARGET_WGS = 2048;   // channels are split across workgroups until the grid has about this many
 
-enum { AUG_NONE = 0, AUG_ZOOM_IN = 1, AUG_ZOOM_OUT = 2 };
-
-struct AugSample {
-  int flip, mode, x0, y0, wh, ww;
-};
-
-__device__ __forceinline__ AugSample aug_sample(const int* p, int H, int W) {
-  AugSample s;
-  s.flip = p[0] != 0;
-  s.mode = (p[1] == AUG_ZOOM_IN || p[1] == AUG_ZOOM_OUT) ? p[1] : AUG_NONE;
-  s.x0 = min(max(p[2], 0), W - 1);
-  s.y0 = min(max(p[3], 0), H - 1);
-  s.wh = min(max(p[4], 1), H);
-  s.ww = min(max(p[5], 1), W);
-  return s;
-}
-
-// ATen's nearest-exact source index (UpSample.h): min(int(floorf((d + 0.5f) * (float(in) / float(out)))), in - 1), all in fp32
-__device__ __forceinline__ int nearest_exact(int d, int in, int out) {
-  const float scale = __fdiv_rn((float)in, (float)out);
-  return min((int)floorf(__fmul_rn(__fadd_rn((float)d, 0.5f), scale)), in - 1);
-}
-
-// source index of output index d along one axis of length `full`; -1: the zero border of zoom-out
-__device__ __forceinline__ int axis_src(int d, int mode, int o0, int win, int full) {
-  int s = d;
-  if (mode == AUG_ZOOM_IN) {
-    const int canvas = min(win, full - o0);                  // the slice [o0 : o0 + win] is cut at the frame's edge
-    s = o0 + nearest_exact(d, canvas, full);
-  } else if (mode == AUG_ZOOM_OUT) {
-    if (d < o0 || d >= o0 + win) return -1;
-    s = nearest_exact(d - o0, full, win);
-  }
-  return min(max(s, 0), full - 1);
-}
-
-__device__ __forceinline__ int col_src(int x, const AugSample& s, int W) {
-  const int c = axis_src(x, s.mode, s.x0, s.ww, W);
-  return (c >= 0 && s.flip) ? W - 1 - c : c;
-}
+// the zoom and flip maps (aug_sample, axis_src, col_src) and the label transforms of one frame: aug_map.cuh
 
 // VEC: W is a multiple of 16 and both bases are 16-byte aligned, so every row starts on a 16-byte boundary.
 // Dynamic LDS: [column map: uint16 x Wp][staging: rows x (pitch + 16)], Wp = W rounded up to 16; the 16 bytes after each staged row
@@ -184,76 +143,11 @@ __global__ __launch_bounds__(AUG_THREADS) void aug_frames_kernel(const unsigned 
   }
 }
 
-__device__ __forceinline__ float clampf(float v, float lo, float hi) { return fminf(fmaxf(v, lo), hi); }   // ATen: min(max(v, lo), hi)
-
-// one 64-lane workgroup per label frame.  Every operation is the reference's single fp32 operation on a tensor and a scalar the host
-// rounded to fp32 once, in the reference's order, with no contraction (w = x1 - x * s rounds x * s first).
+// one 64-lane workgroup per label frame: aug_labels_frame (aug_map.cuh) without rotation
 __global__ __launch_bounds__(64) void aug_labels_kernel(const float* __restrict__ in, const int* __restrict__ counts,
                                                         const int* __restrict__ params, int B, int M, int W, float* __restrict__ out,
                                                         int* __restrict__ counts_out, float* __restrict__ yolox) {
-  const int n = blockIdx.x, lane = threadIdx.x;
-  const int* p = params + (size_t)(n % B) * SAST_AUGMENT_PARAM_WORDS;
-  const int flip = p[0] != 0;
-  const int mode = (p[1] == AUG_ZOOM_IN || p[1] == AUG_ZOOM_OUT) ? p[1] : AUG_NONE;
-  const float fx0 = (float)p[2], fy0 = (float)p[3];
-  const float lox = __int_as_float(p[8]), hix = __int_as_float(p[9]), loy = __int_as_float(p[10]), hiy = __int_as_float(p[11]);
-  const float sc = __int_as_float(p[12]), maxx = __int_as_float(p[13]), maxy = __int_as_float(p[14]);
-  const float wm1 = (float)(W - 1);
-  const int cnt = min(max(counts[n], 0), M);
-  const float* src = in + (size_t)n * M * 7;
-  float* dst = out + (size_t)n * M * 7;
-  float* dsty = yolox ? yolox + (size_t)n * M * 5 : nullptr;
-  int kept = 0;
-  for (int m0 = 0; m0 < cnt; m0 += 64) {
-    const int m = m0 + lane;
-    bool keep = m < cnt;
-    float t = 0.f, x = 0.f, y = 0.f, w = 0.f, h = 0.f, cls = 0.f, conf = 0.f;
-    if (keep) {
-      const float* r = src + (size_t)m * 7;
-      t = r[0]; x = r[1]; y = r[2]; w = r[3]; h = r[4]; cls = r[5]; conf = r[6];
-      if (flip) x = __fsub_rn(__fsub_rn(wm1, x), w);                       // labels.py:339
-      if (mode == AUG_ZOOM_IN) {                                           // labels.py:277-289
-        const float cx0 = clampf(x, lox, hix), cy0 = clampf(y, loy, hiy);
-        const float cx1 = clampf(__fadd_rn(x, w), lox, hix), cy1 = clampf(__fadd_rn(y, h), loy, hiy);
-        x = __fsub_rn(cx0, fx0);
-        y = __fsub_rn(cy0, fy0);
-        w = __fsub_rn(cx1, cx0);
-        h = __fsub_rn(cy1, cy0);
-        keep = w > 0.f && h > 0.f;
-      }
-      if (keep && mode != AUG_NONE) {                                      // scale_: labels.py:326-334
-        const float x1 = fminf(__fmul_rn(__fadd_rn(x, w), sc), maxx), y1 = fminf(__fmul_rn(__fadd_rn(y, h), sc), maxy);
-        x = __fmul_rn(x, sc);
-        y = __fmul_rn(y, sc);
-        w = __fsub_rn(x1, x);
-        h = __fsub_rn(y1, y);
-        keep = w > 0.f && h > 0.f;
-        if (mode == AUG_ZOOM_OUT) {                                        // labels.py:313-314
-          x = __fadd_rn(x, fx0);
-          y = __fadd_rn(y, fy0);
-        }
-      }
-    }
-    const unsigned long long mask = __ballot(keep);
-    if (keep) {
-      const int at = kept + __popcll(mask & ((1ull << lane) - 1ull));
-      float* r = dst + (size_t)at * 7;
-      r[0] = t; r[1] = x; r[2] = y; r[3] = w; r[4] = h; r[5] = cls; r[6] = conf;
-      if (dsty) {                                                          // labels.py:348-352
-        float* q = dsty + (size_t)at * 5;
-        q[0] = cls;
-        q[1] = __fadd_rn(x, __fmul_rn(0.5f, w));
-        q[2] = __fadd_rn(y, __fmul_rn(0.5f, h));
-        q[3] = w;
-        q[4] = h;
-      }
-    }
-    kept += __popcll(mask);
-  }
-  for (int i = kept * 7 + lane; i < M * 7; i += 64) dst[i] = 0.f;
-  if (dsty)
-    for (int i = kept * 5 + lane; i < M * 5; i += 64) dsty[i] = 0.f;
-  if (lane == 0) counts_out[n] = kept;
+  aug_labels_frame<false>(in, counts, params, nullptr, B, M, 0, W, out, counts_out, yolox);
 }
 
 }  // namespace
