@@ -1,6 +1,7 @@
 // C-ABI entry points of the SAST block: STP scoring, MS-WSA (fwd/bwd) and the ConvLSTM.
 // Each entry point enqueues a short chain of kernels on the caller's stream; the GEMMs are
 // the fp32-MFMA template of gemm.cuh with op-specific loaders / fused epilogues.
+// (The entry points of the sample gather, state reset, commit and hand-back are in k_samples.hip.)
 #include <cstdlib>
 #include "gemm_dispatch.cuh"
 #include "kernels.h"
@@ -250,61 +251,6 @@ int sast_mean_square_bwd(const float* const* x, const size_t* n, int count, cons
 int sast_mask_token_fwd(float* x, const uint8_t* mask, const float* token, const float* pos_emb, int rows, int C, int L, sast_stream_t stream) { SAST_ENTRY();
   if (!x || !mask || !token || C % 4 || L < 1) return SAST_EINVAL;
   return mask_token_fwd_launch(x, mask, token, pos_emb, rows, C, L, (hipStream_t)stream);
-}
-int sast_gather_samples(const SastSampleGather* a, sast_stream_t stream) { SAST_ENTRY();
-  if (!a || !a->out || a->n_src < 1 || a->n_src > SAST_GATHER_MAX_SRC || a->n_out < 0 || a->n_out > SAST_GATHER_MAX_OUT || a->sample_floats % 4) return SAST_EINVAL;
-  for (int j = 0; j < a->n_out; ++j) if (a->t_of[j] >= a->n_src || a->b_of[j] >= a->B || !a->src[a->t_of[j]]) return SAST_EINVAL;
-  if (a->n_out == 0) return SAST_OK;
-  return sample_gather_launch(*a, false, (hipStream_t)stream);
-}
-int sast_gather_samples_bwd(const SastSampleGather* a, sast_stream_t stream) { SAST_ENTRY();
-  if (!a || a->n_src < 1 || a->n_src > SAST_GATHER_MAX_SRC || a->n_out < 0 || a->n_out > SAST_GATHER_MAX_OUT || a->B < 1 || a->B > 256 ||
-      a->sample_floats % 4 || (a->n_out && !a->out)) return SAST_EINVAL;
-  for (int t = 0; t < a->n_src; ++t) if (!a->dsrc[t]) return SAST_EINVAL;
-  return sample_gather_launch(*a, true, (hipStream_t)stream);
-}
-int sast_zero_samples(float* x, int B, size_t sample_floats, const SastSampleMask* sel, sast_stream_t stream) { SAST_ENTRY();
-  if (!x || !sel || B < 1 || B > 256 || sample_floats % 4) return SAST_EINVAL;
-  return zero_samples_launch(x, B, sample_floats, *sel, (hipStream_t)stream);
-}
-int sast_select_table(const uint8_t* labelled, int T, int B, int n_out, int32_t* table, int32_t* slot_of, int32_t* n_sel, int32_t* err,
-                      sast_stream_t stream) { SAST_ENTRY();
-  if (!labelled || !slot_of || !n_sel || !err || T < 1 || T > SAST_GATHER_MAX_SRC || B < 1 || B > 256 || n_out < 0 ||
-      n_out > SAST_GATHER_MAX_OUT || (n_out && !table)) return SAST_EINVAL;
-  return select_table_launch(labelled, T, B, n_out, table, slot_of, n_sel, err, (hipStream_t)stream);
-}
-static bool gather_dev_ok(const SastSampleGatherDev* a) {
-  return a && a->n_src >= 1 && a->n_src <= SAST_GATHER_MAX_SRC && a->n_out >= 0 && a->n_out <= SAST_GATHER_MAX_OUT && a->B >= 1 && a->B <= 256 &&
-         a->sample_floats >= 1 && (!a->n_out || a->out);
-}
-int sast_gather_samples_dev(const SastSampleGatherDev* a, sast_stream_t stream) { SAST_ENTRY();
-  if (!gather_dev_ok(a) || (a->n_out && !a->table)) return SAST_EINVAL;
-  for (int t = 0; t < a->n_src; ++t) if (!a->src[t]) return SAST_EINVAL;      // the table is data: any timestep may be named
-  if (a->n_out == 0) return SAST_OK;
-  return sample_gather_dev_launch(*a, false, (hipStream_t)stream);
-}
-int sast_gather_samples_dev_bwd(const SastSampleGatherDev* a, sast_stream_t stream) { SAST_ENTRY();
-  if (!gather_dev_ok(a) || !a->slot_of) return SAST_EINVAL;
-  for (int t = 0; t < a->n_src; ++t) if (!a->dsrc[t]) return SAST_EINVAL;
-  return sample_gather_dev_launch(*a, true, (hipStream_t)stream);
-}
-int sast_zero_samples_dev(const SastSampleZeroDev* a, sast_stream_t stream) { SAST_ENTRY();
-  if (!a || !a->flags || a->n < 0 || a->n > SAST_ZERO_MAX_TENSORS || a->B < 1 || a->B > 256) return SAST_EINVAL;
-  for (int i = 0; i < a->n; ++i) if (!a->x[i] || !a->sample_floats[i]) return SAST_EINVAL;
-  if (a->n == 0) return SAST_OK;
-  return zero_samples_dev_launch(*a, (hipStream_t)stream);
-}
-int sast_commit_samples_dev(const SastSampleCommitDev* a, sast_stream_t stream) { SAST_ENTRY();
-  if (!a || !a->flags || a->n < 0 || a->n > SAST_ZERO_MAX_TENSORS || a->B < 1 || a->B > 256) return SAST_EINVAL;
-  for (int i = 0; i < a->n; ++i) if (!a->dst[i] || !a->src[i] || !a->sample_floats[i]) return SAST_EINVAL;
-  if (a->n == 0) return SAST_OK;
-  return commit_samples_dev_launch(*a, (hipStream_t)stream);
-}
-int sast_copy_tensors(const SastTensorCopy* a, sast_stream_t stream) { SAST_ENTRY();
-  if (!a || a->n < 0 || a->n > SAST_ZERO_MAX_TENSORS) return SAST_EINVAL;
-  for (int i = 0; i < a->n; ++i) if (!a->dst[i] || !a->src[i] || !a->floats[i]) return SAST_EINVAL;
-  if (a->n == 0) return SAST_OK;
-  return copy_tensors_launch(*a, (hipStream_t)stream);
 }
 int sast_mask_token_bwd(const float* dy, const uint8_t* mask, float* dx, float* d_token, int rows, int C, sast_stream_t stream) { SAST_ENTRY();
   if (!dy || !mask || !dx || !d_token || C % 4) return SAST_EINVAL;

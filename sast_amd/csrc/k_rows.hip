@@ -1,6 +1,7 @@
 // Row-wise (per token) HBM-bound kernels: event-tensor statistics, layout change,
 // LayerNorm family, STP weighting, column reductions.  One sub-group of GL lanes owns
 // one token row of C channels (C = 4*GL*VPL), float4 accesses, wave shuffles only.
+// (The whole-sample movers -- label-sparse gather / scatter, state reset, commit and hand-back -- are in k_samples.hip.)
 #include <cstdlib>
 #include "common.cuh"
 #include "kernels.h"
@@ -946,187 +947,6 @@ int mean_square_launch(const float* const* x, float* const* dx, const size_t* n,
   for (int t = 0; t < count; ++t) { j.x[t] = x[t]; j.dx[t] = dx ? dx[t] : nullptr; j.n[t] = n[t]; }
   if (!dx) SAST_LAUNCH(mean_square_fwd_kernel, dim3(blocks, count), dim3(1024), 0, st, j, partials);
   else SAST_LAUNCH(mean_square_bwd_kernel, dim3(blocks, count), dim3(1024), 0, st, j, g, g_stride);
-  SAST_CHECK_LAUNCH();
-  return SAST_OK;
-}
-
-// ============================================================ label-sparse sample gather (modules/utils/detection.py:24-47)
-// BackboneFeatureSelector: over the T timesteps of a sequence only the samples that carry labels are kept,
-// out = cat_t( feat_t[selected_t] ).  One launch copies every selected sample of one feature map (chunk = one sample's H*W*C
-// floats); the backward writes EVERY sample gradient of every timestep (the gathered gradient or zeros) in one launch.
-// Source / destination pointers travel by value (kernel arguments), so a captured launch keeps pointing into the graph's pool.
-__global__ __launch_bounds__(256) void gather_samples_kernel(SastSampleGather a) {
-  const int j = blockIdx.y;
-  const float* __restrict__ src = a.src[a.t_of[j]] + (size_t)a.b_of[j] * a.sample_floats;
-  float* __restrict__ dst = a.out + (size_t)j * a.sample_floats;
-  const size_t n4 = a.sample_floats / 4;
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) st4(dst + 4 * i, ld4(src + 4 * i));
-}
-__global__ __launch_bounds__(256) void scatter_samples_kernel(SastSampleGather a) {
-  const int t = blockIdx.y / a.B, b = blockIdx.y % a.B;
-  int j = -1;
-  for (int k = 0; k < a.n_out; ++k) if (a.t_of[k] == t && a.b_of[k] == b) j = k;      // block-uniform scan (n_out <= 256)
-  float* __restrict__ dst = a.dsrc[t] + (size_t)b * a.sample_floats;
-  const size_t n4 = a.sample_floats / 4;
-  if (j < 0) {
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) st4(dst + 4 * i, zero4());
-  } else {
-    const float* __restrict__ src = a.out + (size_t)j * a.sample_floats;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) st4(dst + 4 * i, ld4(src + 4 * i));
-  }
-}
-int sample_gather_launch(const SastSampleGather& a, bool backward, hipStream_t st) {
-  const size_t n4 = a.sample_floats / 4;
-  int bx = (int)((n4 + 256 * 8 - 1) / (256 * 8));
-  bx = bx < 1 ? 1 : (bx > 64 ? 64 : bx);
-  if (!backward) SAST_LAUNCH(gather_samples_kernel, dim3(bx, a.n_out), dim3(256), 0, st, a);
-  else SAST_LAUNCH(scatter_samples_kernel, dim3(bx, a.n_src * a.B), dim3(256), 0, st, a);
-  SAST_CHECK_LAUNCH();
-  return SAST_OK;
-}
-// RNNStates.reset (modules/utils/detection.py:96-130): state[selected samples] = 0, in place
-__global__ __launch_bounds__(256) void zero_samples_kernel(float* __restrict__ x, size_t sample_floats, SastSampleMask m) {
-  if (!m.sel[blockIdx.y]) return;
-  float* __restrict__ dst = x + (size_t)blockIdx.y * sample_floats;
-  const size_t n4 = sample_floats / 4;
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) st4(dst + 4 * i, zero4());
-}
-int zero_samples_launch(float* x, int B, size_t sample_floats, const SastSampleMask& m, hipStream_t st) {
-  const size_t n4 = sample_floats / 4;
-  int bx = (int)((n4 + 256 * 8 - 1) / (256 * 8));
-  bx = bx < 1 ? 1 : (bx > 64 ? 64 : bx);
-  SAST_LAUNCH(zero_samples_kernel, dim3(bx, B), dim3(256), 0, st, x, sample_floats, m);
-  SAST_CHECK_LAUNCH();
-  return SAST_OK;
-}
-
-// ============================================================ the same selection from DEVICE memory (graph replay on new label patterns)
-// The host-table kernels above carry t_of / b_of and the reset mask as kernel arguments: a captured launch replays one pattern for ever.
-// Here the pattern is data: select_table_kernel lists the flagged (timestep, sample) pairs, the gather / scatter / zero kernels read that
-// list (and the reset flags) from memory.  Only the NUMBER of rows, n_out = K, stays a launch parameter (it is the batch of the PAFPN).
-//
-// One workgroup of 1024 threads walks the n = T * B <= 8192 flags in chunks of 1024, in index order (= timestep-major, batch ascending):
-// rank of a flag = pairs before the chunk + those of the lower waves of the chunk (16 counts in LDS) + popcount of the wave's ballot
-// below the lane.
-__global__ __launch_bounds__(1024) void select_table_kernel(const uint8_t* __restrict__ labelled, int n, int B, int n_out,
-                                                            int32_t* __restrict__ table, int32_t* __restrict__ slot_of,
-                                                            int32_t* __restrict__ n_sel, int32_t* __restrict__ err) {
-  __shared__ int wave_cnt[16];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int base = 0;                                        // flagged pairs before the chunk (the same value in every thread)
-  for (int i0 = 0; i0 < n; i0 += 1024) {
-    const int i = i0 + threadIdx.x;
-    const bool f = i < n && labelled[i] != 0;
-    const unsigned long long m = __ballot(f);
-    if (lane == 0) wave_cnt[wave] = __popcll(m);
-    __syncthreads();
-    int below = 0, total = 0;
-    for (int w = 0; w < 16; ++w) {
-      const int c = wave_cnt[w];
-      below += w < wave ? c : 0;
-      total += c;
-    }
-    if (i < n) {
-      const int j = base + below + __popcll(m & ((1ull << lane) - 1ull));
-      const bool fits = f && j < n_out;
-      slot_of[i] = fits ? j : -1;
-      if (fits) {
-        const int t = i / B;
-        table[2 * j] = t;
-        table[2 * j + 1] = i - t * B;
-      }
-    }
-    base += total;
-    __syncthreads();                                   // wave_cnt is rewritten by the next chunk
-  }
-  for (int j = min(base, n_out) + (int)threadIdx.x; j < n_out; j += 1024) { table[2 * j] = -1; table[2 * j + 1] = -1; }
-  if (threadIdx.x == 0) {
-    *n_sel = base;
-    if (base > n_out) err[0] += 1;                     // pattern truncated
-    if (base < n_out) err[1] += 1;                     // under-full
-  }
-}
-int select_table_launch(const uint8_t* labelled, int T, int B, int n_out, int32_t* table, int32_t* slot_of, int32_t* n_sel, int32_t* err,
-                        hipStream_t st) {
-  SAST_LAUNCH(select_table_kernel, dim3(1), dim3(1024), 0, st, labelled, T * B, B, n_out, table, slot_of, n_sel, err);
-  SAST_CHECK_LAUNCH();
-  return SAST_OK;
-}
-
-// one row of n words, this workgroup's share (blockIdx.x of gridDim.x): dst = src, or zeros when src is null.  16-byte accesses where
-// both rows are 16-byte aligned (always, when the row length is a multiple of 4 floats), single words otherwise and for the tail.
-__device__ __forceinline__ void move_row(float* __restrict__ dst, const float* __restrict__ src, size_t n) {
-  const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x, step = (size_t)gridDim.x * 256;
-  const bool vec = ((reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(src)) & 15) == 0;     // (block-uniform; null counts as aligned)
-  const size_t n4 = vec ? n / 4 : 0;
-  if (src) {
-    for (size_t i = tid; i < n4; i += step) st4(dst + 4 * i, ld4(src + 4 * i));
-    for (size_t i = 4 * n4 + tid; i < n; i += step) dst[i] = src[i];
-  } else {
-    for (size_t i = tid; i < n4; i += step) st4(dst + 4 * i, zero4());
-    for (size_t i = 4 * n4 + tid; i < n; i += step) dst[i] = 0.f;
-  }
-}
-// Table entries and slots are DATA here: one that names no timestep / sample / row of the call moves zeros, never an address outside it.
-__global__ __launch_bounds__(256) void gather_samples_dev_kernel(SastSampleGatherDev a) {
-  const int j = blockIdx.y;
-  const int t = a.table[2 * j], b = a.table[2 * j + 1];
-  const bool ok = t >= 0 && t < a.n_src && b >= 0 && b < a.B;
-  move_row(a.out + (size_t)j * a.sample_floats, ok ? a.src[t] + (size_t)b * a.sample_floats : nullptr, a.sample_floats);
-}
-__global__ __launch_bounds__(256) void scatter_samples_dev_kernel(SastSampleGatherDev a) {
-  const int t = blockIdx.y / a.B, b = blockIdx.y % a.B;
-  const int j = a.slot_of[blockIdx.y];                 // [n_src * B]: one load per block, no scan over the rows
-  const bool ok = j >= 0 && j < a.n_out;
-  move_row(a.dsrc[t] + (size_t)b * a.sample_floats, ok ? a.out + (size_t)j * a.sample_floats : nullptr, a.sample_floats);
-}
-static inline int row_blocks(size_t sample_floats) {
-  const int bx = (int)((sample_floats / 4 + 256 * 8 - 1) / (256 * 8));
-  return bx < 1 ? 1 : (bx > 64 ? 64 : bx);
-}
-int sample_gather_dev_launch(const SastSampleGatherDev& a, bool backward, hipStream_t st) {
-  const int bx = row_blocks(a.sample_floats);
-  if (!backward) SAST_LAUNCH(gather_samples_dev_kernel, dim3(bx, a.n_out), dim3(256), 0, st, a);
-  else SAST_LAUNCH(scatter_samples_dev_kernel, dim3(bx, a.n_src * a.B), dim3(256), 0, st, a);
-  SAST_CHECK_LAUNCH();
-  return SAST_OK;
-}
-// RNNStates.reset with the flags in device memory, every state tensor in one launch: grid (share of a sample, sample, tensor)
-__global__ __launch_bounds__(256) void zero_samples_dev_kernel(SastSampleZeroDev a) {
-  if (!a.flags[blockIdx.y]) return;
-  const size_t n = a.sample_floats[blockIdx.z];
-  move_row(a.x[blockIdx.z] + (size_t)blockIdx.y * n, nullptr, n);
-}
-int zero_samples_dev_launch(const SastSampleZeroDev& a, hipStream_t st) {
-  size_t most = 0;
-  for (int i = 0; i < a.n; ++i) most = a.sample_floats[i] > most ? a.sample_floats[i] : most;
-  SAST_LAUNCH(zero_samples_dev_kernel, dim3(row_blocks(most), a.B, a.n), dim3(256), 0, st, a);
-  SAST_CHECK_LAUNCH();
-  return SAST_OK;
-}
-// the predicated commit of a batch whose rows advance at different moments (sast_amd/online.py): sample b of dst takes sample b of src
-// where flags[b] != 0.  Same grid as the reset above; the flag is read once per workgroup and the branch is workgroup-uniform.
-__global__ __launch_bounds__(256) void commit_samples_dev_kernel(SastSampleCommitDev a) {
-  if (!a.flags[blockIdx.y]) return;
-  const size_t n = a.sample_floats[blockIdx.z], off = (size_t)blockIdx.y * n;
-  move_row(a.dst[blockIdx.z] + off, a.src[blockIdx.z] + off, n);
-}
-int commit_samples_dev_launch(const SastSampleCommitDev& a, hipStream_t st) {
-  size_t most = 0;
-  for (int i = 0; i < a.n; ++i) most = a.sample_floats[i] > most ? a.sample_floats[i] : most;
-  SAST_LAUNCH(commit_samples_dev_kernel, dim3(row_blocks(most), a.B, a.n), dim3(256), 0, st, a);
-  SAST_CHECK_LAUNCH();
-  return SAST_OK;
-}
-// several whole tensors in one launch (the recurrent states handed back into the step's input tensors): grid (share, tensor)
-__global__ __launch_bounds__(256) void copy_tensors_kernel(SastTensorCopy a) {
-  move_row(a.dst[blockIdx.y], a.src[blockIdx.y], a.floats[blockIdx.y]);
-}
-int copy_tensors_launch(const SastTensorCopy& a, hipStream_t st) {
-  size_t most = 0;
-  for (int i = 0; i < a.n; ++i) most = a.floats[i] > most ? a.floats[i] : most;
-  const size_t want = (most / 4 + 256 * 8 - 1) / (256 * 8);
-  SAST_LAUNCH(copy_tensors_kernel, dim3((unsigned)(want < 1 ? 1 : (want > 256 ? 256 : want)), a.n), dim3(256), 0, st, a);
   SAST_CHECK_LAUNCH();
   return SAST_OK;
 }

@@ -50,15 +50,6 @@ int cb_apply_fwd_launch(const float* m, const float* y, const float* gamma, cons
 int cb_apply_bwd_launch(const float* dout, const float* gsum, const int* row_tok, const int* nrows_dev, int rows_max, int tps, int C,
                         float* dz, hipStream_t st, const float* rs = nullptr);
 
-int sample_gather_launch(const SastSampleGather& a, bool backward, hipStream_t st);
-int zero_samples_launch(float* x, int B, size_t sample_floats, const SastSampleMask& m, hipStream_t st);
-int select_table_launch(const uint8_t* labelled, int T, int B, int n_out, int32_t* table, int32_t* slot_of, int32_t* n_sel, int32_t* err,
-                        hipStream_t st);
-int sample_gather_dev_launch(const SastSampleGatherDev& a, bool backward, hipStream_t st);
-int zero_samples_dev_launch(const SastSampleZeroDev& a, hipStream_t st);
-int commit_samples_dev_launch(const SastSampleCommitDev& a, hipStream_t st);
-int copy_tensors_launch(const SastTensorCopy& a, hipStream_t st);
-
 // k_select.hip
 int select_launch(const float* tok, int B, int H, int W, int ph, int pw, int mode, float thr_win, float thr_tok, const SastSel* s,
                   hipStream_t st);
@@ -92,6 +83,8 @@ int mswsa_fused_fwd_launch(const SastMswsaArgs* a, const float* planes, hipStrea
 // k_eval.hip: the Prophesee mAP evaluator has no internal launchers, only the sast_eval_* entry points of include/sast_hip.h
 
 // k_labels.hip: the label front end has no internal launchers either, only the sast_labels_* entry points
+
+// k_samples.hip: nor have the whole-sample movers (label-sparse gather, state reset / commit / hand-back), only their entry points
 
 // k_sampler.hip, k_stream.hip: the random-access and the streaming sampler have none either, only sast_rnd_* / sast_stream_*
 

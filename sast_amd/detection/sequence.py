@@ -40,15 +40,7 @@ class BackboneFeatureSelector:
     def get_batched_backbone_features(self) -> Optional[Dict[int, torch.Tensor]]:
         if len(self.features) == 0:
             return None
-        out = {}
-        for k, items in self.features.items():
-            xs, idx = [v for v, _ in items], [i for _, i in items]
-            nchw = xs[0].dim() == 4 and not xs[0].is_contiguous() and xs[0].permute(0, 2, 3, 1).is_contiguous()
-            if nchw:      # logical NCHW over channels-last storage: gather the NHWC buffers, hand back the same kind of view
-                out[k] = SF.as_nchw_view(SF.gather_samples([SF.as_nhwc(x) for x in xs], idx))
-            else:
-                out[k] = SF.gather_samples(xs, idx)
-        return out
+        return {k: SF.gather_samples([v for v, _ in items], [i for _, i in items]) for k, items in self.features.items()}
 
 
 class DeviceFeatureSelector:

@@ -1554,61 +1554,29 @@ def cat2(a, b):
     return _Cat2.apply(a, b)
 
 
-# ---------------------------------------------------------------------------------------------- (f)2 label-sparse gather
-class _GatherSamples(torch.autograd.Function):
-    """out = cat_t(x_t[idx_t]) over the timesteps of a sequence (BackboneFeatureSelector, modules/utils/detection.py:24-47)."""
-
-    @staticmethod
-    def forward(ctx, table, *xs):
-        _need_gpu(*xs)
-        xs = tuple(x.contiguous() for x in xs)
-        B = xs[0].shape[0]
-        sample = xs[0][0].numel()
-        if any(x.shape != xs[0].shape or x.dtype != torch.float32 for x in xs):
-            raise RuntimeError("sast_amd: gather_samples needs fp32 tensors of one shape (one feature map over the timesteps)")
-        if len(xs) > 32 or len(table) > 256 or B > 256 or sample % 4:
-            raise RuntimeError("sast_amd: gather_samples supports <= 32 timesteps, <= 256 selected samples, batch <= 256")
-        out = torch.empty((len(table),) + tuple(xs[0].shape[1:]), device=xs[0].device)
-        a = L.SastSampleGather()
-        a.n_src, a.n_out, a.B, a.sample_floats, a.out = len(xs), len(table), B, sample, out.data_ptr()
-        for t, x in enumerate(xs):
-            a.src[t] = x.data_ptr()
-        for j, (t, b) in enumerate(table):
-            a.t_of[j], a.b_of[j] = t, b
-        L.check(L.lib().sast_gather_samples(C.byref(a), _stream()), "gather_samples")
-        ctx.table, ctx.meta = table, (len(xs), B, sample, tuple(xs[0].shape))
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        n_src, B, sample, shape = ctx.meta
-        dout = dout.contiguous()
-        dxs = tuple(torch.empty(shape, device=dout.device) for _ in range(n_src))
-        a = L.SastSampleGather()
-        a.n_src, a.n_out, a.B, a.sample_floats, a.out = n_src, len(ctx.table), B, sample, dout.data_ptr()
-        for t, d in enumerate(dxs):
-            a.dsrc[t] = d.data_ptr()
-        for j, (t, b) in enumerate(ctx.table):
-            a.t_of[j], a.b_of[j] = t, b
-        L.check(L.lib().sast_gather_samples_bwd(C.byref(a), _stream()), "gather_samples_bwd")
-        return (None,) + dxs
+# ---------------------------------------------------------------------------------------------- (f)2 whole-sample movers (csrc/k_samples.hip)
+def _dense_fp32(x: torch.Tensor, B: Optional[int] = None) -> bool:
+    """what the sample movers take: a dense fp32 tensor, contiguous or channels-last 4-D (a sample is one chunk of memory either way);
+    with B, the batch of B non-empty samples as its outermost dimension"""
+    ok = x.dtype == torch.float32 and (x.is_contiguous() or (x.dim() == 4 and x.permute(0, 2, 3, 1).is_contiguous()))
+    return ok and (B is None or (x.dim() >= 2 and x.shape[0] == B and x[0].numel() >= 1))
 
 
-def gather_samples(xs, indices) -> torch.Tensor:
-    """xs: the feature map of T timesteps, each (B, ...) fp32; indices: per timestep the list of selected batch indices (unique
-    within a timestep, may be empty) -> (sum_t len(indices[t]), ...) = torch.cat([x[idx] for x, idx in zip(xs, indices) if idx])."""
-    table = tuple((t, int(b)) for t, idx in enumerate(indices) for b in idx)
-    for t, idx in enumerate(indices):
-        if len(set(int(b) for b in idx)) != len(idx):
-            raise RuntimeError("sast_amd: gather_samples needs unique batch indices per timestep")
-    return _GatherSamples.apply(table, *xs)
+def _same_layout(d: torch.Tensor, s: torch.Tensor) -> bool:
+    return s.dtype == d.dtype and d.shape == s.shape and d.stride() == s.stride()
+
+
+def _per_launch(*lists):
+    """the lists cut alike into runs of what one argument struct holds (16 tensors), each run as a list of tuples"""
+    for i0 in range(0, len(lists[0]), L.ZERO_MAX_TENSORS):
+        yield list(zip(*(x[i0:i0 + L.ZERO_MAX_TENSORS] for x in lists)))
 
 
 @torch.no_grad()
 def zero_samples(x: torch.Tensor, indices_or_bool=None) -> torch.Tensor:
     """RNNStates.recursive_reset (modules/utils/detection.py:96-116): x[indices_or_bool] = 0 in place (all samples when None)."""
     _need_gpu(x)
-    if x.dtype != torch.float32 or not (x.is_contiguous() or x.permute(0, 2, 3, 1).is_contiguous()):
+    if not _dense_fp32(x):
         raise RuntimeError("sast_amd: zero_samples needs a dense fp32 tensor with the batch as its outermost dimension")
     B = x.shape[0]
     m = L.SastSampleMask()
@@ -1685,27 +1653,43 @@ def _gather_dev_args(sel: SelectionTable, n_src: int, B: int, sample: int):
     return a
 
 
-class _GatherSamplesDev(torch.autograd.Function):
-    """_GatherSamples with the (timestep, sample) table read from device memory when the kernels run"""
+def _gather_args(pairs, n_src: int, B: int, sample: int):
+    """the argument struct of a gather over `pairs` -- the host tuple of (timestep, sample), or a SelectionTable -- and the name of its
+    entry points (sast_<name>, sast_<name>_bwd)"""
+    if isinstance(pairs, SelectionTable):
+        return _gather_dev_args(pairs, n_src, B, sample), "gather_samples_dev"
+    a = L.SastSampleGather()
+    a.n_src, a.n_out, a.B, a.sample_floats = n_src, len(pairs), B, sample
+    for j, (t, b) in enumerate(pairs):
+        a.t_of[j], a.b_of[j] = t, b
+    return a, "gather_samples"
+
+
+class _GatherSamples(torch.autograd.Function):
+    """out = cat_t(x_t[idx_t]) over the timesteps of a sequence (BackboneFeatureSelector, modules/utils/detection.py:24-47).  `pairs` is the
+    host tuple of (t, b), a kernel argument, or a SelectionTable, read from device memory when the kernels run."""
 
     @staticmethod
-    def forward(ctx, sel, *xs):
+    def forward(ctx, pairs, *xs):
+        on_device = isinstance(pairs, SelectionTable)
+        name = "gather_samples_dev" if on_device else "gather_samples"
         _need_gpu(*xs)
         xs = tuple(x.contiguous() for x in xs)
-        if any(x.shape != xs[0].shape or x.dtype != torch.float32 for x in xs) or xs[0].dim() < 2:
-            raise RuntimeError("sast_amd: gather_samples_dev needs fp32 tensors of one shape (one feature map over the timesteps)")
-        if len(xs) > 32 or xs[0].shape[0] > 256 or xs[0][0].numel() < 1:
-            raise RuntimeError("sast_amd: gather_samples_dev supports <= 32 timesteps, <= 256 selected samples, batch <= 256")
-        if any(x.device != sel.device for x in xs):
-            raise RuntimeError(f"sast_amd: the selection table lives on {sel.device}, the feature maps on {xs[0].device}")
+        if any(x.shape != xs[0].shape or x.dtype != torch.float32 for x in xs) or (on_device and xs[0].dim() < 2):
+            raise RuntimeError(f"sast_amd: {name} needs fp32 tensors of one shape (one feature map over the timesteps)")
         B, sample = xs[0].shape[0], xs[0][0].numel()
-        a = _gather_dev_args(sel, len(xs), B, sample)
-        out = torch.empty((sel.n_out,) + tuple(xs[0].shape[1:]), device=xs[0].device)
-        a.out = _ptr(out) if sel.n_out else None
+        n_out = pairs.n_out if on_device else len(pairs)
+        if len(xs) > 32 or B > 256 or (sample < 1 if on_device else (n_out > 256 or sample % 4)):
+            raise RuntimeError(f"sast_amd: {name} supports <= 32 timesteps, <= 256 selected samples, batch <= 256")
+        if on_device and any(x.device != pairs.device for x in xs):
+            raise RuntimeError(f"sast_amd: the selection table lives on {pairs.device}, the feature maps on {xs[0].device}")
+        a, name = _gather_args(pairs, len(xs), B, sample)
+        out = torch.empty((n_out,) + tuple(xs[0].shape[1:]), device=xs[0].device)
+        a.out = _ptr(out) if n_out else None
         for t, x in enumerate(xs):
             a.src[t] = x.data_ptr()
-        L.check(L.lib().sast_gather_samples_dev(C.byref(a), _stream()), "gather_samples_dev")
-        ctx.sel, ctx.meta = sel, (len(xs), B, sample, tuple(xs[0].shape))
+        L.check(getattr(L.lib(), "sast_" + name)(C.byref(a), _stream()), name)
+        ctx.pairs, ctx.meta = pairs, (len(xs), B, sample, tuple(xs[0].shape))
         return out
 
     @staticmethod
@@ -1713,25 +1697,42 @@ class _GatherSamplesDev(torch.autograd.Function):
         n_src, B, sample, shape = ctx.meta
         dout = dout.contiguous()
         dxs = tuple(torch.empty(shape, device=dout.device) for _ in range(n_src))
-        a = _gather_dev_args(ctx.sel, n_src, B, sample)
-        a.out = _ptr(dout) if ctx.sel.n_out else None
+        a, name = _gather_args(ctx.pairs, n_src, B, sample)
+        a.out = _ptr(dout) if dout.shape[0] else None
         for t, d in enumerate(dxs):
             a.dsrc[t] = d.data_ptr()
-        L.check(L.lib().sast_gather_samples_dev_bwd(C.byref(a), _stream()), "gather_samples_dev_bwd")
+        L.check(getattr(L.lib(), f"sast_{name}_bwd")(C.byref(a), _stream()), name + "_bwd")
         return (None,) + dxs
+
+
+def _gather_views(pairs, xs) -> torch.Tensor:
+    """the gather of feature maps that may be logical NCHW tensors over channels-last storage: those are gathered as their NHWC buffers
+    and come back as the same kind of view"""
+    xs = list(xs)
+    x0 = xs[0]
+    if x0.dim() == 4 and not x0.is_contiguous() and x0.permute(0, 2, 3, 1).is_contiguous():
+        return as_nchw_view(_GatherSamples.apply(pairs, *[as_nhwc(x) for x in xs]))
+    return _GatherSamples.apply(pairs, *xs)
+
+
+def gather_samples(xs, indices) -> torch.Tensor:
+    """xs: the feature map of T timesteps, each (B, ...) fp32; indices: per timestep the list of selected batch indices (unique
+    within a timestep, may be empty) -> (sum_t len(indices[t]), ...) = torch.cat([x[idx] for x, idx in zip(xs, indices) if idx]).
+    Logical NCHW tensors over channels-last storage come back as the same kind of view."""
+    table = tuple((t, int(b)) for t, idx in enumerate(indices) for b in idx)
+    for t, idx in enumerate(indices):
+        if len(set(int(b) for b in idx)) != len(idx):
+            raise RuntimeError("sast_amd: gather_samples needs unique batch indices per timestep")
+    return _gather_views(table, xs)
 
 
 def gather_samples_dev(xs, sel: SelectionTable) -> torch.Tensor:
     """gather_samples with the pairs of `sel` (a SelectionTable updated for these T = len(xs) timesteps): (sel.n_out, ...), row j =
     xs[table[j].t][table[j].b], rows behind n_sel zero; the backward writes the gradient of every sample of every timestep (unselected:
-    zeros).  One launch each way.  Logical NCHW tensors over channels-last storage come back as the same kind of view."""
+    zeros).  One launch each way."""
     if not isinstance(sel, SelectionTable):
         raise TypeError(f"sast_amd: gather_samples_dev needs a SelectionTable, got {type(sel).__name__}")
-    xs = list(xs)
-    x0 = xs[0]
-    if x0.dim() == 4 and not x0.is_contiguous() and x0.permute(0, 2, 3, 1).is_contiguous():
-        return as_nchw_view(_GatherSamplesDev.apply(sel, *[as_nhwc(x) for x in xs]))
-    return _GatherSamplesDev.apply(sel, *xs)
+    return _gather_views(sel, xs)
 
 
 @torch.no_grad()
@@ -1775,21 +1776,18 @@ def zero_samples_dev(tensors, flags: torch.Tensor):
     if not tensors:
         return tensors
     B = tensors[0].shape[0]
-    for x in tensors:
-        if x.dtype != torch.float32 or x.dim() < 2 or x.shape[0] != B or x[0].numel() < 1 or \
-                not (x.is_contiguous() or (x.dim() == 4 and x.permute(0, 2, 3, 1).is_contiguous())):
-            raise RuntimeError("sast_amd: zero_samples_dev needs dense fp32 tensors with the same batch as their outermost dimension")
+    if not all(_dense_fp32(x, B) for x in tensors):
+        raise RuntimeError("sast_amd: zero_samples_dev needs dense fp32 tensors with the same batch as their outermost dimension")
     if B > 256:
         raise RuntimeError("sast_amd: zero_samples_dev supports batch <= 256")
     _check_flags(flags, B, "zero_samples_dev")
     _need_gpu(flags, *tensors)
     if any(x.device != flags.device for x in tensors):
         raise ValueError("sast_amd: zero_samples_dev needs the tensors and the flags on one device")
-    for i0 in range(0, len(tensors), L.ZERO_MAX_TENSORS):
+    for chunk in _per_launch(tensors):
         a = L.SastSampleZeroDev()
-        chunk = tensors[i0:i0 + L.ZERO_MAX_TENSORS]
         a.n, a.B, a.flags = len(chunk), B, flags.data_ptr()
-        for i, x in enumerate(chunk):
+        for i, (x,) in enumerate(chunk):
             a.x[i], a.sample_floats[i] = x.data_ptr(), x[0].numel()
         L.check(L.lib().sast_zero_samples_dev(C.byref(a), _stream()), "zero_samples_dev")
     return tensors
@@ -1807,20 +1805,17 @@ def commit_samples_dev(dsts, srcs, flags: torch.Tensor):
     if not dsts:
         return dsts
     B = dsts[0].shape[0]
-    for d, s in zip(dsts, srcs):
-        if d.dtype != torch.float32 or s.dtype != torch.float32 or d.dim() < 2 or d.shape[0] != B or d[0].numel() < 1 or d.shape != s.shape or \
-                d.stride() != s.stride() or not (d.is_contiguous() or (d.dim() == 4 and d.permute(0, 2, 3, 1).is_contiguous())):
-            raise RuntimeError("sast_amd: commit_samples_dev needs pairs of dense fp32 tensors with one shape and memory layout and the same "
-                               "batch as their outermost dimension")
+    if not all(_dense_fp32(d, B) and _same_layout(d, s) for d, s in zip(dsts, srcs)):
+        raise RuntimeError("sast_amd: commit_samples_dev needs pairs of dense fp32 tensors with one shape and memory layout and the same "
+                           "batch as their outermost dimension")
     if B > 256:
         raise RuntimeError("sast_amd: commit_samples_dev supports batch <= 256")
     _check_flags(flags, B, "commit_samples_dev")
     _need_gpu(flags, *dsts, *srcs)
     if any(x.device != flags.device for x in dsts + srcs):
         raise ValueError("sast_amd: commit_samples_dev needs the tensors and the flags on one device")
-    for i0 in range(0, len(dsts), L.ZERO_MAX_TENSORS):
+    for pairs in _per_launch(dsts, srcs):
         a = L.SastSampleCommitDev()
-        pairs = list(zip(dsts[i0:i0 + L.ZERO_MAX_TENSORS], srcs[i0:i0 + L.ZERO_MAX_TENSORS]))
         a.n, a.B, a.flags = len(pairs), B, flags.data_ptr()
         for i, (d, s) in enumerate(pairs):
             a.dst[i], a.src[i], a.sample_floats[i] = d.data_ptr(), s.data_ptr(), d[0].numel()
@@ -1835,14 +1830,12 @@ def copy_tensors(dsts, srcs) -> None:
     _need_gpu(*dsts, *srcs)
     if len(dsts) != len(srcs):
         raise RuntimeError("sast_amd: copy_tensors needs as many destinations as sources")
-    for d, s in zip(dsts, srcs):
-        if d.dtype != torch.float32 or s.dtype != torch.float32 or d.shape != s.shape or d.stride() != s.stride() or d.device != s.device or \
-                d.numel() < 1 or not (d.is_contiguous() or (d.dim() == 4 and d.permute(0, 2, 3, 1).is_contiguous())):
-            raise RuntimeError("sast_amd: copy_tensors needs pairs of dense fp32 tensors with one shape and memory layout on one device")
-    for i0 in range(0, len(dsts), L.ZERO_MAX_TENSORS):
+    if not all(_dense_fp32(d) and _same_layout(d, s) and d.device == s.device and d.numel() >= 1 for d, s in zip(dsts, srcs)):
+        raise RuntimeError("sast_amd: copy_tensors needs pairs of dense fp32 tensors with one shape and memory layout on one device")
+    for pairs in _per_launch(dsts, srcs):
         a = L.SastTensorCopy()
-        a.n = len(dsts[i0:i0 + L.ZERO_MAX_TENSORS])
-        for i, (d, s) in enumerate(zip(dsts[i0:i0 + L.ZERO_MAX_TENSORS], srcs[i0:i0 + L.ZERO_MAX_TENSORS])):
+        a.n = len(pairs)
+        for i, (d, s) in enumerate(pairs):
             a.dst[i], a.src[i], a.floats[i] = d.data_ptr(), s.data_ptr(), d.numel()
         L.check(L.lib().sast_copy_tensors(C.byref(a), _stream()), "copy_tensors")
 

@@ -90,6 +90,11 @@ def test_argument_errors_without_a_gpu():
         ts.replay(key=5)
 
 
+def test_the_sample_movers_are_built():
+    from sast_amd import build as B
+    assert "k_samples.hip" in B.SOURCES and "k_samples.hip" not in B.SOURCE_FLAGS
+
+
 def _three_steps(fs):
     for _ in range(3):
         fs.add_backbone_features({2: torch.zeros(4, 8)})
@@ -276,6 +281,98 @@ def test_zero_samples_dev_equals_zero_samples(dev):
     n0 = _lib.lib().sast_launch_count()
     SF.copy_tensors(dst, src)
     assert _lib.lib().sast_launch_count() - n0 == 1 and all(torch.equal(d, s) for d, s in zip(dst, src))
+
+
+def _host_pairs_at_the_limits():
+    """32 timesteps of 256 samples, 8 pairs each = the 256 rows a host table holds, in no particular order within a timestep; (0, 0) and
+    (31, 255) are the smallest and the largest values its uint8 entries carry"""
+    rng = np.random.default_rng(256)
+    idx = [[int(b) for b in rng.permutation(256)[:8]] for _ in range(32)]
+    idx[0] = [0] + [b for b in idx[0] if b != 0][:7]
+    idx[31] = [b for b in idx[31] if b != 255][:7] + [255]
+    return idx
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("B,sample,idx", [(256, 4, None), (3, 8200, [[2, 0], []])], ids=["table-at-its-limits", "two-workgroups-per-row"])
+def test_host_table_gather_at_its_limits(dev, B, sample, idx):
+    """The host-table form (BackboneFeatureSelector -> functional.gather_samples) on the mover it shares with the device form: a full table
+    (T = 32, B = 256, n_out = 256, 4 floats per sample) and rows of 8200 floats (two workgroups each; the second timestep has no pair and
+    takes no part, so its gradient is None).  Forward against torch.cat([x[idx]]), backward against torch autograd of that expression,
+    unselected gradients exactly zero, one launch each way."""
+    from sast_amd import _lib
+    from sast_amd.detection.sequence import BackboneFeatureSelector
+    idx = _host_pairs_at_the_limits() if idx is None else idx
+    g = torch.Generator().manual_seed(B)
+    xs_cpu = [torch.randn(B, sample, generator=g) for _ in idx]
+    xs = [x.to(dev).requires_grad_(True) for x in xs_cpu]
+    ref_leaves = [x.clone().requires_grad_(True) for x in xs_cpu]
+    ref = torch.cat([x[i] for x, i in zip(ref_leaves, idx) if i])
+    hsel = BackboneFeatureSelector()
+    for x, i in zip(xs, idx):
+        if i:
+            hsel.add_backbone_features({1: x}, i)
+    count = _lib.lib().sast_launch_count
+    n0 = count()
+    out = hsel.get_batched_backbone_features()[1]
+    assert count() - n0 == 1
+    assert torch.equal(out.cpu(), ref)
+    w = torch.randn(ref.shape, generator=g)
+    w_dev = w.to(dev)
+    n0 = count()
+    out.backward(w_dev)
+    assert count() - n0 == 1
+    ref.backward(w)
+    for t, i in enumerate(idx):
+        if not i:
+            assert xs[t].grad is None and ref_leaves[t].grad is None, t
+            continue
+        assert torch.equal(xs[t].grad.cpu(), ref_leaves[t].grad), t
+        assert float(xs[t].grad[[b for b in range(B) if b not in i]].abs().sum()) == 0.0, t
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("sample", [4, 8200])
+def test_host_zero_samples_at_the_largest_batch(dev, sample):
+    """functional.zero_samples at B = 256 with the first and the last sample flagged, by bool mask and by the index list [0, -1] (indices
+    are taken modulo B), one and two workgroups per sample: against torch indexing, one launch per call"""
+    from sast_amd import _lib, functional as SF
+    B = 256
+    x_cpu = torch.randn(B, sample, generator=torch.Generator().manual_seed(sample))
+    ref = x_cpu.clone()
+    ref[[0, B - 1]] = 0
+    mask = torch.zeros(B, dtype=torch.bool)
+    mask[0] = mask[B - 1] = True
+    for which in (mask, [0, -1]):
+        x = x_cpu.to(dev)
+        n0 = _lib.lib().sast_launch_count()
+        assert SF.zero_samples(x, which) is x
+        assert _lib.lib().sast_launch_count() - n0 == 1
+        assert torch.equal(x.cpu(), ref)
+    assert float(ref[1:B - 1].abs().min()) > 0.0                               # (the unflagged samples are still there)
+
+
+@pytest.mark.gpu
+def test_host_forms_still_refuse_samples_that_are_no_multiple_of_4_floats(dev):
+    """the host-table entry points share the device form's row mover, which takes any row; their own contract (sample_floats % 4 == 0)
+    stands: functional.gather_samples / zero_samples raise as before, the C entry points return an error, and nothing is launched"""
+    import ctypes as C
+    from sast_amd import _lib, functional as SF
+    x = torch.randn(4, 7, device=dev)
+    n0 = _lib.lib().sast_launch_count()
+    with pytest.raises(RuntimeError, match="gather_samples supports"):
+        SF.gather_samples([x, x], [[0, 1], [3]])
+    with pytest.raises(RuntimeError, match="zero_samples failed"):
+        SF.zero_samples(x.clone(), [0])
+    out, dx = torch.zeros(1, 7, device=dev), torch.zeros(4, 7, device=dev)
+    a = _lib.SastSampleGather()
+    a.n_src, a.n_out, a.B, a.sample_floats, a.out = 1, 1, 4, 7, out.data_ptr()
+    a.src[0], a.dsrc[0] = x.data_ptr(), dx.data_ptr()
+    assert _lib.lib().sast_gather_samples(C.byref(a), None) != 0
+    assert _lib.lib().sast_gather_samples_bwd(C.byref(a), None) != 0
+    torch.cuda.synchronize()
+    assert _lib.lib().sast_launch_count() == n0
+    assert float(out.abs().sum()) == 0.0 and float(dx.abs().sum()) == 0.0
 
 
 @pytest.mark.gpu

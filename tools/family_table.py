@@ -12,7 +12,7 @@ FAM = [("fused MS-WSA layer kernels (stage 1: forward, weight planes)", r"mswsa_
        ("selection (scores -> keep masks -> compaction)", r"select_"),
        ("ConvLSTM pointwise backward", r"lstm_"),
        ("input: non_zero_ratio + cast + pad + NCHW->NHWC", r"nzr_|nchw_|input_prep"),
-       ("upsample+concat, slices, sample gather", r"upsample|slice_copy|gather_samples|scatter_samples|zero_samples|select_table|copy_tensors"),
+       ("upsample+concat, slices, sample gather", r"upsample|slice_copy|gather_samples|scatter_samples|zero_samples|commit_samples|move_samples|select_table|copy_tensors"),
        ("AdamW + gradient clear", r"adamw|FillFunctor"),
        ("objective + remaining ATen", r"mean_square|at::|reduce_kernel|multi_tensor|zero_fill")]
 t = collections.OrderedDict((n, [0, 0.0, 0.0]) for n, _ in FAM)
