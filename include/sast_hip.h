@@ -868,6 +868,74 @@ int sast_evt2enc_encode_dat(const void* records, const int64_t* counts, int64_t 
                             int64_t* state, void* ws, void* words, int64_t max_words, int64_t* n_words, int32_t* err,
                             sast_stream_t stream);
 
+/* ---- event noise filters (csrc/k_evfilter.hip): the two standard event-level filters between decode and accumulate, on the device.
+ * The rule is this project's (parity with the Metavision SDK's ActivityNoiseFilterAlgorithm / SpatioTemporalContrastAlgorithm is
+ * unpinned, the SDK is not a dependency; what is pinned is the sequential model of tests/event_filter_model.py).  Per stream row s,
+ * over the events in arrival order:
+ *   t'_i = max(t_last[s], t_0 .. t_i), the queue's running-maximum correction, carried in the filter's own t_last[s]; 0 <= t' < 2^62.
+ *   surface[s, y, x] (int64) is -1 while the pixel has seen no event since the last reset, else 2 * t'_j + (p_j > 0) of the LAST event
+ *   by arrival order at that pixel.  Every event inside the sensor writes it, kept or not: the state never depends on a decision.
+ *   SAST_EVFILTER_ACTIVITY, radius r in 1 .. 3: event i is kept iff some pixel q != (x_i, y_i) inside the sensor within Chebyshev
+ *     distance r holds, as events 0 .. i-1 left it, a value v >= 0 with t'_i - (v >> 1) <= threshold_us.  Polarity plays no part.
+ *   SAST_EVFILTER_CONTRAST: event i is kept iff its own pixel holds, as events 0 .. i-1 left it, v >= 0 with (v & 1) == (p_i > 0)
+ *     and t'_i - (v >> 1) <= threshold_us.
+ *   An event with x outside 0 .. width-1 or y outside 0 .. height-1 is never kept, writes nothing and is counted in err[0]; it still
+ *   advances t'.  The kept events leave in arrival order: x, y, p as they came (int16, p saturated), t = t'.
+ * The decision for an event depends on earlier EVENTS only, never on earlier decisions, so a chunk is decided at once: one device
+ * radix sort (rocprim) of the unique keys (row * H * W + pixel) << index_bits | flat index over the fixed capacity S * chunk_capacity
+ * (slots that hold no event inside the sensor carry the key S * H * W << index_bits | flat index and sort behind); the predecessor of
+ * event i at pixel q is a lower bound in the sorted keys, the surface from before the call where the chunk has none; the last key of
+ * each pixel's run writes the surface; the kept events are compacted per row in order.  A recording cut into calls anywhere (empty
+ * chunks included) gives the events and the state of the recording in one call. */
+enum { SAST_EVFILTER_ACTIVITY = 0, SAST_EVFILTER_CONTRAST = 1 };
+#define SAST_EVFILTER_BLOCK_EVENTS 1024 /* slots a workgroup takes in one step; a row gets ceil(chunk_capacity / this) workgroups ... */
+#define SAST_EVFILTER_MAX_BLOCKS 256    /* ... at most this many, which then take several steps each */
+#define SAST_EVFILTER_LAUNCHES 4        /* the library's own launches of one call; the radix sort's passes come on top */
+typedef struct SastEvFilterArgs {
+  int64_t* surface;         /* int64 [S, height, width]: -1, or 2 * t' + pbit of the pixel's last event */
+  int64_t* t_last;          /* int64 [S]: the time-correction carry */
+  int64_t* seen;            /* int64 [S]: events taken in, cumulative (those outside the sensor included) */
+  int64_t* kept;            /* int64 [S]: events kept, cumulative */
+  int32_t* err;             /* int32 [1], ACCUMULATED: [0] events outside the sensor */
+  void* ws;                 /* sast_evfilter_ws_bytes(S, chunk_capacity, height, width) bytes or more, 8-byte aligned */
+  size_t ws_bytes;
+  int16_t* x;               /* the kept events, [S, out_capacity] from column 0 on */
+  int16_t* y;
+  int16_t* p;
+  int64_t* t;
+  int64_t* out_counts;      /* int64 [S]: the kept events of this call */
+  int64_t out_capacity;     /* >= chunk_capacity */
+  int64_t threshold_us;     /* 0 .. 2^62 - 1 */
+  int32_t S;                /* 1 .. 65535 */
+  int32_t height;           /* 1 .. 32767 */
+  int32_t width;
+  int32_t mode;             /* SAST_EVFILTER_ACTIVITY / SAST_EVFILTER_CONTRAST */
+  int32_t radius;           /* 1 .. 3 (activity; contrast does not read it) */
+  int32_t reserved;
+} SastEvFilterArgs;
+/* bytes of the call's workspace (keys, sorted keys, surface values and keep flags of S * chunk_capacity slots, per-workgroup
+ * summaries, the radix sort's own storage).  0 for shapes the filter does not take: S outside 1 .. 65535, height or width outside
+ * 1 .. 32767, chunk_capacity < 0, S * chunk_capacity > 2^31 - 1, or keys that do not fit 63 bits.  Host only. */
+size_t sast_evfilter_ws_bytes(int S, int64_t chunk_capacity, int height, int width);
+/* per row s: with reset != NULL and reset[s] != 0 the row's surface is set to -1 and t_last[s], seen[s], kept[s] to 0 first (only
+ * the workgroups of such rows sweep their H * W words).  Then the first n_s = min(max(counts[s], 0), chunk_capacity) events of row s
+ * are filtered: x, y, p SAST_DT_I64 / I32 / I16 [S, chunk_capacity], t SAST_DT_I64 / I32.  A row with n_s == 0 and no reset flag is
+ * untouched (out_counts[s] = 0).  SAST_EINVAL before any launch: a null pointer (reset may be), a shape sast_evfilter_ws_bytes
+ * refuses, ws too small or misaligned, out_capacity < chunk_capacity or S * out_capacity > 2^31 - 1, an unknown mode or dtype, radius
+ * outside 1 .. 3, threshold_us outside 0 .. 2^62 - 1.  SAST_ELAUNCH: a launch failed.
+ * SAST_EVFILTER_LAUNCHES launches and one radix sort whose passes depend on the shapes alone (partial time maxima + reset sweep;
+ * corrected times, keys and values; the sort; decisions; compaction + surface + state).  No workgroup reads what another one writes in
+ * the same launch, every store is a plain vector store, results are bit-identical from run to run, nothing is allocated and nothing
+ * synchronises: the call replays inside a graph. */
+int sast_evfilter_apply(const SastEvFilterArgs* f, const void* x, const void* y, const void* p, const void* t, int x_dtype, int y_dtype,
+                        int p_dtype, int t_dtype, const int64_t* counts, int64_t chunk_capacity, const uint8_t* reset,
+                        sast_stream_t stream);
+/* the same from packed records: int32 [S, chunk_capacity, 2], Prophesee's Event2D as sast_evqueue_push takes it with
+ * SAST_EVQUEUE_DT_DAT (t the unsigned word 0, x = w & 16383, y = (w >> 14) & 16383, p = (w >> 28) & 1 of word 1); records 8-byte
+ * aligned. */
+int sast_evfilter_apply_dat(const SastEvFilterArgs* f, const void* records, const int64_t* counts, int64_t chunk_capacity,
+                            const uint8_t* reset, sast_stream_t stream);
+
 /* ---- label front end (csrc/k_labels.hip): the raw Prophesee box records of S recordings side by side -> the filtered labels, the
  * label-frame timestamps, the window-end schedule, the frame -> window map and per-step label tensors, all on the device.  The reference
  * does this offline, per recording: apply_filters, get_base_delta_ts_for_labels_us and labels_and_ev_repr_timestamps of

@@ -17,7 +17,7 @@ LIB = os.path.join(HERE, "libsast_hip.so")
 TOOLS_LIB = os.path.join(HERE, "libsast_hip_tools.so")
 BF16_LIB = os.path.join(HERE, "libsast_hip_bf16.so")
 ARCH = "gfx950"
-SOURCES = ["k_rows.hip", "k_select.hip", "k_attn_mfma.hip", "k_mswsa_fused.hip", "k_block.hip", "k_samples.hip", "k_conv.hip", "k_dwconv.hip", "k_prof.hip", "k_head.hip", "k_config.hip", "k_events.hip", "k_augment.hip", "k_rotaug.hip", "k_eval.hip", "k_labels.hip", "k_sampler.hip", "k_stream.hip", "k_mixed.hip", "k_evt3.hip", "k_evt2.hip", "k_evt3_enc.hip", "k_evt2_enc.hip", "k_track.hip"]
+SOURCES = ["k_rows.hip", "k_select.hip", "k_attn_mfma.hip", "k_mswsa_fused.hip", "k_block.hip", "k_samples.hip", "k_conv.hip", "k_dwconv.hip", "k_prof.hip", "k_head.hip", "k_config.hip", "k_events.hip", "k_augment.hip", "k_rotaug.hip", "k_eval.hip", "k_labels.hip", "k_sampler.hip", "k_stream.hip", "k_mixed.hip", "k_evt3.hip", "k_evt2.hip", "k_evt3_enc.hip", "k_evt2_enc.hip", "k_track.hip", "k_evfilter.hip"]
 TOOLS_SOURCES = ["k_test.hip", "k_dma_test.hip", "k_ws_test.hip"]
 HEADERS = ["common.cuh", "gemm.cuh", "gemm_kloop.inc", "mfma_tiles.cuh", "gemm_dispatch.cuh", "kernels.h", "label_state.cuh", "sampler_rows.cuh", "evt_enc.cuh", "evt_dec.cuh", "aug_map.cuh", os.path.join("..", "..", "include", "sast_hip.h")]
 # k_augment.hip and k_rotaug.hip (aug_map.cuh) restate fp32 tensor arithmetic one rounding at a time: hipcc's default -ffp-contract=fast

@@ -20,7 +20,9 @@ Prophesee's packed Event2D records, or the raw EVT 3.0 / EVT 2.0 / EVT 2.1 words
 gives for the whole recording.  `Evt3Decoder` (csrc/k_evt3.hip) and `Evt2Decoder` (csrc/k_evt2.hip) are the stateful decodes of those
 words alone (one driver, csrc/evt_dec.cuh, and a small policy per format; here `_EventDecoder` and two subclasses); `raw_header`
 (host only) reads the format, the geometry and the end of a .raw file's ASCII header.  `Evt3Encoder` (csrc/k_evt3_enc.hip) and `Evt2Encoder` (csrc/k_evt2_enc.hip) are the way back, columns or Event2D records -> EVT 3.0 / 2.0 / 2.1
-words, and `evt3_raw_header` / `evt2_raw_header` (host only) write the header such a file starts with.
+words, and `evt3_raw_header` / `evt2_raw_header` (host only) write the header such a file starts with.  `EventFilter`
+(csrc/k_evfilter.hip) is the event-level noise filtering between decode and accumulate: the background-activity and the
+spatio-temporal-contrast filter, alone or as `EventQueue(filter=...)` in front of every push.
 
 There is no CPU path: CPU tensors raise the library's "no CPU fallback" error.
 """
@@ -726,6 +728,117 @@ def evt2_raw_header(height: int, width: int, version: str = "2.0") -> bytes:
             f"% generator sast_amd.events.Evt2Encoder\n% end\n").encode("ascii")
 
 
+FILTER_MODES = {"activity": L.EVFILTER_ACTIVITY, "contrast": L.EVFILTER_CONTRAST}
+
+
+class EventFilter:
+    """Event-level noise filters on the device, between decode and accumulate (csrc/k_evfilter.hip; the rule is in include/sast_hip.h
+    and INTEGRATION.md §3b; it is this project's: parity with the Metavision SDK's ActivityNoiseFilterAlgorithm and
+    SpatioTemporalContrastAlgorithm is unpinned, the SDK is not a dependency: what is pinned is the sequential model of
+    tests/event_filter_model.py).
+
+    f = EventFilter(num_streams, height, width, mode="activity" | "contrast", threshold_us=10_000, radius=1)
+    x, y, p, t, n = f(x, y, p, t, counts, reset=None)
+      x, y, p: int64 / int32 / int16 [S, chunk_cap], t: int64 / int32 (microseconds), the columns `EventQueue.push` takes (a decoder's
+        staging columns among them); counts: int64 [S], the events at the head of each row; reset: uint8 / bool [S], non-zero for the
+        rows that start a new recording with this chunk: surface -1, carry and the row's seen / kept 0 first.
+      -> x, y, p int16 [S, chunk_cap], t int64 [S, chunk_cap], n int64 [S] the kept events at the head of each row, in arrival order:
+        what `EventQueue.push` takes.  The tensors are the filter's staging columns: the next call overwrites them.
+    x, y, p, t, n = f.filter_dat(records, counts, reset=None)
+      records: int32 [S, chunk_cap, 2], Prophesee's packed Event2D records as `EventQueue.push_dat` takes them.
+    Per row, in arrival order: t' is the running maximum of the times from the filter's own carry `t_last` (the queue's correction, so
+    the queue's is the identity on what comes out); `surface` holds per pixel -1 or 2 * t' + (p > 0) of the last event there, kept or
+    not.  mode="activity": an event is kept iff another pixel within Chebyshev distance `radius` (1 .. 3) saw an event at most
+    threshold_us before (<=), polarity ignored.  mode="contrast": iff its own pixel's last event had the same polarity and was at most
+    threshold_us before.  Events outside the sensor are dropped and counted (`errors()`), they still advance t'.  The decision never
+    depends on an earlier decision, so a recording cut into chunks anywhere gives the events and state of the recording in one call.
+    State, device tensors allocated by the first ordinary call and never during capture: surface int64 [S, H, W], t_last int64 [S],
+    seen / kept int64 [S] (cumulative per row), err int32 [1].  `reset(streams=None)` is the host-side form of `reset`: those rows
+    (default: all, and the counter) start over.  One call is FILTER_LAUNCHES launches of the library and one device radix sort over
+    S * chunk_cap keys whose passes depend on the shapes alone; after one un-captured warm-up call with the same shapes nothing is
+    allocated and nothing synchronises, so a call can be captured in a graph.  There is no CPU fallback."""
+
+    FILTER_LAUNCHES = L.EVFILTER_LAUNCHES
+
+    def __init__(self, num_streams: int, height: int, width: int, mode: str = "activity", threshold_us: int = 10_000, radius: int = 1):
+        self.num_streams = F.stream_count(num_streams, "events")
+        if not (1 <= int(height) <= 32767 and 1 <= int(width) <= 32767):
+            raise ValueError("sast_amd.events: EventFilter gives x and y as int16: height and width must be in 1 .. 32767")
+        if mode not in FILTER_MODES:
+            raise ValueError(f"sast_amd.events: mode must be one of {tuple(FILTER_MODES)}, got {mode!r}")
+        if isinstance(threshold_us, bool) or not isinstance(threshold_us, int) or not 0 <= threshold_us < 2 ** 62:
+            raise ValueError("sast_amd.events: threshold_us must be an int in 0 .. 2^62 - 1")
+        if isinstance(radius, bool) or not isinstance(radius, int) or not 1 <= radius <= 3:
+            raise ValueError("sast_amd.events: radius must be an int in 1 .. 3")
+        self.height, self.width, self.mode, self.threshold_us, self.radius = int(height), int(width), mode, threshold_us, radius
+        self.surface = self.t_last = self.seen = self.kept = self.err = self.counts = self.x = self.y = self.p = self.t = None
+        self._ws = self._args = None
+
+    def _buffers(self, dev, chunk_cap: int):
+        S = self.num_streams
+        if self.surface is None:
+            F.not_capturing("events")
+            self.surface = torch.full((S, self.height, self.width), -1, dtype=torch.int64, device=dev)
+            self.t_last, self.seen, self.kept, self.counts = (torch.zeros(S, dtype=torch.int64, device=dev) for _ in range(4))
+            self.err = torch.zeros(1, dtype=torch.int32, device=dev)
+        F.lives_on("the filter's state", self.surface.device, "the call's tensors", dev, "events")
+        if self.x is None or self.x.shape[1] < chunk_cap:
+            F.not_capturing("events")
+            need = int(L.lib().sast_evfilter_ws_bytes(S, chunk_cap, self.height, self.width))
+            if need == 0:
+                raise ValueError(f"sast_amd.events: unsupported filter shapes (num_streams={S}, chunk capacity {chunk_cap}, "
+                                 f"{self.height}x{self.width}): the sort keys do not fit 63 bits")
+            room = max(chunk_cap, 1)
+            self.x, self.y, self.p = (torch.zeros(S, room, dtype=torch.int16, device=dev) for _ in range(3))
+            self.t = torch.zeros(S, room, dtype=torch.int64, device=dev)
+            self._ws = torch.zeros(need, dtype=torch.uint8, device=dev)
+            a = self._args = L.SastEvFilterArgs()
+            a.surface, a.t_last, a.seen, a.kept = self.surface.data_ptr(), self.t_last.data_ptr(), self.seen.data_ptr(), self.kept.data_ptr()
+            a.err, a.ws, a.ws_bytes = self.err.data_ptr(), self._ws.data_ptr(), need
+            a.x, a.y, a.p, a.t, a.out_counts = self.x.data_ptr(), self.y.data_ptr(), self.p.data_ptr(), self.t.data_ptr(), self.counts.data_ptr()
+            a.out_capacity, a.threshold_us = room, self.threshold_us
+            a.S, a.height, a.width, a.mode, a.radius = S, self.height, self.width, FILTER_MODES[self.mode], self.radius
+        return self._args
+
+    def errors(self) -> Tuple[int]:
+        """(events outside the sensor,) since the last reset() (synchronises)"""
+        return F.counters(self.err, 1)
+
+    def reset(self, streams=None):
+        """new recordings, from the host: the surface of `streams` (default: all of them) back to -1, their carry and their seen / kept
+        counts to 0; with streams=None the error counter is cleared as well"""
+        F.reset_rows((self.t_last, self.seen, self.kept), self.err, streams, self.num_streams, "events")
+        if self.surface is not None:
+            if streams is None:
+                self.surface.fill_(-1)
+            elif len(list(streams)):
+                self.surface[torch.tensor([int(s) for s in streams], dtype=torch.int64, device=self.surface.device)] = -1
+
+    def _filter(self, entry, head, chunk_cap, counts, reset, tensors):
+        S = self.num_streams
+        F.counts_reset(counts, reset, S, "events")
+        if S * chunk_cap > 2 ** 31 - 1:
+            raise ValueError("sast_amd.events: num_streams * chunk capacity must be below 2^31")
+        _need_gpu(*tensors, counts, reset)
+        F.same_device("events", "the chunk, counts and reset", *tensors, counts, reset)
+        a = self._buffers(counts.device, chunk_cap)
+        # an empty chunk has no storage: any valid device pointer will do, the kernels read no event
+        head = [h or counts.data_ptr() for h in head[:len(tensors)]] + list(head[len(tensors):])
+        L.check(getattr(L.lib(), entry)(C.byref(a), *head, counts.data_ptr(), chunk_cap, None if reset is None else reset.data_ptr(),
+                                        _stream()), entry[len("sast_"):])
+        return self.x, self.y, self.p, self.t, self.counts
+
+    def __call__(self, x: torch.Tensor, y: torch.Tensor, p: torch.Tensor, t: torch.Tensor, counts: torch.Tensor,
+                 reset: Optional[torch.Tensor] = None):
+        codes = F.event_columns(x, y, p, t, self.num_streams, "events", cap_name="chunk capacity")
+        return self._filter("sast_evfilter_apply", [c.data_ptr() for c in (x, y, p, t)] + list(codes), x.shape[1], counts, reset, [x, y, p, t])
+
+    def filter_dat(self, records: torch.Tensor, counts: torch.Tensor, reset: Optional[torch.Tensor] = None):
+        F.tensor_arg(records, "records", "events", (torch.int32,), (("num_streams", self.num_streams), "chunk capacity", 2),
+                     "(two words per Event2D record)", empty_ok=True, dtype_error=TypeError)
+        return self._filter("sast_evfilter_apply_dat", [records.data_ptr()], records.shape[1], counts, reset, [records])
+
+
 class RawHeader(NamedTuple):
     """what `raw_header` reads: format "evt2" / "evt21" / "evt3" / None, width and height (None where the header names none), offset the
     index of the first data byte, fields {key: the rest of the line} of every header line"""
@@ -804,7 +917,7 @@ _QUEUE_ERRORS = ("{} invalid events (x or y outside the sensor, or a polarity ou
 class EventQueue(_Windowed):
     """Device-resident event retention across chunks: push chunks of any size as they arrive, ask for windows as their ends pass.
 
-    q = EventQueue(num_streams, capacity, height, width, ..., duration_us=D | num_events=N)
+    q = EventQueue(num_streams, capacity, height, width, ..., duration_us=D | num_events=N, filter=None)
     q.push(x, y, p, t, counts, reset=None)      chunk columns [S, chunk_cap] (x, y, p: int64 / int32 / int16; t: int64 / int32),
                                                 counts int64 [S]: row s appends the first counts[s] events of chunk row s
     q.push_dat(records, counts, reset=None)     int32 [S, chunk_cap, 2]: Prophesee's packed Event2D records as the reference's reader
@@ -821,6 +934,11 @@ class EventQueue(_Windowed):
                                                 int32 [S, chunk_words] raw EVT 2.0 words, or with version="2.1" int64 [S, chunk_words]
                                                 raw EVT 2.1 words (`Evt2Decoder`, 2 launches in front of the append);
                                                 `evt2_errors()` gives that decoder's three counters.
+    filter: an `EventFilter` for the same streams and sensor: every push then sends its events (the decoder's staging columns and
+                                                device-side counts for raw words) through it in front of the append -- FILTER_LAUNCHES more
+                                                launches and one radix sort per push; `reset` and `reset(streams=)` reach it.  The
+                                                filter sees sensor coordinates (`downsample_by_2` happens in the frames).  None: the
+                                                queue runs the launches and gives the bytes it gives without one.
     frames = q.frames(ends_us, out=None, check=False)    ends_us int64 [S] or [T, S] -> frames as `EventStreams` returns them
     q.reset(streams=None); q.errors(); q.get_shape()
 
@@ -866,7 +984,7 @@ class EventQueue(_Windowed):
 
     def __init__(self, num_streams: int, capacity: int, height: int, width: int, bins: int = 10, count_cutoff: Optional[int] = 10,
                  fastmode: bool = True, duration_us: Optional[int] = None, num_events: Optional[int] = None, downsample_by_2: bool = False,
-                 window_capacity: Optional[int] = None, representation: str = "stacked_histogram"):
+                 window_capacity: Optional[int] = None, representation: str = "stacked_histogram", filter: Optional[EventFilter] = None):
         super().__init__(bins, height, width, count_cutoff, fastmode, downsample_by_2, representation, duration_us, num_events, True,
                          window_capacity)
         if int(height) > 32767 or int(width) > 32767:
@@ -881,6 +999,13 @@ class EventQueue(_Windowed):
         self._args = None
         self.evt3: Optional[Evt3Decoder] = None       # made by the first push_evt3
         self.evt2: Optional[Evt2Decoder] = None       # made by the first push_evt2
+        if filter is not None:
+            if not isinstance(filter, EventFilter):
+                raise TypeError(f"sast_amd.events: filter must be a sast_amd.events.EventFilter (or None), got a {type(filter).__name__}")
+            if (filter.num_streams, filter.height, filter.width) != (self.num_streams, self.height, self.width):
+                raise ValueError(f"sast_amd.events: the filter is for {filter.num_streams} streams of {filter.height}x{filter.width}, the queue "
+                                 f"for {self.num_streams} of {self.height}x{self.width}")
+        self.filter = filter
 
     def _storage(self, dev):
         """the queue's state on `dev` (allocated by the first ordinary call)"""
@@ -908,7 +1033,7 @@ class EventQueue(_Windowed):
     def reset(self, streams=None):
         """new recordings, from the host: rows `streams` (default: all of them) are emptied, their carry and retirement record zeroed;
         with streams=None the error counters are cleared as well"""
-        for dec in (self.evt3, self.evt2):
+        for dec in (self.evt3, self.evt2, self.filter):
             if dec is not None:
                 dec.reset(streams)
         F.reset_rows((self.head, self.count, self.t_last, self.retired, self.retired_t), self.err, streams, self.num_streams, "events")
@@ -927,12 +1052,17 @@ class EventQueue(_Windowed):
 
     def push(self, x: torch.Tensor, y: torch.Tensor, p: torch.Tensor, t: torch.Tensor, counts: torch.Tensor,
              reset: Optional[torch.Tensor] = None) -> None:
+        if self.filter is not None:
+            x, y, p, t, counts = self.filter(x, y, p, t, counts, reset)
         codes = F.event_columns(x, y, p, t, self.num_streams, "events", cap_name="chunk capacity")
         self._push([c.data_ptr() for c in (x, y, p, t)], codes, x.shape[1], counts, reset, [x, y, p, t])
 
     def push_dat(self, records: torch.Tensor, counts: torch.Tensor, reset: Optional[torch.Tensor] = None) -> None:
         F.tensor_arg(records, "records", "events", (torch.int32,), (("num_streams", self.num_streams), "chunk capacity", 2),
                      "(two words per Event2D record)", empty_ok=True, dtype_error=TypeError)
+        if self.filter is not None:
+            x, y, p, t, n = self.filter.filter_dat(records, counts, reset)
+            return self._push([c.data_ptr() for c in (x, y, p, t)], [L.DT_I16, L.DT_I16, L.DT_I16, L.DT_I64], x.shape[1], n, reset, [x, y, p, t])
         self._push([records.data_ptr()] * 4, [L.EVQUEUE_DT_DAT] * 4, records.shape[1], counts, reset, [records])
 
     def _push_words(self, name, cls, fixed, max_events, words, counts, reset):

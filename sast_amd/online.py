@@ -148,7 +148,8 @@ class OnlineDetector:
     od.errors() -> (invalid events, windows over capacity, dropped events, late windows, detections cut by max_det, windows due but
       not yet given after the last push) (synchronises).
 
-    One push, whatever the data: queue push (2 launches; 4 for push_evt3 / push_evt2, the decode in front); `zero_samples_dev` of the held states
+    One push, whatever the data: queue push (2 launches; 4 for push_evt3 / push_evt2, the decode in front; `EventFilter.FILTER_LAUNCHES`
+    more and the filter's radix sort with a filtered queue, `EventQueue(filter=...)`); `zero_samples_dev` of the held states
     by `reset`; the schedule (1 launch) -> ends, due [W, S]; `queue.frames(ends)` (7 launches); then for k < W the detector forward on
     frames[k] with the held states, `commit_samples_dev(held, new, due[k])`, `postprocess_padded`, the record export and, where given,
     the tracker's step and the log's append (1 launch each).  A row whose
