@@ -1421,6 +1421,82 @@ typedef struct {
 int sast_tracker_step(const SastTrackerArgs* tr, const SastTrackStepArgs* step, sast_stream_t stream);
 int sast_tracker_run(const SastTrackerArgs* tr, const SastTrackRunArgs* run, sast_stream_t stream);
 
+/* ---- tracking metrics (csrc/k_trackeval.hip): the CLEAR-MOT counts (Bernardin and Stiefelhagen) of tracked detections against labelled
+ * tracks, for S whole recordings in the record form of sast_evrec_add: gt int32 [S, Gcap, 10] / n_gt int64 [S] and dt int32
+ * [S, Dcap, 10] / n_dt int64 [S] (counts clamped to [0, cap] on the device), both sorted by t.  Word 7 of a record, track_id, is what
+ * this section reads: the label's is the ground-truth track, the detection's the hypothesis id sast_tracker_step / sast_tracker_run
+ * wrote.  The rule below is pinned by the sequential model tests/tracking_eval_model.py; parity with py-motmetrics and TrackEval is
+ * not pinned (neither is installed where this project is built).  Recordings are independent.  One recording, in this order:
+ *   1 sorted   a label or detection record whose t is below its predecessor's: the row adds nothing and word SAST_TE_UNSORTED is raised.
+ *   2 filter   both sides pass filter_boxes exactly as sast_evrec_add applies it: t > 500 000 (each record on its own t) and
+ *              w * w + h * h >= min_diag2, w >= min_side, h >= min_side (fp32, one rounding per operation).  Of the records that
+ *              pass: a detection with track_id == 0 is dropped (SAST_TE_UNTRACKED), then a record of either side with class_id >= K
+ *              is dropped (SAST_TE_BAD_CLASS).
+ *   3 frames   every unique t of the labels left is a frame.  Its hypotheses are the records left of ONE detection run (a maximal
+ *              sequence of equal t in the detection records before the filter, as in sast_tracker_run): the run whose t is nearest
+ *              the frame's, the earlier one on a tie, if |t_run - t| <= time_tol_us; no such run: no hypotheses.  On either side,
+ *              in record order, a record whose track_id an earlier record left of the frame carries is dropped (SAST_TE_DUP_GT,
+ *              SAST_TE_DUP_HYP).  A frame with more than max_labels_per_frame labels or max_hyp_per_frame hypotheses then, or a
+ *              recording with more than max_gt_tracks distinct label ids, refuses the whole row: it adds nothing and raises
+ *              SAST_TE_REFUSED_LABELS / _HYP / _TRACKS (once per row, for the first reason met).
+ *   4 valid    a pair (label o, hypothesis h) is valid when the class ids are equal (any classes with class_agnostic != 0) and
+ *              iou >= iou_thre is true, the IoU being the tracker's ("track ids", step 4: fp32, one rounding per operation, NaN never
+ *              passes; the label is the first box).  Its cost is the fp64 1.0 - (double)iou.
+ *   5 match    carry-over first, in record order of the labels: a track whose last matched hypothesis id last[o] (the last ever,
+ *              across gaps) is not 0 keeps that pair when the id is in the frame, no earlier label has kept it, and the pair is
+ *              valid.  The labels and hypotheses left are matched by the optimal assignment: of all matchings of valid pairs those
+ *              with the most pairs, of these the one with the least cost sum (where that is not unique, any of them).
+ *   6 count    per matched pair, to the label's class: matches += 1, sum_iou += (double)iou; idsw += 1 when last[o] is neither 0 nor
+ *              h; frag += 1 when o was matched before but not in the previous frame that held it; then last[o] = h.  An unmatched
+ *              label: fn += 1 (its class); an unmatched hypothesis: fp += 1 (ITS class).  gt and hyp count the labels and
+ *              hypotheses of the frames by their own class.
+ *   7 tracks   at the end, per label id with `present` frames and `matched` of them matched: mostly tracked when 5 * matched >=
+ *              4 * present, mostly lost when 5 * matched < present, partially tracked otherwise; the track's class is that of its
+ *              first record left.
+ * Output of a call: rows int64 [S, K + 1, SAST_TRACKEVAL_COLS] (the columns below; row K is the sum over the classes, and `frames`
+ * is the recording's frame count in every row), rows_iou fp64 [S, K + 1] (sum_iou; row K is rows 0 .. K - 1 added in that order) and
+ * rows_diag int64 [S, SAST_TRACKEVAL_DIAG] (the words below, per occurrence in a frame; a refused or unsorted row: its reason 1, every
+ * other word and every count 0), all overwritten; then acc, acc_iou and acc_diag, shaped like one row of each, += the rows in row order.
+ * The kernel: one workgroup of 256 threads per recording, frame after frame.  A frame's labels and hypotheses (at most 128 x 128) sit
+ * in LDS; the track table (id, class, last, present, matched, matched in the previous frame) is an open-addressing table keyed by
+ * the label's track_id in ws; the carry-over claims are settled by an LDS atomicMin of the label index; the assignment is a
+ * shortest-augmenting-path solver with fp64 potentials on one wave, two columns per lane, whose column minimum is a wave reduction
+ * and whose fp32 IoUs are recomputed (no cost matrix is held); an invalid pair costs 1e3.  2 launches, no allocation, no
+ * synchronisation.  Refused on the host (SAST_EINVAL, no launch): null or not 8-byte aligned pointers, S outside 1 .. 65535, Gcap or
+ * Dcap < 1, S * Gcap or S * Dcap > 2^31 - 257, K outside 1 .. SAST_EVAL_MAX_CLASSES, max_labels_per_frame or max_hyp_per_frame outside
+ * 1 .. SAST_TRACKEVAL_MAX_FRAME, max_gt_tracks outside 1 .. SAST_TRACKEVAL_MAX_GT_TRACKS, iou_thre not in (0, 1], time_tol_us < 0,
+ * ws_bytes < sast_trackeval_ws_bytes.  sast_trackeval_reset: acc, acc_iou and acc_diag to zero, 1 launch. */
+#define SAST_TRACKEVAL_COLS 12
+#define SAST_TRACKEVAL_DIAG 8
+#define SAST_TRACKEVAL_MAX_FRAME 128
+#define SAST_TRACKEVAL_MAX_GT_TRACKS 65536
+enum { SAST_TE_FRAMES, SAST_TE_GT, SAST_TE_HYP, SAST_TE_MATCHES, SAST_TE_FP, SAST_TE_FN, SAST_TE_IDSW, SAST_TE_FRAG, SAST_TE_GT_TRACKS,
+       SAST_TE_MT, SAST_TE_PT, SAST_TE_ML };
+enum { SAST_TE_UNSORTED, SAST_TE_REFUSED_LABELS, SAST_TE_REFUSED_HYP, SAST_TE_REFUSED_TRACKS, SAST_TE_UNTRACKED, SAST_TE_BAD_CLASS,
+       SAST_TE_DUP_GT, SAST_TE_DUP_HYP };
+typedef struct {
+  const int32_t* gt;       /* [S, Gcap, 10] */
+  const int64_t* n_gt;     /* [S] */
+  const int32_t* dt;       /* [S, Dcap, 10] */
+  const int64_t* n_dt;     /* [S] */
+  int64_t* rows;           /* [S, K + 1, SAST_TRACKEVAL_COLS] */
+  double* rows_iou;        /* [S, K + 1] */
+  int64_t* rows_diag;      /* [S, SAST_TRACKEVAL_DIAG] */
+  int64_t* acc;            /* [K + 1, SAST_TRACKEVAL_COLS], ACCUMULATED */
+  double* acc_iou;         /* [K + 1], ACCUMULATED */
+  int64_t* acc_diag;       /* [SAST_TRACKEVAL_DIAG], ACCUMULATED */
+  void* ws;                /* the track tables of one call, sast_trackeval_ws_bytes(S, max_gt_tracks) bytes; no initial contents needed */
+  size_t ws_bytes;
+  int64_t time_tol_us;
+  int32_t S, Gcap, Dcap, K;
+  int32_t max_gt_tracks, max_labels_per_frame, max_hyp_per_frame, class_agnostic;
+  float iou_thre, min_diag2, min_side;
+  int32_t reserved;
+} SastTrackEvalArgs;
+size_t sast_trackeval_ws_bytes(int S, int max_gt_tracks);   /* 0: an argument out of range.  Host only. */
+int sast_trackeval_add(const SastTrackEvalArgs* a, sast_stream_t stream);
+int sast_trackeval_reset(const SastTrackEvalArgs* a, sast_stream_t stream);
+
 /* ---- tuning knobs.  Every SAST_* environment variable the library reads (tile / split / launch-shape choices, all defaulting to the
  * measured-best setting: DESIGN.md section 7) goes through one registry: the value is read from the environment at first use and cached;
  * sast_config_reload() makes every call site re-read its knob at its next use (a host that sets os.environ inside the process calls

@@ -17,18 +17,19 @@ LIB = os.path.join(HERE, "libsast_hip.so")
 TOOLS_LIB = os.path.join(HERE, "libsast_hip_tools.so")
 BF16_LIB = os.path.join(HERE, "libsast_hip_bf16.so")
 ARCH = "gfx950"
-SOURCES = ["k_rows.hip", "k_select.hip", "k_attn_mfma.hip", "k_mswsa_fused.hip", "k_block.hip", "k_samples.hip", "k_conv.hip", "k_dwconv.hip", "k_prof.hip", "k_head.hip", "k_config.hip", "k_events.hip", "k_augment.hip", "k_rotaug.hip", "k_eval.hip", "k_labels.hip", "k_sampler.hip", "k_stream.hip", "k_mixed.hip", "k_evt3.hip", "k_evt2.hip", "k_evt3_enc.hip", "k_evt2_enc.hip", "k_track.hip", "k_evfilter.hip"]
+SOURCES = ["k_rows.hip", "k_select.hip", "k_attn_mfma.hip", "k_mswsa_fused.hip", "k_block.hip", "k_samples.hip", "k_conv.hip", "k_dwconv.hip", "k_prof.hip", "k_head.hip", "k_config.hip", "k_events.hip", "k_augment.hip", "k_rotaug.hip", "k_eval.hip", "k_labels.hip", "k_sampler.hip", "k_stream.hip", "k_mixed.hip", "k_evt3.hip", "k_evt2.hip", "k_evt3_enc.hip", "k_evt2_enc.hip", "k_track.hip", "k_evfilter.hip", "k_trackeval.hip"]
 TOOLS_SOURCES = ["k_test.hip", "k_dma_test.hip", "k_ws_test.hip"]
-HEADERS = ["common.cuh", "gemm.cuh", "gemm_kloop.inc", "mfma_tiles.cuh", "gemm_dispatch.cuh", "kernels.h", "label_state.cuh", "sampler_rows.cuh", "evt_enc.cuh", "evt_dec.cuh", "aug_map.cuh", os.path.join("..", "..", "include", "sast_hip.h")]
+HEADERS = ["common.cuh", "gemm.cuh", "gemm_kloop.inc", "mfma_tiles.cuh", "gemm_dispatch.cuh", "kernels.h", "label_state.cuh", "sampler_rows.cuh", "evt_enc.cuh", "evt_dec.cuh", "aug_map.cuh", "box_rules.cuh", os.path.join("..", "..", "include", "sast_hip.h")]
 # k_augment.hip and k_rotaug.hip (aug_map.cuh) restate fp32 tensor arithmetic one rounding at a time: hipcc's default -ffp-contract=fast
 # would fuse a * b + c;
 # k_eval.hip does the same for the box filter (fp32) and for COCOeval's IoU and precision / recall (fp64), k_labels.hip for the label
 # filters and ObjectLabelFactory (fp32) and for the label-frame walk and numpy's linspace (fp64), k_sampler.hip for the fp64 weights of
 # the weighted random sampler; k_stream.hip and k_mixed.hip (integers only) are built like k_sampler.hip, whose label state they read;
-# k_track.hip for the tracker's fp32 IoU (one rounding per operation, as tests/tracker_model.py states it)
+# k_track.hip for the tracker's fp32 IoU (one rounding per operation, as tests/tracker_model.py states it), k_trackeval.hip for the same
+# IoU and the box filter (box_rules.cuh holds both) and for the fp64 costs of its assignment
 SOURCE_FLAGS = {"k_augment.hip": ["-ffp-contract=off"], "k_rotaug.hip": ["-ffp-contract=off"], "k_eval.hip": ["-ffp-contract=off"], "k_labels.hip": ["-ffp-contract=off"],
                 "k_sampler.hip": ["-ffp-contract=off"], "k_stream.hip": ["-ffp-contract=off"], "k_mixed.hip": ["-ffp-contract=off"],
-                "k_track.hip": ["-ffp-contract=off"]}
+                "k_track.hip": ["-ffp-contract=off"], "k_trackeval.hip": ["-ffp-contract=off"]}
 FLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result"] + os.environ.get("SAST_EXTRA_FLAGS", "").split()
 
 

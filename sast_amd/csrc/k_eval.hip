@@ -32,6 +32,7 @@
 // The count and match kernels read an image's rows through a SOURCE they are parameterised on: FrameRows (padded [N, M, 7] /
 // [N, A, 7] rows, one frame per image) or RecordRows (ranges of records).  There is one matching.
 // Every fp32 / fp64 operation of the reference is repeated one rounding at a time: build.py compiles this file with -ffp-contract=off.
+#include "box_rules.cuh"
 #include "common.cuh"
 #include "kernels.h"
 
@@ -52,7 +53,6 @@ constexpr int EV_M = SAST_EVSUM_MAXDETS;      // 3: maxDets 1, 10, 100
 constexpr unsigned long long EV_LANE_MASK = (1ull << EV_LANES) - 1;
 constexpr int EV_RANK_SHIFT = 40;             // rec_ign bits 40..46: the record's rank in its (image, category) group
 constexpr int EV_INFO = 16;                   // int32 words of per-frame scratch
-constexpr long long EV_SKIP_US = 500000;
 constexpr unsigned long long EV_IDX_MASK = (1ull << 30) - 1;
 constexpr int EV_MAX_ANCHORS = 8192, EV_MAX_LABELS = 128;
 
@@ -65,16 +65,9 @@ enum { IN_VALID = 0, IN_NGT = 1, IN_NDT = 2, IN_NREC = 3, IN_IMG = 8, IN_GT_OFF 
 constexpr int REC_WORDS = SAST_DET_RECORD_BYTES / 4;   // a BBOX_DTYPE record as int32 words: 0-1 t, 2-5 x y w h, 6 class_id, 8 score
 constexpr int EV_MAX_WINDOW = 8192;
 
-__device__ __forceinline__ bool box_passes(float w, float h, float diag2, float side) {
-  const float d = w * w + h * h;   // fp32, one rounding each (box_filtering.py:34)
-  return d >= diag2 && w >= side && h >= side;
-}
+// box_passes / label_passes (filter_boxes) are box_rules.cuh's: the tracking evaluator applies the same filter
 
 __device__ __forceinline__ unsigned class_of(float v) { return (unsigned)(long long)v; }
-
-__device__ __forceinline__ bool label_passes(const float* r, float diag2, float side) {
-  return (long long)r[0] > EV_SKIP_US && box_passes(r[3], r[4], diag2, side);
-}
 
 // ascending on the result = ascending on the float (-0 == +0)
 __device__ __forceinline__ unsigned score_key(float s) {

@@ -12,6 +12,7 @@
 // orders like its bit pattern, so "best" is the maximum of the 64-bit key  IoU bits << 32 | ~detection << 8 | ~slot.
 // IoUs are recomputed each round (15 flops) rather than kept: LDS holds 32 bytes per detection and 40 per slot, whatever T * m is.
 // This file is built with -ffp-contract=off: the IoU is one fp32 rounding per operation, as the model's.
+#include "box_rules.cuh"
 #include "common.cuh"
 #include "kernels.h"
 
@@ -25,18 +26,8 @@ constexpr int TRK_WAVES = TRK_THREADS / 64;
 static_assert(SAST_TRACK_MAX_TRACKS <= TRK_THREADS, "a thread looks after at most one slot");
 constexpr int TRK_WORDS = SAST_DET_RECORD_BYTES / 8;   // a record is five 8-byte words; word 3 is class_id | track_id << 32
 
-// NaN when either side is NaN (fminf / fmaxf would drop it): a box with a NaN never passes the threshold
-__device__ __forceinline__ float nan_min(float a, float b) { return (a != a || b != b) ? __builtin_nanf("") : (b < a ? b : a); }
-__device__ __forceinline__ float nan_max(float a, float b) { return (a != a || b != b) ? __builtin_nanf("") : (b > a ? b : a); }
-
-__device__ __forceinline__ float track_iou(const float4 a, const float4 b) {   // (x, y, w, h) each
-  const float ax2 = a.x + a.z, ay2 = a.y + a.w, bx2 = b.x + b.z, by2 = b.y + b.w;
-  const float iw = nan_max(0.f, nan_min(ax2, bx2) - nan_max(a.x, b.x));
-  const float ih = nan_max(0.f, nan_min(ay2, by2) - nan_max(a.y, b.y));
-  const float inter = iw * ih;
-  const float uni = a.z * a.w + b.z * b.w - inter;
-  return uni > 0.f ? inter / uni : 0.f;
-}
+// track_iou (NaN when either box has a NaN, so such a box never passes the threshold) is box_rules.cuh's: the tracking evaluator
+// judges a pair by the same number
 
 __device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
 #pragma unroll

@@ -6,18 +6,28 @@ allocation and no synchronisation -- so it sits inside `OnlineDetector`'s captur
 IoU in a strict total order, births into the lowest free slots) is written out in include/sast_hip.h and stated sequentially in
 tests/tracker_model.py.  It is this project's own: parity with any external tracker is not claimed.
 
+`TrackingEvaluator` (csrc/k_trackeval.hip) reads the ids back: the CLEAR-MOT counts of tracked detections against the labelled tracks
+of whole recordings -- matches, misses, false positives, identity switches, fragmentations and the mostly tracked / partially tracked
+/ mostly lost tracks, with MOTA, MOTP, recall and precision derived on the host.  It takes the tensors of
+`PropheseeEvaluator.add_recordings`, so `DetectionLog.records` or what `track_recordings` filled go in as they are.  Its rule is written
+out in include/sast_hip.h ("tracking metrics") and stated sequentially in tests/tracking_eval_model.py.  Parity with py-motmetrics and
+TrackEval is not pinned by a test: neither is installed where this project is built.  IDF1 and HOTA need a global assignment over whole
+recordings and are not computed.
+
 There is no CPU path: CPU tensors raise the library's "no CPU fallback" error.
 """
 from __future__ import annotations
 
 import ctypes as C
 import math
-from typing import Optional, Tuple
+from typing import Dict, Optional, Tuple
 
+import numpy as np
 import torch
 
 from . import _frontend as F
 from . import _lib as L
+from .evaluation import PropheseeEvaluator
 from .functional import _need_gpu, _stream
 
 RECORD_BYTES = L.DET_RECORD_BYTES
@@ -125,3 +135,174 @@ class DetectionTracker:
 
     def errors(self) -> Tuple[int, int, int]:
         return F.counters(self.counters, 4)[:3]
+
+
+COUNT_KEYS = ("frames", "gt", "hyp", "matches", "fp", "fn", "idsw", "frag", "gt_tracks", "mt", "pt", "ml")     # the columns SAST_TE_FRAMES ..
+ERROR_KEYS = ("unsorted", "refused_labels", "refused_hyp", "refused_tracks", "untracked", "bad_class", "duplicate_labels", "duplicate_hyp")
+MAX_FRAME, MAX_GT_TRACKS = L.TRACKEVAL_MAX_FRAME, L.TRACKEVAL_MAX_GT_TRACKS
+assert len(COUNT_KEYS) == L.TRACKEVAL_COLS and len(ERROR_KEYS) == L.TRACKEVAL_DIAG and MAX_FRAME == MAX_TRACKS
+
+
+def _ratio(num: float, den: float) -> float:
+    return float(num) / float(den) if den else math.nan
+
+
+class TrackingEvaluator:
+    """te = TrackingEvaluator(dataset, downsample_by_2, iou_thre=0.5, time_tol_us=0, class_agnostic=False, max_gt_tracks=1024,
+                           max_labels_per_frame=64, max_hyp_per_frame=128)
+      dataset, downsample_by_2: `PropheseeEvaluator`'s -- its classes and its box filter.  A label and a hypothesis may pair when their
+      classes are equal (any classes with class_agnostic) and their IoU, the tracker's fp32 one, is >= iou_thre (in (0, 1]); a frame is
+      a unique label timestamp, its hypotheses the detection run nearest in time within time_tol_us (>= 0; the earlier run on a tie).
+      max_labels_per_frame, max_hyp_per_frame in 1 .. 128 and max_gt_tracks (distinct label ids of a recording) in 1 .. 65536: a
+      recording past one of them is refused whole.
+    te.add_recordings(gt, n_gt, dt, n_dt): the tensors of `PropheseeEvaluator.add_recordings` -- label records int32 [S, Gcap, 10] /
+      int64 [S] against detection records int32 [S, Dcap, 10] / int64 [S], both sorted by t; word 7, track_id, is the ground-truth track
+      of a label and the tracker's id of a detection (0: untracked, dropped).  Two launches, no synchronisation; after one eager call
+      (it allocates the track tables and the rows) it is capturable, and a replay scores the records then in the same tensors.
+    te.rows -> (int64 [S, K + 1, 12], fp64 [S, K + 1]): the counts (COUNT_KEYS) and the IoU sum of the LAST call per recording and class,
+      row K all classes together.
+    te.evaluate() -> dict of COUNT_KEYS as ints and MOTA, MOTP, recall, precision as floats (NaN where the denominator is 0), over
+      everything added since the last reset.  One synchronisation.  Raises ValueError when a recording was not sorted by t and
+      OverflowError when one was refused for a limit: those recordings added nothing.
+    te.per_class() -> {class name: such a dict}; te.merge(other) adds another evaluator's accumulator; te.reset() clears this one's;
+    te.errors() -> dict of ERROR_KEYS (synchronises): the recordings refused, and the records dropped as untracked (track_id 0), for a
+      class id past the dataset's, or as a second record of their track_id in a frame."""
+
+    def __init__(self, dataset: str, downsample_by_2: bool, iou_thre: float = 0.5, time_tol_us: int = 0, class_agnostic: bool = False,
+                 max_gt_tracks: int = 1024, max_labels_per_frame: int = 64, max_hyp_per_frame: int = 128):
+        task = PropheseeEvaluator(dataset, downsample_by_2)            # the classes and the filter thresholds are the evaluator's
+        self.dataset, self.downsample_by_2, self.classes = task.dataset, task.downsample_by_2, task.classes
+        self.min_box_diag, self.min_box_side = task.min_box_diag, task.min_box_side
+        self.iou_thre, self.time_tol_us, self.class_agnostic = float(iou_thre), int(time_tol_us), bool(class_agnostic)
+        self.max_gt_tracks, self.max_labels_per_frame, self.max_hyp_per_frame = int(max_gt_tracks), int(max_labels_per_frame), int(max_hyp_per_frame)
+        if not 0.0 < self.iou_thre <= 1.0:
+            raise ValueError(f"sast_amd.tracking: iou_thre must be in (0, 1], got {iou_thre}")
+        if self.time_tol_us < 0:
+            raise ValueError(f"sast_amd.tracking: time_tol_us must be >= 0, got {time_tol_us}")
+        if not 1 <= self.max_labels_per_frame <= MAX_FRAME or not 1 <= self.max_hyp_per_frame <= MAX_FRAME:
+            raise ValueError(f"sast_amd.tracking: max_labels_per_frame and max_hyp_per_frame must be in 1 .. {MAX_FRAME}, got "
+                             f"{max_labels_per_frame} and {max_hyp_per_frame}")
+        if not 1 <= self.max_gt_tracks <= MAX_GT_TRACKS:
+            raise ValueError(f"sast_amd.tracking: max_gt_tracks must be in 1 .. {MAX_GT_TRACKS}, got {max_gt_tracks}")
+        self._acc = self._rows = self._rows_iou = self._rows_diag = self._ws = None
+        self._last_S, self._retired = 0, []                    # buffers a call with more recordings replaced: a captured graph may hold them
+        self._args = L.SastTrackEvalArgs()
+
+    # the accumulator is ONE int64 tensor, so that evaluate() copies once: [K + 1, 12] counts, K + 1 fp64 IoU sums (as bits), 8 error words
+    def _views(self, acc: torch.Tensor):
+        K1, NC = len(self.classes) + 1, L.TRACKEVAL_COLS
+        return acc[:K1 * NC].view(K1, NC), acc[K1 * NC:K1 * NC + K1].view(torch.float64), acc[K1 * NC + K1:]
+
+    def _new_accumulator(self, dev: torch.device) -> None:
+        a = self._args
+        self._acc = torch.zeros((len(self.classes) + 1) * (L.TRACKEVAL_COLS + 1) + L.TRACKEVAL_DIAG, dtype=torch.int64, device=dev)
+        counts, iou, diag = self._views(self._acc)
+        a.acc, a.acc_iou, a.acc_diag = counts.data_ptr(), iou.data_ptr(), diag.data_ptr()
+        a.K, a.class_agnostic = len(self.classes), int(self.class_agnostic)
+        a.max_gt_tracks, a.max_labels_per_frame, a.max_hyp_per_frame = self.max_gt_tracks, self.max_labels_per_frame, self.max_hyp_per_frame
+        a.iou_thre, a.time_tol_us = self.iou_thre, self.time_tol_us
+        a.min_diag2, a.min_side = float(self.min_box_diag ** 2), float(self.min_box_side)
+
+    def _allocate(self, dev: torch.device, S: int) -> None:
+        F.not_capturing("tracking", "one un-captured call is needed before graph capture (it allocates the track tables and the rows)")
+        K1, NC, ND = len(self.classes) + 1, L.TRACKEVAL_COLS, L.TRACKEVAL_DIAG
+        a = self._args
+        if self._acc is None:
+            self._new_accumulator(dev)
+        a.ws_bytes = int(L.lib().sast_trackeval_ws_bytes(S, self.max_gt_tracks))
+        if a.ws_bytes == 0:
+            raise RuntimeError("sast_amd.tracking: the library refused the track table size")
+        self._retired.append((self._ws, self._rows, self._rows_iou, self._rows_diag))
+        self._ws = torch.empty(a.ws_bytes, dtype=torch.uint8, device=dev)
+        self._rows = torch.zeros(S, K1, NC, dtype=torch.int64, device=dev)
+        self._rows_iou = torch.zeros(S, K1, dtype=torch.float64, device=dev)
+        self._rows_diag = torch.zeros(S, ND, dtype=torch.int64, device=dev)
+        a.ws, a.rows, a.rows_iou, a.rows_diag = self._ws.data_ptr(), self._rows.data_ptr(), self._rows_iou.data_ptr(), self._rows_diag.data_ptr()
+
+    def add_recordings(self, gt: torch.Tensor, n_gt: torch.Tensor, dt: torch.Tensor, n_dt: torch.Tensor) -> None:
+        F.tensor_arg(gt, "gt", "tracking", (torch.int32,), ("S", "Gcap", RECORD_BYTES // 4), "(ten words per box record)", dtype_error=TypeError)
+        S, Gcap = int(gt.shape[0]), int(gt.shape[1])
+        F.tensor_arg(n_gt, "n_gt", "tracking", (torch.int64,), (S,), dtype_error=TypeError)
+        F.tensor_arg(dt, "dt", "tracking", (torch.int32,), (("S", S), "Dcap", RECORD_BYTES // 4), "(ten words per box record)", dtype_error=TypeError)
+        Dcap = int(dt.shape[1])
+        F.tensor_arg(n_dt, "n_dt", "tracking", (torch.int64,), (S,), dtype_error=TypeError)
+        if S > 65535 or S * max(Gcap, Dcap) > (1 << 31) - 257:
+            raise ValueError("sast_amd.tracking: need S <= 65535 recordings and S * Gcap, S * Dcap <= 2^31 - 257 records")
+        _need_gpu(gt, n_gt, dt, n_dt)
+        F.same_device("tracking", "gt, n_gt, dt and n_dt", gt, n_gt, dt, n_dt)
+        if self._acc is not None:
+            F.lives_on("the evaluator", self._acc.device, "the records", gt.device, "tracking")
+        if self._rows is None or self._rows.shape[0] < S:        # sized by the largest S so far; fewer recordings use the front
+            self._allocate(gt.device, S)
+        self._last_S = S
+        a = self._args
+        a.gt, a.n_gt, a.dt, a.n_dt = gt.data_ptr(), n_gt.data_ptr(), dt.data_ptr(), n_dt.data_ptr()
+        a.S, a.Gcap, a.Dcap = S, Gcap, Dcap
+        L.check(L.lib().sast_trackeval_add(C.byref(a), _stream()), "trackeval_add")
+
+    @property
+    def rows(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        if self._rows is None:
+            raise RuntimeError("sast_amd.tracking: rows follow an add_recordings")
+        return self._rows[:self._last_S], self._rows_iou[:self._last_S]
+
+    def reset(self) -> None:
+        """the accumulator and the error words back to zero: one launch, no synchronisation"""
+        if self._acc is not None:
+            L.check(L.lib().sast_trackeval_reset(C.byref(self._args), _stream()), "trackeval_reset")
+
+    def merge(self, other: "TrackingEvaluator") -> None:
+        """other's accumulator added to this one's, as if its recordings had been added here (the IoU sums: this one's plus other's)"""
+        if not isinstance(other, TrackingEvaluator):
+            raise TypeError("sast_amd.tracking: merge takes another TrackingEvaluator")
+        mine = (self.dataset, self.downsample_by_2, self.iou_thre, self.time_tol_us, self.class_agnostic)
+        if mine != (other.dataset, other.downsample_by_2, other.iou_thre, other.time_tol_us, other.class_agnostic):
+            raise ValueError("sast_amd.tracking: merge needs evaluators of the same dataset, downsample_by_2, iou_thre, time_tol_us and class_agnostic")
+        if other._acc is None:
+            return
+        if self._acc is None:
+            F.not_capturing("tracking", "one un-captured call is needed before graph capture (it allocates the accumulator)")
+            self._new_accumulator(other._acc.device)
+        F.lives_on("the evaluator", self._acc.device, "the other one", other._acc.device, "tracking")
+        for dst, src in zip(self._views(self._acc), other._views(other._acc)):
+            dst += src
+
+    def _numbers(self):
+        """(counts int64 [K + 1, 12], IoU sums fp64 [K + 1], error words int64 [8]) on the host: the one synchronisation"""
+        K1, NC = len(self.classes) + 1, L.TRACKEVAL_COLS
+        if self._acc is None:
+            return np.zeros((K1, NC), np.int64), np.zeros(K1, np.float64), np.zeros(L.TRACKEVAL_DIAG, np.int64)
+        host = self._acc.cpu().numpy()
+        return host[:K1 * NC].reshape(K1, NC), host[K1 * NC:K1 * NC + K1].view(np.float64), host[K1 * NC + K1:]
+
+    @staticmethod
+    def _metrics(counts, sum_iou: float) -> Dict[str, float]:
+        out = {k: int(v) for k, v in zip(COUNT_KEYS, counts)}
+        out["MOTA"] = 1.0 - _ratio(out["fn"] + out["fp"] + out["idsw"], out["gt"])
+        out["MOTP"] = _ratio(sum_iou, out["matches"])
+        out["recall"] = _ratio(out["matches"], out["gt"])
+        out["precision"] = _ratio(out["matches"], out["matches"] + out["fp"])
+        return out
+
+    def _checked(self):
+        counts, iou, diag = self._numbers()
+        if diag[L.TE_UNSORTED]:
+            raise ValueError(f"sast_amd.tracking: {int(diag[L.TE_UNSORTED])} recording(s) given to add_recordings were not sorted by t (labels "
+                             "or detections) and were not evaluated")
+        refused = {"max_labels_per_frame": int(diag[L.TE_REFUSED_LABELS]), "max_hyp_per_frame": int(diag[L.TE_REFUSED_HYP]),
+                   "max_gt_tracks": int(diag[L.TE_REFUSED_TRACKS])}
+        if any(refused.values()):
+            raise OverflowError("sast_amd.tracking: recordings did not fit the limits and were not evaluated -- "
+                                + ", ".join(f"{v} recording(s) refused for {k}={getattr(self, k)}" for k, v in refused.items() if v))
+        return counts, iou
+
+    def evaluate(self) -> Dict[str, float]:
+        counts, iou = self._checked()
+        return self._metrics(counts[-1], float(iou[-1]))
+
+    def per_class(self) -> Dict[str, Dict[str, float]]:
+        counts, iou = self._checked()
+        return {name: self._metrics(counts[k], float(iou[k])) for k, name in enumerate(self.classes)}
+
+    def errors(self) -> Dict[str, int]:
+        return {k: int(v) for k, v in zip(ERROR_KEYS, self._numbers()[2])}
